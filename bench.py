@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: forward_features, C=32, 64^3, N=4000 (BASELINE.json configs[1]) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1: either under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...`, or bare -
     bench.py then starts that launcher itself as a child process, before it touches torch or the GPU)
 
@@ -9,9 +9,12 @@ A step is one pass of the hot path over one batch of `--batch` synthetic cfg-2 m
 (one mvx_forward_features_batch call: prep kernel + voxelize kernel), inputs already resident in
 HBM, outputs left in HBM. value = molecules/s over all ranks (weak scaling: per-GPU batch fixed;
 molecules are independent, so ranks share nothing and there is no collective on the data path).
-Rank 0 prints ONE JSON line with `roofline` (voxelize kernel, HIP events on the launch stream,
-algorithmic bytes of SURVEY.md §8d) and `cpu_baseline` (numpy port of the reference algorithm timed
-on this host, N=1 only).
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and reports `value` and
+`ms_per_step`; --full adds what takes runs of its own: `roofline` (voxelize kernel, HIP events on the
+launch stream, algorithmic bytes of SURVEY.md §8d, HBM traffic from child rocprofv3 passes), the
+post-timing `parity_spot` against the CPU oracle and `cpu_baseline` (numpy port of the reference
+algorithm timed on this host, N=1 only).
+--dump-outputs DIR: rank 0 writes what its last timed step computed as DIR/*.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -109,6 +112,27 @@ def parity_spot(out, coords, feats, picks, radius=1.0, dimension=64, sigma=0.5):
     return "ok", worst_all
 
 
+DUMP_SAMPLE = 1 << 22  # voxels in the seeded sample over the whole batch (16 MB of float32)
+
+
+def dump_outputs(out, dump_dir: str) -> None:
+    """--dump-outputs: the grids the last timed step left in `out` (B, C, D, D, D) float32, in ~50 MB at the default
+    workload, so that two builds can be compared output for output on the same seeded inputs:
+      grid_first.npy    (C, D, D, D) float32, the whole grid of the batch's first molecule
+      grid_sample.npy   (2^22,) float32, the voxels at fixed flat positions of the batch (np.random.default_rng(0), sorted)
+      channel_sums.npy  (B, C) float64, the sum of every (molecule, channel) grid: every voxel of the batch counts"""
+    import torch
+
+    os.makedirs(dump_dir, exist_ok=True)
+    flat = out.reshape(-1)
+    idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=min(DUMP_SAMPLE, flat.numel())))
+    sample = flat[torch.from_numpy(idx).to(out.device)]
+    sums = torch.stack([out[b].to(torch.float64).sum(dim=(1, 2, 3)) for b in range(out.shape[0])])
+    np.save(os.path.join(dump_dir, "grid_first.npy"), out[0].cpu().numpy())
+    np.save(os.path.join(dump_dir, "grid_sample.npy"), sample.cpu().numpy())
+    np.save(os.path.join(dump_dir, "channel_sums.npy"), sums.cpu().numpy())
+
+
 def load_pmc_traffic(molecules_per_launch: int):
     """HBM bytes per voxelize launch from the committed rocprofv3 --pmc summary, if it matches this config."""
     path = os.path.join(ROOT, "profiles", "pmc_latest.json")
@@ -168,6 +192,52 @@ def measure_pmc_traffic(batch: int, budget_s: float = 90.0):
     return total, (f"measured in this run: child rocprofv3 --pmc WRITE_SIZE / --pmc FETCH_SIZE passes over bench.py --traffic-probe "
                    f"(same launch, {batch} molecules); WRITE_SIZE {got['WRITE_SIZE']:.4g} B + 2 x FETCH_SIZE {got['FETCH_SIZE']:.4g} B "
                    f"(gfx950 correction) per launch")
+
+
+def roofline(args, kernel_ms, profiled_ms_per_step: float, ms_per_step: float, coords, B: int, C_: int, kernel_name: str):
+    """--full: the `roofline` record of the line from pass 2's kernel durations, with the HBM traffic per launch."""
+    # the library cuts a step's batch into equal chunks of molecules only beyond 65535 (molecule, channel chunk)
+    # pairs; per launch = B / launches_per_step molecules x (4*C*D^3 + N*(24 + 4*C + 4))
+    lps = max(1, len(kernel_ms) // args.steps)
+    step_bytes = sum(4 * C_ * 64**3 + c.shape[0] * (24 + 4 * C_ + 4) for c in coords)
+    alg_bytes = step_bytes // lps
+    k = np.sort(np.asarray(kernel_ms, dtype=np.float64)) if kernel_ms else np.array([float("nan")])
+    k_ms = float(np.mean(k))
+    achieved = alg_bytes / (k_ms * 1e-3) / 1e9
+    traffic, traffic_source = None, None
+    if args.workload == "cfg2":
+        why = "--pmc-traffic off"
+        if args.pmc_traffic == "auto" and args.gpus == 1 and lps == 1:
+            traffic, why = measure_pmc_traffic(B)
+            traffic_source = why if traffic is not None else None
+        if traffic is None:
+            traffic = load_pmc_traffic(B // lps)
+            if traffic is not None:
+                traffic_source = ("profiles/pmc_latest.json (rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE passes of this command on the "
+                                  f"builder's box; replayed here, not measured in this run: {why})")
+    return {
+        "bound": "hbm",
+        "kernel": kernel_name,
+        "achieved": achieved,
+        "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBPS,
+        "step_frac": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+        "kernel_ms_avg": k_ms,
+        "kernel_ms_min": float(k[0]),
+        "kernel_ms_p50": float(k[len(k) // 2]),
+        "kernel_ms_max": float(k[-1]),
+        "kernel_ms_list": [round(float(x), 4) for x in kernel_ms],
+        "kernel_ms_source": f"pass 2: the same {args.steps} steps repeated right after the timed ones with HIP events "
+                            "around the voxelize launch on its stream (mvx_set_profiling); `value` is pass 1, no events",
+        "profiled_pass_ms_per_step": profiled_ms_per_step,
+        "kernel_launches_timed": len(kernel_ms),
+        "launches_per_step": lps,
+        "molecules_per_launch": B // lps,
+        "algorithmic_bytes_per_launch": alg_bytes,
+        "traffic": traffic,
+        "traffic_source": traffic_source,
+    }
 
 
 def traffic_probe(args):
@@ -355,12 +425,17 @@ def main():
                     help="cfg2 = the headline metric (default); cfg4 = 1024 ligands x world size, sharded by atom count")
     ap.add_argument("--batch", type=int, default=256, help="cfg-2 molecules per GPU per step (8.6 GB of grids at 256)")
     ap.add_argument("--ligands-per-gpu", type=int, default=128, help="cfg-4: the job holds this many ligands per rank")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the events pass (`roofline`), the "
+                         "HBM traffic (--pmc-traffic), the `parity_spot` check against the CPU oracle and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, ~50 MB")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (--full; 0 disables)")
     ap.add_argument("--overlap", type=int, default=0,
                     help="1: mvx_set_overlap - the pre-pass of step k+1 runs under the voxelize launch of step k (the inputs "
                          "are HBM-resident and complete before the loop, which is that mode's contract); 0: serial calls")
     ap.add_argument("--pmc-traffic", choices=("auto", "off"), default="auto",
-                    help="auto (N = 1, cfg2): measure roofline.traffic in this run with two child rocprofv3 --pmc passes "
+                    help="auto (--full, N = 1, cfg2): measure roofline.traffic in this run with two child rocprofv3 --pmc passes "
                          "(~30 s); if that is not possible, or off: the committed profiles/pmc_latest.json figure, labelled as replayed")
     ap.add_argument("--traffic-probe", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--prewarm", type=int, default=PREWARM_LAUNCHES,
@@ -368,6 +443,8 @@ def main():
     ap.add_argument("--rehearse", action="store_true",
                     help="plumbing only: launcher, rendezvous, barrier, MAX, one JSON line - no GPU work, not a measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` with no launcher around it: become the launcher. This happens before torch is imported
     # or the GPU is touched, and the ranks are children - nothing is re-executed.
@@ -446,21 +523,26 @@ def main():
     elapsed, rank_s, ranks_seen = ranks.max_and_gather(my_elapsed)
     rank_ms = [1e3 * s / args.steps for s in rank_s]
 
-    # Pass 2 - the same K steps again, back to back, with the library's HIP events around the voxelize launch (recorded on
-    # the launch stream): the kernel durations the roofline figure is built from. The events cost ~11 us of idle GPU per
-    # step, which is why this pass does not feed `value`.
-    vox.set_profiling(True)
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    vox.read_kernel_times_ms()  # discard
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    profiled_ms_per_step = 1e3 * (time.perf_counter() - t1) / args.steps
-    kernel_ms = vox.read_kernel_times_ms()
-    vox.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+
+    # Pass 2 (--full) - the same K steps again, back to back, with the library's HIP events around the voxelize launch
+    # (recorded on the launch stream): the kernel durations the roofline figure is built from. The events cost ~11 us of
+    # idle GPU per step, which is why this pass does not feed `value`.
+    kernel_ms = None
+    if args.full:
+        vox.set_profiling(True)
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        vox.read_kernel_times_ms()  # discard
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        profiled_ms_per_step = 1e3 * (time.perf_counter() - t1) / args.steps
+        kernel_ms = vox.read_kernel_times_ms()
+        vox.set_profiling(False)
 
     # who ran where, and how fast its kernel was: a scaling efficiency below par can then be pinned on a rank / a device
     props = torch.cuda.get_device_properties(dev_index)
@@ -474,33 +556,8 @@ def main():
     distinct = len({(r["uuid"], r["pci"], r["device_index"]) for r in per_rank})
     devices_shared = distinct < world
 
-    # post-timing spot check of the grids the timed steps left behind (rank 0, outside the timed region)
-    spot, spot_worst = None, None
     if rank == 0:
-        picks = sorted({0, B // 2, B - 1})
-        spot, spot_worst = parity_spot(out, coords, feats, picks)
-
-    if rank == 0:
-        # the library cuts a step's batch into equal chunks of molecules only beyond 65535 (molecule, channel chunk)
-        # pairs; per launch = B / launches_per_step molecules x (4*C*D^3 + N*(24 + 4*C + 4))
-        lps = max(1, len(kernel_ms) // args.steps)
-        step_bytes = sum(4 * C_ * 64**3 + c.shape[0] * (24 + 4 * C_ + 4) for c in coords)
-        alg_bytes = step_bytes // lps
-        k = np.sort(np.asarray(kernel_ms, dtype=np.float64)) if kernel_ms else np.array([float("nan")])
-        k_ms = float(np.mean(k))
-        achieved = alg_bytes / (k_ms * 1e-3) / 1e9
         ms_per_step = 1e3 * elapsed / args.steps
-        traffic, traffic_source = None, None
-        if args.workload == "cfg2":
-            why = "--pmc-traffic off"
-            if args.pmc_traffic == "auto" and args.gpus == 1 and lps == 1:
-                traffic, why = measure_pmc_traffic(B)
-                traffic_source = why if traffic is not None else None
-            if traffic is None:
-                traffic = load_pmc_traffic(B // lps)
-                if traffic is not None:
-                    traffic_source = ("profiles/pmc_latest.json (rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE passes of this command on the "
-                                      f"builder's box; replayed here, not measured in this run: {why})")
         res = {
             "metric": "molecules/sec + achieved HBM GB/s, forward_features C=32 64^3 N=4000" if args.workload == "cfg2"
                       else "molecules/sec, batch of ligands (cfg-4), forward_features C=16 64^3 N~50",
@@ -529,41 +586,20 @@ def main():
                 "parallelism": f"{args.gpus} independent ranks, molecules sharded, no collective on the data path",
                 "gpus_visible_per_rank": ndev,
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": kernel_name,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS,
-                "step_frac": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                "kernel_ms_avg": k_ms,
-                "kernel_ms_min": float(k[0]),
-                "kernel_ms_p50": float(k[len(k) // 2]),
-                "kernel_ms_max": float(k[-1]),
-                "kernel_ms_list": [round(float(x), 4) for x in kernel_ms],
-                "kernel_ms_source": f"pass 2: the same {args.steps} steps repeated right after the timed ones with HIP events "
-                                    "around the voxelize launch on its stream (mvx_set_profiling); `value` is pass 1, no events",
-                "profiled_pass_ms_per_step": profiled_ms_per_step,
-                "kernel_launches_timed": len(kernel_ms),
-                "launches_per_step": lps,
-                "molecules_per_launch": B // lps,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "traffic": traffic,
-                "traffic_source": traffic_source,
-            },
             "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms)},
             "per_rank": per_rank,
-            "parity_spot": spot,
-            "parity_spot_max_abs": spot_worst,
         }
+        if args.full:
+            res["roofline"] = roofline(args, kernel_ms, profiled_ms_per_step, ms_per_step, coords, B, C_, kernel_name)
+            # post-timing spot check of the grids the timed steps left behind (outside the timed region)
+            res["parity_spot"], res["parity_spot_max_abs"] = parity_spot(out, coords, feats, sorted({0, B // 2, B - 1}))
         if devices_shared:  # (a rehearsal of the N-rank code path on fewer GPUs: the aggregate is NOT an N-GPU figure)
             res["shared_device_molecules_per_s"] = job_molecules * args.steps / elapsed
             res["note"] = (f"{world} ranks on {distinct} device(s): ranks share GPUs, so `value` is withheld; "
                            "shared_device_molecules_per_s is what the shared device(s) delivered")
         if ranks.note:
             res["collective_note"] = ranks.note
-        if args.gpus == 1 and args.cpu_seconds > 0 and args.workload == "cfg2":
+        if args.full and args.gpus == 1 and args.cpu_seconds > 0 and args.workload == "cfg2":
             res["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
         print(json.dumps(res), flush=True)
     ranks.close()

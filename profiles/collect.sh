@@ -16,7 +16,7 @@ WARMUP=${WARMUP:-20}
 PREWARM=$(python3 -c "import bench; print(bench.PREWARM_LAUNCHES)")
 # explicit --steps / --warmup: the slices below are derived from these, never from bench.py's defaults.
 # Dispatch order of one run: PREWARM pre-warm + WARMUP warm-up + STEPS timed (pass 1, `value`) + 2 + STEPS (pass 2, events)
-BENCH="python3 bench.py --cpu-seconds 0 --pmc-traffic off --batch $BATCH --steps $STEPS --warmup $WARMUP"
+BENCH="python3 bench.py --full --cpu-seconds 0 --pmc-traffic off --batch $BATCH --steps $STEPS --warmup $WARMUP"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/kernel_trace" -- $BENCH > "$out/kernel_trace.log" 2>&1 || echo "kernel-trace failed"
 i=0
 for grp in "WRITE_SIZE GRBM_GUI_ACTIVE" "FETCH_SIZE" \
@@ -38,7 +38,7 @@ agg = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(out + "/pmc*/**/*counter_collection.csv", recursive=True):
     for row in csv.DictReader(open(f)):
         agg[row["Kernel_Name"]][row["Counter_Name"]].append(float(row["Counter_Value"]))
-lines = [f"# rocprofv3 --kernel-trace --stats (python3 bench.py --cpu-seconds 0 --batch {batch} --steps {steps} --warmup {warmup}: "
+lines = [f"# rocprofv3 --kernel-trace --stats (python3 bench.py --full --cpu-seconds 0 --batch {batch} --steps {steps} --warmup {warmup}: "
          f"{prewarm} pre-warm + {warmup} warm-up + {steps} timed steps (pass 1) + 2 + {steps} steps with events (pass 2))"]
 for r in sorted(stats, key=lambda r: -float(r["TotalDurationNs"])):
     lines.append(f'{r["Name"][:110]:110s} calls={r["Calls"]:>4s} avg_ns={float(r["AverageNs"]):12.1f} pct={r["Percentage"]}')

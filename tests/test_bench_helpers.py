@@ -28,6 +28,27 @@ def test_cpu_baseline_leg_reports_the_contract_fields():
     assert "numpy_port" in r["sample"] and r["openmp_port"]["value"] > 0
 
 
+def test_dump_outputs_writes_a_fixed_sample_of_the_grids(tmp_path):
+    """--dump-outputs: fixed names, float32 / float64 only, the same positions on every run, and at most 64 MB at the
+    default workload (256 cfg-2 molecules, C = 32, 64^3)."""
+    import torch
+
+    out = torch.rand((3, 2, 8, 8, 8), generator=torch.Generator().manual_seed(0))
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(out, str(d))
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert list(got) == ["channel_sums.npy", "grid_first.npy", "grid_sample.npy"]
+    for f, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / f))
+    assert got["grid_first.npy"].dtype == np.float32 and np.array_equal(got["grid_first.npy"], out[0].numpy())
+    idx = np.sort(np.random.default_rng(0).integers(0, out.numel(), size=out.numel()))
+    assert got["grid_sample.npy"].dtype == np.float32 and np.array_equal(got["grid_sample.npy"], out.numpy().reshape(-1)[idx])
+    sums = got["channel_sums.npy"]
+    assert sums.dtype == np.float64 and sums.shape == (3, 2)
+    assert np.allclose(sums, out.numpy().astype(np.float64).sum(axis=(2, 3, 4)), rtol=1e-12)
+    assert 32 * 64**3 * 4 + bench.DUMP_SAMPLE * 4 + 256 * 32 * 8 <= 64 * 2**20
+
+
 def test_committed_pmc_summary_matches_the_default_workload():
     d = json.load(open(os.path.join(ROOT, "profiles", "pmc_latest.json")))
     per_launch = d["molecules_per_launch"]
@@ -76,6 +97,11 @@ def test_bare_bench_launches_its_own_ranks(n):
 def test_bench_refuses_a_launcher_of_the_wrong_size():
     res = _bench(["--gpus", "2", "--rehearse"], {"WORLD_SIZE": "3", "RANK": "0"})
     assert res.returncode == 2 and "WORLD_SIZE=3" in res.stderr and res.stdout == ""
+
+
+def test_bench_refuses_zero_timed_steps():
+    res = _bench(["--steps", "0"])
+    assert res.returncode == 2 and "--steps" in res.stderr and res.stdout == ""
 
 
 def test_bare_bench_relays_the_exit_code_of_failed_ranks():

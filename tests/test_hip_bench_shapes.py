@@ -123,6 +123,45 @@ def test_bench_spot_check_helper():
     assert bench.parity_spot(out, coords, feats, picks=(0, 2))[0].startswith("FAIL")
 
 
+def test_plain_bench_run_and_its_dumped_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline fields only, `ms_per_step` over the
+    K timed steps, and the dumped grids are what the timed path computed (molecule 0 against the CPU oracle)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    res = subprocess.run([sys.executable, os.path.join(bench.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                          "--prewarm", "5", "--dump-outputs", str(tmp_path)], cwd=bench.ROOT, env=env, stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, timeout=600, text=True)
+    assert res.returncode == 0, res.stderr[-3000:]
+    lines = res.stdout.splitlines()
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["unit"] == "molecules/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 8 * 1e3 / rec["ms_per_step"]) <= 1e-9 * rec["value"]
+    assert not {"roofline", "parity_spot", "cpu_baseline"} & set(rec)
+    names = sorted(os.listdir(tmp_path))
+    assert names == ["channel_sums.npy", "grid_first.npy", "grid_sample.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in names) <= 64 * 2**20
+    first = np.load(tmp_path / "grid_first.npy")
+    _, coords, feats = bench.make_batch(1, 0)
+    from oracle import c_oracle
+
+    assert_north_star(first, c_oracle.voxelize(coords[0], feats[0], 1.0, dimension=64))
+    sums = np.load(tmp_path / "channel_sums.npy")
+    assert sums.dtype == np.float64 and sums.shape == (8, 32)
+    assert np.allclose(sums[0], first.astype(np.float64).sum(axis=(1, 2, 3)), rtol=1e-9)
+    sample = np.load(tmp_path / "grid_sample.npy")
+    idx = np.sort(np.random.default_rng(0).integers(0, 8 * 32 * 64**3, size=bench.DUMP_SAMPLE))
+    in_first = idx < first.size
+    assert sample.dtype == np.float32 and np.array_equal(sample[in_first], first.reshape(-1)[idx[in_first]])
+
+
 def test_pacing_guard_rows_are_recorded(record_property):
     """The store pacing of the slab kernels is tuned to launch shapes (mvx_tuning.h): this test records - it does not
     assert a rate, boxes of the pool differ by +-2 % and short runs sit on the clock ramp - the kernel's fraction of the

@@ -68,7 +68,7 @@ def test_two_ranks_voxelize_their_shards_of_cfg4(tmp_path):
 @pytest.mark.parametrize("workload,extra", [("cfg2", ["--batch", "8"]), ("cfg4", ["--ligands-per-gpu", "16"])])
 def test_bench_py_two_rank_code_path(workload, extra):
     res = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", workload,
-                        "--cpu-seconds", "0"] + extra)
+                        "--full", "--cpu-seconds", "0"] + extra)
     assert res.returncode == 0, res.stdout[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, "rank 0 prints exactly one JSON line"
@@ -110,7 +110,7 @@ def test_bare_bench_py_starts_its_own_ranks_on_the_hip_path(n, extra):
     """The driver's N-GPU command without the launcher (`python3 bench.py --gpus N ...`): one JSON line, every rank
     counted, parity spot check green. On this 1-GPU box the ranks share the device (at most 4 here: the pool allows six
     processes on a card) and rendezvous over gloo; the 8-rank form is rehearsed without GPU work in test_bench_helpers.py."""
-    res = _bare_bench(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--prewarm", "5", "--cpu-seconds", "0"] + extra)
+    res = _bare_bench(["--gpus", str(n), "--steps", "2", "--warmup", "1", "--prewarm", "5", "--full", "--cpu-seconds", "0"] + extra)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
     lines = res.stdout.splitlines()
     assert len(lines) == 1 and lines[0].startswith("{"), res.stdout[-2000:]
@@ -131,7 +131,7 @@ def test_bench_py_rccl_branch_with_one_rank():
     env["MVX_BENCH_COLLECTIVES"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--cpu-seconds", "0", "--pmc-traffic", "off"]
+           "--batch", "8", "--full", "--cpu-seconds", "0", "--pmc-traffic", "off"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600, text=True)
     assert res.returncode == 0, res.stdout[-3000:]
     rec = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][0])
@@ -141,7 +141,7 @@ def test_bench_py_rccl_branch_with_one_rank():
 def test_bench_py_measures_its_hbm_traffic_in_the_run():
     """roofline.traffic of the N = 1 line: two child `rocprofv3 --pmc` passes (WRITE_SIZE, FETCH_SIZE) over the same
     launch, in this run - not a figure replayed from profiles/."""
-    res = _bare_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--cpu-seconds", "0"])
+    res = _bare_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--full", "--cpu-seconds", "0"])
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]
     rec = json.loads(res.stdout.splitlines()[-1])
     rf = rec["roofline"]
