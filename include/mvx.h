@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVX_VERSION 140 /* 0.1.4: mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
+#define MVX_VERSION 140 /* 0.1.4: mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
 
 typedef enum mvx_status {
     MVX_OK = 0,
@@ -74,6 +74,16 @@ enum mvx_xform_flags {
 };
 
 /*
+ * Element type of the grid (mvx_config.grid_type). MVX_GRID_BF16 (precision 32 only): the arithmetic is the float32
+ * handle's, bit for bit; every float32 value is rounded to bfloat16 (to nearest, ties to even; subnormals kept, a NaN stays
+ * a NaN) as the kernels store it - the grid a float32 handle writes, converted by torch's .to(torch.bfloat16). `out` then
+ * points to bfloat16 elements (2 bytes, 2-byte aligned; host outputs are staged with 2-byte elements); features and radii
+ * stay float32. Rows of whole groups of four voxels (D % 4 == 0) on an 8-byte aligned grid get 8-byte stores, anything else
+ * is written run by run (16-byte stores inside each run, 2-byte stores at its ends).
+ */
+enum mvx_grid_type { MVX_GRID_REAL = 0, MVX_GRID_BF16 = 1 };
+
+/*
  * Geometry + density of one voxelizer. Replaces the constructor state of
  * BaseVoxelizer.__init__ (base/voxelizer.py:15-38) and numpy Voxelizer.__init__/_setup_block
  * (numpy/voxelizer.py:22-58).
@@ -89,7 +99,7 @@ typedef struct mvx_config {
     int32_t precision; /* 32 (or 0) | 64: the `precision` argument of Voxelizer.__init__ (numpy/voxelizer.py:28,33-34):
                           element type of features, radii and the grid, and the type distances, densities and sums
                           are evaluated in */
-    int32_t reserved;  /* 0 */
+    int32_t grid_type; /* enum mvx_grid_type: element type of the grid (0 = the precision's real type) */
 } mvx_config;
 
 /* float for a precision-32 handle, double for a precision-64 handle (the reference's `self.fp`). */
@@ -259,6 +269,10 @@ typedef struct mvx_plan {
     int32_t reserved;
 } mvx_plan;
 int mvx_plan_call(const mvx_plan_query *query, mvx_plan *plan);
+/* The plan of a call on a grid of the given mvx_grid_type; mvx_plan_call is grid_type 0. MVX_GRID_BF16: `out_aligned16`
+ * stands for the grid's 8-byte alignment (one store of four bfloat16 voxels), and the plan is the float32 plan of that query.
+ * MVX_ERR_INVALID for an unknown grid_type, and for MVX_GRID_BF16 with precision 64. */
+int mvx_plan_call_grid(const mvx_plan_query *q, int32_t grid_type, mvx_plan *p);
 #ifdef __cplusplus
 }
 #endif

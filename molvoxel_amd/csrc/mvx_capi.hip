@@ -354,7 +354,9 @@ int run(mvx_handle *h, const RunArgs &r) {
     const int D = g.D;
     const bool f64 = (h->cfg.precision == 64);
     const size_t esz = f64 ? sizeof(double) : sizeof(float); // element size of features, radii and the grid
-    const size_t out_bytes = (size_t)r.B * r.C * D * D * D * esz;
+    const bool bf16 = h->cfg.grid_type == MVX_GRID_BF16;      // ... except for a bfloat16 grid (2-byte elements)
+    if (bf16 && (reinterpret_cast<uintptr_t>(r.out) & 1u)) return fail(MVX_ERR_INVALID, "a bfloat16 grid must be 2-byte aligned");
+    const size_t out_bytes = (size_t)r.B * r.C * D * D * D * (bf16 ? sizeof(uint16_t) : esz);
     void *d_out = r.out;
     if (r.out_kind == MVX_HOST) {
         if ((rc = ensure(h->out_stage, out_bytes))) return rc;
@@ -370,7 +372,8 @@ int run(mvx_handle *h, const RunArgs &r) {
     q.radii_type = r.radii_type;
     q.B = r.B;
     q.C = r.C;
-    q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & 15u) == 0 ? 1 : 0;
+    // (a bfloat16 grid's vector store is 8 bytes: mvx_plan_call_grid)
+    q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & (bf16 ? 7u : 15u)) == 0 ? 1 : 0;
     q.total_atoms = total;
     q.max_atoms = max_atoms;
     const mvx_plan plan = plan_call(q, h->knobs);
@@ -515,6 +518,7 @@ int run(mvx_handle *h, const RunArgs &r) {
     va.Tc = d_Tc;
     va.kc = d_kc;
     va.out = d_out;
+    va.bf16 = bf16 ? 1 : 0;
     va.narrow_sub = h->narrow_sub;
     va.p.res = g.res;
     va.p.half = g.half;
@@ -572,7 +576,7 @@ int run(mvx_handle *h, const RunArgs &r) {
                 if (r.in_kind == MVX_HOST) resolve_host_centers(&da.pa.xf_one, 1);
             }
         }
-        if ((rc = timed_launch(h, s, [&] { return launch_voxelize_direct(da, va.p, max_atoms, static_cast<float *>(d_out), ct, gauss, lr_blocks, s); })))
+        if ((rc = timed_launch(h, s, [&] { return launch_voxelize_direct(da, va.p, max_atoms, d_out, bf16, ct, gauss, lr_blocks, s); })))
             return rc;
         if (in.slot) {
             HIP_TRY(hipEventRecord(in.slot->done, s));
@@ -690,6 +694,9 @@ int mvx_create(const mvx_config *cfg, mvx_handle **out) {
     if (cfg->density == MVX_GAUSSIAN && !(cfg->sigma > 0.0)) return fail(MVX_ERR_INVALID, "sigma must be > 0");
     if (cfg->precision != 0 && cfg->precision != 32 && cfg->precision != 64)
         return fail(MVX_ERR_INVALID, "precision must be 32 or 64"); // numpy/voxelizer.py:33
+    if (cfg->grid_type != MVX_GRID_REAL && cfg->grid_type != MVX_GRID_BF16) return fail(MVX_ERR_INVALID, "unknown grid_type");
+    if (cfg->grid_type == MVX_GRID_BF16 && cfg->precision == 64)
+        return fail(MVX_ERR_INVALID, "a bfloat16 grid needs precision 32 (float32 arithmetic, rounded as it is stored)");
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0) {

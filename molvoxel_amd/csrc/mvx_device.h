@@ -21,6 +21,7 @@
 
 #include <math.h>
 #include <type_traits>
+#include <hip/hip_bf16.h>
 #include <hip/hip_ext.h>
 
 // cdist-order arithmetic must not be fused, whatever flags the TU is built with.
@@ -457,6 +458,20 @@ __device__ __forceinline__ void store_f4(float *dst, const float4 v) {
     __builtin_nontemporal_store(x, reinterpret_cast<f4 *>(dst));
 }
 
+// Grid element type of the float32 kernels: float, or __bf16 for bfloat16 grids (mvx_config.grid_type = MVX_GRID_BF16). The
+// accumulators, the sums and the write-out tile stay float32; a value is rounded to bfloat16 (to nearest, ties to even,
+// subnormals kept, NaN stays NaN: torch's own conversion) by the plain conversion as it is stored - v_cvt_pk_bf16_f32,
+// two values per instruction. One tile slot of four voxels goes out as one store: 16 B (float), 8 B (bfloat16: the same
+// slot map, form (a) of DESIGN.md "bfloat16 grids"), non-temporal like store_f4.
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_q(float *dst, const float4 v) { store_f4(dst, v); }
+__device__ __forceinline__ void store_q(__bf16 *dst, const float4 v) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    const bf16x4 y = __builtin_convertvector(((f4){v.x, v.y, v.z, v.w}), bf16x4);
+    __builtin_nontemporal_store(__builtin_bit_cast(u2, y), reinterpret_cast<u2 *>(dst));
+}
+
 // floats per tile row: SUBZ*NW plus a pad that keeps ds_write_b32 conflict-free for the lane -> (row, column) map
 __host__ __device__ __forceinline__ int row_stride_floats(int NW) { return SUBZ * NW + 8; }
 // words per staged row: 16 of record + the channel weights, padded to an ODD number of 16-B quads - the row filter reads one
@@ -550,12 +565,16 @@ __device__ __forceinline__ void accumulate_row(float2v (&acc)[(CT + 1) / 2], con
 // (C = 8) 1.01 -> 1.55 (4-byte stores at a 16-byte lane stride before). One 4-byte store per lane over consecutive floats
 // (no alignment cases at all) is slower than either: 1.6-2.0.
 struct RunLayout {
-    int SC, SX, SY; // tile floats between channels, x planes, rows
+    int SC, SX, SY; // tile elements between channels, x planes, rows
     int joined;     // the slab spans whole rows: the rows of one (channel, x) follow each other in the grid (SY = D)
-    int run_len;    // floats per run
+    int run_len;    // elements per run
     int ny, nx;     // rows / planes of the slab inside the grid
-    int seg;        // floats of a row inside the slab
+    int seg;        // elements of a row inside the slab
 };
+// G: grid elements per 16-byte group (4 float, 8 bfloat16); the strides are congruent mod G to the grid's. A bfloat16 tile
+// (SY <= 8 NW + 7, SX <= 4 SY + 7, SC <= 2 SX + 14 elements of 2 B) is smaller than the float tile of the same slab
+// (RPC * RS floats per channel): it fits the allocation of the float32 kernel.
+template <int G = 4>
 __device__ __forceinline__ RunLayout run_layout(int NW, int x0, int y0, int z0, const VoxParams &P) {
     RunLayout R;
     const int D = P.D;
@@ -565,26 +584,33 @@ __device__ __forceinline__ RunLayout run_layout(int NW, int x0, int y0, int z0, 
     R.nx = min(SUBX, D - x0);
     R.seg = R.joined ? D : min(SUBZ * NW, D - z0);
     R.run_len = R.joined ? R.ny * D : R.seg;
-    R.SY = R.joined ? D : SUBZ * NW + ((D - SUBZ * NW) & 3);
-    R.SX = SUBY * R.SY + ((int)(D2 - (unsigned)(SUBY * R.SY)) & 3);
-    R.SC = ((SUBX * R.SX + 3) & ~3) + (int)((D2 * (unsigned)D) & 3u);
+    R.SY = R.joined ? D : SUBZ * NW + ((D - SUBZ * NW) & (G - 1));
+    R.SX = SUBY * R.SY + ((int)(D2 - (unsigned)(SUBY * R.SY)) & (G - 1));
+    R.SC = ((SUBX * R.SX + (G - 1)) & ~(G - 1)) + (int)((D2 * (unsigned)D) & (unsigned)(G - 1));
     return R;
 }
-// offset of the tile's first run: congruent mod 4 to the 4-byte index of the run's first float in memory
-__device__ __forceinline__ int run_tile_origin(size_t S0, const float *out) {
-    return (int)(((unsigned)S0 + (unsigned)(reinterpret_cast<uintptr_t>(out) >> 2)) & 3u);
+// offset of the tile's first run: congruent mod G to the element index of the run's first element in memory
+template <typename OT>
+__device__ __forceinline__ int run_tile_origin(size_t S0, const OT *out) {
+    constexpr int G = 16 / sizeof(OT), ESH = sizeof(OT) == 4 ? 2 : 1;
+    return (int)(((unsigned)S0 + (unsigned)(reinterpret_cast<uintptr_t>(out) >> ESH)) & (unsigned)(G - 1));
 }
 
-// `nch` tile channels starting at grid channel ch0 (S0: the first run's first float, floats from `out`); ZERO: zeros, no tile
-template <bool ZERO>
-__device__ __forceinline__ void store_runs(const float *tile, const RunLayout &R, int L0, int nch, int ch0, size_t S0, int tid,
-                                           int nthr, float *out, const VoxParams &P) {
+// `nch` tile channels starting at grid channel ch0 (S0: the first run's first element, elements from `out`); ZERO: zeros, no
+// tile. OT = __bf16: groups of 8 elements, up to 7 + 7 edge elements per run as 2-byte stores, a bfloat16 tile.
+template <bool ZERO, typename OT = float>
+__device__ __forceinline__ void store_runs(const OT *tile, const RunLayout &R, int L0, int nch, int ch0, size_t S0, int tid,
+                                           int nthr, OT *out, const VoxParams &P) {
     typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    typedef typename std::conditional<std::is_same<OT, float>::value, f4, u4>::type V16; // one 16-byte group
+    constexpr int G = 16 / sizeof(OT), GSH = G == 4 ? 2 : 3; // elements per group
+    constexpr int NE = G - 1, ESH = GSH + 1;                  // edge elements at most at either end; 2 G edge slots per run
     const int D = P.D, run_len = R.run_len;
     const int ry_sh = R.joined ? 0 : SUBY_SH; // runs per (channel, x): 1 | SUBY (rows beyond the grid are skipped)
     const int nruns = (min(nch, P.C - ch0) << SUBX_SH) << ry_sh;
     const size_t D2 = (size_t)D * D, D3 = D2 * D;
-    // run r = ((c * SUBX + x) << ry_sh) + yy: its first float in the grid and in the tile
+    // run r = ((c * SUBX + x) << ry_sh) + yy: its first element in the grid and in the tile
     auto locate = [&](int r, size_t &S, int &lbase) -> bool {
         const int yy = r & ((1 << ry_sh) - 1), cx = r >> ry_sh, x = cx & (SUBX - 1), c = cx >> SUBX_SH;
         S = S0 + (size_t)(unsigned)c * D3 + (size_t)((unsigned)x * (unsigned)D2 + (unsigned)(yy * D));
@@ -592,7 +618,7 @@ __device__ __forceinline__ void store_runs(const float *tile, const RunLayout &R
         return x < R.nx && yy < R.ny;
     };
     // 16-byte slots: thread -> (slot j of run rfirst, rfirst + rstep, ...), slots per run rounded up to a power of two
-    const int QS = run_len >> 2; // a run has QS or QS - 1 whole aligned quads
+    const int QS = run_len >> GSH; // a run has QS or QS - 1 whole aligned groups
     if (QS) {
         const int qsh = 32 - __builtin_clz((unsigned)QS - 1u | 1u) - (QS == 1 ? 1 : 0); // ceil(log2(QS)); 2^qsh <= nthr
         const int j = tid & ((1 << qsh) - 1), rstep = nthr >> qsh;
@@ -600,26 +626,26 @@ __device__ __forceinline__ void store_runs(const float *tile, const RunLayout &R
             size_t S;
             int lbase;
             const bool ok = locate(r, S, lbase);
-            const int i0 = ((4 - lbase) & 3) + 4 * j; // (floats before the run's first aligned one) + 4 j
-            if (ok && i0 + 4 <= run_len) {
-                f4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (!ZERO) v = *reinterpret_cast<const f4 *>(tile + lbase + i0);
-                *reinterpret_cast<f4 *>(out + S + i0) = v;
+            const int i0 = ((G - lbase) & (G - 1)) + G * j; // (elements before the run's first aligned one) + G j
+            if (ok && i0 + G <= run_len) {
+                V16 v = {0, 0, 0, 0};
+                if (!ZERO) v = *reinterpret_cast<const V16 *>(tile + lbase + i0);
+                *reinterpret_cast<V16 *>(out + S + i0) = v;
             }
         }
     }
-    // edge floats: thread e takes float k = e % 8 (< 6) of run e / 8 - k < 3: before the first aligned float; else after the
-    // last whole quad
-    for (int e = tid; e < nruns * 8; e += nthr) {
-        const int r = e >> 3, k = e & 7;
+    // edge elements: thread e takes element k = e % 2G (< 2 NE) of run e / 2G - k < NE: before the first aligned element;
+    // else after the last whole group
+    for (int e = tid; e < nruns * 2 * G; e += nthr) {
+        const int r = e >> ESH, k = e & (2 * G - 1);
         size_t S;
         int lbase;
         const bool ok = locate(r, S, lbase);
-        const int a = min((4 - lbase) & 3, run_len);
-        const int nfull = (run_len - a) >> 2;
-        const int i = k < 3 ? k : a + 4 * nfull + (k - 3);
-        if (ok && k < 6 && (k < 3 ? k < a : i < run_len)) {
-            const float v = ZERO ? 0.0f : tile[lbase + i];
+        const int a = min((G - lbase) & (G - 1), run_len);
+        const int nfull = (run_len - a) >> GSH;
+        const int i = k < NE ? k : a + G * nfull + (k - NE);
+        if (ok && k < 2 * NE && (k < NE ? k < a : i < run_len)) {
+            const OT v = ZERO ? (OT)0.0f : tile[lbase + i];
             out[S + i] = v;
         }
     }
@@ -629,11 +655,12 @@ __device__ __forceinline__ void store_runs(const float *tile, const RunLayout &R
 // may still hold candidate rows) and ends without one.
 // RUNS: the kernel also serves grids whose rows are not whole 16-byte quads (store_runs). Compiled into the per-lane-range
 // kernels and the run-wise kernels (voxelize_runs_kernel, voxelize_pair_runs_kernel) only: the aligned-grid kernels keep their
-// register budget.
-template <int CT, bool RUNS, int CRMAX = CR_F32>
+// register budget. OT: grid element type (store_q); a bfloat16 grid's run-wise path keeps a bfloat16 tile (store_runs).
+template <int CT, bool RUNS, int CRMAX = CR_F32, typename OT = float>
 __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], bool any, float *tile, int tid, int lane,
-                                           int wave, int NW, int b, int cbase, int x0, int y0, int z0, float *out,
+                                           int wave, int NW, int b, int cbase, int x0, int y0, int z0, OT *out,
                                            const VoxParams &P) {
+    constexpr int G = 16 / sizeof(OT); // elements per 16-byte group (run-wise path)
     constexpr int CR = CT < CRMAX ? CT : CRMAX; // channels per write-out round
     constexpr int NROUND = CT / CR;
     const int D = P.D;
@@ -648,29 +675,29 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
     const int zq = z0 + 4 * q;
     const int sxx = (rfirst >> SUBY_SH) & (SUBX - 1), syy = rfirst & (SUBY - 1), cfirst = rfirst / RPC;
     const bool vox_ok = (x0 + sxx < D) && (y0 + syy < D) && (zq < D);
-    float *dst0 = out + ((size_t)b * P.C + cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
+    OT *dst0 = out + ((size_t)b * P.C + cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
     if (!any) {
         // Pacing: a workgroup that has nothing to compute would fire its 64 KB of stores the moment it starts; holding
         // them back ~1.7 us (4096 cycles) lets the store streams of the resident workgroups interleave: ligand batches
         // 6.2 -> 6.7 TB/s (sleep 16 / 32 / 48 / 64 / 80 / 100: +0.9 / 2.8 / 4.7 / 7.5 / 7.0 / 3.7 %).
         // (only when several rounds of workgroups follow each other; a small launch would just start later)
-        if (P.pace) __builtin_amdgcn_s_sleep(EMPTY_HOLD);
+        if (P.pace) __builtin_amdgcn_s_sleep(pacing<OT>::empty_hold);
         if (RUNS && !P.vec_store) {
-            const RunLayout R = run_layout(NW, x0, y0, z0, P);
+            const RunLayout R = run_layout<G>(NW, x0, y0, z0, P);
             const size_t S0 = (((size_t)b * P.C + cbase) * D + x0) * D2 + (size_t)y0 * D + z0;
-            store_runs<true>(nullptr, R, run_tile_origin(S0, out), CT, cbase, S0, tid, NW * 64, out, P);
+            store_runs<true, OT>(nullptr, R, run_tile_origin(S0, out), CT, cbase, S0, tid, NW * 64, out, P);
             return;
         }
         if (vox_ok) {
 #pragma unroll
             for (int p = 0; p < (CT + 3) / 4; ++p) {
                 const int c = cfirst + 4 * p;
-                if (c < CT && cbase + c < P.C) store_f4(dst0 + (size_t)(4 * p) * D3, make_float4(0.f, 0.f, 0.f, 0.f));
+                if (c < CT && cbase + c < P.C) store_q(dst0 + (size_t)(4 * p) * D3, make_float4(0.f, 0.f, 0.f, 0.f));
                 // ... and the fill itself goes out in pieces of two store instructions (16 KB per workgroup) ~1300 cycles
                 // apart, like the write-out rounds of OpsMx32::write: ligand batches 6.55 -> 6.83 TB/s (0.85 of peak;
                 // 512 / 1024 / 1536 / 2048 cycles: +2 / +3.5 / +4.3 / +3.6 %; with a first wait of 2048 instead of 4096
                 // cycles: -1 / +1 %)
-                if (P.pace && (p & 1) && p + 1 < (CT + 3) / 4) __builtin_amdgcn_s_sleep(EMPTY_SPLIT);
+                if (P.pace && (p & 1) && p + 1 < (CT + 3) / 4) __builtin_amdgcn_s_sleep(pacing<OT>::empty_split);
             }
         }
         return;
@@ -679,7 +706,8 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
     const int col = SUBZ * wave + lz;
     const int rxy = lx * SUBY + ly;
     if (RUNS && !P.vec_store) { // rows that are not whole 16-byte quads: the tile holds the slab's runs as they lie in memory (store_runs)
-        const RunLayout R = run_layout(NW, x0, y0, z0, P);
+        const RunLayout R = run_layout<G>(NW, x0, y0, z0, P);
+        OT *rtile = reinterpret_cast<OT *>(tile);
         const size_t S0 = (((size_t)b * P.C + cbase) * D + x0) * D2 + (size_t)y0 * D + z0;
         const bool zok = !R.joined || col < D; // (packed rows: a voxel beyond the row would land in the next row)
         const int mine = lx * R.SX + ly * R.SY + col;
@@ -692,11 +720,11 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
 #pragma unroll
                 for (int c = 0; c < CR; ++c) {
                     const int cg = rd * CR + c;
-                    tile[L0 + c * R.SC + mine] = (cg & 1) ? acc[cg / 2].y : acc[cg / 2].x;
+                    rtile[L0 + c * R.SC + mine] = (OT)((cg & 1) ? acc[cg / 2].y : acc[cg / 2].x);
                 }
             }
             __syncthreads();
-            store_runs<false>(tile, R, L0, CR, cbase + rd * CR, S0r, tid, NW * 64, out, P);
+            store_runs<false, OT>(rtile, R, L0, CR, cbase + rd * CR, S0r, tid, NW * 64, out, P);
         }
         return;
     }
@@ -718,7 +746,7 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
                 const int c = cfirst + 4 * p; // channel inside the round
                 if (c < CR && cbase + rd * CR + c < P.C) {
                     const float4 v = *reinterpret_cast<const float4 *>(tile + (rfirst + 4 * RPC * p) * RS + 4 * q);
-                    store_f4(dst0 + (size_t)(rd * CR + 4 * p) * D3, v);
+                    store_q(dst0 + (size_t)(rd * CR + 4 * p) * D3, v);
                 }
             }
         }
@@ -752,7 +780,7 @@ __device__ __forceinline__ LaneCtx make_lane_ctx(int lane, int wave, int x0, int
 // the per-candidate update and the write-out. OpsF32: one voxel per lane, CT float32 channels per lane on the vector ALU
 // (chunks of fewer than 32 channels, per-lane-range variants); OpsMx32 / OpsPair (mvx_ops32.h): 32 channels on the
 // matrix cores / candidate pairs on the vector ALU; OpsF64 / OpsMx64 (mvx_f64.hip): float64 grids.
-template <int CT_, bool GAUSS, bool LANE_RANGE>
+template <int CT_, bool GAUSS, bool LANE_RANGE, typename OT = float>
 struct OpsF32 {
     static constexpr bool RUNS = LANE_RANGE; // carries the run-wise write-out (store_runs)
     static constexpr int CT = CT_;
@@ -786,8 +814,8 @@ struct OpsF32 {
     }
     static __device__ __forceinline__ void write(const Acc &acc, bool any, unsigned *un, int tid, int lane, int wave, int NW,
                                                  int b, const LaneCtx &L, int x0, int y0, int z0, void *out, const VoxParams &P) {
-        write_slab<CT, LANE_RANGE>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0,
-                       static_cast<float *>(out), P);
+        write_slab<CT, LANE_RANGE, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0,
+                                               z0, static_cast<OT *>(out), P);
     }
 };
 

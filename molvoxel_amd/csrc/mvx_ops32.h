@@ -30,7 +30,7 @@ namespace mvx {
 // lanes 32-63, so every lane writes 4 channels x 2 planes per round) and its read-back / store code unchanged.
 typedef float f16v __attribute__((ext_vector_type(16)));
 
-template <bool GAUSS, bool LANE_RANGE, bool GROUPED_ = false, bool RUNS_ = LANE_RANGE>
+template <bool GAUSS, bool LANE_RANGE, bool GROUPED_ = false, bool RUNS_ = LANE_RANGE, typename OT = float>
 struct OpsMx32 {
     static constexpr int CT = 32;
     static constexpr bool RUNS = RUNS_; // carries the run-wise write-out (store_runs)
@@ -128,10 +128,10 @@ struct OpsMx32 {
     }
     static __device__ __forceinline__ void write(const Acc &acc, int any, unsigned *un, int tid, int lane, int wave, int NW,
                                                  int b, const LaneCtx &L, int x0, int y0, int z0, void *out_, const VoxParams &P) {
-        float *out = static_cast<float *>(out_);
+        OT *out = static_cast<OT *>(out_);
         if (!any) { // zero fill without the LDS round trip: the one-voxel-per-lane code (no accumulator is read)
             float2v zero[16];
-            write_slab<32, RUNS>(zero, false, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0, out, P);
+            write_slab<32, RUNS, CR_F32, OT>(zero, false, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0, out, P);
             return;
         }
         float *tile = reinterpret_cast<float *>(un);
@@ -145,7 +145,7 @@ struct OpsMx32 {
         const int q = tid - rfirst * F4, zq = z0 + 4 * q;
         const int sxx = (rfirst >> SUBY_SH) & (SUBX - 1), syy = rfirst & (SUBY - 1), cfirst = rfirst / RPC;
         const bool vox_ok = (x0 + sxx < D) && (y0 + syy < D) && (zq < D);
-        float *dst0 = out + ((size_t)b * P.C + L.cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
+        OT *dst0 = out + ((size_t)b * P.C + L.cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
         // this lane's voxel column in the tile, and the first of its four channels of a round
         const int lz = lane & (SUBZ - 1), ly = (lane >> SUBZ_SH) & (SUBY - 1), h = lane >> 5;
         float *mine = tile + (4 * h * RPC + ly) * RS + SUBZ * wave + lz; // + (c * RPC + x * SUBY) * RS
@@ -166,7 +166,7 @@ struct OpsMx32 {
                     const int c = cfirst + 4 * p; // channel inside the round
                     if (c < CR && L.cbase + rd * CR + c < P.C) {
                         const float4 v = *reinterpret_cast<const float4 *>(tile + (rfirst + 4 * RPC * p) * RS + 4 * q);
-                        store_f4(dst0 + (size_t)(rd * CR + 4 * p) * D3, v);
+                        store_q(dst0 + (size_t)(rd * CR + 4 * p) * D3, v);
                     }
                 }
             }
@@ -178,10 +178,11 @@ struct OpsMx32 {
             // stores' acknowledgement instead (s_waitcnt vmcnt(0)) gives +4 % where the sleep gives +4.7 %; a sleep after
             // every store instruction, or waves starting their first round apart, the same or less.
             if (rd < 3 && any == 2)
-                for (int i = 0; i < NW; i += 2) __builtin_amdgcn_s_sleep(ROUND_SLEEP_STEP);
+                for (int i = 0; i < NW; i += 2) __builtin_amdgcn_s_sleep(pacing<OT>::round_sleep_step);
         };
         if (RUNS && !P.vec_store) { // rows that are not whole 16-byte quads: the tile holds the slab's runs as they lie in memory
-            const RunLayout R = run_layout(NW, x0, y0, z0, P);
+            const RunLayout R = run_layout<16 / sizeof(OT)>(NW, x0, y0, z0, P);
+            OT *rtile = reinterpret_cast<OT *>(un); // (a bfloat16 grid: a bfloat16 tile, store_runs)
             const size_t S0 = (((size_t)b * P.C + L.cbase) * D + x0) * D2 + (size_t)y0 * D + z0;
             const int col = SUBZ * wave + lz;
             const bool zok = !R.joined || col < D;
@@ -194,12 +195,12 @@ struct OpsMx32 {
                 if (zok) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
-                        tile[L0 + mine_r + c * R.SC] = acc.p0[4 * rd + c];
-                        tile[L0 + mine_r + c * R.SC + R.SX] = acc.p1[4 * rd + c];
+                        rtile[L0 + mine_r + c * R.SC] = (OT)acc.p0[4 * rd + c];
+                        rtile[L0 + mine_r + c * R.SC + R.SX] = (OT)acc.p1[4 * rd + c];
                     }
                 }
                 __syncthreads();
-                store_runs<false>(tile, R, L0, CR, L.cbase + rd * CR, S0r, tid, NW * 64, out, P);
+                store_runs<false, OT>(rtile, R, L0, CR, L.cbase + rd * CR, S0r, tid, NW * 64, out, P);
             }
             return;
         }
@@ -228,7 +229,7 @@ struct OpsMx32 {
 // fma(0, w, acc) = acc). Its rows (<= 32 words) are staged two per load instruction with addresses formed on the
 // vector ALU (stage_round_v): the eight scalar index loads and 64-bit scalar address computations per wave were
 // half of the scalar instructions.
-template <int CT_, bool GAUSS, bool RUNS_ = false>
+template <int CT_, bool GAUSS, bool RUNS_ = false, typename OT = float>
 struct OpsPair {
     static constexpr int CT = CT_;
     static constexpr bool RUNS = RUNS_; // carries the run-wise write-out (store_runs): the per-molecule kernel and voxelize_pair_runs_kernel
@@ -312,8 +313,8 @@ struct OpsPair {
     }
     static __device__ __forceinline__ void write(const Acc &acc, bool any, unsigned *un, int tid, int lane, int wave, int NW,
                                                  int b, const LaneCtx &L, int x0, int y0, int z0, void *out, const VoxParams &P) {
-        write_slab<CT, RUNS>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0,
-                             static_cast<float *>(out), P);
+        write_slab<CT, RUNS, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0,
+                                         static_cast<OT *>(out), P);
     }
 };
 

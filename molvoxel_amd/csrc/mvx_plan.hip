@@ -167,3 +167,12 @@ extern "C" int mvx_plan_call(const mvx_plan_query *query, mvx_plan *plan) {
     *plan = mvx::plan_call(*query, mvx::PlanKnobs{});
     return MVX_OK;
 }
+
+// A bfloat16 grid is written by the float32 kernels with the same slot map (four voxels per store: 8 bytes instead of 16), so its
+// plan is the float32 plan of the same query: rows of whole groups of four (D % 4 == 0) and an out_aligned16 that stands for
+// the 8-byte alignment of the grid take the vector stores, anything else the run-wise write-out.
+extern "C" int mvx_plan_call_grid(const mvx_plan_query *query, int32_t grid_type, mvx_plan *plan) {
+    if (grid_type != MVX_GRID_REAL && grid_type != MVX_GRID_BF16) return MVX_ERR_INVALID;
+    if (grid_type == MVX_GRID_BF16 && query && query->precision == 64) return MVX_ERR_INVALID;
+    return mvx_plan_call(query, plan);
+}

@@ -35,28 +35,28 @@ static size_t voxelize_mx_lds_bytes(int32_t NW) { return std::max(voxelize_lds_b
 
 // voxelize_kernel's arithmetic: 32-channel chunks go to the matrix cores (OpsMx32), narrower chunks to the vector ALU in
 // candidate pairs (OpsPair); the per-lane-range variants keep one voxel per lane and candidate (OpsF32)
-template <int CT, bool GAUSS, bool LANE_RANGE, bool GROUPED>
+template <int CT, bool GAUSS, bool LANE_RANGE, bool GROUPED, typename OT = float>
 struct SlabOps {
-    typedef OpsF32<CT, GAUSS, LANE_RANGE> type;
+    typedef OpsF32<CT, GAUSS, LANE_RANGE, OT> type;
 };
-template <int CT, bool GAUSS>
-struct SlabOps<CT, GAUSS, false, false> {
-    typedef OpsPair<CT, GAUSS> type;
+template <int CT, bool GAUSS, typename OT>
+struct SlabOps<CT, GAUSS, false, false, OT> {
+    typedef OpsPair<CT, GAUSS, false, OT> type;
 };
 // (not the per-lane-range variants - blockdim 4, 5, 12, ...: their six extra index comparisons per voxel do not fit the
 // 64 registers of the two-voxel layout without scratch: 0.527 against 0.479 ms per 64 cfg-2 molecules at blockdim 5)
-template <bool GAUSS>
-struct SlabOps<32, GAUSS, false, false> {
-    typedef OpsMx32<GAUSS, false, false> type;
+template <bool GAUSS, typename OT>
+struct SlabOps<32, GAUSS, false, false, OT> {
+    typedef OpsMx32<GAUSS, false, false, false, OT> type;
 };
-template <bool GAUSS>
-struct SlabOps<32, GAUSS, false, true> {
-    typedef OpsMx32<GAUSS, false, true> type;
+template <bool GAUSS, typename OT>
+struct SlabOps<32, GAUSS, false, true, OT> {
+    typedef OpsMx32<GAUSS, false, true, false, OT> type;
 };
 // (grouped launches - channel-wise features by radius - exist on the matrix-core path only, per-lane ranges or not)
-template <bool GAUSS>
-struct SlabOps<32, GAUSS, true, true> {
-    typedef OpsMx32<GAUSS, true, true> type;
+template <bool GAUSS, typename OT>
+struct SlabOps<32, GAUSS, true, true, OT> {
+    typedef OpsMx32<GAUSS, true, true, true, OT> type;
 };
 
 template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
@@ -65,6 +65,16 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
                     const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc, float *__restrict__ out,
                     const VoxParams P) {
     typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED>::type Ops;
+#include "mvx_slab_body.inc"
+}
+// bfloat16 grids (mvx_config.grid_type = MVX_GRID_BF16): the same slab body; only the store of the write-out differs (Ops<..., __bf16>).
+// Every float32 slab kernel has such a twin of its own name: the float32 kernels and their names stay as they are.
+template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
+__global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
+    voxelize_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                         const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
+                         __bf16 *__restrict__ out, const VoxParams P) {
+    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED, __bf16>::type Ops;
 #include "mvx_slab_body.inc"
 }
 
@@ -81,11 +91,10 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
 // channels (accumulator sets, eight row loads in flight); at the 64 of voxelize_kernel it spilled 1 ... 17 registers.
 // (16 channels: 96 registers and no gain over one sub-tile per wave, 0.228 ms both - they keep voxelize_kernel.)
 constexpr int narrow_waves_per_simd(int ct, int nsub) { return 8; }
-template <int CT, bool GAUSS, int NSUB>
-__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
-    voxelize_narrow_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                           const uint2 *__restrict__ slist_ext, float *__restrict__ out, const VoxParams P) {
-    typedef OpsPair<CT, GAUSS> Ops;
+template <int CT, bool GAUSS, int NSUB, typename OT>
+__device__ __forceinline__ void narrow_body(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                                            const uint2 *__restrict__ slist_ext, OT *__restrict__ out, const VoxParams &P) {
+    typedef OpsPair<CT, GAUSS, false, OT> Ops;
     constexpr int SW = Ops::SW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned *un = reinterpret_cast<unsigned *>(smem);
@@ -207,15 +216,15 @@ __global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
     const int zq = z0 + 4 * q;
     const int sxx = (rfirst >> SUBY_SH) & (SUBX - 1), syy = rfirst & (SUBY - 1), cfirst = rfirst / RPC; // cfirst < CPP
     const bool vox_ok = (x0 + sxx < D) && (y0 + syy < D) && (zq < D);
-    float *dst0 = out + ((size_t)b * P.C + cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
+    OT *dst0 = out + ((size_t)b * P.C + cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
     if (n_hdr == 0) { // zero fill without the LDS round trip, held back and sent in pieces in big launches (write_slab)
-        if (P.pace) __builtin_amdgcn_s_sleep(EMPTY_HOLD);
+        if (P.pace) __builtin_amdgcn_s_sleep(pacing<OT>::empty_hold);
         if (vox_ok) {
 #pragma unroll
             for (int p = 0; p < (CT + CPP - 1) / CPP; ++p) {
                 const int c = cfirst + CPP * p;
-                if (c < CT && cbase + c < P.C) store_f4(dst0 + (size_t)(CPP * p) * D3, make_float4(0.f, 0.f, 0.f, 0.f));
-                if (P.pace && ((p + 1) * CPP) % 8 == 0 && p + 1 < (CT + CPP - 1) / CPP) __builtin_amdgcn_s_sleep(EMPTY_SPLIT);
+                if (c < CT && cbase + c < P.C) store_q(dst0 + (size_t)(CPP * p) * D3, make_float4(0.f, 0.f, 0.f, 0.f));
+                if (P.pace && ((p + 1) * CPP) % 8 == 0 && p + 1 < (CT + CPP - 1) / CPP) __builtin_amdgcn_s_sleep(pacing<OT>::empty_split);
             }
         }
         return;
@@ -242,11 +251,23 @@ __global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
                 const int c = cfirst + CPP * p; // channel inside the round
                 if (c < CR && cbase + rd * CR + c < P.C) {
                     const float4 v = *reinterpret_cast<const float4 *>(tile + (rfirst + CPP * RPC * p) * RS + 4 * q);
-                    store_f4(dst0 + (size_t)(rd * CR + CPP * p) * D3, v);
+                    store_q(dst0 + (size_t)(rd * CR + CPP * p) * D3, v);
                 }
             }
         }
     }
+}
+template <int CT, bool GAUSS, int NSUB>
+__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
+    voxelize_narrow_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                           const uint2 *__restrict__ slist_ext, float *__restrict__ out, const VoxParams P) {
+    narrow_body<CT, GAUSS, NSUB>(rec, w, slist, slist_ext, out, P);
+}
+template <int CT, bool GAUSS, int NSUB>
+__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
+    voxelize_narrow_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                                const uint2 *__restrict__ slist_ext, __bf16 *__restrict__ out, const VoxParams P) {
+    narrow_body<CT, GAUSS, NSUB>(rec, w, slist, slist_ext, out, P);
 }
 
 // 32-channel chunks of float32 grids whose rows are not whole 16-byte quads (odd dimensions, unaligned grid slices): the
@@ -262,6 +283,16 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
     constexpr bool GROUPED = false;
 #include "mvx_slab_body.inc"
 }
+template <bool GAUSS, int MAXT>
+__global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
+    voxelize_runs_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                              const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
+                              __bf16 *__restrict__ out, const VoxParams P) {
+    typedef OpsMx32<GAUSS, false, false, true, __bf16> Ops;
+    constexpr int CT = 32;
+    constexpr bool GROUPED = false;
+#include "mvx_slab_body.inc"
+}
 
 // Narrow chunks (1 ... 16 channels) of such grids: the candidate-pair walk (OpsPair) with the run-wise write-out. Until late in
 // round 4 these launches went to the per-lane-range kernels (OpsF32: one candidate and one voxel per lane step, six index
@@ -273,6 +304,15 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
                               const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
                               float *__restrict__ out, const VoxParams P) {
     typedef OpsPair<CT, GAUSS, true> Ops;
+    constexpr bool GROUPED = false;
+#include "mvx_slab_body.inc"
+}
+template <int CT, bool GAUSS, int MAXT>
+__global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
+    voxelize_pair_runs_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                                   const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
+                                   __bf16 *__restrict__ out, const VoxParams P) {
+    typedef OpsPair<CT, GAUSS, true, __bf16> Ops;
     constexpr bool GROUPED = false;
 #include "mvx_slab_body.inc"
 }
@@ -322,6 +362,25 @@ constexpr bool mx_kernel() {
     return std::is_same<typename SlabOps<CT, GAUSS, LANE_RANGE, false>::type, OpsMx32<GAUSS, LANE_RANGE, false>>::value;
 }
 
+// the kernel of a grid element type: float -> the float32 kernels, __bf16 -> their bfloat16 twins
+template <int CT, bool G, bool LR, int MT, bool GR = false>
+static auto slab_kernel(float *) { return &voxelize_kernel<CT, G, LR, MT, GR>; }
+template <int CT, bool G, bool LR, int MT, bool GR = false>
+static auto slab_kernel(__bf16 *) { return &voxelize_bf16_kernel<CT, G, LR, MT, GR>; }
+template <bool G, int MT>
+static auto runs_kernel(float *) { return &voxelize_runs_kernel<G, MT>; }
+template <bool G, int MT>
+static auto runs_kernel(__bf16 *) { return &voxelize_runs_bf16_kernel<G, MT>; }
+template <int CT, bool G, int MT>
+static auto pair_runs_kernel(float *) { return &voxelize_pair_runs_kernel<CT, G, MT>; }
+template <int CT, bool G, int MT>
+static auto pair_runs_kernel(__bf16 *) { return &voxelize_pair_runs_bf16_kernel<CT, G, MT>; }
+template <int CT, bool G, int NSUB>
+static auto narrow_kernel(float *) { return &voxelize_narrow_kernel<CT, G, NSUB>; }
+template <int CT, bool G, int NSUB>
+static auto narrow_kernel(__bf16 *) { return &voxelize_narrow_bf16_kernel<CT, G, NSUB>; }
+
+template <typename OT>
 struct GroupedFn {
     const VoxArgs &a;
     int32_t nb;
@@ -337,16 +396,17 @@ struct GroupedFn {
             static LdsLimit raised;
             const size_t main_lds = voxelize_mx_lds_bytes(p.NW);
             p.dcap = (int32_t)main_lds; // where the slots' {T, k} table sits in LDS
-            auto kern = &voxelize_kernel<CT, GAUSS, LANE_RANGE, MAXT, true>;
+            auto kern = slab_kernel<CT, GAUSS, LANE_RANGE, MAXT, true>((OT *)nullptr);
             hipError_t e = raise_lds_limit(kern, main_lds + 16 * CHAN_GROUP_SLOTS, raised);
             if (e != hipSuccess) return e;
             launch_profiled(kern, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), main_lds + 16 * CHAN_GROUP_SLOTS, s, a.rec, a.w,
-                            a.slist, a.slist_ext, a.Tc, a.kc, static_cast<float *>(a.out), p);
+                            a.slist, a.slist_ext, a.Tc, a.kc, static_cast<OT *>(a.out), p);
             return hipGetLastError();
         }
     }
 };
 
+template <typename OT>
 struct LaunchFn {
     const VoxArgs &a;
     int32_t nb;
@@ -370,44 +430,44 @@ struct LaunchFn {
                     hipError_t en = raise_lds_limit(kn, lds_n, raised_n);
                     if (en != hipSuccess) return en;
                     launch_profiled(kn, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW / nsub * 64), lds_n, s, a.rec, a.w, a.slist,
-                                    a.slist_ext, static_cast<float *>(a.out), a.p);
+                                    a.slist_ext, static_cast<OT *>(a.out), a.p);
                     return hipGetLastError();
                 };
                 if constexpr (CT <= 4) {
-                    if (nsub == 4) return launch_n(&voxelize_narrow_kernel<CT, GAUSS, 4>);
+                    if (nsub == 4) return launch_n(narrow_kernel<CT, GAUSS, 4>((OT *)nullptr));
                 }
-                if (nsub == 2) return launch_n(&voxelize_narrow_kernel<CT, GAUSS, 2>);
+                if (nsub == 2) return launch_n(narrow_kernel<CT, GAUSS, 2>((OT *)nullptr));
             }
         }
-        auto kern = &voxelize_kernel<CT, GAUSS, LANE_RANGE, MAXT>;
+        auto kern = slab_kernel<CT, GAUSS, LANE_RANGE, MAXT>((OT *)nullptr);
         LdsLimit *state = &raised;
         if (!p.vec_store) {
             if constexpr (mx) {
                 static LdsLimit raised_runs;
-                kern = &voxelize_runs_kernel<GAUSS, MAXT>;
+                kern = runs_kernel<GAUSS, MAXT>((OT *)nullptr);
                 state = &raised_runs;
             } else if constexpr (!LANE_RANGE) { // narrow chunks: the pair walk with store_runs
                 static LdsLimit raised_pair_runs;
-                kern = &voxelize_pair_runs_kernel<CT, GAUSS, MAXT>;
+                kern = pair_runs_kernel<CT, GAUSS, MAXT>((OT *)nullptr);
                 state = &raised_pair_runs;
             }
         }
         hipError_t e = raise_lds_limit(kern, lds, *state);
         if (e != hipSuccess) return e;
         launch_profiled(kern, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), lds, s, a.rec, a.w,
-                        a.slist, a.slist_ext, a.Tc, a.kc, static_cast<float *>(a.out), a.p);
+                        a.slist, a.slist_ext, a.Tc, a.kc, static_cast<OT *>(a.out), a.p);
         return hipGetLastError();
     }
 };
 
 hipError_t launch_voxelize(const VoxArgs &a, int32_t nb, int32_t ct, bool gauss, bool lane_range, hipStream_t s) {
     KernelKey k{ct, gauss, lane_range, a.p.NW <= 8 ? 512 : 1024};
-    return for_kernel(k, LaunchFn{a, nb, s});
+    return a.bf16 ? for_kernel(k, LaunchFn<__bf16>{a, nb, s}) : for_kernel(k, LaunchFn<float>{a, nb, s});
 }
 
 hipError_t launch_voxelize_grouped(const VoxArgs &a, int32_t nb, bool gauss, bool lane_range, hipStream_t s) {
     KernelKey k{32, gauss, lane_range, a.p.NW <= 8 ? 512 : 1024};
-    return for_kernel(k, GroupedFn{a, nb, s});
+    return a.bf16 ? for_kernel(k, GroupedFn<__bf16>{a, nb, s}) : for_kernel(k, GroupedFn<float>{a, nb, s});
 }
 
 } // namespace mvx

@@ -34,6 +34,22 @@ constexpr int PACE_MAX_CANDIDATES = 48;
 // sustained loop 0.791 / 0.807 - but 64 in bursts of 20 calls, tools/variants.py: 0.394 / 0.417 ms per call: the limit stays)
 constexpr long long PACE_ROUNDS_MIN_WGS = 49152;
 constexpr long long PACE_EMPTY_MIN_WGS = 4096;
+// bfloat16 grids (mvx_config.grid_type = MVX_GRID_BF16): a slab queues half the bytes of its float32 twin, and the sleeps
+// are dead time - no pacing (s_sleep 0). Same box, kernel bfloat16 / float32 (hold, split, round step; tools/rate_bf16.py
+// --lib, profiles/r05_bf16.txt): cfg-2 x 256: 64/10/3 0.868-0.874, 64/20/6 (the float32 values) 0.902, 32/10/3 0.871,
+// 64/10/0 0.836, 0/0/0 0.829-0.832; cfg-4 x 128 ligands: 0.812-0.814 / 0.853 / 0.676 / 0.811 / 0.580; cfg-3 x 256 and
+// D = 49 x 64 0.87 and 0.77 whatever the values. (EA write stalls with bfloat16 grids: 1/7 of float32's.)
+constexpr int EMPTY_HOLD_BF16 = 0;
+constexpr int EMPTY_SPLIT_BF16 = 0;
+constexpr int ROUND_SLEEP_STEP_BF16 = 0;
+template <typename OT>
+struct pacing { // per grid element type (float: the float32 constants above)
+    static constexpr int empty_hold = EMPTY_HOLD, empty_split = EMPTY_SPLIT, round_sleep_step = ROUND_SLEEP_STEP;
+};
+template <>
+struct pacing<__bf16> {
+    static constexpr int empty_hold = EMPTY_HOLD_BF16, empty_split = EMPTY_SPLIT_BF16, round_sleep_step = ROUND_SLEEP_STEP_BF16;
+};
 
 // ---- occupancy targets ------------------------------------------------------------------------------------------------------
 // waves per SIMD the 1024-thread slab variants (whole rows of 65 ... 128 voxels: 9 ... 16 waves) are compiled for: 8 = 64

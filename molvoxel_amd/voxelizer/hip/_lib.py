@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(CSRC, "libmvx_hip.so")
 MVX_HOST, MVX_DEVICE = 0, 1
 MVX_GAUSSIAN, MVX_BINARY = 0, 1
 MVX_RADII_SCALAR, MVX_RADII_ATOM, MVX_RADII_CHANNEL = 0, 1, 2
+MVX_GRID_REAL, MVX_GRID_BF16 = 0, 1
 MVX_XF_CENTER, MVX_XF_ROTATE, MVX_XF_TRANSLATE, MVX_XF_RECENTER, MVX_XF_CENTER_PTR = 1, 2, 4, 8, 16
 
 
@@ -27,7 +28,7 @@ class MvxConfig(C.Structure):
         ("density", C.c_int32),
         ("device", C.c_int32),
         ("precision", C.c_int32),
-        ("reserved", C.c_int32),
+        ("grid_type", C.c_int32),
     ]
 
 
@@ -91,6 +92,7 @@ SIGNATURES = {
     "mvx_debug_read_records": (C.c_int, [Handle, _vp, _i64, _vp]),
     "mvx_debug_set_option": (C.c_int, [Handle, C.c_char_p, _i32]),
     "mvx_plan_call": (C.c_int, [C.POINTER(MvxPlanQuery), C.POINTER(MvxPlan)]),
+    "mvx_plan_call_grid": (C.c_int, [C.POINTER(MvxPlanQuery), _i32, C.POINTER(MvxPlan)]),
     "mvx_alloc": (C.c_int, [Handle, _i64, C.POINTER(C.c_void_p)]),
     "mvx_free": (C.c_int, [Handle, _vp]),
     "mvx_memcpy": (C.c_int, [Handle, _vp, _vp, _i64, _i32, _i32, _vp]),
@@ -127,12 +129,17 @@ def check(rc: int):
 
 
 def plan_call(dimension, C_, B=1, total_atoms=0, max_atoms=None, mode="features", radii_type="scalar", precision=32,
-              blockdim=8, out_aligned16=True) -> dict:
-    """How libmvx_hip would execute a call of this shape (mvx_plan_call: a pure host function, no GPU needed)."""
+              blockdim=8, out_aligned16=True, grid_type=MVX_GRID_REAL) -> dict:
+    """How libmvx_hip would execute a call of this shape (mvx_plan_call: a pure host function, no GPU needed).
+    grid_type MVX_GRID_BF16: the plan of a bfloat16 grid (mvx_plan_call_grid; out_aligned16 then stands for 8-byte
+    alignment)."""
     q = MvxPlanQuery(dimension, blockdim, precision, MODES[mode], RADII[radii_type], B, C_, 1 if out_aligned16 else 0,
                      total_atoms, total_atoms if max_atoms is None else max_atoms)
     p = MvxPlan()
-    check(load().mvx_plan_call(C.byref(q), C.byref(p)))
+    if grid_type == MVX_GRID_REAL:
+        check(load().mvx_plan_call(C.byref(q), C.byref(p)))
+    else:
+        check(load().mvx_plan_call_grid(C.byref(q), int(grid_type), C.byref(p)))
     return {name: getattr(p, name) for name, _ in MvxPlan._fields_ if name != "reserved"}
 
 

@@ -10,7 +10,9 @@ There is no CPU fallback: construction fails without the shared library or witho
 Array arguments may be numpy arrays (host: staged through pinned memory by the library) or torch
 CUDA tensors on this voxelizer's device (zero-copy via data_ptr on the current torch stream).
 Grids this backend allocates are torch CUDA tensors by default (`output="torch"`), so results stay
-in HBM; pass `output="numpy"` (or a numpy `out_grid`) for host arrays.
+in HBM; pass `output="numpy"` (or a numpy `out_grid`) for host arrays. `grid_dtype="bfloat16"` makes the
+kernels write bfloat16 grids directly: the float32 grid rounded to nearest even as it is stored, bit for bit
+what `.to(torch.bfloat16)` of the float32 grid gives, at half the bytes.
 """
 from __future__ import annotations
 
@@ -57,16 +59,19 @@ class Voxelizer(BaseVoxelizer):
         device=None,
         output: str = "torch",
         overlap_prepass: bool = False,
+        grid_dtype=None,
         **kwargs,
     ):
         super().__init__(resolution, dimension, radii_type, density_type, **kwargs)
         assert precision in [32, 64]
         assert output in ("torch", "numpy")
+        self._bf16 = self._is_bf16_grid(grid_dtype, precision, output)  # (checked before anything touches a device)
         if output == "torch" and torch is None:
             raise ImportError("output='torch' needs PyTorch; use output='numpy'")
         self.precision = precision
         self.fp = np.float32 if precision == 32 else np.float64  # numpy/voxelizer.py:34
         self._tfp = None if torch is None else (torch.float32 if precision == 32 else torch.float64)
+        self._gdt = torch.bfloat16 if self._bf16 else self._tfp  # element type of the grids (torch)
         self.blockdim = blockdim if blockdim is not None else 8  # numpy/voxelizer.py:38
         self.num_blocks = -(-dimension // self.blockdim)
         self.output = output
@@ -87,12 +92,33 @@ class Voxelizer(BaseVoxelizer):
             _lib.MVX_GAUSSIAN if density_type == "gaussian" else _lib.MVX_BINARY,
             self._device_index,
             int(precision),
-            0,
+            _lib.MVX_GRID_BF16 if self._bf16 else _lib.MVX_GRID_REAL,
         )
         _lib.check(self._lib.mvx_create(C.byref(cfg), C.byref(self._handle)))
         self.overlap_prepass = bool(overlap_prepass)
         if self.overlap_prepass:
             self.set_overlap_prepass(True)
+
+    @staticmethod
+    def _is_bf16_grid(grid_dtype, precision, output) -> bool:
+        """grid_dtype: None (the precision's type), "float32" / torch.float32 (precision 32), "bfloat16" / torch.bfloat16
+        (precision 32, torch output: numpy has no bfloat16)."""
+        if grid_dtype is None:
+            return False
+        name = str(grid_dtype).replace("torch.", "") if (torch is not None and isinstance(grid_dtype, torch.dtype)) else grid_dtype
+        if name not in ("float32", "bfloat16"):
+            raise ValueError(f"grid_dtype must be None, 'float32' or 'bfloat16' (or the torch dtypes), not {grid_dtype!r}")
+        if precision != 32:
+            raise ValueError(f"grid_dtype={name!r} needs precision=32 (a precision-64 voxelizer writes float64 grids)")
+        if name == "bfloat16" and output != "torch":
+            raise ValueError("grid_dtype='bfloat16' needs output='torch': numpy has no bfloat16")
+        return name == "bfloat16"
+
+    @property
+    def grid_dtype(self):
+        """Element type of the grids this voxelizer writes: torch.float32 / torch.float64 (the precision's), or
+        torch.bfloat16. (numpy dtype without torch.)"""
+        return self._gdt if self._gdt is not None else self.fp
 
     def set_overlap_prepass(self, enable: bool):
         """Loops of large `forward_batch` calls: run the pre-pass of call k+1 under the voxelize launches of call k
@@ -142,7 +168,7 @@ class Voxelizer(BaseVoxelizer):
             shape = (batch_size,) + shape
         if self.output == "torch":
             fn = torch.zeros if init_zero else torch.empty
-            return fn(shape, dtype=self._tfp, device=self.device)
+            return fn(shape, dtype=self._gdt, device=self.device)
         if torch is not None and torch.cuda.is_available():
             # numpy grids live in pinned host memory (torch's caching host allocator): the copy back is a direct DMA
             # at PCIe speed instead of a staged pageable copy (3.4 -> ~0.7 ms per cfg-2 grid)
@@ -173,7 +199,8 @@ class Voxelizer(BaseVoxelizer):
         if idx != self._device_index:
             kw = {"sigma": self._sigma} if self.is_density_type_gaussian else {}
             return type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
-                              self.blockdim, idx, self.output, self.overlap_prepass, **kw)
+                              self.blockdim, idx, self.output, self.overlap_prepass,
+                              grid_dtype="bfloat16" if self._bf16 else None, **kw)
         return self
 
     def cuda(self):
@@ -276,10 +303,13 @@ class Voxelizer(BaseVoxelizer):
         if out_grid is None:
             out_grid = self.get_empty_grid(shape[0])
         if _is_torch(out_grid):
-            if self._on_device(out_grid) and out_grid.is_contiguous() and out_grid.dtype == self._tfp:
+            if self._on_device(out_grid) and out_grid.is_contiguous() and out_grid.dtype == self._gdt:
                 return out_grid, _lib.MVX_DEVICE, out_grid, None
-            tmp = torch.empty(tuple(out_grid.shape), dtype=self._tfp, device=self.device)
+            tmp = torch.empty(tuple(out_grid.shape), dtype=self._gdt, device=self.device)
             return tmp, _lib.MVX_DEVICE, out_grid, "copy_torch"
+        if self._bf16:  # a numpy grid (no bfloat16 there): the bfloat16 grid is made on the device and copied as float32
+            tmp = torch.empty(tuple(out_grid.shape), dtype=self._gdt, device=self.device)
+            return tmp, _lib.MVX_DEVICE, out_grid, "copy_numpy_bf16"
         if out_grid.flags.c_contiguous and out_grid.dtype == self.fp:
             return out_grid, _lib.MVX_HOST, out_grid, None
         tmp = np.empty(out_grid.shape, dtype=self.fp)
@@ -291,6 +321,8 @@ class Voxelizer(BaseVoxelizer):
             ret.copy_(buf)
         elif how == "copy_numpy":
             ret[...] = buf
+        elif how == "copy_numpy_bf16":
+            ret[...] = buf.float().cpu().numpy()
         return ret
 
     def _radii_type_code(self):
@@ -446,7 +478,7 @@ class Voxelizer(BaseVoxelizer):
         coords (sumN,3) float64; offsets (B+1,) int64 (host); centers (B,3) | None;
         channels: (sumN,C) float -> features, (sumN,) int -> types, None -> single;
         radii: python float | (sumN,) | (C,) per this voxelizer's radii_type.
-        out_grid: (B,C,D,H,W) float32 (torch CUDA tensor on this device or numpy), fully overwritten.
+        out_grid: (B,C,D,H,W) of this voxelizer's grid_dtype (torch CUDA tensor on this device or numpy), fully overwritten.
         A random transform, if requested, is drawn per molecule in molecule order.
         """
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)

@@ -4,6 +4,7 @@
 Stamps per workgroup (s_memtime = shader cycles; only deltas inside a workgroup are meaningful):
   0 start | 1 line arrived | 2 rows staged by wave 0 | 3 staging barrier passed | 8+w walk end of wave w |
   4 barrier after the walk | 5 write-out round 0 (4 channels) done | 6 all stores issued | 7 = candidates in the line
+GRID=bfloat16 in the environment: the same calls on a bfloat16 grid (voxelize_bf16_kernel, the same stamps).
 """
 import ctypes as C
 import os
@@ -21,17 +22,19 @@ _l.SIGNATURES["mvx_debug_read_diag"] = (C.c_int, [_l.Handle, C.c_void_p, C.c_int
 import molvoxel_amd
 from molvoxel_amd import workloads as W
 
+GRID = {"grid_dtype": os.environ["GRID"]} if os.environ.get("GRID") else {}
+
 CFG5 = len(sys.argv) > 1 and sys.argv[1] == "cfg5"  # one cfg-5 molecule (N = 10 000, 128^3), binned route
 B = (int(sys.argv[3]) if len(sys.argv) > 3 else 1) if CFG5 else (int(sys.argv[1]) if len(sys.argv) > 1 else 256)
 if CFG5:
     wl = W.cfg5(batch=B)
-    vox = molvoxel_amd.create_voxelizer(0.5, 128, "atom-wise", "gaussian", library="hip", sigma=1.0)
+    vox = molvoxel_amd.create_voxelizer(0.5, 128, "atom-wise", "gaussian", library="hip", sigma=1.0, **GRID)
     vox.debug_option("direct", 0)
     radii = vox.asarray(np.concatenate(wl.radii), "radii")
     nwg = 4096 * B
 else:
     wl = W.cfg2(batch=B)
-    vox = molvoxel_amd.create_voxelizer(0.5, 64, library="hip")
+    vox = molvoxel_amd.create_voxelizer(0.5, 64, library="hip", **GRID)
     radii = float(os.environ.get("RADIUS", "1.0"))  # scalar radius in Angstrom (cfg-2 itself: 1.0)
     nwg = B * 512
     vox.debug_option("direct", 0)
@@ -55,7 +58,7 @@ t = t[ok]
 kc = lambda a, b: (t[:, b] - t[:, a]) / 1000.0
 def line(name, x):
     print(f"{name:34s} p10 {np.percentile(x, 10):6.2f}  p50 {np.percentile(x, 50):6.2f}  p90 {np.percentile(x, 90):6.2f}  mean {x.mean():6.2f}")
-print(f"{'cfg-5' if CFG5 else 'cfg-2'} x {B}" + ("" if CFG5 else f" radius {radii}") + f": {int(ok.sum())} non-empty workgroups of {nwg}; candidates per line p50 {np.median(n[ok]):.0f} max {n[ok].max():.0f}")
+print(f"{'cfg-5' if CFG5 else 'cfg-2'} x {B} {GRID.get('grid_dtype', 'float32')}" + ("" if CFG5 else f" radius {radii}") + f": {int(ok.sum())} non-empty workgroups of {nwg}; candidates per line p50 {np.median(n[ok]):.0f} max {n[ok].max():.0f}")
 print("phase (kilocycles per workgroup)")
 line("line load             0 -> 1", kc(0, 1))
 line("row loads + LDS       1 -> 2", kc(1, 2))
