@@ -186,6 +186,41 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const mvx_real *radi
                        int32_t out_kind, void *stream);
 
 /*
+ * Backward pass of a batched call (no counterpart in the reference: its torch backend runs under torch.no_grad()).
+ * Given G = dL/dgrid for the grid the forward call with the same arguments wrote, returns the gradients of L with respect
+ * to the atom coordinates and (features mode) the feature rows. With p_n the position of atom n after centring / transform
+ * and rho_{n,c}(v) = m_{n,c}(v) * exp2(k * float32(d2)) (gaussian; float64 grids: exp(c * d2)) or m_{n,c}(v) (binary),
+ * m the forward's membership rule bit for bit (d2 <= T and the voxel inside the atom's admitted ranges; channel-wise radii
+ * for features: per channel T_c, k_c), so that grid[c, v] = sum_n w[n,c] rho_{n,c}(v) (w: the feature row, onehot(type),
+ * or 1):
+ *   dL/dw[n,c]     = sum_v G[c,v] rho_{n,c}(v)                                                     (features mode only)
+ *   dL/dp_n        = sum_v (sum_c G[c,v] w[n,c] rho_{n,c}(v) 2 ln2 k_{n,c}) (p_n - g_v)   (float64 grids: 2 c, not 2 ln2 k)
+ *   dL/dcoords_n   = M^T dL/dp_n, M the linear part of the transform (identity without MVX_XF_ROTATE; with it M^T is the
+ *                    same sandwich product with the conjugate quaternion, exact for |q| != 1 too)
+ * The membership m is the forward's bit for bit; the float32 density value is too. Float64 Gaussian values are evaluated
+ * with the library exp, while the forward's 32-channel float64 matrix-core walk uses its own exp (within ~1 ulp): there the
+ * gradients are those of a density that may differ from the stored grid in the last ulp.
+ * Derivative almost everywhere: the jump of rho at the truncation radius is ignored, so binary density gives zero coordinate
+ * gradients. The gradient with respect to a centre is -sum of dL/dcoords over the molecule (no MVX_XF_RECENTER: the caller
+ * reduces it). No gradients with respect to radii or sigma.
+ * Outputs are fully overwritten (atoms that reach no voxel get exact zeros) and deterministic: no atomics, fixed-order
+ * reductions; a molecule's gradients are bit for bit the same in any batch. Arguments as in the forward entries (same
+ * offsets / xforms / radii: the pre-pass is recomputed from them, nothing is kept from the forward call).
+ *   mode: 0 features, 1 types, 2 single (as mvx_plan_query.mode; single: C = 1). grad_out: (B, C, D, D, D) in the handle's
+ *   grid type (float, double or bfloat16), every channel of one molecule below 4 GiB. grad_coords: (sumN, 3) double or
+ *   NULL; grad_features: (sumN, C) mvx_real or NULL (features mode only); not both NULL.
+ * Device pointers except offsets / xforms (host, as in the forward entries; a MVX_XF_CENTER_PTR centre is a device
+ * pointer): this entry takes no host-resident arrays. Asynchronous on `stream`; not recorded by mvx_set_profiling. Keeps
+ * buffers of its own, so it never writes a workspace set an overlapped forward pre-pass (mvx_set_overlap) may be using.
+ * MVX_ERR_INVALID before any device is touched for a null handle, a bad mode, grad_features outside features mode,
+ * C <= 0, both outputs NULL or non-monotone offsets.
+ */
+int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                       double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                       int32_t B, int32_t C, const void *grad_out, double *grad_coords, mvx_real *grad_features,
+                       void *stream);
+
+/*
  * Replaces do_transform on an (N,3) fp64 point cloud (numpy/transform.py:44-60): out = transformed coords.
  * Exposed so that RandomTransform/T objects can run on device-resident coordinates.
  */
@@ -226,6 +261,8 @@ int mvx_debug_read_records(mvx_handle *h, void *host_dst, int64_t n, void *strea
  *   "max_ct64" = 16 | 32: float64 grids: channels one workgroup accumulates (default 32: Gaussian grids of more than
  *              16 channels take 32 per workgroup on 4-wave slabs; 16 = the two-chunk form every other grid uses);
  *   "nw" = 1..16: waves (8-voxel z sub-tiles) per slab instead of the plan's (0 = the plan); measurement aid;
+ *   "grad_order" = 0 / 1: mvx_backward_batch runs the atoms in the caller's order (0, the default) or in spatial order,
+ *              each XCD one contiguous range of it (1); results are the same bits either way. Measurement aid;
  *   "dense_grid": accepted and ignored (round 2's second voxelize launch no longer exists). */
 int mvx_debug_set_option(mvx_handle *h, const char *name, int32_t value);
 

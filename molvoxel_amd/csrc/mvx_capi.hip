@@ -4,6 +4,7 @@
 // arguments) and a small ring of pinned host slots so that calls with device-resident data are
 // fully asynchronous on the caller's stream (no hidden device synchronisation). There is no CPU
 // fallback in this library: without a usable HIP device mvx_create fails.
+#include "mvx_grad.h"
 #include "mvx_internal.h"
 #include "mvx_plan.h"
 
@@ -93,6 +94,13 @@ struct mvx_handle {
     hipStream_t side = nullptr;
     hipEvent_t ev_in = nullptr;
     std::vector<hipEvent_t> ev_pre;
+    // the backward pass (mvx_backward_batch) keeps buffers of its own: it never writes a workspace set that an overlapped
+    // pre-pass (mvx_set_overlap) on the side stream may be filling, nor one that voxelize launches may still read
+    DevBuf grad_rec, grad_xp, grad_meta, grad_aux, grad_sort;
+    // "grad_order" option: 0 atoms in the caller's order (the default), 1 in spatial order, XCD by XCD. The spatial order cuts
+    // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
+    // more than it saves (profiles/r05_grad.txt)
+    int grad_order = 0;
     int narrow_sub = 0; // "narrow_sub" option: sub-tiles per wave of narrow chunks (1: voxelize_kernel; 2 | 4: voxelize_narrow_kernel; 0: the rule)
     int dbg = 0; // diagnostic builds (-DMVX_DIAG) only
 };
@@ -341,6 +349,33 @@ int timed_launch(mvx_handle *h, hipStream_t s, Launch &&launch) {
     return MVX_OK;
 }
 
+// The pre-pass arguments of a call that do not point into its buffers (forward and backward share them: the backward's
+// records are the forward's). Pointers are null, the transform is none, the launch covers atoms [0, total).
+PrepArgs prep_args(const mvx_handle *h, int mode, int radii_type, double radius_scalar, int B, int C, int64_t total) {
+    const bool f64 = (h->cfg.precision == 64);
+    PrepArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.mode = mode;
+    pa.precision = f64 ? 64 : 32;
+    pa.first = 0;
+    pa.total = total;
+    pa.B = B;
+    pa.C = C;
+    pa.radius_scalar = radius_scalar;
+    pa.T_scalar = -1.0;
+    pa.k_scalar = 0.0f;
+    if (radii_type == MVX_RADII_SCALAR && !f64)
+        scalar_radius_constants(radius_scalar, h->sigma32, h->cfg.density == MVX_GAUSSIAN, &pa.T_scalar, &pa.k_scalar);
+    if (radii_type == MVX_RADII_SCALAR) pa.radii_src = RAD_SCALAR;
+    else if (radii_type == MVX_RADII_ATOM) pa.radii_src = RAD_ATOM;
+    else pa.radii_src = (mode == MODE_FEATURES) ? RAD_CHANNEL_FEATURES : RAD_CHANNEL_BY_TYPE;
+    pa.density = h->cfg.density;
+    pa.sigma32 = h->sigma32;
+    pa.sigma64 = h->cfg.sigma;
+    pa.g = h->g;
+    return pa;
+}
+
 int run(mvx_handle *h, const RunArgs &r) {
     int64_t total = 0, max_atoms = 0;
     int rc = validate(h, r, total, max_atoms);
@@ -474,35 +509,16 @@ int run(mvx_handle *h, const RunArgs &r) {
     }
 
     // ---- kernel arguments -------------------------------------------------------------------------
-    PrepArgs pa;
+    PrepArgs pa = prep_args(h, r.mode, r.radii_type, r.radius_scalar, r.B, r.C, total);
     pa.coords = in.coords;
     pa.radii = in.radii;
     pa.types = (r.mode == MODE_TYPES) ? reinterpret_cast<const int32_t *>(in.channels) : nullptr;
     pa.features = (r.mode == MODE_FEATURES) ? in.channels : nullptr;
-    pa.mode = r.mode;
     pa.Cpad = Cpad;
     pa.offsets = in.offsets;
     pa.xforms = in.xforms;
-    std::memset(&pa.xf_one, 0, sizeof(pa.xf_one));
     if (by_value && r.xforms) pa.xf_one = r.xforms[0];
     pa.chan_aux = d_rmax;
-    pa.precision = f64 ? 64 : 32;
-    pa.first = 0;
-    pa.total = total;
-    pa.B = r.B;
-    pa.C = r.C;
-    pa.radius_scalar = r.radius_scalar;
-    pa.T_scalar = -1.0;
-    pa.k_scalar = 0.0f;
-    if (r.radii_type == MVX_RADII_SCALAR && !f64)
-        scalar_radius_constants(r.radius_scalar, h->sigma32, h->cfg.density == MVX_GAUSSIAN, &pa.T_scalar, &pa.k_scalar);
-    if (r.radii_type == MVX_RADII_SCALAR) pa.radii_src = RAD_SCALAR;
-    else if (r.radii_type == MVX_RADII_ATOM) pa.radii_src = RAD_ATOM;
-    else pa.radii_src = chanwise ? RAD_CHANNEL_FEATURES : RAD_CHANNEL_BY_TYPE;
-    pa.density = h->cfg.density;
-    pa.sigma32 = h->sigma32;
-    pa.sigma64 = h->cfg.sigma;
-    pa.g = g;
     pa.rec = reinterpret_cast<AtomRec *>(w.rec.p);
     pa.wbuf = direct_w ? nullptr : w.wbuf.p;
     pa.xp = reinterpret_cast<uint2 *>(w.xp.p);
@@ -723,7 +739,8 @@ int mvx_destroy(mvx_handle *h) {
     if (!h) return MVX_OK;
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
-    std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage};
+    std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage,
+                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort};
     for (Workspace &w : h->ws) {
         for (DevBuf *b : {&w.rec, &w.wbuf, &w.xp, &w.xlist, &w.slist, &w.meta, &w.aux}) bufs.push_back(b);
         if (w.ev_pre) (void)hipEventDestroy(w.ev_pre);
@@ -810,6 +827,118 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const void *radii, d
     const int64_t off[2] = {0, N};
     return mvx_forward_single_batch(h, coords, radii, radius_scalar, radii_type, off, xform, 1, out, in_kind,
                                     out_kind, stream);
+}
+
+int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                       double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
+                       int32_t C, const void *grad_out, double *grad_coords, void *grad_features, void *stream) {
+    // ---- what is checked before any device is touched ----
+    if (mode < MODE_FEATURES || mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
+    if (grad_features && mode != MODE_FEATURES) return fail(MVX_ERR_INVALID, "grad_features exists in features mode only");
+    if (C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
+    if (mode == MODE_SINGLE && C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
+    if (!grad_coords && !grad_features) return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
+    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (radii_type < MVX_RADII_SCALAR || radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
+    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
+    if (B > 0 && !offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
+    if (B > 0 && offsets[0] != 0) return fail(MVX_ERR_INVALID, "offsets[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (offsets[b + 1] < offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    const int64_t total = B > 0 ? offsets[B] : 0;
+    if (total == 0) return MVX_OK; // (no atoms: no gradient rows)
+    if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (!coords || !grad_out) return fail(MVX_ERR_INVALID, "coords / grad_out must not be null");
+    if (mode != MODE_SINGLE && !channels) return fail(MVX_ERR_INVALID, "channels must not be null");
+    if (!radii && radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
+    const bool f64 = h->cfg.precision == 64, bf16 = h->cfg.grid_type == MVX_GRID_BF16;
+    const size_t gsz = bf16 ? 2 : (f64 ? 8 : 4);
+    const size_t D = (size_t)h->g.D;
+    if (D * D * D * gsz >= ((size_t)1 << 32)) return fail(MVX_ERR_INVALID, "one channel of the grid must stay below 4 GiB");
+
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = adopt_stream(h, s);
+    if (rc) return rc;
+
+    // offsets (+ transforms) through a pinned slot, as the forward stages them
+    const size_t off_bytes = align_up((size_t)(B + 1) * sizeof(int64_t), 16);
+    const size_t xf_bytes = xforms ? (size_t)B * sizeof(mvx_xform) : 0;
+    PinnedSlot *slot = nullptr;
+    if ((rc = acquire_slot(h, off_bytes + xf_bytes, &slot))) return rc;
+    if ((rc = ensure(h->grad_meta, off_bytes + xf_bytes))) return rc;
+    std::memcpy(slot->p, offsets, (size_t)(B + 1) * sizeof(int64_t));
+    if (xforms) std::memcpy(slot->p + off_bytes, xforms, xf_bytes);
+    HIP_TRY(hipMemcpyAsync(h->grad_meta.p, slot->p, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
+    const int64_t *d_offsets = reinterpret_cast<const int64_t *>(h->grad_meta.p);
+    const mvx_xform *d_xforms = xforms ? reinterpret_cast<const mvx_xform *>((char *)h->grad_meta.p + off_bytes) : nullptr;
+
+    if ((rc = ensure(h->grad_rec, (size_t)total * sizeof(AtomRec)))) return rc;
+    if ((rc = ensure(h->grad_xp, (size_t)total * sizeof(uint2)))) return rc;
+    const bool gauss = h->cfg.density == MVX_GAUSSIAN;
+    const bool chanwise = radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES;
+    void *d_rmax = nullptr;
+    double *d_Tc = nullptr;
+    void *d_kc = nullptr;
+    if (chanwise) { // [max radius | per-channel thresholds | per-channel coefficients]
+        const size_t tc_off = 16, kc_off = tc_off + align_up((size_t)C * sizeof(double), 16);
+        if ((rc = ensure(h->grad_aux, kc_off + (size_t)C * sizeof(double)))) return rc;
+        d_rmax = h->grad_aux.p;
+        d_Tc = reinterpret_cast<double *>((char *)h->grad_aux.p + tc_off);
+        d_kc = (char *)h->grad_aux.p + kc_off;
+        HIP_TRY(launch_grad_chan(radii, C, f64, gauss, h->sigma32, h->cfg.sigma, d_rmax, d_Tc, d_kc, s));
+    }
+
+    // the forward's pre-pass: positions, thresholds, coefficients and admitted ranges of every atom, bit for bit
+    PrepArgs pa = prep_args(h, mode, radii_type, radius_scalar, B, C, total);
+    pa.coords = coords;
+    pa.radii = radii;
+    pa.types = mode == MODE_TYPES ? static_cast<const int32_t *>(channels) : nullptr;
+    pa.features = nullptr; // (no packed weights: the gradient kernel reads the feature rows in place)
+    pa.Cpad = C;
+    pa.offsets = d_offsets;
+    pa.xforms = d_xforms;
+    pa.chan_aux = d_rmax;
+    pa.rec = reinterpret_cast<AtomRec *>(h->grad_rec.p);
+    pa.wbuf = nullptr;
+    pa.xp = reinterpret_cast<uint2 *>(h->grad_xp.p);
+    HIP_TRY(launch_prep(pa, s));
+
+    // "grad_order" 1: neighbouring atoms in neighbouring waves of one XCD, so that the rows of G they read meet in its L2
+    // (the order decides which wave runs an atom, never what the atom's gradients are)
+    const uint32_t *order = nullptr;
+    int32_t xcd_span = 0;
+    if (h->grad_order) {
+        const size_t ob = grad_order_bytes(total, B, h->g.D);
+        if ((rc = ensure(h->grad_sort, ob))) return rc;
+        HIP_TRY(launch_grad_order(pa.rec, d_offsets, B, total, h->g.D, h->grad_sort.p, h->grad_sort.cap, &order, s));
+        xcd_span = (int32_t)(((total + 3) / 4 + 7) / 8);
+    }
+
+    GradArgs ga;
+    ga.rec = pa.rec;
+    ga.w = mode == MODE_FEATURES ? channels : nullptr;
+    ga.g = grad_out;
+    ga.offsets = d_offsets;
+    ga.xforms = d_xforms;
+    ga.Tc = d_Tc;
+    ga.kc = d_kc;
+    ga.grad_coords = grad_coords;
+    ga.grad_w = grad_features;
+    ga.order = order;
+    ga.xcd_span = xcd_span;
+    ga.total = total;
+    ga.B = B;
+    ga.C = C;
+    ga.D = h->g.D;
+    ga.res = h->g.res;
+    ga.half = h->g.half;
+    HIP_TRY(launch_grad(ga, mode, bf16 ? 1 : (f64 ? 2 : 0), gauss, chanwise, s));
+    HIP_TRY(hipEventRecord(slot->done, s));
+    slot->in_flight = true;
+    return MVX_OK;
 }
 
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,
@@ -909,6 +1038,7 @@ int mvx_debug_set_option(mvx_handle *h, const char *name, int32_t value) {
     else if (n == "max_ct") k.max_ct = std::max(1, std::min(32, (int)value));
     else if (n == "direct") k.direct_mode = value < 0 ? -1 : (value ? 1 : 0);
     else if (n == "max_ct64") k.max_ct64 = value >= 32 ? 32 : 16;
+    else if (n == "grad_order") h->grad_order = value ? 1 : 0;
     else if (n == "narrow_sub") h->narrow_sub = (value == 1 || value == 2 || value == 4) ? value : 0;
     else if (n == "dense_grid") (void)value; // (accepted and ignored: there is no second voxelize launch any more)
     else if (n == "nw") k.force_nw = (value >= 1 && value <= 16) ? value : 0; // waves (8-voxel z sub-tiles) per slab; 0 = the default plan

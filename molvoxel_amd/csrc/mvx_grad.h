@@ -1,0 +1,35 @@
+// mvx_grad.h - what the C-ABI TU (mvx_capi.hip) needs of the backward pass (mvx_grad.hip).
+#pragma once
+#include "mvx_internal.h"
+
+namespace mvx {
+
+struct GradArgs {
+    const AtomRec *rec;      // prep_kernel's records of the call
+    const void *w;           // features (total, C) in the handle's real type (features mode)
+    const void *g;           // G = dL/dgrid: (B, C, D, D, D) in the handle's grid type
+    const int64_t *offsets;  // device, B + 1
+    const mvx_xform *xforms; // device, B records, or null
+    const double *Tc;        // channel-wise radii for features: per-channel thresholds ...
+    const void *kc;          // ... and coefficients (float, or double for float64 grids)
+    double *grad_coords;     // (total, 3) or null
+    void *grad_w;            // (total, C) real or null
+    const uint32_t *order;   // the atoms in processing order (launch_grad_order), or null: atom order
+    int64_t total;
+    int32_t B, C, D;
+    int32_t xcd_span;        // > 0: XCD x takes workgroups [x * xcd_span, (x + 1) * xcd_span) of the order (8 xcd_span launched)
+    double res, half;
+};
+
+// channel-wise radii for features: rmax[0] = max(radii) (what prep_kernel culls with), per-channel thresholds Tc and
+// coefficients kc (float, or double for f64), from the forward's d2_threshold / gauss_coeff (float64: their *64 forms)
+hipError_t launch_grad_chan(const void *radii, int32_t C, bool f64, bool gauss, float sigma32, double sigma64, void *rmax, double *Tc,
+                            void *kc, hipStream_t s);
+// Spatial processing order of the atoms ("grad_order" option: key kernel + radix sort) in `ws` (grad_order_bytes); *order points into ws.
+size_t grad_order_bytes(int64_t total, int B, int D);
+hipError_t launch_grad_order(const AtomRec *rec, const int64_t *offsets, int B, int64_t total, int D, void *ws, size_t ws_bytes,
+                             const uint32_t **order, hipStream_t s);
+// grid_kind: 0 float, 1 bfloat16, 2 double. mode: Mode (single: the records carry type 0). One wave per atom record.
+hipError_t launch_grad(const GradArgs &a, int32_t mode, int32_t grid_kind, bool gauss, bool chanwise, hipStream_t s);
+
+} // namespace mvx

@@ -12,7 +12,9 @@ CUDA tensors on this voxelizer's device (zero-copy via data_ptr on the current t
 Grids this backend allocates are torch CUDA tensors by default (`output="torch"`), so results stay
 in HBM; pass `output="numpy"` (or a numpy `out_grid`) for host arrays. `grid_dtype="bfloat16"` makes the
 kernels write bfloat16 grids directly: the float32 grid rounded to nearest even as it is stored, bit for bit
-what `.to(torch.bfloat16)` of the float32 grid gives, at half the bytes.
+what `.to(torch.bfloat16)` of the float32 grid gives, at half the bytes. `differentiable=True` makes grids computed from device
+tensors that require grad (`coords`, `features`, `center`) part of the autograd graph: the backward pass runs on the GPU
+(mvx_backward_batch) and returns gradients with respect to those tensors.
 """
 from __future__ import annotations
 
@@ -60,11 +62,15 @@ class Voxelizer(BaseVoxelizer):
         output: str = "torch",
         overlap_prepass: bool = False,
         grid_dtype=None,
+        differentiable: bool = False,
         **kwargs,
     ):
         super().__init__(resolution, dimension, radii_type, density_type, **kwargs)
         assert precision in [32, 64]
         assert output in ("torch", "numpy")
+        if differentiable and output != "torch":
+            raise ValueError("differentiable=True needs output='torch': gradients flow through torch tensors")
+        self.differentiable = bool(differentiable)
         self._bf16 = self._is_bf16_grid(grid_dtype, precision, output)  # (checked before anything touches a device)
         if output == "torch" and torch is None:
             raise ImportError("output='torch' needs PyTorch; use output='numpy'")
@@ -200,7 +206,7 @@ class Voxelizer(BaseVoxelizer):
             kw = {"sigma": self._sigma} if self.is_density_type_gaussian else {}
             return type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
                               self.blockdim, idx, self.output, self.overlap_prepass,
-                              grid_dtype="bfloat16" if self._bf16 else None, **kw)
+                              grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable, **kw)
         return self
 
     def cuda(self):
@@ -339,13 +345,19 @@ class Voxelizer(BaseVoxelizer):
         """coords (V,3), center (3,) | None, features (V,C), radii scalar | (V,) | (C,); out (C,D,H,W)."""
         self._check_args_features(coords, features, radii, out_grid)
         C_ = features.shape[1]
+        grad = self._grad_wanted(coords, features, center, radii, out_grid)
         c, f, r, in_kind, keep = self._prepare_inputs(coords, features, "features", radii)
+        center = self._grad_center(center) if grad else center
         xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
         buf, out_kind, ret, how = self._resolve_out(out_grid, (C_,))
         rs = float(radii) if r is None else 0.0
-        rc = self._lib.mvx_forward_features(
+        launch = lambda: self._lib.mvx_forward_features(  # noqa: E731
             self._handle, self._ptr(c), self._ptr(f), self._ptr(r), rs, self._radii_type_code(), c.shape[0], C_,
             xf, self._ptr(buf), in_kind, out_kind, self._stream())
+        if grad:
+            return self._autograd(launch, ret, "features", c, f, center, None, r, rs, np.array([0, c.shape[0]], np.int64),
+                                  self._xform_copy(xf), 1, C_)
+        rc = launch()
         if rc:
             _lib.check(rc)
         return self._finish_out(buf, ret, how) if how else ret
@@ -379,17 +391,23 @@ class Voxelizer(BaseVoxelizer):
             C_ = radii.shape[0]  # numpy/voxelizer.py:275-276
         else:
             C_ = n_types  # max(types) + 1 over ALL atoms, numpy/voxelizer.py:278
+        grad = self._grad_wanted(coords, None, center, radii, out_grid)
         c, t, r, in_kind, keep = self._prepare_inputs(coords, types, "types", radii)
         if self.is_radii_type_channel_wise and r is not None and r.shape[0] < C_:
             # channel-wise radii are indexed by type only; pad so the (C,) contract of the ABI holds
             pad = C_ - r.shape[0]
             r = torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])
+        center = self._grad_center(center) if grad else center
         xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
         buf, out_kind, ret, how = self._resolve_out(out_grid, (C_,))
         rs = float(radii) if r is None else 0.0
-        rc = self._lib.mvx_forward_types(
+        launch = lambda: self._lib.mvx_forward_types(  # noqa: E731
             self._handle, self._ptr(c), self._ptr(t), self._ptr(r), rs, self._radii_type_code(), c.shape[0], int(C_),
             xf, self._ptr(buf), in_kind, out_kind, self._stream())
+        if grad:
+            return self._autograd(launch, ret, "types", c, None, center, t, r, rs, np.array([0, c.shape[0]], np.int64),
+                                  self._xform_copy(xf), 1, int(C_))
+        rc = launch()
         if rc:
             _lib.check(rc)
         return self._finish_out(buf, ret, how) if how else ret
@@ -445,13 +463,19 @@ class Voxelizer(BaseVoxelizer):
     def forward_single(self, coords, center, radii, random_translation=0.0, random_rotation=False, out_grid=None):
         """coords (V,3), center (3,) | None, radii scalar | (V,); out (1,D,H,W)."""
         self._check_args_single(coords, radii, out_grid)
+        grad = self._grad_wanted(coords, None, center, radii, out_grid)
         c, _, r, in_kind, keep = self._prepare_inputs(coords, None, None, radii)
+        center = self._grad_center(center) if grad else center
         xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
         buf, out_kind, ret, how = self._resolve_out(out_grid, (1,))
         rs = float(radii) if r is None else 0.0
-        rc = self._lib.mvx_forward_single(
+        launch = lambda: self._lib.mvx_forward_single(  # noqa: E731
             self._handle, self._ptr(c), self._ptr(r), rs, self._radii_type_code(), c.shape[0],
             xf, self._ptr(buf), in_kind, out_kind, self._stream())
+        if grad:
+            return self._autograd(launch, ret, "single", c, None, center, None, r, rs, np.array([0, c.shape[0]], np.int64),
+                                  self._xform_copy(xf), 1, 1)
+        rc = launch()
         if rc:
             _lib.check(rc)
         return self._finish_out(buf, ret, how) if how else ret
@@ -493,6 +517,10 @@ class Voxelizer(BaseVoxelizer):
         else:
             kind, C_ = "features", channels.shape[1]
         self._check_args_batch(coords, channels, kind, radii, int(C_))
+        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers, radii, out_grid)
+        user_centers = centers  # (a conversion made below, for autograd or for the ABI, is "fresh")
+        if grad and centers is not None:
+            centers = self._grad_center(centers)
         c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
         # With overlap_prepass the library's side stream reads the inputs without waiting for the caller's stream.
         # Arrays this layer had to convert just now (dtype / layout fixes, the int32 copy of `types`) were produced
@@ -508,6 +536,7 @@ class Voxelizer(BaseVoxelizer):
             fresh = fresh or self.overlap_prepass
         need_xf = centers is not None or random_rotation or (random_translation and random_translation > 0.0)
         xf_ptr = None
+        dev_cen = None
         if need_xf:
             xfs = (_lib.MvxXform * B)()
             cen = dev_cen = None
@@ -515,7 +544,7 @@ class Voxelizer(BaseVoxelizer):
                 if in_kind == _lib.MVX_DEVICE and self._on_device(centers):  # by pointer: no copy to the host
                     dev_cen = centers.to(torch.float64).contiguous().reshape(B, 3)
                     keep.append(dev_cen)
-                    fresh = fresh or (self.overlap_prepass and dev_cen.data_ptr() != centers.data_ptr())
+                    fresh = fresh or (self.overlap_prepass and dev_cen.data_ptr() != user_centers.data_ptr())
                 else:
                     cen = centers.detach().cpu().numpy() if _is_torch(centers) else np.asarray(centers)
                     cen = cen.reshape(B, 3)
@@ -537,18 +566,23 @@ class Voxelizer(BaseVoxelizer):
         off_ptr = offsets.ctypes.data
         rt = self._radii_type_code()
         if kind == "features":
-            rc = self._lib.mvx_forward_features_batch(self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt,
-                                                      off_ptr, xf_ptr, B, int(C_), self._ptr(buf), in_kind, out_kind,
-                                                      self._stream())
+            launch = lambda: self._lib.mvx_forward_features_batch(  # noqa: E731
+                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, int(C_),
+                self._ptr(buf), in_kind, out_kind, self._stream())
         elif kind == "types":
-            rc = self._lib.mvx_forward_types_batch(self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt,
-                                                   off_ptr, xf_ptr, B, int(C_), self._ptr(buf), in_kind, out_kind,
-                                                   self._stream())
+            launch = lambda: self._lib.mvx_forward_types_batch(  # noqa: E731
+                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, int(C_),
+                self._ptr(buf), in_kind, out_kind, self._stream())
         else:
             assert not self.is_radii_type_channel_wise, "Channel-Wise Radii Type is not supported"
-            rc = self._lib.mvx_forward_single_batch(self._handle, self._ptr(c), self._ptr(r), rs, rt, off_ptr, xf_ptr,
-                                                    B, self._ptr(buf), in_kind, out_kind, self._stream())
-        _lib.check(rc)
+            launch = lambda: self._lib.mvx_forward_single_batch(  # noqa: E731
+                self._handle, self._ptr(c), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, self._ptr(buf), in_kind, out_kind,
+                self._stream())
+        if grad:
+            return self._autograd(launch, ret, kind or "single", c, ch if kind == "features" else None,
+                                  dev_cen, ch if kind == "types" else None, r, rs, offsets,
+                                  xfs if need_xf else None, B, int(C_))
+        _lib.check(launch())
         return self._finish_out(buf, ret, how)
 
     def _check_args_batch(self, coords, channels, kind, radii, C_):
@@ -578,6 +612,61 @@ class Voxelizer(BaseVoxelizer):
             assert tuple(radii.shape) == (V,), f"radii does not match dimension (number of atoms,): {tuple(radii.shape)} vs {(V,)}"
 
     # ------------------------------------------------------------------------------------------
+    # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
+    def _grad_wanted(self, coords, features, center, radii, out_grid) -> bool:
+        """True when this call must record an autograd graph: differentiable voxelizer, grad mode on, and coords / features /
+        center a tensor that requires grad. Raises for what the backward pass does not cover."""
+        if not self.differentiable or torch is None or not torch.is_grad_enabled():
+            return False
+        if _is_torch(radii) and radii.requires_grad:
+            raise NotImplementedError("gradients with respect to radii are not supported")
+        tracked = [x for x in (coords, features, center) if _is_torch(x) and x.requires_grad]
+        if not tracked:
+            return False
+        for x in tracked + [coords]:
+            if not self._on_device(x):
+                raise NotImplementedError(
+                    f"differentiable calls need coords and every tensor that requires grad on this voxelizer's device "
+                    f"({self.device}); move them there first (got {getattr(x, 'device', 'a host array')})")
+        if out_grid is not None:
+            raise ValueError("out_grid cannot be combined with a recorded autograd graph: let the call allocate the grid")
+        return True
+
+    def _grad_center(self, center):
+        """A device centre as the call hands it to the library (float64, contiguous); the conversion is recorded by autograd."""
+        if self._on_device(center) and not (center.dtype == torch.float64 and center.is_contiguous()):
+            return center.to(torch.float64).contiguous()
+        return center
+
+    @staticmethod
+    def _xform_copy(xf):
+        """The mvx_xform record of a single-molecule call (the voxelizer reuses its own), or None."""
+        return None if xf is None else _lib.MvxXform.from_buffer_copy(_lib.MvxXform.from_address(xf))
+
+    def _autograd(self, launch, ret, mode, c, f, center, types, r, rs, offsets, xforms, B, C_):
+        cen = center if (_is_torch(center) and self._on_device(center)) else None
+        spec = dict(mode=mode, types=types, radii=r, rs=rs, offsets=np.ascontiguousarray(offsets, np.int64), xforms=xforms,
+                    B=B, C=C_)
+        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen)
+
+    def _backward(self, spec, c, f, grad, need_features):
+        """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None) for dL/dgrid = grad, on the current stream."""
+        g = grad.to(device=self.device, dtype=self._gdt).contiguous()
+        gc = torch.empty((c.shape[0], 3), dtype=torch.float64, device=self.device)
+        gf = torch.empty((c.shape[0], spec["C"]), dtype=self._tfp, device=self.device) if need_features else None
+        if c.shape[0] == 0:  # no atoms: no gradient rows (the library would see null outputs)
+            return gc, gf
+        mode = spec["mode"]
+        ch = f if mode == "features" else spec["types"]
+        xf = spec["xforms"]
+        rc = self._lib.mvx_backward_batch(
+            self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(spec["radii"]), spec["rs"],
+            self._radii_type_code(), spec["offsets"].ctypes.data, None if xf is None else C.addressof(xf), spec["B"],
+            spec["C"], self._ptr(g), self._ptr(gc), self._ptr(gf), self._stream())
+        _lib.check(rc)
+        return gc, gf
+
+    # ------------------------------------------------------------------------------------------
     # measurement hooks used by bench.py (HIP events around the voxelize kernel on the launch stream)
     def debug_option(self, name: str, value: int):
         """Testing aid (mvx_debug_set_option): force code paths production sizes rarely reach."""
@@ -603,6 +692,35 @@ class Voxelizer(BaseVoxelizer):
         from .transform import do_random_transform
 
         return do_random_transform(coords, center, random_translation, random_rotation)
+
+
+if torch is not None:
+
+    class _VoxelizeFunction(torch.autograd.Function):
+        """grid = voxelize(coords, features, center): the forward call as it runs without autograd (same kernels, same
+        bits); backward = mvx_backward_batch from the saved inputs and the call's mvx_xform records."""
+
+        @staticmethod
+        def forward(ctx, vox, launch, ret, spec, c, f, cen):
+            _lib.check(launch())
+            ctx.vox, ctx.spec = vox, spec
+            ctx.save_for_backward(c, f, cen)
+            return ret
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad):
+            c, f, cen = ctx.saved_tensors
+            need_c, need_f, need_cen = ctx.needs_input_grad[4:7]
+            gc, gf = ctx.vox._backward(ctx.spec, c, f, grad, need_f)
+            gcen = None
+            if need_cen:  # p = M (coords - center) + t: dL/dcenter = -sum of dL/dcoords over the molecule
+                if cen.numel() == 3:
+                    gcen = -gc.sum(0).reshape(cen.shape)
+                else:
+                    lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
+                    gcen = -torch.segment_reduce(gc, "sum", lengths=lengths, axis=0).reshape(cen.shape)
+            return None, None, None, None, gc if need_c else None, gf, gcen
 
 
 def transform_on_device(coords, center, translation, quaternion):
