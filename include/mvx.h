@@ -202,7 +202,7 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const mvx_real *radi
  * gradients are those of a density that may differ from the stored grid in the last ulp.
  * Derivative almost everywhere: the jump of rho at the truncation radius is ignored, so binary density gives zero coordinate
  * gradients. The gradient with respect to a centre is -sum of dL/dcoords over the molecule (no MVX_XF_RECENTER: the caller
- * reduces it). No gradients with respect to radii or sigma.
+ * reduces it). No gradients with respect to radii (mvx_backward_radii_batch gives them) or sigma.
  * Outputs are fully overwritten (atoms that reach no voxel get exact zeros) and deterministic: no atomics, fixed-order
  * reductions; a molecule's gradients are bit for bit the same in any batch. Arguments as in the forward entries (same
  * offsets / xforms / radii: the pre-pass is recomputed from them, nothing is kept from the forward call).
@@ -219,6 +219,26 @@ int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const 
                        double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
                        int32_t B, int32_t C, const void *grad_out, double *grad_coords, mvx_real *grad_features,
                        void *stream);
+
+/*
+ * mvx_backward_batch plus the gradient with respect to the radii, in one walk: grad_coords / grad_features are the bits
+ * mvx_backward_batch writes (either or both may be NULL here), and
+ *   grad_radii: double, shaped like the radii array: (sumN,) for MVX_RADII_ATOM, (C,) for MVX_RADII_CHANNEL.
+ * With kfac = 2 ln2 k (float32 arithmetic; float64 grids: 2 c) and k, c proportional to r^-2, d rho / d r = -(kfac / r) d2 rho:
+ *   one radius per atom   dL/dr_n = -(1/r_n) sum_v (sum_c G[c,v] w[n,c] rho_{n,c}(v)) kfac_n d2_n(v)       (every mode)
+ *   channel-wise, types   dL/dr_c = the same per-atom term summed over the atoms of type c (types >= C: none)
+ *   channel-wise, feat.   dL/dr_c = -(kfac_c / r_c) sum_n w[n,c] sum_v G[c,v] rho_{n,c}(v) d2_n(v)
+ * r is the value the forward used (the element of radii, widened to double). Channel-wise sums run over every atom of the
+ * call, all molecules (one radius vector serves the batch), in a fixed order without atomics: deterministic. Binary density:
+ * zeros. Not differentiated: the jump of m at the truncation threshold and the culls that depend on r (almost everywhere,
+ * as for the coordinates). Channel-wise radii use handle-owned workspace of 8 bytes per atom (types) or per atom and
+ * channel (features). MVX_ERR_INVALID before any device is touched for what mvx_backward_batch rejects (except that
+ * grad_coords and grad_features may both be NULL), a NULL grad_radii, scalar radii and channel-wise radii in single mode.
+ */
+int mvx_backward_radii_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                             double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                             int32_t B, int32_t C, const void *grad_out, double *grad_coords, mvx_real *grad_features,
+                             double *grad_radii, void *stream);
 
 /*
  * Replaces do_transform on an (N,3) fp64 point cloud (numpy/transform.py:44-60): out = transformed coords.

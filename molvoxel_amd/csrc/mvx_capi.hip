@@ -97,6 +97,7 @@ struct mvx_handle {
     // the backward pass (mvx_backward_batch) keeps buffers of its own: it never writes a workspace set that an overlapped
     // pre-pass (mvx_set_overlap) on the side stream may be filling, nor one that voxelize launches may still read
     DevBuf grad_rec, grad_xp, grad_meta, grad_aux, grad_sort;
+    DevBuf grad_rpart; // radius gradients: per-atom / per-(channel, atom) partials of channel-wise radii and their stage sums
     // "grad_order" option: 0 atoms in the caller's order (the default), 1 in spatial order, XCD by XCD. The spatial order cuts
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
     // more than it saves (profiles/r05_grad.txt)
@@ -740,7 +741,7 @@ int mvx_destroy(mvx_handle *h) {
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
     std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage,
-                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort};
+                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart};
     for (Workspace &w : h->ws) {
         for (DevBuf *b : {&w.rec, &w.wbuf, &w.xp, &w.xlist, &w.slist, &w.meta, &w.aux}) bufs.push_back(b);
         if (w.ev_pre) (void)hipEventDestroy(w.ev_pre);
@@ -829,15 +830,25 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const void *radii, d
                                     out_kind, stream);
 }
 
-int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
-                       double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
-                       int32_t C, const void *grad_out, double *grad_coords, void *grad_features, void *stream) {
+// mvx_backward_batch (with_radii false) and mvx_backward_radii_batch (with_radii true: grad_radii as well)
+static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                         double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
+                         int32_t C, const void *grad_out, double *grad_coords, void *grad_features, bool with_radii,
+                         double *grad_radii, void *stream) {
     // ---- what is checked before any device is touched ----
     if (mode < MODE_FEATURES || mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
     if (grad_features && mode != MODE_FEATURES) return fail(MVX_ERR_INVALID, "grad_features exists in features mode only");
     if (C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
     if (mode == MODE_SINGLE && C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
-    if (!grad_coords && !grad_features) return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
+    if (with_radii) { // (grad_coords and grad_features may both be null: grad_radii is an output)
+        if (!grad_radii) return fail(MVX_ERR_INVALID, "grad_radii must not be null");
+        if (radii_type == MVX_RADII_SCALAR)
+            return fail(MVX_ERR_INVALID, "radii_type: scalar radii have no radius array for grad_radii (atom-wise or channel-wise radii only)");
+        if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE)
+            return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode (no grad_radii)");
+    } else if (!grad_coords && !grad_features) {
+        return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
+    }
     if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
     if (radii_type < MVX_RADII_SCALAR || radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
     if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
@@ -847,8 +858,19 @@ int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const 
         if (offsets[b + 1] < offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
     const int64_t total = B > 0 ? offsets[B] : 0;
-    if (total == 0) return MVX_OK; // (no atoms: no gradient rows)
+    // (no atoms: no gradient rows; channel-wise radii still get their C zeros)
+    const bool radii_by_channel = with_radii && radii_type == MVX_RADII_CHANNEL;
+    if (total == 0 && !radii_by_channel) return MVX_OK;
     if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (total == 0) {
+        DeviceGuard guard(h->device);
+        if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        int rc = adopt_stream(h, s);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)C * sizeof(double), s));
+        return MVX_OK;
+    }
     if (!coords || !grad_out) return fail(MVX_ERR_INVALID, "coords / grad_out must not be null");
     if (mode != MODE_SINGLE && !channels) return fail(MVX_ERR_INVALID, "channels must not be null");
     if (!radii && radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
@@ -935,10 +957,50 @@ int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const 
     ga.D = h->g.D;
     ga.res = h->g.res;
     ga.half = h->g.half;
-    HIP_TRY(launch_grad(ga, mode, bf16 ? 1 : (f64 ? 2 : 0), gauss, chanwise, s));
+    const int32_t grid_kind = bf16 ? 1 : (f64 ? 2 : 0);
+    if (!with_radii) {
+        HIP_TRY(launch_grad(ga, mode, grid_kind, gauss, chanwise, s));
+    } else if (!gauss) { // binary density: zero radius gradients (the a.e. derivative), the walk for the other outputs only
+        HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)(radii_type == MVX_RADII_CHANNEL ? C : total) * sizeof(double), s));
+        if (grad_coords || grad_features) HIP_TRY(launch_grad(ga, mode, grid_kind, gauss, chanwise, s));
+    } else {
+        // radius partials: straight into grad_radii (one radius per atom), or per atom / per (channel, atom) into grad_rpart
+        // and reduced over all atoms of the call in a fixed order (channel-wise radii: one radius vector for the batch)
+        RadiiArgs ra;
+        ra.radii = radii;
+        ra.grad_radii = grad_radii;
+        ra.part = nullptr;
+        double *stage = nullptr;
+        if (radii_type == MVX_RADII_CHANNEL) {
+            const size_t npart = chanwise ? (size_t)C * (size_t)total : (size_t)total;
+            const size_t part_bytes = align_up(npart * sizeof(double), 256);
+            if ((rc = ensure(h->grad_rpart, part_bytes + grad_radii_stage_doubles(total, C) * sizeof(double)))) return rc;
+            ra.part = reinterpret_cast<double *>(h->grad_rpart.p);
+            stage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes);
+        }
+        HIP_TRY(launch_grad_radii(ga, ra, mode, grid_kind, chanwise, s));
+        if (radii_type == MVX_RADII_CHANNEL)
+            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(channels), radii,
+                                             chanwise ? d_kc : nullptr, f64, total, C, stage, grad_radii, s));
+    }
     HIP_TRY(hipEventRecord(slot->done, s));
     slot->in_flight = true;
     return MVX_OK;
+}
+
+int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                       double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
+                       int32_t C, const void *grad_out, double *grad_coords, void *grad_features, void *stream) {
+    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
+                         grad_features, false, nullptr, stream);
+}
+
+int mvx_backward_radii_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                             double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
+                             int32_t C, const void *grad_out, double *grad_coords, void *grad_features, double *grad_radii,
+                             void *stream) {
+    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
+                         grad_features, true, grad_radii, stream);
 }
 
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,

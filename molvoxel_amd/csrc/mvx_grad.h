@@ -21,6 +21,14 @@ struct GradArgs {
     double res, half;
 };
 
+// radius gradients (mvx_backward_radii_batch, grad_radii_kernel): where the walk puts its radius partials
+struct RadiiArgs {
+    const void *radii;  // the call's radii array (real): atom-wise radii, read by the per-atom write
+    double *grad_radii; // one radius per atom: (total,) dL/dr, written by the walk itself
+    double *part;       // or the partials grad_radii_reduce sums: (total,) per atom (types mode, radii by type) or
+                        // (C, total) channel-major per (channel, atom) (features, channel-wise radii)
+};
+
 // channel-wise radii for features: rmax[0] = max(radii) (what prep_kernel culls with), per-channel thresholds Tc and
 // coefficients kc (float, or double for f64), from the forward's d2_threshold / gauss_coeff (float64: their *64 forms)
 hipError_t launch_grad_chan(const void *radii, int32_t C, bool f64, bool gauss, float sigma32, double sigma64, void *rmax, double *Tc,
@@ -31,5 +39,14 @@ hipError_t launch_grad_order(const AtomRec *rec, const int64_t *offsets, int B, 
                              const uint32_t **order, hipStream_t s);
 // grid_kind: 0 float, 1 bfloat16, 2 double. mode: Mode (single: the records carry type 0). One wave per atom record.
 hipError_t launch_grad(const GradArgs &a, int32_t mode, int32_t grid_kind, bool gauss, bool chanwise, hipStream_t s);
+// The same walk with the radius partials (Gaussian density only: a binary density has zero radius gradients), in one pass
+// with the coordinate and feature gradients, which are grad_kernel's bits.
+hipError_t launch_grad_radii(const GradArgs &a, const RadiiArgs &r, int32_t mode, int32_t grid_kind, bool chanwise, hipStream_t s);
+// Channel-wise radii: dL/dr_c from RadiiArgs::part in a fixed order (no atomics). types: the atoms' (total,) partials of type c,
+// scaled by -1/r_c; else the (C, total) partials, scaled by -(kfac_c / r_c) with kc from launch_grad_chan. `stage` holds
+// grad_radii_stage_doubles(total, C) doubles.
+size_t grad_radii_stage_doubles(int64_t total, int32_t C);
+hipError_t launch_grad_radii_reduce(const double *part, const int32_t *types, const void *radii, const void *kc, bool f64, int64_t total,
+                                    int32_t C, double *stage, double *grad_radii, hipStream_t s);
 
 } // namespace mvx

@@ -14,7 +14,9 @@ in HBM; pass `output="numpy"` (or a numpy `out_grid`) for host arrays. `grid_dty
 kernels write bfloat16 grids directly: the float32 grid rounded to nearest even as it is stored, bit for bit
 what `.to(torch.bfloat16)` of the float32 grid gives, at half the bytes. `differentiable=True` makes grids computed from device
 tensors that require grad (`coords`, `features`, `center`) part of the autograd graph: the backward pass runs on the GPU
-(mvx_backward_batch) and returns gradients with respect to those tensors.
+(mvx_backward_batch) and returns gradients with respect to those tensors. `radii_grad=True` (with `differentiable=True`)
+adds a radii tensor that requires grad to them (mvx_backward_radii_batch, atom-wise or channel-wise radii); scalar radii stay
+python floats without gradient: learn a single radius as `r.expand(N)` on an atom-wise voxelizer.
 """
 from __future__ import annotations
 
@@ -63,6 +65,7 @@ class Voxelizer(BaseVoxelizer):
         overlap_prepass: bool = False,
         grid_dtype=None,
         differentiable: bool = False,
+        radii_grad: bool = False,
         **kwargs,
     ):
         super().__init__(resolution, dimension, radii_type, density_type, **kwargs)
@@ -70,7 +73,10 @@ class Voxelizer(BaseVoxelizer):
         assert output in ("torch", "numpy")
         if differentiable and output != "torch":
             raise ValueError("differentiable=True needs output='torch': gradients flow through torch tensors")
+        if radii_grad and not differentiable:
+            raise ValueError("radii_grad=True needs differentiable=True: radius gradients are part of the autograd graph")
         self.differentiable = bool(differentiable)
+        self.radii_grad = bool(radii_grad)
         self._bf16 = self._is_bf16_grid(grid_dtype, precision, output)  # (checked before anything touches a device)
         if output == "torch" and torch is None:
             raise ImportError("output='torch' needs PyTorch; use output='numpy'")
@@ -206,7 +212,8 @@ class Voxelizer(BaseVoxelizer):
             kw = {"sigma": self._sigma} if self.is_density_type_gaussian else {}
             return type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
                               self.blockdim, idx, self.output, self.overlap_prepass,
-                              grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable, **kw)
+                              grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
+                              radii_grad=self.radii_grad, **kw)
         return self
 
     def cuda(self):
@@ -615,12 +622,13 @@ class Voxelizer(BaseVoxelizer):
     # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
     def _grad_wanted(self, coords, features, center, radii, out_grid) -> bool:
         """True when this call must record an autograd graph: differentiable voxelizer, grad mode on, and coords / features /
-        center a tensor that requires grad. Raises for what the backward pass does not cover."""
+        center (or, with radii_grad, radii) a tensor that requires grad. Raises for what the backward pass does not cover."""
         if not self.differentiable or torch is None or not torch.is_grad_enabled():
             return False
-        if _is_torch(radii) and radii.requires_grad:
-            raise NotImplementedError("gradients with respect to radii are not supported")
-        tracked = [x for x in (coords, features, center) if _is_torch(x) and x.requires_grad]
+        if _is_torch(radii) and radii.requires_grad and not self.radii_grad:
+            raise NotImplementedError("gradients with respect to radii are not supported unless the voxelizer is created with "
+                                      "radii_grad=True")
+        tracked = [x for x in (coords, features, center, radii) if _is_torch(x) and x.requires_grad]
         if not tracked:
             return False
         for x in tracked + [coords]:
@@ -645,26 +653,34 @@ class Voxelizer(BaseVoxelizer):
 
     def _autograd(self, launch, ret, mode, c, f, center, types, r, rs, offsets, xforms, B, C_):
         cen = center if (_is_torch(center) and self._on_device(center)) else None
+        # radii_grad: the radii as the call hands them to the library (dtype conversion / type padding recorded by autograd)
+        rin = r if (self.radii_grad and _is_torch(r) and r.requires_grad) else None
         spec = dict(mode=mode, types=types, radii=r, rs=rs, offsets=np.ascontiguousarray(offsets, np.int64), xforms=xforms,
                     B=B, C=C_)
-        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen)
+        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen, rin)
 
-    def _backward(self, spec, c, f, grad, need_features):
-        """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None) for dL/dgrid = grad, on the current stream."""
+    def _backward(self, spec, c, f, grad, need_features, need_radii=False):
+        """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None, dL/dradii shaped and typed like the call's radii or None)
+        for dL/dgrid = grad, on the current stream."""
         g = grad.to(device=self.device, dtype=self._gdt).contiguous()
         gc = torch.empty((c.shape[0], 3), dtype=torch.float64, device=self.device)
         gf = torch.empty((c.shape[0], spec["C"]), dtype=self._tfp, device=self.device) if need_features else None
-        if c.shape[0] == 0:  # no atoms: no gradient rows (the library would see null outputs)
-            return gc, gf
+        r = spec["radii"]
+        gr = torch.zeros(r.shape[0], dtype=torch.float64, device=self.device) if need_radii else None
+        if c.shape[0] == 0:  # no atoms: no gradient rows (the library would see null outputs); channel-wise radii get zeros
+            return gc, gf, None if gr is None else gr.to(r.dtype)
         mode = spec["mode"]
         ch = f if mode == "features" else spec["types"]
         xf = spec["xforms"]
-        rc = self._lib.mvx_backward_batch(
-            self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(spec["radii"]), spec["rs"],
-            self._radii_type_code(), spec["offsets"].ctypes.data, None if xf is None else C.addressof(xf), spec["B"],
-            spec["C"], self._ptr(g), self._ptr(gc), self._ptr(gf), self._stream())
+        args = (self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), spec["rs"],
+                self._radii_type_code(), spec["offsets"].ctypes.data, None if xf is None else C.addressof(xf), spec["B"],
+                spec["C"], self._ptr(g), self._ptr(gc), self._ptr(gf))
+        if gr is None:
+            rc = self._lib.mvx_backward_batch(*args, self._stream())
+        else:  # one walk: the same coordinate / feature bits as mvx_backward_batch, and dL/dradii
+            rc = self._lib.mvx_backward_radii_batch(*args, self._ptr(gr), self._stream())
         _lib.check(rc)
-        return gc, gf
+        return gc, gf, None if gr is None else gr.to(r.dtype)
 
     # ------------------------------------------------------------------------------------------
     # measurement hooks used by bench.py (HIP events around the voxelize kernel on the launch stream)
@@ -697,11 +713,11 @@ class Voxelizer(BaseVoxelizer):
 if torch is not None:
 
     class _VoxelizeFunction(torch.autograd.Function):
-        """grid = voxelize(coords, features, center): the forward call as it runs without autograd (same kernels, same
+        """grid = voxelize(coords, features, center, radii): the forward call as it runs without autograd (same kernels, same
         bits); backward = mvx_backward_batch from the saved inputs and the call's mvx_xform records."""
 
         @staticmethod
-        def forward(ctx, vox, launch, ret, spec, c, f, cen):
+        def forward(ctx, vox, launch, ret, spec, c, f, cen, r):
             _lib.check(launch())
             ctx.vox, ctx.spec = vox, spec
             ctx.save_for_backward(c, f, cen)
@@ -711,8 +727,8 @@ if torch is not None:
         @torch.autograd.function.once_differentiable
         def backward(ctx, grad):
             c, f, cen = ctx.saved_tensors
-            need_c, need_f, need_cen = ctx.needs_input_grad[4:7]
-            gc, gf = ctx.vox._backward(ctx.spec, c, f, grad, need_f)
+            need_c, need_f, need_cen, need_r = ctx.needs_input_grad[4:8]
+            gc, gf, gr = ctx.vox._backward(ctx.spec, c, f, grad, need_f, need_r)
             gcen = None
             if need_cen:  # p = M (coords - center) + t: dL/dcenter = -sum of dL/dcoords over the molecule
                 if cen.numel() == 3:
@@ -720,7 +736,7 @@ if torch is not None:
                 else:
                     lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
                     gcen = -torch.segment_reduce(gc, "sum", lengths=lengths, axis=0).reshape(cen.shape)
-            return None, None, None, None, gc if need_c else None, gf, gcen
+            return None, None, None, None, gc if need_c else None, gf, gcen, gr
 
 
 def transform_on_device(coords, center, translation, quaternion):

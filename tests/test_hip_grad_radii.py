@@ -1,0 +1,397 @@
+"""Radius gradients on the GPU (radii_grad=True, mvx_backward_radii_batch): atom-wise and channel-wise dL/dradii against
+per-atom densities from the CPU oracle, finite differences at precision 64, the other gradients unchanged bit for bit,
+determinism, batch independence, processing order and the autograd plumbing (dtype, expand, padded channel radii)."""
+import numpy as np
+import pytest
+
+from tests.test_hip_grad import LN2, _axis, _close, _k32, _molecule, _rho
+
+pytestmark = pytest.mark.gpu
+
+
+def _vox(D, radii_type="atom-wise", density="gaussian", radii_grad=True, **kw):
+    import molvoxel_amd as mv
+
+    return mv.create_voxelizer(0.5, D, radii_type, density, library="hip", differentiable=True, radii_grad=radii_grad, **kw)
+
+
+def _d2(xyz, n, D):
+    ax = _axis(D)
+    return ((xyz[n, 0] - ax[:, None, None]) ** 2 + (xyz[n, 1] - ax[None, :, None]) ** 2) + (xyz[n, 2] - ax[None, None, :]) ** 2
+
+
+def _ref_radii(xyz, w, radii, radii_type, G, D, density, blockdim, types=None):
+    """numpy float64 reference of dL/dradii and a bound on sum|terms| (float32 coefficients, as precision 32 evaluates them).
+    w: (N, C) channel weights (features, or one-hot types). radii_type "atom-wise": (N,); "channel-wise": (C,) for features,
+    or with `types` the radius of each atom's type."""
+    N, C_ = xyz.shape[0], G.shape[0]
+    if radii_type == "channel-wise" and types is None:
+        g, b = np.zeros(C_), np.zeros(C_)
+        for n in range(N):
+            rho = _rho(xyz, n, radii, "channel-wise", C_, D, density, blockdim)
+            t = (G * rho).reshape(C_, -1) * _d2(xyz, n, D).reshape(1, -1) * w[n][:, None]
+            g += t.sum(1)
+            b += np.abs(t).sum(1)
+        if density != "gaussian":
+            return np.zeros(C_), b
+        s = np.array([2 * LN2 * _k32(r) / float(np.float32(r)) for r in radii])
+        return -s * g, np.abs(s) * b
+    rad = np.asarray(radii, np.float32)
+    atom_r = rad if types is None else np.array([rad[t] if t < len(rad) else 1.0 for t in types], np.float32)
+    g, b = np.zeros(N), np.zeros(N)
+    if density == "gaussian":
+        for n in range(N):
+            if types is not None and types[n] >= len(rad):
+                continue
+            rho = _rho(xyz, n, atom_r, "atom-wise", C_, D, density, blockdim)[0]
+            r = float(atom_r[n])
+            e = (G * w[n][:, None, None, None]).sum(0) * rho * (2 * LN2 * _k32(r))
+            t = e * _d2(xyz, n, D) / r
+            g[n], b[n] = -t.sum(), np.abs(t).sum()
+    if types is None:
+        return g, b
+    gc, bc = np.zeros(len(rad)), np.zeros(len(rad))
+    for n, t in enumerate(types):
+        if t < len(rad):
+            gc[t] += g[n]
+            bc[t] += b[n]
+    return gc, bc
+
+
+def _onehot(types, C_):
+    w = np.zeros((len(types), C_))
+    for n, t in enumerate(types):
+        if t < C_:
+            w[n, t] = 1.0
+    return w
+
+
+CASES = [  # radii_type, density, D, blockdim, C
+    ("atom-wise", "gaussian", 20, 6, 5), ("atom-wise", "gaussian", 17, 8, 40), ("atom-wise", "binary", 20, 8, 5),
+    ("channel-wise", "gaussian", 20, 6, 5), ("channel-wise", "gaussian", 18, 8, 8), ("channel-wise", "gaussian", 17, 6, 71),
+    ("channel-wise", "binary", 20, 8, 8),
+]
+
+
+@pytest.mark.parametrize("radii_type, density, D, blockdim, C_", CASES)
+def test_feature_mode_radius_gradients_match_the_oracle(radii_type, density, D, blockdim, C_):
+    import torch
+
+    N = 22
+    rng, xyz, feats = _molecule(21, N, D, C_)
+    if radii_type == "atom-wise":
+        radii = rng.uniform(0.8, 2.0, N).astype(np.float32)
+    else:
+        radii = rng.choice([0.9, 1.4, 2.0], C_).astype(np.float32)
+        if C_ > 32:
+            radii[40] = 2.3  # the largest radius (the cull's) only in the second chunk
+    G = rng.standard_normal((C_, D, D, D)).astype(np.float32)
+    vox = _vox(D, radii_type, density, blockdim=blockdim)
+    c = torch.tensor(xyz, device="cuda", requires_grad=True)
+    r = torch.tensor(radii, device="cuda", requires_grad=True)
+    grid = vox.forward_features(c, None, torch.tensor(feats, device="cuda"), r)
+    (grid.double() * torch.as_tensor(G, device="cuda")).sum().backward()
+    assert r.grad is not None and r.grad.dtype == torch.float32 and tuple(r.grad.shape) == radii.shape
+    want, bound = _ref_radii(xyz, feats.astype(np.float64), radii, radii_type, G.astype(np.float64), D, density, blockdim)
+    got = r.grad.double().cpu().numpy()
+    if density == "binary":
+        assert not np.any(got)
+    else:
+        assert np.any(got)
+        _close(got, want, bound, "dL/dradii")
+
+
+@pytest.mark.parametrize("radii_type, blockdim", [("atom-wise", 8), ("channel-wise", 6), ("channel-wise", 8)])
+def test_types_mode_radius_gradients_match_the_oracle(radii_type, blockdim):
+    import torch
+
+    D, N, C_ = 21, 30, 5
+    rng, xyz, _ = _molecule(22, N, D, C_)
+    types = rng.integers(0, C_, N)
+    if radii_type == "atom-wise":
+        types[3] = C_ + 2  # beyond the channels of the call: no density, no gradient
+        radii = rng.uniform(0.8, 2.0, N).astype(np.float32)
+    else:
+        radii = rng.choice([1.0, 1.3, 1.7], C_).astype(np.float32)
+    G = rng.standard_normal((C_, D, D, D)).astype(np.float32)
+    vox = _vox(D, radii_type, blockdim=blockdim)
+    c = torch.tensor(xyz, device="cuda", requires_grad=True)
+    r = torch.tensor(radii, device="cuda", requires_grad=True)
+    grid = vox.forward_batch(c, np.array([0, N]), None, torch.tensor(types, device="cuda"), r, num_channels=C_)[0]
+    (grid * torch.as_tensor(G, device="cuda")).sum().backward()
+    want, bound = _ref_radii(xyz, _onehot(types, C_), radii, radii_type, G.astype(np.float64), D, "gaussian", blockdim,
+                             types=types if radii_type == "channel-wise" else None)
+    got = r.grad.double().cpu().numpy()
+    _close(got, want, bound, "dL/dradii")
+    if radii_type == "atom-wise":
+        assert got[3] == 0.0
+
+
+def test_single_mode_radius_gradients_match_the_oracle():
+    import torch
+
+    D, N = 20, 25
+    rng, xyz, _ = _molecule(23, N, D, 1)
+    radii = rng.uniform(0.8, 2.0, N).astype(np.float32)
+    G = rng.standard_normal((1, D, D, D)).astype(np.float32)
+    vox = _vox(D, "atom-wise", blockdim=6)
+    r = torch.tensor(radii, device="cuda", requires_grad=True)
+    grid = vox.forward_single(torch.tensor(xyz, device="cuda"), None, r)
+    (grid * torch.as_tensor(G, device="cuda")).sum().backward()
+    want, bound = _ref_radii(xyz, np.ones((N, 1)), radii, "atom-wise", G.astype(np.float64), D, "gaussian", 6)
+    _close(r.grad.double().cpu().numpy(), want, bound, "dL/dradii")
+
+
+@pytest.mark.parametrize("radii_type, C_", [("atom-wise", 3), ("channel-wise", 3), ("channel-wise", 40)])
+def test_finite_differences_at_precision_64(radii_type, C_):
+    import torch
+
+    D, N = 20, 6
+    rng, xyz, feats = _molecule(24, N, D, C_, spread=0.3)
+    feats = feats.astype(np.float64)
+    radii = rng.uniform(0.9, 1.6, N) if radii_type == "atom-wise" else rng.choice([0.9, 1.2, 1.6], C_)
+    G = torch.as_tensor(rng.standard_normal((C_, D, D, D)), device="cuda")
+    f = torch.tensor(feats, device="cuda")
+    vox = _vox(D, radii_type, precision=64)
+    r = torch.tensor(radii, device="cuda", requires_grad=True)
+    (vox.forward_features(torch.tensor(xyz, device="cuda"), None, f, r) * G).sum().backward()
+    an = r.grad.cpu().numpy()
+    assert r.grad.dtype == torch.float64
+    plain = _vox(D, radii_type, precision=64, radii_grad=False)
+    ones = torch.ones((1, C_), dtype=torch.float64, device="cuda")
+
+    def support(rad):  # where each atom alone reaches, channel by channel
+        out = []
+        for n in range(N):
+            rn = torch.tensor(rad[n:n + 1] if radii_type == "atom-wise" else rad, device="cuda")
+            out.append((plain.forward_features(torch.tensor(xyz[n:n + 1], device="cuda"), None, ones, rn) != 0).cpu())
+        return torch.stack(out)
+
+    base = support(radii)
+    h = 1e-6
+    checked = 0
+    for j in range(len(radii)):
+        vals = []
+        for sgn in (1, -1):
+            rad = radii.copy()
+            rad[j] += sgn * h
+            if not torch.equal(support(rad), base):
+                break  # the support moved: the a.e. derivative does not see the jump
+            vals.append(float((plain.forward_features(torch.tensor(xyz, device="cuda"), None, f, torch.tensor(rad, device="cuda"))
+                               * G).sum()))
+        if len(vals) < 2:
+            continue
+        fd = (vals[0] - vals[1]) / (2 * h)
+        assert abs(fd - an[j]) <= 1e-6 * max(abs(an[j]), 1.0), (j, fd, an[j])
+        checked += 1
+    if radii_type == "atom-wise":  # (one radius per atom: few entries per call, so a second molecule adds more)
+        assert checked >= 4
+    else:
+        assert checked >= 3 if C_ == 3 else checked >= 12
+
+
+def test_finite_differences_atom_wise_reach_twelve_entries():
+    """Precision 64, one radius per atom: at least 12 checked entries over a molecule of 16 atoms."""
+    import torch
+
+    D, N, C_ = 20, 16, 3
+    rng, xyz, feats = _molecule(25, N, D, C_, spread=0.35)
+    radii = rng.uniform(0.9, 1.6, N)
+    G = torch.as_tensor(rng.standard_normal((C_, D, D, D)), device="cuda")
+    f = torch.tensor(feats.astype(np.float64), device="cuda")
+    vox = _vox(D, "atom-wise", precision=64)
+    r = torch.tensor(radii, device="cuda", requires_grad=True)
+    (vox.forward_features(torch.tensor(xyz, device="cuda"), None, f, r) * G).sum().backward()
+    an = r.grad.cpu().numpy()
+    plain = _vox(D, "atom-wise", precision=64, radii_grad=False)
+    ones = torch.ones((1, C_), dtype=torch.float64, device="cuda")
+
+    def support(n, rn):
+        return (plain.forward_features(torch.tensor(xyz[n:n + 1], device="cuda"), None, ones,
+                                       torch.tensor([rn], device="cuda")) != 0).cpu()
+
+    h = 1e-6
+    checked = 0
+    for n in range(N):
+        base = support(n, radii[n])
+        vals = []
+        for sgn in (1, -1):
+            rad = radii.copy()
+            rad[n] += sgn * h
+            if not torch.equal(support(n, rad[n]), base):
+                break
+            vals.append(float((plain.forward_features(torch.tensor(xyz, device="cuda"), None, f, torch.tensor(rad, device="cuda"))
+                               * G).sum()))
+        if len(vals) < 2:
+            continue
+        fd = (vals[0] - vals[1]) / (2 * h)
+        assert abs(fd - an[n]) <= 1e-6 * max(abs(an[n]), 1.0), (n, fd, an[n])
+        checked += 1
+    assert checked >= 12
+
+
+@pytest.mark.parametrize("grid_dtype, precision, radii_type", [
+    (None, 32, "atom-wise"), ("bfloat16", 32, "atom-wise"), (None, 64, "atom-wise"),
+    (None, 32, "channel-wise"), ("bfloat16", 32, "channel-wise"), (None, 64, "channel-wise")])
+def test_other_gradients_are_unchanged(grid_dtype, precision, radii_type):
+    """radii_grad=True: grid, coords.grad, features.grad and center.grad are the bits of a radii_grad=False voxelizer."""
+    import torch
+
+    D, N, C_ = 22, 40, 36
+    rng, xyz, feats = _molecule(26, N, D, C_, spread=0.3)
+    tdt = torch.float32 if precision == 32 else torch.float64
+    radii = rng.uniform(0.8, 1.8, N) if radii_type == "atom-wise" else rng.choice([1.0, 1.5, 1.9], C_)
+    cen = np.array([0.2, -0.3, 0.1])
+    G = torch.as_tensor(rng.standard_normal((C_, D, D, D)), device="cuda")
+    out = []
+    for rg in (False, True):
+        vox = _vox(D, radii_type, radii_grad=rg, precision=precision, grid_dtype=grid_dtype)
+        c = torch.tensor(xyz, device="cuda", requires_grad=True)
+        f = torch.tensor(feats, device="cuda", dtype=tdt, requires_grad=True)
+        ct = torch.tensor(cen, device="cuda", requires_grad=True)
+        r = torch.tensor(radii, device="cuda", dtype=tdt, requires_grad=rg)
+        np.random.seed(5)
+        grid = vox.forward_features(c, ct, f, r, random_translation=0.5, random_rotation=True)
+        grid.backward(G.to(grid.dtype))
+        out.append((grid.detach(), c.grad, f.grad, ct.grad, r.grad))
+    for a, b in zip(out[0][:4], out[1][:4]):
+        assert torch.equal(a, b)
+    assert out[0][4] is None and out[1][4] is not None and bool(torch.isfinite(out[1][4]).all()) and bool(out[1][4].any())
+
+
+def test_determinism_batch_independence_and_order():
+    import torch
+
+    D, C_ = 22, 8
+    sizes = [17, 0, 25, 1, 9]
+    rng = np.random.default_rng(27)
+    W = 0.5 * (D - 1)
+    mols = [rng.uniform(-W * 0.45, W * 0.45, (n, 3)) for n in sizes]
+    feats = [rng.standard_normal((n, C_)).astype(np.float32) for n in sizes]
+    ar = [rng.uniform(0.8, 1.8, n).astype(np.float32) for n in sizes]
+    cr = rng.choice([1.0, 1.4, 1.8], C_).astype(np.float32)
+    G = torch.as_tensor(rng.standard_normal((len(sizes), C_, D, D, D)), device="cuda", dtype=torch.float32)
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    for radii_type in ("atom-wise", "channel-wise"):
+        vox = _vox(D, radii_type, blockdim=8)
+        radii = np.concatenate(ar) if radii_type == "atom-wise" else cr
+
+        def batched(order):
+            vox.debug_option("grad_order", order)
+            c = torch.tensor(np.concatenate(mols), device="cuda", requires_grad=True)
+            f = torch.tensor(np.concatenate(feats), device="cuda", requires_grad=True)
+            r = torch.tensor(radii, device="cuda", requires_grad=True)
+            (vox.forward_batch(c, offsets, None, f, r) * G).sum().backward()
+            return c.grad, f.grad, r.grad
+
+        a, b, o = batched(0), batched(0), batched(1)
+        vox.debug_option("grad_order", 0)
+        for x, y, z in zip(a, b, o):
+            assert torch.equal(x, y) and torch.equal(x, z)
+        total = torch.zeros(C_, dtype=torch.float64, device="cuda")
+        for i, n in enumerate(sizes):
+            c = torch.tensor(mols[i], device="cuda", requires_grad=True)
+            f = torch.tensor(feats[i], device="cuda")
+            r = torch.tensor(ar[i] if radii_type == "atom-wise" else cr, device="cuda", requires_grad=True)
+            (vox.forward_features(c, None, f, r) * G[i]).sum().backward()
+            if radii_type == "atom-wise":
+                assert torch.equal(r.grad, a[2][offsets[i]:offsets[i + 1]])
+            else:
+                total += r.grad.double()
+        if radii_type == "channel-wise":
+            got = a[2].double()
+            assert torch.allclose(got, total, rtol=1e-6, atol=1e-12 * float(total.abs().max()))
+
+
+def test_channel_wise_batch_sum_at_precision_64():
+    """Channel-wise dL/dr of a batch equals the sum of the per-molecule results to 1e-12 relative (float64 throughout)."""
+    import torch
+
+    D, C_ = 20, 5
+    sizes = [12, 0, 1, 20]
+    rng = np.random.default_rng(28)
+    W = 0.5 * (D - 1)
+    mols = [rng.uniform(-W * 0.45, W * 0.45, (n, 3)) for n in sizes]
+    feats = [rng.standard_normal((n, C_)) for n in sizes]
+    cr = rng.choice([1.0, 1.4, 1.8], C_)
+    G = torch.as_tensor(rng.standard_normal((len(sizes), C_, D, D, D)), device="cuda")
+    offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    vox = _vox(D, "channel-wise", precision=64)
+    r = torch.tensor(cr, device="cuda", requires_grad=True)
+    (vox.forward_batch(torch.tensor(np.concatenate(mols), device="cuda"), offsets, None,
+                       torch.tensor(np.concatenate(feats), device="cuda"), r) * G).sum().backward()
+    total = torch.zeros(C_, dtype=torch.float64, device="cuda")
+    for i in range(len(sizes)):
+        ri = torch.tensor(cr, device="cuda", requires_grad=True)
+        (vox.forward_features(torch.tensor(mols[i], device="cuda"), None, torch.tensor(feats[i], device="cuda"), ri) * G[i]).sum().backward()
+        total += ri.grad
+    assert torch.allclose(r.grad, total, rtol=1e-12, atol=1e-12 * float(total.abs().max()))
+
+
+def test_plumbing_dtype_expand_and_padding():
+    import torch
+
+    D, N, C_ = 20, 18, 4
+    rng, xyz, feats = _molecule(29, N, D, C_, spread=0.35)
+    G = torch.as_tensor(rng.standard_normal((C_, D, D, D)), device="cuda", dtype=torch.float32)
+    f = torch.tensor(feats, device="cuda")
+    # float64 radii on a precision-32 voxelizer: the conversion is recorded, the gradient comes back in float64
+    vox = _vox(D, "atom-wise")
+    r64 = torch.tensor(rng.uniform(0.9, 1.6, N), device="cuda", requires_grad=True)
+    (vox.forward_features(torch.tensor(xyz, device="cuda"), None, f, r64) * G).sum().backward()
+    assert r64.grad.dtype == torch.float64
+    r32 = r64.detach().float().requires_grad_(True)
+    (vox.forward_features(torch.tensor(xyz, device="cuda"), None, f, r32) * G).sum().backward()
+    assert torch.equal(r64.grad, r32.grad.double())
+    # one learned radius as r.expand(N): the sum of the atom-wise gradients
+    one = torch.tensor(1.3, device="cuda", requires_grad=True)
+    (vox.forward_features(torch.tensor(xyz, device="cuda"), None, f, one.expand(N)) * G).sum().backward()
+    ra = torch.full((N,), 1.3, device="cuda", requires_grad=True)
+    (vox.forward_features(torch.tensor(xyz, device="cuda"), None, f, ra) * G).sum().backward()
+    assert torch.allclose(one.grad, ra.grad.sum(), rtol=1e-5, atol=1e-6 * float(ra.grad.abs().sum()))
+    assert one.grad != 0
+    # channel-wise radii in forward_batch types mode, padded up to num_channels: the padding gets no gradient
+    types = rng.integers(0, 3, N)
+    types[0], types[1], types[2] = 0, 1, 2
+    vc = _vox(D, "channel-wise")
+    rc = torch.tensor([1.1, 1.5, 1.3], device="cuda", requires_grad=True)
+    grid = vc.forward_batch(torch.tensor(xyz, device="cuda"), np.array([0, N]), None, torch.tensor(types, device="cuda"), rc,
+                            num_channels=C_ + 2)
+    assert tuple(grid.shape) == (1, C_ + 2, D, D, D)
+    Gt = torch.as_tensor(rng.standard_normal((1, C_ + 2, D, D, D)), device="cuda", dtype=torch.float32)
+    (grid * Gt).sum().backward()
+    assert tuple(rc.grad.shape) == (3,) and bool(rc.grad.all())
+    want, bound = _ref_radii(xyz, _onehot(types, C_ + 2), np.array([1.1, 1.5, 1.3], np.float32), "channel-wise",
+                             Gt[0].double().cpu().numpy(), D, "gaussian", 8, types=types)
+    _close(rc.grad.double().cpu().numpy(), want, bound, "dL/dradii")
+    # scalar radii stay python floats: no gradient, and the coordinate gradients still flow
+    vs = _vox(D, "scalar")
+    c = torch.tensor(xyz, device="cuda", requires_grad=True)
+    (vs.forward_features(c, None, f, 1.3) * G).sum().backward()
+    assert c.grad is not None
+    # without radii_grad a radii tensor that requires grad still raises
+    with pytest.raises(NotImplementedError, match="radii"):
+        _vox(D, "atom-wise", radii_grad=False).forward_features(c, None, f, torch.full((N,), 1.2, device="cuda", requires_grad=True))
+
+
+def test_headline_shape_spot_check():
+    import torch
+
+    D, N, C_, B = 64, 4000, 32, 4
+    rng = np.random.default_rng(30)
+    W = 0.5 * (D - 1)
+    xyz = [rng.uniform(-W / 2, W / 2, (N, 3)) for _ in range(B)]
+    feats = [rng.random((N, C_)).astype(np.float32) for _ in range(B)]
+    G = torch.as_tensor(rng.standard_normal((B, C_, D, D, D)), device="cuda", dtype=torch.float32)
+    vox = _vox(D)
+    r = torch.ones(B * N, device="cuda", requires_grad=True)
+    grid = vox.forward_batch(torch.tensor(np.concatenate(xyz), device="cuda"), np.arange(B + 1) * N, None,
+                             torch.tensor(np.concatenate(feats), device="cuda"), r)
+    (grid * G).sum().backward()
+    gr = r.grad.double().cpu().numpy()
+    Gn = G.cpu().numpy().astype(np.float64)
+    for b in range(B):
+        pick = rng.choice(N, 25, replace=False)
+        want, bound = _ref_radii(xyz[b][pick], feats[b][pick].astype(np.float64), np.ones(25, np.float32), "atom-wise", Gn[b], D,
+                                 "gaussian", 8)
+        _close(gr[b * N + pick], want, bound, "dL/dradii")
