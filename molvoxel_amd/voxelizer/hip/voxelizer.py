@@ -656,12 +656,23 @@ class Voxelizer(BaseVoxelizer):
         # radii_grad: the radii as the call hands them to the library (dtype conversion / type padding recorded by autograd)
         rin = r if (self.radii_grad and _is_torch(r) and r.requires_grad) else None
         spec = dict(mode=mode, types=types, radii=r, rs=rs, offsets=np.ascontiguousarray(offsets, np.int64), xforms=xforms,
-                    B=B, C=C_)
+                    B=B, C=C_, settings=self._grad_settings())
         return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen, rin)
+
+    def _grad_settings(self):
+        """What the backward reads from the voxelizer rather than from the call: density, sigma and radii type."""
+        return (self.density_type, float(getattr(self, "_sigma", 0.5)) if self.is_density_type_gaussian else None,
+                self.radii_type)
 
     def _backward(self, spec, c, f, grad, need_features, need_radii=False):
         """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None, dL/dradii shaped and typed like the call's radii or None)
         for dL/dgrid = grad, on the current stream."""
+        now = self._grad_settings()
+        if now != spec["settings"]:
+            raise RuntimeError(
+                "the voxelizer's density / sigma / radii type changed between the forward call and backward() "
+                f"(forward: {spec['settings']}, now: {now}); the gradients would be those of another grid. Restore the "
+                "settings before backward(), or use one voxelizer per setting")
         g = grad.to(device=self.device, dtype=self._gdt).contiguous()
         gc = torch.empty((c.shape[0], 3), dtype=torch.float64, device=self.device)
         gf = torch.empty((c.shape[0], spec["C"]), dtype=self._tfp, device=self.device) if need_features else None

@@ -1,77 +1,19 @@
-"""Backward pass on the GPU (differentiable=True, mvx_backward_batch): feature and coordinate gradients against per-atom
-densities from the CPU oracle, finite differences at precision 64, the adjoint identity, transforms and centres,
+"""Backward pass on the GPU (differentiable=True, mvx_backward_batch): feature and coordinate gradients against the float64
+reference (tests/grad_reference.py), finite differences at precision 64, the adjoint identity, transforms and centres,
 determinism, batch independence, bfloat16 grids, types / single modes and the unchanged default."""
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from tests.grad_reference import close as _close
+from tests.grad_reference import ref_grads as _ref_grads
 
-LN2 = float(np.log(2.0))
+pytestmark = pytest.mark.gpu
 
 
 def _vox(D, radii_type="scalar", density="gaussian", **kw):
     import molvoxel_amd as mv
 
     return mv.create_voxelizer(0.5, D, radii_type, density, library="hip", differentiable=True, **kw)
-
-
-def _axis(D, res=0.5):
-    return np.arange(D) * res - res * (D - 1) / 2.0
-
-
-def _k32(r, sigma=0.5):
-    rs = float(np.float32(r)) * float(np.float32(sigma))
-    return float(np.float32(-0.5 * 1.4426950408889634 / (rs * rs)))
-
-
-def _rho(xyz, n, radii, radii_type, C_, D, density, blockdim):
-    """(C', D, D, D) float64 densities of atom n alone (per-atom culls: exact); C' = C for channel-wise radii, else 1."""
-    from oracle import c_oracle
-
-    kw = dict(dimension=D, blockdim=blockdim, density=density, radii_type=radii_type)
-    one = xyz[n:n + 1]
-    if radii_type == "channel-wise":
-        return c_oracle.voxelize(one, np.ones((1, C_), np.float32), radii, **kw).astype(np.float64)
-    r = radii if radii_type == "scalar" else np.asarray(radii[n:n + 1], np.float32)
-    return c_oracle.voxelize(one, None, r, **kw).astype(np.float64)
-
-
-def _ref_grads(xyz, feats, radii, radii_type, G, D, density, blockdim, wmode="features", types=None):
-    """numpy float64 reference: (dL/dw (N,C), bound on sum|terms| of dL/dw, dL/dp (N,3), its bound)."""
-    N, C_ = xyz.shape[0], G.shape[0]
-    ax = _axis(D)
-    gw, bw = np.zeros((N, C_)), np.zeros((N, C_))
-    gp, bp = np.zeros((N, 3)), np.zeros((N, 3))
-    for n in range(N):
-        rho = _rho(xyz, n, radii, radii_type, C_, D, density, blockdim)
-        if wmode == "features":
-            w = feats[n].astype(np.float64)
-        else:
-            w = np.zeros(C_)
-            t = 0 if wmode == "single" else int(types[n])
-            if t < C_:
-                w[t] = 1.0
-        if radii_type == "channel-wise":
-            k = np.array([_k32(r) for r in radii])
-        else:
-            k = np.full(C_, _k32(radii if radii_type == "scalar" else radii[n]))
-        rc = rho if rho.shape[0] == C_ else np.broadcast_to(rho, (C_,) + rho.shape[1:])
-        gw[n] = (G * rc).reshape(C_, -1).sum(1)
-        bw[n] = np.abs(G * rc).reshape(C_, -1).sum(1)
-        if density == "gaussian":
-            s = (G * rc * (w * 2 * LN2 * k)[:, None, None, None]).sum(0)
-            d = [xyz[n, 0] - ax[:, None, None], xyz[n, 1] - ax[None, :, None], xyz[n, 2] - ax[None, None, :]]
-            for i in range(3):
-                gp[n, i] = (s * d[i]).sum()
-                bp[n, i] = np.abs(s * d[i]).sum()
-    return gw, bw, gp, bp
-
-
-def _close(got, ref, bound, what):
-    err = np.abs(got - ref)
-    tol = 2e-5 * bound + 1e-7
-    bad = err > tol
-    assert not bad.any(), f"{what}: {int(bad.sum())} off, worst {err[bad].max()} at {np.argwhere(bad)[:3].tolist()}"
 
 
 def _molecule(seed, N, D, C_, spread=0.45):
@@ -430,3 +372,44 @@ def test_processing_order_does_not_change_the_gradients():
         (grid * G).sum().backward()
         out.append((c.grad, f.grad))
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
+
+
+@pytest.mark.parametrize("change", ["density", "sigma", "radii_type"])
+def test_settings_changed_between_forward_and_backward_raise(change):
+    """The backward reads the voxelizer's density, sigma and radii type: a change after the forward call is an error, not
+    the gradients of another grid. Settings restored before backward() give the forward's gradients."""
+    import torch
+
+    D, N, C_ = 20, 12, 3
+    rng, xyz, feats = _molecule(14, N, D, C_)
+    G = torch.as_tensor(rng.standard_normal((C_, D, D, D)), device="cuda", dtype=torch.float32)
+    radii = torch.tensor(rng.uniform(0.9, 1.5, N).astype(np.float32), device="cuda")
+    sigma = 0.7 if change == "sigma" else 0.5
+
+    def forward(vox):
+        c = torch.tensor(xyz, device="cuda", requires_grad=True)
+        return c, vox.forward_features(c, None, torch.tensor(feats, device="cuda"), radii)
+
+    def mutate(vox):
+        if change == "density":
+            vox.density_type = "binary"
+        elif change == "sigma":
+            vox.density_type = "gaussian"  # (the setter falls back to the default sigma, 0.5)
+        else:
+            vox.radii_type = "scalar"
+
+    vox = _vox(D, "atom-wise", sigma=sigma)
+    c, grid = forward(vox)
+    mutate(vox)
+    with pytest.raises(RuntimeError, match="changed between the forward call and backward"):
+        grid.backward(G)
+    if change == "sigma":
+        return
+    c0, g0 = forward(_vox(D, "atom-wise"))
+    g0.backward(G)
+    vox = _vox(D, "atom-wise")
+    c, grid = forward(vox)
+    mutate(vox)
+    vox.density_type, vox.radii_type = "gaussian", "atom-wise"
+    grid.backward(G)
+    assert torch.equal(c.grad, c0.grad) and c.grad.any()

@@ -1,10 +1,12 @@
 """Radius gradients on the GPU (radii_grad=True, mvx_backward_radii_batch): atom-wise and channel-wise dL/dradii against
-per-atom densities from the CPU oracle, finite differences at precision 64, the other gradients unchanged bit for bit,
+the float64 reference (tests/grad_reference.py), finite differences at precision 64, the other gradients unchanged bit for bit,
 determinism, batch independence, processing order and the autograd plumbing (dtype, expand, padded channel radii)."""
 import numpy as np
 import pytest
 
-from tests.test_hip_grad import LN2, _axis, _close, _k32, _molecule, _rho
+from tests.grad_reference import close as _close
+from tests.grad_reference import ref_radii as _ref_radii
+from tests.test_hip_grad import _molecule
 
 pytestmark = pytest.mark.gpu
 
@@ -13,49 +15,6 @@ def _vox(D, radii_type="atom-wise", density="gaussian", radii_grad=True, **kw):
     import molvoxel_amd as mv
 
     return mv.create_voxelizer(0.5, D, radii_type, density, library="hip", differentiable=True, radii_grad=radii_grad, **kw)
-
-
-def _d2(xyz, n, D):
-    ax = _axis(D)
-    return ((xyz[n, 0] - ax[:, None, None]) ** 2 + (xyz[n, 1] - ax[None, :, None]) ** 2) + (xyz[n, 2] - ax[None, None, :]) ** 2
-
-
-def _ref_radii(xyz, w, radii, radii_type, G, D, density, blockdim, types=None):
-    """numpy float64 reference of dL/dradii and a bound on sum|terms| (float32 coefficients, as precision 32 evaluates them).
-    w: (N, C) channel weights (features, or one-hot types). radii_type "atom-wise": (N,); "channel-wise": (C,) for features,
-    or with `types` the radius of each atom's type."""
-    N, C_ = xyz.shape[0], G.shape[0]
-    if radii_type == "channel-wise" and types is None:
-        g, b = np.zeros(C_), np.zeros(C_)
-        for n in range(N):
-            rho = _rho(xyz, n, radii, "channel-wise", C_, D, density, blockdim)
-            t = (G * rho).reshape(C_, -1) * _d2(xyz, n, D).reshape(1, -1) * w[n][:, None]
-            g += t.sum(1)
-            b += np.abs(t).sum(1)
-        if density != "gaussian":
-            return np.zeros(C_), b
-        s = np.array([2 * LN2 * _k32(r) / float(np.float32(r)) for r in radii])
-        return -s * g, np.abs(s) * b
-    rad = np.asarray(radii, np.float32)
-    atom_r = rad if types is None else np.array([rad[t] if t < len(rad) else 1.0 for t in types], np.float32)
-    g, b = np.zeros(N), np.zeros(N)
-    if density == "gaussian":
-        for n in range(N):
-            if types is not None and types[n] >= len(rad):
-                continue
-            rho = _rho(xyz, n, atom_r, "atom-wise", C_, D, density, blockdim)[0]
-            r = float(atom_r[n])
-            e = (G * w[n][:, None, None, None]).sum(0) * rho * (2 * LN2 * _k32(r))
-            t = e * _d2(xyz, n, D) / r
-            g[n], b[n] = -t.sum(), np.abs(t).sum()
-    if types is None:
-        return g, b
-    gc, bc = np.zeros(len(rad)), np.zeros(len(rad))
-    for n, t in enumerate(types):
-        if t < len(rad):
-            gc[t] += g[n]
-            bc[t] += b[n]
-    return gc, bc
 
 
 def _onehot(types, C_):

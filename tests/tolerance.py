@@ -21,6 +21,12 @@ NORTH_STAR_ABS = 1e-5  # BASELINE.json north_star: "within 1e-5 abs for the Gaus
                        # on every BASELINE configuration (sums of a few units); the relative branch above is for the dense
                        # goldens and the fuzz's clustered draws only
 P64_TOL = 1e-12  # float64 grids: exp / summation-order differences only
+# Gradients (tests/grad_reference.py): |got - ref| <= REL * bound + ABS, bound = sum of |terms| of the output.
+GRAD_REL, GRAD_ABS = 2e-5, 1e-7  # precision 32: float32 densities (exp2f against expf) and float32 channel sums
+# precision 64: float64 densities from exp(c d2) against the reference's exp(-0.5 (dr / sigma)^2) (~1e-15 relative) and
+# float64 sums in another order. Over tests/test_hip_grad_fuzz.py's 200 draws the worst |got - ref| / bound was 1.4e-15
+# (coordinates; features 1.3e-15, atom-wise radii 8e-16, sums over atoms 2e-16): the bar leaves a factor of about 70.
+GRAD64_REL, GRAD64_ABS = 1e-13, 1e-15
 
 
 def assert_membership(out, ref):
