@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVX_VERSION 140 /* 0.1.4: mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
+#define MVX_VERSION 140 /* 0.1.4: mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
 
 typedef enum mvx_status {
     MVX_OK = 0,
@@ -202,7 +202,8 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const mvx_real *radi
  * gradients are those of a density that may differ from the stored grid in the last ulp.
  * Derivative almost everywhere: the jump of rho at the truncation radius is ignored, so binary density gives zero coordinate
  * gradients. The gradient with respect to a centre is -sum of dL/dcoords over the molecule (no MVX_XF_RECENTER: the caller
- * reduces it). No gradients with respect to radii (mvx_backward_radii_batch gives them) or sigma.
+ * reduces it). No gradients with respect to radii (mvx_backward_radii_batch gives them) or sigma
+ * (mvx_backward_density_batch gives it, and the gradient of a scalar radius).
  * Outputs are fully overwritten (atoms that reach no voxel get exact zeros) and deterministic: no atomics, fixed-order
  * reductions; a molecule's gradients are bit for bit the same in any batch. Arguments as in the forward entries (same
  * offsets / xforms / radii: the pre-pass is recomputed from them, nothing is kept from the forward call).
@@ -234,11 +235,43 @@ int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const 
  * as for the coordinates). Channel-wise radii use handle-owned workspace of 8 bytes per atom (types) or per atom and
  * channel (features). MVX_ERR_INVALID before any device is touched for what mvx_backward_batch rejects (except that
  * grad_coords and grad_features may both be NULL), a NULL grad_radii, scalar radii and channel-wise radii in single mode.
+ * No gradient with respect to sigma or to a scalar radius here: mvx_backward_density_batch gives both.
  */
 int mvx_backward_radii_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
                              double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
                              int32_t B, int32_t C, const void *grad_out, double *grad_coords, mvx_real *grad_features,
                              double *grad_radii, void *stream);
+
+/*
+ * mvx_backward_radii_batch plus the gradients with respect to sigma and to a scalar radius, from the same walk: grad_coords /
+ * grad_features / grad_radii, where requested, are the bits mvx_backward_batch / mvx_backward_radii_batch write (each may be
+ * NULL here; grad_radii is invalid with MVX_RADII_SCALAR), and
+ *   grad_sigma:          one double on the device, or NULL
+ *   grad_radius_scalar:  one double on the device, or NULL; MVX_RADII_SCALAR only
+ * At least one of grad_sigma, grad_radius_scalar and grad_radii must be non-NULL. k and c are proportional to (r sigma)^-2
+ * and the membership m (d / r <= 1, the culls) does not depend on sigma, so with P_n = sum_v (sum_c G[c,v] w[n,c] rho_{n,c}(v))
+ * kfac_n d2_n(v), the per-atom sum of mvx_backward_radii_batch:
+ *   scalar radius         dL/dr     = -(1/r) sum_n P_n                                                      (every mode)
+ *   one radius per atom, radii by type, scalar radius
+ *                         dL/dsigma = -(1/sigma) sum_n P_n                                                   (every mode)
+ *   channel-wise, feat.   dL/dsigma = -(1/sigma) sum_c kfac_c sum_n w[n,c] sum_v G[c,v] rho_{n,c}(v) d2_n(v)
+ *                                   = sum_c (r_c / sigma) dL/dr_c
+ * r and sigma are the values the forward used: float(radius_scalar) and float(sigma) widened to double for float32
+ * arithmetic, the doubles for float64 grids. dL/dsigma is the exact derivative where the grid is smooth in sigma (m has no
+ * jump in sigma); dL/dr is the derivative almost everywhere, as for the other radii. The sums run over every atom of the
+ * call, all molecules (one sigma and one scalar radius serve the batch), in a fixed order without atomics: chunks of atoms,
+ * a fixed butterfly per wave, the waves in order, the chunks in order. Two runs give the same bits, under either "grad_order".
+ * One walk feeds grad_radii, grad_sigma and grad_radius_scalar (channel-wise features: the second walk of
+ * mvx_backward_radii_batch). Outputs are fully overwritten; a call without atoms writes zeros; binary density: zeros.
+ * Handle-owned workspace of 8 bytes per atom, or per atom and channel (channel-wise features), whether or not grad_radii is
+ * asked for. MVX_ERR_INVALID before any device is touched for what mvx_backward_batch rejects (except that grad_coords and
+ * grad_features may both be NULL), all three of grad_sigma / grad_radius_scalar / grad_radii NULL, grad_radius_scalar with
+ * radii that are not scalar, grad_radii with scalar radii, and channel-wise radii in single mode.
+ */
+int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                               double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                               int32_t B, int32_t C, const void *grad_out, double *grad_coords, mvx_real *grad_features,
+                               double *grad_radii, double *grad_sigma, double *grad_radius_scalar, void *stream);
 
 /*
  * Replaces do_transform on an (N,3) fp64 point cloud (numpy/transform.py:44-60): out = transformed coords.

@@ -830,11 +830,15 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const void *radii, d
                                     out_kind, stream);
 }
 
-// mvx_backward_batch (with_radii false) and mvx_backward_radii_batch (with_radii true: grad_radii as well)
+// mvx_backward_batch (BWD_PLAIN), mvx_backward_radii_batch (BWD_RADII: grad_radii as well) and mvx_backward_density_batch
+// (BWD_DENSITY: grad_sigma / grad_rscalar / grad_radii, each or NULL)
+enum BackwardKind { BWD_PLAIN, BWD_RADII, BWD_DENSITY };
+
 static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                          double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
-                         int32_t C, const void *grad_out, double *grad_coords, void *grad_features, bool with_radii,
-                         double *grad_radii, void *stream) {
+                         int32_t C, const void *grad_out, double *grad_coords, void *grad_features, BackwardKind kind,
+                         double *grad_radii, double *grad_sigma, double *grad_rscalar, void *stream) {
+    const bool with_radii = kind == BWD_RADII, with_density = kind == BWD_DENSITY;
     // ---- what is checked before any device is touched ----
     if (mode < MODE_FEATURES || mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
     if (grad_features && mode != MODE_FEATURES) return fail(MVX_ERR_INVALID, "grad_features exists in features mode only");
@@ -846,6 +850,15 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
             return fail(MVX_ERR_INVALID, "radii_type: scalar radii have no radius array for grad_radii (atom-wise or channel-wise radii only)");
         if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE)
             return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode (no grad_radii)");
+    } else if (with_density) { // (grad_coords and grad_features may both be null here too)
+        if (!grad_sigma && !grad_rscalar && !grad_radii)
+            return fail(MVX_ERR_INVALID, "grad_sigma, grad_radius_scalar and grad_radii are all null");
+        if (grad_rscalar && radii_type != MVX_RADII_SCALAR)
+            return fail(MVX_ERR_INVALID, "radii_type: grad_radius_scalar exists with scalar radii only");
+        if (grad_radii && radii_type == MVX_RADII_SCALAR)
+            return fail(MVX_ERR_INVALID, "radii_type: scalar radii have no radius array for grad_radii (grad_radius_scalar gives dL/dr)");
+        if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE)
+            return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode");
     } else if (!grad_coords && !grad_features) {
         return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
     }
@@ -858,9 +871,9 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
         if (offsets[b + 1] < offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
     const int64_t total = B > 0 ? offsets[B] : 0;
-    // (no atoms: no gradient rows; channel-wise radii still get their C zeros)
-    const bool radii_by_channel = with_radii && radii_type == MVX_RADII_CHANNEL;
-    if (total == 0 && !radii_by_channel) return MVX_OK;
+    // (no atoms: no gradient rows; channel-wise radii still get their C zeros, sigma and a scalar radius their zero)
+    const bool radii_by_channel = grad_radii && radii_type == MVX_RADII_CHANNEL;
+    if (total == 0 && !radii_by_channel && !with_density) return MVX_OK;
     if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
     if (total == 0) {
         DeviceGuard guard(h->device);
@@ -868,7 +881,9 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
         hipStream_t s = reinterpret_cast<hipStream_t>(stream);
         int rc = adopt_stream(h, s);
         if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)C * sizeof(double), s));
+        if (radii_by_channel) HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)C * sizeof(double), s));
+        if (grad_sigma) HIP_TRY(hipMemsetAsync(grad_sigma, 0, sizeof(double), s));
+        if (grad_rscalar) HIP_TRY(hipMemsetAsync(grad_rscalar, 0, sizeof(double), s));
         return MVX_OK;
     }
     if (!coords || !grad_out) return fail(MVX_ERR_INVALID, "coords / grad_out must not be null");
@@ -958,11 +973,44 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
     ga.res = h->g.res;
     ga.half = h->g.half;
     const int32_t grid_kind = bf16 ? 1 : (f64 ? 2 : 0);
-    if (!with_radii) {
+    if (kind == BWD_PLAIN) {
         HIP_TRY(launch_grad(ga, mode, grid_kind, gauss, chanwise, s));
-    } else if (!gauss) { // binary density: zero radius gradients (the a.e. derivative), the walk for the other outputs only
-        HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)(radii_type == MVX_RADII_CHANNEL ? C : total) * sizeof(double), s));
+    } else if (!gauss) { // binary density: zero radius and sigma gradients (the a.e. derivative), the walk for the other outputs only
+        if (grad_radii)
+            HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)(radii_type == MVX_RADII_CHANNEL ? C : total) * sizeof(double), s));
+        if (grad_sigma) HIP_TRY(hipMemsetAsync(grad_sigma, 0, sizeof(double), s));
+        if (grad_rscalar) HIP_TRY(hipMemsetAsync(grad_rscalar, 0, sizeof(double), s));
         if (grad_coords || grad_features) HIP_TRY(launch_grad(ga, mode, grid_kind, gauss, chanwise, s));
+    } else if (with_density) {
+        // The radius walk with its partials kept per atom (or per channel and atom) in grad_rpart, whatever the radii type:
+        // [partials | channel-wise: stage sums of grad_radii_reduce, C doubles for a grad_radii nobody asked for | the chunk
+        // sums of all atoms]. One walk feeds grad_radii, grad_sigma and grad_rscalar.
+        const bool by_channel = radii_type == MVX_RADII_CHANNEL;
+        const size_t npart = chanwise ? (size_t)C * (size_t)total : (size_t)total;
+        const size_t part_bytes = align_up(npart * sizeof(double), 256);
+        const size_t rstage_bytes = by_channel ? align_up((grad_radii_stage_doubles(total, C) + (size_t)C) * sizeof(double), 256) : 0;
+        if ((rc = ensure(h->grad_rpart, part_bytes + rstage_bytes + grad_density_stage_doubles(total) * sizeof(double)))) return rc;
+        RadiiArgs ra;
+        ra.radii = radii;
+        ra.grad_radii = nullptr;
+        ra.part = reinterpret_cast<double *>(h->grad_rpart.p);
+        double *rstage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes);
+        double *dstage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes + rstage_bytes);
+        // sigma and the scalar radius as the forward used them
+        const double sigma = f64 ? h->cfg.sigma : (double)h->sigma32;
+        const double rsc = f64 ? radius_scalar : (double)(float)radius_scalar;
+        HIP_TRY(launch_grad_radii(ga, ra, mode, grid_kind, chanwise, s));
+        if (by_channel && (grad_radii || chanwise)) { // (features: grad_sigma needs the stage sums of this reduction)
+            double *gr = grad_radii ? grad_radii : rstage + grad_radii_stage_doubles(total, C);
+            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(channels), radii,
+                                             chanwise ? d_kc : nullptr, f64, total, C, rstage, gr, s));
+        }
+        if (chanwise) {
+            if (grad_sigma) HIP_TRY(launch_grad_density_chan(rstage, total, C, d_kc, f64, sigma, grad_sigma, s));
+        } else if (grad_sigma || grad_rscalar || !by_channel) {
+            HIP_TRY(launch_grad_density_sum(ra.part, total, radii, f64, by_channel ? nullptr : grad_radii, rsc, sigma, dstage,
+                                            grad_sigma, grad_rscalar, s));
+        }
     } else {
         // radius partials: straight into grad_radii (one radius per atom), or per atom / per (channel, atom) into grad_rpart
         // and reduced over all atoms of the call in a fixed order (channel-wise radii: one radius vector for the batch)
@@ -992,7 +1040,7 @@ int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const 
                        double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                        int32_t C, const void *grad_out, double *grad_coords, void *grad_features, void *stream) {
     return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
-                         grad_features, false, nullptr, stream);
+                         grad_features, BWD_PLAIN, nullptr, nullptr, nullptr, stream);
 }
 
 int mvx_backward_radii_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
@@ -1000,7 +1048,15 @@ int mvx_backward_radii_batch(mvx_handle *h, int32_t mode, const double *coords, 
                              int32_t C, const void *grad_out, double *grad_coords, void *grad_features, double *grad_radii,
                              void *stream) {
     return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
-                         grad_features, true, grad_radii, stream);
+                         grad_features, BWD_RADII, grad_radii, nullptr, nullptr, stream);
+}
+
+int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                               double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
+                               int32_t C, const void *grad_out, double *grad_coords, void *grad_features, double *grad_radii,
+                               double *grad_sigma, double *grad_radius_scalar, void *stream) {
+    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
+                         grad_features, BWD_DENSITY, grad_radii, grad_sigma, grad_radius_scalar, stream);
 }
 
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,

@@ -48,5 +48,16 @@ hipError_t launch_grad_radii(const GradArgs &a, const RadiiArgs &r, int32_t mode
 size_t grad_radii_stage_doubles(int64_t total, int32_t C);
 hipError_t launch_grad_radii_reduce(const double *part, const int32_t *types, const void *radii, const void *kc, bool f64, int64_t total,
                                     int32_t C, double *stage, double *grad_radii, hipStream_t s);
+// Sigma and scalar-radius gradients (mvx_backward_density_batch, mvx_grad_density.hip): the (total,) per-atom partials of
+// RadiiArgs::part summed over the call in a fixed order (no atomics), then grad_sigma[0] = -sum / sigma and grad_radius[0] =
+// -sum / r (each or NULL). With `grad_radii` (one radius per atom, `radii` the call's array) also dL/dr_n = -part[n] / radii[n],
+// the bits the walk writes itself without RadiiArgs::part. `stage` holds grad_density_stage_doubles(total) doubles.
+size_t grad_density_stage_doubles(int64_t total);
+hipError_t launch_grad_density_sum(const double *part, int64_t total, const void *radii, bool f64, double *grad_radii, double r,
+                                   double sigma, double *stage, double *grad_sigma, double *grad_radius, hipStream_t s);
+// Channel-wise radii for features: grad_sigma[0] = -(1/sigma) sum_c kfac_c S_c from launch_grad_radii_reduce's `stage` sums
+// (S_c: the chunks of channel c in order) and launch_grad_chan's kc, the channels in a fixed order.
+hipError_t launch_grad_density_chan(const double *stage, int64_t total, int32_t C, const void *kc, bool f64, double sigma,
+                                    double *grad_sigma, hipStream_t s);
 
 } // namespace mvx

@@ -15,8 +15,9 @@ kernels write bfloat16 grids directly: the float32 grid rounded to nearest even 
 what `.to(torch.bfloat16)` of the float32 grid gives, at half the bytes. `differentiable=True` makes grids computed from device
 tensors that require grad (`coords`, `features`, `center`) part of the autograd graph: the backward pass runs on the GPU
 (mvx_backward_batch) and returns gradients with respect to those tensors. `radii_grad=True` (with `differentiable=True`)
-adds a radii tensor that requires grad to them (mvx_backward_radii_batch, atom-wise or channel-wise radii); scalar radii stay
-python floats without gradient: learn a single radius as `r.expand(N)` on an atom-wise voxelizer.
+adds a radii tensor that requires grad to them (mvx_backward_radii_batch, atom-wise or channel-wise radii; on a scalar-radii
+voxelizer a one-element radii tensor, mvx_backward_density_batch). `sigma_grad=True` (with `differentiable=True`) lets `sigma=`
+/ `set_sigma()` take a one-element tensor that gets dL/dsigma (mvx_backward_density_batch).
 """
 from __future__ import annotations
 
@@ -66,8 +67,19 @@ class Voxelizer(BaseVoxelizer):
         grid_dtype=None,
         differentiable: bool = False,
         radii_grad: bool = False,
+        sigma_grad: bool = False,
         **kwargs,
     ):
+        # sigma as a tensor (sigma_grad): kept as `sigma_tensor`; `_sigma` stays the python float the base class stores
+        self._sigma_src = None  # (tensor, its _version when read, the value read)
+        self._rscalar_src = None  # the same for a scalar-radius tensor (radii_grad on a scalar-radii voxelizer)
+        sigma_src = None
+        if _is_torch(kwargs.get("sigma")):
+            if not sigma_grad:
+                raise ValueError("sigma is a tensor: create the voxelizer with sigma_grad=True (and differentiable=True) to learn "
+                                 "sigma, or pass a python float")
+            sigma_src = self._read_scalar_tensor(kwargs["sigma"], "sigma")
+            kwargs = dict(kwargs, sigma=sigma_src[2])
         super().__init__(resolution, dimension, radii_type, density_type, **kwargs)
         assert precision in [32, 64]
         assert output in ("torch", "numpy")
@@ -75,8 +87,12 @@ class Voxelizer(BaseVoxelizer):
             raise ValueError("differentiable=True needs output='torch': gradients flow through torch tensors")
         if radii_grad and not differentiable:
             raise ValueError("radii_grad=True needs differentiable=True: radius gradients are part of the autograd graph")
+        if sigma_grad and not differentiable:
+            raise ValueError("sigma_grad=True needs differentiable=True: the sigma gradient is part of the autograd graph")
         self.differentiable = bool(differentiable)
         self.radii_grad = bool(radii_grad)
+        self.sigma_grad = bool(sigma_grad)
+        self._sigma_src = sigma_src
         self._bf16 = self._is_bf16_grid(grid_dtype, precision, output)  # (checked before anything touches a device)
         if output == "torch" and torch is None:
             raise ImportError("output='torch' needs PyTorch; use output='numpy'")
@@ -167,6 +183,63 @@ class Voxelizer(BaseVoxelizer):
                 pass
             self._handle = None
 
+    @property
+    def sigma_tensor(self):
+        """The tensor `sigma=` / `set_sigma()` gave (sigma_grad=True), or None: sigma is a python float."""
+        return None if self._sigma_src is None else self._sigma_src[0]
+
+    @staticmethod
+    def _read_scalar_tensor(t, what):
+        """(tensor, its _version, its value as a python float): one read to the host (a synchronisation for a device tensor)."""
+        if t.numel() != 1:
+            raise ValueError(f"{what} should be a python float or a one-element tensor, not a tensor of shape {tuple(t.shape)}")
+        value = float(t.detach().reshape(()).item())
+        if not value > 0.0:
+            raise ValueError(f"{what} must be positive, got {value}")
+        return t, t._version, value
+
+    def set_sigma(self, value):
+        """Replace sigma: a python float, or with sigma_grad=True a one-element tensor (kept as `sigma_tensor`; it gets
+        dL/dsigma when it requires grad). A tensor is read to the host here and again before a call only after it was written
+        in place (its `_version` moved, as `optimizer.step()` does): one synchronisation per step, none per call."""
+        if _is_torch(value):
+            if not self.sigma_grad:
+                raise ValueError("sigma is a tensor: create the voxelizer with sigma_grad=True (and differentiable=True) to learn "
+                                 "sigma, or pass a python float")
+            src = self._read_scalar_tensor(value, "sigma")
+        else:
+            if not float(value) > 0.0:
+                raise ValueError(f"sigma must be positive, got {float(value)}")
+            src = None
+        self._sigma_src = src
+        if self.is_density_type_gaussian:  # (binary density stores no sigma: base class)
+            self._sigma = src[2] if src is not None else float(value)
+            self._density_changed()
+
+    def _sync_sigma(self):
+        """Before a call: re-read a sigma tensor that was written since its last read and hand the value to the library."""
+        t, version, _ = self._sigma_src
+        if t._version != version:
+            self._sigma_src = self._read_scalar_tensor(t, "sigma")
+            if self.is_density_type_gaussian:
+                self._sigma = self._sigma_src[2]
+                self._density_changed()
+
+    def _on_density_type(self, value):
+        if value == "gaussian":  # the default sigma comes back (base class): a sigma tensor no longer describes the density
+            self._sigma_src = None
+        super()._on_density_type(value)
+
+    def _scalar_radius(self, radii):
+        """radii_grad on a scalar-radii voxelizer: a one-element radii tensor -> (python float, the tensor). Read to the host when
+        the tensor is new or was written in place since its last read (`_types_extent`'s rule). Anything else: (radii, None)."""
+        if not (self.radii_grad and self.is_radii_type_scalar and _is_torch(radii) and radii.numel() == 1):
+            return radii, None
+        hit = self._rscalar_src
+        if hit is None or hit[0] is not radii or hit[1] != radii._version:
+            hit = self._rscalar_src = self._read_scalar_tensor(radii, "radii")
+        return hit[2], radii
+
     def _density_changed(self):
         if getattr(self, "_handle", None) is not None:
             dens = _lib.MVX_GAUSSIAN if self.is_density_type_gaussian else _lib.MVX_BINARY
@@ -209,11 +282,11 @@ class Voxelizer(BaseVoxelizer):
         """torch-backend compatibility: a handle is bound to one GPU; moving re-creates it."""
         idx = self._resolve_device(device)
         if idx != self._device_index:
-            kw = {"sigma": self._sigma} if self.is_density_type_gaussian else {}
+            kw = {"sigma": self._sigma if self._sigma_src is None else self._sigma_src[0]} if self.is_density_type_gaussian else {}
             return type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
                               self.blockdim, idx, self.output, self.overlap_prepass,
                               grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
-                              radii_grad=self.radii_grad, **kw)
+                              radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, **kw)
         return self
 
     def cuda(self):
@@ -350,9 +423,12 @@ class Voxelizer(BaseVoxelizer):
     def forward_features(self, coords, center, features, radii, random_translation=0.0, random_rotation=False,
                          out_grid=None):
         """coords (V,3), center (3,) | None, features (V,C), radii scalar | (V,) | (C,); out (C,D,H,W)."""
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, rten = self._scalar_radius(radii)
         self._check_args_features(coords, features, radii, out_grid)
         C_ = features.shape[1]
-        grad = self._grad_wanted(coords, features, center, radii, out_grid)
+        grad = self._grad_wanted(coords, features, center, radii, out_grid, rten)
         c, f, r, in_kind, keep = self._prepare_inputs(coords, features, "features", radii)
         center = self._grad_center(center) if grad else center
         xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
@@ -363,7 +439,7 @@ class Voxelizer(BaseVoxelizer):
             xf, self._ptr(buf), in_kind, out_kind, self._stream())
         if grad:
             return self._autograd(launch, ret, "features", c, f, center, None, r, rs, np.array([0, c.shape[0]], np.int64),
-                                  self._xform_copy(xf), 1, C_)
+                                  self._xform_copy(xf), 1, C_, rten)
         rc = launch()
         if rc:
             _lib.check(rc)
@@ -391,6 +467,9 @@ class Voxelizer(BaseVoxelizer):
     def forward_types(self, coords, center, types, radii, random_translation=0.0, random_rotation=False,
                       out_grid=None):
         """coords (V,3), center (3,) | None, types (V,), radii scalar | (V,) | (C,); out (C,D,H,W)."""
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, rten = self._scalar_radius(radii)
         n_types = self._check_args_types(coords, types, radii, out_grid)
         if out_grid is not None:
             C_ = out_grid.shape[0]  # extra channels stay zero (numpy/voxelizer.py:337)
@@ -398,7 +477,7 @@ class Voxelizer(BaseVoxelizer):
             C_ = radii.shape[0]  # numpy/voxelizer.py:275-276
         else:
             C_ = n_types  # max(types) + 1 over ALL atoms, numpy/voxelizer.py:278
-        grad = self._grad_wanted(coords, None, center, radii, out_grid)
+        grad = self._grad_wanted(coords, None, center, radii, out_grid, rten)
         c, t, r, in_kind, keep = self._prepare_inputs(coords, types, "types", radii)
         if self.is_radii_type_channel_wise and r is not None and r.shape[0] < C_:
             # channel-wise radii are indexed by type only; pad so the (C,) contract of the ABI holds
@@ -413,7 +492,7 @@ class Voxelizer(BaseVoxelizer):
             xf, self._ptr(buf), in_kind, out_kind, self._stream())
         if grad:
             return self._autograd(launch, ret, "types", c, None, center, t, r, rs, np.array([0, c.shape[0]], np.int64),
-                                  self._xform_copy(xf), 1, int(C_))
+                                  self._xform_copy(xf), 1, int(C_), rten)
         rc = launch()
         if rc:
             _lib.check(rc)
@@ -469,8 +548,11 @@ class Voxelizer(BaseVoxelizer):
     # SINGLE  (replaces numpy/voxelizer.py:370-477)
     def forward_single(self, coords, center, radii, random_translation=0.0, random_rotation=False, out_grid=None):
         """coords (V,3), center (3,) | None, radii scalar | (V,); out (1,D,H,W)."""
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, rten = self._scalar_radius(radii)
         self._check_args_single(coords, radii, out_grid)
-        grad = self._grad_wanted(coords, None, center, radii, out_grid)
+        grad = self._grad_wanted(coords, None, center, radii, out_grid, rten)
         c, _, r, in_kind, keep = self._prepare_inputs(coords, None, None, radii)
         center = self._grad_center(center) if grad else center
         xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
@@ -481,7 +563,7 @@ class Voxelizer(BaseVoxelizer):
             xf, self._ptr(buf), in_kind, out_kind, self._stream())
         if grad:
             return self._autograd(launch, ret, "single", c, None, center, None, r, rs, np.array([0, c.shape[0]], np.int64),
-                                  self._xform_copy(xf), 1, 1)
+                                  self._xform_copy(xf), 1, 1, rten)
         rc = launch()
         if rc:
             _lib.check(rc)
@@ -512,6 +594,9 @@ class Voxelizer(BaseVoxelizer):
         out_grid: (B,C,D,H,W) of this voxelizer's grid_dtype (torch CUDA tensor on this device or numpy), fully overwritten.
         A random transform, if requested, is drawn per molecule in molecule order.
         """
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, rten = self._scalar_radius(radii)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         B = offsets.shape[0] - 1
         assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
@@ -524,7 +609,7 @@ class Voxelizer(BaseVoxelizer):
         else:
             kind, C_ = "features", channels.shape[1]
         self._check_args_batch(coords, channels, kind, radii, int(C_))
-        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers, radii, out_grid)
+        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers, radii, out_grid, rten)
         user_centers = centers  # (a conversion made below, for autograd or for the ABI, is "fresh")
         if grad and centers is not None:
             centers = self._grad_center(centers)
@@ -588,7 +673,7 @@ class Voxelizer(BaseVoxelizer):
         if grad:
             return self._autograd(launch, ret, kind or "single", c, ch if kind == "features" else None,
                                   dev_cen, ch if kind == "types" else None, r, rs, offsets,
-                                  xfs if need_xf else None, B, int(C_))
+                                  xfs if need_xf else None, B, int(C_), rten)
         _lib.check(launch())
         return self._finish_out(buf, ret, how)
 
@@ -620,16 +705,19 @@ class Voxelizer(BaseVoxelizer):
 
     # ------------------------------------------------------------------------------------------
     # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
-    def _grad_wanted(self, coords, features, center, radii, out_grid) -> bool:
+    def _grad_wanted(self, coords, features, center, radii, out_grid, rten=None) -> bool:
         """True when this call must record an autograd graph: differentiable voxelizer, grad mode on, and coords / features /
-        center (or, with radii_grad, radii) a tensor that requires grad. Raises for what the backward pass does not cover."""
+        center (or, with radii_grad, radii; with sigma_grad, the sigma tensor) a tensor that requires grad. `rten`: the
+        scalar-radius tensor of the call (_scalar_radius). Raises for what the backward pass does not cover."""
         if not self.differentiable or torch is None or not torch.is_grad_enabled():
             return False
         if _is_torch(radii) and radii.requires_grad and not self.radii_grad:
             raise NotImplementedError("gradients with respect to radii are not supported unless the voxelizer is created with "
                                       "radii_grad=True")
         tracked = [x for x in (coords, features, center, radii) if _is_torch(x) and x.requires_grad]
-        if not tracked:
+        # sigma and a scalar radius travel as host values: their tensors may live anywhere
+        scalars = [x for x in (self.sigma_tensor, rten) if x is not None and x.requires_grad]
+        if not tracked and not scalars:
             return False
         for x in tracked + [coords]:
             if not self._on_device(x):
@@ -651,22 +739,25 @@ class Voxelizer(BaseVoxelizer):
         """The mvx_xform record of a single-molecule call (the voxelizer reuses its own), or None."""
         return None if xf is None else _lib.MvxXform.from_buffer_copy(_lib.MvxXform.from_address(xf))
 
-    def _autograd(self, launch, ret, mode, c, f, center, types, r, rs, offsets, xforms, B, C_):
+    def _autograd(self, launch, ret, mode, c, f, center, types, r, rs, offsets, xforms, B, C_, rten=None):
         cen = center if (_is_torch(center) and self._on_device(center)) else None
         # radii_grad: the radii as the call hands them to the library (dtype conversion / type padding recorded by autograd)
         rin = r if (self.radii_grad and _is_torch(r) and r.requires_grad) else None
         spec = dict(mode=mode, types=types, radii=r, rs=rs, offsets=np.ascontiguousarray(offsets, np.int64), xforms=xforms,
                     B=B, C=C_, settings=self._grad_settings())
-        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen, rin)
+        sig = self.sigma_tensor
+        sig = sig if (sig is not None and sig.requires_grad) else None
+        rsc = rten if (rten is not None and rten.requires_grad) else None
+        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen, rin, sig, rsc)
 
     def _grad_settings(self):
         """What the backward reads from the voxelizer rather than from the call: density, sigma and radii type."""
         return (self.density_type, float(getattr(self, "_sigma", 0.5)) if self.is_density_type_gaussian else None,
                 self.radii_type)
 
-    def _backward(self, spec, c, f, grad, need_features, need_radii=False):
-        """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None, dL/dradii shaped and typed like the call's radii or None)
-        for dL/dgrid = grad, on the current stream."""
+    def _backward(self, spec, c, f, grad, need_features, need_radii=False, need_sigma=False, need_rscalar=False):
+        """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None, dL/dradii shaped and typed like the call's radii or None,
+        dL/dsigma and dL/d(scalar radius) as 0-dim float64 device tensors or None) for dL/dgrid = grad, on the current stream."""
         now = self._grad_settings()
         if now != spec["settings"]:
             raise RuntimeError(
@@ -678,20 +769,26 @@ class Voxelizer(BaseVoxelizer):
         gf = torch.empty((c.shape[0], spec["C"]), dtype=self._tfp, device=self.device) if need_features else None
         r = spec["radii"]
         gr = torch.zeros(r.shape[0], dtype=torch.float64, device=self.device) if need_radii else None
+        gs = torch.zeros(2, dtype=torch.float64, device=self.device) if (need_sigma or need_rscalar) else None  # [sigma, radius]
+        gsig = gs[0] if need_sigma else None
+        grs = gs[1] if need_rscalar else None
         if c.shape[0] == 0:  # no atoms: no gradient rows (the library would see null outputs); channel-wise radii get zeros
-            return gc, gf, None if gr is None else gr.to(r.dtype)
+            return gc, gf, None if gr is None else gr.to(r.dtype), gsig, grs
         mode = spec["mode"]
         ch = f if mode == "features" else spec["types"]
         xf = spec["xforms"]
         args = (self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), spec["rs"],
                 self._radii_type_code(), spec["offsets"].ctypes.data, None if xf is None else C.addressof(xf), spec["B"],
                 spec["C"], self._ptr(g), self._ptr(gc), self._ptr(gf))
-        if gr is None:
+        if gs is not None:  # the radius walk with its partials reduced over the call: dL/dsigma, dL/d(scalar radius)
+            rc = self._lib.mvx_backward_density_batch(*args, self._ptr(gr), gs.data_ptr() if need_sigma else None,
+                                                      gs.data_ptr() + 8 if need_rscalar else None, self._stream())
+        elif gr is None:
             rc = self._lib.mvx_backward_batch(*args, self._stream())
         else:  # one walk: the same coordinate / feature bits as mvx_backward_batch, and dL/dradii
             rc = self._lib.mvx_backward_radii_batch(*args, self._ptr(gr), self._stream())
         _lib.check(rc)
-        return gc, gf, None if gr is None else gr.to(r.dtype)
+        return gc, gf, None if gr is None else gr.to(r.dtype), gsig, grs
 
     # ------------------------------------------------------------------------------------------
     # measurement hooks used by bench.py (HIP events around the voxelize kernel on the launch stream)
@@ -724,22 +821,26 @@ class Voxelizer(BaseVoxelizer):
 if torch is not None:
 
     class _VoxelizeFunction(torch.autograd.Function):
-        """grid = voxelize(coords, features, center, radii): the forward call as it runs without autograd (same kernels, same
-        bits); backward = mvx_backward_batch from the saved inputs and the call's mvx_xform records."""
+        """grid = voxelize(coords, features, center, radii, sigma, scalar radius): the forward call as it runs without autograd
+        (same kernels, same bits); backward = mvx_backward_batch (mvx_backward_radii_batch with radii, mvx_backward_density_batch
+        with sigma or a scalar radius) from the saved inputs and the call's mvx_xform records."""
 
         @staticmethod
-        def forward(ctx, vox, launch, ret, spec, c, f, cen, r):
+        def forward(ctx, vox, launch, ret, spec, c, f, cen, r, sig, rsc):
             _lib.check(launch())
             ctx.vox, ctx.spec = vox, spec
             ctx.save_for_backward(c, f, cen)
+            ctx.scalars = (sig, rsc)  # (read for their shape, dtype and device only: the values travelled as host floats)
             return ret
 
         @staticmethod
         @torch.autograd.function.once_differentiable
         def backward(ctx, grad):
             c, f, cen = ctx.saved_tensors
-            need_c, need_f, need_cen, need_r = ctx.needs_input_grad[4:8]
-            gc, gf, gr = ctx.vox._backward(ctx.spec, c, f, grad, need_f, need_r)
+            need_c, need_f, need_cen, need_r, need_sig, need_rsc = ctx.needs_input_grad[4:10]
+            gc, gf, gr, gsig, grs = ctx.vox._backward(ctx.spec, c, f, grad, need_f, need_r, need_sig, need_rsc)
+            like = lambda g, t: None if g is None else g.to(dtype=t.dtype).reshape(t.shape).to(t.device)  # noqa: E731
+            gsig, grs = like(gsig, ctx.scalars[0]), like(grs, ctx.scalars[1])
             gcen = None
             if need_cen:  # p = M (coords - center) + t: dL/dcenter = -sum of dL/dcoords over the molecule
                 if cen.numel() == 3:
@@ -747,7 +848,7 @@ if torch is not None:
                 else:
                     lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
                     gcen = -torch.segment_reduce(gc, "sum", lengths=lengths, axis=0).reshape(cen.shape)
-            return None, None, None, None, gc if need_c else None, gf, gcen, gr
+            return None, None, None, None, gc if need_c else None, gf, gcen, gr, gsig, grs
 
 
 def transform_on_device(coords, center, translation, quaternion):
