@@ -84,6 +84,15 @@ enum mvx_xform_flags {
 enum mvx_grid_type { MVX_GRID_REAL = 0, MVX_GRID_BF16 = 1 };
 
 /*
+ * Memory layout of the grid (mvx_set_grid_layout). MVX_LAYOUT_NCDHW: (B, C, D, D, D) with z fastest, the default and the
+ * reference's. MVX_LAYOUT_NDHWC (channels-last; precision 32 only, float32 or bfloat16 elements): element (b, c, x, y, z) lies
+ * at index (((b D + x) D + y) D + z) C + c of `out` - torch.channels_last_3d of the same logical (B, C, D, D, D) tensor, what
+ * the 3D convolutions want. Every value is bit for bit the one the NCDHW handle writes, every element is written once per
+ * call, zeros included; only addresses differ. With C == 1 the two layouts coincide.
+ */
+enum mvx_grid_layout { MVX_LAYOUT_NCDHW = 0, MVX_LAYOUT_NDHWC = 1 };
+
+/*
  * Geometry + density of one voxelizer. Replaces the constructor state of
  * BaseVoxelizer.__init__ (base/voxelizer.py:15-38) and numpy Voxelizer.__init__/_setup_block
  * (numpy/voxelizer.py:22-58).
@@ -142,6 +151,13 @@ int mvx_set_density(mvx_handle *h, int32_t density, double sigma);
  * on the stream. Applies to MVX_DEVICE inputs and outputs on the batched three-launch path; other calls are unaffected.
  */
 int mvx_set_overlap(mvx_handle *h, int32_t enable);
+/*
+ * Layout of the grids the forward entry points write from now on (enum mvx_grid_layout; a new handle writes MVX_LAYOUT_NCDHW).
+ * MVX_ERR_INVALID, before any device is touched: an unknown layout value, a NULL handle, MVX_LAYOUT_NDHWC on a precision-64
+ * handle. Host outputs (MVX_HOST) are supported: the staging buffer is written in the layout and copied as it is. The
+ * backward entry points read `grad_out` as (B, C, D, D, D) contiguous whatever the handle's layout.
+ */
+int mvx_set_grid_layout(mvx_handle *h, int32_t layout);
 
 /*
  * Batched entry points: B molecules stored back to back, molecule b owning atoms
@@ -363,6 +379,11 @@ int mvx_plan_call(const mvx_plan_query *query, mvx_plan *plan);
  * stands for the grid's 8-byte alignment (one store of four bfloat16 voxels), and the plan is the float32 plan of that query.
  * MVX_ERR_INVALID for an unknown grid_type, and for MVX_GRID_BF16 with precision 64. */
 int mvx_plan_call_grid(const mvx_plan_query *q, int32_t grid_type, mvx_plan *p);
+/* ... and of the given mvx_grid_layout; mvx_plan_call_grid is layout 0. MVX_LAYOUT_NDHWC: `out_aligned16` is the grid's 16-byte
+ * alignment for either element type, vec_store = 1 exactly when every voxel's channel run starts on a 16-byte boundary
+ * (C * element size a multiple of 16, aligned grid), rows are cut into slabs of at most 8 waves, no pacing, no XCD ranges;
+ * C == 1 gives the contiguous plan. MVX_ERR_INVALID for an unknown layout, and for MVX_LAYOUT_NDHWC with precision 64. */
+int mvx_plan_call_layout(const mvx_plan_query *q, int32_t grid_type, int32_t layout, mvx_plan *p);
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,7 @@ struct mvx_handle {
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
     // more than it saves (profiles/r05_grad.txt)
     int grad_order = 0;
+    int32_t layout = MVX_LAYOUT_NCDHW; // mvx_set_grid_layout
     int narrow_sub = 0; // "narrow_sub" option: sub-tiles per wave of narrow chunks (1: voxelize_kernel; 2 | 4: voxelize_narrow_kernel; 0: the rule)
     int dbg = 0; // diagnostic builds (-DMVX_DIAG) only
 };
@@ -409,10 +410,12 @@ int run(mvx_handle *h, const RunArgs &r) {
     q.B = r.B;
     q.C = r.C;
     // (a bfloat16 grid's vector store is 8 bytes: mvx_plan_call_grid)
-    q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & (bf16 ? 7u : 15u)) == 0 ? 1 : 0;
+    // channels-last grids (C > 1; one channel IS the contiguous layout): 16-byte channel runs for either element type
+    const bool ndhwc = h->layout == MVX_LAYOUT_NDHWC && !f64 && r.C > 1;
+    q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & ((bf16 && !ndhwc) ? 7u : 15u)) == 0 ? 1 : 0;
     q.total_atoms = total;
     q.max_atoms = max_atoms;
-    const mvx_plan plan = plan_call(q, h->knobs);
+    const mvx_plan plan = plan_call(q, h->knobs, ndhwc ? MVX_LAYOUT_NDHWC : MVX_LAYOUT_NCDHW, bf16 ? 2 : 4);
     const bool direct = plan.route == MVX_ROUTE_DIRECT;
     const bool mx64 = plan.route == MVX_ROUTE_F64_MX;
     const int ct = plan.ct, ncc = plan.ncc, nchunk = plan.nchunk;
@@ -536,6 +539,7 @@ int run(mvx_handle *h, const RunArgs &r) {
     va.kc = d_kc;
     va.out = d_out;
     va.bf16 = bf16 ? 1 : 0;
+    va.ndhwc = ndhwc ? 1 : 0;
     va.narrow_sub = h->narrow_sub;
     va.p.res = g.res;
     va.p.half = g.half;
@@ -567,7 +571,7 @@ int run(mvx_handle *h, const RunArgs &r) {
     // per-lane-range kernels, voxelize_runs_kernel (the matrix-core walk of 32-channel chunks) and voxelize_pair_runs_kernel
     // (the candidate-pair walk of narrow chunks), nowhere else
     const bool lr_blocks = plan.lane_range != 0;
-    const bool runs = !f64 && !va.p.vec_store;
+    const bool runs = !f64 && !ndhwc && !va.p.vec_store; // (channels-last: both store forms live in every kernel)
     const bool lane_range = lr_blocks || runs;
     auto lane_range_for = [&](int32_t) { return lr_blocks; }; // (run-wise write-out: voxelize_runs_kernel / voxelize_pair_runs_kernel)
 
@@ -593,7 +597,7 @@ int run(mvx_handle *h, const RunArgs &r) {
                 if (r.in_kind == MVX_HOST) resolve_host_centers(&da.pa.xf_one, 1);
             }
         }
-        if ((rc = timed_launch(h, s, [&] { return launch_voxelize_direct(da, va.p, max_atoms, d_out, bf16, ct, gauss, lr_blocks, s); })))
+        if ((rc = timed_launch(h, s, [&] { return launch_voxelize_direct(da, va.p, max_atoms, d_out, bf16, ndhwc, ct, gauss, lr_blocks, s); })))
             return rc;
         if (in.slot) {
             HIP_TRY(hipEventRecord(in.slot->done, s));
@@ -650,6 +654,7 @@ int run(mvx_handle *h, const RunArgs &r) {
                 continue;
             }
             va.p.ncc = plan.nfull;
+            va.p.ncc_inv = umulhi_inverse(plan.nfull); // (the main launch of a call with a remainder launch has nfull, not ncc, chunks per molecule)
             va.p.c0 = 0;
             // the bracket holds voxelize_kernel alone (what rocprofv3 reports under that name)
             if ((rc = timed_launch(h, s, [&] { return launch_voxelize(va, b1 - b0, ct, gauss, lane_range_for(ct), s); }))) return rc;
@@ -771,6 +776,15 @@ int mvx_set_density(mvx_handle *h, int32_t density, double sigma) {
         h->cfg.sigma = sigma;
         h->sigma32 = (float)sigma;
     }
+    return MVX_OK;
+}
+
+int mvx_set_grid_layout(mvx_handle *h, int32_t layout) {
+    if (layout != MVX_LAYOUT_NCDHW && layout != MVX_LAYOUT_NDHWC) return fail(MVX_ERR_INVALID, "unknown grid layout");
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (layout == MVX_LAYOUT_NDHWC && h->cfg.precision == 64)
+        return fail(MVX_ERR_INVALID, "a channels-last grid needs precision 32");
+    h->layout = layout;
     return MVX_OK;
 }
 

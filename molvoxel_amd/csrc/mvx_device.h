@@ -472,6 +472,103 @@ __device__ __forceinline__ void store_q(__bf16 *dst, const float4 v) {
     __builtin_nontemporal_store(__builtin_bit_cast(u2, y), reinterpret_cast<u2 *>(dst));
 }
 
+// ---- channels-last (NDHWC) grids (mvx_set_grid_layout) -------------------------------------------------------------------
+// Layout is a compile-time policy carried by the element type parameter: OT = Ndhwc<float> | Ndhwc<__bf16> selects the
+// channels-last write-out of the same walk; grid_elem<OT> gives the element type the pointer has. Element (b, c, x, y, z) lies at
+// (((b D + x) D + y) D + z) C + c: the CT channels a lane holds for its voxel are ONE contiguous run of the grid, so they are
+// stored straight from the accumulator registers - no LDS tile, no barrier, no run-wise machinery (store_runs exists because
+// NCDHW rows of odd D are unaligned; here alignment depends on C alone). Two store forms, chosen per call
+// (VoxParams::vec_store): 16-byte non-temporal stores when every channel run starts on a 16-byte boundary (C % 4 == 0 for
+// float, C % 8 == 0 for bfloat16, and an aligned grid), else one plain store per element (C = 5, 33, remainder chunks of such
+// C, grids off alignment: the lines are completed in L2 by the neighbouring lanes). Unpaced: the NCDHW sleeps were tuned for
+// another store stream.
+template <typename ET>
+struct Ndhwc {};
+template <typename OT>
+struct grid_elem {
+    typedef OT type;
+    static constexpr bool NDHWC = false;
+};
+template <typename ET>
+struct grid_elem<Ndhwc<ET>> {
+    typedef ET type;
+    static constexpr bool NDHWC = true;
+};
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 pack_bf16x8(float a, float b, float c, float d, float e, float f, float g, float h) {
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    typedef unsigned u2 __attribute__((ext_vector_type(2)));
+    const u2 lo = __builtin_bit_cast(u2, __builtin_convertvector(((f4){a, b, c, d}), bf16x4));
+    const u2 hi = __builtin_bit_cast(u2, __builtin_convertvector(((f4){e, f, g, h}), bf16x4));
+    return (u32x4){lo.x, lo.y, hi.x, hi.y};
+}
+// N consecutive channels of one voxel, v[i] -> dst[i] = channel ch0 + i (channels >= C do not exist). vec: 16-byte stores - the
+// caller guarantees 16-byte aligned runs, and groups then lie wholly inside or outside C.
+template <int N>
+__device__ __forceinline__ void store_channels(float *dst, const float (&v)[N], int ch0, int C, bool vec) {
+    if constexpr (N % 4 == 0) {
+        if (vec) {
+#pragma unroll
+            for (int g = 0; g < N / 4; ++g)
+                if (ch0 + 4 * g < C) store_f4(dst + 4 * g, make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]));
+            return;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        if (ch0 + i < C) dst[i] = v[i];
+}
+template <int N>
+__device__ __forceinline__ void store_channels(__bf16 *dst, const float (&v)[N], int ch0, int C, bool vec) {
+    if constexpr (N % 8 == 0) {
+        if (vec) {
+#pragma unroll
+            for (int g = 0; g < N / 8; ++g)
+                if (ch0 + 8 * g < C)
+                    __builtin_nontemporal_store(pack_bf16x8(v[8 * g], v[8 * g + 1], v[8 * g + 2], v[8 * g + 3], v[8 * g + 4], v[8 * g + 5],
+                                                            v[8 * g + 6], v[8 * g + 7]),
+                                                reinterpret_cast<u32x4 *>(dst + 8 * g));
+            return;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        if (ch0 + i < C) dst[i] = (__bf16)v[i];
+}
+// One voxel per lane (OpsF32, OpsPair, the narrow kernels): the lane's CT accumulators to its voxel of sub-tile `subtile`.
+// An empty slab's accumulators are the zeros they were set to: the same stores are its zero fill.
+template <int CT, typename ET>
+__device__ __forceinline__ void write_ndhwc(const float2v (&acc)[(CT + 1) / 2], int lane, int subtile, int b, int cbase, int x0, int y0,
+                                            int z0, ET *out, const VoxParams &P) {
+    const int D = P.D;
+    const int ix = x0 + (lane >> (SUBZ_SH + SUBY_SH)), iy = y0 + ((lane >> SUBZ_SH) & (SUBY - 1)), iz = z0 + SUBZ * subtile + (lane & (SUBZ - 1));
+    if (ix >= D || iy >= D || iz >= D) return;
+    float v[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) v[c] = (c & 1) ? acc[c / 2].y : acc[c / 2].x;
+    ET *dst = out + ((((size_t)b * D + ix) * D + iy) * D + iz) * (size_t)P.C + cbase;
+    store_channels<CT>(dst, v, cbase, P.C, P.vec_store != 0);
+}
+// ... and NSUB accumulator sets of one lane (the narrow kernels: sub-tiles subtile0 .. subtile0 + NSUB - 1, SUBZ voxels apart
+// along z): one address, NSUB offsets
+template <int CT, int NSUB, typename ET>
+__device__ __forceinline__ void write_ndhwc_sets(const float2v (&acc)[NSUB][(CT + 1) / 2], int lane, int subtile0, int b, int cbase, int x0,
+                                                 int y0, int z0, ET *out, const VoxParams &P) {
+    const int D = P.D;
+    const int ix = x0 + (lane >> (SUBZ_SH + SUBY_SH)), iy = y0 + ((lane >> SUBZ_SH) & (SUBY - 1)), iz = z0 + SUBZ * subtile0 + (lane & (SUBZ - 1));
+    if (ix >= D || iy >= D) return;
+    ET *dst = out + ((((size_t)b * D + ix) * D + iy) * D + iz) * (size_t)P.C + cbase;
+    const int step = SUBZ * P.C;
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s) {
+        if (iz + SUBZ * s >= D) break;
+        float v[CT];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) v[c] = (c & 1) ? acc[s][c / 2].y : acc[s][c / 2].x;
+        store_channels<CT>(dst + s * step, v, cbase, P.C, P.vec_store != 0);
+    }
+}
+
 // floats per tile row: SUBZ*NW plus a pad that keeps ds_write_b32 conflict-free for the lane -> (row, column) map
 __host__ __device__ __forceinline__ int row_stride_floats(int NW) { return SUBZ * NW + 8; }
 // words per staged row: 16 of record + the channel weights, padded to an ODD number of 16-B quads - the row filter reads one
@@ -814,8 +911,11 @@ struct OpsF32 {
     }
     static __device__ __forceinline__ void write(const Acc &acc, bool any, unsigned *un, int tid, int lane, int wave, int NW,
                                                  int b, const LaneCtx &L, int x0, int y0, int z0, void *out, const VoxParams &P) {
-        write_slab<CT, LANE_RANGE, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0,
-                                               z0, static_cast<OT *>(out), P);
+        if constexpr (grid_elem<OT>::NDHWC)
+            write_ndhwc<CT>(acc, lane, wave, b, L.cbase, x0, y0, z0, static_cast<typename grid_elem<OT>::type *>(out), P);
+        else
+            write_slab<CT, LANE_RANGE, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0,
+                                                   z0, static_cast<OT *>(out), P);
     }
 };
 

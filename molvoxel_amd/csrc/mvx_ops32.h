@@ -126,12 +126,63 @@ struct OpsMx32 {
             }
         }
     }
+    // Channels-last write-out: lane l holds, for voxel (ly, lz) = ((l % 32) / 8, l % 8) of the x0 plane (p0) and of the x0 + 1
+    // plane (p1), the channels 8 m + 4 (l / 32) + 0..3 in registers 4 m + 0..3 - four runs of 16 bytes (float) per plane, and
+    // lanes l, l + 32 together cover 32 contiguous bytes of the voxel's 128-byte line per store instruction; the four
+    // instructions of a plane complete every line. bfloat16: v_permlane32_swap hands the lower lane channels 16 k .. 16 k + 7
+    // and the upper lane 16 k + 8 .. 16 k + 15 of a register pair (the two halves hold the same voxel), one 16-byte store each.
+    static __device__ __forceinline__ void store_plane(const f16v &p, float *d, int ch, int C, bool vec, bool ok, int h) {
+        if (!ok) return;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const float v[4] = {p[4 * m], p[4 * m + 1], p[4 * m + 2], p[4 * m + 3]};
+            store_channels<4>(d + 8 * m + 4 * h, v, ch + 8 * m + 4 * h, C, vec);
+        }
+    }
+    static __device__ __forceinline__ void store_plane(const f16v &p, __bf16 *d, int ch, int C, bool vec, bool ok, int h) {
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        typedef unsigned u2 __attribute__((ext_vector_type(2)));
+        if (vec) { // (uniform; the swaps run with every lane active: both halves of a voxel share `ok`)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const u2 a = __builtin_bit_cast(u2, __builtin_convertvector(((f4){p[8 * k], p[8 * k + 1], p[8 * k + 2], p[8 * k + 3]}), bf16x4));
+                const u2 c = __builtin_bit_cast(u2, __builtin_convertvector(((f4){p[8 * k + 4], p[8 * k + 5], p[8 * k + 6], p[8 * k + 7]}), bf16x4));
+                const auto sx = __builtin_amdgcn_permlane32_swap(a.x, c.x, false, false);
+                const auto sy = __builtin_amdgcn_permlane32_swap(a.y, c.y, false, false);
+                const int o = 16 * k + 8 * h;
+                if (ok && ch + o < C) __builtin_nontemporal_store((u32x4){sx[0], sy[0], sx[1], sy[1]}, reinterpret_cast<u32x4 *>(d + o));
+            }
+            return;
+        }
+        if (!ok) return;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const float v[4] = {p[4 * m], p[4 * m + 1], p[4 * m + 2], p[4 * m + 3]};
+            store_channels<4>(d + 8 * m + 4 * h, v, ch + 8 * m + 4 * h, C, false);
+        }
+    }
+    template <typename ET>
+    static __device__ __forceinline__ void write_ndhwc_mx(const Acc &acc, int lane, int subtile, int b, int cbase, int x0, int y0, int z0,
+                                                          ET *out, const VoxParams &P) {
+        const int D = P.D, h = lane >> 5;
+        const int iy = y0 + ((lane >> SUBZ_SH) & (SUBY - 1)), iz = z0 + SUBZ * subtile + (lane & (SUBZ - 1));
+        const bool yz = iy < D && iz < D;
+        const size_t C = (size_t)P.C;
+        ET *d = out + ((((size_t)b * D + x0) * D + iy) * D + iz) * C + cbase; // (formed for lanes outside the grid too, never used there)
+        store_plane(acc.p0, d, cbase, P.C, P.vec_store != 0, yz && x0 < D, h);
+        store_plane(acc.p1, d + (size_t)D * D * C, cbase, P.C, P.vec_store != 0, yz && x0 + 1 < D, h);
+    }
     static __device__ __forceinline__ void write(const Acc &acc, int any, unsigned *un, int tid, int lane, int wave, int NW,
                                                  int b, const LaneCtx &L, int x0, int y0, int z0, void *out_, const VoxParams &P) {
-        OT *out = static_cast<OT *>(out_);
+        typedef typename grid_elem<OT>::type ET; // (OT itself but for the channels-last tags)
+        ET *out = static_cast<ET *>(out_);
+        if constexpr (grid_elem<OT>::NDHWC) { // channels-last grids: straight from the accumulator registers
+            write_ndhwc_mx(acc, lane, wave, b, L.cbase, x0, y0, z0, out, P);
+            return;
+        }
         if (!any) { // zero fill without the LDS round trip: the one-voxel-per-lane code (no accumulator is read)
             float2v zero[16];
-            write_slab<32, RUNS, CR_F32, OT>(zero, false, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0, out, P);
+            write_slab<32, RUNS, CR_F32, ET>(zero, false, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0, out, P);
             return;
         }
         float *tile = reinterpret_cast<float *>(un);
@@ -145,7 +196,7 @@ struct OpsMx32 {
         const int q = tid - rfirst * F4, zq = z0 + 4 * q;
         const int sxx = (rfirst >> SUBY_SH) & (SUBX - 1), syy = rfirst & (SUBY - 1), cfirst = rfirst / RPC;
         const bool vox_ok = (x0 + sxx < D) && (y0 + syy < D) && (zq < D);
-        OT *dst0 = out + ((size_t)b * P.C + L.cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
+        ET *dst0 = out + ((size_t)b * P.C + L.cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
         // this lane's voxel column in the tile, and the first of its four channels of a round
         const int lz = lane & (SUBZ - 1), ly = (lane >> SUBZ_SH) & (SUBY - 1), h = lane >> 5;
         float *mine = tile + (4 * h * RPC + ly) * RS + SUBZ * wave + lz; // + (c * RPC + x * SUBY) * RS
@@ -181,8 +232,8 @@ struct OpsMx32 {
                 for (int i = 0; i < NW; i += 2) __builtin_amdgcn_s_sleep(pacing<OT>::round_sleep_step);
         };
         if (RUNS && !P.vec_store) { // rows that are not whole 16-byte quads: the tile holds the slab's runs as they lie in memory
-            const RunLayout R = run_layout<16 / sizeof(OT)>(NW, x0, y0, z0, P);
-            OT *rtile = reinterpret_cast<OT *>(un); // (a bfloat16 grid: a bfloat16 tile, store_runs)
+            const RunLayout R = run_layout<16 / sizeof(ET)>(NW, x0, y0, z0, P);
+            ET *rtile = reinterpret_cast<ET *>(un); // (a bfloat16 grid: a bfloat16 tile, store_runs)
             const size_t S0 = (((size_t)b * P.C + L.cbase) * D + x0) * D2 + (size_t)y0 * D + z0;
             const int col = SUBZ * wave + lz;
             const bool zok = !R.joined || col < D;
@@ -195,12 +246,12 @@ struct OpsMx32 {
                 if (zok) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
-                        rtile[L0 + mine_r + c * R.SC] = (OT)acc.p0[4 * rd + c];
-                        rtile[L0 + mine_r + c * R.SC + R.SX] = (OT)acc.p1[4 * rd + c];
+                        rtile[L0 + mine_r + c * R.SC] = (ET)acc.p0[4 * rd + c];
+                        rtile[L0 + mine_r + c * R.SC + R.SX] = (ET)acc.p1[4 * rd + c];
                     }
                 }
                 __syncthreads();
-                store_runs<false, OT>(rtile, R, L0, CR, L.cbase + rd * CR, S0r, tid, NW * 64, out, P);
+                store_runs<false, ET>(rtile, R, L0, CR, L.cbase + rd * CR, S0r, tid, NW * 64, out, P);
             }
             return;
         }
@@ -313,8 +364,11 @@ struct OpsPair {
     }
     static __device__ __forceinline__ void write(const Acc &acc, bool any, unsigned *un, int tid, int lane, int wave, int NW,
                                                  int b, const LaneCtx &L, int x0, int y0, int z0, void *out, const VoxParams &P) {
-        write_slab<CT, RUNS, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0,
-                                         static_cast<OT *>(out), P);
+        if constexpr (grid_elem<OT>::NDHWC)
+            write_ndhwc<CT>(acc, lane, wave, b, L.cbase, x0, y0, z0, static_cast<typename grid_elem<OT>::type *>(out), P);
+        else
+            write_slab<CT, RUNS, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0,
+                                             static_cast<OT *>(out), P);
     }
 };
 

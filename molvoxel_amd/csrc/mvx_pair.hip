@@ -118,6 +118,21 @@ __global__ void __launch_bounds__(1024) voxelize_pair_bf16_kernel(const DirectAr
     typedef typename PairOps<CT, GAUSS, LR, __bf16>::type Ops;
 #include "mvx_pair_body.inc"
 }
+// channels-last (NDHWC) grids: the same body with the channels-last write-out (Ops<..., Ndhwc<...>>), under names of their own
+template <int CT, bool GAUSS, bool XF, bool LR = false>
+__global__ void __launch_bounds__(1024) voxelize_pair_ndhwc_kernel(const DirectArgs A, float *__restrict__ out, const VoxParams P) {
+    typedef typename PairOps<CT, GAUSS, LR, Ndhwc<float>>::type Ops;
+#include "mvx_pair_body.inc"
+}
+template <int CT, bool GAUSS, bool XF, bool LR = false>
+__global__ void __launch_bounds__(1024) voxelize_pair_bf16_ndhwc_kernel(const DirectArgs A, __bf16 *__restrict__ out, const VoxParams P) {
+    typedef typename PairOps<CT, GAUSS, LR, Ndhwc<__bf16>>::type Ops;
+#include "mvx_pair_body.inc"
+}
+template <int CT, bool G, bool XF, bool LR>
+static auto pair_kernel(Ndhwc<float> *) { return &voxelize_pair_ndhwc_kernel<CT, G, XF, LR>; }
+template <int CT, bool G, bool XF, bool LR>
+static auto pair_kernel(Ndhwc<__bf16> *) { return &voxelize_pair_bf16_ndhwc_kernel<CT, G, XF, LR>; }
 template <int CT, bool G, bool XF, bool LR>
 static auto pair_kernel(float *) { return &voxelize_pair_kernel<CT, G, XF, LR>; }
 template <int CT, bool G, bool XF, bool LR>
@@ -127,12 +142,13 @@ static auto pair_kernel(__bf16 *) { return &voxelize_pair_bf16_kernel<CT, G, XF,
 // dispatch
 // ------------------------------------------------------------------------------------------------
 template <int CT, bool GAUSS, bool XF, bool LR, typename OT>
-static hipError_t launch_pair_t(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, OT *out, hipStream_t s) {
+static hipError_t launch_pair_t(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, OT *out_, hipStream_t s) {
+    typename grid_elem<OT>::type *out = reinterpret_cast<typename grid_elem<OT>::type *>(out_); // (OT: the element type or its channels-last tag)
     static LdsLimit raised;
     VoxParams q = p;
     q.dcap = pair_segw(max_atoms, p.NW);
     const size_t lds = pair_lds_bytes(CT, p.NW, q.dcap);
-    auto kern = pair_kernel<CT, GAUSS, XF, LR>(out);
+    auto kern = pair_kernel<CT, GAUSS, XF, LR>(out_);
     hipError_t e = raise_lds_limit(kern, lds, raised);
     if (e != hipSuccess) return e;
     launch_profiled(kern, dim3((unsigned)(p.nsy * ((p.nsx + 1) / 2)), (unsigned)(p.B * p.ncc)), dim3(p.NW * 128), lds, s, d, out, q);
@@ -166,8 +182,11 @@ static hipError_t launch_direct_t(const DirectArgs &d, const VoxParams &p, int64
 #undef MVX_CASE
     return hipErrorInvalidValue;
 }
-hipError_t launch_voxelize_direct(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, void *out, bool bf16, int32_t ct,
+hipError_t launch_voxelize_direct(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, void *out, bool bf16, bool ndhwc, int32_t ct,
                                   bool gauss, bool lane_range, hipStream_t s) {
+    if (ndhwc)
+        return bf16 ? launch_direct_t(d, p, max_atoms, static_cast<Ndhwc<__bf16> *>(out), ct, gauss, lane_range, s)
+                    : launch_direct_t(d, p, max_atoms, static_cast<Ndhwc<float> *>(out), ct, gauss, lane_range, s);
     return bf16 ? launch_direct_t(d, p, max_atoms, static_cast<__bf16 *>(out), ct, gauss, lane_range, s)
                 : launch_direct_t(d, p, max_atoms, static_cast<float *>(out), ct, gauss, lane_range, s);
 }

@@ -20,6 +20,7 @@ struct PlanKnobs {
     double mall_budget = MALL_BUDGET;
 };
 
-mvx_plan plan_call(const mvx_plan_query &q, const PlanKnobs &k);
+// layout: enum mvx_grid_layout; elem_bytes: bytes of a grid element (channels-last grids: the alignment of the channel runs)
+mvx_plan plan_call(const mvx_plan_query &q, const PlanKnobs &k, int32_t layout = MVX_LAYOUT_NCDHW, int32_t elem_bytes = 4);
 
 } // namespace mvx

@@ -64,10 +64,12 @@ void plan_slabs(int D, int max_waves, bool whole_rows, int force_nw, mvx_plan &p
 
 } // namespace
 
-mvx_plan plan_call(const mvx_plan_query &q, const PlanKnobs &k) {
+mvx_plan plan_call(const mvx_plan_query &q, const PlanKnobs &k, int32_t layout, int32_t elem_bytes) {
     mvx_plan p{};
     const int D = q.dimension, C = q.C, B = q.B;
     const bool f64 = q.precision == 64;
+    // channels-last (NDHWC) grids; with one channel the layout IS the contiguous one: the contiguous plan, the existing kernels
+    const bool ndhwc = layout == MVX_LAYOUT_NDHWC && !f64 && C > 1;
     const bool chanwise = q.radii_type == MVX_RADII_CHANNEL && q.mode == MODE_FEATURES;
     const int bd = q.blockdim > 0 ? q.blockdim : 8;
     const int nb = (D + bd - 1) / bd;
@@ -105,7 +107,19 @@ mvx_plan plan_call(const mvx_plan_query &q, const PlanKnobs &k) {
         }
     }
     p.route = f64 ? (mx64 ? MVX_ROUTE_F64_MX : MVX_ROUTE_F64_DENSE) : (direct ? MVX_ROUTE_DIRECT : MVX_ROUTE_BINNED);
-    if (p.route == MVX_ROUTE_BINNED) plan_slabs(D, 8, true, k.force_nw, p, !f64 && D % 4 == 0 && q.out_aligned16 != 0);
+    if (p.route == MVX_ROUTE_BINNED && !ndhwc) plan_slabs(D, 8, true, k.force_nw, p, !f64 && D % 4 == 0 && q.out_aligned16 != 0);
+    if (p.route == MVX_ROUTE_BINNED && ndhwc && k.force_nw == 0) {
+        // Channels-last: where a row is cut does not matter to the stores (a voxel's channels are one run whatever its
+        // neighbours are), so rows longer than 8 sub-tiles are cut into as few, equally long chunks as 8 waves allow - no
+        // 1024-thread kernel variants in this layout - and no half-empty last chunk (D = 72: 5 + 4 sub-tiles, not 8 + 1).
+        const int nsz = (D + SUBZ - 1) / SUBZ;
+        p.nzc = (nsz + 7) / 8;
+        p.nw = (nsz + p.nzc - 1) / p.nzc;
+        p.nzc = (nsz + p.nw - 1) / p.nw;
+    } else if (ndhwc && p.nw > 8) { // ("nw" measurement knob: this layout has no slabs of more than 8 waves)
+        p.nw = 8;
+        p.nzc = ((D + SUBZ - 1) / SUBZ + 7) / 8;
+    }
     const long long per_mol = (long long)p.nsx * p.nsy * p.nzc;
 
     // ---- remainder channels --------------------------------------------------------------------------------------------
@@ -146,7 +160,10 @@ mvx_plan plan_call(const mvx_plan_query &q, const PlanKnobs &k) {
     // 16-B stores need whole float4 groups per row (D % 4 == 0) and a 16-B aligned grid; anything else (odd dimensions, a
     // slice `grid[i]` of a batch grid whose slices are not 16-B multiples) is written run by run (store_runs)
     p.vec_store = (D % (f64 ? 2 : 4) == 0 && q.out_aligned16) ? 1 : 0;
-    p.xcd_ranges = (!f64 && !p.vec_store && p.nzc == 1) ? 1 : 0;
+    // channels-last: a function of C and the base alignment, not of D - every voxel's channel run (C elements) starts on a
+    // 16-byte boundary; anything else is stored element by element. No run-wise write-out, so no XCD ranges.
+    if (ndhwc) p.vec_store = (((long long)C * elem_bytes) % 16 == 0 && q.out_aligned16) ? 1 : 0;
+    p.xcd_ranges = (!f64 && !ndhwc && !p.vec_store && p.nzc == 1) ? 1 : 0;
     // a sub-tile lies inside one reference block when its edges divide blockdim (or there is a single block): the block
     // cull is then wave-uniform and already folded into the candidate ranges; otherwise every lane checks its voxel's index
     p.lane_range = !(nb == 1 || (bd % SUBX == 0 && bd % SUBY == 0 && bd % SUBZ == 0)) ? 1 : 0;
@@ -154,6 +171,7 @@ mvx_plan plan_call(const mvx_plan_query &q, const PlanKnobs &k) {
     // ---- pacing (mvx_tuning.h) ---------------------------------------------------------------------------------------------
     const long long wgs = (long long)B * per_mol * p.ncc;
     p.pace = wgs >= PACE_ROUNDS_MIN_WGS ? 2 : (wgs > PACE_EMPTY_MIN_WGS ? 1 : 0);
+    if (ndhwc) p.pace = 0; // (the sleeps were tuned for the NCDHW store stream; this write-out has none)
     return p;
 }
 
@@ -175,4 +193,16 @@ extern "C" int mvx_plan_call_grid(const mvx_plan_query *query, int32_t grid_type
     if (grid_type != MVX_GRID_REAL && grid_type != MVX_GRID_BF16) return MVX_ERR_INVALID;
     if (grid_type == MVX_GRID_BF16 && query && query->precision == 64) return MVX_ERR_INVALID;
     return mvx_plan_call(query, plan);
+}
+
+// The plan of a call on a grid of the given element type and layout (mvx_set_grid_layout). MVX_LAYOUT_NCDHW: mvx_plan_call_grid.
+// MVX_LAYOUT_NDHWC: `out_aligned16` is the grid's 16-byte alignment for either element type; vec_store says whether every
+// voxel's channel run starts on a 16-byte boundary. One channel: the contiguous plan (the layouts coincide).
+extern "C" int mvx_plan_call_layout(const mvx_plan_query *query, int32_t grid_type, int32_t layout, mvx_plan *plan) {
+    if (layout != MVX_LAYOUT_NCDHW && layout != MVX_LAYOUT_NDHWC) return MVX_ERR_INVALID;
+    if (layout == MVX_LAYOUT_NDHWC && query && query->precision == 64) return MVX_ERR_INVALID;
+    const int rc = mvx_plan_call_grid(query, grid_type, plan);
+    if (rc != MVX_OK || layout == MVX_LAYOUT_NCDHW) return rc;
+    *plan = mvx::plan_call(*query, mvx::PlanKnobs{}, layout, grid_type == MVX_GRID_BF16 ? 2 : 4);
+    return MVX_OK;
 }

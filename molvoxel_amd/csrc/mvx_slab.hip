@@ -78,6 +78,26 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
 #include "mvx_slab_body.inc"
 }
 
+// channels-last (NDHWC) grids (mvx_set_grid_layout): the same slab body with the channels-last write-out (Ops<..., Ndhwc<float>> /
+// Ops<..., Ndhwc<__bf16>>: every lane stores its voxel's channel run from registers), under names of their own. Slabs of at most
+// 8 waves only (plan_call cuts longer rows: a cut costs this layout nothing, a voxel's channels are whole 16-byte groups).
+template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
+__global__ void __launch_bounds__(MAXT, 8)
+    voxelize_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                          const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc, float *__restrict__ out,
+                          const VoxParams P) {
+    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED, Ndhwc<float>>::type Ops;
+#include "mvx_slab_body.inc"
+}
+template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
+__global__ void __launch_bounds__(MAXT, 8)
+    voxelize_bf16_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                               const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
+                               __bf16 *__restrict__ out, const VoxParams P) {
+    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED, Ndhwc<__bf16>>::type Ops;
+#include "mvx_slab_body.inc"
+}
+
 // ---- voxelize_narrow_kernel: narrow chunks with NSUB (2 or 4) sub-tiles per wave -------------------------------------------
 // What is left of a narrow launch after OpsPair is per-wave fixed cost: at cfg-3 density a wave walks two or three candidate
 // pairs (~85 vector instructions) around ~110 of prologue, staging, row filter and write-out, and as many scalar ones. Here a
@@ -93,7 +113,8 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
 constexpr int narrow_waves_per_simd(int ct, int nsub) { return 8; }
 template <int CT, bool GAUSS, int NSUB, typename OT>
 __device__ __forceinline__ void narrow_body(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                                            const uint2 *__restrict__ slist_ext, OT *__restrict__ out, const VoxParams &P) {
+                                            const uint2 *__restrict__ slist_ext, typename grid_elem<OT>::type *__restrict__ out, const VoxParams &P) {
+    typedef typename grid_elem<OT>::type ET; // (OT itself but for the channels-last tags)
     typedef OpsPair<CT, GAUSS, false, OT> Ops;
     constexpr int SW = Ops::SW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -202,6 +223,10 @@ __device__ __forceinline__ void narrow_body(const unsigned *__restrict__ rec, co
         }
     }
 
+    if constexpr (grid_elem<OT>::NDHWC) { // channels-last grids: every lane stores its voxels' channel runs from registers
+        write_ndhwc_sets<CT, NSUB>(acc, lane, NSUB * wave, b, cbase, x0, y0, z0, out, P);
+        return;
+    }
     // ---- write-out: [channel][x, y row][z] tile, CR_F32 channels per round, read back as float4 rows of the whole slab ----
     constexpr int CR = CT < CR_F32 ? CT : CR_F32, NROUND = CT / CR;
     const int D = P.D, RS = row_stride_floats(NS);
@@ -216,7 +241,7 @@ __device__ __forceinline__ void narrow_body(const unsigned *__restrict__ rec, co
     const int zq = z0 + 4 * q;
     const int sxx = (rfirst >> SUBY_SH) & (SUBX - 1), syy = rfirst & (SUBY - 1), cfirst = rfirst / RPC; // cfirst < CPP
     const bool vox_ok = (x0 + sxx < D) && (y0 + syy < D) && (zq < D);
-    OT *dst0 = out + ((size_t)b * P.C + cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
+    ET *dst0 = out + ((size_t)b * P.C + cbase + cfirst) * D3 + (size_t)(x0 + sxx) * D2 + (size_t)(y0 + syy) * D + zq;
     if (n_hdr == 0) { // zero fill without the LDS round trip, held back and sent in pieces in big launches (write_slab)
         if (P.pace) __builtin_amdgcn_s_sleep(pacing<OT>::empty_hold);
         if (vox_ok) {
@@ -261,13 +286,25 @@ template <int CT, bool GAUSS, int NSUB>
 __global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
     voxelize_narrow_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
                            const uint2 *__restrict__ slist_ext, float *__restrict__ out, const VoxParams P) {
-    narrow_body<CT, GAUSS, NSUB>(rec, w, slist, slist_ext, out, P);
+    narrow_body<CT, GAUSS, NSUB, float>(rec, w, slist, slist_ext, out, P);
 }
 template <int CT, bool GAUSS, int NSUB>
 __global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
     voxelize_narrow_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
                                 const uint2 *__restrict__ slist_ext, __bf16 *__restrict__ out, const VoxParams P) {
-    narrow_body<CT, GAUSS, NSUB>(rec, w, slist, slist_ext, out, P);
+    narrow_body<CT, GAUSS, NSUB, __bf16>(rec, w, slist, slist_ext, out, P);
+}
+template <int CT, bool GAUSS, int NSUB>
+__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
+    voxelize_narrow_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                                 const uint2 *__restrict__ slist_ext, float *__restrict__ out, const VoxParams P) {
+    narrow_body<CT, GAUSS, NSUB, Ndhwc<float>>(rec, w, slist, slist_ext, out, P);
+}
+template <int CT, bool GAUSS, int NSUB>
+__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
+    voxelize_narrow_bf16_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                                      const uint2 *__restrict__ slist_ext, __bf16 *__restrict__ out, const VoxParams P) {
+    narrow_body<CT, GAUSS, NSUB, Ndhwc<__bf16>>(rec, w, slist, slist_ext, out, P);
 }
 
 // 32-channel chunks of float32 grids whose rows are not whole 16-byte quads (odd dimensions, unaligned grid slices): the
@@ -367,6 +404,10 @@ template <int CT, bool G, bool LR, int MT, bool GR = false>
 static auto slab_kernel(float *) { return &voxelize_kernel<CT, G, LR, MT, GR>; }
 template <int CT, bool G, bool LR, int MT, bool GR = false>
 static auto slab_kernel(__bf16 *) { return &voxelize_bf16_kernel<CT, G, LR, MT, GR>; }
+template <int CT, bool G, bool LR, int MT, bool GR = false>
+static auto slab_kernel(Ndhwc<float> *) { return &voxelize_ndhwc_kernel<CT, G, LR, MT, GR>; }
+template <int CT, bool G, bool LR, int MT, bool GR = false>
+static auto slab_kernel(Ndhwc<__bf16> *) { return &voxelize_bf16_ndhwc_kernel<CT, G, LR, MT, GR>; }
 template <bool G, int MT>
 static auto runs_kernel(float *) { return &voxelize_runs_kernel<G, MT>; }
 template <bool G, int MT>
@@ -379,6 +420,10 @@ template <int CT, bool G, int NSUB>
 static auto narrow_kernel(float *) { return &voxelize_narrow_kernel<CT, G, NSUB>; }
 template <int CT, bool G, int NSUB>
 static auto narrow_kernel(__bf16 *) { return &voxelize_narrow_bf16_kernel<CT, G, NSUB>; }
+template <int CT, bool G, int NSUB>
+static auto narrow_kernel(Ndhwc<float> *) { return &voxelize_narrow_ndhwc_kernel<CT, G, NSUB>; }
+template <int CT, bool G, int NSUB>
+static auto narrow_kernel(Ndhwc<__bf16> *) { return &voxelize_narrow_bf16_ndhwc_kernel<CT, G, NSUB>; }
 
 template <typename OT>
 struct GroupedFn {
@@ -387,7 +432,7 @@ struct GroupedFn {
     hipStream_t s;
     template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT>
     hipError_t operator()() const {
-        if constexpr (CT != 32) {
+        if constexpr (CT != 32 || (grid_elem<OT>::NDHWC && MAXT > 512)) { // (channels-last: slabs of at most 8 waves)
             return hipErrorInvalidValue;
         } else {
             VoxParams p = a.p;
@@ -400,7 +445,7 @@ struct GroupedFn {
             hipError_t e = raise_lds_limit(kern, main_lds + 16 * CHAN_GROUP_SLOTS, raised);
             if (e != hipSuccess) return e;
             launch_profiled(kern, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), main_lds + 16 * CHAN_GROUP_SLOTS, s, a.rec, a.w,
-                            a.slist, a.slist_ext, a.Tc, a.kc, static_cast<OT *>(a.out), p);
+                            a.slist, a.slist_ext, a.Tc, a.kc, static_cast<typename grid_elem<OT>::type *>(a.out), p);
             return hipGetLastError();
         }
     }
@@ -413,6 +458,10 @@ struct LaunchFn {
     hipStream_t s;
     template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT>
     hipError_t operator()() const {
+        constexpr bool NDHWC = grid_elem<OT>::NDHWC;
+        typedef typename grid_elem<OT>::type ET;
+        if constexpr (NDHWC && MAXT > 512) return hipErrorInvalidValue; // (channels-last: slabs of at most 8 waves, plan_call)
+        else {
         const VoxParams &p = a.p;
         if (nb <= 0) return hipSuccess;
         if ((long long)nb * p.ncc > 65535) return hipErrorInvalidConfiguration;
@@ -422,18 +471,21 @@ struct LaunchFn {
         if (CT < 32 && !LANE_RANGE) lds = std::max(lds, (size_t)65 * cand_stride_words(CT) * 4); // (the vector staging's dump row: stage_round_v)
         if constexpr (CT < 16 && !LANE_RANGE) { // narrow chunks: several sub-tiles per wave (voxelize_narrow_kernel)
             // four where the accumulator sets fit (1 or 4 channels) and the row is a multiple of four sub-tiles, else two
-            const int nsub = a.narrow_sub > 0 ? a.narrow_sub : ((CT <= 4 && p.NW % 4 == 0) ? 4 : 2);
-            if (nsub > 1 && p.NW % nsub == 0 && p.vec_store) {
+            // (channels-last: four sub-tiles for one channel only - four sets of four accumulators and their channel runs need
+            // 66 registers, 2 spilled at the 64 of this kernel)
+            constexpr int CT4 = NDHWC ? 1 : 4; // widest chunk served with four sub-tiles per wave
+            const int nsub = a.narrow_sub > 0 ? a.narrow_sub : ((CT <= CT4 && p.NW % 4 == 0) ? 4 : 2);
+            if (nsub > 1 && p.NW % nsub == 0 && (p.vec_store || NDHWC)) { // (the channels-last write-out has both store forms)
                 static LdsLimit raised_n;
                 const size_t lds_n = lds; // (64 rows + the staging's dump row)
                 auto launch_n = [&](auto kn) {
                     hipError_t en = raise_lds_limit(kn, lds_n, raised_n);
                     if (en != hipSuccess) return en;
                     launch_profiled(kn, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW / nsub * 64), lds_n, s, a.rec, a.w, a.slist,
-                                    a.slist_ext, static_cast<OT *>(a.out), a.p);
+                                    a.slist_ext, static_cast<ET *>(a.out), a.p);
                     return hipGetLastError();
                 };
-                if constexpr (CT <= 4) {
+                if constexpr (CT <= CT4) {
                     if (nsub == 4) return launch_n(narrow_kernel<CT, GAUSS, 4>((OT *)nullptr));
                 }
                 if (nsub == 2) return launch_n(narrow_kernel<CT, GAUSS, 2>((OT *)nullptr));
@@ -441,7 +493,7 @@ struct LaunchFn {
         }
         auto kern = slab_kernel<CT, GAUSS, LANE_RANGE, MAXT>((OT *)nullptr);
         LdsLimit *state = &raised;
-        if (!p.vec_store) {
+        if constexpr (!NDHWC) if (!p.vec_store) {
             if constexpr (mx) {
                 static LdsLimit raised_runs;
                 kern = runs_kernel<GAUSS, MAXT>((OT *)nullptr);
@@ -455,18 +507,21 @@ struct LaunchFn {
         hipError_t e = raise_lds_limit(kern, lds, *state);
         if (e != hipSuccess) return e;
         launch_profiled(kern, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), lds, s, a.rec, a.w,
-                        a.slist, a.slist_ext, a.Tc, a.kc, static_cast<OT *>(a.out), a.p);
+                        a.slist, a.slist_ext, a.Tc, a.kc, static_cast<ET *>(a.out), a.p);
         return hipGetLastError();
+        }
     }
 };
 
 hipError_t launch_voxelize(const VoxArgs &a, int32_t nb, int32_t ct, bool gauss, bool lane_range, hipStream_t s) {
     KernelKey k{ct, gauss, lane_range, a.p.NW <= 8 ? 512 : 1024};
+    if (a.ndhwc) return a.bf16 ? for_kernel(k, LaunchFn<Ndhwc<__bf16>>{a, nb, s}) : for_kernel(k, LaunchFn<Ndhwc<float>>{a, nb, s});
     return a.bf16 ? for_kernel(k, LaunchFn<__bf16>{a, nb, s}) : for_kernel(k, LaunchFn<float>{a, nb, s});
 }
 
 hipError_t launch_voxelize_grouped(const VoxArgs &a, int32_t nb, bool gauss, bool lane_range, hipStream_t s) {
     KernelKey k{32, gauss, lane_range, a.p.NW <= 8 ? 512 : 1024};
+    if (a.ndhwc) return a.bf16 ? for_kernel(k, GroupedFn<Ndhwc<__bf16>>{a, nb, s}) : for_kernel(k, GroupedFn<Ndhwc<float>>{a, nb, s});
     return a.bf16 ? for_kernel(k, GroupedFn<__bf16>{a, nb, s}) : for_kernel(k, GroupedFn<float>{a, nb, s});
 }
 

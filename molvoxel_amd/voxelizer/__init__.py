@@ -26,7 +26,7 @@ def _backend(library: str):
 
 def create_voxelizer(resolution: float = 0.5, dimension: int = 64, radii_type: str = "scalar",
                      density_type: str = "gaussian", library: str = "hip", **kwargs) -> Voxelizer:
-    """kwargs go to the backend: `sigma`, `blockdim`, `precision`, `device`, `output`."""
+    """kwargs go to the backend: `sigma`, `blockdim`, `precision`, `device`, `output`, `grid_dtype`, `grid_layout`."""
     return _backend(library).Voxelizer(resolution, dimension, radii_type, density_type, **kwargs)
 
 

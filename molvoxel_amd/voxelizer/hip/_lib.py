@@ -16,6 +16,7 @@ MVX_HOST, MVX_DEVICE = 0, 1
 MVX_GAUSSIAN, MVX_BINARY = 0, 1
 MVX_RADII_SCALAR, MVX_RADII_ATOM, MVX_RADII_CHANNEL = 0, 1, 2
 MVX_GRID_REAL, MVX_GRID_BF16 = 0, 1
+MVX_LAYOUT_NCDHW, MVX_LAYOUT_NDHWC = 0, 1
 MVX_XF_CENTER, MVX_XF_ROTATE, MVX_XF_TRANSLATE, MVX_XF_RECENTER, MVX_XF_CENTER_PTR = 1, 2, 4, 8, 16
 
 
@@ -79,6 +80,7 @@ SIGNATURES = {
     "mvx_destroy": (C.c_int, [Handle]),
     "mvx_set_density": (C.c_int, [Handle, _i32, _dbl]),
     "mvx_set_overlap": (C.c_int, [Handle, _i32]),
+    "mvx_set_grid_layout": (C.c_int, [Handle, _i32]),
     "mvx_forward_features_batch": (C.c_int, [Handle, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "mvx_forward_types_batch": (C.c_int, [Handle, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp]),
     "mvx_forward_single_batch": (C.c_int, [Handle, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
@@ -97,6 +99,7 @@ SIGNATURES = {
     "mvx_debug_set_option": (C.c_int, [Handle, C.c_char_p, _i32]),
     "mvx_plan_call": (C.c_int, [C.POINTER(MvxPlanQuery), C.POINTER(MvxPlan)]),
     "mvx_plan_call_grid": (C.c_int, [C.POINTER(MvxPlanQuery), _i32, C.POINTER(MvxPlan)]),
+    "mvx_plan_call_layout": (C.c_int, [C.POINTER(MvxPlanQuery), _i32, _i32, C.POINTER(MvxPlan)]),
     "mvx_alloc": (C.c_int, [Handle, _i64, C.POINTER(C.c_void_p)]),
     "mvx_free": (C.c_int, [Handle, _vp]),
     "mvx_memcpy": (C.c_int, [Handle, _vp, _vp, _i64, _i32, _i32, _vp]),
@@ -133,14 +136,17 @@ def check(rc: int):
 
 
 def plan_call(dimension, C_, B=1, total_atoms=0, max_atoms=None, mode="features", radii_type="scalar", precision=32,
-              blockdim=8, out_aligned16=True, grid_type=MVX_GRID_REAL) -> dict:
+              blockdim=8, out_aligned16=True, grid_type=MVX_GRID_REAL, layout=MVX_LAYOUT_NCDHW) -> dict:
     """How libmvx_hip would execute a call of this shape (mvx_plan_call: a pure host function, no GPU needed).
     grid_type MVX_GRID_BF16: the plan of a bfloat16 grid (mvx_plan_call_grid; out_aligned16 then stands for 8-byte
-    alignment)."""
+    alignment). layout MVX_LAYOUT_NDHWC: the plan of a channels-last grid (mvx_plan_call_layout; out_aligned16 is 16-byte
+    alignment for either element type)."""
     q = MvxPlanQuery(dimension, blockdim, precision, MODES[mode], RADII[radii_type], B, C_, 1 if out_aligned16 else 0,
                      total_atoms, total_atoms if max_atoms is None else max_atoms)
     p = MvxPlan()
-    if grid_type == MVX_GRID_REAL:
+    if layout != MVX_LAYOUT_NCDHW:
+        check(load().mvx_plan_call_layout(C.byref(q), int(grid_type), int(layout), C.byref(p)))
+    elif grid_type == MVX_GRID_REAL:
         check(load().mvx_plan_call(C.byref(q), C.byref(p)))
     else:
         check(load().mvx_plan_call_grid(C.byref(q), int(grid_type), C.byref(p)))

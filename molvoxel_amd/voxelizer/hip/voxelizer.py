@@ -16,7 +16,10 @@ what `.to(torch.bfloat16)` of the float32 grid gives, at half the bytes. `differ
 tensors that require grad (`coords`, `features`, `center`) part of the autograd graph: the backward pass runs on the GPU
 (mvx_backward_batch) and returns gradients with respect to those tensors. `radii_grad=True` (with `differentiable=True`)
 adds a radii tensor that requires grad to them (mvx_backward_radii_batch, atom-wise or channel-wise radii; on a scalar-radii
-voxelizer a one-element radii tensor, mvx_backward_density_batch). `sigma_grad=True` (with `differentiable=True`) lets `sigma=`
+voxelizer a one-element radii tensor, mvx_backward_density_batch). `grid_layout="channels_last"` makes the kernels write
+channels-last (NDHWC, `torch.channels_last_3d`) grids directly: same logical shape, same bits, the strides 3D convolutions want
+(faster than converting afterwards with bfloat16 grids; experimental with float32 grids: DESIGN.md section 14).
+`sigma_grad=True` (with `differentiable=True`) lets `sigma=`
 / `set_sigma()` take a one-element tensor that gets dL/dsigma (mvx_backward_density_batch).
 """
 from __future__ import annotations
@@ -68,6 +71,7 @@ class Voxelizer(BaseVoxelizer):
         differentiable: bool = False,
         radii_grad: bool = False,
         sigma_grad: bool = False,
+        grid_layout=None,
         **kwargs,
     ):
         # sigma as a tensor (sigma_grad): kept as `sigma_tensor`; `_sigma` stays the python float the base class stores
@@ -94,6 +98,7 @@ class Voxelizer(BaseVoxelizer):
         self.sigma_grad = bool(sigma_grad)
         self._sigma_src = sigma_src
         self._bf16 = self._is_bf16_grid(grid_dtype, precision, output)  # (checked before anything touches a device)
+        self._cl = self._is_channels_last(grid_layout, precision, output)  # (the same)
         if output == "torch" and torch is None:
             raise ImportError("output='torch' needs PyTorch; use output='numpy'")
         self.precision = precision
@@ -123,6 +128,8 @@ class Voxelizer(BaseVoxelizer):
             _lib.MVX_GRID_BF16 if self._bf16 else _lib.MVX_GRID_REAL,
         )
         _lib.check(self._lib.mvx_create(C.byref(cfg), C.byref(self._handle)))
+        if self._cl:
+            _lib.check(self._lib.mvx_set_grid_layout(self._handle, _lib.MVX_LAYOUT_NDHWC))
         self.overlap_prepass = bool(overlap_prepass)
         if self.overlap_prepass:
             self.set_overlap_prepass(True)
@@ -141,6 +148,45 @@ class Voxelizer(BaseVoxelizer):
         if name == "bfloat16" and output != "torch":
             raise ValueError("grid_dtype='bfloat16' needs output='torch': numpy has no bfloat16")
         return name == "bfloat16"
+
+    @staticmethod
+    def _is_channels_last(grid_layout, precision, output) -> bool:
+        """grid_layout: None / "contiguous" / torch.contiguous_format (NCDHW), or "channels_last" / torch.channels_last_3d
+        (NDHWC strides on the same logical shape; precision 32, torch output)."""
+        names = {None: False, "contiguous": False, "channels_last": True}
+        if torch is not None:
+            names.update({torch.contiguous_format: False, torch.channels_last_3d: True})
+        try:
+            cl = names[grid_layout]
+        except (KeyError, TypeError):
+            raise ValueError(f"grid_layout must be None, 'contiguous' or 'channels_last' (or torch.contiguous_format / "
+                             f"torch.channels_last_3d), not {grid_layout!r}") from None
+        if cl and precision != 32:
+            raise ValueError("grid_layout='channels_last' needs precision=32 (float32 or bfloat16 grids)")
+        if cl and output != "torch":
+            raise ValueError("grid_layout='channels_last' needs output='torch': the layout is a torch memory format")
+        return cl
+
+    @property
+    def grid_layout(self) -> str:
+        """"contiguous" (C, D, H, W with W fastest) or "channels_last" (the same logical shape with the channel fastest)."""
+        return "channels_last" if self._cl else "contiguous"
+
+    def _dense_in_layout(self, t) -> bool:
+        """Is the torch grid `t` dense in this voxelizer's layout (what the kernels write without a temporary)?"""
+        if not self._cl:
+            return t.is_contiguous()
+        return (t if t.dim() == 5 else t.unsqueeze(0)).is_contiguous(memory_format=torch.channels_last_3d)
+
+    def _empty_torch(self, shape, init_zero=False):
+        fn = torch.zeros if init_zero else torch.empty
+        if not self._cl:
+            return fn(tuple(shape), dtype=self._gdt, device=self.device)
+        if len(shape) == 5:  # exactly torch.empty(shape, memory_format=torch.channels_last_3d)
+            t = torch.empty(tuple(shape), dtype=self._gdt, device=self.device, memory_format=torch.channels_last_3d)
+            return t.zero_() if init_zero else t
+        # a single grid: the permute(3, 0, 1, 2) view of a (D, H, W, C) buffer - unsqueeze(0) is channels-last-3d contiguous
+        return fn(tuple(shape[1:]) + (shape[0],), dtype=self._gdt, device=self.device).permute(3, 0, 1, 2)
 
     @property
     def grid_dtype(self):
@@ -252,8 +298,7 @@ class Voxelizer(BaseVoxelizer):
         if batch_size is not None:
             shape = (batch_size,) + shape
         if self.output == "torch":
-            fn = torch.zeros if init_zero else torch.empty
-            return fn(shape, dtype=self._gdt, device=self.device)
+            return self._empty_torch(shape, init_zero)
         if torch is not None and torch.cuda.is_available():
             # numpy grids live in pinned host memory (torch's caching host allocator): the copy back is a direct DMA
             # at PCIe speed instead of a staged pageable copy (3.4 -> ~0.7 ms per cfg-2 grid)
@@ -286,7 +331,7 @@ class Voxelizer(BaseVoxelizer):
             return type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
                               self.blockdim, idx, self.output, self.overlap_prepass,
                               grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
-                              radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, **kw)
+                              radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout, **kw)
         return self
 
     def cuda(self):
@@ -389,12 +434,12 @@ class Voxelizer(BaseVoxelizer):
         if out_grid is None:
             out_grid = self.get_empty_grid(shape[0])
         if _is_torch(out_grid):
-            if self._on_device(out_grid) and out_grid.is_contiguous() and out_grid.dtype == self._gdt:
+            if self._on_device(out_grid) and self._dense_in_layout(out_grid) and out_grid.dtype == self._gdt:
                 return out_grid, _lib.MVX_DEVICE, out_grid, None
-            tmp = torch.empty(tuple(out_grid.shape), dtype=self._gdt, device=self.device)
+            tmp = self._empty_torch(tuple(out_grid.shape))
             return tmp, _lib.MVX_DEVICE, out_grid, "copy_torch"
-        if self._bf16:  # a numpy grid (no bfloat16 there): the bfloat16 grid is made on the device and copied as float32
-            tmp = torch.empty(tuple(out_grid.shape), dtype=self._gdt, device=self.device)
+        if self._bf16 or self._cl:  # a numpy grid (no bfloat16, no channels-last there): made on the device, copied as float32
+            tmp = self._empty_torch(tuple(out_grid.shape))
             return tmp, _lib.MVX_DEVICE, out_grid, "copy_numpy_bf16"
         if out_grid.flags.c_contiguous and out_grid.dtype == self.fp:
             return out_grid, _lib.MVX_HOST, out_grid, None
