@@ -384,6 +384,11 @@ int mvx_plan_call_grid(const mvx_plan_query *q, int32_t grid_type, mvx_plan *p);
  * (C * element size a multiple of 16, aligned grid), rows are cut into slabs of at most 8 waves, no pacing, no XCD ranges;
  * C == 1 gives the contiguous plan. MVX_ERR_INVALID for an unknown layout, and for MVX_LAYOUT_NDHWC with precision 64. */
 int mvx_plan_call_layout(const mvx_plan_query *q, int32_t grid_type, int32_t layout, mvx_plan *p);
+/* Testing aid: the plan the last forward call on this handle took - mvx_plan_call_layout of that call's shape with the handle's
+ * debug options ("chunks", "mall_budget_kb", "direct", "max_ct", "nw" ...) applied, which the pure functions above cannot see.
+ * Lets a test assert that a call really was cut into `nchunk` molecule chunks where no launch count shows it (float64 grids
+ * run every chunk's pre-pass and then one voxelize launch). MVX_ERR_INVALID before the first forward call. */
+int mvx_debug_last_plan(mvx_handle *h, mvx_plan *plan);
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,8 @@ struct mvx_handle {
     // more than it saves (profiles/r05_grad.txt)
     int grad_order = 0;
     int32_t layout = MVX_LAYOUT_NCDHW; // mvx_set_grid_layout
+    mvx_plan last_plan{}; // the plan of the last forward call, debug options applied (mvx_debug_last_plan)
+    bool has_plan = false;
     int narrow_sub = 0; // "narrow_sub" option: sub-tiles per wave of narrow chunks (1: voxelize_kernel; 2 | 4: voxelize_narrow_kernel; 0: the rule)
     int dbg = 0; // diagnostic builds (-DMVX_DIAG) only
 };
@@ -416,6 +418,8 @@ int run(mvx_handle *h, const RunArgs &r) {
     q.total_atoms = total;
     q.max_atoms = max_atoms;
     const mvx_plan plan = plan_call(q, h->knobs, ndhwc ? MVX_LAYOUT_NDHWC : MVX_LAYOUT_NCDHW, bf16 ? 2 : 4);
+    h->last_plan = plan;
+    h->has_plan = true;
     const bool direct = plan.route == MVX_ROUTE_DIRECT;
     const bool mx64 = plan.route == MVX_ROUTE_F64_MX;
     const int ct = plan.ct, ncc = plan.ncc, nchunk = plan.nchunk;
@@ -1195,6 +1199,13 @@ int mvx_debug_set_option(mvx_handle *h, const char *name, int32_t value) {
     }
 #endif
     else return fail(MVX_ERR_INVALID, "unknown option: " + n);
+    return MVX_OK;
+}
+
+int mvx_debug_last_plan(mvx_handle *h, mvx_plan *plan) {
+    if (!h || !plan) return fail(MVX_ERR_INVALID, "null argument");
+    if (!h->has_plan) return fail(MVX_ERR_INVALID, "no forward call on this handle yet");
+    *plan = h->last_plan;
     return MVX_OK;
 }
 

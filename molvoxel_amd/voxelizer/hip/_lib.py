@@ -97,6 +97,7 @@ SIGNATURES = {
     "mvx_last_kernel_ms": (C.c_int, [Handle, C.POINTER(C.c_float)]),
     "mvx_debug_read_records": (C.c_int, [Handle, _vp, _i64, _vp]),
     "mvx_debug_set_option": (C.c_int, [Handle, C.c_char_p, _i32]),
+    "mvx_debug_last_plan": (C.c_int, [Handle, C.POINTER(MvxPlan)]),
     "mvx_plan_call": (C.c_int, [C.POINTER(MvxPlanQuery), C.POINTER(MvxPlan)]),
     "mvx_plan_call_grid": (C.c_int, [C.POINTER(MvxPlanQuery), _i32, C.POINTER(MvxPlan)]),
     "mvx_plan_call_layout": (C.c_int, [C.POINTER(MvxPlanQuery), _i32, _i32, C.POINTER(MvxPlan)]),

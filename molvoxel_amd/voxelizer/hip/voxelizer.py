@@ -841,6 +841,12 @@ class Voxelizer(BaseVoxelizer):
         """Testing aid (mvx_debug_set_option): force code paths production sizes rarely reach."""
         _lib.check(self._lib.mvx_debug_set_option(self._handle, name.encode(), int(value)))
 
+    def last_plan(self) -> dict:
+        """Testing aid (mvx_debug_last_plan): the plan of the last forward call on this handle, debug options applied."""
+        p = _lib.MvxPlan()
+        _lib.check(self._lib.mvx_debug_last_plan(self._handle, C.byref(p)))
+        return {name: getattr(p, name) for name, _ in _lib.MvxPlan._fields_ if name != "reserved"}
+
     def set_profiling(self, enable: bool):
         _lib.check(self._lib.mvx_set_profiling(self._handle, 1 if enable else 0))
 

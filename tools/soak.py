@@ -5,6 +5,10 @@
     python3 tools/soak.py routes FIRST COUNT     direct kernel against binned pipeline, bit for bit, on inputs that stress the
                                                  direct kernel's float32 candidate scan: far-away centres (|c| up to 1e5),
                                                  random rotations / translations, every radii kind and operator
+
+SOAK_DIMS=65,66,72 draws grid sizes from another list; SOAK_CUTS=SEED (batches) cuts every batch into several launches: each
+voxelizer draws an Infinity Cache budget ("mall_budget_kb") or a side-stream chunk count ("chunks"), as tests/test_hip_batch_cuts.py
+forces them.
 """
 import importlib.util
 import sys
@@ -21,6 +25,20 @@ import os
 
 if os.environ.get("SOAK_DIMS"):  # e.g. SOAK_DIMS=65,66,72,88,100,101,127: grid sizes outside the committed fuzz list
     fz.DIMS = [int(x) for x in os.environ["SOAK_DIMS"].split(",")]
+
+if os.environ.get("SOAK_CUTS"):  # e.g. SOAK_CUTS=1: molecule cuts drawn per voxelizer (= per batch in `batches`)
+    _create, _cut_rng = mv.create_voxelizer, np.random.default_rng(int(os.environ["SOAK_CUTS"]))
+
+    def _create_cut(*args, **kw):
+        v = _create(*args, **kw)
+        kind = str(_cut_rng.choice(["budget", "budget", "chunks", "none"]))
+        if kind == "budget":  # 1 KB: one molecule per chunk
+            v.debug_option("mall_budget_kb", int(_cut_rng.choice([1, 100, 500, 2000, 20000])))
+        elif kind == "chunks":  # (takes effect from 4 molecules per chunk)
+            v.debug_option("chunks", int(_cut_rng.choice([2, 3, 5])))
+        return v
+
+    mv.create_voxelizer = _create_cut
 
 if sys.argv[1] == "routes":
     import torch
