@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVX_VERSION 140 /* 0.1.4: mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
+#define MVX_VERSION 140 /* 0.1.4: mvx_select_views and mvx_forward_views (additive: many views of one shared cloud); mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
 
 typedef enum mvx_status {
     MVX_OK = 0,
@@ -200,6 +200,47 @@ int mvx_forward_types(mvx_handle *h, const double *coords, const int32_t *types,
 int mvx_forward_single(mvx_handle *h, const double *coords, const mvx_real *radii, double radius_scalar,
                        int32_t radii_type, int64_t N, const mvx_xform *xform, mvx_real *out, int32_t in_kind,
                        int32_t out_kind, void *stream);
+
+/*
+ * Many views of ONE shared point cloud (no counterpart in the reference, which voxelizes one box per call): a large structure
+ * voxelized into B boxes, each with its own transform (centre, optional rotation and translation) - binding-site scanning,
+ * per-residue environments, sliding windows. Equivalent to the batched entry on the cloud repeated B times, bit for bit,
+ * without the B copies: per view, the atoms that pass the forward's box cull (rule step 1) are selected on the device, their
+ * rows are gathered into a compact batch, and that batch runs through the unchanged pipeline.
+ *
+ * The cloud is N atoms: coords (N, 3) double; channels as `mode` says (0 features: (N, C) mvx_real, 1 types: (N,) int32,
+ * 2 single: NULL, C = 1); radii as in the batched entries for one molecule of N atoms. `xforms`: B records on the host, one
+ * per view, never NULL with B > 0 (a view of the whole cloud is a record with flags = 0); a MVX_XF_CENTER_PTR centre lives in
+ * the memory `in_kind` names. Host-resident inputs (MVX_HOST) are uploaded once - the cloud, not B copies of it.
+ *
+ * mvx_select_views: offsets_out_host (B + 1 int64, HOST memory) and index_out (int64, DEVICE memory, index_capacity
+ *   elements): index_out[offsets[b] .. offsets[b + 1]) are the atoms of view b in ascending order - those whose transformed
+ *   position passes the box cull with the radius the pre-pass culls with (the scalar radius; radii[n]; radii[types[n]], and
+ *   types outside [0, C) never pass; max(radii) for channel-wise features). Every atom that reaches a voxel of view b is in
+ *   the set. Deterministic: no atomics, two calls give the same bytes. `types` is read in types mode only and may be NULL
+ *   otherwise. The offsets are copied to the host inside the call: ONE stream synchronisation per call, after which
+ *   offsets_out_host is valid. If index_capacity < offsets[B] the call returns MVX_ERR_INVALID with offsets_out_host filled
+ *   in and index_out untouched, so the caller can size the buffer and call again; index_out = NULL with index_capacity = 0 is
+ *   that sizing call (MVX_OK when no view keeps an atom).
+ * mvx_forward_views: out is (B, C, D, D, D) in the handle's grid type and layout, `out_kind` tagged, fully overwritten: the
+ *   grids mvx_forward_*_batch writes for the cloud repeated B times with the same xforms. Selection (one stream
+ *   synchronisation, as above), one gather launch into handle-owned buffers (per selected atom: 24 bytes of coordinates, its
+ *   feature row or type, its radius when radii are atom-wise; 8 bytes of index; 12 bytes per (view, 1024 atoms) of counts),
+ *   then the batched pipeline on the compact batch: bfloat16 and channels-last grids, precision 64, host outputs, molecule
+ *   chunks and the debug options apply as they do there. mvx_set_overlap does not apply to this entry (its inputs are
+ *   produced on the caller's stream by the call itself).
+ * Both return MVX_ERR_INVALID before any device is touched for: a NULL handle; a bad mode, radii_type or memory kind; B < 0,
+ * N < 0 or C <= 0 (single mode: C != 1); NULL xforms with B > 0; channel-wise radii in single mode; a missing array (coords
+ * with N > 0, radii where the radii type needs them, types / channels where the mode needs them, out / offsets_out_host).
+ * N == 0 or B == 0: zero offsets; zero grids (B > 0) or nothing.
+ */
+int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types_or_null, const mvx_real *radii,
+                     double radius_scalar, int32_t radii_type, int32_t mode, int64_t N, int32_t C, const mvx_xform *xforms,
+                     int32_t B, int64_t *index_out, int64_t index_capacity, int64_t *offsets_out_host, int32_t in_kind,
+                     void *stream);
+int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                      double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                      mvx_real *out, int32_t in_kind, int32_t out_kind, void *stream);
 
 /*
  * Backward pass of a batched call (no counterpart in the reference: its torch backend runs under torch.no_grad()).

@@ -7,6 +7,7 @@
 #include "mvx_grad.h"
 #include "mvx_internal.h"
 #include "mvx_plan.h"
+#include "mvx_views.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -102,6 +103,9 @@ struct mvx_handle {
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
     // more than it saves (profiles/r05_grad.txt)
     int grad_order = 0;
+    // views of a shared cloud (mvx_select_views / mvx_forward_views): the views' transforms, per-(view, tile) counts and bases,
+    // offsets, max channel radius, and - mvx_forward_views - the selected indices and the gathered rows handed to run()
+    DevBuf view_xf, view_counts, view_base, view_off, view_aux, view_index, view_coords, view_chan, view_radii;
     int32_t layout = MVX_LAYOUT_NCDHW; // mvx_set_grid_layout
     mvx_plan last_plan{}; // the plan of the last forward call, debug options applied (mvx_debug_last_plan)
     bool has_plan = false;
@@ -750,7 +754,9 @@ int mvx_destroy(mvx_handle *h) {
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
     std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage,
-                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart};
+                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart,
+                                  &h->view_xf, &h->view_counts, &h->view_base, &h->view_off, &h->view_aux, &h->view_index,
+                                  &h->view_coords, &h->view_chan, &h->view_radii};
     for (Workspace &w : h->ws) {
         for (DevBuf *b : {&w.rec, &w.wbuf, &w.xp, &w.xlist, &w.slist, &w.meta, &w.aux}) bufs.push_back(b);
         if (w.ev_pre) (void)hipEventDestroy(w.ev_pre);
@@ -846,6 +852,240 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const void *radii, d
     const int64_t off[2] = {0, N};
     return mvx_forward_single_batch(h, coords, radii, radius_scalar, radii_type, off, xform, 1, out, in_kind,
                                     out_kind, stream);
+}
+
+// ---- views of one shared cloud (mvx_views.hip) ----------------------------------------------------------------------------
+namespace {
+
+struct ViewCall {
+    int mode;
+    const double *coords;
+    const void *channels; // features (N, C) | types (N,) | null
+    const void *radii;
+    double radius_scalar;
+    int radii_type;
+    int64_t N;
+    int C;
+    const mvx_xform *xforms;
+    int B;
+    int in_kind;
+    hipStream_t stream;
+};
+
+// What both entries reject before any device is touched. `own`: what the entry found wrong with its own arguments (null: nothing);
+// the handle is looked at last, so every other rule can be checked without a device.
+int validate_views(const mvx_handle *h, const ViewCall &v, const char *own) {
+    if (v.mode != MODE_FEATURES && v.mode != MODE_TYPES && v.mode != MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode");
+    if (v.radii_type < MVX_RADII_SCALAR || v.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
+    if (v.in_kind != MVX_HOST && v.in_kind != MVX_DEVICE) return fail(MVX_ERR_INVALID, "bad memory kind");
+    if (v.B < 0 || v.N < 0 || v.C <= 0) return fail(MVX_ERR_INVALID, "B and N must be >= 0 and C > 0");
+    if (v.B > 0 && !v.xforms)
+        return fail(MVX_ERR_INVALID, "xforms must not be null (a view of the whole cloud is a record with flags = 0)");
+    if (v.radii_type == MVX_RADII_CHANNEL && v.mode == MODE_SINGLE)
+        return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported"); // numpy/voxelizer.py:443
+    if (v.mode == MODE_SINGLE && v.C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel");
+    if (v.N > 0 && !v.coords) return fail(MVX_ERR_INVALID, "coords must not be null");
+    if (!v.radii && (v.radii_type == MVX_RADII_CHANNEL || (v.radii_type == MVX_RADII_ATOM && v.N > 0)))
+        return fail(MVX_ERR_INVALID, "radii array required");
+    if (v.N > 0 && v.mode == MODE_TYPES && !v.channels) return fail(MVX_ERR_INVALID, "types must not be null");
+    if (v.N >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (own) return fail(MVX_ERR_INVALID, own);
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    return MVX_OK;
+}
+
+// the cloud and the views' transforms as device arrays
+struct ViewInputs {
+    const double *coords = nullptr;
+    const void *channels = nullptr;
+    const void *radii = nullptr;
+    const mvx_xform *xforms = nullptr;       // device copy of the B records
+    std::vector<mvx_xform> xforms_host;      // the records as run() gets them (host centres folded in)
+};
+
+// Host-resident arrays are uploaded once - the cloud, not B copies of it - through a pinned slot; `select_only`: the feature
+// rows are not needed (the selection reads coordinates, types and radii).
+int stage_views(mvx_handle *h, const ViewCall &v, bool select_only, ViewInputs &in) {
+    hipStream_t s = v.stream;
+    const size_t esz = h->cfg.precision == 64 ? sizeof(double) : sizeof(float);
+    const bool host_in = v.in_kind == MVX_HOST;
+    const size_t chan_elem = v.mode == MODE_FEATURES ? (select_only ? 0 : (size_t)v.C * esz) : (v.mode == MODE_TYPES ? sizeof(int32_t) : 0);
+    const size_t rad_count = v.radii_type == MVX_RADII_ATOM ? (size_t)v.N : (v.radii_type == MVX_RADII_CHANNEL ? (size_t)v.C : 0);
+    const size_t xf_bytes = align_up((size_t)v.B * sizeof(mvx_xform), 16);
+    const size_t co_bytes = host_in ? align_up((size_t)v.N * 3 * sizeof(double), 16) : 0;
+    const size_t ch_bytes = host_in ? align_up((size_t)v.N * chan_elem, 16) : 0;
+    const size_t ra_bytes = host_in ? align_up(rad_count * esz, 16) : 0;
+    in.xforms_host.assign(v.xforms, v.xforms + v.B);
+    if (host_in) resolve_host_centers(in.xforms_host.data(), v.B);
+    PinnedSlot *slot = nullptr;
+    int rc;
+    if ((rc = acquire_slot(h, xf_bytes + co_bytes + ch_bytes + ra_bytes, &slot))) return rc;
+    if ((rc = ensure(h->view_xf, xf_bytes))) return rc;
+    std::memcpy(slot->p, in.xforms_host.data(), (size_t)v.B * sizeof(mvx_xform));
+    HIP_TRY(hipMemcpyAsync(h->view_xf.p, slot->p, (size_t)v.B * sizeof(mvx_xform), hipMemcpyHostToDevice, s));
+    in.xforms = reinterpret_cast<const mvx_xform *>(h->view_xf.p);
+    in.coords = v.coords;
+    in.channels = v.channels;
+    in.radii = v.radii;
+    if (host_in) {
+        auto upload = [&](DevBuf &dst, const void *src, size_t used, char *staging, const void *&dev) -> int {
+            if (used == 0 || !src) return MVX_OK;
+            if (int e = ensure(dst, used)) return e;
+            std::memcpy(staging, src, used);
+            HIP_TRY(hipMemcpyAsync(dst.p, staging, used, hipMemcpyHostToDevice, s));
+            dev = dst.p;
+            return MVX_OK;
+        };
+        char *q = slot->p + xf_bytes;
+        const void *dev_coords = v.coords;
+        if ((rc = upload(h->in_coords, v.coords, (size_t)v.N * 3 * sizeof(double), q, dev_coords))) return rc;
+        in.coords = static_cast<const double *>(dev_coords);
+        if ((rc = upload(h->in_chan, v.channels, (size_t)v.N * chan_elem, q + co_bytes, in.channels))) return rc;
+        if ((rc = upload(h->in_radii, v.radii, rad_count * esz, q + co_bytes + ch_bytes, in.radii))) return rc;
+    }
+    HIP_TRY(hipEventRecord(slot->done, s));
+    slot->in_flight = true;
+    return MVX_OK;
+}
+
+// Count, scan, one copy of the offsets to the host (THE synchronisation of a views call), fill. `index` / `capacity`: the
+// caller's buffer, or null: the handle's own (mvx_forward_views), grown to fit. Returns MVX_ERR_INVALID with the offsets filled
+// in when the caller's buffer is too small.
+int select_views(mvx_handle *h, const ViewCall &v, const ViewInputs &in, int64_t *index, int64_t capacity, bool own_index,
+                 int64_t *offsets_host) {
+    hipStream_t s = v.stream;
+    if (v.N == 0) {
+        std::fill(offsets_host, offsets_host + v.B + 1, (int64_t)0);
+        return MVX_OK;
+    }
+    const int64_t ntiles64 = (v.N + VIEW_TILE - 1) / VIEW_TILE;
+    const bool views_in_x = v.B >= ntiles64;
+    if (std::min<int64_t>(v.B, ntiles64) > 65535 || (int64_t)v.B * ntiles64 >= (int64_t)1 << 31)
+        return fail(MVX_ERR_INVALID, "too many (view, tile) pairs for one launch");
+    ViewArgs a;
+    a.pa = prep_args(h, v.mode, v.radii_type, v.radius_scalar, v.B, v.C, v.N);
+    a.pa.coords = in.coords;
+    a.pa.radii = in.radii;
+    a.pa.types = v.mode == MODE_TYPES ? static_cast<const int32_t *>(in.channels) : nullptr;
+    a.pa.xforms = in.xforms;
+    a.ntiles = (int32_t)ntiles64;
+    a.views_in_x = views_in_x ? 1 : 0;
+    int rc;
+    if (a.pa.radii_src == RAD_CHANNEL_FEATURES) {
+        if ((rc = ensure(h->view_aux, 16))) return rc;
+        HIP_TRY(launch_view_rmax(in.radii, v.C, a.pa.precision, h->view_aux.p, s));
+        a.pa.chan_aux = h->view_aux.p;
+    }
+    const size_t M = (size_t)v.B * (size_t)ntiles64;
+    const size_t off_bytes = (size_t)(v.B + 1) * sizeof(int64_t);
+    if ((rc = ensure(h->view_counts, M * sizeof(int32_t)))) return rc;
+    if ((rc = ensure(h->view_base, M * sizeof(int64_t)))) return rc;
+    if ((rc = ensure(h->view_off, off_bytes))) return rc;
+    PinnedSlot *slot = nullptr;
+    if ((rc = acquire_slot(h, off_bytes, &slot))) return rc;
+    HIP_TRY(launch_view_count(a, static_cast<int32_t *>(h->view_counts.p), s));
+    HIP_TRY(launch_view_scan(static_cast<const int32_t *>(h->view_counts.p), v.B, a.ntiles, static_cast<int64_t *>(h->view_base.p),
+                             static_cast<int64_t *>(h->view_off.p), s));
+    HIP_TRY(hipMemcpyAsync(slot->p, h->view_off.p, off_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    std::memcpy(offsets_host, slot->p, off_bytes);
+    const int64_t total = offsets_host[v.B];
+    if (own_index) {
+        if ((rc = ensure(h->view_index, (size_t)total * sizeof(int64_t)))) return rc;
+        index = static_cast<int64_t *>(h->view_index.p);
+    } else if (capacity < total || (total > 0 && !index)) {
+        return fail(MVX_ERR_INVALID, "index_capacity is smaller than offsets[B]: size the buffer from offsets_out_host and call again");
+    }
+    if (total > 0) HIP_TRY(launch_view_fill(a, static_cast<const int64_t *>(h->view_base.p), index, s));
+    return MVX_OK;
+}
+
+inline int gather_width(size_t row_bytes, const void *a, const void *b) {
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | (uintptr_t)row_bytes;
+    return (bits & 15u) == 0 ? 16 : ((bits & 7u) == 0 ? 8 : 4);
+}
+
+} // namespace
+
+int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types, const void *radii, double radius_scalar,
+                     int32_t radii_type, int32_t mode, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                     int64_t *index_out, int64_t index_capacity, int64_t *offsets_out_host, int32_t in_kind, void *stream) {
+    ViewCall v{mode, coords, types, radii, radius_scalar, radii_type, N, C, xforms, B, in_kind, reinterpret_cast<hipStream_t>(stream)};
+    const char *own = !offsets_out_host ? "offsets_out_host must not be null"
+                      : (index_capacity < 0 || (index_capacity > 0 && !index_out)) ? "index_out must not be null" : nullptr;
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (B == 0 || N == 0) {
+        std::fill(offsets_out_host, offsets_out_host + B + 1, (int64_t)0);
+        return MVX_OK;
+    }
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    if (int rc = adopt_stream(h, v.stream)) return rc;
+    ViewInputs in;
+    if (int rc = stage_views(h, v, true, in)) return rc;
+    return select_views(h, v, in, index_out, index_capacity, false, offsets_out_host);
+}
+
+int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                      double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                      void *out, int32_t in_kind, int32_t out_kind, void *stream) {
+    ViewCall v{mode, coords, channels, radii, radius_scalar, radii_type, N, C, xforms, B, in_kind, reinterpret_cast<hipStream_t>(stream)};
+    const char *own = (out_kind != MVX_HOST && out_kind != MVX_DEVICE) ? "bad memory kind"
+                      : (B > 0 && !out) ? "out must not be null"
+                      : (B > 0 && N > 0 && mode != MODE_SINGLE && !channels) ? "channels must not be null" : nullptr;
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (B == 0) return MVX_OK;
+    std::vector<int64_t> offsets((size_t)B + 1, 0);
+    RunArgs r{mode, coords, channels, radii, radius_scalar, radii_type, offsets.data(), xforms, B, C, out, in_kind, out_kind, v.stream};
+    if (N == 0) return run(h, r); // B molecules without atoms: zero grids
+    ViewInputs in;
+    {
+        DeviceGuard guard(h->device);
+        if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+        hipStream_t s = v.stream;
+        int rc;
+        if ((rc = adopt_stream(h, s))) return rc;
+        if ((rc = stage_views(h, v, false, in))) return rc;
+        if ((rc = select_views(h, v, in, nullptr, 0, true, offsets.data()))) return rc;
+        const int64_t total = offsets[B];
+        if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+        // one gather launch: coordinates, feature rows or types, atom-wise radii
+        const size_t esz = h->cfg.precision == 64 ? sizeof(double) : sizeof(float);
+        GatherArgs g{};
+        g.index = static_cast<const int64_t *>(h->view_index.p);
+        g.total = total;
+        auto add = [&](DevBuf &dst, const void *src, size_t row_bytes) -> int {
+            if (int e = ensure(dst, (size_t)total * row_bytes)) return e;
+            const int i = g.narr++;
+            g.src[i] = static_cast<const char *>(src);
+            g.dst[i] = static_cast<char *>(dst.p);
+            g.row_bytes[i] = (int32_t)row_bytes;
+            g.width[i] = gather_width(row_bytes, src, dst.p);
+            return MVX_OK;
+        };
+        if ((rc = add(h->view_coords, in.coords, 3 * sizeof(double)))) return rc;
+        r.coords = static_cast<const double *>(h->view_coords.p);
+        if (mode != MODE_SINGLE) {
+            if ((size_t)C * esz > (size_t)1 << 30) return fail(MVX_ERR_INVALID, "too many channels");
+            if ((rc = add(h->view_chan, in.channels, mode == MODE_FEATURES ? (size_t)C * esz : sizeof(int32_t)))) return rc;
+            r.channels = h->view_chan.p;
+        }
+        r.radii = in.radii; // (scalar: unused; channel-wise: the C radii as they are)
+        if (radii_type == MVX_RADII_ATOM) {
+            if ((rc = add(h->view_radii, in.radii, esz))) return rc;
+            r.radii = h->view_radii.p;
+        }
+        HIP_TRY(launch_view_gather(g, s));
+    }
+    r.xforms = in.xforms_host.data();
+    r.in_kind = MVX_DEVICE;
+    // (the gathered rows are produced on the caller's stream just now: the pre-pass must not run ahead of them on the side
+    // stream, so cross-call overlap does not apply to this entry)
+    const bool overlap = h->overlap;
+    h->overlap = false;
+    const int rc = run(h, r);
+    h->overlap = overlap;
+    return rc;
 }
 
 // mvx_backward_batch (BWD_PLAIN), mvx_backward_radii_batch (BWD_RADII: grad_radii as well) and mvx_backward_density_batch

@@ -274,47 +274,7 @@ __device__ __forceinline__ bool prep_atom(const PrepArgs &A, int64_t a, const do
     double rc;   // fp64 radius the culls use
     double rwin; // widest radius for the conservative index window
     double r64 = 0.0; // float64 grids: the membership radius as np.divide sees it
-    bool keep = true;
-    int32_t type = 0;
-    if (A.types) {
-        type = A.types[a];
-        if (type < 0 || type >= A.C) keep = false; // never index radii / channels out of range
-    }
-    if (A.radii_src == RAD_SCALAR) {
-        rc = A.radius_scalar;
-        r32 = (float)A.radius_scalar;
-        r64 = A.radius_scalar;
-        rwin = f64 ? r64 : (double)r32;
-        for (int i = 0; i < 3; ++i) keep = keep && (p[i] > lb - rc) && (p[i] < ub + rc); // numpy/voxelizer.py:487-488
-    } else if (A.radii_src == RAD_CHANNEL_FEATURES) {
-        double lo, hi;
-        if (f64) { // np.float64 scalar: plain float64 arithmetic
-            r64 = rmax64;
-            r32 = (float)r64;
-            rc = rwin = r64;
-            lo = lb - r64;
-            hi = ub + r64;
-        } else {
-            const float rmax = rmax32;
-            r32 = rmax;
-            rc = rwin = (double)rmax;
-            // np.float32 scalar: (python float -/+ float32) is evaluated in float32 (NEP 50), numpy/voxelizer.py:138
-            lo = (double)((float)lb - rmax);
-            hi = (double)((float)ub + rmax);
-        }
-        for (int i = 0; i < 3; ++i) keep = keep && (p[i] > lo) && (p[i] < hi);
-    } else {
-        const int64_t ri = (A.radii_src == RAD_ATOM) ? a : (keep ? (int64_t)type : -1); // numpy/voxelizer.py:284-285
-        if (f64) {
-            r64 = ri >= 0 ? static_cast<const double *>(A.radii)[ri] : 0.0;
-            r32 = (float)r64;
-            rc = rwin = r64;
-        } else {
-            r32 = ri >= 0 ? static_cast<const float *>(A.radii)[ri] : 0.0f;
-            rc = rwin = (double)r32;
-        }
-        for (int i = 0; i < 3; ++i) keep = keep && (p[i] + rc > lb) && (p[i] - rc < ub); // numpy/voxelizer.py:491-492
-    }
+#include "mvx_box_cull.inc" // -> keep, type, r32, rc, rwin, r64
 
     R.px = p[0];
     R.py = p[1];

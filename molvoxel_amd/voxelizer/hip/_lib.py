@@ -87,6 +87,8 @@ SIGNATURES = {
     "mvx_forward_features": (C.c_int, [Handle, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _vp]),
     "mvx_forward_types": (C.c_int, [Handle, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _vp, _i32, _i32, _vp]),
     "mvx_forward_single": (C.c_int, [Handle, _vp, _vp, _dbl, _i32, _i64, _vp, _vp, _i32, _i32, _vp]),
+    "mvx_select_views": (C.c_int, [Handle, _vp, _vp, _vp, _dbl, _i32, _i32, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _i32, _vp]),
+    "mvx_forward_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _vp]),
     "mvx_backward_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "mvx_backward_radii_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mvx_backward_density_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,

@@ -639,6 +639,14 @@ class Voxelizer(BaseVoxelizer):
         out_grid: (B,C,D,H,W) of this voxelizer's grid_dtype (torch CUDA tensor on this device or numpy), fully overwritten.
         A random transform, if requested, is drawn per molecule in molecule order.
         """
+        return self._forward_batch(coords, offsets, centers, channels, radii, num_channels, out_grid, random_translation,
+                                   random_rotation)
+
+    def _forward_batch(self, coords, offsets, centers, channels, radii, num_channels=None, out_grid=None,
+                       random_translation=0.0, random_rotation=False, xforms=None, fresh_inputs=False):
+        """forward_batch's body. xforms: (records, device centres) already drawn by the caller (forward_views on a
+        differentiable voxelizer) instead of new ones; fresh_inputs: the caller made the inputs on the current stream a
+        moment ago, so with overlap_prepass the stream is synchronised before the side stream may read them."""
         if self._sigma_src is not None:
             self._sync_sigma()
         radii, rten = self._scalar_radius(radii)
@@ -671,27 +679,16 @@ class Voxelizer(BaseVoxelizer):
             pad = int(C_) - r.shape[0]
             r = torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])
             fresh = fresh or self.overlap_prepass
-        need_xf = centers is not None or random_rotation or (random_translation and random_translation > 0.0)
-        xf_ptr = None
-        dev_cen = None
-        if need_xf:
-            xfs = (_lib.MvxXform * B)()
-            cen = dev_cen = None
-            if centers is not None:
-                if in_kind == _lib.MVX_DEVICE and self._on_device(centers):  # by pointer: no copy to the host
-                    dev_cen = centers.to(torch.float64).contiguous().reshape(B, 3)
-                    keep.append(dev_cen)
-                    fresh = fresh or (self.overlap_prepass and dev_cen.data_ptr() != user_centers.data_ptr())
-                else:
-                    cen = centers.detach().cpu().numpy() if _is_torch(centers) else np.asarray(centers)
-                    cen = cen.reshape(B, 3)
-            for b in range(B):
-                self._make_xform(None if cen is None else cen[b], random_translation, random_rotation)
-                if dev_cen is not None:
-                    self._xf.center_ptr = dev_cen.data_ptr() + 24 * b
-                    self._xf.flags |= _lib.MVX_XF_CENTER | _lib.MVX_XF_CENTER_PTR
-                C.memmove(C.addressof(xfs) + b * C.sizeof(_lib.MvxXform), self._xf_addr, C.sizeof(_lib.MvxXform))
-            xf_ptr = C.addressof(xfs)
+        fresh = fresh or (self.overlap_prepass and fresh_inputs and in_kind == _lib.MVX_DEVICE)
+        if xforms is not None:  # forward_views on a differentiable voxelizer: the records it drew for its views
+            xfs, dev_cen = xforms
+            need_xf = True
+        else:
+            need_xf = centers is not None or random_rotation or (random_translation and random_translation > 0.0)
+            xfs, dev_cen = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep) if need_xf else (None, None)
+            if dev_cen is not None:
+                fresh = fresh or (self.overlap_prepass and dev_cen.data_ptr() != user_centers.data_ptr())
+        xf_ptr = C.addressof(xfs) if need_xf else None
         if out_grid is None:
             out_grid = self.get_empty_grid(C_, batch_size=B)
         assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
@@ -722,6 +719,26 @@ class Voxelizer(BaseVoxelizer):
         _lib.check(launch())
         return self._finish_out(buf, ret, how)
 
+    def _make_xforms(self, B, centers, in_kind, random_translation, random_rotation, keep):
+        """B mvx_xform records, one per molecule (forward_batch) or view (forward_views): centring + the random transform,
+        drawn record by record in order. Returns (records, the device centres handed over by pointer or None)."""
+        xfs = (_lib.MvxXform * B)()
+        cen = dev_cen = None
+        if centers is not None:
+            if in_kind == _lib.MVX_DEVICE and self._on_device(centers):  # by pointer: no copy to the host
+                dev_cen = centers.to(torch.float64).contiguous().reshape(B, 3)
+                keep.append(dev_cen)
+            else:
+                cen = centers.detach().cpu().numpy() if _is_torch(centers) else np.asarray(centers)
+                cen = cen.reshape(B, 3)
+        for b in range(B):
+            self._make_xform(None if cen is None else cen[b], random_translation, random_rotation)
+            if dev_cen is not None:
+                self._xf.center_ptr = dev_cen.data_ptr() + 24 * b
+                self._xf.flags |= _lib.MVX_XF_CENTER | _lib.MVX_XF_CENTER_PTR
+            C.memmove(C.addressof(xfs) + b * C.sizeof(_lib.MvxXform), self._xf_addr, C.sizeof(_lib.MvxXform))
+        return xfs, dev_cen
+
     def _check_args_batch(self, coords, channels, kind, radii, C_):
         """The per-molecule checks (_check_args_features / _types / _single) for atoms stored back to back: the
         library reads sumN rows of channels and sumN | C radii, so every array must really have them."""
@@ -747,6 +764,120 @@ class Voxelizer(BaseVoxelizer):
         else:
             assert not _np_isscalar(radii), f"the radii type of voxelizer is `atom-wise`, radii should be Array[{V},]"
             assert tuple(radii.shape) == (V,), f"radii does not match dimension (number of atoms,): {tuple(radii.shape)} vs {(V,)}"
+
+    # ------------------------------------------------------------------------------------------
+    # VIEWS (many boxes of one shared point cloud: mvx_select_views / mvx_forward_views)
+    def _views_args(self, coords, centers, channels, radii, num_channels):
+        """(kind, C, radii, scalar-radius tensor) of a views call: forward_batch's rules for one molecule of N atoms."""
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, rten = self._scalar_radius(radii)
+        if channels is None:
+            kind, C_ = None, 1
+        elif channels.ndim == 1:
+            kind = "types"
+            C_ = num_channels if num_channels is not None else (
+                radii.shape[0] if self.is_radii_type_channel_wise else int(channels.max()) + 1)
+        else:
+            kind, C_ = "features", channels.shape[1]
+        self._check_args_batch(coords, channels, kind, radii, int(C_))
+        assert centers is not None and centers.ndim == 2 and centers.shape[1] == 3, (
+            f"centers does not match dimension: {tuple(getattr(centers, 'shape', ()))} vs ('B', 3)")
+        return kind, int(C_), radii, rten
+
+    def _views_inputs(self, coords, channels, kind, radii, C_):
+        c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
+        if kind == "types" and self.is_radii_type_channel_wise and r.shape[0] < C_:  # (as forward_batch: the (C,) contract of the ABI)
+            pad = C_ - r.shape[0]
+            r = torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])
+            keep.append(r)
+        return c, ch, r, in_kind, keep
+
+    def _select(self, c, types, r, rs, kind, C_, xfs, B, in_kind):
+        """mvx_select_views into an index buffer sized from the call's shape: B * N entries when that is small, else the
+        last call's total with some room. One call (one synchronisation) unless the buffer turns out too small: the library
+        then reports MVX_ERR_INVALID with the offsets filled in, and the call is repeated with the exact size."""
+        N = int(c.shape[0])
+        offsets = np.full(B + 1, -1, dtype=np.int64)
+        args = (self._handle, self._ptr(c), self._ptr(types), self._ptr(r), rs, self._radii_type_code(),
+                _lib.MODES[kind or "single"], N, C_, C.addressof(xfs), B)
+        cap = B * N if B * N <= (1 << 20) else min(B * N, max(1 << 20, 2 * getattr(self, "_views_total", 0)))
+        index = torch.empty(cap, dtype=torch.int64, device=self.device)
+        rc = self._lib.mvx_select_views(*args, index.data_ptr() if cap else None, cap, offsets.ctypes.data, in_kind, self._stream())
+        if rc != 0 and offsets[-1] > cap:  # too small: size it from the offsets and call again
+            index = torch.empty(int(offsets[-1]), dtype=torch.int64, device=self.device)
+            rc = self._lib.mvx_select_views(*args, index.data_ptr(), index.numel(), offsets.ctypes.data, in_kind, self._stream())
+        _lib.check(rc)
+        self._views_total = int(offsets[-1])
+        return index[:int(offsets[-1])], offsets
+
+    def select_views(self, coords, centers, channels=None, radii=None, random_translation=0.0, random_rotation=False):
+        """The atoms each view of a shared cloud can see: (index, offsets), index an int64 tensor on this voxelizer's
+        device, offsets a numpy int64 array of B + 1 entries; index[offsets[b]:offsets[b + 1]] are, in ascending order, the
+        atoms that pass the forward's box cull for view b (every atom that reaches a voxel of that view's grid is among
+        them). Arguments as forward_views; feature values are not read. Synchronises the stream (the offsets come to the host)."""
+        return self._select_views(coords, centers, channels, radii, random_translation, random_rotation)
+
+    def _select_views(self, coords, centers, channels, radii, random_translation=0.0, random_rotation=False, num_channels=None,
+                      xforms=None):
+        """select_views' body. num_channels: the channel count of a types call; xforms: records already drawn."""
+        kind, C_, radii, _ = self._views_args(coords, centers, channels, radii, num_channels)
+        B = int(centers.shape[0])
+        c, ch, r, in_kind, keep = self._views_inputs(coords, channels if kind == "types" else None, kind if kind == "types" else None,
+                                                     radii, C_)
+        xfs, _ = xforms if xforms is not None else self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
+        rs = float(radii) if _np_isscalar(radii) else 0.0
+        return self._select(c, ch, r, rs, kind, C_, xfs, B, in_kind)
+
+    def forward_views(self, coords, centers, channels, radii, num_channels=None, out_grid=None, random_translation=0.0,
+                      random_rotation=False):
+        """Voxelize B boxes of ONE shared point cloud: grid b is the cloud seen from centers[b] (and through view b's random
+        transform). The (B, C, D, H, W) result is, bit for bit, forward_batch on the cloud repeated B times - without the B
+        copies: each view's atoms are selected on the device (those that pass the forward's box cull), gathered into a
+        compact batch and voxelized by the batched pipeline.
+
+        coords (N,3) float64; centers (B,3); channels: (N,C) float -> features, (N,) int -> types, None -> single;
+        radii: python float | (N,) | (C,) per this voxelizer's radii_type - forward_batch's rules for one molecule of N
+        atoms, and in types mode the channel count is inferred as forward_batch infers it for the whole cloud.
+        A random transform, if requested, is drawn per view in view order, exactly as forward_batch draws one per molecule:
+        with the same seed both calls use the same transforms.
+        The call synchronises the stream once (the per-view atom counts come to the host). `overlap_prepass` does not
+        apply to this entry. On a differentiable voxelizer with inputs that require grad the call is select_views, a torch
+        gather of the selected rows and forward_batch on them: autograd sums every view's gradient into the shared tensors.
+        """
+        kind, C_, cradii, rten = self._views_args(coords, centers, channels, radii, num_channels)
+        B = int(centers.shape[0])
+        if self._grad_wanted(coords, channels if kind == "features" else None, centers, cradii, out_grid, rten):
+            cen = self._grad_center(centers)
+            keep = []
+            in_kind = _lib.MVX_DEVICE  # (_grad_wanted: coords live on this device)
+            xforms = self._make_xforms(B, cen, in_kind, random_translation, random_rotation, keep)
+            with torch.no_grad():
+                index, offsets = self._select_views(coords, centers, channels, cradii,
+                                                    num_channels=C_ if kind == "types" else None, xforms=xforms)
+
+            def take(x):
+                if _is_torch(x):
+                    return x[index.to(x.device)]
+                return np.asarray(x)[index.cpu().numpy()]
+
+            r_sel = take(cradii) if self.is_radii_type_atom_wise else radii
+            # (the gathered rows are made on this stream just now: with overlap_prepass the side stream must not read them
+            # early - fresh_inputs makes _forward_batch synchronise first)
+            return self._forward_batch(coords[index], offsets, cen, None if channels is None else take(channels), r_sel,
+                                       num_channels=C_ if kind == "types" else None, xforms=xforms, fresh_inputs=True)
+        c, ch, r, in_kind, keep = self._views_inputs(coords, channels, kind, cradii, C_)
+        xfs, _ = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
+        if out_grid is None:
+            out_grid = self.get_empty_grid(C_, batch_size=B)
+        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
+            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
+        buf, out_kind, ret, how = self._resolve_out(out_grid, None)
+        rs = float(cradii) if _np_isscalar(cradii) else 0.0
+        _lib.check(self._lib.mvx_forward_views(
+            self._handle, _lib.MODES[kind or "single"], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
+            int(c.shape[0]), C_, C.addressof(xfs), B, self._ptr(buf), in_kind, out_kind, self._stream()))
+        return self._finish_out(buf, ret, how)
 
     # ------------------------------------------------------------------------------------------
     # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
