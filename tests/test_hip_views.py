@@ -12,11 +12,13 @@ import pytest
 
 from tests import views_reference as vr
 from tests.tolerance import assert_exact, assert_gaussian
+from tests.views_rows import CUBE  # noqa: F401  (clouds are uniform in a cube of this edge, centred at the origin)
+from tests.views_rows import centers as _centers
+from tests.views_rows import cloud as _cloud
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CUBE = 40.0  # clouds are uniform in a cube of this edge, centred at the origin
 
 
 def _vox(D, res, radii_type="scalar", density="gaussian", variant="float32", **kw):
@@ -29,39 +31,6 @@ def _vox(D, res, radii_type="scalar", density="gaussian", variant="float32", **k
     elif variant == "precision64":
         kw["precision"] = 64
     return mv.create_voxelizer(res, D, radii_type, density, "hip", output="torch", **kw)
-
-
-def _cloud(seed, N, mode, C, radii_type, edge=CUBE):
-    """(coords, channels, radii) as numpy arrays for one cloud of N atoms."""
-    rng = np.random.default_rng(seed)
-    xyz = rng.uniform(-edge / 2, edge / 2, (N, 3))
-    if mode == "features":
-        chan = rng.random((N, C)).astype(np.float32)
-    elif mode == "types":
-        chan = rng.integers(0, C, N).astype(np.int64)
-    else:
-        chan = None
-    if radii_type == "scalar":
-        radii = 1.5
-    elif radii_type == "atom-wise":
-        radii = rng.uniform(0.8, 2.2, N).astype(np.float32)
-    else:
-        radii = rng.uniform(0.8, 2.2, C).astype(np.float32)
-    return xyz, chan, radii
-
-
-def _centers(seed, B, xyz):
-    """View 0 is centred 1 000 A away (no atoms), view 1 on the cloud, the rest on atoms / random points of the cube."""
-    rng = np.random.default_rng(seed + 1)
-    cen = rng.uniform(-CUBE / 2, CUBE / 2, (B, 3))
-    if xyz.shape[0]:
-        pick = rng.integers(0, xyz.shape[0], B)
-        cen[::2] = xyz[pick[::2]]
-    if B >= 2:
-        cen[0] = [1000.0, 0.0, 0.0]
-        cen[1] = 0.0
-    return cen
-
 
 def _dev(vox, x, dtype=None):
     import torch

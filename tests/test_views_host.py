@@ -12,6 +12,7 @@ import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
 from tests import views_reference as vr
+from tests import views_rows as rows
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MVX_ERR_INVALID = -1
@@ -182,3 +183,131 @@ def test_view_kernels_use_no_scratch():
         assert r["scratch"] == 0 and r["vspill"] == 0 and r["sspill"] == 0, (k, r)
         if "count" in k or "fill" in k:  # the B x N kernels: at least three waves per SIMD (512 VGPRs / 3 = 170, granule 8)
             assert r["vgpr"] <= 168, (k, r)
+
+
+# ---- the complete restatement (views_reference: keep_mask / margin / select_exact) and the rows of test_hip_views_scale.py ----
+FACE = dict(resolution=0.3, dimension=17)  # half = 2.4 is no float32 value, and neither is 2.4 + 1.7
+FACE_RADII = np.array([1.1, 1.7, 0.9], np.float32)
+
+
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_channelwise_bound_is_the_float32_one_at_precision_32(axis):
+    ub = 0.3 * 16 / 2.0
+    hi32 = float(np.float32(ub) + np.float32(1.7))
+    hi64 = ub + float(np.float32(1.7))
+    assert hi32 != hi64  # the geometry tells the two bounds apart
+    xyz, keep = vr.edge_cloud(**FACE, source="channel-features", radius=FACE_RADII, axis=axis, reach=1)
+    # (inner, outer) on the upper face, then on the lower one: one float64 ulp either side of the float32-evaluated bound
+    assert np.array_equal(xyz[:, axis], [np.nextafter(hi32, 0.0), hi32, np.nextafter(-hi32, 0.0), -hi32])
+    assert list(keep) == [True, False, True, False]
+    wide, _ = vr.edge_cloud(**FACE, source="channel-features", radius=FACE_RADII, axis=axis, reach=3)
+    got = vr.keep_mask(wide, **FACE, source="channel-features", radii=FACE_RADII)
+    assert list(got) == [True] * 3 + [False] * 3 + [True] * 3 + [False] * 3
+    # the float64 bound (select with cull_radius: right for every other source) decides at least one of them differently
+    (old,) = vr.select(wide, np.zeros((1, 3)), vr.cull_radius(FACE_RADII, "channel-wise", features_mode=True), 0.3, 17)
+    assert not np.array_equal(old, np.flatnonzero(got))
+    # at precision 64 the bound is the plain float64 one
+    xyz64, keep64 = vr.edge_cloud(**FACE, source="channel-features", radius=FACE_RADII.astype(np.float64), precision=64, axis=axis, reach=1)
+    assert np.array_equal(xyz64[:, axis], [np.nextafter(hi64, 0.0), hi64, np.nextafter(-hi64, 0.0), -hi64])
+    assert list(keep64) == [True, False, True, False]
+
+
+def test_edge_cloud_of_the_atom_wise_form():
+    # p + r > lb and p - r < ub are float64 sums: the flip lies where the rounded sum crosses the bound
+    r = float(np.float32(1.7))
+    xyz, keep = vr.edge_cloud(**FACE, source="atom-wise", radius=np.float32(1.7), reach=2)
+    assert list(keep) == [True, True, False, False] * 2
+    p = xyz[:, 0]
+    assert np.array_equal(keep[:4], p[:4] - r < 2.4) and np.array_equal(keep[4:], p[4:] + r > -2.4)
+    assert np.all(np.abs(np.abs(p) - (2.4 + r)) < 1e-14)
+
+
+@pytest.mark.parametrize("rotated", [False, True], ids=["identity", "rotated"])
+@pytest.mark.parametrize("radii_type", ["scalar", "atom-wise"])
+def test_restated_selection_equals_the_oracle_box_test(radii_type, rotated):
+    from oracle import numpy_port
+
+    res, D = 1.0, 16
+    xyz, _, radii = rows.cloud(31, 3000, "single", 1, radii_type)
+    cen = rows.centers(31, 9, xyz)
+    p = vr.view_positions(xyz, cen, 5, **rows.TRANSFORM) if rotated else vr.view_positions(xyz, cen)
+    if rotated:  # the protocol of forward_views: one draw per view, in view order, from the seeded global RNG
+        from molvoxel_amd.voxelizer.hip.transform import do_transform, draw_forward_transform
+
+        np.random.seed(5)
+        for b in range(9):
+            t, q = draw_forward_transform(1.0, True)
+            assert np.array_equal(p[b], do_transform(xyz - cen[b], None, t, q))
+    else:
+        assert np.array_equal(p[3], vr.positions(xyz, cen[3]))
+    index, offsets = vr.select_exact(p, res, D, radii_type, radii)
+    spec = numpy_port.GridSpec(res, D)
+    size = vr.cull_radius(radii, radii_type)
+    assert offsets[0] == 0 and offsets[-1] == index.size and offsets[1] == 0 and index.size > 1000
+    for b in range(9):
+        assert np.array_equal(index[offsets[b]:offsets[b + 1]], numpy_port._box_keep(spec, p[b], size))
+    m = vr.margin(p, res, D, radii_type, radii)
+    assert m.shape == (9, 3000) and np.all(m > 0)
+
+
+def test_reference_types_outside_the_range_never_pass():
+    p = np.zeros((1, 6, 3))
+    types = np.array([-3, -1, 0, 4, 5, 9])
+    for source, radii in (("scalar", 1.5), ("by-type", np.ones(5, np.float32)), ("atom-wise", np.ones(6, np.float32))):
+        keep = vr.keep_mask(p, 1.0, 16, source, radii, types=types, num_channels=5)
+        assert list(keep[0]) == [False, False, True, True, False, False]
+        assert np.array_equal(np.isinf(vr.margin(p, 1.0, 16, source, radii, types=types, num_channels=5)[0]), ~keep[0])
+
+
+@pytest.mark.parametrize("row", rows.SCAN_ROWS, ids=lambda r: r.id)
+def test_scan_rows_reach_the_pieces_they_name(row):
+    ntiles = -(-row.N // rows.VIEW_TILE)
+    assert row.M == row.B * ntiles and row.per == -(-row.M // rows.SCAN_THREADS)
+    assert min(row.B, ntiles) <= 65535  # the launch-grid rule of mvx_capi.hip: the smaller extent goes in gridDim.y
+
+
+@pytest.mark.parametrize("case", rows.SCAN_CASES, ids=rows.case_id)
+def test_no_scan_row_has_an_atom_within_the_margin(case):
+    row, rotated = case
+    index, offsets, least = rows.row_reference(row, rotated)
+    print(f"{rows.case_id(case)}: total {int(offsets[-1])}, smallest margin {least:.3g} A")
+    assert least >= rows.MARGIN  # zero pairs below it: the GPU test compares every atom
+    counts = np.diff(offsets)
+    assert counts[0] == 0 and offsets[-1] == index.size > 0 and counts.max() > 1
+    if row.shape == "thin-sorted":  # (the fixture, not the kernel)
+        tiles = vr.tile_counts(index, offsets, row.N)
+        assert (tiles == rows.VIEW_TILE).sum() >= 1 and (tiles == 0).sum() >= 200
+    if row.shape == "thin-shuffled":
+        assert (vr.tile_counts(index, offsets, row.N)[1:] > 0).mean() > 0.99
+
+
+@pytest.mark.parametrize("case", rows.SOURCE_CASES, ids=lambda c: f"{c[0].id}-{'rotated' if c[1] else 'identity'}")
+def test_no_source_row_has_an_atom_within_the_margin(case):
+    row, rotated = case
+    index, offsets, least = rows.source_reference(row, rotated)
+    print(f"{row.id}: total {int(offsets[-1])}, smallest margin {least:.3g} A")
+    assert least >= rows.MARGIN
+    assert np.diff(offsets)[0] == 0 and index.size > 1000
+    if row.source == "channel-features":
+        radii = rows.source_inputs(row)[3]
+        assert int(np.argmax(radii)) == 37
+        assert (float(np.float32(radii[37])) == float(radii[37])) == (row.precision == 32)
+
+
+def test_the_comparison_reports_a_swap_and_a_shifted_offset():
+    row = next(r for r in rows.SCAN_ROWS if r.id == "B345-N3000")
+    index, offsets, _ = rows.row_reference(row, False)
+    assert vr.selection_mismatch(index.copy(), offsets.copy(), index, offsets) is None
+    b = int(np.argmax(np.diff(offsets)))  # a view with more than `per` atoms
+    at = int(offsets[b]) + row.per
+    assert offsets[b + 1] - offsets[b] > row.per + 1
+    swapped = index.copy()
+    swapped[[at - 1, at]] = swapped[[at, at - 1]]  # two neighbours across position `per` of the view
+    msg = vr.selection_mismatch(swapped, offsets, index, offsets)
+    assert msg is not None and f"view {b}, entry {row.per - 1}" in msg
+    shifted = offsets.copy()
+    shifted[b] += 1
+    msg = vr.selection_mismatch(index, shifted, index, offsets)
+    assert msg is not None and f"offsets[{b}]" in msg
+    assert vr.selection_mismatch(index[:-1], offsets, index, offsets) is not None
+    assert vr.selection_mismatch(index.astype(np.int32), offsets, index, offsets) is not None
