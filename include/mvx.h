@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVX_VERSION 140 /* 0.1.4: mvx_select_views and mvx_forward_views (additive: many views of one shared cloud); mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
+#define MVX_VERSION 140 /* 0.1.4: MVX_XF_POSE_PTR, MVX_XF_TRANSLATE_ONCE and mvx_pose_grad_batch (additive: explicit rigid poses and their gradients); mvx_select_views and mvx_forward_views (additive: many views of one shared cloud); mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
 
 typedef enum mvx_status {
     MVX_OK = 0,
@@ -69,8 +69,16 @@ enum mvx_xform_flags {
     MVX_XF_ROTATE = 2,    /* p = q * p * q^-1 */
     MVX_XF_TRANSLATE = 4, /* p = p + trans (twice when MVX_XF_ROTATE is also set, as the reference does) */
     MVX_XF_RECENTER = 8,  /* p = p + center after the rotation (do_transform with a center, numpy/transform.py:51-54) */
-    MVX_XF_CENTER_PTR = 16 /* the centre is read from center_ptr (3 doubles in the memory `in_kind` names) instead of
+    MVX_XF_CENTER_PTR = 16, /* the centre is read from center_ptr (3 doubles in the memory `in_kind` names) instead of
                               center[]: a device-resident `center` tensor never has to visit the host */
+    MVX_XF_POSE_PTR = 32,  /* an explicit rigid pose: center_ptr points at 10 doubles [c0 c1 c2 | q0 q1 q2 q3 | t0 t1 t2] in the
+                              memory `in_kind` names, p = q (x - c) conj(q) + t: the centre subtracted, the sandwich product in
+                              the operation order of MVX_XF_ROTATE with q as given (the linear part scales by |q|^2; normalise
+                              q beforehand for a pure rotation), then t - rounded to float32 when it is read, as `trans` is -
+                              added ONCE. Every other flag bit of such a record must be clear. Every entry that takes records
+                              accepts it; a device-resident pose never visits the host (a small kernel rewrites the call's
+                              device copy of the record as MVX_XF_CENTER | ROTATE | TRANSLATE | TRANSLATE_ONCE) */
+    MVX_XF_TRANSLATE_ONCE = 64 /* with MVX_XF_ROTATE | MVX_XF_TRANSLATE: the translation is added once, not twice */
 };
 
 /*
@@ -125,7 +133,8 @@ typedef struct mvx_xform {
     double quat[4];   /* (q0, q1, q2, q3) as returned by random_quaternion, _quaternion.py:13-21 */
     float trans[3];   /* float32 like numpy/transform.py:76 */
     uint32_t flags;   /* enum mvx_xform_flags */
-    const double *center_ptr; /* MVX_XF_CENTER_PTR: where the centre lives (same memory kind as coords) */
+    const double *center_ptr; /* MVX_XF_CENTER_PTR: where the centre lives (same memory kind as coords);
+                                 MVX_XF_POSE_PTR: where the 10 doubles of the pose live */
 } mvx_xform;
 
 typedef struct mvx_handle mvx_handle;
@@ -329,6 +338,27 @@ int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords
                                double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
                                int32_t B, int32_t C, const void *grad_out, double *grad_coords, mvx_real *grad_features,
                                double *grad_radii, double *grad_sigma, double *grad_radius_scalar, void *stream);
+
+/*
+ * Gradients with respect to explicit rigid poses (MVX_XF_POSE_PTR records; no counterpart in the reference): the reduction of
+ * the per-atom gradients a backward entry wrote for the same call (grad_coords = M^T dL/dp) to dL/dc, dL/dq and dL/dt of every
+ * molecule, on the device. Per molecule with pose (c, q, t), M = M(q) the linear part of the sandwich product (it scales by
+ * |q|^2), g_n = grad_coords[n], s = sum_n g_n, U = sum_n g_n (x_n - c)^T and n4 = |q|^4 (M M^T = |q|^4 I, so dL/dp_n = M g_n / n4):
+ *   dL/dc   = -s
+ *   dL/dt   = M s / n4                          (straight through the float32 rounding of t)
+ *   dL/dq_k = < dM/dq_k , M U / n4 >            (k = 0 .. 3; q is used as given, nothing is normalised)
+ * U is accumulated from x_n - c, never as sum g x^T - s c^T (centres lie tens of Angstrom from the origin).
+ * grad_pose: (B, 10) doubles on the device, [dc0 dc1 dc2 | dq0 dq1 dq2 dq3 | dt0 dt1 dt2] per molecule, fully overwritten; a
+ * molecule without atoms gets zeros; q = 0 gives a non-finite row. Deterministic: one workgroup per molecule, each wave takes
+ * the molecule's atoms in chunks of 64 in order, a fixed butterfly per wave, the waves in order; no atomics; a molecule's row
+ * is bit for bit the same in any batch and across runs. coords, grad_coords, grad_pose and the poses the records point at are
+ * device pointers; offsets and xforms are host pointers as in the backward entries. Asynchronous on `stream`.
+ * MVX_ERR_INVALID before any device is touched for: B < 0; NULL grad_pose, xforms or offsets with B > 0; non-monotone offsets;
+ * NULL coords or grad_coords with atoms present; a record without MVX_XF_POSE_PTR (or with other flag bits, or a NULL
+ * center_ptr); a NULL handle.
+ */
+int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_coords, const int64_t *offsets,
+                        const mvx_xform *xforms, int32_t B, double *grad_pose, void *stream);
 
 /*
  * Replaces do_transform on an (N,3) fp64 point cloud (numpy/transform.py:44-60): out = transformed coords.

@@ -7,6 +7,7 @@
 #include "mvx_grad.h"
 #include "mvx_internal.h"
 #include "mvx_plan.h"
+#include "mvx_pose.h"
 #include "mvx_views.h"
 
 #include <algorithm>
@@ -98,6 +99,7 @@ struct mvx_handle {
     // the backward pass (mvx_backward_batch) keeps buffers of its own: it never writes a workspace set that an overlapped
     // pre-pass (mvx_set_overlap) on the side stream may be filling, nor one that voxelize launches may still read
     DevBuf grad_rec, grad_xp, grad_meta, grad_aux, grad_sort;
+    DevBuf pose_meta;  // mvx_pose_grad_batch: the call's offsets and records
     DevBuf grad_rpart; // radius gradients: per-atom / per-(channel, atom) partials of channel-wise radii and their stage sums
     // "grad_order" option: 0 atoms in the caller's order (the default), 1 in spatial order, XCD by XCD. The spatial order cuts
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
@@ -221,6 +223,20 @@ int adopt_stream(mvx_handle *h, hipStream_t s) {
     return MVX_OK;
 }
 
+// Explicit poses (MVX_XF_POSE_PTR): the other flag bits of such a record are clear and its pointer is set.
+int check_pose_records(const mvx_xform *xf, int n) {
+    for (int i = 0; xf && i < n; ++i)
+        if ((xf[i].flags & MVX_XF_POSE_PTR) && (xf[i].flags != MVX_XF_POSE_PTR || !xf[i].center_ptr))
+            return fail(MVX_ERR_INVALID, "a MVX_XF_POSE_PTR record must have every other flag bit clear and a non-null center_ptr");
+    return MVX_OK;
+}
+
+bool has_pose_records(const mvx_xform *xf, int n) {
+    for (int i = 0; xf && i < n; ++i)
+        if (xf[i].flags & MVX_XF_POSE_PTR) return true;
+    return false;
+}
+
 // ---- 1. what the library checks itself (shapes are the Python layer's job) -----------------------------------------
 int validate(const mvx_handle *h, const RunArgs &r, int64_t &total, int64_t &max_atoms) {
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
@@ -246,7 +262,7 @@ int validate(const mvx_handle *h, const RunArgs &r, int64_t &total, int64_t &max
         return fail(MVX_ERR_INVALID, "radii array required");
     if (total > 0 && r.mode != MODE_SINGLE && !r.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
     if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
-    return MVX_OK;
+    return check_pose_records(r.xforms, r.B);
 }
 
 // ---- 2. inputs and metadata on the device ---------------------------------------------------------------------------
@@ -259,9 +275,16 @@ struct DeviceInputs {
     PinnedSlot *slot = nullptr; // holds the host copies until `done` fires
 };
 
-// With host-resident inputs a centre given by pointer (MVX_XF_CENTER_PTR) is a host pointer: fold it into center[].
+// With host-resident inputs a centre given by pointer (MVX_XF_CENTER_PTR) is a host pointer: fold it into center[]; a pose
+// (MVX_XF_POSE_PTR) likewise: the record becomes the plain one pose_resolve_kernel writes for device poses.
 void resolve_host_centers(mvx_xform *xf, int n) {
     for (int i = 0; i < n; ++i) {
+        if (xf[i].flags & MVX_XF_POSE_PTR) {
+            double pose[10];
+            std::memcpy(pose, xf[i].center_ptr, sizeof(pose));
+            pose_to_record(pose, xf[i]);
+            continue;
+        }
         if (xf[i].flags & MVX_XF_CENTER_PTR) {
             if (xf[i].center_ptr) std::memcpy(xf[i].center, xf[i].center_ptr, 3 * sizeof(double));
             xf[i].flags &= ~(uint32_t)MVX_XF_CENTER_PTR;
@@ -307,6 +330,8 @@ int stage_inputs(mvx_handle *h, Workspace &w, const RunArgs &r, int64_t total, s
             if (host_in) resolve_host_centers(reinterpret_cast<mvx_xform *>(pin + off_bytes), r.B);
         }
         HIP_TRY(hipMemcpyAsync(w.meta.p, pin, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
+        if (!host_in && has_pose_records(r.xforms, r.B)) // device-resident poses: the device copy becomes plain records
+            HIP_TRY(launch_pose_resolve(reinterpret_cast<mvx_xform *>((char *)w.meta.p + off_bytes), r.B, s));
         w.meta_last.assign(reinterpret_cast<const char *>(r.offsets), reinterpret_cast<const char *>(r.offsets) + meta_used);
         w.meta_valid = !r.xforms; // (a later call on another stream waits for this stream first: adopt_stream)
     }
@@ -465,7 +490,9 @@ int run(mvx_handle *h, const RunArgs &r) {
     }
 
     DeviceInputs in;
-    const bool by_value = (r.B == 1 && r.in_kind == MVX_DEVICE && nchunk == 1); // one molecule of device arrays
+    // (a device-resident pose is read on the device: its record is staged and resolved there, never passed by value)
+    const bool dev_pose = r.in_kind == MVX_DEVICE && has_pose_records(r.xforms, r.B);
+    const bool by_value = (r.B == 1 && r.in_kind == MVX_DEVICE && nchunk == 1 && !dev_pose); // one molecule of device arrays
     if (by_value) { // nothing to stage: extent and transform travel with the launches
         in.coords = r.coords;
         in.channels = r.channels;
@@ -598,9 +625,9 @@ int run(mvx_handle *h, const RunArgs &r) {
         da.N = total;
         if (r.B == 1) { // one molecule: extent and transform by value, no metadata on the device
             da.pa.offsets = nullptr;
-            da.pa.xforms = nullptr;
+            da.pa.xforms = dev_pose ? in.xforms : nullptr;
             std::memset(&da.pa.xf_one, 0, sizeof(da.pa.xf_one));
-            if (r.xforms) {
+            if (r.xforms && !dev_pose) {
                 da.pa.xf_one = r.xforms[0];
                 if (r.in_kind == MVX_HOST) resolve_host_centers(&da.pa.xf_one, 1);
             }
@@ -754,7 +781,7 @@ int mvx_destroy(mvx_handle *h) {
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
     std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage,
-                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart,
+                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart, &h->pose_meta,
                                   &h->view_xf, &h->view_counts, &h->view_base, &h->view_off, &h->view_aux, &h->view_index,
                                   &h->view_coords, &h->view_chan, &h->view_radii};
     for (Workspace &w : h->ws) {
@@ -891,7 +918,7 @@ int validate_views(const mvx_handle *h, const ViewCall &v, const char *own) {
     if (v.N >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
     if (own) return fail(MVX_ERR_INVALID, own);
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    return MVX_OK;
+    return check_pose_records(v.xforms, v.B); // (the first rule that reads the records)
 }
 
 // the cloud and the views' transforms as device arrays
@@ -923,6 +950,7 @@ int stage_views(mvx_handle *h, const ViewCall &v, bool select_only, ViewInputs &
     if ((rc = ensure(h->view_xf, xf_bytes))) return rc;
     std::memcpy(slot->p, in.xforms_host.data(), (size_t)v.B * sizeof(mvx_xform));
     HIP_TRY(hipMemcpyAsync(h->view_xf.p, slot->p, (size_t)v.B * sizeof(mvx_xform), hipMemcpyHostToDevice, s));
+    if (!host_in && has_pose_records(v.xforms, v.B)) HIP_TRY(launch_pose_resolve(static_cast<mvx_xform *>(h->view_xf.p), v.B, s));
     in.xforms = reinterpret_cast<const mvx_xform *>(h->view_xf.p);
     in.coords = v.coords;
     in.channels = v.channels;
@@ -1128,6 +1156,7 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
     for (int b = 0; b < B; ++b)
         if (offsets[b + 1] < offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (int prc = check_pose_records(xforms, B)) return prc; // (the first rule that reads the records)
     const int64_t total = B > 0 ? offsets[B] : 0;
     // (no atoms: no gradient rows; channel-wise radii still get their C zeros, sigma and a scalar radius their zero)
     const bool radii_by_channel = grad_radii && radii_type == MVX_RADII_CHANNEL;
@@ -1167,6 +1196,8 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
     std::memcpy(slot->p, offsets, (size_t)(B + 1) * sizeof(int64_t));
     if (xforms) std::memcpy(slot->p + off_bytes, xforms, xf_bytes);
     HIP_TRY(hipMemcpyAsync(h->grad_meta.p, slot->p, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
+    if (has_pose_records(xforms, B)) // (this entry takes device arrays only: the poses are device memory)
+        HIP_TRY(launch_pose_resolve(reinterpret_cast<mvx_xform *>((char *)h->grad_meta.p + off_bytes), B, s));
     const int64_t *d_offsets = reinterpret_cast<const int64_t *>(h->grad_meta.p);
     const mvx_xform *d_xforms = xforms ? reinterpret_cast<const mvx_xform *>((char *)h->grad_meta.p + off_bytes) : nullptr;
 
@@ -1317,9 +1348,50 @@ int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords
                          grad_features, BWD_DENSITY, grad_radii, grad_sigma, grad_radius_scalar, stream);
 }
 
+int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_coords, const int64_t *offsets,
+                        const mvx_xform *xforms, int32_t B, double *grad_pose, void *stream) {
+    // ---- what is checked before any device is touched ----
+    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (B > 0 && !grad_pose) return fail(MVX_ERR_INVALID, "grad_pose must not be null");
+    if (B > 0 && !xforms) return fail(MVX_ERR_INVALID, "xforms must not be null");
+    if (B > 0 && !offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
+    if (B > 0 && offsets[0] != 0) return fail(MVX_ERR_INVALID, "offsets[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (offsets[b + 1] < offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
+    const int64_t total = B > 0 ? offsets[B] : 0;
+    if (total > 0 && (!coords || !grad_coords)) return fail(MVX_ERR_INVALID, "coords / grad_coords must not be null");
+    for (int b = 0; b < B; ++b)
+        if (!(xforms[b].flags & MVX_XF_POSE_PTR)) return fail(MVX_ERR_INVALID, "every record must be a MVX_XF_POSE_PTR record");
+    if (int prc = check_pose_records(xforms, B)) return prc;
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (B == 0) return MVX_OK;
+
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = adopt_stream(h, s);
+    if (rc) return rc;
+    // offsets and records through a pinned slot, as the backward entries stage them (the records stay as they are: the
+    // kernel reads each pose through its pointer)
+    const size_t off_bytes = align_up((size_t)(B + 1) * sizeof(int64_t), 16);
+    const size_t xf_bytes = (size_t)B * sizeof(mvx_xform);
+    PinnedSlot *slot = nullptr;
+    if ((rc = acquire_slot(h, off_bytes + xf_bytes, &slot))) return rc;
+    if ((rc = ensure(h->pose_meta, off_bytes + xf_bytes))) return rc;
+    std::memcpy(slot->p, offsets, (size_t)(B + 1) * sizeof(int64_t));
+    std::memcpy(slot->p + off_bytes, xforms, xf_bytes);
+    HIP_TRY(hipMemcpyAsync(h->pose_meta.p, slot->p, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_pose_grad(coords, grad_coords, reinterpret_cast<const int64_t *>(h->pose_meta.p),
+                             reinterpret_cast<const mvx_xform *>((char *)h->pose_meta.p + off_bytes), B, grad_pose, s));
+    HIP_TRY(hipEventRecord(slot->done, s));
+    slot->in_flight = true;
+    return MVX_OK;
+}
+
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,
                          int32_t in_kind, int32_t out_kind, void *stream) {
     if (!h || !xform || (N > 0 && (!coords || !out))) return fail(MVX_ERR_INVALID, "null argument");
+    if (int prc = check_pose_records(xform, 1)) return prc;
     if (N <= 0) return MVX_OK;
     DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
@@ -1335,6 +1407,7 @@ int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const m
     std::memcpy(slot->p, xform, sizeof(mvx_xform));
     if (host_in) resolve_host_centers(reinterpret_cast<mvx_xform *>(slot->p), 1);
     HIP_TRY(hipMemcpyAsync(h->xf_buf.p, slot->p, xf_bytes, hipMemcpyHostToDevice, s));
+    if (!host_in && has_pose_records(xform, 1)) HIP_TRY(launch_pose_resolve(static_cast<mvx_xform *>(h->xf_buf.p), 1, s));
     const double *d_in = coords;
     if (host_in) {
         if ((rc = ensure(h->in_coords, co_bytes))) return rc;

@@ -139,7 +139,12 @@ __device__ inline void apply_xform(const mvx_xform &xf, double &x, double &y, do
             z += t2;
         }
     }
-    if (xf.flags & MVX_XF_TRANSLATE) { // ... and `coords = coords + translation` again (reference quirk Q4)
+    // ... and `coords = coords + translation` again (reference quirk Q4) - not after the rotation of an explicit pose.
+    // One scalar mask and the branch that was here before: written as a second comparison, or as a factor on t, the condition
+    // moved the per-molecule kernels' register spills past the bounds the resource tests pin.
+    static_assert((MVX_XF_TRANSLATE_ONCE >> 4) == MVX_XF_TRANSLATE && (MVX_XF_ROTATE << 1) == MVX_XF_TRANSLATE,
+                  "both shifted flags must land on MVX_XF_TRANSLATE");
+    if (xf.flags & ~((xf.flags >> 4) & (xf.flags << 1)) & MVX_XF_TRANSLATE) {
         x = x + t0;
         y = y + t1;
         z = z + t2;
@@ -184,7 +189,8 @@ __device__ __forceinline__ XformF32 make_xform_f32(const mvx_xform &xf) {
     X.c0 = cen ? (float)c0 : 0.0f;
     X.c1 = cen ? (float)c1 : 0.0f;
     X.c2 = cen ? (float)c2 : 0.0f;
-    const float tm = tr ? (rot ? 2.0f : 1.0f) : 0.0f; // the translation is applied twice after a rotation (quirk Q4)
+    // the translation is applied twice after a rotation (quirk Q4), once for an explicit pose (MVX_XF_TRANSLATE_ONCE)
+    const float tm = tr ? ((rot && !(xf.flags & MVX_XF_TRANSLATE_ONCE)) ? 2.0f : 1.0f) : 0.0f;
     X.o0 = tm * xf.trans[0] + (rec ? (float)c0 : 0.0f);
     X.o1 = tm * xf.trans[1] + (rec ? (float)c1 : 0.0f);
     X.o2 = tm * xf.trans[2] + (rec ? (float)c2 : 0.0f);

@@ -18,6 +18,7 @@ MVX_RADII_SCALAR, MVX_RADII_ATOM, MVX_RADII_CHANNEL = 0, 1, 2
 MVX_GRID_REAL, MVX_GRID_BF16 = 0, 1
 MVX_LAYOUT_NCDHW, MVX_LAYOUT_NDHWC = 0, 1
 MVX_XF_CENTER, MVX_XF_ROTATE, MVX_XF_TRANSLATE, MVX_XF_RECENTER, MVX_XF_CENTER_PTR = 1, 2, 4, 8, 16
+MVX_XF_POSE_PTR, MVX_XF_TRANSLATE_ONCE = 32, 64
 
 
 class MvxConfig(C.Structure):
@@ -93,6 +94,7 @@ SIGNATURES = {
     "mvx_backward_radii_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mvx_backward_density_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp]),
+    "mvx_pose_grad_batch": (C.c_int, [Handle, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "mvx_transform_coords": (C.c_int, [Handle, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "mvx_set_profiling": (C.c_int, [Handle, _i32]),
     "mvx_profile_read": (C.c_int, [Handle, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),

@@ -21,6 +21,8 @@ channels-last (NDHWC, `torch.channels_last_3d`) grids directly: same logical sha
 (faster than converting afterwards with bfloat16 grids; experimental with float32 grids: DESIGN.md section 14).
 `sigma_grad=True` (with `differentiable=True`) lets `sigma=`
 / `set_sigma()` take a one-element tensor that gets dL/dsigma (mvx_backward_density_batch).
+`forward_posed_batch` / `forward_posed_views` / `select_posed_views` take explicit rigid poses p = q (x - c) conj(q) + t instead of
+drawing random transforms; on a differentiable voxelizer the poses get their gradients (mvx_pose_grad_batch).
 """
 from __future__ import annotations
 
@@ -643,10 +645,11 @@ class Voxelizer(BaseVoxelizer):
                                    random_rotation)
 
     def _forward_batch(self, coords, offsets, centers, channels, radii, num_channels=None, out_grid=None,
-                       random_translation=0.0, random_rotation=False, xforms=None, fresh_inputs=False):
+                       random_translation=0.0, random_rotation=False, xforms=None, fresh_inputs=False, pose=None):
         """forward_batch's body. xforms: (records, device centres) already drawn by the caller (forward_views on a
-        differentiable voxelizer) instead of new ones; fresh_inputs: the caller made the inputs on the current stream a
-        moment ago, so with overlap_prepass the stream is synchronised before the side stream may read them."""
+        differentiable voxelizer, the posed forms) instead of new ones; fresh_inputs: the caller made the inputs on the current
+        stream a moment ago, so with overlap_prepass the stream is synchronised before the side stream may read them; pose: the
+        packed (B, 10) poses the records point at (the posed forms; `centers` is None then)."""
         if self._sigma_src is not None:
             self._sync_sigma()
         radii, rten = self._scalar_radius(radii)
@@ -662,7 +665,8 @@ class Voxelizer(BaseVoxelizer):
         else:
             kind, C_ = "features", channels.shape[1]
         self._check_args_batch(coords, channels, kind, radii, int(C_))
-        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers, radii, out_grid, rten)
+        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, radii,
+                                 out_grid, rten)
         user_centers = centers  # (a conversion made below, for autograd or for the ABI, is "fresh")
         if grad and centers is not None:
             centers = self._grad_center(centers)
@@ -715,7 +719,7 @@ class Voxelizer(BaseVoxelizer):
         if grad:
             return self._autograd(launch, ret, kind or "single", c, ch if kind == "features" else None,
                                   dev_cen, ch if kind == "types" else None, r, rs, offsets,
-                                  xfs if need_xf else None, B, int(C_), rten)
+                                  xfs if need_xf else None, B, int(C_), rten, pose)
         _lib.check(launch())
         return self._finish_out(buf, ret, how)
 
@@ -845,13 +849,26 @@ class Voxelizer(BaseVoxelizer):
         apply to this entry. On a differentiable voxelizer with inputs that require grad the call is select_views, a torch
         gather of the selected rows and forward_batch on them: autograd sums every view's gradient into the shared tensors.
         """
+        return self._forward_views(coords, centers, channels, radii, num_channels, out_grid, random_translation, random_rotation)
+
+    def _forward_views(self, coords, centers, channels, radii, num_channels=None, out_grid=None, random_translation=0.0,
+                       random_rotation=False, posed=None):
+        """forward_views' body. posed: (quaternions, translations) of forward_posed_views: the views' records are explicit
+        poses instead of centres with random transforms."""
         kind, C_, cradii, rten = self._views_args(coords, centers, channels, radii, num_channels)
         B = int(centers.shape[0])
-        if self._grad_wanted(coords, channels if kind == "features" else None, centers, cradii, out_grid, rten):
-            cen = self._grad_center(centers)
+        pose = None
+        if posed is not None:
+            pose = self._pack_pose(B, centers, posed[0], posed[1], self._on_device(coords))
+        if self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, cradii, out_grid,
+                             rten):
             keep = []
             in_kind = _lib.MVX_DEVICE  # (_grad_wanted: coords live on this device)
-            xforms = self._make_xforms(B, cen, in_kind, random_translation, random_rotation, keep)
+            if pose is None:
+                cen = self._grad_center(centers)
+                xforms = self._make_xforms(B, cen, in_kind, random_translation, random_rotation, keep)
+            else:
+                cen, xforms = None, (self._pose_xforms(pose, B), None)
             with torch.no_grad():
                 index, offsets = self._select_views(coords, centers, channels, cradii,
                                                     num_channels=C_ if kind == "types" else None, xforms=xforms)
@@ -865,9 +882,12 @@ class Voxelizer(BaseVoxelizer):
             # (the gathered rows are made on this stream just now: with overlap_prepass the side stream must not read them
             # early - fresh_inputs makes _forward_batch synchronise first)
             return self._forward_batch(coords[index], offsets, cen, None if channels is None else take(channels), r_sel,
-                                       num_channels=C_ if kind == "types" else None, xforms=xforms, fresh_inputs=True)
+                                       num_channels=C_ if kind == "types" else None, xforms=xforms, fresh_inputs=True, pose=pose)
         c, ch, r, in_kind, keep = self._views_inputs(coords, channels, kind, cradii, C_)
-        xfs, _ = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
+        if pose is None:
+            xfs, _ = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
+        else:
+            xfs = self._pose_xforms(pose, B)
         if out_grid is None:
             out_grid = self.get_empty_grid(C_, batch_size=B)
         assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
@@ -878,6 +898,69 @@ class Voxelizer(BaseVoxelizer):
             self._handle, _lib.MODES[kind or "single"], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
             int(c.shape[0]), C_, C.addressof(xfs), B, self._ptr(buf), in_kind, out_kind, self._stream()))
         return self._finish_out(buf, ret, how)
+
+    # ------------------------------------------------------------------------------------------
+    # POSES (explicit rigid transforms: MVX_XF_POSE_PTR records, mvx_pose_grad_batch)
+    def _pack_pose(self, B, centers, quaternions, translations, on_device):
+        """The (B, 10) float64 block [c | q | t] the records of a posed call point at. With coordinates on this device the block
+        is a tensor there: torch tensors are packed with torch ops (recorded by autograd; their values never visit the host and
+        nothing synchronises), numpy poses are packed on the host and uploaded. With host coordinates: a numpy array."""
+        def shape(x):
+            return tuple(getattr(x, "shape", ()))
+
+        assert shape(quaternions) == (B, 4), f"quaternions does not match dimension: {shape(quaternions)} vs {(B, 4)}"
+        assert shape(translations) == (B, 3), f"translations does not match dimension: {shape(translations)} vs {(B, 3)}"
+        assert centers is None or shape(centers) == (B, 3), f"centers does not match dimension: {shape(centers)} vs {(B, 3)}"
+        parts = [centers, quaternions, translations]
+        if on_device and any(self._on_device(x) for x in parts):
+            dev = [torch.zeros((B, 3), dtype=torch.float64, device=self.device) if x is None else
+                   (x if _is_torch(x) else torch.as_tensor(np.asarray(x, dtype=np.float64))).to(device=self.device, dtype=torch.float64)
+                   for x in parts]
+            return torch.cat(dev, dim=1).contiguous()
+        host = [np.zeros((B, 3)) if x is None else
+                np.asarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float64) for x in parts]
+        block = np.ascontiguousarray(np.concatenate(host, axis=1), dtype=np.float64)
+        return torch.as_tensor(block, device=self.device) if on_device else block
+
+    def _pose_xforms(self, pose, B):
+        """B MVX_XF_POSE_PTR records, record b pointing at row b of the packed poses."""
+        xfs = (_lib.MvxXform * B)()
+        base = self._ptr(pose)
+        for b in range(B):
+            xfs[b].flags = _lib.MVX_XF_POSE_PTR
+            xfs[b].center_ptr = base + 80 * b
+        return xfs
+
+    def forward_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, num_channels=None,
+                            out_grid=None):
+        """forward_batch with one explicit rigid pose per molecule instead of random transforms: atom x of molecule b lands at
+        p = q_b (x - c_b) conj(q_b) + t_b - the centre subtracted, the sandwich product in the random rotation's operation order
+        with q as given (the linear part scales by |q|^2: normalise q in torch beforehand for a pure rotation, autograd carries
+        the normalisation), then t, rounded to float32, added once.
+
+        quaternions (B,4) as (q0, q1, q2, q3); translations (B,3); centers (B,3) | None (c = 0); any float dtype, torch tensors
+        or numpy arrays. Tensors on this voxelizer's device are handed over by pointer: no host round trip, no synchronisation.
+        The other arguments are forward_batch's. On a differentiable voxelizer, `centers`, `quaternions` and `translations`
+        that require grad get dL/dc, dL/dq and dL/dt (mvx_pose_grad_batch; deterministic), next to the gradients of coords,
+        features, radii and sigma. q = 0 gives non-finite pose gradients."""
+        B = np.asarray(offsets).shape[0] - 1
+        pose = self._pack_pose(B, centers, quaternions, translations, self._on_device(coords))
+        return self._forward_batch(coords, offsets, None, channels, radii, num_channels, out_grid,
+                                   xforms=(self._pose_xforms(pose, B), None), fresh_inputs=_is_torch(pose), pose=pose)
+
+    def forward_posed_views(self, coords, centers, quaternions, translations, channels, radii, num_channels=None, out_grid=None):
+        """forward_views with one explicit rigid pose per view instead of a centre and a random transform: B poses of ONE
+        shared cloud (docking poses of a ligand, the 24 cube rotations, poses under refinement) without B copies of it - bit for
+        bit forward_posed_batch on the cloud repeated B times. centers (B,3), quaternions (B,4), translations (B,3) as there.
+        On a differentiable voxelizer every view's pose gets its own gradient and the per-atom gradients of all views sum into
+        the shared tensors. Synchronises the stream once, as forward_views does."""
+        return self._forward_views(coords, centers, channels, radii, num_channels, out_grid, posed=(quaternions, translations))
+
+    def select_posed_views(self, coords, centers, quaternions, translations, channels=None, radii=None):
+        """select_views for explicit poses: the atoms each pose of forward_posed_views keeps, as (index, offsets)."""
+        B = int(centers.shape[0])
+        pose = self._pack_pose(B, centers, quaternions, translations, self._on_device(coords))
+        return self._select_views(coords, centers, channels, radii, xforms=(self._pose_xforms(pose, B), None))
 
     # ------------------------------------------------------------------------------------------
     # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
@@ -915,7 +998,7 @@ class Voxelizer(BaseVoxelizer):
         """The mvx_xform record of a single-molecule call (the voxelizer reuses its own), or None."""
         return None if xf is None else _lib.MvxXform.from_buffer_copy(_lib.MvxXform.from_address(xf))
 
-    def _autograd(self, launch, ret, mode, c, f, center, types, r, rs, offsets, xforms, B, C_, rten=None):
+    def _autograd(self, launch, ret, mode, c, f, center, types, r, rs, offsets, xforms, B, C_, rten=None, pose=None):
         cen = center if (_is_torch(center) and self._on_device(center)) else None
         # radii_grad: the radii as the call hands them to the library (dtype conversion / type padding recorded by autograd)
         rin = r if (self.radii_grad and _is_torch(r) and r.requires_grad) else None
@@ -924,7 +1007,7 @@ class Voxelizer(BaseVoxelizer):
         sig = self.sigma_tensor
         sig = sig if (sig is not None and sig.requires_grad) else None
         rsc = rten if (rten is not None and rten.requires_grad) else None
-        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen, rin, sig, rsc)
+        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen, rin, sig, rsc, pose)
 
     def _grad_settings(self):
         """What the backward reads from the voxelizer rather than from the call: density, sigma and radii type."""
@@ -966,6 +1049,15 @@ class Voxelizer(BaseVoxelizer):
         _lib.check(rc)
         return gc, gf, None if gr is None else gr.to(r.dtype), gsig, grs
 
+    def _pose_backward(self, spec, c, gc):
+        """dL/dpose (B, 10) float64 = [dL/dc | dL/dq | dL/dt] per molecule from the call's dL/dcoords, on the current stream."""
+        gp = torch.zeros((spec["B"], 10), dtype=torch.float64, device=self.device)
+        if c.shape[0] == 0 or spec["B"] == 0:
+            return gp
+        _lib.check(self._lib.mvx_pose_grad_batch(self._handle, self._ptr(c), self._ptr(gc), spec["offsets"].ctypes.data,
+                                                 C.addressof(spec["xforms"]), spec["B"], gp.data_ptr(), self._stream()))
+        return gp
+
     # ------------------------------------------------------------------------------------------
     # measurement hooks used by bench.py (HIP events around the voxelize kernel on the launch stream)
     def debug_option(self, name: str, value: int):
@@ -1003,23 +1095,23 @@ class Voxelizer(BaseVoxelizer):
 if torch is not None:
 
     class _VoxelizeFunction(torch.autograd.Function):
-        """grid = voxelize(coords, features, center, radii, sigma, scalar radius): the forward call as it runs without autograd
+        """grid = voxelize(coords, features, center, radii, sigma, scalar radius, packed poses): the forward call as it runs without autograd
         (same kernels, same bits); backward = mvx_backward_batch (mvx_backward_radii_batch with radii, mvx_backward_density_batch
         with sigma or a scalar radius) from the saved inputs and the call's mvx_xform records."""
 
         @staticmethod
-        def forward(ctx, vox, launch, ret, spec, c, f, cen, r, sig, rsc):
+        def forward(ctx, vox, launch, ret, spec, c, f, cen, r, sig, rsc, pose):
             _lib.check(launch())
             ctx.vox, ctx.spec = vox, spec
-            ctx.save_for_backward(c, f, cen)
+            ctx.save_for_backward(c, f, cen, pose)  # (pose: the packed (B, 10) block the call's records point at; kept alive)
             ctx.scalars = (sig, rsc)  # (read for their shape, dtype and device only: the values travelled as host floats)
             return ret
 
         @staticmethod
         @torch.autograd.function.once_differentiable
         def backward(ctx, grad):
-            c, f, cen = ctx.saved_tensors
-            need_c, need_f, need_cen, need_r, need_sig, need_rsc = ctx.needs_input_grad[4:10]
+            c, f, cen, pose = ctx.saved_tensors
+            need_c, need_f, need_cen, need_r, need_sig, need_rsc, need_pose = ctx.needs_input_grad[4:11]
             gc, gf, gr, gsig, grs = ctx.vox._backward(ctx.spec, c, f, grad, need_f, need_r, need_sig, need_rsc)
             like = lambda g, t: None if g is None else g.to(dtype=t.dtype).reshape(t.shape).to(t.device)  # noqa: E731
             gsig, grs = like(gsig, ctx.scalars[0]), like(grs, ctx.scalars[1])
@@ -1030,7 +1122,9 @@ if torch is not None:
                 else:
                     lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
                     gcen = -torch.segment_reduce(gc, "sum", lengths=lengths, axis=0).reshape(cen.shape)
-            return None, None, None, None, gc if need_c else None, gf, gcen, gr, gsig, grs
+            # explicit poses: the per-atom gradients reduced to dL/dc, dL/dq, dL/dt per molecule (autograd splits the block)
+            gpose = ctx.vox._pose_backward(ctx.spec, c, gc) if need_pose else None
+            return None, None, None, None, gc if need_c else None, gf, gcen, gr, gsig, grs, gpose
 
 
 def transform_on_device(coords, center, translation, quaternion):
