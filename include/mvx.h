@@ -340,6 +340,36 @@ int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords
                                double *grad_radii, double *grad_sigma, double *grad_radius_scalar, void *stream);
 
 /*
+ * Scores of a batch against a constant field grid F, without the grids (no counterpart in the reference): the score
+ * S_b = sum_{c,v} F[c,v] grid_b[c,v] is linear in the grid, so with rho and w as for mvx_backward_batch it splits by atom,
+ *   S_b = sum_{n in b} s_n,   s_n = sum_v sum_c F[c,v] w[n,c] rho_{n,c}(v),
+ * and one walk of the atoms' admitted boxes over F - the walk of mvx_backward_batch - gives the scores, the per-atom
+ * contributions s_n and the gradients of L = sum_b S_b. No grid is written or read and no copy of the field is made.
+ *   field:            the handle's grid type (float, double or bfloat16), NCDHW contiguous whatever the handle's grid layout,
+ *                     every channel below 4 GiB
+ *   field_mol_stride: in elements: 0 = one (C, D, D, D) field shared by all molecules, C * D^3 = a (B, C, D, D, D) field per
+ *                     molecule; anything else is MVX_ERR_INVALID
+ *   scores:           (B,) double, never NULL with B > 0; a molecule without atoms scores exactly 0
+ *   atom_scores:      (sumN,) double or NULL; an atom with no admitted voxel gets an exact zero
+ *   grad_coords:      (sumN, 3) double or NULL; grad_features: (sumN, C) mvx_real or NULL (features mode only)
+ * All three optional outputs may be NULL: scores only. grad_coords / grad_features are the bits mvx_backward_batch writes for
+ * grad_out = the field laid out per molecule (each molecule's rows are dS_b/d(.)); binary density gives zero coordinate
+ * gradients but non-zero scores and feature gradients. s_n is accumulated in float64 from the float32 products F w rho of the
+ * coordinate path (float64 grids: double products), one fixed butterfly per atom; a molecule's score is the sum of its s_n in
+ * a fixed order (one workgroup per molecule: each wave takes chunks of 64 atoms in order, a butterfly per wave, the waves in
+ * order). No atomics: a molecule's score and rows are bit for bit the same in any batch, across runs and under either
+ * "grad_order". Outputs are fully overwritten. Without atom_scores the per-atom scores live in handle-owned workspace of 8
+ * bytes per atom. Device pointers except offsets / xforms (host; MVX_XF_CENTER_PTR and MVX_XF_POSE_PTR records included), as
+ * in mvx_backward_batch, whose staging and buffers this entry shares: it never touches a forward workspace set. Asynchronous
+ * on `stream`. MVX_ERR_INVALID before any device is touched for what mvx_backward_batch rejects (except that grad_coords and
+ * grad_features may both be NULL), a NULL scores with B > 0, a NULL field with atoms present and a bad field_mol_stride.
+ */
+int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                    double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                    int32_t B, int32_t C, const void *field, int64_t field_mol_stride,
+                    double *scores, double *atom_scores, double *grad_coords, mvx_real *grad_features, void *stream);
+
+/*
  * Gradients with respect to explicit rigid poses (MVX_XF_POSE_PTR records; no counterpart in the reference): the reduction of
  * the per-atom gradients a backward entry wrote for the same call (grad_coords = M^T dL/dp) to dL/dc, dL/dq and dL/dt of every
  * molecule, on the device. Per molecule with pose (c, q, t), M = M(q) the linear part of the sandwich product (it scales by

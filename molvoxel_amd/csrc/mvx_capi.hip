@@ -101,6 +101,7 @@ struct mvx_handle {
     DevBuf grad_rec, grad_xp, grad_meta, grad_aux, grad_sort;
     DevBuf pose_meta;  // mvx_pose_grad_batch: the call's offsets and records
     DevBuf grad_rpart; // radius gradients: per-atom / per-(channel, atom) partials of channel-wise radii and their stage sums
+    DevBuf score_atoms; // mvx_score_batch without atom_scores: the per-atom scores its reduction reads, 8 bytes per atom
     // "grad_order" option: 0 atoms in the caller's order (the default), 1 in spatial order, XCD by XCD. The spatial order cuts
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
     // more than it saves (profiles/r05_grad.txt)
@@ -781,7 +782,7 @@ int mvx_destroy(mvx_handle *h) {
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
     std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage,
-                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart, &h->pose_meta,
+                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart, &h->pose_meta, &h->score_atoms,
                                   &h->view_xf, &h->view_counts, &h->view_base, &h->view_off, &h->view_aux, &h->view_index,
                                   &h->view_coords, &h->view_chan, &h->view_radii};
     for (Workspace &w : h->ws) {
@@ -1117,13 +1118,21 @@ int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const v
 }
 
 // mvx_backward_batch (BWD_PLAIN), mvx_backward_radii_batch (BWD_RADII: grad_radii as well) and mvx_backward_density_batch
-// (BWD_DENSITY: grad_sigma / grad_rscalar / grad_radii, each or NULL)
-enum BackwardKind { BWD_PLAIN, BWD_RADII, BWD_DENSITY };
+// (BWD_DENSITY: grad_sigma / grad_rscalar / grad_radii, each or NULL); mvx_score_batch (BWD_SCORE: `grad_out` is the constant
+// field, ScoreCall its stride and the score outputs; grad_coords and grad_features each or NULL)
+enum BackwardKind { BWD_PLAIN, BWD_RADII, BWD_DENSITY, BWD_SCORE };
+
+struct ScoreCall {
+    int64_t mol_stride;  // 0 (one field for all molecules) or C * D^3
+    double *scores;      // (B,)
+    double *atom_scores; // (total,) or null: handle-owned workspace
+};
 
 static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                          double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                          int32_t C, const void *grad_out, double *grad_coords, void *grad_features, BackwardKind kind,
-                         double *grad_radii, double *grad_sigma, double *grad_rscalar, void *stream) {
+                         double *grad_radii, double *grad_sigma, double *grad_rscalar, void *stream,
+                         const ScoreCall *score = nullptr) {
     const bool with_radii = kind == BWD_RADII, with_density = kind == BWD_DENSITY;
     // ---- what is checked before any device is touched ----
     if (mode < MODE_FEATURES || mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
@@ -1145,6 +1154,9 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
             return fail(MVX_ERR_INVALID, "radii_type: scalar radii have no radius array for grad_radii (grad_radius_scalar gives dL/dr)");
         if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE)
             return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode");
+    } else if (score) { // (grad_coords, grad_features and atom_scores may all be null: scores alone)
+        if (score->mol_stride < 0) return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
+        if (B > 0 && !score->scores) return fail(MVX_ERR_INVALID, "scores must not be null");
     } else if (!grad_coords && !grad_features) {
         return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
     }
@@ -1160,7 +1172,7 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
     const int64_t total = B > 0 ? offsets[B] : 0;
     // (no atoms: no gradient rows; channel-wise radii still get their C zeros, sigma and a scalar radius their zero)
     const bool radii_by_channel = grad_radii && radii_type == MVX_RADII_CHANNEL;
-    if (total == 0 && !radii_by_channel && !with_density) return MVX_OK;
+    if (total == 0 && !radii_by_channel && !with_density && !(score && B > 0)) return MVX_OK;
     if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
     if (total == 0) {
         DeviceGuard guard(h->device);
@@ -1171,15 +1183,18 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
         if (radii_by_channel) HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)C * sizeof(double), s));
         if (grad_sigma) HIP_TRY(hipMemsetAsync(grad_sigma, 0, sizeof(double), s));
         if (grad_rscalar) HIP_TRY(hipMemsetAsync(grad_rscalar, 0, sizeof(double), s));
+        if (score) HIP_TRY(hipMemsetAsync(score->scores, 0, (size_t)B * sizeof(double), s)); // (no atoms: every molecule scores 0)
         return MVX_OK;
     }
-    if (!coords || !grad_out) return fail(MVX_ERR_INVALID, "coords / grad_out must not be null");
+    if (!coords || !grad_out) return fail(MVX_ERR_INVALID, score ? "coords / field must not be null" : "coords / grad_out must not be null");
     if (mode != MODE_SINGLE && !channels) return fail(MVX_ERR_INVALID, "channels must not be null");
     if (!radii && radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
     const bool f64 = h->cfg.precision == 64, bf16 = h->cfg.grid_type == MVX_GRID_BF16;
     const size_t gsz = bf16 ? 2 : (f64 ? 8 : 4);
     const size_t D = (size_t)h->g.D;
     if (D * D * D * gsz >= ((size_t)1 << 32)) return fail(MVX_ERR_INVALID, "one channel of the grid must stay below 4 GiB");
+    if (score && score->mol_stride != 0 && (uint64_t)score->mol_stride != (uint64_t)C * D * D * D)
+        return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
 
     DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
@@ -1264,6 +1279,18 @@ static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, cons
     const int32_t grid_kind = bf16 ? 1 : (f64 ? 2 : 0);
     if (kind == BWD_PLAIN) {
         HIP_TRY(launch_grad(ga, mode, grid_kind, gauss, chanwise, s));
+    } else if (kind == BWD_SCORE) {
+        // one walk over the field: the per-atom scores (the caller's array, or workspace), dS/dcoords and dS/dfeatures where
+        // asked for; then every molecule's atoms summed in a fixed order
+        ScoreArgs sa;
+        sa.atom_scores = score->atom_scores;
+        sa.mol_stride = score->mol_stride;
+        if (!sa.atom_scores) {
+            if ((rc = ensure(h->score_atoms, (size_t)total * sizeof(double)))) return rc;
+            sa.atom_scores = reinterpret_cast<double *>(h->score_atoms.p);
+        }
+        HIP_TRY(launch_score(ga, sa, mode, grid_kind, gauss, chanwise, s));
+        HIP_TRY(launch_score_reduce(sa.atom_scores, d_offsets, B, score->scores, s));
     } else if (!gauss) { // binary density: zero radius and sigma gradients (the a.e. derivative), the walk for the other outputs only
         if (grad_radii)
             HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)(radii_type == MVX_RADII_CHANNEL ? C : total) * sizeof(double), s));
@@ -1346,6 +1373,15 @@ int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords
                                double *grad_sigma, double *grad_radius_scalar, void *stream) {
     return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
                          grad_features, BWD_DENSITY, grad_radii, grad_sigma, grad_radius_scalar, stream);
+}
+
+int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                    double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B, int32_t C,
+                    const void *field, int64_t field_mol_stride, double *scores, double *atom_scores, double *grad_coords,
+                    void *grad_features, void *stream) {
+    const ScoreCall sc{field_mol_stride, scores, atom_scores};
+    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, field, grad_coords,
+                         grad_features, BWD_SCORE, nullptr, nullptr, nullptr, stream, &sc);
 }
 
 int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_coords, const int64_t *offsets,

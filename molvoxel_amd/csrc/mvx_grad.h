@@ -29,6 +29,12 @@ struct RadiiArgs {
                         // (C, total) channel-major per (channel, atom) (features, channel-wise radii)
 };
 
+// scores against a constant field (mvx_score_batch, score_kernel): GradArgs::g is the field F instead of dL/dgrid
+struct ScoreArgs {
+    double *atom_scores; // (total,) s_n, written by the walk: the caller's array or handle-owned workspace
+    int64_t mol_stride;  // elements between the fields of two molecules: 0 (one field shared by all) or C * D^3
+};
+
 // channel-wise radii for features: rmax[0] = max(radii) (what prep_kernel culls with), per-channel thresholds Tc and
 // coefficients kc (float, or double for f64), from the forward's d2_threshold / gauss_coeff (float64: their *64 forms)
 hipError_t launch_grad_chan(const void *radii, int32_t C, bool f64, bool gauss, float sigma32, double sigma64, void *rmax, double *Tc,
@@ -42,6 +48,13 @@ hipError_t launch_grad(const GradArgs &a, int32_t mode, int32_t grid_kind, bool 
 // The same walk with the radius partials (Gaussian density only: a binary density has zero radius gradients), in one pass
 // with the coordinate and feature gradients, which are grad_kernel's bits.
 hipError_t launch_grad_radii(const GradArgs &a, const RadiiArgs &r, int32_t mode, int32_t grid_kind, bool chanwise, hipStream_t s);
+// The same walk over a constant field F (mvx_score.hip): s_n = sum_v sum_c F[c,v] w[n,c] rho_{n,c}(v) per atom into
+// ScoreArgs::atom_scores, in one pass with the coordinate and feature gradients, which are grad_kernel's bits for G = F laid
+// out per molecule. Binary density walks the box too (it scores, though its coordinate gradients are zero).
+hipError_t launch_score(const GradArgs &a, const ScoreArgs &sa, int32_t mode, int32_t grid_kind, bool gauss, bool chanwise,
+                        hipStream_t s);
+// scores[b] = sum of atom_scores over molecule b in a fixed order (one workgroup per molecule, no atomics); 0 without atoms
+hipError_t launch_score_reduce(const double *atom_scores, const int64_t *offsets, int32_t B, double *scores, hipStream_t s);
 // Channel-wise radii: dL/dr_c from RadiiArgs::part in a fixed order (no atomics). types: the atoms' (total,) partials of type c,
 // scaled by -1/r_c; else the (C, total) partials, scaled by -(kfac_c / r_c) with kc from launch_grad_chan. `stage` holds
 // grad_radii_stage_doubles(total, C) doubles.

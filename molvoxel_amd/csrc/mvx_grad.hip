@@ -28,6 +28,8 @@ template <typename GT, int MODE, bool GAUSS, bool CHANWISE>
 __global__ void __launch_bounds__(256) grad_kernel(GradArgs A) {
     constexpr bool RADII = false;
     constexpr RadiiArgs RA{}; // (no radius partials: never read)
+    constexpr bool SCORE = false;
+    constexpr ScoreArgs SA{}; // (no scores: never read)
 #include "mvx_grad_body.inc"
 }
 

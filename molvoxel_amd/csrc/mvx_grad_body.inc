@@ -1,7 +1,10 @@
-// mvx_grad_body.inc - the body of the gradient walk, included by grad_kernel (mvx_grad.hip, RADII = false) and by its twin
-// grad_radii_kernel (mvx_grad_radii.hip, RADII = true): one text, two kernels whose names stay apart and whose coordinate and
-// feature gradients are the same bits. Expects the kernel parameters A (GradArgs) and RA (RadiiArgs), the template
-// parameters GT, MODE, GAUSS, CHANWISE and a constexpr bool RADII. With RADII the walk also forms the radius partials
+// mvx_grad_body.inc - the body of the gradient walk, included by grad_kernel (mvx_grad.hip, RADII = false), by its twin
+// grad_radii_kernel (mvx_grad_radii.hip, RADII = true) and by score_kernel (mvx_score.hip, SCORE = true): one text, three
+// kernels whose names stay apart and whose coordinate and feature gradients are the same bits. Expects the kernel parameters
+// A (GradArgs), RA (RadiiArgs) and SA (ScoreArgs), the template parameters GT, MODE, GAUSS, CHANWISE and the constexpr bools
+// RADII and SCORE. With SCORE, A.g is a constant field F (one per molecule, or one for all: SA.mol_stride) and the walk also
+// forms the atom's score s_n = sum_v sum_c F[c,v] w[n,c] rho_{n,c}(v) - e without kfac - in float64 from the float32 products
+// of the coordinate path, for binary density too. With RADII the walk also forms the radius partials
 // (kfac: dk/dr = -2k/r, so d rho / d r = -(kfac / r) d2 rho):
 //   one radius per atom       rp = sum_v e(v) d2(v), e as for the coordinates; dL/dr_n = -rp / r_n, or rp alone into RA.part
 //                             (types mode, radii by type: grad_radii_reduce sums it per type and scales by -1/r_c)
@@ -37,6 +40,7 @@
     const int D = A.D;
     const size_t D3 = (size_t)D * D * D;
     const GT *gm = static_cast<const GT *>(A.g) + (size_t)bm * A.C * D3; // this molecule's G
+    if constexpr (SCORE) gm = static_cast<const GT *>(A.g) + (size_t)bm * (size_t)SA.mol_stride; // (stride 0: the one field)
 
     auto voxel = [&](int v, double &dx, double &dy, double &dz, size_t &off) {
         const int iz = v % nz, t = v / nz, iy = t % ny, ix = t / ny;
@@ -55,10 +59,11 @@
 
     double cp0 = 0.0, cp1 = 0.0, cp2 = 0.0; // this lane's coordinate partials
     double rp = 0.0;                        // RADII, one radius per atom: this lane's sum of e d2
+    double sp = 0.0;                        // SCORE: this lane's share of s_n
     if constexpr (!FEAT) {
         const int ch = MODE == MODE_TYPES ? R.type : 0; // (an atom of type >= C has no admitted box)
         const GT *gc = gm + (size_t)(ch < A.C ? ch : 0) * D3;
-        if (GAUSS) {
+        if (GAUSS || SCORE) { // (binary density has no coordinate gradient, but it scores)
             for (int v0 = 0; v0 < nbox; v0 += 64) {
                 const int v = v0 + lane;
                 double dx, dy, dz;
@@ -67,11 +72,14 @@
                 const double d2 = (dx * dx + dy * dy) + dz * dz; // cdist order, no fma
                 const real rho = density(d2, T, k32, c64, v < nbox);
                 if (rho != (real)0) { // (binary density: no coordinate gradient, nothing to read)
-                    const double e = (double)(load_grad(gc + off) * rho) * kfac;
-                    cp0 += e * dx;
-                    cp1 += e * dy;
-                    cp2 += e * dz;
-                    if constexpr (RADII) rp += e * d2;
+                    if constexpr (GAUSS) {
+                        const double e = (double)(load_grad(gc + off) * rho) * kfac;
+                        cp0 += e * dx;
+                        cp1 += e * dy;
+                        cp2 += e * dz;
+                        if constexpr (RADII) rp += e * d2;
+                    }
+                    if constexpr (SCORE) sp += (double)(load_grad(gc + off) * rho);
                 }
             }
         }
@@ -117,6 +125,7 @@
                             cp2 += e * dz;
                             if constexpr (RADII) rp += e * d2;
                         }
+                        if constexpr (SCORE) sp += (double)(s * rho);
                     }
                 } else { // per channel: its own threshold and coefficient, the box of the largest radius
                     const real *kcr = static_cast<const real *>(A.kc);
@@ -132,6 +141,7 @@
                                     const real gv = gload(c);
                                     acc[c] = fma(gv, rho, acc[c]);
                                     if constexpr (GAUSS) e += (double)(gv * wrow[ch] * rho) * (F64 ? 2.0 : 2.0 * LN2) * (double)kv;
+                                    if constexpr (SCORE) sp += (double)(gv * wrow[ch] * rho);
                                 }
                             }
                         }
@@ -199,4 +209,8 @@
                 RA.grad_radii[a] = S != 0.0 ? -S / r : 0.0;                      // dL/dr = -(1/r) sum_v e d2
             }
         }
+    }
+    if constexpr (SCORE) { // s_n: one fixed butterfly, an atom without admitted voxels gets an exact zero
+        const double S = wave_sum(sp);
+        if (lane == 0) SA.atom_scores[a] = S;
     }

@@ -18,6 +18,8 @@ namespace mvx {
 template <typename GT, int MODE, bool GAUSS, bool CHANWISE>
 __global__ void __launch_bounds__(256) grad_radii_kernel(GradArgs A, RadiiArgs RA) {
     constexpr bool RADII = true;
+    constexpr bool SCORE = false;
+    constexpr ScoreArgs SA{}; // (no scores: never read)
 #include "mvx_grad_body.inc"
 }
 

@@ -94,6 +94,7 @@ SIGNATURES = {
     "mvx_backward_radii_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mvx_backward_density_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp]),
+    "mvx_score_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "mvx_pose_grad_batch": (C.c_int, [Handle, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "mvx_transform_coords": (C.c_int, [Handle, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "mvx_set_profiling": (C.c_int, [Handle, _i32]),

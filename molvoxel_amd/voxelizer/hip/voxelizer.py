@@ -963,6 +963,122 @@ class Voxelizer(BaseVoxelizer):
         return self._select_views(coords, centers, channels, radii, xforms=(self._pose_xforms(pose, B), None))
 
     # ------------------------------------------------------------------------------------------
+    # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
+    def score_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, random_translation=0.0,
+                    random_rotation=False, per_atom=False):
+        """S_b = sum(field * grid_b) for the B grids forward_batch would write with the same arguments - without writing them.
+        The score is linear in the grid, so one walk of the atoms' boxes over the one field gives every molecule's score, the
+        per-atom contributions and, on a differentiable voxelizer, dS/dcoords and dS/dfeatures (mvx_score_batch).
+
+        field: (C,D,H,W), shared by all molecules, or (B,C,D,H,W), one per molecule; converted with
+        `.to(device, grid_dtype).contiguous()` and read as NCDHW on a channels-last voxelizer too. A constant: a field that
+        requires grad raises NotImplementedError. The other arguments are forward_batch's (transforms drawn per molecule in
+        the same RNG order); host arrays are moved to the device. Needs output="torch".
+        Returns scores (B,) float64 on this device; with per_atom=True (scores, atom_scores (sumN,) float64) where
+        scores[b] = sum of molecule b's atom_scores. Deterministic: no atomics, a molecule's values do not depend on its batch.
+        On a differentiable voxelizer coords, features and centers that require grad get their gradients from the same walk;
+        backward() only scales the saved rows. Gradients with respect to radii and sigma are not supported here."""
+        return self._score_batch(coords, offsets, centers, channels, radii, field, num_channels, random_translation,
+                                 random_rotation, per_atom)
+
+    def score_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, field, num_channels=None,
+                          per_atom=False):
+        """score_batch with one explicit rigid pose per molecule (forward_posed_batch's arguments and records): the scores of
+        B poses against `field`. On a differentiable voxelizer `centers`, `quaternions` and `translations` that require grad get
+        dS/dc, dS/dq and dS/dt (mvx_pose_grad_batch on the scaled per-atom gradients)."""
+        self._score_guard(field)
+        B = np.asarray(offsets).shape[0] - 1
+        pose = self._pack_pose(B, centers, quaternions, translations, True)
+        return self._score_batch(coords, offsets, None, channels, radii, field, num_channels, per_atom=per_atom,
+                                 xforms=(self._pose_xforms(pose, B), None), pose=pose)
+
+    def _score_guard(self, field):
+        """What a score call refuses before it looks at anything else."""
+        if self.output != "torch":
+            raise ValueError("score_batch / score_posed_batch need output='torch': the scores are tensors on the voxelizer's device")
+        if _is_torch(field) and field.requires_grad:
+            raise NotImplementedError("gradients with respect to the field are not supported: dS/dfield is the grid itself - "
+                                      "use forward_batch (forward_posed_batch) and (grid * field).sum() for them")
+
+    def _score_no_density_grads(self, radii, rten):
+        """Radius and sigma gradients of the score are out of scope: a radii, sigma or scalar-radius tensor that requires grad."""
+        if not self.differentiable or not torch.is_grad_enabled():
+            return
+        for what, x in (("radii", radii), ("sigma", self.sigma_tensor), ("a scalar radius", rten)):
+            if _is_torch(x) and x.requires_grad:
+                raise NotImplementedError(f"score calls give no gradient with respect to {what}: detach it, or use forward_batch "
+                                          "and (grid * field).sum() for that gradient")
+
+    def _check_args_score(self, field, B, C_):
+        shape = tuple(getattr(field, "shape", ()))
+        one = self.grid_dimension(C_)
+        assert shape in (one, (B,) + one), f"field does not match dimension: {shape} vs {one} or {(B,) + one}"
+        return len(shape) == 5
+
+    def _score_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, random_translation=0.0,
+                     random_rotation=False, per_atom=False, xforms=None, pose=None):
+        """score_batch's body, in the order of _forward_batch. xforms / pose: the posed form's records and packed poses."""
+        self._score_guard(field)
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, rten = self._scalar_radius(radii)
+        self._score_no_density_grads(radii, rten)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        B = offsets.shape[0] - 1
+        assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
+        if channels is None:
+            kind, C_ = None, 1
+        elif channels.ndim == 1:
+            kind = "types"
+            C_ = num_channels if num_channels is not None else (
+                radii.shape[0] if self.is_radii_type_channel_wise else int(channels.max()) + 1)
+        else:
+            kind, C_ = "features", channels.shape[1]
+        C_ = int(C_)
+        self._check_args_batch(coords, channels, kind, radii, C_)
+        per_mol = self._check_args_score(field, B, C_)
+        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, None, None)
+        if grad and centers is not None:
+            centers = self._grad_center(centers)
+        if not self._on_device(coords):  # this entry takes device arrays only
+            coords = (coords.detach() if _is_torch(coords) else torch.as_tensor(np.asarray(coords, dtype=np.float64))).to(self.device)
+        c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
+        if kind == "types" and self.is_radii_type_channel_wise and r.shape[0] < C_:
+            r = torch.cat([r, r.new_ones(C_ - r.shape[0])])  # (as forward_batch: radii are indexed by type only)
+        if xforms is not None:
+            xfs, dev_cen = xforms
+            need_xf = True
+        else:
+            need_xf = centers is not None or random_rotation or (random_translation and random_translation > 0.0)
+            xfs, dev_cen = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep) if need_xf else (None, None)
+        F = (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
+        rs = float(radii) if _np_isscalar(radii) else 0.0
+        N = c.shape[0]
+        mode = kind or "single"
+        feat = ch if kind == "features" else None
+        need_gf = grad and feat is not None and feat.requires_grad
+
+        def call():
+            scores = torch.empty(B, dtype=torch.float64, device=self.device)
+            atoms = torch.empty(N, dtype=torch.float64, device=self.device) if per_atom else None
+            gc = torch.empty((N, 3), dtype=torch.float64, device=self.device) if grad else None
+            gf = torch.empty((N, C_), dtype=self._tfp, device=self.device) if need_gf else None
+            _lib.check(self._lib.mvx_score_batch(
+                self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
+                offsets.ctypes.data, C.addressof(xfs) if need_xf else None, B, C_, self._ptr(F),
+                C_ * self.dimension ** 3 if per_mol else 0, self._ptr(scores), self._ptr(atoms), self._ptr(gc), self._ptr(gf),
+                self._stream()))
+            return scores, atoms, gc, gf
+
+        if not grad:
+            scores, atoms, _, _ = call()
+            return (scores, atoms) if per_atom else scores
+        spec = dict(offsets=offsets, xforms=xfs if need_xf else None, B=B)
+        cen = dev_cen if (_is_torch(dev_cen) and self._on_device(dev_cen)) else None
+        out = _ScoreFunction.apply(self, call, spec, per_atom, c, feat, cen, pose)
+        return out if per_atom else out[0]
+
+    # ------------------------------------------------------------------------------------------
     # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
     def _grad_wanted(self, coords, features, center, radii, out_grid, rten=None) -> bool:
         """True when this call must record an autograd graph: differentiable voxelizer, grad mode on, and coords / features /
@@ -1125,6 +1241,44 @@ if torch is not None:
             # explicit poses: the per-atom gradients reduced to dL/dc, dL/dq, dL/dt per molecule (autograd splits the block)
             gpose = ctx.vox._pose_backward(ctx.spec, c, gc) if need_pose else None
             return None, None, None, None, gc if need_c else None, gf, gcen, gr, gsig, grs, gpose
+
+
+    class _ScoreFunction(torch.autograd.Function):
+        """scores (and atom_scores) = score(coords, features, center, packed poses): the one walk of mvx_score_batch also writes
+        dS/dcoords and dS/dfeatures, which are saved; backward scales each atom's rows by its upstream (dL/dS of its molecule plus,
+        with per_atom, dL/ds_n) and reduces centres and poses as _VoxelizeFunction does. No second walk."""
+
+        @staticmethod
+        def forward(ctx, vox, call, spec, per_atom, c, f, cen, pose):
+            scores, atoms, gc, gf = call()
+            ctx.vox, ctx.spec = vox, spec
+            ctx.save_for_backward(c, cen, pose, gc, gf)
+            if per_atom:
+                return scores, atoms
+            return (scores,)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, gs, ga=None):
+            c, cen, pose, gc, gf = ctx.saved_tensors
+            need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[4:8]
+            N = gc.shape[0]
+            lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
+            up = torch.zeros(N, dtype=torch.float64, device=gc.device)  # dL/ds_n
+            if gs is not None:
+                up = torch.repeat_interleave(gs.to(torch.float64), lengths, output_size=N)
+            if ga is not None:
+                up = up + ga.to(torch.float64)
+            gcs = gc * up[:, None]
+            gfs = (gf * up[:, None].to(gf.dtype)) if (need_f and gf is not None) else None
+            gcen = None
+            if need_cen:
+                if cen.numel() == 3:
+                    gcen = -gcs.sum(0).reshape(cen.shape)
+                else:
+                    gcen = -torch.segment_reduce(gcs, "sum", lengths=lengths, axis=0).reshape(cen.shape)
+            gpose = ctx.vox._pose_backward(ctx.spec, c, gcs) if need_pose else None
+            return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose
 
 
 def transform_on_device(coords, center, translation, quaternion):
