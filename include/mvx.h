@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVX_VERSION 140 /* 0.1.4: MVX_XF_POSE_PTR, MVX_XF_TRANSLATE_ONCE and mvx_pose_grad_batch (additive: explicit rigid poses and their gradients); mvx_select_views and mvx_forward_views (additive: many views of one shared cloud); mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
+#define MVX_VERSION 140 /* 0.1.4: mvx_score_views and mvx_views_reduce (additive: scores of many views of one shared cloud and the reduction of their rows onto its atoms); MVX_XF_POSE_PTR, MVX_XF_TRANSLATE_ONCE and mvx_pose_grad_batch (additive: explicit rigid poses and their gradients); mvx_select_views and mvx_forward_views (additive: many views of one shared cloud); mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
 
 typedef enum mvx_status {
     MVX_OK = 0,
@@ -389,6 +389,51 @@ int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const voi
  */
 int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_coords, const int64_t *offsets,
                         const mvx_xform *xforms, int32_t B, double *grad_pose, void *stream);
+
+/*
+ * Scores of B views of ONE shared cloud against a constant field, without the grids and without B copies of the cloud (no
+ * counterpart in the reference): mvx_score_batch on the compact batch mvx_forward_views voxelizes. The cloud, `mode`, radii
+ * and the B host records are those of mvx_forward_views; every array is a device array (centre and pose pointers point into
+ * device memory). field, field_view_stride (0 = one (C, D, D, D) field for all views, C * D^3 = one per view) and the outputs
+ * follow mvx_score_batch. The selected rows are gathered into handle-owned buffers (mvx_forward_views' gather) and walked once.
+ *   index == NULL:  the entry selects the views' atoms itself (ONE stream synchronisation, as mvx_forward_views) and ignores
+ *                   offsets_host. Only `scores` may be asked for: the caller cannot know the length of the per-row outputs,
+ *                   so atom_scores, grad_coords and grad_features must be NULL.
+ *   index != NULL:  index (device) and offsets_host (B + 1 entries, host) are a selection mvx_select_views returned for the same
+ *                   cloud, radii and records; the entry does not synchronise. With total = offsets_host[B]: atom_scores (total,)
+ *                   double, grad_coords (total, 3) double, grad_features (total, C) mvx_real (features mode), each or NULL, in
+ *                   selection order: row k belongs to atom index[k] of its view. mvx_views_reduce sums such rows onto the atoms.
+ * scores (B,) double: a view that keeps no atom scores exactly 0. B == 0 writes nothing; N == 0 writes zero scores.
+ * Every value is the bit mvx_score_batch gives for coords[index], the gathered channels and radii, the offsets and the same
+ * records; against the cloud repeated B times the per-atom values of kept atoms are the same bits, and a view's score is the
+ * same bit when the view keeps the whole cloud (elsewhere the fixed-order sum of a view's atoms groups other atoms together: the
+ * scores agree to float64 rounding). Deterministic, asynchronous on `stream` (apart from the selection).
+ * MVX_ERR_INVALID before any device is touched for: what mvx_select_views rejects for the cloud and the records; features mode
+ * without channels; grad_features outside features mode; a negative field_view_stride, or one that is neither 0 nor C * D^3; NULL
+ * scores with B > 0; a NULL field with atoms to score; per-row outputs without an index; an index without offsets_host;
+ * offsets_host[0] != 0, decreasing offsets or offsets_host[B] >= 2^31; a NULL handle.
+ */
+int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                    double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                    const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
+                    double *scores, double *atom_scores, double *grad_coords, mvx_real *grad_features, void *stream);
+
+/*
+ * Rows of a selection summed back onto the shared atoms (the backward step of anything computed per (view, atom) row):
+ *   out[n, j] = sum over the views b whose segment index[offsets[b] .. offsets[b + 1]) holds atom n of rows[slot(b, n), j]
+ * index (device) and offsets_host (B + 1 entries, host) as mvx_select_views returns them: every segment ascending, entries in
+ * [0, N). rows: (offsets_host[B], width) device array of `row_type` elements (enum mvx_row_type); out: (N, width) of the same
+ * type, fully overwritten - an atom no view holds gets an exact-zero row. The sums are accumulated in double and rounded once
+ * when the rows are float. No atomics: per atom and column, each lane of a wave adds its views in ascending order (wave w of
+ * four takes the views 64 (w + 4 k) + lane), a fixed butterfly per wave, the four waves in a fixed order - the order of the
+ * additions depends on (B, N, index, offsets) alone, never on the machine, the launch or the run. Workspace: the B + 1 offsets.
+ * Asynchronous on `stream`. MVX_ERR_INVALID before any device is touched for: B < 0 or N < 0; width <= 0; a bad row_type; NULL
+ * offsets_host with B > 0, offsets_host[0] != 0, decreasing offsets or offsets_host[B] >= 2^31; NULL index or rows with rows
+ * present; NULL out with N > 0; a NULL handle.
+ */
+enum mvx_row_type { MVX_ROW_FLOAT = 0, MVX_ROW_DOUBLE = 1 };
+int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets_host, int32_t B, int64_t N, const void *rows,
+                     int32_t width, int32_t row_type, void *out, void *stream);
 
 /*
  * Replaces do_transform on an (N,3) fp64 point cloud (numpy/transform.py:44-60): out = transformed coords.

@@ -109,6 +109,7 @@ struct mvx_handle {
     // views of a shared cloud (mvx_select_views / mvx_forward_views): the views' transforms, per-(view, tile) counts and bases,
     // offsets, max channel radius, and - mvx_forward_views - the selected indices and the gathered rows handed to run()
     DevBuf view_xf, view_counts, view_base, view_off, view_aux, view_index, view_coords, view_chan, view_radii;
+    DevBuf view_red_off; // mvx_views_reduce: the call's offsets
     int32_t layout = MVX_LAYOUT_NCDHW; // mvx_set_grid_layout
     mvx_plan last_plan{}; // the plan of the last forward call, debug options applied (mvx_debug_last_plan)
     bool has_plan = false;
@@ -784,7 +785,7 @@ int mvx_destroy(mvx_handle *h) {
     std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage,
                                   &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart, &h->pose_meta, &h->score_atoms,
                                   &h->view_xf, &h->view_counts, &h->view_base, &h->view_off, &h->view_aux, &h->view_index,
-                                  &h->view_coords, &h->view_chan, &h->view_radii};
+                                  &h->view_coords, &h->view_chan, &h->view_radii, &h->view_red_off};
     for (Workspace &w : h->ws) {
         for (DevBuf *b : {&w.rec, &w.wbuf, &w.xp, &w.xlist, &w.slist, &w.meta, &w.aux}) bufs.push_back(b);
         if (w.ev_pre) (void)hipEventDestroy(w.ev_pre);
@@ -1034,6 +1035,47 @@ inline int gather_width(size_t row_bytes, const void *a, const void *b) {
     return (bits & 15u) == 0 ? 16 : ((bits & 7u) == 0 ? 8 : 4);
 }
 
+// The compact batch of a selection: the rows `index` names, gathered by one launch into the handle's view_* buffers -
+// coordinates, feature rows or types, atom-wise radii (other radii stay where they are).
+struct ViewBatch {
+    const double *coords = nullptr;
+    const void *channels = nullptr;
+    const void *radii = nullptr;
+};
+
+int gather_views(mvx_handle *h, int mode, int C, int radii_type, const double *coords, const void *channels, const void *radii,
+                 const int64_t *index, int64_t total, hipStream_t s, ViewBatch &vb) {
+    const size_t esz = h->cfg.precision == 64 ? sizeof(double) : sizeof(float);
+    GatherArgs g{};
+    g.index = index;
+    g.total = total;
+    auto add = [&](DevBuf &dst, const void *src, size_t row_bytes) -> int {
+        if (int e = ensure(dst, (size_t)total * row_bytes)) return e;
+        const int i = g.narr++;
+        g.src[i] = static_cast<const char *>(src);
+        g.dst[i] = static_cast<char *>(dst.p);
+        g.row_bytes[i] = (int32_t)row_bytes;
+        g.width[i] = gather_width(row_bytes, src, dst.p);
+        return MVX_OK;
+    };
+    int rc;
+    if ((rc = add(h->view_coords, coords, 3 * sizeof(double)))) return rc;
+    vb.coords = static_cast<const double *>(h->view_coords.p);
+    vb.channels = channels;
+    if (mode != MODE_SINGLE) {
+        if ((size_t)C * esz > (size_t)1 << 30) return fail(MVX_ERR_INVALID, "too many channels");
+        if ((rc = add(h->view_chan, channels, mode == MODE_FEATURES ? (size_t)C * esz : sizeof(int32_t)))) return rc;
+        vb.channels = h->view_chan.p;
+    }
+    vb.radii = radii; // (scalar: unused; channel-wise: the C radii as they are)
+    if (radii_type == MVX_RADII_ATOM) {
+        if ((rc = add(h->view_radii, radii, esz))) return rc;
+        vb.radii = h->view_radii.p;
+    }
+    HIP_TRY(launch_view_gather(g, s));
+    return MVX_OK;
+}
+
 } // namespace
 
 int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types, const void *radii, double radius_scalar,
@@ -1078,33 +1120,13 @@ int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const v
         if ((rc = select_views(h, v, in, nullptr, 0, true, offsets.data()))) return rc;
         const int64_t total = offsets[B];
         if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
-        // one gather launch: coordinates, feature rows or types, atom-wise radii
-        const size_t esz = h->cfg.precision == 64 ? sizeof(double) : sizeof(float);
-        GatherArgs g{};
-        g.index = static_cast<const int64_t *>(h->view_index.p);
-        g.total = total;
-        auto add = [&](DevBuf &dst, const void *src, size_t row_bytes) -> int {
-            if (int e = ensure(dst, (size_t)total * row_bytes)) return e;
-            const int i = g.narr++;
-            g.src[i] = static_cast<const char *>(src);
-            g.dst[i] = static_cast<char *>(dst.p);
-            g.row_bytes[i] = (int32_t)row_bytes;
-            g.width[i] = gather_width(row_bytes, src, dst.p);
-            return MVX_OK;
-        };
-        if ((rc = add(h->view_coords, in.coords, 3 * sizeof(double)))) return rc;
-        r.coords = static_cast<const double *>(h->view_coords.p);
-        if (mode != MODE_SINGLE) {
-            if ((size_t)C * esz > (size_t)1 << 30) return fail(MVX_ERR_INVALID, "too many channels");
-            if ((rc = add(h->view_chan, in.channels, mode == MODE_FEATURES ? (size_t)C * esz : sizeof(int32_t)))) return rc;
-            r.channels = h->view_chan.p;
-        }
-        r.radii = in.radii; // (scalar: unused; channel-wise: the C radii as they are)
-        if (radii_type == MVX_RADII_ATOM) {
-            if ((rc = add(h->view_radii, in.radii, esz))) return rc;
-            r.radii = h->view_radii.p;
-        }
-        HIP_TRY(launch_view_gather(g, s));
+        ViewBatch vb;
+        if ((rc = gather_views(h, mode, C, radii_type, in.coords, in.channels, in.radii, static_cast<const int64_t *>(h->view_index.p),
+                               total, s, vb)))
+            return rc;
+        r.coords = vb.coords;
+        r.channels = vb.channels;
+        r.radii = vb.radii;
     }
     r.xforms = in.xforms_host.data();
     r.in_kind = MVX_DEVICE;
@@ -1419,6 +1441,104 @@ int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_
     HIP_TRY(hipMemcpyAsync(h->pose_meta.p, slot->p, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
     HIP_TRY(launch_pose_grad(coords, grad_coords, reinterpret_cast<const int64_t *>(h->pose_meta.p),
                              reinterpret_cast<const mvx_xform *>((char *)h->pose_meta.p + off_bytes), B, grad_pose, s));
+    HIP_TRY(hipEventRecord(slot->done, s));
+    slot->in_flight = true;
+    return MVX_OK;
+}
+
+// what is wrong with the offsets of a selection handed back by the caller (B + 1 entries), or null
+static const char *bad_view_offsets(const int64_t *offsets, int32_t B) {
+    if (!offsets) return "offsets_host must not be null with an index";
+    if (offsets[0] != 0) return "offsets[0] must be 0";
+    for (int b = 0; b < B; ++b)
+        if (offsets[b + 1] < offsets[b]) return "offsets must be non-decreasing";
+    if (offsets[B] >= (int64_t)1 << 31) return "too many atoms: offsets[B] must stay below 2^31";
+    return nullptr;
+}
+
+int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                    double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                    const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
+                    double *scores, double *atom_scores, double *grad_coords, void *grad_features, void *stream) {
+    ViewCall v{mode, coords, channels, radii, radius_scalar, radii_type, N, C, xforms, B, MVX_DEVICE, reinterpret_cast<hipStream_t>(stream)};
+    // ---- what is checked before any device is touched ----
+    const bool per_row = atom_scores || grad_coords || grad_features;
+    const char *own = nullptr;
+    if (grad_features && mode != MODE_FEATURES) own = "grad_features exists in features mode only";
+    else if (field_view_stride < 0) own = "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)";
+    else if (B > 0 && !scores) own = "scores must not be null";
+    else if (!index && per_row)
+        own = "atom_scores, grad_coords and grad_features need an index: their rows are laid out in selection order (mvx_select_views)";
+    else if (index && B > 0) own = bad_view_offsets(offsets_host, B);
+    if (!own && B > 0 && N > 0) {
+        if (mode == MODE_FEATURES && !channels) own = "channels must not be null";
+        else if (!field && (!index || offsets_host[B] > 0)) own = "field must not be null";
+    }
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (field_view_stride != 0 && (uint64_t)field_view_stride != (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D)
+        return fail(MVX_ERR_INVALID, "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)");
+    if (B == 0) return MVX_OK;
+    const ScoreCall sc{field_view_stride, scores, atom_scores};
+    std::vector<int64_t> own_offsets;
+    const int64_t *offsets = offsets_host;
+    ViewBatch vb;
+    if (N == 0 || !index) { // (N == 0: B views without atoms score 0, whatever the caller's selection says)
+        own_offsets.assign((size_t)B + 1, 0);
+        offsets = own_offsets.data();
+    }
+    if (N > 0) {
+        DeviceGuard guard(h->device);
+        if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+        hipStream_t s = v.stream;
+        int rc;
+        if ((rc = adopt_stream(h, s))) return rc;
+        if (!index) { // the selection itself: one stream synchronisation
+            ViewInputs in;
+            if ((rc = stage_views(h, v, true, in))) return rc;
+            if ((rc = select_views(h, v, in, nullptr, 0, true, own_offsets.data()))) return rc;
+            if (own_offsets[B] >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+            index = static_cast<const int64_t *>(h->view_index.p);
+        }
+        if ((rc = gather_views(h, mode, C, radii_type, coords, channels, radii, index, offsets[B], s, vb))) return rc;
+    }
+    // the compact batch through the walk of mvx_score_batch: the records as the caller gave them (device centres and poses)
+    return backward_impl(h, mode, vb.coords, vb.channels, vb.radii, radius_scalar, radii_type, offsets, xforms, B, C, field,
+                         grad_coords, grad_features, BWD_SCORE, nullptr, nullptr, nullptr, stream, &sc);
+}
+
+int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets_host, int32_t B, int64_t N, const void *rows,
+                     int32_t width, int32_t row_type, void *out, void *stream) {
+    // ---- what is checked before any device is touched ----
+    if (B < 0 || N < 0) return fail(MVX_ERR_INVALID, "B and N must be >= 0");
+    if (width <= 0 || width > VIEW_REDUCE_MAX_WIDTH) return fail(MVX_ERR_INVALID, "width must be > 0 (and at most 65535 * 32)");
+    if (row_type != MVX_ROW_FLOAT && row_type != MVX_ROW_DOUBLE) return fail(MVX_ERR_INVALID, "bad row_type");
+    if (N >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (B > 0)
+        if (const char *bad = bad_view_offsets(offsets_host, B)) return fail(MVX_ERR_INVALID, bad);
+    const int64_t total = B > 0 ? offsets_host[B] : 0;
+    if (total > 0 && (!index || !rows)) return fail(MVX_ERR_INVALID, "index / rows must not be null");
+    if (N > 0 && !out) return fail(MVX_ERR_INVALID, "out must not be null");
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (N == 0) return MVX_OK;
+
+    DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    int rc = adopt_stream(h, s);
+    if (rc) return rc;
+    const bool f64 = row_type == MVX_ROW_DOUBLE;
+    if (total == 0) { // no view holds an atom: exact zeros
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)N * (size_t)width * (f64 ? sizeof(double) : sizeof(float)), s));
+        return MVX_OK;
+    }
+    // the offsets through a pinned slot, as the backward entries stage theirs
+    const size_t off_bytes = (size_t)(B + 1) * sizeof(int64_t);
+    PinnedSlot *slot = nullptr;
+    if ((rc = acquire_slot(h, off_bytes, &slot))) return rc;
+    if ((rc = ensure(h->view_red_off, off_bytes))) return rc;
+    std::memcpy(slot->p, offsets_host, off_bytes);
+    HIP_TRY(hipMemcpyAsync(h->view_red_off.p, slot->p, off_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_view_reduce(index, static_cast<const int64_t *>(h->view_red_off.p), B, N, rows, width, f64, out, s));
     HIP_TRY(hipEventRecord(slot->done, s));
     slot->in_flight = true;
     return MVX_OK;

@@ -1,5 +1,5 @@
-// mvx_views.h - many views of one shared point cloud (mvx_select_views / mvx_forward_views): what mvx_views.hip launches for
-// the C-ABI TU (mvx_capi.hip).
+// mvx_views.h - many views of one shared point cloud (mvx_select_views / mvx_forward_views / mvx_score_views /
+// mvx_views_reduce): what mvx_views.hip and mvx_views_reduce.hip launch for the C-ABI TU (mvx_capi.hip).
 #pragma once
 #include "mvx_internal.h"
 
@@ -36,5 +36,11 @@ hipError_t launch_view_scan(const int32_t *counts, int32_t B, int32_t ntiles, in
 // index[offsets[b] ..] = the passing atoms of view b in ascending order
 hipError_t launch_view_fill(const ViewArgs &a, const int64_t *tile_base, int64_t *index, hipStream_t s);
 hipError_t launch_view_gather(const GatherArgs &g, hipStream_t s);
+
+// mvx_views_reduce.hip: out[n, :] = the sum of rows[slot, :] over the views whose segment of `index` holds atom n (rows and out
+// float, or double with rows_f64; `width` columns, at most VIEW_REDUCE_MAX_WIDTH); every row of out is written
+constexpr int32_t VIEW_REDUCE_MAX_WIDTH = 65535 * 32;
+hipError_t launch_view_reduce(const int64_t *index, const int64_t *offsets, int32_t B, int64_t N, const void *rows, int32_t width,
+                              bool rows_f64, void *out, hipStream_t s);
 
 } // namespace mvx

@@ -19,6 +19,7 @@ MVX_GRID_REAL, MVX_GRID_BF16 = 0, 1
 MVX_LAYOUT_NCDHW, MVX_LAYOUT_NDHWC = 0, 1
 MVX_XF_CENTER, MVX_XF_ROTATE, MVX_XF_TRANSLATE, MVX_XF_RECENTER, MVX_XF_CENTER_PTR = 1, 2, 4, 8, 16
 MVX_XF_POSE_PTR, MVX_XF_TRANSLATE_ONCE = 32, 64
+MVX_ROW_FLOAT, MVX_ROW_DOUBLE = 0, 1
 
 
 class MvxConfig(C.Structure):
@@ -95,7 +96,10 @@ SIGNATURES = {
     "mvx_backward_density_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp]),
     "mvx_score_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "mvx_pose_grad_batch": (C.c_int, [Handle, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "mvx_score_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                  _vp, _vp]),
+    "mvx_views_reduce": (C.c_int, [Handle, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp]),
+    "mvx_pose_grad_batch":(C.c_int, [Handle, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "mvx_transform_coords": (C.c_int, [Handle, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),
     "mvx_set_profiling": (C.c_int, [Handle, _i32]),
     "mvx_profile_read": (C.c_int, [Handle, C.POINTER(C.c_float), _i32, C.POINTER(_i32)]),

@@ -1079,6 +1079,115 @@ class Voxelizer(BaseVoxelizer):
         return out if per_atom else out[0]
 
     # ------------------------------------------------------------------------------------------
+    # SCORES OF VIEWS (many poses or boxes of one shared cloud against a field: mvx_score_views / mvx_views_reduce)
+    def score_views(self, coords, centers, channels, radii, field, num_channels=None, random_translation=0.0,
+                    random_rotation=False, per_atom=False):
+        """S_b = sum(field * grid_b) for the B grids forward_views would write with the same arguments - without the grids and
+        without B copies of the cloud: each view's atoms are selected on the device, gathered into a compact batch and walked
+        once over the field (mvx_score_views). The values are score_batch's, bit for bit, on coords[index], the gathered
+        channels and offsets of select_views.
+
+        coords (N,3), centers (B,3), channels and radii as forward_views (transforms drawn per view in its RNG order); field
+        (C,D,H,W), shared by all views, or (B,C,D,H,W), one per view, converted as score_batch converts it; host arrays are
+        moved to the device. Needs output="torch". Returns scores (B,) float64; with per_atom=True (scores, atom_scores, index,
+        offsets): atom_scores (total,) float64 in selection order - atom_scores[k] belongs to atom index[k] of its view - and
+        (index, offsets) as select_views returns them. Without gradients and without per_atom the call is one library call
+        (one stream synchronisation, for the selection). On a differentiable voxelizer coords, features and centers that
+        require grad get their gradients: the per-(view, atom) rows of the one walk are saved, backward() scales them and sums
+        them onto the shared atoms with mvx_views_reduce - deterministic (no atomics, a fixed order of additions), so two runs
+        give the same bits. Gradients with respect to radii, sigma and the field are not supported here."""
+        return self._score_views(coords, centers, channels, radii, field, num_channels, random_translation, random_rotation,
+                                 per_atom)
+
+    def score_posed_views(self, coords, centers, quaternions, translations, channels, radii, field, num_channels=None,
+                          per_atom=False):
+        """score_views with one explicit rigid pose per view (forward_posed_views' arguments and records): the scores of B
+        poses of ONE shared cloud against `field`. On a differentiable voxelizer `centers`, `quaternions` and `translations`
+        that require grad get dS/dc, dS/dq and dS/dt per view (mvx_pose_grad_batch on the scaled rows)."""
+        self._score_guard(field)
+        return self._score_views(coords, centers, channels, radii, field, num_channels, per_atom=per_atom,
+                                 posed=(quaternions, translations))
+
+    def views_reduce(self, rows, index, offsets, num_atoms):
+        """Rows of a selection summed back onto the shared atoms: out[n] = the sum of rows[k] over the slots k with
+        index[k] == n, one slot per view that holds atom n. rows (total,) or (total, W) float32 | float64 on this device,
+        (index, offsets) as select_views returns them; returns (num_atoms,) or (num_atoms, W) of the rows' dtype. Accumulated in
+        float64, rounded once; no atomics and a fixed order of additions (mvx_views_reduce): two runs give the same bits."""
+        assert _is_torch(rows) and self._on_device(rows) and rows.dtype in (torch.float32, torch.float64), (
+            "rows should be a float32 or float64 tensor on this voxelizer's device")
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        total = int(offsets[-1]) if offsets.shape[0] else 0
+        assert rows.ndim in (1, 2) and rows.shape[0] == total, f"rows does not match the selection: {tuple(rows.shape)} vs {(total, 'W')}"
+        assert int(index.shape[0]) == total and index.dtype == torch.int64, "index does not match offsets"
+        flat = rows.ndim == 1
+        W = 1 if flat else int(rows.shape[1])
+        r = rows.reshape(total, W).contiguous()
+        out = torch.empty((int(num_atoms), W), dtype=r.dtype, device=self.device)
+        if W > 0:
+            idx = index if index.is_contiguous() else index.contiguous()
+            _lib.check(self._lib.mvx_views_reduce(
+                self._handle, self._ptr(idx) if total else None, offsets.ctypes.data, offsets.shape[0] - 1, int(num_atoms),
+                self._ptr(r) if total else None, W, _lib.MVX_ROW_DOUBLE if r.dtype == torch.float64 else _lib.MVX_ROW_FLOAT,
+                self._ptr(out) if num_atoms else None, self._stream()))
+        return out.reshape(int(num_atoms)) if flat else out
+
+    def _score_views(self, coords, centers, channels, radii, field, num_channels=None, random_translation=0.0,
+                     random_rotation=False, per_atom=False, posed=None):
+        """score_views' body, in the order of _score_batch. posed: (quaternions, translations) of score_posed_views."""
+        self._score_guard(field)
+        kind, C_, cradii, rten = self._views_args(coords, centers, channels, radii, num_channels)
+        self._score_no_density_grads(cradii, rten)
+        B = int(centers.shape[0])
+        per_view = self._check_args_score(field, B, C_)
+        pose = self._pack_pose(B, centers, posed[0], posed[1], True) if posed is not None else None
+        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, None, None)
+        if not self._on_device(coords):  # this entry takes device arrays only
+            coords = (coords.detach() if _is_torch(coords) else torch.as_tensor(np.asarray(coords, dtype=np.float64))).to(self.device)
+        c, ch, r, in_kind, keep = self._views_inputs(coords, channels, kind, cradii, C_)
+        if pose is None:
+            xfs, dev_cen = self._make_xforms(B, self._grad_center(centers) if grad else centers, in_kind, random_translation,
+                                             random_rotation, keep)
+        else:
+            xfs, dev_cen = self._pose_xforms(pose, B), None
+        F = (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
+        rs = float(cradii) if _np_isscalar(cradii) else 0.0
+        N = int(c.shape[0])
+        mode = kind or "single"
+        feat = ch if kind == "features" else None
+        need_gf = grad and feat is not None and feat.requires_grad
+        stride = C_ * self.dimension ** 3 if per_view else 0
+
+        def call(index, offsets):
+            """One mvx_score_views call: with a selection, the per-row outputs this call needs; without, scores alone."""
+            total = 0 if index is None else int(offsets[-1])
+            scores = torch.empty(B, dtype=torch.float64, device=self.device)
+            atoms = torch.empty(total, dtype=torch.float64, device=self.device) if (per_atom and index is not None) else None
+            gc = torch.empty((total, 3), dtype=torch.float64, device=self.device) if (grad and index is not None) else None
+            gf = torch.empty((total, C_), dtype=self._tfp, device=self.device) if (need_gf and index is not None) else None
+            # (an empty selection: an empty tensor has no address, but a non-null index is what says "selected" to the library)
+            some = index is not None and total > 0
+            pad = torch.empty(1, dtype=torch.int64, device=self.device) if (index is not None and not some) else None
+            _lib.check(self._lib.mvx_score_views(
+                self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(), N, C_,
+                C.addressof(xfs), B, None if index is None else (index if some else pad).data_ptr(),
+                offsets.ctypes.data if index is not None else None, self._ptr(F), stride, self._ptr(scores),
+                self._ptr(atoms) if some else None, self._ptr(gc) if some else None, self._ptr(gf) if some else None,
+                self._stream()))
+            return scores, atoms, gc, gf
+
+        if not grad and not per_atom:
+            return call(None, None)[0]
+        with torch.no_grad():
+            index, offsets = self._select(c, ch if kind == "types" else None, r, rs, kind, C_, xfs, B, in_kind)
+        if not grad:
+            scores, atoms, _, _ = call(index, offsets)
+            return scores, atoms, index, offsets
+        spec = dict(offsets=offsets, xforms=xfs, B=B, N=N, index=index)
+        cen = dev_cen if (_is_torch(dev_cen) and self._on_device(dev_cen)) else None
+        out = _ScoreViewsFunction.apply(self, lambda: call(index, offsets), spec, per_atom, c, feat, cen, pose)
+        return (out[0], out[1], index, offsets) if per_atom else out[0]
+
+    # ------------------------------------------------------------------------------------------
     # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
     def _grad_wanted(self, coords, features, center, radii, out_grid, rten=None) -> bool:
         """True when this call must record an autograd graph: differentiable voxelizer, grad mode on, and coords / features /
@@ -1279,6 +1388,47 @@ if torch is not None:
                     gcen = -torch.segment_reduce(gcs, "sum", lengths=lengths, axis=0).reshape(cen.shape)
             gpose = ctx.vox._pose_backward(ctx.spec, c, gcs) if need_pose else None
             return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose
+
+
+    class _ScoreViewsFunction(torch.autograd.Function):
+        """scores (and atom_scores) of B views of one shared cloud = score(coords, features, centres, packed poses): the one walk of
+        mvx_score_views also writes dS/dcoords and dS/dfeatures per (view, atom) row, which are saved. backward scales each row by
+        its upstream, as _ScoreFunction does, sums the rows onto the shared atoms with mvx_views_reduce (no autograd index
+        backward, no atomics), and reduces centres and poses per view. No second walk."""
+
+        @staticmethod
+        def forward(ctx, vox, call, spec, per_atom, c, f, cen, pose):
+            scores, atoms, gc, gf = call()
+            ctx.vox, ctx.spec = vox, spec
+            ctx.save_for_backward(c, cen, pose, gc, gf, spec["index"])
+            if per_atom:
+                return scores, atoms
+            return (scores,)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, gs, ga=None):
+            c, cen, pose, gc, gf, index = ctx.saved_tensors
+            need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[4:8]
+            vox, spec = ctx.vox, ctx.spec
+            total = gc.shape[0]
+            # (through pinned memory: a pageable copy would synchronise the stream)
+            lengths = torch.from_numpy(np.diff(spec["offsets"])).pin_memory().to(gc.device, non_blocking=True)
+            up = torch.zeros(total, dtype=torch.float64, device=gc.device)  # dL/ds of every (view, atom) row
+            if gs is not None:
+                up = torch.repeat_interleave(gs.to(torch.float64), lengths, output_size=total)
+            if ga is not None:
+                up = up + ga.to(torch.float64)
+            gcs = gc * up[:, None]
+            gcoords = vox.views_reduce(gcs, index, spec["offsets"], spec["N"]) if need_c else None
+            gfeat = None
+            if need_f and gf is not None:
+                gfeat = vox.views_reduce(gf * up[:, None].to(gf.dtype), index, spec["offsets"], spec["N"])
+            gcen = None
+            if need_cen:
+                gcen = -torch.segment_reduce(gcs, "sum", lengths=lengths, axis=0).reshape(cen.shape)
+            gpose = vox._pose_backward(spec, c[index], gcs) if need_pose else None
+            return None, None, None, None, gcoords, gfeat, gcen, gpose
 
 
 def transform_on_device(coords, center, translation, quaternion):
