@@ -40,16 +40,31 @@ int fail_hip(hipError_t e, const char *what) {
         if (_e != hipSuccess) return fail_hip(_e, #expr); \
     } while (0)
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
+
+// Device memory, pinned memory and events are freed by their owners' destructors (mvx_destroy); no owner can be copied.
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
 };
 
-struct PinnedSlot {
+struct DevBuf : NoCopy {
+    void *p = nullptr;
+    size_t cap = 0;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+struct PinnedSlot : NoCopy {
     char *p = nullptr;
     size_t cap = 0;
     hipEvent_t done = nullptr;
     bool in_flight = false;
+    ~PinnedSlot() {
+        if (p) (void)hipHostFree(p);
+        if (done) (void)hipEventDestroy(done);
+    }
 };
 
 constexpr int NSLOTS = 4;
@@ -59,16 +74,20 @@ constexpr int NSLOTS = 4;
 // What the binned pipeline's pre-pass writes and its voxelize launches read. Two sets exist so that, with
 // mvx_set_overlap, the pre-pass of call k+1 can fill one set on the side stream while call k's voxelize launches
 // still read the other.
-struct Workspace {
+struct Workspace : NoCopy {
     DevBuf rec, wbuf, xp, xlist, slist, meta, aux;
     std::vector<char> meta_last; // host copy of the offsets the device meta buffer holds
     bool meta_valid = false;
     hipEvent_t ev_pre = nullptr; // pre-pass into this set finished (side stream)
     hipEvent_t ev_vox = nullptr; // the launches reading this set finished (caller's stream)
     bool vox_recorded = false;
+    ~Workspace() {
+        if (ev_pre) (void)hipEventDestroy(ev_pre);
+        if (ev_vox) (void)hipEventDestroy(ev_vox);
+    }
 };
 
-struct mvx_handle {
+struct mvx_handle : NoCopy {
     mvx_config cfg;
     Geom g;
     float sigma32;
@@ -115,6 +134,14 @@ struct mvx_handle {
     bool has_plan = false;
     int narrow_sub = 0; // "narrow_sub" option: sub-tiles per wave of narrow chunks (1: voxelize_kernel; 2 | 4: voxelize_narrow_kernel; 0: the rule)
     int dbg = 0; // diagnostic builds (-DMVX_DIAG) only
+
+    ~mvx_handle() { // (the buffers, slots and workspace sets free themselves)
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_pre) (void)hipEventDestroy(e);
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        if (ev_switch) (void)hipEventDestroy(ev_switch);
+        if (side) (void)hipStreamDestroy(side);
+    }
 };
 
 namespace {
@@ -170,6 +197,14 @@ int acquire_slot(mvx_handle *h, size_t bytes, PinnedSlot **out) {
     return MVX_OK;
 }
 
+// Every call that acquired a slot ends with this: a later call must not overwrite pinned memory that a copy still reads.
+int release_slot(PinnedSlot *slot, hipStream_t s) {
+    if (!slot) return MVX_OK;
+    HIP_TRY(hipEventRecord(slot->done, s));
+    slot->in_flight = true;
+    return MVX_OK;
+}
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 void make_geom(mvx_handle *h) {
@@ -188,19 +223,25 @@ void make_geom(mvx_handle *h) {
     h->sigma32 = (float)c.sigma;
 }
 
-struct RunArgs {
+// One call as every entry describes it; the entries fill it from their arguments, nothing below them takes those loose.
+struct Call {
     int mode;
     const double *coords;
     const void *channels; // float features (sumN, C) | int32 types (sumN) | null
     const void *radii; // float, or double for a precision-64 handle (like features and out)
     double radius_scalar;
     int radii_type;
-    const int64_t *offsets;
+    const int64_t *offsets; // batches: B + 1 host entries; views of one cloud: null
+    int64_t N;              // views: the atoms of the shared cloud
     const mvx_xform *xforms;
     int B, C;
-    void *out;
-    int in_kind, out_kind;
     hipStream_t stream;
+    int in_kind; // MVX_HOST | MVX_DEVICE: where coords, channels, radii and the memory behind the records' pointers live
+};
+
+struct RunArgs : Call {
+    void *out;
+    int out_kind;
 };
 
 // Orders this call after the previous call's work when the caller switched streams (see mvx_handle::last_stream).
@@ -225,6 +266,14 @@ int adopt_stream(mvx_handle *h, hipStream_t s) {
     return MVX_OK;
 }
 
+// How every call that touches the device begins: the handle's device current while it lives, the call ordered on its stream.
+struct CallScope {
+    DeviceGuard guard;
+    int rc; // not MVX_OK: what the entry returns
+    CallScope(mvx_handle *h, hipStream_t s)
+        : guard(h->device), rc(guard.err != hipSuccess ? fail_hip(guard.err, "hipSetDevice") : adopt_stream(h, s)) {}
+};
+
 // Explicit poses (MVX_XF_POSE_PTR): the other flag bits of such a record are clear and its pointer is set.
 int check_pose_records(const mvx_xform *xf, int n) {
     for (int i = 0; xf && i < n; ++i)
@@ -239,8 +288,26 @@ bool has_pose_records(const mvx_xform *xf, int n) {
     return false;
 }
 
+// All atoms of a call and its largest molecule; too_many: the total does not fit (each entry reports it where it always did).
+struct Extent {
+    int64_t total = 0, max_atoms = 0;
+    bool too_many() const { return total >= (int64_t)1 << 31; }
+};
+
+// The rules for host offsets (B + 1 entries, not null; B <= 0: nothing to check): the text of the first broken one, or null.
+const char *check_offsets(const int64_t *offsets, int B, Extent &e) {
+    if (B <= 0) return nullptr;
+    if (offsets[0] != 0) return "offsets[0] must be 0";
+    for (int b = 0; b < B; ++b) {
+        if (offsets[b + 1] < offsets[b]) return "offsets must be non-decreasing";
+        e.max_atoms = std::max(e.max_atoms, offsets[b + 1] - offsets[b]);
+    }
+    e.total = offsets[B];
+    return nullptr;
+}
+
 // ---- 1. what the library checks itself (shapes are the Python layer's job) -----------------------------------------
-int validate(const mvx_handle *h, const RunArgs &r, int64_t &total, int64_t &max_atoms) {
+int validate(const mvx_handle *h, const RunArgs &r, Extent &e) {
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
     if (r.B < 0 || r.C <= 0) return fail(MVX_ERR_INVALID, "B must be >= 0 and C > 0");
     if (r.B == 0) return MVX_OK;
@@ -251,32 +318,17 @@ int validate(const mvx_handle *h, const RunArgs &r, int64_t &total, int64_t &max
         return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported"); // numpy/voxelizer.py:443
     if ((r.in_kind != MVX_HOST && r.in_kind != MVX_DEVICE) || (r.out_kind != MVX_HOST && r.out_kind != MVX_DEVICE))
         return fail(MVX_ERR_INVALID, "bad memory kind");
-    if (r.offsets[0] != 0) return fail(MVX_ERR_INVALID, "offsets[0] must be 0");
-    total = r.offsets[r.B];
-    max_atoms = 0; // of one molecule
-    for (int b = 0; b < r.B; ++b) {
-        if (r.offsets[b + 1] < r.offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
-        max_atoms = std::max(max_atoms, r.offsets[b + 1] - r.offsets[b]);
-    }
-    if (total > 0 && !r.coords) return fail(MVX_ERR_INVALID, "coords must not be null");
+    if (const char *bad = check_offsets(r.offsets, r.B, e)) return fail(MVX_ERR_INVALID, bad);
+    if (e.total > 0 && !r.coords) return fail(MVX_ERR_INVALID, "coords must not be null");
     // (an empty molecule comes with empty, possibly null, per-atom arrays)
-    if (!r.radii && (r.radii_type == MVX_RADII_CHANNEL || (r.radii_type == MVX_RADII_ATOM && total > 0)))
+    if (!r.radii && (r.radii_type == MVX_RADII_CHANNEL || (r.radii_type == MVX_RADII_ATOM && e.total > 0)))
         return fail(MVX_ERR_INVALID, "radii array required");
-    if (total > 0 && r.mode != MODE_SINGLE && !r.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
-    if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (e.total > 0 && r.mode != MODE_SINGLE && !r.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
+    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
     return check_pose_records(r.xforms, r.B);
 }
 
 // ---- 2. inputs and metadata on the device ---------------------------------------------------------------------------
-struct DeviceInputs {
-    const int64_t *offsets = nullptr;
-    const mvx_xform *xforms = nullptr;
-    const double *coords = nullptr;
-    const void *channels = nullptr;
-    const void *radii = nullptr;
-    PinnedSlot *slot = nullptr; // holds the host copies until `done` fires
-};
-
 // With host-resident inputs a centre given by pointer (MVX_XF_CENTER_PTR) is a host pointer: fold it into center[]; a pose
 // (MVX_XF_POSE_PTR) likewise: the record becomes the plain one pose_resolve_kernel writes for device poses.
 void resolve_host_centers(mvx_xform *xf, int n) {
@@ -295,70 +347,108 @@ void resolve_host_centers(mvx_xform *xf, int n) {
     }
 }
 
+// A call's inputs as the kernels read them: offsets and records (stage_meta), the caller's arrays or copies (upload_arrays).
+struct DeviceInputs {
+    const int64_t *offsets = nullptr;
+    const mvx_xform *xforms = nullptr;
+    const double *coords = nullptr;
+    const void *channels = nullptr;
+    const void *radii = nullptr;
+    PinnedSlot *slot = nullptr; // holds the host copies until release_slot
+    char *rest = nullptr;       // the slot's bytes behind offsets and records: stage_meta's `extra`
+    DeviceInputs() = default;
+    explicit DeviceInputs(const Call &c) : coords(c.coords), channels(c.channels), radii(c.radii) {} // the caller's arrays
+};
+
+// Offsets (c.offsets, B + 1) and / or records (c.xforms, B) through one pinned slot into `dst` as [offsets, padded to 16 bytes |
+// records] by one async copy. `resolve`: what the records point at is folded into them (host memory: before they travel; device
+// poses: by pose_resolve_kernel on the device copy). The caller ends with release_slot(in.slot).
+int stage_meta(mvx_handle *h, DevBuf &dst, const Call &c, bool resolve, size_t extra, DeviceInputs &in) {
+    const size_t off_used = c.offsets ? (size_t)(c.B + 1) * sizeof(int64_t) : 0;
+    const size_t off_bytes = align_up(off_used, 16);
+    const size_t xf_bytes = c.xforms ? (size_t)c.B * sizeof(mvx_xform) : 0;
+    int rc;
+    if ((rc = ensure(dst, off_bytes + xf_bytes))) return rc;
+    if ((rc = acquire_slot(h, off_bytes + xf_bytes + extra, &in.slot))) return rc;
+    char *pin = in.slot->p;
+    if (c.offsets) std::memcpy(pin, c.offsets, off_used);
+    if (c.xforms) {
+        std::memcpy(pin + off_bytes, c.xforms, xf_bytes);
+        if (resolve && c.in_kind == MVX_HOST) resolve_host_centers(reinterpret_cast<mvx_xform *>(pin + off_bytes), c.B);
+    }
+    HIP_TRY(hipMemcpyAsync(dst.p, pin, off_bytes + xf_bytes, hipMemcpyHostToDevice, c.stream));
+    mvx_xform *d_xf = reinterpret_cast<mvx_xform *>((char *)dst.p + off_bytes);
+    if (resolve && c.in_kind != MVX_HOST && has_pose_records(c.xforms, c.B)) // the device copy becomes plain records
+        HIP_TRY(launch_pose_resolve(d_xf, c.B, c.stream));
+    in.offsets = c.offsets ? reinterpret_cast<const int64_t *>(dst.p) : nullptr;
+    in.xforms = c.xforms ? d_xf : nullptr;
+    in.rest = pin + off_bytes + xf_bytes;
+    return MVX_OK;
+}
+
+// Bytes of a call's arrays for `atoms` atoms (a selection of views reads no feature rows); in a slot each is padded to 16.
+struct ArrayBytes {
+    size_t coords, chan, radii;
+    size_t padded() const { return align_up(coords, 16) + align_up(chan, 16) + align_up(radii, 16); }
+};
+
+ArrayBytes array_bytes(const Call &c, int64_t atoms, size_t esz, bool with_features = true) {
+    const size_t chan_elem = c.mode == MODE_FEATURES ? (with_features ? (size_t)c.C * esz : 0) : (c.mode == MODE_TYPES ? sizeof(int32_t) : 0);
+    const size_t rad_count = c.radii_type == MVX_RADII_ATOM ? (size_t)atoms : (c.radii_type == MVX_RADII_CHANNEL ? (size_t)c.C : 0);
+    return {(size_t)atoms * 3 * sizeof(double), (size_t)atoms * chan_elem, rad_count * esz};
+}
+
+// One host array into `dst` through its part of a pinned slot (memcpy, async H2D); `dev` then points at the device copy.
+template <typename T>
+int upload(DevBuf &dst, const T *src, size_t bytes, char *staging, hipStream_t s, const T *&dev) {
+    if (bytes == 0 || !src) return MVX_OK;
+    if (int e = ensure(dst, bytes)) return e;
+    std::memcpy(staging, src, bytes);
+    HIP_TRY(hipMemcpyAsync(dst.p, staging, bytes, hipMemcpyHostToDevice, s));
+    dev = static_cast<const T *>(dst.p);
+    return MVX_OK;
+}
+
+// The host arrays `in` points at through in.rest into the handle's input buffers (forward and views): `in` gets the copies.
+int upload_arrays(mvx_handle *h, const ArrayBytes &n, hipStream_t s, DeviceInputs &in) {
+    int rc;
+    char *staging = in.rest;
+    if ((rc = upload(h->in_coords, in.coords, n.coords, staging, s, in.coords))) return rc;
+    staging += align_up(n.coords, 16);
+    if ((rc = upload(h->in_chan, in.channels, n.chan, staging, s, in.channels))) return rc;
+    return upload(h->in_radii, in.radii, n.radii, staging + align_up(n.chan, 16), s, in.radii);
+}
+
 // Host-resident arrays go through one pinned slot (a single memcpy each, then async H2D on the caller's stream);
 // device-resident arrays are used where they are. Offsets and transforms always come from the host.
 int stage_inputs(mvx_handle *h, Workspace &w, const RunArgs &r, int64_t total, size_t esz, hipStream_t s, DeviceInputs &in) {
-    const size_t off_bytes = align_up((size_t)(r.B + 1) * sizeof(int64_t), 16);
-    const size_t xf_bytes = r.xforms ? align_up((size_t)r.B * sizeof(mvx_xform), 16) : 0;
     const bool host_in = (r.in_kind == MVX_HOST);
-    const size_t chan_elem = (r.mode == MODE_FEATURES) ? (size_t)r.C * esz : (r.mode == MODE_TYPES ? sizeof(int32_t) : 0);
-    size_t rad_count = 0;
-    if (r.radii_type == MVX_RADII_ATOM) rad_count = (size_t)total;
-    else if (r.radii_type == MVX_RADII_CHANNEL) rad_count = (size_t)r.C;
-    const size_t co_bytes = host_in ? align_up((size_t)total * 3 * sizeof(double), 16) : 0;
-    const size_t ch_bytes = host_in ? align_up((size_t)total * chan_elem, 16) : 0;
-    const size_t ra_bytes = host_in ? align_up(rad_count * esz, 16) : 0;
-
+    const ArrayBytes nb = array_bytes(r, total, esz);
+    const size_t extra = host_in ? nb.padded() : 0;
+    const size_t meta_used = (size_t)(r.B + 1) * sizeof(int64_t);
     int rc;
     const void *meta_before = w.meta.p;
-    if ((rc = ensure(w.meta, off_bytes + xf_bytes))) return rc;
+    if ((rc = ensure(w.meta, align_up(meta_used, 16) + (r.xforms ? (size_t)r.B * sizeof(mvx_xform) : 0)))) return rc;
     if (w.meta.p != meta_before) w.meta_valid = false;
     // offsets (+ transforms) go to the device only when they differ from what the last call left there
     // (same-shaped batches, the common case in a training loop, skip a 5 us copy kernel)
-    const size_t meta_used = (size_t)(r.B + 1) * sizeof(int64_t);
     const bool meta_same = !r.xforms && w.meta_valid && w.meta_last.size() == meta_used &&
                            std::memcmp(w.meta_last.data(), r.offsets, meta_used) == 0;
     // a pinned slot (and the event that releases it: a barrier packet on the stream, ~6 us of idle GPU) only when
     // something is staged through it
-    char *pin = nullptr;
-    if (!meta_same || host_in) {
-        if ((rc = acquire_slot(h, off_bytes + xf_bytes + co_bytes + ch_bytes + ra_bytes, &in.slot))) return rc;
-        pin = in.slot->p;
-    }
+    in = DeviceInputs(r);
     if (!meta_same) {
-        std::memcpy(pin, r.offsets, meta_used);
-        if (r.xforms) {
-            std::memcpy(pin + off_bytes, r.xforms, (size_t)r.B * sizeof(mvx_xform));
-            if (host_in) resolve_host_centers(reinterpret_cast<mvx_xform *>(pin + off_bytes), r.B);
-        }
-        HIP_TRY(hipMemcpyAsync(w.meta.p, pin, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
-        if (!host_in && has_pose_records(r.xforms, r.B)) // device-resident poses: the device copy becomes plain records
-            HIP_TRY(launch_pose_resolve(reinterpret_cast<mvx_xform *>((char *)w.meta.p + off_bytes), r.B, s));
+        Call c = r;
+        c.stream = s; // (with mvx_set_overlap: the side stream)
+        if ((rc = stage_meta(h, w.meta, c, true, extra, in))) return rc;
         w.meta_last.assign(reinterpret_cast<const char *>(r.offsets), reinterpret_cast<const char *>(r.offsets) + meta_used);
         w.meta_valid = !r.xforms; // (a later call on another stream waits for this stream first: adopt_stream)
+    } else if (host_in) {
+        if ((rc = acquire_slot(h, extra, &in.slot))) return rc;
+        in.rest = in.slot->p;
     }
-    in.offsets = reinterpret_cast<const int64_t *>(w.meta.p);
-    in.xforms = r.xforms ? reinterpret_cast<const mvx_xform *>((char *)w.meta.p + off_bytes) : nullptr;
-    in.coords = r.coords;
-    in.channels = r.channels;
-    in.radii = r.radii;
-    if (!host_in) return MVX_OK;
-
-    auto upload = [&](DevBuf &dst, const void *src, size_t used, size_t padded, char *staging, const void *&dev) -> int {
-        if (used == 0) return MVX_OK;
-        if (int e = ensure(dst, padded)) return e;
-        std::memcpy(staging, src, used);
-        HIP_TRY(hipMemcpyAsync(dst.p, staging, padded, hipMemcpyHostToDevice, s));
-        dev = dst.p;
-        return MVX_OK;
-    };
-    char *q = pin + off_bytes + xf_bytes;
-    const void *dev_coords = in.coords;
-    if ((rc = upload(h->in_coords, r.coords, (size_t)total * 3 * sizeof(double), co_bytes, q, dev_coords))) return rc;
-    in.coords = static_cast<const double *>(dev_coords);
-    if ((rc = upload(h->in_chan, r.channels, (size_t)total * chan_elem, ch_bytes, q + co_bytes, in.channels))) return rc;
-    if ((rc = upload(h->in_radii, r.radii, rad_count * esz, ra_bytes, q + co_bytes + ch_bytes, in.radii))) return rc;
-    return MVX_OK;
+    in.offsets = reinterpret_cast<const int64_t *>(w.meta.p); // (the last call's, without records, where they are the same)
+    return host_in ? upload_arrays(h, nb, s, in) : MVX_OK;
 }
 
 // ---- 3. how the call is executed: plan_call (mvx_plan.hip) ---------------------------------------------------------
@@ -385,246 +475,250 @@ int timed_launch(mvx_handle *h, hipStream_t s, Launch &&launch) {
 }
 
 // The pre-pass arguments of a call that do not point into its buffers (forward and backward share them: the backward's
-// records are the forward's). Pointers are null, the transform is none, the launch covers atoms [0, total).
-PrepArgs prep_args(const mvx_handle *h, int mode, int radii_type, double radius_scalar, int B, int C, int64_t total) {
+// records are the forward's): the inputs as `in` holds them, no workspace pointers, no packed weights, the transform is none,
+// the launch covers atoms [0, total).
+PrepArgs prep_args(const mvx_handle *h, const Call &c, int64_t total, const DeviceInputs &in) {
     const bool f64 = (h->cfg.precision == 64);
     PrepArgs pa;
     std::memset(&pa, 0, sizeof(pa));
-    pa.mode = mode;
+    pa.mode = c.mode;
     pa.precision = f64 ? 64 : 32;
-    pa.first = 0;
     pa.total = total;
-    pa.B = B;
-    pa.C = C;
-    pa.radius_scalar = radius_scalar;
+    pa.B = c.B;
+    pa.C = c.C;
+    pa.radius_scalar = c.radius_scalar;
     pa.T_scalar = -1.0;
-    pa.k_scalar = 0.0f;
-    if (radii_type == MVX_RADII_SCALAR && !f64)
-        scalar_radius_constants(radius_scalar, h->sigma32, h->cfg.density == MVX_GAUSSIAN, &pa.T_scalar, &pa.k_scalar);
-    if (radii_type == MVX_RADII_SCALAR) pa.radii_src = RAD_SCALAR;
-    else if (radii_type == MVX_RADII_ATOM) pa.radii_src = RAD_ATOM;
-    else pa.radii_src = (mode == MODE_FEATURES) ? RAD_CHANNEL_FEATURES : RAD_CHANNEL_BY_TYPE;
+    if (c.radii_type == MVX_RADII_SCALAR && !f64)
+        scalar_radius_constants(c.radius_scalar, h->sigma32, h->cfg.density == MVX_GAUSSIAN, &pa.T_scalar, &pa.k_scalar);
+    if (c.radii_type == MVX_RADII_SCALAR) pa.radii_src = RAD_SCALAR;
+    else if (c.radii_type == MVX_RADII_ATOM) pa.radii_src = RAD_ATOM;
+    else pa.radii_src = (c.mode == MODE_FEATURES) ? RAD_CHANNEL_FEATURES : RAD_CHANNEL_BY_TYPE;
     pa.density = h->cfg.density;
     pa.sigma32 = h->sigma32;
     pa.sigma64 = h->cfg.sigma;
     pa.g = h->g;
+    pa.coords = in.coords;
+    pa.radii = in.radii;
+    pa.types = c.mode == MODE_TYPES ? static_cast<const int32_t *>(in.channels) : nullptr;
+    pa.offsets = in.offsets;
+    pa.xforms = in.xforms;
     return pa;
 }
 
-int run(mvx_handle *h, const RunArgs &r) {
-    int64_t total = 0, max_atoms = 0;
-    int rc = validate(h, r, total, max_atoms);
-    if (rc || r.B == 0) return rc;
+// Channel-wise features, float64 tables (float64 grids and every backward): [max radius | C thresholds | C coefficients].
+constexpr size_t CHAN_TC_OFF = 16;
+inline size_t chan_kc_off(int C) { return CHAN_TC_OFF + align_up((size_t)C * sizeof(double), 16); }
 
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-    hipStream_t s = r.stream;
-    if ((rc = adopt_stream(h, s))) return rc;
-    const Geom &g = h->g;
-    const int D = g.D;
-    const bool f64 = (h->cfg.precision == 64);
-    const size_t esz = f64 ? sizeof(double) : sizeof(float); // element size of features, radii and the grid
-    const bool bf16 = h->cfg.grid_type == MVX_GRID_BF16;      // ... except for a bfloat16 grid (2-byte elements)
-    if (bf16 && (reinterpret_cast<uintptr_t>(r.out) & 1u)) return fail(MVX_ERR_INVALID, "a bfloat16 grid must be 2-byte aligned");
-    const size_t out_bytes = (size_t)r.B * r.C * D * D * D * (bf16 ? sizeof(uint16_t) : esz);
-    void *d_out = r.out;
-    if (r.out_kind == MVX_HOST) {
-        if ((rc = ensure(h->out_stage, out_bytes))) return rc;
-        d_out = h->out_stage.p;
-    }
-
-    // ---- how this call is executed: one pure function of its shape (mvx_plan.hip, pinned by tests/test_plan.py) --------
-    mvx_plan_query q{};
-    q.dimension = D;
-    q.blockdim = g.bd;
-    q.precision = f64 ? 64 : 32;
-    q.mode = r.mode;
-    q.radii_type = r.radii_type;
-    q.B = r.B;
-    q.C = r.C;
-    // (a bfloat16 grid's vector store is 8 bytes: mvx_plan_call_grid)
-    // channels-last grids (C > 1; one channel IS the contiguous layout): 16-byte channel runs for either element type
-    const bool ndhwc = h->layout == MVX_LAYOUT_NDHWC && !f64 && r.C > 1;
-    q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & ((bf16 && !ndhwc) ? 7u : 15u)) == 0 ? 1 : 0;
-    q.total_atoms = total;
-    q.max_atoms = max_atoms;
-    const mvx_plan plan = plan_call(q, h->knobs, ndhwc ? MVX_LAYOUT_NDHWC : MVX_LAYOUT_NCDHW, bf16 ? 2 : 4);
-    h->last_plan = plan;
-    h->has_plan = true;
-    const bool direct = plan.route == MVX_ROUTE_DIRECT;
-    const bool mx64 = plan.route == MVX_ROUTE_F64_MX;
-    const int ct = plan.ct, ncc = plan.ncc, nchunk = plan.nchunk;
-    const size_t per_molecule = (size_t)plan.nsx * plan.nsy * plan.nzc;
-
-    const bool forced_pipeline = h->knobs.pipeline > 1 && r.B >= 4 * h->knobs.pipeline;
-    // Cross-call overlap (mvx_set_overlap): this call's pre-pass fills the other workspace set on the side stream,
-    // under the previous call's voxelize launches. Device-resident inputs and outputs only.
-    // Batches only (mvx.h: "the batched three-launch path"): a per-molecule call hands over arrays its Python layer may
-    // have converted on the caller's stream a moment ago, which the side stream would not wait for.
-    const bool overlap = h->overlap && !direct && r.B > 1 && nchunk == 1 && !forced_pipeline && r.in_kind == MVX_DEVICE && r.out_kind == MVX_DEVICE;
-    if (overlap) h->cur ^= 1;
-    Workspace &w = h->ws[h->cur];
-    // (the side stream only serves the "chunks" test option and mvx_set_overlap; chunks cut for the cache, or for the
-    // gridDim.y limit, run their launches back to back on the caller's stream)
-    const bool side_stream = forced_pipeline || overlap;
-    hipStream_t pre = s;
-    if (side_stream) {
-        if (!h->side) {
-            // lowest priority: the pre-pass should take the slots the voxelize launch leaves, not compete
-            int lo = 0, hi = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            HIP_TRY(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, lo));
-        }
-        if (!h->ev_in) HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
-        pre = h->side;
-    }
-    if (overlap) {
-        if (!w.ev_pre) HIP_TRY(hipEventCreateWithFlags(&w.ev_pre, hipEventDisableTiming));
-        if (!w.ev_vox) HIP_TRY(hipEventCreateWithFlags(&w.ev_vox, hipEventDisableTiming));
-        // this set was last read by the call before the previous one: its launches must have drained. (Nothing makes
-        // the side stream wait for the caller's stream otherwise: that is the caller's promise about the inputs.)
-        if (w.vox_recorded) {
-            HIP_TRY(hipStreamWaitEvent(pre, w.ev_vox, 0));
-        } else { // first use of the set: order behind everything the caller's stream holds so far
-            HIP_TRY(hipEventRecord(h->ev_in, s));
-            HIP_TRY(hipStreamWaitEvent(pre, h->ev_in, 0));
-        }
-    }
-
-    DeviceInputs in;
-    // (a device-resident pose is read on the device: its record is staged and resolved there, never passed by value)
-    const bool dev_pose = r.in_kind == MVX_DEVICE && has_pose_records(r.xforms, r.B);
-    const bool by_value = (r.B == 1 && r.in_kind == MVX_DEVICE && nchunk == 1 && !dev_pose); // one molecule of device arrays
-    if (by_value) { // nothing to stage: extent and transform travel with the launches
-        in.coords = r.coords;
-        in.channels = r.channels;
-        in.radii = r.radii;
-    } else if ((rc = stage_inputs(h, w, r, total, esz, overlap ? pre : s, in))) {
-        return rc;
-    }
-
-    // ---- workspace --------------------------------------------------------------------------------
-    const size_t n_alloc = (size_t)std::max<int64_t>(total, 1);
-    const int Cpad = plan.cpad;
-    const bool direct_w = plan.weights_in_place != 0;
-    const size_t nslabs = (size_t)r.B * per_molecule;
-    if (nslabs * (size_t)ncc + 1 > (size_t)0x7fffffff) return fail(MVX_ERR_INVALID, "batch too large for one call");
-    if (!direct) {
-        if ((rc = ensure(w.rec, n_alloc * sizeof(AtomRec)))) return rc;
-        if (!direct_w && (rc = ensure(w.wbuf, n_alloc * (size_t)Cpad * esz))) return rc;
-        if ((rc = ensure(w.xp, n_alloc * sizeof(uint2)))) return rc;
-        // x-lists: packed regions, (sum(N) + 2*B) * nsx entries; slab lines: primary + extension entries per slab
-        // (+ 64 B: a wave reads its eight entries of an overflowing slab's list as one group, up to seven past the list's end)
-        if ((rc = ensure(w.xlist, ((size_t)total + 2 * (size_t)r.B) * plan.nsx * sizeof(uint2) + 64))) return rc;
-        if ((rc = ensure(w.slist, nslabs * (SLAB_LINE_ENTRIES + SLAB_EXT_ENTRIES) * sizeof(uint2)))) return rc;
-    }
-    uint2 *d_xlist = reinterpret_cast<uint2 *>(w.xlist.p);
-    uint2 *d_slist = reinterpret_cast<uint2 *>(w.slist.p);
-    uint2 *d_slist_ext = d_slist ? d_slist + nslabs * SLAB_LINE_ENTRIES : nullptr; // extension lines live behind the primary lines
-
-    const bool gauss = (h->cfg.density == MVX_GAUSSIAN);
-    const bool chanwise = (r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_FEATURES);
-    void *d_rmax = nullptr;
+// One forward call: what the steps of run() hand to each other, and the steps themselves in the order run() takes them.
+struct Forward {
+    mvx_handle *h;
+    const RunArgs &r;
+    const Extent ext;
+    const bool f64 = h->cfg.precision == 64, bf16 = h->cfg.grid_type == MVX_GRID_BF16, gauss = h->cfg.density == MVX_GAUSSIAN;
+    const bool chanwise = r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_FEATURES;
+    const size_t esz = f64 ? sizeof(double) : sizeof(float); // element size of features, radii and the grid (but bfloat16 grids: 2)
+    // make_plan:
+    bool ndhwc = false, overlap = false, side_stream = false, dev_pose = false, by_value = false;
+    size_t out_bytes = 0;
+    void *d_out = nullptr;
+    mvx_plan plan{};
+    Workspace *w = nullptr;
+    // order_prepass: the pre-pass's stream - the caller's (s), or the side stream
+    hipStream_t s = r.stream, pre = s;
+    DeviceInputs in;   // run(): the caller's arrays, or stage_inputs
+    size_t nslabs = 0; // size_workspace
+    // chan_tables:
+    void *d_rmax = nullptr; // (channel-wise features: the tables chan_aux_kernel / chan_aux64_kernel write)
     double *d_Tc = nullptr;
     float *d_kc = nullptr;
     ChanGroups *d_groups = nullptr;
     int32_t *d_chan_slot = nullptr;
-    if (chanwise) {
-        if (f64) { // [max radius | per-channel thresholds | per-channel coefficients]
-            const size_t tc_off = 16, kc_off = tc_off + align_up((size_t)r.C * sizeof(double), 16);
-            if ((rc = ensure(w.aux, kc_off + (size_t)r.C * sizeof(double)))) return rc;
-            d_rmax = w.aux.p;
-            d_Tc = reinterpret_cast<double *>((char *)w.aux.p + tc_off);
-            d_kc = reinterpret_cast<float *>((char *)w.aux.p + kc_off); // (double coefficients behind a float pointer)
-            HIP_TRY(launch_chan_aux64(static_cast<const double *>(in.radii), r.C, h->cfg.density, h->cfg.sigma,
-                                      static_cast<double *>(d_rmax), d_Tc, reinterpret_cast<double *>(d_kc), overlap ? pre : s));
-        } else { // [max radius | one ChanGroups per chunk of 32 channels | the channels' radius slots (int32 x C)]
-            const size_t slot_off = 16 + (size_t)ncc * sizeof(ChanGroups);
-            if ((rc = ensure(w.aux, slot_off + (size_t)r.C * sizeof(int32_t)))) return rc;
-            d_rmax = w.aux.p;
-            d_groups = reinterpret_cast<ChanGroups *>((char *)w.aux.p + 16);
-            d_chan_slot = reinterpret_cast<int32_t *>((char *)w.aux.p + slot_off);
-            HIP_TRY(launch_chan_aux(static_cast<const float *>(in.radii), r.C, h->cfg.density, h->sigma32, static_cast<float *>(d_rmax),
-                                    d_groups, d_chan_slot, overlap ? pre : s));
+    // kernel_args:
+    PrepArgs pa{};
+    VoxArgs va{};
+    bool lr_blocks = false, lane_range = false;
+    Forward(mvx_handle *h_, const RunArgs &r_, const Extent &e) : h(h_), r(r_), ext(e) {}
+    hipStream_t staging_stream() const { return overlap ? pre : s; }
+    // ---- how this call is executed: one pure function of its shape (mvx_plan.hip, pinned by tests/test_plan.py) ----
+    int make_plan() {
+        const Geom &g = h->g;
+        const size_t D = (size_t)g.D;
+        if (bf16 && (reinterpret_cast<uintptr_t>(r.out) & 1u)) return fail(MVX_ERR_INVALID, "a bfloat16 grid must be 2-byte aligned");
+        out_bytes = (size_t)r.B * r.C * D * D * D * (bf16 ? sizeof(uint16_t) : esz);
+        d_out = r.out;
+        if (r.out_kind == MVX_HOST) {
+            if (int rc = ensure(h->out_stage, out_bytes)) return rc;
+            d_out = h->out_stage.p;
         }
+        mvx_plan_query q{};
+        q.dimension = g.D;
+        q.blockdim = g.bd;
+        q.precision = f64 ? 64 : 32;
+        q.mode = r.mode;
+        q.radii_type = r.radii_type;
+        q.B = r.B;
+        q.C = r.C;
+        // (a bfloat16 grid's vector store is 8 bytes: mvx_plan_call_grid)
+        // channels-last grids (C > 1; one channel IS the contiguous layout): 16-byte channel runs for either element type
+        ndhwc = h->layout == MVX_LAYOUT_NDHWC && !f64 && r.C > 1;
+        q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & ((bf16 && !ndhwc) ? 7u : 15u)) == 0 ? 1 : 0;
+        q.total_atoms = ext.total;
+        q.max_atoms = ext.max_atoms;
+        plan = plan_call(q, h->knobs, ndhwc ? MVX_LAYOUT_NDHWC : MVX_LAYOUT_NCDHW, bf16 ? 2 : 4);
+        h->last_plan = plan;
+        h->has_plan = true;
+        const bool forced_pipeline = h->knobs.pipeline > 1 && r.B >= 4 * h->knobs.pipeline;
+        // Cross-call overlap (mvx_set_overlap): this call's pre-pass fills the other workspace set on the side stream,
+        // under the previous call's voxelize launches. Device-resident inputs and outputs only.
+        // Batches only (mvx.h: "the batched three-launch path"): a per-molecule call hands over arrays its Python layer may
+        // have converted on the caller's stream a moment ago, which the side stream would not wait for.
+        overlap = h->overlap && plan.route != MVX_ROUTE_DIRECT && r.B > 1 && plan.nchunk == 1 && !forced_pipeline &&
+                  r.in_kind == MVX_DEVICE && r.out_kind == MVX_DEVICE;
+        if (overlap) h->cur ^= 1;
+        w = &h->ws[h->cur];
+        // (the side stream only serves the "chunks" test option and mvx_set_overlap; chunks cut for the cache, or for the
+        // gridDim.y limit, run their launches back to back on the caller's stream)
+        side_stream = forced_pipeline || overlap;
+        // (a device-resident pose is read on the device: its record is staged and resolved there, never passed by value)
+        dev_pose = r.in_kind == MVX_DEVICE && has_pose_records(r.xforms, r.B);
+        by_value = (r.B == 1 && r.in_kind == MVX_DEVICE && plan.nchunk == 1 && !dev_pose); // one molecule of device arrays
+        return MVX_OK;
     }
-
-    // ---- kernel arguments -------------------------------------------------------------------------
-    PrepArgs pa = prep_args(h, r.mode, r.radii_type, r.radius_scalar, r.B, r.C, total);
-    pa.coords = in.coords;
-    pa.radii = in.radii;
-    pa.types = (r.mode == MODE_TYPES) ? reinterpret_cast<const int32_t *>(in.channels) : nullptr;
-    pa.features = (r.mode == MODE_FEATURES) ? in.channels : nullptr;
-    pa.Cpad = Cpad;
-    pa.offsets = in.offsets;
-    pa.xforms = in.xforms;
-    if (by_value && r.xforms) pa.xf_one = r.xforms[0];
-    pa.chan_aux = d_rmax;
-    pa.rec = reinterpret_cast<AtomRec *>(w.rec.p);
-    pa.wbuf = direct_w ? nullptr : w.wbuf.p;
-    pa.xp = reinterpret_cast<uint2 *>(w.xp.p);
-
-    VoxArgs va;
-    va.rec = reinterpret_cast<const unsigned *>(w.rec.p);
-    va.w = reinterpret_cast<const unsigned *>(direct_w ? in.channels : w.wbuf.p);
-    va.xlist = d_xlist;
-    va.slist = d_slist;
-    va.slist_ext = d_slist_ext;
-    va.offsets = in.offsets;
-    va.n_one = total;
-    va.Tc = d_Tc;
-    va.kc = d_kc;
-    va.out = d_out;
-    va.bf16 = bf16 ? 1 : 0;
-    va.ndhwc = ndhwc ? 1 : 0;
-    va.narrow_sub = h->narrow_sub;
-    va.p.res = g.res;
-    va.p.half = g.half;
-    va.p.D = D;
-    va.p.C = r.C;
-    va.p.B = r.B;
-    va.p.nsx = plan.nsx;
-    va.p.nsy = plan.nsy;
-    va.p.nzc = plan.nzc;
-    va.p.ncc = ncc;
-    va.p.nsy_inv = umulhi_inverse(plan.nsy);
-    va.p.nzc_inv = umulhi_inverse(plan.nzc);
-    va.p.nsx_inv = umulhi_inverse(plan.nsx);
-    va.p.ncc_inv = umulhi_inverse(ncc);
-    va.p.b0 = 0;
-    va.p.c0 = 0;
-    va.p.NW = plan.nw;
-    va.p.nslab = (uint32_t)(plan.nsx * plan.nsy * plan.nzc);
-    va.p.w_stride = plan.grouped ? r.C : Cpad;
-    va.p.dcap = f64 ? (mx64 ? 0 : 64) : 0; // (float64: rows per round of the general slab loop, 0 selects the matrix-core kernel)
-    va.p.vec_store = plan.vec_store;
-    va.p.xcd_ranges = plan.xcd_ranges;
-    va.p.pace = plan.pace;
-    va.p.sigma = h->cfg.sigma;
+    // ---- the pre-pass's stream and, with cross-call overlap, what it waits for before it refills its workspace set ----
+    int order_prepass() {
+        if (side_stream) {
+            if (!h->side) {
+                // lowest priority: the pre-pass should take the slots the voxelize launch leaves, not compete
+                int lo = 0, hi = 0;
+                HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
+                HIP_TRY(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, lo));
+            }
+            if (!h->ev_in) HIP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming));
+            pre = h->side;
+        }
+        if (overlap) {
+            if (!w->ev_pre) HIP_TRY(hipEventCreateWithFlags(&w->ev_pre, hipEventDisableTiming));
+            if (!w->ev_vox) HIP_TRY(hipEventCreateWithFlags(&w->ev_vox, hipEventDisableTiming));
+            // this set was last read by the call before the previous one: its launches must have drained. (Nothing makes
+            // the side stream wait for the caller's stream otherwise: that is the caller's promise about the inputs.)
+            if (w->vox_recorded) {
+                HIP_TRY(hipStreamWaitEvent(pre, w->ev_vox, 0));
+            } else { // first use of the set: order behind everything the caller's stream holds so far
+                HIP_TRY(hipEventRecord(h->ev_in, s));
+                HIP_TRY(hipStreamWaitEvent(pre, h->ev_in, 0));
+            }
+        }
+        return MVX_OK;
+    }
+    // ---- workspace of the binned pipeline ----
+    int size_workspace() {
+        const size_t n_alloc = (size_t)std::max<int64_t>(ext.total, 1);
+        nslabs = (size_t)r.B * ((size_t)plan.nsx * plan.nsy * plan.nzc);
+        if (nslabs * (size_t)plan.ncc + 1 > (size_t)0x7fffffff) return fail(MVX_ERR_INVALID, "batch too large for one call");
+        if (plan.route == MVX_ROUTE_DIRECT) return MVX_OK;
+        int rc;
+        if ((rc = ensure(w->rec, n_alloc * sizeof(AtomRec)))) return rc;
+        if (!plan.weights_in_place && (rc = ensure(w->wbuf, n_alloc * (size_t)plan.cpad * esz))) return rc;
+        if ((rc = ensure(w->xp, n_alloc * sizeof(uint2)))) return rc;
+        // x-lists: packed regions, (sum(N) + 2*B) * nsx entries; slab lines: primary + extension entries per slab
+        // (+ 64 B: a wave reads its eight entries of an overflowing slab's list as one group, up to seven past the list's end)
+        if ((rc = ensure(w->xlist, ((size_t)ext.total + 2 * (size_t)r.B) * plan.nsx * sizeof(uint2) + 64))) return rc;
+        return ensure(w->slist, nslabs * (SLAB_LINE_ENTRIES + SLAB_EXT_ENTRIES) * sizeof(uint2));
+    }
+    // ---- channel-wise features: the per-channel tables of this call ----
+    int chan_tables() {
+        if (!chanwise) return MVX_OK;
+        DevBuf &aux = w->aux;
+        if (f64) {
+            if (int rc = ensure(aux, chan_kc_off(r.C) + (size_t)r.C * sizeof(double))) return rc;
+            d_rmax = aux.p;
+            d_Tc = reinterpret_cast<double *>((char *)aux.p + CHAN_TC_OFF);
+            d_kc = reinterpret_cast<float *>((char *)aux.p + chan_kc_off(r.C)); // (double coefficients behind a float pointer)
+            HIP_TRY(launch_chan_aux64(static_cast<const double *>(in.radii), r.C, h->cfg.density, h->cfg.sigma,
+                                      static_cast<double *>(d_rmax), d_Tc, reinterpret_cast<double *>(d_kc), staging_stream()));
+        } else { // [max radius | one ChanGroups per chunk of 32 channels | the channels' radius slots (int32 x C)]
+            const size_t slot_off = 16 + (size_t)plan.ncc * sizeof(ChanGroups);
+            if (int rc = ensure(aux, slot_off + (size_t)r.C * sizeof(int32_t))) return rc;
+            d_rmax = aux.p;
+            d_groups = reinterpret_cast<ChanGroups *>((char *)aux.p + 16);
+            d_chan_slot = reinterpret_cast<int32_t *>((char *)aux.p + slot_off);
+            HIP_TRY(launch_chan_aux(static_cast<const float *>(in.radii), r.C, h->cfg.density, h->sigma32, static_cast<float *>(d_rmax),
+                                    d_groups, d_chan_slot, staging_stream()));
+        }
+        return MVX_OK;
+    }
+    // ---- kernel arguments ----
+    void kernel_args() {
+        const Geom &g = h->g;
+        const bool direct_w = plan.weights_in_place != 0;
+        uint2 *d_slist = reinterpret_cast<uint2 *>(w->slist.p);
+        pa = prep_args(h, r, ext.total, in);
+        pa.features = (r.mode == MODE_FEATURES) ? in.channels : nullptr;
+        pa.Cpad = plan.cpad;
+        if (by_value && r.xforms) pa.xf_one = r.xforms[0];
+        pa.chan_aux = d_rmax;
+        pa.rec = reinterpret_cast<AtomRec *>(w->rec.p);
+        pa.wbuf = direct_w ? nullptr : w->wbuf.p;
+        pa.xp = reinterpret_cast<uint2 *>(w->xp.p);
+        va.rec = reinterpret_cast<const unsigned *>(w->rec.p);
+        va.w = reinterpret_cast<const unsigned *>(direct_w ? in.channels : w->wbuf.p);
+        va.xlist = reinterpret_cast<uint2 *>(w->xlist.p);
+        va.slist = d_slist;
+        va.slist_ext = d_slist ? d_slist + nslabs * SLAB_LINE_ENTRIES : nullptr; // extension lines live behind the primary lines
+        va.offsets = in.offsets;
+        va.n_one = ext.total;
+        va.Tc = d_Tc;
+        va.kc = d_kc;
+        va.out = d_out;
+        va.bf16 = bf16 ? 1 : 0;
+        va.ndhwc = ndhwc ? 1 : 0;
+        va.narrow_sub = h->narrow_sub;
+        va.p.res = g.res;
+        va.p.half = g.half;
+        va.p.D = g.D;
+        va.p.C = r.C;
+        va.p.B = r.B;
+        va.p.nsx = plan.nsx;
+        va.p.nsy = plan.nsy;
+        va.p.nzc = plan.nzc;
+        va.p.ncc = plan.ncc;
+        va.p.nsy_inv = umulhi_inverse(plan.nsy);
+        va.p.nzc_inv = umulhi_inverse(plan.nzc);
+        va.p.nsx_inv = umulhi_inverse(plan.nsx);
+        va.p.ncc_inv = umulhi_inverse(plan.ncc);
+        va.p.b0 = 0;
+        va.p.c0 = 0;
+        va.p.NW = plan.nw;
+        va.p.nslab = (uint32_t)(plan.nsx * plan.nsy * plan.nzc);
+        va.p.w_stride = plan.grouped ? r.C : plan.cpad;
+        va.p.dcap = f64 ? (plan.route == MVX_ROUTE_F64_MX ? 0 : 64) : 0; // (float64: rows per round of the general slab loop, 0 selects the matrix-core kernel)
+        va.p.vec_store = plan.vec_store;
+        va.p.xcd_ranges = plan.xcd_ranges;
+        va.p.pace = plan.pace;
+        va.p.sigma = h->cfg.sigma;
 #ifdef MVX_DIAG
-    va.p.dbg = h->dbg;
+        va.p.dbg = h->dbg;
 #endif
-    // float32 grids whose rows are not whole 16-byte quads need the run-wise write-out (store_runs): compiled into the
-    // per-lane-range kernels, voxelize_runs_kernel (the matrix-core walk of 32-channel chunks) and voxelize_pair_runs_kernel
-    // (the candidate-pair walk of narrow chunks), nowhere else
-    const bool lr_blocks = plan.lane_range != 0;
-    const bool runs = !f64 && !ndhwc && !va.p.vec_store; // (channels-last: both store forms live in every kernel)
-    const bool lane_range = lr_blocks || runs;
-    auto lane_range_for = [&](int32_t) { return lr_blocks; }; // (run-wise write-out: voxelize_runs_kernel / voxelize_pair_runs_kernel)
-
-    if (direct) {
+        // float32 grids whose rows are not whole 16-byte quads need the run-wise write-out (store_runs): compiled into the
+        // per-lane-range kernels, voxelize_runs_kernel (the matrix-core walk of 32-channel chunks) and voxelize_pair_runs_kernel
+        // (the candidate-pair walk of narrow chunks), nowhere else
+        lr_blocks = plan.lane_range != 0;
+        lane_range = lr_blocks || (!f64 && !ndhwc && !va.p.vec_store); // (channels-last: both store forms live in every kernel)
+    }
+    // ---- the whole call in one launch (voxelize_pair_kernel): no workspace, no pre-pass ----
+    int launch_direct() {
         DirectArgs da;
         da.pa = pa;
         da.pa.rec = nullptr;
 #ifdef MVX_DIAG // stamps of every workgroup (8 x 8 B each), read back with mvx_debug_read_records
-        if ((rc = ensure(w.rec, nslabs * (size_t)ncc * 64))) return rc;
-        da.pa.rec = reinterpret_cast<AtomRec *>(w.rec.p);
-        HIP_TRY(hipMemsetAsync(w.rec.p, 0, nslabs * (size_t)ncc * 64, s)); // (slots filled by atomicMax need a zero start)
+        if (int rc = ensure(w->rec, nslabs * (size_t)plan.ncc * 64)) return rc;
+        da.pa.rec = reinterpret_cast<AtomRec *>(w->rec.p);
+        HIP_TRY(hipMemsetAsync(w->rec.p, 0, nslabs * (size_t)plan.ncc * 64, s)); // (slots filled by atomicMax need a zero start)
 #endif
         da.pa.wbuf = nullptr;
         da.pa.xp = nullptr;
         da.pa.chan_aux = nullptr;
-        da.N = total;
+        da.N = ext.total;
         if (r.B == 1) { // one molecule: extent and transform by value, no metadata on the device
             da.pa.offsets = nullptr;
             da.pa.xforms = dev_pose ? in.xforms : nullptr;
@@ -634,91 +728,102 @@ int run(mvx_handle *h, const RunArgs &r) {
                 if (r.in_kind == MVX_HOST) resolve_host_centers(&da.pa.xf_one, 1);
             }
         }
-        if ((rc = timed_launch(h, s, [&] { return launch_voxelize_direct(da, va.p, max_atoms, d_out, bf16, ndhwc, ct, gauss, lr_blocks, s); })))
-            return rc;
-        if (in.slot) {
-            HIP_TRY(hipEventRecord(in.slot->done, s));
-            in.slot->in_flight = true;
+        return timed_launch(h, s, [&] { return launch_voxelize_direct(da, va.p, ext.max_atoms, d_out, bf16, ndhwc, plan.ct, gauss, lr_blocks, s); });
+    }
+    // ---- the binned pipeline: pre-pass (prep + x-binning) and voxelize launches, chunk by chunk where the plan cuts the batch ----
+    int launch_binned() {
+        const int nchunk = plan.nchunk, ct = plan.ct;
+        uint2 *xlist = reinterpret_cast<uint2 *>(w->xlist.p), *slist = reinterpret_cast<uint2 *>(w->slist.p);
+        int rc;
+        if (side_stream && !overlap) {
+            while ((int)h->ev_pre.size() < nchunk) {
+                hipEvent_t e = nullptr;
+                HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                h->ev_pre.push_back(e);
+            }
+            // inputs (and the workspace, still read by the previous call's launches) are ready once `s` gets here
+            HIP_TRY(hipEventRecord(h->ev_in, s));
+            HIP_TRY(hipStreamWaitEvent(pre, h->ev_in, 0));
         }
+        auto chunk_begin = [&](int k) { return (int)((int64_t)r.B * k / nchunk); };
+        auto prepass = [&](int k) -> int {
+            const int b0 = chunk_begin(k), b1 = chunk_begin(k + 1);
+            pa.first = r.offsets[b0];
+            pa.total = r.offsets[b1];
+            HIP_TRY(launch_prep(pa, pre));
+            HIP_TRY(launch_xbin(pa.xp, in.offsets, ext.total, b0, b1 - b0, ext.max_atoms, plan.nsx, plan.nsy, plan.nzc, plan.nw, xlist, slist,
+                                slist + nslabs * SLAB_LINE_ENTRIES, pre));
+            if (side_stream) HIP_TRY(hipEventRecord(overlap ? w->ev_pre : h->ev_pre[k], pre));
+            return MVX_OK;
+        };
+        const bool interleave = !side_stream && !f64 && nchunk > 1; // chunk by chunk: pre-pass, then its voxelize launch
+        for (int k = 0; k < nchunk && !interleave; ++k)
+            if ((rc = prepass(k))) return rc;
+        if (f64) { // float64 grids: one launch over the whole batch
+            for (int k = 0; k < nchunk && side_stream; ++k) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
+            if ((rc = timed_launch(h, s, [&] { return launch_voxelize64(va, ct, gauss, chanwise, lr_blocks, s); }))) return rc;
+        } else {
+            for (int k = 0; k < nchunk; ++k) {
+                const int b0 = chunk_begin(k), b1 = chunk_begin(k + 1);
+                if (interleave && (rc = prepass(k))) return rc;
+                if (side_stream) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
+                va.p.b0 = b0;
+                if (plan.grouped) {
+                    // channels grouped by radius (chan_aux_kernel): chunks of 32 channels on the matrix-core path, one
+                    // threshold test and one density per radius slot and candidate, feature rows read in place
+                    VoxArgs vg = va;
+                    vg.Tc = reinterpret_cast<const double *>(d_groups);
+                    vg.kc = reinterpret_cast<const float *>(d_chan_slot);
+                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize_grouped(vg, b1 - b0, gauss, lane_range, s); }))) return rc;
+                    continue;
+                }
+                va.p.ncc = plan.nfull;
+                va.p.ncc_inv = umulhi_inverse(plan.nfull); // (the main launch of a call with a remainder launch has nfull, not ncc, chunks per molecule)
+                va.p.c0 = 0;
+                // the bracket holds voxelize_kernel alone (what rocprofv3 reports under that name)
+                if ((rc = timed_launch(h, s, [&] { return launch_voxelize(va, b1 - b0, ct, gauss, lr_blocks, s); }))) return rc;
+                if (plan.ct_rem) { // the remainder channels [nfull * ct, C) with a narrower kernel
+                    va.p.ncc = 1;
+                    va.p.c0 = plan.nfull * ct;
+                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize(va, b1 - b0, plan.ct_rem, gauss, lr_blocks, s); }))) return rc;
+                }
+            }
+        }
+        if (overlap) { // the next call but one refills this set
+            HIP_TRY(hipEventRecord(w->ev_vox, s));
+            w->vox_recorded = true;
+        } else {
+            w->vox_recorded = false; // (its reads are ordered on the caller's stream only)
+        }
+        return MVX_OK;
+    }
+    // ---- how both routes end: the slot may be reused once the stream gets here; a host grid is copied back and waited for ----
+    int finish() {
+        if (int rc = release_slot(in.slot, s)) return rc;
         if (r.out_kind == MVX_HOST) {
             HIP_TRY(hipMemcpyAsync(r.out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
         }
         return MVX_OK;
     }
+};
 
-    // ---- launches -----------------------------------------------------------------------------------------------
-    if (side_stream && !overlap) {
-        while ((int)h->ev_pre.size() < nchunk) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            h->ev_pre.push_back(e);
-        }
-        // inputs (and the workspace, still read by the previous call's launches) are ready once `s` gets here
-        HIP_TRY(hipEventRecord(h->ev_in, s));
-        HIP_TRY(hipStreamWaitEvent(pre, h->ev_in, 0));
-    }
-    auto chunk_begin = [&](int k) { return (int)((int64_t)r.B * k / nchunk); };
-    auto prepass = [&](int k) -> int {
-        const int b0 = chunk_begin(k), b1 = chunk_begin(k + 1);
-        pa.first = r.offsets[b0];
-        pa.total = r.offsets[b1];
-        HIP_TRY(launch_prep(pa, pre));
-        HIP_TRY(launch_xbin(pa.xp, in.offsets, total, b0, b1 - b0, max_atoms, plan.nsx, plan.nsy, plan.nzc, plan.nw, d_xlist, d_slist,
-                            d_slist_ext, pre));
-        if (side_stream) HIP_TRY(hipEventRecord(overlap ? w.ev_pre : h->ev_pre[k], pre));
-        return MVX_OK;
-    };
-    const bool interleave = !side_stream && !f64 && nchunk > 1; // chunk by chunk: pre-pass, then its voxelize launch
-    for (int k = 0; k < nchunk && !interleave; ++k)
-        if ((rc = prepass(k))) return rc;
-    if (f64) { // float64 grids: one launch over the whole batch
-        for (int k = 0; k < nchunk && side_stream; ++k) HIP_TRY(hipStreamWaitEvent(s, overlap ? w.ev_pre : h->ev_pre[k], 0));
-        if ((rc = timed_launch(h, s, [&] { return launch_voxelize64(va, ct, gauss, chanwise, lr_blocks, s); }))) return rc;
-    } else {
-        for (int k = 0; k < nchunk; ++k) {
-            const int b0 = chunk_begin(k), b1 = chunk_begin(k + 1);
-            if (interleave && (rc = prepass(k))) return rc;
-            if (side_stream) HIP_TRY(hipStreamWaitEvent(s, overlap ? w.ev_pre : h->ev_pre[k], 0));
-            va.p.b0 = b0;
-            if (plan.grouped) {
-                // channels grouped by radius (chan_aux_kernel): chunks of 32 channels on the matrix-core path, one
-                // threshold test and one density per radius slot and candidate, feature rows read in place
-                VoxArgs vg = va;
-                vg.Tc = reinterpret_cast<const double *>(d_groups);
-                vg.kc = reinterpret_cast<const float *>(d_chan_slot);
-                if ((rc = timed_launch(h, s, [&] { return launch_voxelize_grouped(vg, b1 - b0, gauss, lane_range, s); }))) return rc;
-                continue;
-            }
-            va.p.ncc = plan.nfull;
-            va.p.ncc_inv = umulhi_inverse(plan.nfull); // (the main launch of a call with a remainder launch has nfull, not ncc, chunks per molecule)
-            va.p.c0 = 0;
-            // the bracket holds voxelize_kernel alone (what rocprofv3 reports under that name)
-            if ((rc = timed_launch(h, s, [&] { return launch_voxelize(va, b1 - b0, ct, gauss, lane_range_for(ct), s); }))) return rc;
-            if (plan.ct_rem) { // the remainder channels [nfull * ct, C) with a narrower kernel
-                va.p.ncc = 1;
-                va.p.c0 = plan.nfull * ct;
-                if ((rc = timed_launch(h, s, [&] { return launch_voxelize(va, b1 - b0, plan.ct_rem, gauss, lane_range_for(plan.ct_rem), s); }))) return rc;
-            }
-        }
-    }
-
-    if (overlap) { // the next call but one refills this set
-        HIP_TRY(hipEventRecord(w.ev_vox, s));
-        w.vox_recorded = true;
-    } else {
-        w.vox_recorded = false; // (its reads are ordered on the caller's stream only)
-    }
-    if (in.slot) {
-        HIP_TRY(hipEventRecord(in.slot->done, s));
-        in.slot->in_flight = true;
-    }
-
-    if (r.out_kind == MVX_HOST) {
-        HIP_TRY(hipMemcpyAsync(r.out, d_out, out_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    return MVX_OK;
+int run(mvx_handle *h, const RunArgs &r) {
+    Extent ext;
+    int rc = validate(h, r, ext);
+    if (rc || r.B == 0) return rc;
+    CallScope scope(h, r.stream);
+    if (scope.rc) return scope.rc;
+    Forward f(h, r, ext); // (each step reads what the steps before it set: see the members' comments)
+    if ((rc = f.make_plan())) return rc;
+    if ((rc = f.order_prepass())) return rc;
+    if (f.by_value) f.in = DeviceInputs(r); // nothing to stage: extent and transform travel with the launches
+    else if ((rc = stage_inputs(h, *f.w, r, f.ext.total, f.esz, f.staging_stream(), f.in))) return rc;
+    if ((rc = f.size_workspace())) return rc;
+    if ((rc = f.chan_tables())) return rc;
+    f.kernel_args();
+    if ((rc = f.plan.route == MVX_ROUTE_DIRECT ? f.launch_direct() : f.launch_binned())) return rc;
+    return f.finish();
 }
 
 } // namespace
@@ -782,27 +887,7 @@ int mvx_destroy(mvx_handle *h) {
     if (!h) return MVX_OK;
     DeviceGuard guard(h->device);
     (void)hipDeviceSynchronize();
-    std::vector<DevBuf *> bufs = {&h->xf_buf, &h->in_coords, &h->in_chan, &h->in_radii, &h->out_stage,
-                                  &h->grad_rec, &h->grad_xp, &h->grad_meta, &h->grad_aux, &h->grad_sort, &h->grad_rpart, &h->pose_meta, &h->score_atoms,
-                                  &h->view_xf, &h->view_counts, &h->view_base, &h->view_off, &h->view_aux, &h->view_index,
-                                  &h->view_coords, &h->view_chan, &h->view_radii, &h->view_red_off};
-    for (Workspace &w : h->ws) {
-        for (DevBuf *b : {&w.rec, &w.wbuf, &w.xp, &w.xlist, &w.slist, &w.meta, &w.aux}) bufs.push_back(b);
-        if (w.ev_pre) (void)hipEventDestroy(w.ev_pre);
-        if (w.ev_vox) (void)hipEventDestroy(w.ev_vox);
-    }
-    for (DevBuf *b : bufs)
-        if (b->p) (void)hipFree(b->p);
-    for (PinnedSlot &s : h->slots) {
-        if (s.p) (void)hipHostFree(s.p);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : h->ev_pre) (void)hipEventDestroy(e);
-    if (h->ev_in) (void)hipEventDestroy(h->ev_in);
-    if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    delete h;
+    delete h; // (buffers, slots, events and the side stream: freed by their owners)
     return MVX_OK;
 }
 
@@ -837,26 +922,23 @@ int mvx_forward_features_batch(mvx_handle *h, const double *coords, const void *
                                double radius_scalar, int32_t radii_type, const int64_t *offsets,
                                const mvx_xform *xforms, int32_t B, int32_t C, void *out, int32_t in_kind,
                                int32_t out_kind, void *stream) {
-    RunArgs r{MODE_FEATURES, coords, features, radii, radius_scalar, radii_type, offsets, xforms, B, C, out,
-              in_kind, out_kind, reinterpret_cast<hipStream_t>(stream)};
-    return run(h, r);
+    return run(h, RunArgs{{MODE_FEATURES, coords, features, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                           reinterpret_cast<hipStream_t>(stream), in_kind}, out, out_kind});
 }
 
 int mvx_forward_types_batch(mvx_handle *h, const double *coords, const int32_t *types, const void *radii,
                             double radius_scalar, int32_t radii_type, const int64_t *offsets,
                             const mvx_xform *xforms, int32_t B, int32_t C, void *out, int32_t in_kind,
                             int32_t out_kind, void *stream) {
-    RunArgs r{MODE_TYPES, coords, types, radii, radius_scalar, radii_type, offsets, xforms, B, C, out,
-              in_kind, out_kind, reinterpret_cast<hipStream_t>(stream)};
-    return run(h, r);
+    return run(h, RunArgs{{MODE_TYPES, coords, types, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                           reinterpret_cast<hipStream_t>(stream), in_kind}, out, out_kind});
 }
 
 int mvx_forward_single_batch(mvx_handle *h, const double *coords, const void *radii, double radius_scalar,
                              int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                              void *out, int32_t in_kind, int32_t out_kind, void *stream) {
-    RunArgs r{MODE_SINGLE, coords, nullptr, radii, radius_scalar, radii_type, offsets, xforms, B, 1, out,
-              in_kind, out_kind, reinterpret_cast<hipStream_t>(stream)};
-    return run(h, r);
+    return run(h, RunArgs{{MODE_SINGLE, coords, nullptr, radii, radius_scalar, radii_type, offsets, 0, xforms, B, 1,
+                           reinterpret_cast<hipStream_t>(stream), in_kind}, out, out_kind});
 }
 
 int mvx_forward_features(mvx_handle *h, const double *coords, const void *features, const void *radii,
@@ -886,24 +968,10 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const void *radii, d
 // ---- views of one shared cloud (mvx_views.hip) ----------------------------------------------------------------------------
 namespace {
 
-struct ViewCall {
-    int mode;
-    const double *coords;
-    const void *channels; // features (N, C) | types (N,) | null
-    const void *radii;
-    double radius_scalar;
-    int radii_type;
-    int64_t N;
-    int C;
-    const mvx_xform *xforms;
-    int B;
-    int in_kind;
-    hipStream_t stream;
-};
-
-// What both entries reject before any device is touched. `own`: what the entry found wrong with its own arguments (null: nothing);
+// A views call has N atoms, B views and no offsets. What its entries reject before any device is touched. `own`: what the entry
+// found wrong with its own arguments (null: nothing);
 // the handle is looked at last, so every other rule can be checked without a device.
-int validate_views(const mvx_handle *h, const ViewCall &v, const char *own) {
+int validate_views(const mvx_handle *h, const Call &v, const char *own) {
     if (v.mode != MODE_FEATURES && v.mode != MODE_TYPES && v.mode != MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode");
     if (v.radii_type < MVX_RADII_SCALAR || v.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
     if (v.in_kind != MVX_HOST && v.in_kind != MVX_DEVICE) return fail(MVX_ERR_INVALID, "bad memory kind");
@@ -924,80 +992,38 @@ int validate_views(const mvx_handle *h, const ViewCall &v, const char *own) {
 }
 
 // the cloud and the views' transforms as device arrays
-struct ViewInputs {
-    const double *coords = nullptr;
-    const void *channels = nullptr;
-    const void *radii = nullptr;
-    const mvx_xform *xforms = nullptr;       // device copy of the B records
-    std::vector<mvx_xform> xforms_host;      // the records as run() gets them (host centres folded in)
+struct ViewInputs : DeviceInputs {
+    explicit ViewInputs(const Call &v) : DeviceInputs(v) {}
+    std::vector<mvx_xform> xforms_host; // the records as run() gets them (host centres folded in)
 };
 
 // Host-resident arrays are uploaded once - the cloud, not B copies of it - through a pinned slot; `select_only`: the feature
 // rows are not needed (the selection reads coordinates, types and radii).
-int stage_views(mvx_handle *h, const ViewCall &v, bool select_only, ViewInputs &in) {
-    hipStream_t s = v.stream;
-    const size_t esz = h->cfg.precision == 64 ? sizeof(double) : sizeof(float);
+int stage_views(mvx_handle *h, const Call &v, bool select_only, ViewInputs &in) {
     const bool host_in = v.in_kind == MVX_HOST;
-    const size_t chan_elem = v.mode == MODE_FEATURES ? (select_only ? 0 : (size_t)v.C * esz) : (v.mode == MODE_TYPES ? sizeof(int32_t) : 0);
-    const size_t rad_count = v.radii_type == MVX_RADII_ATOM ? (size_t)v.N : (v.radii_type == MVX_RADII_CHANNEL ? (size_t)v.C : 0);
-    const size_t xf_bytes = align_up((size_t)v.B * sizeof(mvx_xform), 16);
-    const size_t co_bytes = host_in ? align_up((size_t)v.N * 3 * sizeof(double), 16) : 0;
-    const size_t ch_bytes = host_in ? align_up((size_t)v.N * chan_elem, 16) : 0;
-    const size_t ra_bytes = host_in ? align_up(rad_count * esz, 16) : 0;
+    const ArrayBytes nb = array_bytes(v, v.N, h->cfg.precision == 64 ? sizeof(double) : sizeof(float), !select_only);
     in.xforms_host.assign(v.xforms, v.xforms + v.B);
     if (host_in) resolve_host_centers(in.xforms_host.data(), v.B);
-    PinnedSlot *slot = nullptr;
+    Call records = v;
+    records.xforms = in.xforms_host.data(); // (host poses: folded in just now)
     int rc;
-    if ((rc = acquire_slot(h, xf_bytes + co_bytes + ch_bytes + ra_bytes, &slot))) return rc;
-    if ((rc = ensure(h->view_xf, xf_bytes))) return rc;
-    std::memcpy(slot->p, in.xforms_host.data(), (size_t)v.B * sizeof(mvx_xform));
-    HIP_TRY(hipMemcpyAsync(h->view_xf.p, slot->p, (size_t)v.B * sizeof(mvx_xform), hipMemcpyHostToDevice, s));
-    if (!host_in && has_pose_records(v.xforms, v.B)) HIP_TRY(launch_pose_resolve(static_cast<mvx_xform *>(h->view_xf.p), v.B, s));
-    in.xforms = reinterpret_cast<const mvx_xform *>(h->view_xf.p);
-    in.coords = v.coords;
-    in.channels = v.channels;
-    in.radii = v.radii;
-    if (host_in) {
-        auto upload = [&](DevBuf &dst, const void *src, size_t used, char *staging, const void *&dev) -> int {
-            if (used == 0 || !src) return MVX_OK;
-            if (int e = ensure(dst, used)) return e;
-            std::memcpy(staging, src, used);
-            HIP_TRY(hipMemcpyAsync(dst.p, staging, used, hipMemcpyHostToDevice, s));
-            dev = dst.p;
-            return MVX_OK;
-        };
-        char *q = slot->p + xf_bytes;
-        const void *dev_coords = v.coords;
-        if ((rc = upload(h->in_coords, v.coords, (size_t)v.N * 3 * sizeof(double), q, dev_coords))) return rc;
-        in.coords = static_cast<const double *>(dev_coords);
-        if ((rc = upload(h->in_chan, v.channels, (size_t)v.N * chan_elem, q + co_bytes, in.channels))) return rc;
-        if ((rc = upload(h->in_radii, v.radii, rad_count * esz, q + co_bytes + ch_bytes, in.radii))) return rc;
-    }
-    HIP_TRY(hipEventRecord(slot->done, s));
-    slot->in_flight = true;
-    return MVX_OK;
+    if ((rc = stage_meta(h, h->view_xf, records, !host_in, host_in ? nb.padded() : 0, in))) return rc;
+    if (host_in && (rc = upload_arrays(h, nb, v.stream, in))) return rc;
+    return release_slot(in.slot, v.stream);
 }
 
 // Count, scan, one copy of the offsets to the host (THE synchronisation of a views call), fill. `index` / `capacity`: the
 // caller's buffer, or null: the handle's own (mvx_forward_views), grown to fit. Returns MVX_ERR_INVALID with the offsets filled
 // in when the caller's buffer is too small.
-int select_views(mvx_handle *h, const ViewCall &v, const ViewInputs &in, int64_t *index, int64_t capacity, bool own_index,
+int select_views(mvx_handle *h, const Call &v, const ViewInputs &in, int64_t *index, int64_t capacity, bool own_index,
                  int64_t *offsets_host) {
-    hipStream_t s = v.stream;
-    if (v.N == 0) {
-        std::fill(offsets_host, offsets_host + v.B + 1, (int64_t)0);
-        return MVX_OK;
-    }
+    hipStream_t s = v.stream; // (N > 0: the entries answer a cloud without atoms themselves)
     const int64_t ntiles64 = (v.N + VIEW_TILE - 1) / VIEW_TILE;
     const bool views_in_x = v.B >= ntiles64;
     if (std::min<int64_t>(v.B, ntiles64) > 65535 || (int64_t)v.B * ntiles64 >= (int64_t)1 << 31)
         return fail(MVX_ERR_INVALID, "too many (view, tile) pairs for one launch");
     ViewArgs a;
-    a.pa = prep_args(h, v.mode, v.radii_type, v.radius_scalar, v.B, v.C, v.N);
-    a.pa.coords = in.coords;
-    a.pa.radii = in.radii;
-    a.pa.types = v.mode == MODE_TYPES ? static_cast<const int32_t *>(in.channels) : nullptr;
-    a.pa.xforms = in.xforms;
+    a.pa = prep_args(h, v, v.N, in);
     a.ntiles = (int32_t)ntiles64;
     a.views_in_x = views_in_x ? 1 : 0;
     int rc;
@@ -1011,7 +1037,7 @@ int select_views(mvx_handle *h, const ViewCall &v, const ViewInputs &in, int64_t
     if ((rc = ensure(h->view_counts, M * sizeof(int32_t)))) return rc;
     if ((rc = ensure(h->view_base, M * sizeof(int64_t)))) return rc;
     if ((rc = ensure(h->view_off, off_bytes))) return rc;
-    PinnedSlot *slot = nullptr;
+    PinnedSlot *slot = nullptr; // (device to host, waited for below: nothing to release)
     if ((rc = acquire_slot(h, off_bytes, &slot))) return rc;
     HIP_TRY(launch_view_count(a, static_cast<int32_t *>(h->view_counts.p), s));
     HIP_TRY(launch_view_scan(static_cast<const int32_t *>(h->view_counts.p), v.B, a.ntiles, static_cast<int64_t *>(h->view_base.p),
@@ -1035,16 +1061,9 @@ inline int gather_width(size_t row_bytes, const void *a, const void *b) {
     return (bits & 15u) == 0 ? 16 : ((bits & 7u) == 0 ? 8 : 4);
 }
 
-// The compact batch of a selection: the rows `index` names, gathered by one launch into the handle's view_* buffers -
-// coordinates, feature rows or types, atom-wise radii (other radii stay where they are).
-struct ViewBatch {
-    const double *coords = nullptr;
-    const void *channels = nullptr;
-    const void *radii = nullptr;
-};
-
-int gather_views(mvx_handle *h, int mode, int C, int radii_type, const double *coords, const void *channels, const void *radii,
-                 const int64_t *index, int64_t total, hipStream_t s, ViewBatch &vb) {
+// The compact batch of a selection: the rows of the cloud (device arrays) that `index` names, gathered by one launch into the
+// handle's view_* buffers for `batch` - coordinates, feature rows or types, atom-wise radii (other radii stay where they are).
+int gather_views(mvx_handle *h, const Call &cloud, const int64_t *index, int64_t total, Call &batch) {
     const size_t esz = h->cfg.precision == 64 ? sizeof(double) : sizeof(float);
     GatherArgs g{};
     g.index = index;
@@ -1059,20 +1078,20 @@ int gather_views(mvx_handle *h, int mode, int C, int radii_type, const double *c
         return MVX_OK;
     };
     int rc;
-    if ((rc = add(h->view_coords, coords, 3 * sizeof(double)))) return rc;
-    vb.coords = static_cast<const double *>(h->view_coords.p);
-    vb.channels = channels;
-    if (mode != MODE_SINGLE) {
-        if ((size_t)C * esz > (size_t)1 << 30) return fail(MVX_ERR_INVALID, "too many channels");
-        if ((rc = add(h->view_chan, channels, mode == MODE_FEATURES ? (size_t)C * esz : sizeof(int32_t)))) return rc;
-        vb.channels = h->view_chan.p;
+    if ((rc = add(h->view_coords, cloud.coords, 3 * sizeof(double)))) return rc;
+    batch.coords = static_cast<const double *>(h->view_coords.p);
+    batch.channels = cloud.channels;
+    if (cloud.mode != MODE_SINGLE) {
+        if ((size_t)cloud.C * esz > (size_t)1 << 30) return fail(MVX_ERR_INVALID, "too many channels");
+        if ((rc = add(h->view_chan, cloud.channels, cloud.mode == MODE_FEATURES ? (size_t)cloud.C * esz : sizeof(int32_t)))) return rc;
+        batch.channels = h->view_chan.p;
     }
-    vb.radii = radii; // (scalar: unused; channel-wise: the C radii as they are)
-    if (radii_type == MVX_RADII_ATOM) {
-        if ((rc = add(h->view_radii, radii, esz))) return rc;
-        vb.radii = h->view_radii.p;
+    batch.radii = cloud.radii; // (scalar: unused; channel-wise: the C radii as they are)
+    if (cloud.radii_type == MVX_RADII_ATOM) {
+        if ((rc = add(h->view_radii, cloud.radii, esz))) return rc;
+        batch.radii = h->view_radii.p;
     }
-    HIP_TRY(launch_view_gather(g, s));
+    HIP_TRY(launch_view_gather(g, cloud.stream));
     return MVX_OK;
 }
 
@@ -1081,7 +1100,7 @@ int gather_views(mvx_handle *h, int mode, int C, int radii_type, const double *c
 int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types, const void *radii, double radius_scalar,
                      int32_t radii_type, int32_t mode, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                      int64_t *index_out, int64_t index_capacity, int64_t *offsets_out_host, int32_t in_kind, void *stream) {
-    ViewCall v{mode, coords, types, radii, radius_scalar, radii_type, N, C, xforms, B, in_kind, reinterpret_cast<hipStream_t>(stream)};
+    const Call v{mode, coords, types, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), in_kind};
     const char *own = !offsets_out_host ? "offsets_out_host must not be null"
                       : (index_capacity < 0 || (index_capacity > 0 && !index_out)) ? "index_out must not be null" : nullptr;
     if (int rc = validate_views(h, v, own)) return rc;
@@ -1089,10 +1108,9 @@ int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types, 
         std::fill(offsets_out_host, offsets_out_host + B + 1, (int64_t)0);
         return MVX_OK;
     }
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-    if (int rc = adopt_stream(h, v.stream)) return rc;
-    ViewInputs in;
+    CallScope scope(h, v.stream);
+    if (scope.rc) return scope.rc;
+    ViewInputs in(v);
     if (int rc = stage_views(h, v, true, in)) return rc;
     return select_views(h, v, in, index_out, index_capacity, false, offsets_out_host);
 }
@@ -1100,33 +1118,30 @@ int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types, 
 int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                       double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                       void *out, int32_t in_kind, int32_t out_kind, void *stream) {
-    ViewCall v{mode, coords, channels, radii, radius_scalar, radii_type, N, C, xforms, B, in_kind, reinterpret_cast<hipStream_t>(stream)};
+    const Call v{mode, coords, channels, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), in_kind};
     const char *own = (out_kind != MVX_HOST && out_kind != MVX_DEVICE) ? "bad memory kind"
                       : (B > 0 && !out) ? "out must not be null"
                       : (B > 0 && N > 0 && mode != MODE_SINGLE && !channels) ? "channels must not be null" : nullptr;
     if (int rc = validate_views(h, v, own)) return rc;
     if (B == 0) return MVX_OK;
     std::vector<int64_t> offsets((size_t)B + 1, 0);
-    RunArgs r{mode, coords, channels, radii, radius_scalar, radii_type, offsets.data(), xforms, B, C, out, in_kind, out_kind, v.stream};
+    RunArgs r{v, out, out_kind}; // the views as a batch of B molecules
+    r.offsets = offsets.data();
     if (N == 0) return run(h, r); // B molecules without atoms: zero grids
-    ViewInputs in;
+    ViewInputs in(v);
     {
-        DeviceGuard guard(h->device);
-        if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-        hipStream_t s = v.stream;
-        int rc;
-        if ((rc = adopt_stream(h, s))) return rc;
+        CallScope scope(h, v.stream);
+        int rc = scope.rc;
+        if (rc) return rc;
         if ((rc = stage_views(h, v, false, in))) return rc;
         if ((rc = select_views(h, v, in, nullptr, 0, true, offsets.data()))) return rc;
         const int64_t total = offsets[B];
         if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
-        ViewBatch vb;
-        if ((rc = gather_views(h, mode, C, radii_type, in.coords, in.channels, in.radii, static_cast<const int64_t *>(h->view_index.p),
-                               total, s, vb)))
-            return rc;
-        r.coords = vb.coords;
-        r.channels = vb.channels;
-        r.radii = vb.radii;
+        Call cloud = v; // ... as device arrays
+        cloud.coords = in.coords;
+        cloud.channels = in.channels;
+        cloud.radii = in.radii;
+        if ((rc = gather_views(h, cloud, static_cast<const int64_t *>(h->view_index.p), total, r))) return rc;
     }
     r.xforms = in.xforms_host.data();
     r.in_kind = MVX_DEVICE;
@@ -1150,260 +1165,290 @@ struct ScoreCall {
     double *atom_scores; // (total,) or null: handle-owned workspace
 };
 
-static int backward_impl(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
-                         double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
-                         int32_t C, const void *grad_out, double *grad_coords, void *grad_features, BackwardKind kind,
-                         double *grad_radii, double *grad_sigma, double *grad_rscalar, void *stream,
-                         const ScoreCall *score = nullptr) {
-    const bool with_radii = kind == BWD_RADII, with_density = kind == BWD_DENSITY;
-    // ---- what is checked before any device is touched ----
-    if (mode < MODE_FEATURES || mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
-    if (grad_features && mode != MODE_FEATURES) return fail(MVX_ERR_INVALID, "grad_features exists in features mode only");
-    if (C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
-    if (mode == MODE_SINGLE && C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
-    if (with_radii) { // (grad_coords and grad_features may both be null: grad_radii is an output)
-        if (!grad_radii) return fail(MVX_ERR_INVALID, "grad_radii must not be null");
-        if (radii_type == MVX_RADII_SCALAR)
+// What a backward call reads next to its Call and where its results go (outputs a kind does not have are null).
+struct GradOut {
+    BackwardKind kind;
+    const void *grad_out; // dL/dgrid; BWD_SCORE: the field
+    double *grad_coords;
+    void *grad_features;
+    double *grad_radii, *grad_sigma, *grad_rscalar;
+    ScoreCall score; // BWD_SCORE only
+};
+
+namespace {
+
+// ---- what is checked before any device is touched, up to the first rule that needs the atom count ----
+int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent &e) {
+    if (c.mode < MODE_FEATURES || c.mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
+    if (o.grad_features && c.mode != MODE_FEATURES) return fail(MVX_ERR_INVALID, "grad_features exists in features mode only");
+    if (c.C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
+    if (c.mode == MODE_SINGLE && c.C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
+    if (o.kind == BWD_RADII) { // (grad_coords and grad_features may both be null: grad_radii is an output)
+        if (!o.grad_radii) return fail(MVX_ERR_INVALID, "grad_radii must not be null");
+        if (c.radii_type == MVX_RADII_SCALAR)
             return fail(MVX_ERR_INVALID, "radii_type: scalar radii have no radius array for grad_radii (atom-wise or channel-wise radii only)");
-        if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE)
+        if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE)
             return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode (no grad_radii)");
-    } else if (with_density) { // (grad_coords and grad_features may both be null here too)
-        if (!grad_sigma && !grad_rscalar && !grad_radii)
+    } else if (o.kind == BWD_DENSITY) { // (grad_coords and grad_features may both be null here too)
+        if (!o.grad_sigma && !o.grad_rscalar && !o.grad_radii)
             return fail(MVX_ERR_INVALID, "grad_sigma, grad_radius_scalar and grad_radii are all null");
-        if (grad_rscalar && radii_type != MVX_RADII_SCALAR)
+        if (o.grad_rscalar && c.radii_type != MVX_RADII_SCALAR)
             return fail(MVX_ERR_INVALID, "radii_type: grad_radius_scalar exists with scalar radii only");
-        if (grad_radii && radii_type == MVX_RADII_SCALAR)
+        if (o.grad_radii && c.radii_type == MVX_RADII_SCALAR)
             return fail(MVX_ERR_INVALID, "radii_type: scalar radii have no radius array for grad_radii (grad_radius_scalar gives dL/dr)");
-        if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE)
+        if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE)
             return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode");
-    } else if (score) { // (grad_coords, grad_features and atom_scores may all be null: scores alone)
-        if (score->mol_stride < 0) return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
-        if (B > 0 && !score->scores) return fail(MVX_ERR_INVALID, "scores must not be null");
-    } else if (!grad_coords && !grad_features) {
+    } else if (o.kind == BWD_SCORE) { // (grad_coords, grad_features and atom_scores may all be null: scores alone)
+        if (o.score.mol_stride < 0) return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
+        if (c.B > 0 && !o.score.scores) return fail(MVX_ERR_INVALID, "scores must not be null");
+    } else if (!o.grad_coords && !o.grad_features) {
         return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
     }
-    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
-    if (radii_type < MVX_RADII_SCALAR || radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
-    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
-    if (B > 0 && !offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
-    if (B > 0 && offsets[0] != 0) return fail(MVX_ERR_INVALID, "offsets[0] must be 0");
-    for (int b = 0; b < B; ++b)
-        if (offsets[b + 1] < offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
+    if (c.B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (c.radii_type < MVX_RADII_SCALAR || c.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
+    if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
+    if (c.B > 0 && !c.offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
+    if (const char *bad = check_offsets(c.offsets, c.B, e)) return fail(MVX_ERR_INVALID, bad);
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    if (int prc = check_pose_records(xforms, B)) return prc; // (the first rule that reads the records)
-    const int64_t total = B > 0 ? offsets[B] : 0;
-    // (no atoms: no gradient rows; channel-wise radii still get their C zeros, sigma and a scalar radius their zero)
-    const bool radii_by_channel = grad_radii && radii_type == MVX_RADII_CHANNEL;
-    if (total == 0 && !radii_by_channel && !with_density && !(score && B > 0)) return MVX_OK;
-    if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
-    if (total == 0) {
-        DeviceGuard guard(h->device);
-        if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-        int rc = adopt_stream(h, s);
-        if (rc) return rc;
-        if (radii_by_channel) HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)C * sizeof(double), s));
-        if (grad_sigma) HIP_TRY(hipMemsetAsync(grad_sigma, 0, sizeof(double), s));
-        if (grad_rscalar) HIP_TRY(hipMemsetAsync(grad_rscalar, 0, sizeof(double), s));
-        if (score) HIP_TRY(hipMemsetAsync(score->scores, 0, (size_t)B * sizeof(double), s)); // (no atoms: every molecule scores 0)
-        return MVX_OK;
-    }
-    if (!coords || !grad_out) return fail(MVX_ERR_INVALID, score ? "coords / field must not be null" : "coords / grad_out must not be null");
-    if (mode != MODE_SINGLE && !channels) return fail(MVX_ERR_INVALID, "channels must not be null");
-    if (!radii && radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
-    const bool f64 = h->cfg.precision == 64, bf16 = h->cfg.grid_type == MVX_GRID_BF16;
-    const size_t gsz = bf16 ? 2 : (f64 ? 8 : 4);
+    return check_pose_records(c.xforms, c.B); // (the first rule that reads the records)
+}
+
+// ---- ... and what a call with atoms must bring ----
+int check_backward_arrays(const mvx_handle *h, const Call &c, const GradOut &o) {
+    const bool score = o.kind == BWD_SCORE;
+    if (!c.coords || !o.grad_out) return fail(MVX_ERR_INVALID, score ? "coords / field must not be null" : "coords / grad_out must not be null");
+    if (c.mode != MODE_SINGLE && !c.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
+    if (!c.radii && c.radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
+    const size_t gsz = h->cfg.grid_type == MVX_GRID_BF16 ? 2 : (h->cfg.precision == 64 ? 8 : 4);
     const size_t D = (size_t)h->g.D;
     if (D * D * D * gsz >= ((size_t)1 << 32)) return fail(MVX_ERR_INVALID, "one channel of the grid must stay below 4 GiB");
-    if (score && score->mol_stride != 0 && (uint64_t)score->mol_stride != (uint64_t)C * D * D * D)
+    if (score && o.score.mol_stride != 0 && (uint64_t)o.score.mol_stride != (uint64_t)c.C * D * D * D)
         return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
-
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc = adopt_stream(h, s);
-    if (rc) return rc;
-
-    // offsets (+ transforms) through a pinned slot, as the forward stages them
-    const size_t off_bytes = align_up((size_t)(B + 1) * sizeof(int64_t), 16);
-    const size_t xf_bytes = xforms ? (size_t)B * sizeof(mvx_xform) : 0;
-    PinnedSlot *slot = nullptr;
-    if ((rc = acquire_slot(h, off_bytes + xf_bytes, &slot))) return rc;
-    if ((rc = ensure(h->grad_meta, off_bytes + xf_bytes))) return rc;
-    std::memcpy(slot->p, offsets, (size_t)(B + 1) * sizeof(int64_t));
-    if (xforms) std::memcpy(slot->p + off_bytes, xforms, xf_bytes);
-    HIP_TRY(hipMemcpyAsync(h->grad_meta.p, slot->p, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
-    if (has_pose_records(xforms, B)) // (this entry takes device arrays only: the poses are device memory)
-        HIP_TRY(launch_pose_resolve(reinterpret_cast<mvx_xform *>((char *)h->grad_meta.p + off_bytes), B, s));
-    const int64_t *d_offsets = reinterpret_cast<const int64_t *>(h->grad_meta.p);
-    const mvx_xform *d_xforms = xforms ? reinterpret_cast<const mvx_xform *>((char *)h->grad_meta.p + off_bytes) : nullptr;
-
-    if ((rc = ensure(h->grad_rec, (size_t)total * sizeof(AtomRec)))) return rc;
-    if ((rc = ensure(h->grad_xp, (size_t)total * sizeof(uint2)))) return rc;
-    const bool gauss = h->cfg.density == MVX_GAUSSIAN;
-    const bool chanwise = radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES;
-    void *d_rmax = nullptr;
-    double *d_Tc = nullptr;
-    void *d_kc = nullptr;
-    if (chanwise) { // [max radius | per-channel thresholds | per-channel coefficients]
-        const size_t tc_off = 16, kc_off = tc_off + align_up((size_t)C * sizeof(double), 16);
-        if ((rc = ensure(h->grad_aux, kc_off + (size_t)C * sizeof(double)))) return rc;
-        d_rmax = h->grad_aux.p;
-        d_Tc = reinterpret_cast<double *>((char *)h->grad_aux.p + tc_off);
-        d_kc = (char *)h->grad_aux.p + kc_off;
-        HIP_TRY(launch_grad_chan(radii, C, f64, gauss, h->sigma32, h->cfg.sigma, d_rmax, d_Tc, d_kc, s));
-    }
-
-    // the forward's pre-pass: positions, thresholds, coefficients and admitted ranges of every atom, bit for bit
-    PrepArgs pa = prep_args(h, mode, radii_type, radius_scalar, B, C, total);
-    pa.coords = coords;
-    pa.radii = radii;
-    pa.types = mode == MODE_TYPES ? static_cast<const int32_t *>(channels) : nullptr;
-    pa.features = nullptr; // (no packed weights: the gradient kernel reads the feature rows in place)
-    pa.Cpad = C;
-    pa.offsets = d_offsets;
-    pa.xforms = d_xforms;
-    pa.chan_aux = d_rmax;
-    pa.rec = reinterpret_cast<AtomRec *>(h->grad_rec.p);
-    pa.wbuf = nullptr;
-    pa.xp = reinterpret_cast<uint2 *>(h->grad_xp.p);
-    HIP_TRY(launch_prep(pa, s));
-
-    // "grad_order" 1: neighbouring atoms in neighbouring waves of one XCD, so that the rows of G they read meet in its L2
-    // (the order decides which wave runs an atom, never what the atom's gradients are)
-    const uint32_t *order = nullptr;
-    int32_t xcd_span = 0;
-    if (h->grad_order) {
-        const size_t ob = grad_order_bytes(total, B, h->g.D);
-        if ((rc = ensure(h->grad_sort, ob))) return rc;
-        HIP_TRY(launch_grad_order(pa.rec, d_offsets, B, total, h->g.D, h->grad_sort.p, h->grad_sort.cap, &order, s));
-        xcd_span = (int32_t)(((total + 3) / 4 + 7) / 8);
-    }
-
-    GradArgs ga;
-    ga.rec = pa.rec;
-    ga.w = mode == MODE_FEATURES ? channels : nullptr;
-    ga.g = grad_out;
-    ga.offsets = d_offsets;
-    ga.xforms = d_xforms;
-    ga.Tc = d_Tc;
-    ga.kc = d_kc;
-    ga.grad_coords = grad_coords;
-    ga.grad_w = grad_features;
-    ga.order = order;
-    ga.xcd_span = xcd_span;
-    ga.total = total;
-    ga.B = B;
-    ga.C = C;
-    ga.D = h->g.D;
-    ga.res = h->g.res;
-    ga.half = h->g.half;
-    const int32_t grid_kind = bf16 ? 1 : (f64 ? 2 : 0);
-    if (kind == BWD_PLAIN) {
-        HIP_TRY(launch_grad(ga, mode, grid_kind, gauss, chanwise, s));
-    } else if (kind == BWD_SCORE) {
-        // one walk over the field: the per-atom scores (the caller's array, or workspace), dS/dcoords and dS/dfeatures where
-        // asked for; then every molecule's atoms summed in a fixed order
-        ScoreArgs sa;
-        sa.atom_scores = score->atom_scores;
-        sa.mol_stride = score->mol_stride;
-        if (!sa.atom_scores) {
-            if ((rc = ensure(h->score_atoms, (size_t)total * sizeof(double)))) return rc;
-            sa.atom_scores = reinterpret_cast<double *>(h->score_atoms.p);
-        }
-        HIP_TRY(launch_score(ga, sa, mode, grid_kind, gauss, chanwise, s));
-        HIP_TRY(launch_score_reduce(sa.atom_scores, d_offsets, B, score->scores, s));
-    } else if (!gauss) { // binary density: zero radius and sigma gradients (the a.e. derivative), the walk for the other outputs only
-        if (grad_radii)
-            HIP_TRY(hipMemsetAsync(grad_radii, 0, (size_t)(radii_type == MVX_RADII_CHANNEL ? C : total) * sizeof(double), s));
-        if (grad_sigma) HIP_TRY(hipMemsetAsync(grad_sigma, 0, sizeof(double), s));
-        if (grad_rscalar) HIP_TRY(hipMemsetAsync(grad_rscalar, 0, sizeof(double), s));
-        if (grad_coords || grad_features) HIP_TRY(launch_grad(ga, mode, grid_kind, gauss, chanwise, s));
-    } else if (with_density) {
-        // The radius walk with its partials kept per atom (or per channel and atom) in grad_rpart, whatever the radii type:
-        // [partials | channel-wise: stage sums of grad_radii_reduce, C doubles for a grad_radii nobody asked for | the chunk
-        // sums of all atoms]. One walk feeds grad_radii, grad_sigma and grad_rscalar.
-        const bool by_channel = radii_type == MVX_RADII_CHANNEL;
-        const size_t npart = chanwise ? (size_t)C * (size_t)total : (size_t)total;
-        const size_t part_bytes = align_up(npart * sizeof(double), 256);
-        const size_t rstage_bytes = by_channel ? align_up((grad_radii_stage_doubles(total, C) + (size_t)C) * sizeof(double), 256) : 0;
-        if ((rc = ensure(h->grad_rpart, part_bytes + rstage_bytes + grad_density_stage_doubles(total) * sizeof(double)))) return rc;
-        RadiiArgs ra;
-        ra.radii = radii;
-        ra.grad_radii = nullptr;
-        ra.part = reinterpret_cast<double *>(h->grad_rpart.p);
-        double *rstage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes);
-        double *dstage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes + rstage_bytes);
-        // sigma and the scalar radius as the forward used them
-        const double sigma = f64 ? h->cfg.sigma : (double)h->sigma32;
-        const double rsc = f64 ? radius_scalar : (double)(float)radius_scalar;
-        HIP_TRY(launch_grad_radii(ga, ra, mode, grid_kind, chanwise, s));
-        if (by_channel && (grad_radii || chanwise)) { // (features: grad_sigma needs the stage sums of this reduction)
-            double *gr = grad_radii ? grad_radii : rstage + grad_radii_stage_doubles(total, C);
-            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(channels), radii,
-                                             chanwise ? d_kc : nullptr, f64, total, C, rstage, gr, s));
-        }
-        if (chanwise) {
-            if (grad_sigma) HIP_TRY(launch_grad_density_chan(rstage, total, C, d_kc, f64, sigma, grad_sigma, s));
-        } else if (grad_sigma || grad_rscalar || !by_channel) {
-            HIP_TRY(launch_grad_density_sum(ra.part, total, radii, f64, by_channel ? nullptr : grad_radii, rsc, sigma, dstage,
-                                            grad_sigma, grad_rscalar, s));
-        }
-    } else {
-        // radius partials: straight into grad_radii (one radius per atom), or per atom / per (channel, atom) into grad_rpart
-        // and reduced over all atoms of the call in a fixed order (channel-wise radii: one radius vector for the batch)
-        RadiiArgs ra;
-        ra.radii = radii;
-        ra.grad_radii = grad_radii;
-        ra.part = nullptr;
-        double *stage = nullptr;
-        if (radii_type == MVX_RADII_CHANNEL) {
-            const size_t npart = chanwise ? (size_t)C * (size_t)total : (size_t)total;
-            const size_t part_bytes = align_up(npart * sizeof(double), 256);
-            if ((rc = ensure(h->grad_rpart, part_bytes + grad_radii_stage_doubles(total, C) * sizeof(double)))) return rc;
-            ra.part = reinterpret_cast<double *>(h->grad_rpart.p);
-            stage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes);
-        }
-        HIP_TRY(launch_grad_radii(ga, ra, mode, grid_kind, chanwise, s));
-        if (radii_type == MVX_RADII_CHANNEL)
-            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(channels), radii,
-                                             chanwise ? d_kc : nullptr, f64, total, C, stage, grad_radii, s));
-    }
-    HIP_TRY(hipEventRecord(slot->done, s));
-    slot->in_flight = true;
     return MVX_OK;
 }
+
+// zeros for `nradii` radius gradients, for sigma and for a scalar radius, where the call has these outputs
+int zero_density_grads(const GradOut &o, size_t nradii, hipStream_t s) {
+    if (o.grad_radii && nradii) HIP_TRY(hipMemsetAsync(o.grad_radii, 0, nradii * sizeof(double), s));
+    if (o.grad_sigma) HIP_TRY(hipMemsetAsync(o.grad_sigma, 0, sizeof(double), s));
+    if (o.grad_rscalar) HIP_TRY(hipMemsetAsync(o.grad_rscalar, 0, sizeof(double), s));
+    return MVX_OK;
+}
+
+// ---- no atoms: no gradient rows; channel-wise radii still get their C zeros, sigma and a scalar radius their zero ----
+int backward_no_atoms(const Call &c, const GradOut &o) {
+    if (int rc = zero_density_grads(o, c.radii_type == MVX_RADII_CHANNEL ? (size_t)c.C : 0, c.stream)) return rc;
+    if (o.kind == BWD_SCORE) HIP_TRY(hipMemsetAsync(o.score.scores, 0, (size_t)c.B * sizeof(double), c.stream)); // (every molecule scores 0)
+    return MVX_OK;
+}
+
+// One backward call with atoms, once it is on the device: what its steps share, the staging, and one step per BackwardKind.
+struct Backward {
+    mvx_handle *h;
+    const Call &c;
+    const GradOut &o;
+    const int64_t total;
+    const hipStream_t s = c.stream;
+    const bool f64 = h->cfg.precision == 64, gauss = h->cfg.density == MVX_GAUSSIAN;
+    const bool chanwise = c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES;
+    const int32_t grid_kind = h->cfg.grid_type == MVX_GRID_BF16 ? 1 : (f64 ? 2 : 0);
+    void *d_kc = nullptr; // channel-wise features: the per-channel coefficients (ga.kc)
+    DeviceInputs in{c};   // the caller's arrays; stage(): the device copy of offsets and records, the slot they went through
+    GradArgs ga;
+    Backward(mvx_handle *h_, const Call &c_, const GradOut &o_, int64_t total_) : h(h_), c(c_), o(o_), total(total_) {}
+    // ---- staging, channel-wise tables and the forward's pre-pass: the records of every atom, bit for bit ----
+    int stage() {
+        int rc; // (offsets and records through a pinned slot, as the forward stages them; the poses are device memory)
+        if ((rc = stage_meta(h, h->grad_meta, c, true, 0, in))) return rc;
+        if ((rc = ensure(h->grad_rec, (size_t)total * sizeof(AtomRec)))) return rc;
+        if ((rc = ensure(h->grad_xp, (size_t)total * sizeof(uint2)))) return rc;
+        void *d_rmax = nullptr;
+        double *d_Tc = nullptr;
+        if (chanwise) {
+            if ((rc = ensure(h->grad_aux, chan_kc_off(c.C) + (size_t)c.C * sizeof(double)))) return rc;
+            d_rmax = h->grad_aux.p;
+            d_Tc = reinterpret_cast<double *>((char *)h->grad_aux.p + CHAN_TC_OFF);
+            d_kc = (char *)h->grad_aux.p + chan_kc_off(c.C);
+            HIP_TRY(launch_grad_chan(c.radii, c.C, f64, gauss, h->sigma32, h->cfg.sigma, d_rmax, d_Tc, d_kc, s));
+        }
+        PrepArgs pa = prep_args(h, c, total, in); // (no packed weights: the gradient kernel reads the feature rows in place)
+        pa.Cpad = c.C;
+        pa.chan_aux = d_rmax;
+        pa.rec = reinterpret_cast<AtomRec *>(h->grad_rec.p);
+        pa.wbuf = nullptr;
+        pa.xp = reinterpret_cast<uint2 *>(h->grad_xp.p);
+        HIP_TRY(launch_prep(pa, s));
+
+        // "grad_order" 1: neighbouring atoms in neighbouring waves of one XCD, so that the rows of G they read meet in its L2
+        // (the order decides which wave runs an atom, never what the atom's gradients are)
+        ga.order = nullptr;
+        ga.xcd_span = 0;
+        if (h->grad_order) {
+            const size_t ob = grad_order_bytes(total, c.B, h->g.D);
+            if ((rc = ensure(h->grad_sort, ob))) return rc;
+            HIP_TRY(launch_grad_order(pa.rec, in.offsets, c.B, total, h->g.D, h->grad_sort.p, h->grad_sort.cap, &ga.order, s));
+            ga.xcd_span = (int32_t)(((total + 3) / 4 + 7) / 8);
+        }
+        ga.rec = pa.rec;
+        ga.w = c.mode == MODE_FEATURES ? c.channels : nullptr;
+        ga.g = o.grad_out;
+        ga.offsets = in.offsets;
+        ga.xforms = in.xforms;
+        ga.Tc = d_Tc;
+        ga.kc = d_kc;
+        ga.grad_coords = o.grad_coords;
+        ga.grad_w = o.grad_features;
+        ga.total = total;
+        ga.B = c.B;
+        ga.C = c.C;
+        ga.D = h->g.D;
+        ga.res = h->g.res;
+        ga.half = h->g.half;
+        return MVX_OK;
+    }
+
+    int plain() { // BWD_PLAIN
+        HIP_TRY(launch_grad(ga, c.mode, grid_kind, gauss, chanwise, s));
+        return MVX_OK;
+    }
+    // BWD_SCORE: one walk over the field: the per-atom scores (the caller's array, or workspace), dS/dcoords and dS/dfeatures
+    // where asked for; then every molecule's atoms summed in a fixed order
+    int score() {
+        ScoreArgs sa;
+        sa.atom_scores = o.score.atom_scores;
+        sa.mol_stride = o.score.mol_stride;
+        if (!sa.atom_scores) {
+            if (int rc = ensure(h->score_atoms, (size_t)total * sizeof(double))) return rc;
+            sa.atom_scores = reinterpret_cast<double *>(h->score_atoms.p);
+        }
+        HIP_TRY(launch_score(ga, sa, c.mode, grid_kind, gauss, chanwise, s));
+        HIP_TRY(launch_score_reduce(sa.atom_scores, in.offsets, c.B, o.score.scores, s));
+        return MVX_OK;
+    }
+    // binary density: zero radius and sigma gradients (the a.e. derivative), the walk for the other outputs only
+    int binary() {
+        if (int rc = zero_density_grads(o, (size_t)(c.radii_type == MVX_RADII_CHANNEL ? c.C : total), s)) return rc;
+        return (o.grad_coords || o.grad_features) ? plain() : MVX_OK;
+    }
+    // bytes of the radius partials, one per atom or per (channel, atom), in front of the stage sums in grad_rpart
+    size_t part_bytes() const { return align_up((chanwise ? (size_t)c.C * (size_t)total : (size_t)total) * sizeof(double), 256); }
+    // BWD_DENSITY: the radius walk with its partials kept per atom (or per channel and atom) in grad_rpart, whatever the radii
+    // type: [partials | channel-wise: stage sums of grad_radii_reduce, C doubles for a grad_radii nobody asked for | the chunk
+    // sums of all atoms]. One walk feeds grad_radii, grad_sigma and grad_rscalar.
+    int density() {
+        if (!gauss) return binary();
+        const bool by_channel = c.radii_type == MVX_RADII_CHANNEL;
+        const size_t rstage_bytes = by_channel ? align_up((grad_radii_stage_doubles(total, c.C) + (size_t)c.C) * sizeof(double), 256) : 0;
+        if (int rc = ensure(h->grad_rpart, part_bytes() + rstage_bytes + grad_density_stage_doubles(total) * sizeof(double))) return rc;
+        RadiiArgs ra;
+        ra.radii = c.radii;
+        ra.grad_radii = nullptr;
+        ra.part = reinterpret_cast<double *>(h->grad_rpart.p);
+        double *rstage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes());
+        double *dstage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes() + rstage_bytes);
+        // sigma and the scalar radius as the forward used them
+        const double sigma = f64 ? h->cfg.sigma : (double)h->sigma32;
+        const double rsc = f64 ? c.radius_scalar : (double)(float)c.radius_scalar;
+        HIP_TRY(launch_grad_radii(ga, ra, c.mode, grid_kind, chanwise, s));
+        if (by_channel && (o.grad_radii || chanwise)) { // (features: grad_sigma needs the stage sums of this reduction)
+            double *gr = o.grad_radii ? o.grad_radii : rstage + grad_radii_stage_doubles(total, c.C);
+            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(c.channels), c.radii,
+                                             chanwise ? d_kc : nullptr, f64, total, c.C, rstage, gr, s));
+        }
+        if (chanwise) {
+            if (o.grad_sigma) HIP_TRY(launch_grad_density_chan(rstage, total, c.C, d_kc, f64, sigma, o.grad_sigma, s));
+        } else if (o.grad_sigma || o.grad_rscalar || !by_channel) {
+            HIP_TRY(launch_grad_density_sum(ra.part, total, c.radii, f64, by_channel ? nullptr : o.grad_radii, rsc, sigma, dstage,
+                                            o.grad_sigma, o.grad_rscalar, s));
+        }
+        return MVX_OK;
+    }
+    // BWD_RADII: radius partials straight into grad_radii (one radius per atom), or per atom / per (channel, atom) into
+    // grad_rpart and reduced over all atoms of the call in a fixed order (channel-wise radii: one radius vector for the batch)
+    int radii() {
+        if (!gauss) return binary();
+        RadiiArgs ra;
+        ra.radii = c.radii;
+        ra.grad_radii = o.grad_radii;
+        ra.part = nullptr;
+        double *stage = nullptr;
+        if (c.radii_type == MVX_RADII_CHANNEL) {
+            if (int rc = ensure(h->grad_rpart, part_bytes() + grad_radii_stage_doubles(total, c.C) * sizeof(double))) return rc;
+            ra.part = reinterpret_cast<double *>(h->grad_rpart.p);
+            stage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes());
+        }
+        HIP_TRY(launch_grad_radii(ga, ra, c.mode, grid_kind, chanwise, s));
+        if (c.radii_type == MVX_RADII_CHANNEL)
+            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(c.channels), c.radii,
+                                             chanwise ? d_kc : nullptr, f64, total, c.C, stage, o.grad_radii, s));
+        return MVX_OK;
+    }
+};
+
+int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
+    Extent e;
+    int rc = check_backward(h, c, o, e);
+    if (rc) return rc;
+    const bool radii_by_channel = o.grad_radii && c.radii_type == MVX_RADII_CHANNEL;
+    if (e.total == 0 && !radii_by_channel && o.kind != BWD_DENSITY && !(o.kind == BWD_SCORE && c.B > 0)) return MVX_OK;
+    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (e.total > 0 && (rc = check_backward_arrays(h, c, o))) return rc;
+    CallScope scope(h, c.stream);
+    if (scope.rc) return scope.rc;
+    if (e.total == 0) return backward_no_atoms(c, o);
+    Backward b(h, c, o, e.total);
+    if ((rc = b.stage())) return rc;
+    switch (o.kind) {
+    case BWD_PLAIN: rc = b.plain(); break;
+    case BWD_SCORE: rc = b.score(); break;
+    case BWD_RADII: rc = b.radii(); break;
+    case BWD_DENSITY: rc = b.density(); break;
+    }
+    return rc ? rc : release_slot(b.in.slot, c.stream);
+}
+
+// what is wrong with the offsets of a selection handed back by the caller (B + 1 entries), or null
+const char *bad_view_offsets(const int64_t *offsets, int32_t B, Extent &e) {
+    if (!offsets) return "offsets_host must not be null with an index";
+    if (const char *bad = check_offsets(offsets, B, e)) return bad;
+    return e.too_many() ? "too many atoms: offsets[B] must stay below 2^31" : nullptr;
+}
+
+} // namespace
 
 int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                        double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                        int32_t C, const void *grad_out, double *grad_coords, void *grad_features, void *stream) {
-    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
-                         grad_features, BWD_PLAIN, nullptr, nullptr, nullptr, stream);
+    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+                         {BWD_PLAIN, grad_out, grad_coords, grad_features, nullptr, nullptr, nullptr, {}});
 }
 
 int mvx_backward_radii_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                              double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                              int32_t C, const void *grad_out, double *grad_coords, void *grad_features, double *grad_radii,
                              void *stream) {
-    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
-                         grad_features, BWD_RADII, grad_radii, nullptr, nullptr, stream);
+    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+                         {BWD_RADII, grad_out, grad_coords, grad_features, grad_radii, nullptr, nullptr, {}});
 }
 
 int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                                double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                                int32_t C, const void *grad_out, double *grad_coords, void *grad_features, double *grad_radii,
                                double *grad_sigma, double *grad_radius_scalar, void *stream) {
-    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, grad_out, grad_coords,
-                         grad_features, BWD_DENSITY, grad_radii, grad_sigma, grad_radius_scalar, stream);
+    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+                         {BWD_DENSITY, grad_out, grad_coords, grad_features, grad_radii, grad_sigma, grad_radius_scalar, {}});
 }
 
 int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                     double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B, int32_t C,
                     const void *field, int64_t field_mol_stride, double *scores, double *atom_scores, double *grad_coords,
                     void *grad_features, void *stream) {
-    const ScoreCall sc{field_mol_stride, scores, atom_scores};
-    return backward_impl(h, mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, field, grad_coords,
-                         grad_features, BWD_SCORE, nullptr, nullptr, nullptr, stream, &sc);
+    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+                         {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_mol_stride, scores, atom_scores}});
 }
 
 int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_coords, const int64_t *offsets,
@@ -1413,97 +1458,78 @@ int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_
     if (B > 0 && !grad_pose) return fail(MVX_ERR_INVALID, "grad_pose must not be null");
     if (B > 0 && !xforms) return fail(MVX_ERR_INVALID, "xforms must not be null");
     if (B > 0 && !offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
-    if (B > 0 && offsets[0] != 0) return fail(MVX_ERR_INVALID, "offsets[0] must be 0");
-    for (int b = 0; b < B; ++b)
-        if (offsets[b + 1] < offsets[b]) return fail(MVX_ERR_INVALID, "offsets must be non-decreasing");
-    const int64_t total = B > 0 ? offsets[B] : 0;
-    if (total > 0 && (!coords || !grad_coords)) return fail(MVX_ERR_INVALID, "coords / grad_coords must not be null");
+    Extent e;
+    if (const char *bad = check_offsets(offsets, B, e)) return fail(MVX_ERR_INVALID, bad);
+    if (e.total > 0 && (!coords || !grad_coords)) return fail(MVX_ERR_INVALID, "coords / grad_coords must not be null");
     for (int b = 0; b < B; ++b)
         if (!(xforms[b].flags & MVX_XF_POSE_PTR)) return fail(MVX_ERR_INVALID, "every record must be a MVX_XF_POSE_PTR record");
     if (int prc = check_pose_records(xforms, B)) return prc;
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
     if (B == 0) return MVX_OK;
 
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc = adopt_stream(h, s);
-    if (rc) return rc;
+    Call c{}; // (what stage_meta reads)
+    c.offsets = offsets;
+    c.xforms = xforms;
+    c.B = B;
+    c.stream = reinterpret_cast<hipStream_t>(stream);
+    c.in_kind = MVX_DEVICE;
+    CallScope scope(h, c.stream);
+    if (scope.rc) return scope.rc;
     // offsets and records through a pinned slot, as the backward entries stage them (the records stay as they are: the
     // kernel reads each pose through its pointer)
-    const size_t off_bytes = align_up((size_t)(B + 1) * sizeof(int64_t), 16);
-    const size_t xf_bytes = (size_t)B * sizeof(mvx_xform);
-    PinnedSlot *slot = nullptr;
-    if ((rc = acquire_slot(h, off_bytes + xf_bytes, &slot))) return rc;
-    if ((rc = ensure(h->pose_meta, off_bytes + xf_bytes))) return rc;
-    std::memcpy(slot->p, offsets, (size_t)(B + 1) * sizeof(int64_t));
-    std::memcpy(slot->p + off_bytes, xforms, xf_bytes);
-    HIP_TRY(hipMemcpyAsync(h->pose_meta.p, slot->p, off_bytes + xf_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_pose_grad(coords, grad_coords, reinterpret_cast<const int64_t *>(h->pose_meta.p),
-                             reinterpret_cast<const mvx_xform *>((char *)h->pose_meta.p + off_bytes), B, grad_pose, s));
-    HIP_TRY(hipEventRecord(slot->done, s));
-    slot->in_flight = true;
-    return MVX_OK;
-}
-
-// what is wrong with the offsets of a selection handed back by the caller (B + 1 entries), or null
-static const char *bad_view_offsets(const int64_t *offsets, int32_t B) {
-    if (!offsets) return "offsets_host must not be null with an index";
-    if (offsets[0] != 0) return "offsets[0] must be 0";
-    for (int b = 0; b < B; ++b)
-        if (offsets[b + 1] < offsets[b]) return "offsets must be non-decreasing";
-    if (offsets[B] >= (int64_t)1 << 31) return "too many atoms: offsets[B] must stay below 2^31";
-    return nullptr;
+    DeviceInputs in;
+    if (int rc = stage_meta(h, h->pose_meta, c, false, 0, in)) return rc;
+    HIP_TRY(launch_pose_grad(coords, grad_coords, in.offsets, in.xforms, B, grad_pose, c.stream));
+    return release_slot(in.slot, c.stream);
 }
 
 int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                     double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                     const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
                     double *scores, double *atom_scores, double *grad_coords, void *grad_features, void *stream) {
-    ViewCall v{mode, coords, channels, radii, radius_scalar, radii_type, N, C, xforms, B, MVX_DEVICE, reinterpret_cast<hipStream_t>(stream)};
+    const Call v{mode, coords, channels, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), MVX_DEVICE};
     // ---- what is checked before any device is touched ----
     const bool per_row = atom_scores || grad_coords || grad_features;
+    Extent e; // of the caller's selection
     const char *own = nullptr;
     if (grad_features && mode != MODE_FEATURES) own = "grad_features exists in features mode only";
     else if (field_view_stride < 0) own = "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)";
     else if (B > 0 && !scores) own = "scores must not be null";
     else if (!index && per_row)
         own = "atom_scores, grad_coords and grad_features need an index: their rows are laid out in selection order (mvx_select_views)";
-    else if (index && B > 0) own = bad_view_offsets(offsets_host, B);
+    else if (index && B > 0) own = bad_view_offsets(offsets_host, B, e);
     if (!own && B > 0 && N > 0) {
         if (mode == MODE_FEATURES && !channels) own = "channels must not be null";
-        else if (!field && (!index || offsets_host[B] > 0)) own = "field must not be null";
+        else if (!field && (!index || e.total > 0)) own = "field must not be null";
     }
     if (int rc = validate_views(h, v, own)) return rc;
     if (field_view_stride != 0 && (uint64_t)field_view_stride != (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D)
         return fail(MVX_ERR_INVALID, "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)");
     if (B == 0) return MVX_OK;
-    const ScoreCall sc{field_view_stride, scores, atom_scores};
+    // the compact batch through the walk of mvx_score_batch: the records as the caller gave them (device centres and poses)
+    Call batch = v;
+    batch.coords = nullptr;
+    batch.channels = batch.radii = nullptr;
+    batch.offsets = offsets_host;
     std::vector<int64_t> own_offsets;
-    const int64_t *offsets = offsets_host;
-    ViewBatch vb;
     if (N == 0 || !index) { // (N == 0: B views without atoms score 0, whatever the caller's selection says)
         own_offsets.assign((size_t)B + 1, 0);
-        offsets = own_offsets.data();
+        batch.offsets = own_offsets.data();
     }
     if (N > 0) {
-        DeviceGuard guard(h->device);
-        if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-        hipStream_t s = v.stream;
-        int rc;
-        if ((rc = adopt_stream(h, s))) return rc;
+        CallScope scope(h, v.stream);
+        int rc = scope.rc;
+        if (rc) return rc;
         if (!index) { // the selection itself: one stream synchronisation
-            ViewInputs in;
+            ViewInputs in(v);
             if ((rc = stage_views(h, v, true, in))) return rc;
             if ((rc = select_views(h, v, in, nullptr, 0, true, own_offsets.data()))) return rc;
             if (own_offsets[B] >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
             index = static_cast<const int64_t *>(h->view_index.p);
         }
-        if ((rc = gather_views(h, mode, C, radii_type, coords, channels, radii, index, offsets[B], s, vb))) return rc;
+        if ((rc = gather_views(h, v, index, batch.offsets[B], batch))) return rc;
     }
-    // the compact batch through the walk of mvx_score_batch: the records as the caller gave them (device centres and poses)
-    return backward_impl(h, mode, vb.coords, vb.channels, vb.radii, radius_scalar, radii_type, offsets, xforms, B, C, field,
-                         grad_coords, grad_features, BWD_SCORE, nullptr, nullptr, nullptr, stream, &sc);
+    return backward_impl(h, batch, {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_view_stride, scores, atom_scores}});
 }
 
 int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets_host, int32_t B, int64_t N, const void *rows,
@@ -1513,35 +1539,31 @@ int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets
     if (width <= 0 || width > VIEW_REDUCE_MAX_WIDTH) return fail(MVX_ERR_INVALID, "width must be > 0 (and at most 65535 * 32)");
     if (row_type != MVX_ROW_FLOAT && row_type != MVX_ROW_DOUBLE) return fail(MVX_ERR_INVALID, "bad row_type");
     if (N >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+    Extent e;
     if (B > 0)
-        if (const char *bad = bad_view_offsets(offsets_host, B)) return fail(MVX_ERR_INVALID, bad);
-    const int64_t total = B > 0 ? offsets_host[B] : 0;
-    if (total > 0 && (!index || !rows)) return fail(MVX_ERR_INVALID, "index / rows must not be null");
+        if (const char *bad = bad_view_offsets(offsets_host, B, e)) return fail(MVX_ERR_INVALID, bad);
+    if (e.total > 0 && (!index || !rows)) return fail(MVX_ERR_INVALID, "index / rows must not be null");
     if (N > 0 && !out) return fail(MVX_ERR_INVALID, "out must not be null");
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
     if (N == 0) return MVX_OK;
 
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    int rc = adopt_stream(h, s);
-    if (rc) return rc;
+    Call c{}; // (what stage_meta reads)
+    c.offsets = offsets_host;
+    c.B = B;
+    c.stream = reinterpret_cast<hipStream_t>(stream);
+    c.in_kind = MVX_DEVICE;
+    CallScope scope(h, c.stream);
+    if (scope.rc) return scope.rc;
     const bool f64 = row_type == MVX_ROW_DOUBLE;
-    if (total == 0) { // no view holds an atom: exact zeros
-        HIP_TRY(hipMemsetAsync(out, 0, (size_t)N * (size_t)width * (f64 ? sizeof(double) : sizeof(float)), s));
+    if (e.total == 0) { // no view holds an atom: exact zeros
+        HIP_TRY(hipMemsetAsync(out, 0, (size_t)N * (size_t)width * (f64 ? sizeof(double) : sizeof(float)), c.stream));
         return MVX_OK;
     }
     // the offsets through a pinned slot, as the backward entries stage theirs
-    const size_t off_bytes = (size_t)(B + 1) * sizeof(int64_t);
-    PinnedSlot *slot = nullptr;
-    if ((rc = acquire_slot(h, off_bytes, &slot))) return rc;
-    if ((rc = ensure(h->view_red_off, off_bytes))) return rc;
-    std::memcpy(slot->p, offsets_host, off_bytes);
-    HIP_TRY(hipMemcpyAsync(h->view_red_off.p, slot->p, off_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(launch_view_reduce(index, static_cast<const int64_t *>(h->view_red_off.p), B, N, rows, width, f64, out, s));
-    HIP_TRY(hipEventRecord(slot->done, s));
-    slot->in_flight = true;
-    return MVX_OK;
+    DeviceInputs in;
+    if (int rc = stage_meta(h, h->view_red_off, c, false, 0, in)) return rc;
+    HIP_TRY(launch_view_reduce(index, in.offsets, B, N, rows, width, f64, out, c.stream));
+    return release_slot(in.slot, c.stream);
 }
 
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,
@@ -1549,36 +1571,28 @@ int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const m
     if (!h || !xform || (N > 0 && (!coords || !out))) return fail(MVX_ERR_INVALID, "null argument");
     if (int prc = check_pose_records(xform, 1)) return prc;
     if (N <= 0) return MVX_OK;
-    DeviceGuard guard(h->device);
-    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (int rc0 = adopt_stream(h, s)) return rc0;
-    const size_t xf_bytes = align_up(sizeof(mvx_xform), 16);
+    Call c{}; // (what stage_meta reads: one record, no offsets)
+    c.xforms = xform;
+    c.B = 1;
+    c.stream = s;
+    c.in_kind = in_kind;
+    CallScope scope(h, s);
+    if (scope.rc) return scope.rc;
     const size_t co_bytes = (size_t)N * 3 * sizeof(double);
     const bool host_in = in_kind == MVX_HOST, host_out = out_kind == MVX_HOST;
-    PinnedSlot *slot = nullptr;
-    int rc = acquire_slot(h, xf_bytes + (host_in ? co_bytes : 0), &slot);
+    DeviceInputs in;
+    int rc = stage_meta(h, h->xf_buf, c, true, host_in ? co_bytes : 0, in);
     if (rc) return rc;
-    if ((rc = ensure(h->xf_buf, xf_bytes))) return rc;
-    std::memcpy(slot->p, xform, sizeof(mvx_xform));
-    if (host_in) resolve_host_centers(reinterpret_cast<mvx_xform *>(slot->p), 1);
-    HIP_TRY(hipMemcpyAsync(h->xf_buf.p, slot->p, xf_bytes, hipMemcpyHostToDevice, s));
-    if (!host_in && has_pose_records(xform, 1)) HIP_TRY(launch_pose_resolve(static_cast<mvx_xform *>(h->xf_buf.p), 1, s));
     const double *d_in = coords;
-    if (host_in) {
-        if ((rc = ensure(h->in_coords, co_bytes))) return rc;
-        std::memcpy(slot->p + xf_bytes, coords, co_bytes);
-        HIP_TRY(hipMemcpyAsync(h->in_coords.p, slot->p + xf_bytes, co_bytes, hipMemcpyHostToDevice, s));
-        d_in = reinterpret_cast<const double *>(h->in_coords.p);
-    }
+    if (host_in && (rc = upload(h->in_coords, coords, co_bytes, in.rest, s, d_in))) return rc;
     double *d_out = out;
     if (host_out) {
         if ((rc = ensure(h->out_stage, co_bytes))) return rc;
         d_out = reinterpret_cast<double *>(h->out_stage.p);
     }
-    HIP_TRY(launch_transform(d_in, N, reinterpret_cast<const mvx_xform *>(h->xf_buf.p), d_out, s));
-    HIP_TRY(hipEventRecord(slot->done, s));
-    slot->in_flight = true;
+    HIP_TRY(launch_transform(d_in, N, in.xforms, d_out, s));
+    if ((rc = release_slot(in.slot, s))) return rc;
     if (host_out) {
         HIP_TRY(hipMemcpyAsync(out, d_out, co_bytes, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));

@@ -1,4 +1,4 @@
-// Internal declarations shared by the kernel TU (mvx_kernels.hip) and the C-ABI TU (mvx_capi.hip).
+// Internal declarations shared by the kernel translation units (one .hip file per kernel family) and the C-ABI one (mvx_capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

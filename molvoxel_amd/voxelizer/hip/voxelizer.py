@@ -656,15 +656,8 @@ class Voxelizer(BaseVoxelizer):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         B = offsets.shape[0] - 1
         assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
-        if channels is None:
-            kind, C_ = None, 1
-        elif channels.ndim == 1:
-            kind = "types"
-            C_ = num_channels if num_channels is not None else (
-                radii.shape[0] if self.is_radii_type_channel_wise else int(channels.max()) + 1)
-        else:
-            kind, C_ = "features", channels.shape[1]
-        self._check_args_batch(coords, channels, kind, radii, int(C_))
+        kind, C_ = self._batch_kind(channels, radii, num_channels)
+        self._check_args_batch(coords, channels, kind, radii, C_)
         grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, radii,
                                  out_grid, rten)
         user_centers = centers  # (a conversion made below, for autograd or for the ABI, is "fresh")
@@ -678,21 +671,12 @@ class Voxelizer(BaseVoxelizer):
         fresh = self.overlap_prepass and in_kind == _lib.MVX_DEVICE and (
             c is not coords or (kind == "features" and ch is not channels) or (r is not None and r is not radii)
             or (kind == "types" and self._types_fresh))
-        if kind == "types" and self.is_radii_type_channel_wise and r.shape[0] < C_:
-            # channel-wise radii are indexed by type only; pad so the (C,) contract of the ABI holds (as forward_types)
-            pad = int(C_) - r.shape[0]
-            r = torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])
-            fresh = fresh or self.overlap_prepass
-        fresh = fresh or (self.overlap_prepass and fresh_inputs and in_kind == _lib.MVX_DEVICE)
-        if xforms is not None:  # forward_views on a differentiable voxelizer: the records it drew for its views
-            xfs, dev_cen = xforms
-            need_xf = True
-        else:
-            need_xf = centers is not None or random_rotation or (random_translation and random_translation > 0.0)
-            xfs, dev_cen = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep) if need_xf else (None, None)
-            if dev_cen is not None:
-                fresh = fresh or (self.overlap_prepass and dev_cen.data_ptr() != user_centers.data_ptr())
-        xf_ptr = C.addressof(xfs) if need_xf else None
+        r, padded = self._pad_type_radii(r, kind, C_)
+        fresh = fresh or (self.overlap_prepass and (padded or (fresh_inputs and in_kind == _lib.MVX_DEVICE)))
+        xfs, dev_cen = self._call_xforms(B, centers, in_kind, random_translation, random_rotation, keep, xforms)
+        if xforms is None and dev_cen is not None:
+            fresh = fresh or (self.overlap_prepass and dev_cen.data_ptr() != user_centers.data_ptr())
+        xf_ptr = None if xfs is None else C.addressof(xfs)
         if out_grid is None:
             out_grid = self.get_empty_grid(C_, batch_size=B)
         assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
@@ -705,11 +689,11 @@ class Voxelizer(BaseVoxelizer):
         rt = self._radii_type_code()
         if kind == "features":
             launch = lambda: self._lib.mvx_forward_features_batch(  # noqa: E731
-                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, int(C_),
+                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, C_,
                 self._ptr(buf), in_kind, out_kind, self._stream())
         elif kind == "types":
             launch = lambda: self._lib.mvx_forward_types_batch(  # noqa: E731
-                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, int(C_),
+                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, C_,
                 self._ptr(buf), in_kind, out_kind, self._stream())
         else:
             assert not self.is_radii_type_channel_wise, "Channel-Wise Radii Type is not supported"
@@ -718,10 +702,46 @@ class Voxelizer(BaseVoxelizer):
                 self._stream())
         if grad:
             return self._autograd(launch, ret, kind or "single", c, ch if kind == "features" else None,
-                                  dev_cen, ch if kind == "types" else None, r, rs, offsets,
-                                  xfs if need_xf else None, B, int(C_), rten, pose)
+                                  dev_cen, ch if kind == "types" else None, r, rs, offsets, xfs, B, C_, rten, pose)
         _lib.check(launch())
         return self._finish_out(buf, ret, how)
+
+    def _batch_kind(self, channels, radii, num_channels):
+        """(kind, C) of a batch or views call from its channels: None -> single, (sumN,) int -> types, (sumN, C) -> features."""
+        if channels is None:
+            return None, 1
+        if channels.ndim != 1:
+            return "features", int(channels.shape[1])
+        if num_channels is not None:
+            return "types", int(num_channels)
+        return "types", int(radii.shape[0] if self.is_radii_type_channel_wise else int(channels.max()) + 1)
+
+    def _pad_type_radii(self, r, kind, C_):
+        """Channel-wise radii are indexed by type only: padded with ones so that the (C,) contract of the ABI holds (as
+        forward_types). Returns (radii, whether a new array was made)."""
+        if not (kind == "types" and self.is_radii_type_channel_wise and r.shape[0] < C_):
+            return r, False
+        pad = C_ - r.shape[0]
+        return (torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])), True
+
+    def _call_xforms(self, B, centers, in_kind, random_translation, random_rotation, keep, xforms):
+        """The records of a batch call as (records or None, device centres or None). xforms: the pair the caller drew already
+        (forward_views on a differentiable voxelizer, the posed forms) instead of new ones."""
+        if xforms is not None:
+            return xforms
+        if centers is not None or random_rotation or (random_translation and random_translation > 0.0):
+            return self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
+        return None, None
+
+    def _device_coords(self, coords):
+        """coords on this voxelizer's device (the score entries take device arrays only): host arrays are moved there."""
+        if self._on_device(coords):
+            return coords
+        return (coords.detach() if _is_torch(coords) else torch.as_tensor(np.asarray(coords, dtype=np.float64))).to(self.device)
+
+    def _field_tensor(self, field):
+        """The field of a score call as the library reads it: on this device, of the grid's dtype, contiguous."""
+        return (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
 
     def _make_xforms(self, B, centers, in_kind, random_translation, random_rotation, keep):
         """B mvx_xform records, one per molecule (forward_batch) or view (forward_views): centring + the random transform,
@@ -776,24 +796,16 @@ class Voxelizer(BaseVoxelizer):
         if self._sigma_src is not None:
             self._sync_sigma()
         radii, rten = self._scalar_radius(radii)
-        if channels is None:
-            kind, C_ = None, 1
-        elif channels.ndim == 1:
-            kind = "types"
-            C_ = num_channels if num_channels is not None else (
-                radii.shape[0] if self.is_radii_type_channel_wise else int(channels.max()) + 1)
-        else:
-            kind, C_ = "features", channels.shape[1]
-        self._check_args_batch(coords, channels, kind, radii, int(C_))
+        kind, C_ = self._batch_kind(channels, radii, num_channels)
+        self._check_args_batch(coords, channels, kind, radii, C_)
         assert centers is not None and centers.ndim == 2 and centers.shape[1] == 3, (
             f"centers does not match dimension: {tuple(getattr(centers, 'shape', ()))} vs ('B', 3)")
-        return kind, int(C_), radii, rten
+        return kind, C_, radii, rten
 
     def _views_inputs(self, coords, channels, kind, radii, C_):
         c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
-        if kind == "types" and self.is_radii_type_channel_wise and r.shape[0] < C_:  # (as forward_batch: the (C,) contract of the ABI)
-            pad = C_ - r.shape[0]
-            r = torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])
+        r, padded = self._pad_type_radii(r, kind, C_)
+        if padded:
             keep.append(r)
         return c, ch, r, in_kind, keep
 
@@ -1026,32 +1038,16 @@ class Voxelizer(BaseVoxelizer):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         B = offsets.shape[0] - 1
         assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
-        if channels is None:
-            kind, C_ = None, 1
-        elif channels.ndim == 1:
-            kind = "types"
-            C_ = num_channels if num_channels is not None else (
-                radii.shape[0] if self.is_radii_type_channel_wise else int(channels.max()) + 1)
-        else:
-            kind, C_ = "features", channels.shape[1]
-        C_ = int(C_)
+        kind, C_ = self._batch_kind(channels, radii, num_channels)
         self._check_args_batch(coords, channels, kind, radii, C_)
         per_mol = self._check_args_score(field, B, C_)
         grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, None, None)
         if grad and centers is not None:
             centers = self._grad_center(centers)
-        if not self._on_device(coords):  # this entry takes device arrays only
-            coords = (coords.detach() if _is_torch(coords) else torch.as_tensor(np.asarray(coords, dtype=np.float64))).to(self.device)
-        c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
-        if kind == "types" and self.is_radii_type_channel_wise and r.shape[0] < C_:
-            r = torch.cat([r, r.new_ones(C_ - r.shape[0])])  # (as forward_batch: radii are indexed by type only)
-        if xforms is not None:
-            xfs, dev_cen = xforms
-            need_xf = True
-        else:
-            need_xf = centers is not None or random_rotation or (random_translation and random_translation > 0.0)
-            xfs, dev_cen = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep) if need_xf else (None, None)
-        F = (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
+        c, ch, r, in_kind, keep = self._prepare_inputs(self._device_coords(coords), channels, kind, radii)
+        r, _ = self._pad_type_radii(r, kind, C_)
+        xfs, dev_cen = self._call_xforms(B, centers, in_kind, random_translation, random_rotation, keep, xforms)
+        F = self._field_tensor(field)
         rs = float(radii) if _np_isscalar(radii) else 0.0
         N = c.shape[0]
         mode = kind or "single"
@@ -1065,7 +1061,7 @@ class Voxelizer(BaseVoxelizer):
             gf = torch.empty((N, C_), dtype=self._tfp, device=self.device) if need_gf else None
             _lib.check(self._lib.mvx_score_batch(
                 self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
-                offsets.ctypes.data, C.addressof(xfs) if need_xf else None, B, C_, self._ptr(F),
+                offsets.ctypes.data, None if xfs is None else C.addressof(xfs), B, C_, self._ptr(F),
                 C_ * self.dimension ** 3 if per_mol else 0, self._ptr(scores), self._ptr(atoms), self._ptr(gc), self._ptr(gf),
                 self._stream()))
             return scores, atoms, gc, gf
@@ -1073,7 +1069,7 @@ class Voxelizer(BaseVoxelizer):
         if not grad:
             scores, atoms, _, _ = call()
             return (scores, atoms) if per_atom else scores
-        spec = dict(offsets=offsets, xforms=xfs if need_xf else None, B=B)
+        spec = dict(offsets=offsets, xforms=xfs, B=B)
         cen = dev_cen if (_is_torch(dev_cen) and self._on_device(dev_cen)) else None
         out = _ScoreFunction.apply(self, call, spec, per_atom, c, feat, cen, pose)
         return out if per_atom else out[0]
@@ -1141,15 +1137,13 @@ class Voxelizer(BaseVoxelizer):
         per_view = self._check_args_score(field, B, C_)
         pose = self._pack_pose(B, centers, posed[0], posed[1], True) if posed is not None else None
         grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, None, None)
-        if not self._on_device(coords):  # this entry takes device arrays only
-            coords = (coords.detach() if _is_torch(coords) else torch.as_tensor(np.asarray(coords, dtype=np.float64))).to(self.device)
-        c, ch, r, in_kind, keep = self._views_inputs(coords, channels, kind, cradii, C_)
+        c, ch, r, in_kind, keep = self._views_inputs(self._device_coords(coords), channels, kind, cradii, C_)
         if pose is None:
             xfs, dev_cen = self._make_xforms(B, self._grad_center(centers) if grad else centers, in_kind, random_translation,
                                              random_rotation, keep)
         else:
             xfs, dev_cen = self._pose_xforms(pose, B), None
-        F = (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
+        F = self._field_tensor(field)
         rs = float(cradii) if _np_isscalar(cradii) else 0.0
         N = int(c.shape[0])
         mode = kind or "single"
@@ -1317,6 +1311,24 @@ class Voxelizer(BaseVoxelizer):
         return do_random_transform(coords, center, random_translation, random_rotation)
 
 
+def _row_upstream(gs, ga, lengths, total):
+    """dL/ds of every saved row of a score call: dL/dS of the row's molecule (view) plus, with per_atom, dL/ds_n."""
+    up = torch.zeros(total, dtype=torch.float64, device=lengths.device)
+    if gs is not None:
+        up = torch.repeat_interleave(gs.to(torch.float64), lengths, output_size=total)
+    if ga is not None:
+        up = up + ga.to(torch.float64)
+    return up
+
+
+def _center_grad(g, cen, lengths):
+    """p = M (coords - center) + t: dL/dcenter = -sum of dL/dcoords over the molecule. lengths: the molecules' atom counts on
+    g's device, or None: all rows belong to the one centre."""
+    if lengths is None:
+        return -g.sum(0).reshape(cen.shape)
+    return -torch.segment_reduce(g, "sum", lengths=lengths, axis=0).reshape(cen.shape)
+
+
 if torch is not None:
 
     class _VoxelizeFunction(torch.autograd.Function):
@@ -1341,12 +1353,9 @@ if torch is not None:
             like = lambda g, t: None if g is None else g.to(dtype=t.dtype).reshape(t.shape).to(t.device)  # noqa: E731
             gsig, grs = like(gsig, ctx.scalars[0]), like(grs, ctx.scalars[1])
             gcen = None
-            if need_cen:  # p = M (coords - center) + t: dL/dcenter = -sum of dL/dcoords over the molecule
-                if cen.numel() == 3:
-                    gcen = -gc.sum(0).reshape(cen.shape)
-                else:
-                    lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
-                    gcen = -torch.segment_reduce(gc, "sum", lengths=lengths, axis=0).reshape(cen.shape)
+            if need_cen:
+                gcen = _center_grad(gc, cen, None if cen.numel() == 3 else
+                                    torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device))
             # explicit poses: the per-atom gradients reduced to dL/dc, dL/dq, dL/dt per molecule (autograd splits the block)
             gpose = ctx.vox._pose_backward(ctx.spec, c, gc) if need_pose else None
             return None, None, None, None, gc if need_c else None, gf, gcen, gr, gsig, grs, gpose
@@ -1371,21 +1380,11 @@ if torch is not None:
         def backward(ctx, gs, ga=None):
             c, cen, pose, gc, gf = ctx.saved_tensors
             need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[4:8]
-            N = gc.shape[0]
             lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
-            up = torch.zeros(N, dtype=torch.float64, device=gc.device)  # dL/ds_n
-            if gs is not None:
-                up = torch.repeat_interleave(gs.to(torch.float64), lengths, output_size=N)
-            if ga is not None:
-                up = up + ga.to(torch.float64)
+            up = _row_upstream(gs, ga, lengths, gc.shape[0])
             gcs = gc * up[:, None]
             gfs = (gf * up[:, None].to(gf.dtype)) if (need_f and gf is not None) else None
-            gcen = None
-            if need_cen:
-                if cen.numel() == 3:
-                    gcen = -gcs.sum(0).reshape(cen.shape)
-                else:
-                    gcen = -torch.segment_reduce(gcs, "sum", lengths=lengths, axis=0).reshape(cen.shape)
+            gcen = _center_grad(gcs, cen, None if cen.numel() == 3 else lengths) if need_cen else None
             gpose = ctx.vox._pose_backward(ctx.spec, c, gcs) if need_pose else None
             return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose
 
@@ -1411,22 +1410,15 @@ if torch is not None:
             c, cen, pose, gc, gf, index = ctx.saved_tensors
             need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[4:8]
             vox, spec = ctx.vox, ctx.spec
-            total = gc.shape[0]
             # (through pinned memory: a pageable copy would synchronise the stream)
             lengths = torch.from_numpy(np.diff(spec["offsets"])).pin_memory().to(gc.device, non_blocking=True)
-            up = torch.zeros(total, dtype=torch.float64, device=gc.device)  # dL/ds of every (view, atom) row
-            if gs is not None:
-                up = torch.repeat_interleave(gs.to(torch.float64), lengths, output_size=total)
-            if ga is not None:
-                up = up + ga.to(torch.float64)
+            up = _row_upstream(gs, ga, lengths, gc.shape[0])  # dL/ds of every (view, atom) row
             gcs = gc * up[:, None]
             gcoords = vox.views_reduce(gcs, index, spec["offsets"], spec["N"]) if need_c else None
             gfeat = None
             if need_f and gf is not None:
                 gfeat = vox.views_reduce(gf * up[:, None].to(gf.dtype), index, spec["offsets"], spec["N"])
-            gcen = None
-            if need_cen:
-                gcen = -torch.segment_reduce(gcs, "sum", lengths=lengths, axis=0).reshape(cen.shape)
+            gcen = _center_grad(gcs, cen, lengths) if need_cen else None
             gpose = vox._pose_backward(spec, c[index], gcs) if need_pose else None
             return None, None, None, None, gcoords, gfeat, gcen, gpose
 
