@@ -47,7 +47,7 @@
 extern "C" {
 #endif
 
-#define MVX_VERSION 140 /* 0.1.4: mvx_score_views and mvx_views_reduce (additive: scores of many views of one shared cloud and the reduction of their rows onto its atoms); MVX_XF_POSE_PTR, MVX_XF_TRANSLATE_ONCE and mvx_pose_grad_batch (additive: explicit rigid poses and their gradients); mvx_select_views and mvx_forward_views (additive: many views of one shared cloud); mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
+#define MVX_VERSION 140 /* 0.1.4: mvx_forward_sum_batch (additive: one summed grid per batch); mvx_score_views and mvx_views_reduce (additive: scores of many views of one shared cloud and the reduction of their rows onto its atoms); MVX_XF_POSE_PTR, MVX_XF_TRANSLATE_ONCE and mvx_pose_grad_batch (additive: explicit rigid poses and their gradients); mvx_select_views and mvx_forward_views (additive: many views of one shared cloud); mvx_backward_density_batch (additive: sigma and scalar-radius gradients); mvx_config.grid_type (bfloat16 grids) and mvx_plan_call_grid (additive); mvx_plan_call (the decision table as a pure function), channel-wise radii grouped per chunk of 32 channels, narrow chunks in candidate pairs; 0.1.3: one voxelize launch per batched call, channel-wise radii grouped on the device; 0.1.2: mvx_xform.center_ptr, stream hand-over, unaligned out, mvx_debug_set_option */
 
 typedef enum mvx_status {
     MVX_OK = 0,
@@ -368,6 +368,41 @@ int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const voi
                     double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
                     int32_t B, int32_t C, const void *field, int64_t field_mol_stride,
                     double *scores, double *atom_scores, double *grad_coords, mvx_real *grad_features, void *stream);
+
+/*
+ * ONE grid for a whole batch (no counterpart in the reference): the sum, weighted or not, of the B grids the forward entries
+ * would write for the same arguments, without those grids. With rho and w as for mvx_backward_batch and the atoms
+ * n = 0 .. sumN-1 in the caller's order (molecule boundaries from offsets, a transform per molecule):
+ *   out[c, v] = sum over n, in that order, of u[n,c] rho_{n,c}(v)
+ *   u[n,c] = w[n,c], or float32(atom_weights[n] * w[n,c]) with atom_weights (one float per atom, any sign)
+ * The sum is the float32 fma(u, rho, acc) chain the forward kernels run inside one molecule, continued across the molecule
+ * boundaries, starting from 0 (accumulate == 0: out is fully overwritten; B == 0 or no atoms writes zeros) or from the value
+ * already in out (accumulate == 1: out is read and updated; B == 0 or no atoms leaves it untouched). rho is the forward's
+ * membership and density value bit for bit, so: an unweighted call whose molecules are only centred gives the bits of the
+ * per-molecule forward on the one merged molecule concat_b(coords_b - c_b); a weighted features call the bits of the
+ * unweighted call on the rows scaled in float32; a call split at a molecule boundary into two calls, the second accumulating,
+ * the bits of the one call.
+ *   out: (C, D, D, D) float32, NCDHW contiguous and 16-byte aligned, whatever the handle's grid_type / layout (a bfloat16
+ *        partial sum could not be reloaded exactly). mode: 0 features, 1 types, 2 single (C = 1).
+ * Deterministic: one workgroup per (output slab, chunk of 32 channels) walks the molecules' candidate lines of its slab one
+ * after another with the accumulators in registers and writes once; no atomics, and no split of the molecules over
+ * workgroups - the bits depend on the atom order alone, never on the launch shape or on how the batch is cut. Molecule
+ * chunks: the pre-pass workspace is cut as the forward cuts it (Infinity Cache budget, "chunks" / "mall_budget_kb" options);
+ * chunk k > 0 continues the sums chunk k - 1 wrote. Workspace: the forward's pre-pass buffers, with weight rows padded to whole
+ * chunks of 32 channels (feature rows of such a width and without atom_weights are read in place).
+ * Device pointers except offsets / xforms (host; MVX_XF_CENTER_PTR and MVX_XF_POSE_PTR records included), exactly as in
+ * mvx_backward_batch. Asynchronous on `stream`.
+ * MVX_ERR_INVALID before any device is touched for what mvx_backward_batch rejects for these arguments (a bad mode, C <= 0,
+ * single mode with C != 1, B < 0, a bad radii_type, channel-wise radii in single mode, NULL or non-monotone offsets, a NULL
+ * handle, a bad pose record, NULL arrays with atoms present), a NULL out, accumulate outside {0, 1}, an out that is not
+ * 16-byte aligned, and for the four configurations the kernel does not serve, each named in the message: a precision-64
+ * handle; channel-wise radii with features; a dimension that is no multiple of 4; a blockdim that needs per-lane ranges
+ * (mvx_plan.lane_range = 1).
+ */
+int mvx_forward_sum_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                          double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                          int32_t B, int32_t C, const float *atom_weights /* (sumN,) or NULL */,
+                          float *out /* (C, D, D, D) */, int32_t accumulate, void *stream);
 
 /*
  * Gradients with respect to explicit rigid poses (MVX_XF_POSE_PTR records; no counterpart in the reference): the reduction of

@@ -8,6 +8,7 @@
 #include "mvx_internal.h"
 #include "mvx_plan.h"
 #include "mvx_pose.h"
+#include "mvx_sum.h"
 #include "mvx_views.h"
 
 #include <algorithm>
@@ -242,6 +243,12 @@ struct Call {
 struct RunArgs : Call {
     void *out;
     int out_kind;
+};
+
+// mvx_forward_sum_batch: what a forward call that sums its molecules into ONE (C, D, D, D) float32 grid brings next to its RunArgs
+struct SumCall {
+    const float *atom_weights; // (sumN,) device, or null
+    bool accumulate;           // the sums start from the values in `out`
 };
 
 // Orders this call after the previous call's work when the caller switched streams (see mvx_handle::last_stream).
@@ -514,7 +521,8 @@ struct Forward {
     mvx_handle *h;
     const RunArgs &r;
     const Extent ext;
-    const bool f64 = h->cfg.precision == 64, bf16 = h->cfg.grid_type == MVX_GRID_BF16, gauss = h->cfg.density == MVX_GAUSSIAN;
+    const SumCall *const sum; // not null: one summed float32 NCDHW grid (mvx_forward_sum_batch) instead of B grids
+    const bool f64 = h->cfg.precision == 64, bf16 = !sum && h->cfg.grid_type == MVX_GRID_BF16, gauss = h->cfg.density == MVX_GAUSSIAN;
     const bool chanwise = r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_FEATURES;
     const size_t esz = f64 ? sizeof(double) : sizeof(float); // element size of features, radii and the grid (but bfloat16 grids: 2)
     // make_plan:
@@ -537,14 +545,14 @@ struct Forward {
     PrepArgs pa{};
     VoxArgs va{};
     bool lr_blocks = false, lane_range = false;
-    Forward(mvx_handle *h_, const RunArgs &r_, const Extent &e) : h(h_), r(r_), ext(e) {}
+    Forward(mvx_handle *h_, const RunArgs &r_, const Extent &e, const SumCall *sum_ = nullptr) : h(h_), r(r_), ext(e), sum(sum_) {}
     hipStream_t staging_stream() const { return overlap ? pre : s; }
     // ---- how this call is executed: one pure function of its shape (mvx_plan.hip, pinned by tests/test_plan.py) ----
     int make_plan() {
         const Geom &g = h->g;
         const size_t D = (size_t)g.D;
         if (bf16 && (reinterpret_cast<uintptr_t>(r.out) & 1u)) return fail(MVX_ERR_INVALID, "a bfloat16 grid must be 2-byte aligned");
-        out_bytes = (size_t)r.B * r.C * D * D * D * (bf16 ? sizeof(uint16_t) : esz);
+        out_bytes = (size_t)(sum ? 1 : r.B) * r.C * D * D * D * (bf16 ? sizeof(uint16_t) : esz);
         d_out = r.out;
         if (r.out_kind == MVX_HOST) {
             if (int rc = ensure(h->out_stage, out_bytes)) return rc;
@@ -560,11 +568,24 @@ struct Forward {
         q.C = r.C;
         // (a bfloat16 grid's vector store is 8 bytes: mvx_plan_call_grid)
         // channels-last grids (C > 1; one channel IS the contiguous layout): 16-byte channel runs for either element type
-        ndhwc = h->layout == MVX_LAYOUT_NDHWC && !f64 && r.C > 1;
+        ndhwc = !sum && h->layout == MVX_LAYOUT_NDHWC && !f64 && r.C > 1;
         q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & ((bf16 && !ndhwc) ? 7u : 15u)) == 0 ? 1 : 0;
         q.total_atoms = ext.total;
         q.max_atoms = ext.max_atoms;
         plan = plan_call(q, h->knobs, ndhwc ? MVX_LAYOUT_NDHWC : MVX_LAYOUT_NCDHW, bf16 ? 2 : 4);
+        if (sum) {
+            // The summed grid: the binned pipeline with chunks of 32 channels on the matrix-core walk whatever C is - the plan of
+            // a features call of ceil(C / 32) whole chunks (no remainder launch, no one-launch route) - over weight rows zero
+            // padded to whole chunks. Feature rows that already are that wide and carry no per-atom weight are read in place.
+            PlanKnobs k = h->knobs;
+            k.direct_mode = 0;
+            k.max_ct = 32;
+            q.mode = MODE_FEATURES;
+            if (q.radii_type == MVX_RADII_CHANNEL) q.radii_type = MVX_RADII_ATOM; // (radii[types]: one radius per atom, no grouped launch)
+            q.C = (r.C + 31) / 32 * 32;
+            plan = plan_call(q, k, MVX_LAYOUT_NCDHW, 4);
+            if (r.mode != MODE_FEATURES || q.C != r.C || sum->atom_weights) plan.weights_in_place = 0;
+        }
         h->last_plan = plan;
         h->has_plan = true;
         const bool forced_pipeline = h->knobs.pipeline > 1 && r.B >= 4 * h->knobs.pipeline;
@@ -572,7 +593,7 @@ struct Forward {
         // under the previous call's voxelize launches. Device-resident inputs and outputs only.
         // Batches only (mvx.h: "the batched three-launch path"): a per-molecule call hands over arrays its Python layer may
         // have converted on the caller's stream a moment ago, which the side stream would not wait for.
-        overlap = h->overlap && plan.route != MVX_ROUTE_DIRECT && r.B > 1 && plan.nchunk == 1 && !forced_pipeline &&
+        overlap = !sum && h->overlap && plan.route != MVX_ROUTE_DIRECT && r.B > 1 && plan.nchunk == 1 && !forced_pipeline &&
                   r.in_kind == MVX_DEVICE && r.out_kind == MVX_DEVICE;
         if (overlap) h->cur ^= 1;
         w = &h->ws[h->cur];
@@ -751,6 +772,8 @@ struct Forward {
             pa.first = r.offsets[b0];
             pa.total = r.offsets[b1];
             HIP_TRY(launch_prep(pa, pre));
+            if (sum && sum->atom_weights) // u[n, c] = fl32(a_n * w[n, c]): the packed rows of this chunk's atoms, scaled in place
+                HIP_TRY(launch_scale_rows(static_cast<float *>(pa.wbuf), sum->atom_weights, pa.first, pa.total, pa.Cpad, pre));
             HIP_TRY(launch_xbin(pa.xp, in.offsets, ext.total, b0, b1 - b0, ext.max_atoms, plan.nsx, plan.nsy, plan.nzc, plan.nw, xlist, slist,
                                 slist + nslabs * SLAB_LINE_ENTRIES, pre));
             if (side_stream) HIP_TRY(hipEventRecord(overlap ? w->ev_pre : h->ev_pre[k], pre));
@@ -768,6 +791,10 @@ struct Forward {
                 if (interleave && (rc = prepass(k))) return rc;
                 if (side_stream) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
                 va.p.b0 = b0;
+                if (sum) { // one launch per molecule chunk; chunk k > 0 continues the sums chunk k - 1 wrote
+                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize_sum(va, b1 - b0, gauss, sum->accumulate || k > 0, s); }))) return rc;
+                    continue;
+                }
                 if (plan.grouped) {
                     // channels grouped by radius (chan_aux_kernel): chunks of 32 channels on the matrix-core path, one
                     // threshold test and one density per radius slot and candidate, feature rows read in place
@@ -808,13 +835,12 @@ struct Forward {
     }
 };
 
-int run(mvx_handle *h, const RunArgs &r) {
-    Extent ext;
-    int rc = validate(h, r, ext);
-    if (rc || r.B == 0) return rc;
+// The steps of a forward call that passed its checks and has molecules; sum: the call writes one summed grid (SumCall).
+int run_checked(mvx_handle *h, const RunArgs &r, const Extent &ext, const SumCall *sum) {
+    int rc;
     CallScope scope(h, r.stream);
     if (scope.rc) return scope.rc;
-    Forward f(h, r, ext); // (each step reads what the steps before it set: see the members' comments)
+    Forward f(h, r, ext, sum); // (each step reads what the steps before it set: see the members' comments)
     if ((rc = f.make_plan())) return rc;
     if ((rc = f.order_prepass())) return rc;
     if (f.by_value) f.in = DeviceInputs(r); // nothing to stage: extent and transform travel with the launches
@@ -824,6 +850,61 @@ int run(mvx_handle *h, const RunArgs &r) {
     f.kernel_args();
     if ((rc = f.plan.route == MVX_ROUTE_DIRECT ? f.launch_direct() : f.launch_binned())) return rc;
     return f.finish();
+}
+
+int run(mvx_handle *h, const RunArgs &r) {
+    Extent ext;
+    int rc = validate(h, r, ext);
+    if (rc || r.B == 0) return rc;
+    return run_checked(h, r, ext, nullptr);
+}
+
+// ---- mvx_forward_sum_batch: its own checks (those of the backward entries for the same arguments, in their order, then what
+// the summed kernel does not serve), the calls without atoms, then the forward's steps with a SumCall ----
+int run_sum(mvx_handle *h, const RunArgs &r, int32_t accumulate, const float *atom_weights) {
+    if (r.mode < MODE_FEATURES || r.mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
+    if (r.C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
+    if (r.mode == MODE_SINGLE && r.C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
+    if (!r.out) return fail(MVX_ERR_INVALID, "out must not be null");
+    if (accumulate != 0 && accumulate != 1) return fail(MVX_ERR_INVALID, "accumulate must be 0 or 1");
+    if (r.B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (r.radii_type < MVX_RADII_SCALAR || r.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
+    if (r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
+    if (r.B > 0 && !r.offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
+    Extent e;
+    if (const char *bad = check_offsets(r.offsets, r.B, e)) return fail(MVX_ERR_INVALID, bad);
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (int rc = check_pose_records(r.xforms, r.B)) return rc;
+    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (e.total > 0) {
+        if (!r.coords) return fail(MVX_ERR_INVALID, "coords must not be null");
+        if (r.mode != MODE_SINGLE && !r.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
+        if (!r.radii && r.radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
+    }
+    if (h->cfg.precision == 64) return fail(MVX_ERR_INVALID, "forward_sum: precision 64 is not supported (float32 sums only)");
+    if (r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_FEATURES)
+        return fail(MVX_ERR_INVALID, "forward_sum: channel-wise radii with features are not supported (the grouped launch)");
+    if (h->g.D % 4 != 0) return fail(MVX_ERR_INVALID, "forward_sum: a dimension that is no multiple of 4 is not supported (run-wise write-out)");
+    {
+        mvx_plan_query q{};
+        q.dimension = h->g.D;
+        q.blockdim = h->g.bd;
+        q.precision = 32;
+        q.C = r.C;
+        if (plan_call(q, PlanKnobs{}).lane_range)
+            return fail(MVX_ERR_INVALID, "forward_sum: a blockdim that needs per-lane ranges is not supported");
+    }
+    if (reinterpret_cast<uintptr_t>(r.out) & 15u) return fail(MVX_ERR_INVALID, "out must be 16-byte aligned");
+    if (e.total == 0) { // no atoms: zeros, or - accumulating - nothing at all
+        if (accumulate) return MVX_OK;
+        CallScope scope(h, r.stream);
+        if (scope.rc) return scope.rc;
+        const size_t D = (size_t)h->g.D;
+        HIP_TRY(hipMemsetAsync(r.out, 0, (size_t)r.C * D * D * D * sizeof(float), r.stream));
+        return MVX_OK;
+    }
+    const SumCall sc{atom_weights, accumulate != 0};
+    return run_checked(h, r, e, &sc);
 }
 
 } // namespace
@@ -963,6 +1044,14 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const void *radii, d
     const int64_t off[2] = {0, N};
     return mvx_forward_single_batch(h, coords, radii, radius_scalar, radii_type, off, xform, 1, out, in_kind,
                                     out_kind, stream);
+}
+
+int mvx_forward_sum_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                          double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
+                          int32_t C, const float *atom_weights, float *out, int32_t accumulate, void *stream) {
+    const RunArgs r{{mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                     reinterpret_cast<hipStream_t>(stream), MVX_DEVICE}, out, MVX_DEVICE};
+    return run_sum(h, r, accumulate, atom_weights);
 }
 
 // ---- views of one shared cloud (mvx_views.hip) ----------------------------------------------------------------------------

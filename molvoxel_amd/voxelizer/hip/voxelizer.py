@@ -23,6 +23,9 @@ channels-last (NDHWC, `torch.channels_last_3d`) grids directly: same logical sha
 / `set_sigma()` take a one-element tensor that gets dL/dsigma (mvx_backward_density_batch).
 `forward_posed_batch` / `forward_posed_views` / `select_posed_views` take explicit rigid poses p = q (x - c) conj(q) + t instead of
 drawing random transforms; on a differentiable voxelizer the poses get their gradients (mvx_pose_grad_batch).
+`forward_sum` / `forward_posed_sum` write ONE float32 grid, the (weighted) sum of a batch's grids, without the B grids
+(mvx_forward_sum_batch); `field_grad=True` (with `differentiable=True`) lets `score_batch` / `score_posed_batch` take a shared
+field that requires grad: dL/dfield is such a weighted sum.
 """
 from __future__ import annotations
 
@@ -74,6 +77,7 @@ class Voxelizer(BaseVoxelizer):
         radii_grad: bool = False,
         sigma_grad: bool = False,
         grid_layout=None,
+        field_grad: bool = False,
         **kwargs,
     ):
         # sigma as a tensor (sigma_grad): kept as `sigma_tensor`; `_sigma` stays the python float the base class stores
@@ -95,7 +99,10 @@ class Voxelizer(BaseVoxelizer):
             raise ValueError("radii_grad=True needs differentiable=True: radius gradients are part of the autograd graph")
         if sigma_grad and not differentiable:
             raise ValueError("sigma_grad=True needs differentiable=True: the sigma gradient is part of the autograd graph")
+        if field_grad and not differentiable:
+            raise ValueError("field_grad=True needs differentiable=True: the field gradient is part of the autograd graph")
         self.differentiable = bool(differentiable)
+        self.field_grad = bool(field_grad)
         self.radii_grad = bool(radii_grad)
         self.sigma_grad = bool(sigma_grad)
         self._sigma_src = sigma_src
@@ -333,7 +340,8 @@ class Voxelizer(BaseVoxelizer):
             return type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
                               self.blockdim, idx, self.output, self.overlap_prepass,
                               grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
-                              radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout, **kw)
+                              radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout,
+                              field_grad=getattr(self, "field_grad", False), **kw)
         return self
 
     def cuda(self):
@@ -975,6 +983,102 @@ class Voxelizer(BaseVoxelizer):
         return self._select_views(coords, centers, channels, radii, xforms=(self._pose_xforms(pose, B), None))
 
     # ------------------------------------------------------------------------------------------
+    # SUMS (one grid for a whole batch: mvx_forward_sum_batch)
+    def forward_sum(self, coords, offsets, centers, channels, radii, weights=None, num_channels=None, out_grid=None,
+                    accumulate=False, random_translation=0.0, random_rotation=False):
+        """ONE (C,D,H,W) float32 grid: the sum over the B molecules, weighted or not, of the grids forward_batch would write
+        with the same arguments - without writing them (an occupancy map of a trajectory, of conformers, of docking poses).
+        The sum runs over the atoms in the caller's order, molecule after molecule, in the float32 fma chain the kernels run
+        inside one molecule: deterministic, independent of how the batch is cut, and for molecules that are only centred bit
+        for bit the per-molecule forward on the one merged molecule.
+
+        Arguments, checks, RNG order and records are forward_batch's; host arrays are moved to the device. Needs
+        output="torch". weights: None, (B,) one per molecule (expanded per atom on the device; this reading wins where B equals
+        the atom count) or (sumN,) one per atom, converted to float32: atom n contributes float32(weights[n] * w[n, c]) * rho.
+        out_grid: a contiguous float32 (C,D,H,W) tensor on this device, whatever the voxelizer's grid_dtype / grid_layout;
+        fully overwritten, or - accumulate=True, which needs out_grid - read and updated (a batch of no atoms leaves it
+        untouched). Returns the grid. The result is NOT part of the autograd graph: inputs that require grad are read as values.
+        Not supported (NotImplementedError; use forward_batch(...).sum(0)): precision 64, channel-wise radii with features,
+        dimensions that are no multiple of 4, and blockdims that cut through the kernels' 2 x 4 x 8 sub-tiles."""
+        return self._forward_sum(coords, offsets, centers, channels, radii, weights, num_channels, out_grid, accumulate,
+                                 random_translation, random_rotation)
+
+    def forward_posed_sum(self, coords, offsets, centers, quaternions, translations, channels, radii, weights=None,
+                          num_channels=None, out_grid=None, accumulate=False):
+        """forward_sum with one explicit rigid pose per molecule (forward_posed_batch's arguments and records): the (weighted)
+        sum of the grids of B poses in one float32 (C,D,H,W) grid. Not part of the autograd graph."""
+        self._sum_guard(channels)
+        B = np.asarray(offsets).shape[0] - 1
+        pose = self._pack_pose(B, centers, quaternions, translations, True)
+        return self._forward_sum(coords, offsets, None, channels, radii, weights, num_channels, out_grid, accumulate,
+                                 xforms=(self._pose_xforms(pose, B), None), pose=pose)
+
+    def _sum_guard(self, channels):
+        """What a summed call refuses before it looks at anything else: the configurations voxelize_sum_kernel does not serve."""
+        if self.output != "torch":
+            raise ValueError("forward_sum / forward_posed_sum need output='torch': the grid is a tensor on the voxelizer's device")
+        alt = "use forward_batch(...).sum(0) (forward_posed_batch(...).sum(0)) instead"
+        if getattr(self, "precision", 32) == 64:
+            raise NotImplementedError(f"forward_sum does not support precision 64 (float32 sums only): {alt}")
+        if self.is_radii_type_channel_wise and channels is not None and getattr(channels, "ndim", 1) == 2:
+            raise NotImplementedError(f"forward_sum does not support channel-wise radii with features: {alt}")
+        D, bd = int(self.dimension), int(getattr(self, "blockdim", None) or 8)
+        if D % 4 != 0:
+            raise NotImplementedError(f"forward_sum does not support a dimension that is no multiple of 4 (got {D}): {alt}")
+        if -(-D // bd) > 1 and bd % 8 != 0:  # (mvx_plan.lane_range: reference blocks that cut through 2 x 4 x 8 sub-tiles)
+            raise NotImplementedError(f"forward_sum does not support blockdim={bd} at dimension {D} (per-lane ranges): {alt}")
+
+    def _sum_weights(self, weights, offsets, N):
+        """The weights of a summed call as the library reads them: None, or (sumN,) float32 on this device."""
+        if weights is None:
+            return None
+        B = offsets.shape[0] - 1
+        w = (weights.detach() if _is_torch(weights) else torch.as_tensor(np.asarray(weights))).to(device=self.device, dtype=torch.float32)
+        shape = tuple(w.shape)
+        assert shape in ((B,), (N,)), f"weights does not match dimension: {shape} vs {(B,)} or {(N,)}"
+        if shape == (B,):
+            lengths = torch.as_tensor(np.diff(offsets), device=self.device)
+            w = torch.repeat_interleave(w, lengths, output_size=N)
+        return w.contiguous()
+
+    def _forward_sum(self, coords, offsets, centers, channels, radii, weights=None, num_channels=None, out_grid=None,
+                     accumulate=False, random_translation=0.0, random_rotation=False, xforms=None, pose=None):
+        """forward_sum's body, in the order of _forward_batch. xforms / pose: the posed form's records and packed poses."""
+        self._sum_guard(channels)
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, _ = self._scalar_radius(radii)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        B = offsets.shape[0] - 1
+        assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
+        kind, C_ = self._batch_kind(channels, radii, num_channels)
+        self._check_args_batch(coords, channels, kind, radii, C_)
+        if accumulate and out_grid is None:
+            raise ValueError("accumulate=True needs out_grid: there is nothing to add to")
+        if out_grid is not None:
+            assert tuple(getattr(out_grid, "shape", ())) == self.grid_dimension(C_), (
+                f"Output grid dimension incorrect: {tuple(getattr(out_grid, 'shape', ()))} vs {self.grid_dimension(C_)}")
+            if not (self._on_device(out_grid) and out_grid.dtype == torch.float32 and out_grid.is_contiguous()):
+                raise ValueError("out_grid of forward_sum must be a contiguous float32 tensor on this voxelizer's device")
+        with torch.no_grad():
+            w = self._sum_weights(weights, offsets, int(coords.shape[0]))
+            c, ch, r, in_kind, keep = self._prepare_inputs(self._device_coords(coords), channels, kind, radii)
+            r, _ = self._pad_type_radii(r, kind, C_)
+            xfs, _ = self._call_xforms(B, centers, in_kind, random_translation, random_rotation, keep, xforms)
+            rs = float(radii) if _np_isscalar(radii) else 0.0
+            return self._sum_call(kind or "single", c, ch, r, rs, offsets, xfs, B, C_, w, out_grid, accumulate)
+
+    def _sum_call(self, mode, c, ch, r, rs, offsets, xfs, B, C_, w, out, accumulate):
+        """One mvx_forward_sum_batch call on device arrays, on the current stream; out None: a new grid."""
+        if out is None:
+            out = torch.empty(self.grid_dimension(C_), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.mvx_forward_sum_batch(
+            self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
+            offsets.ctypes.data, None if xfs is None else C.addressof(xfs), B, C_, self._ptr(w), self._ptr(out),
+            1 if accumulate else 0, self._stream()))
+        return out
+
+    # ------------------------------------------------------------------------------------------
     # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
     def score_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, random_translation=0.0,
                     random_rotation=False, per_atom=False):
@@ -984,8 +1088,10 @@ class Voxelizer(BaseVoxelizer):
 
         field: (C,D,H,W), shared by all molecules, or (B,C,D,H,W), one per molecule; converted with
         `.to(device, grid_dtype).contiguous()` and read as NCDHW on a channels-last voxelizer too. A constant: a field that
-        requires grad raises NotImplementedError. The other arguments are forward_batch's (transforms drawn per molecule in
-        the same RNG order); host arrays are moved to the device. Needs output="torch".
+        requires grad raises NotImplementedError - unless the voxelizer was made with field_grad=True and the field is the
+        shared (C,D,H,W) one: backward() then returns dL/dfield, the grids summed with one weight per atom (forward_sum).
+        The other arguments are forward_batch's (transforms drawn per molecule in the same RNG order); host arrays are moved to
+        the device. Needs output="torch".
         Returns scores (B,) float64 on this device; with per_atom=True (scores, atom_scores (sumN,) float64) where
         scores[b] = sum of molecule b's atom_scores. Deterministic: no atomics, a molecule's values do not depend on its batch.
         On a differentiable voxelizer coords, features and centers that require grad get their gradients from the same walk;
@@ -998,17 +1104,20 @@ class Voxelizer(BaseVoxelizer):
         """score_batch with one explicit rigid pose per molecule (forward_posed_batch's arguments and records): the scores of
         B poses against `field`. On a differentiable voxelizer `centers`, `quaternions` and `translations` that require grad get
         dS/dc, dS/dq and dS/dt (mvx_pose_grad_batch on the scaled per-atom gradients)."""
-        self._score_guard(field)
+        self._score_guard(field, True)
         B = np.asarray(offsets).shape[0] - 1
         pose = self._pack_pose(B, centers, quaternions, translations, True)
         return self._score_batch(coords, offsets, None, channels, radii, field, num_channels, per_atom=per_atom,
                                  xforms=(self._pose_xforms(pose, B), None), pose=pose)
 
-    def _score_guard(self, field):
-        """What a score call refuses before it looks at anything else."""
+    def _score_guard(self, field, shared_field_grad=False):
+        """What a score call refuses before it looks at anything else. shared_field_grad: the call is one of those that, on a
+        field_grad voxelizer, give a shared (C, D, H, W) field its gradient (score_batch / score_posed_batch)."""
         if self.output != "torch":
             raise ValueError("score_batch / score_posed_batch need output='torch': the scores are tensors on the voxelizer's device")
         if _is_torch(field) and field.requires_grad:
+            if shared_field_grad and getattr(self, "field_grad", False) and field.dim() == 4:
+                return  # dL/dfield = the weighted summed grid (forward_sum): _ScoreFunction.backward
             raise NotImplementedError("gradients with respect to the field are not supported: dS/dfield is the grid itself - "
                                       "use forward_batch (forward_posed_batch) and (grid * field).sum() for them")
 
@@ -1030,7 +1139,11 @@ class Voxelizer(BaseVoxelizer):
     def _score_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, random_translation=0.0,
                      random_rotation=False, per_atom=False, xforms=None, pose=None):
         """score_batch's body, in the order of _forward_batch. xforms / pose: the posed form's records and packed poses."""
-        self._score_guard(field)
+        self._score_guard(field, True)
+        fgrad = (_is_torch(field) and field.requires_grad and getattr(self, "field_grad", False) and self.differentiable
+                 and torch.is_grad_enabled())
+        if fgrad:  # (what forward_sum cannot serve is refused now, not in backward())
+            self._sum_guard(channels)
         if self._sigma_src is not None:
             self._sync_sigma()
         radii, rten = self._scalar_radius(radii)
@@ -1066,12 +1179,14 @@ class Voxelizer(BaseVoxelizer):
                 self._stream()))
             return scores, atoms, gc, gf
 
-        if not grad:
+        if not grad and not fgrad:
             scores, atoms, _, _ = call()
             return (scores, atoms) if per_atom else scores
         spec = dict(offsets=offsets, xforms=xfs, B=B)
+        if fgrad:  # the call as forward_sum repeats it in backward(): same offsets and records, the random draws included
+            spec.update(mode=mode, channels=ch, radii=r, rs=rs, C=C_, keep=keep)
         cen = dev_cen if (_is_torch(dev_cen) and self._on_device(dev_cen)) else None
-        out = _ScoreFunction.apply(self, call, spec, per_atom, c, feat, cen, pose)
+        out = _ScoreFunction.apply(self, call, spec, per_atom, c, feat, cen, pose, field if fgrad else None)
         return out if per_atom else out[0]
 
     # ------------------------------------------------------------------------------------------
@@ -1367,10 +1482,11 @@ if torch is not None:
         with per_atom, dL/ds_n) and reduces centres and poses as _VoxelizeFunction does. No second walk."""
 
         @staticmethod
-        def forward(ctx, vox, call, spec, per_atom, c, f, cen, pose):
+        def forward(ctx, vox, call, spec, per_atom, c, f, cen, pose, field=None):
             scores, atoms, gc, gf = call()
             ctx.vox, ctx.spec = vox, spec
             ctx.save_for_backward(c, cen, pose, gc, gf)
+            ctx.field_like = None if field is None else (field.dtype, field.device)
             if per_atom:
                 return scores, atoms
             return (scores,)
@@ -1379,14 +1495,21 @@ if torch is not None:
         @torch.autograd.function.once_differentiable
         def backward(ctx, gs, ga=None):
             c, cen, pose, gc, gf = ctx.saved_tensors
-            need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[4:8]
-            lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device)
-            up = _row_upstream(gs, ga, lengths, gc.shape[0])
-            gcs = gc * up[:, None]
+            need_c, need_f, need_cen, need_pose, need_field = ctx.needs_input_grad[4:9]
+            lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=c.device)
+            up = _row_upstream(gs, ga, lengths, c.shape[0])
+            gcs = gc * up[:, None] if gc is not None else None
             gfs = (gf * up[:, None].to(gf.dtype)) if (need_f and gf is not None) else None
             gcen = _center_grad(gcs, cen, None if cen.numel() == 3 else lengths) if need_cen else None
             gpose = ctx.vox._pose_backward(ctx.spec, c, gcs) if need_pose else None
-            return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose
+            gfield = None
+            if need_field and ctx.field_like is not None:
+                # dL/dfield[c, v] = sum_n up_n w[n,c] rho_{n,c}(v): the saved call's grids summed with one float32 weight per atom
+                sp = ctx.spec
+                gfield = ctx.vox._sum_call(sp["mode"], c, sp["channels"], sp["radii"], sp["rs"], sp["offsets"], sp["xforms"], sp["B"],
+                                           sp["C"], up.to(torch.float32), None, False)
+                gfield = gfield.to(dtype=ctx.field_like[0]).to(ctx.field_like[1])
+            return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose, gfield
 
 
     class _ScoreViewsFunction(torch.autograd.Function):
