@@ -405,6 +405,45 @@ int mvx_forward_sum_batch(mvx_handle *h, int32_t mode, const double *coords, con
                           float *out /* (C, D, D, D) */, int32_t accumulate, void *stream);
 
 /*
+ * ONE summed grid for B views of ONE shared cloud (no counterpart in the reference): mvx_forward_sum_batch on the compact batch
+ * mvx_forward_views voxelizes - the occupancy map of 1 024 docking poses of a ligand, or of 256 boxes of a pocket, without B
+ * copies of the cloud and without the B grids. The cloud, `mode`, radii and the B host records are those of mvx_forward_views;
+ * every array is a device array, as for mvx_forward_sum_batch and mvx_score_views (centre and pose pointers point into device
+ * memory). view_weights: NULL or (B,) float32 on the device, one weight per view, expanded on the device to one per selected
+ * atom from the selection's offsets (no host round trip): it behaves as a (B,) molecule weight does in a summed batch.
+ * out: (C, D, D, D) float32 NCDHW, 16-byte aligned, whatever the handle's grid type and layout; accumulate as in
+ * mvx_forward_sum_batch. ONE stream synchronisation (the selection, as mvx_forward_views), then asynchronous on `stream`.
+ * The result is, bit for bit, mvx_forward_sum_batch on the cloud repeated B times with the same records - equivalently on
+ * coords[index], the gathered channels and radii and the offsets of mvx_select_views: culled atoms add nothing and the atom
+ * order is the same. B == 0: MVX_OK, nothing written. N == 0, or no view selects an atom: zeros, or with accumulate nothing
+ * touched. mvx_set_sum_parts applies, with the views as the molecules.
+ * MVX_ERR_INVALID, everything before any device is touched, in this order: a bad mode; a bad radii_type; B < 0, N < 0 or
+ * C <= 0; NULL xforms with B > 0; channel-wise radii in single mode; single mode with C != 1; NULL coords with N > 0; a missing
+ * radii array; NULL types in types mode with N > 0; N >= 2^31; accumulate outside {0, 1}; NULL out with B > 0; NULL channels in
+ * features mode with B > 0 and N > 0; a NULL handle; a bad pose record; then (B > 0) the four configurations the summed kernel
+ * does not serve, with the texts of mvx_forward_sum_batch - a precision-64 handle, channel-wise radii with features, a
+ * dimension that is no multiple of 4, a blockdim that needs per-lane ranges - and an out that is not 16-byte aligned.
+ */
+int mvx_forward_views_sum(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                          double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                          const float *view_weights, float *out, int32_t accumulate, void *stream);
+
+/*
+ * Summed grids in parts (opt-in; a new handle has parts = 1, which is the path and the bits described above). A summed call
+ * runs at most slabs x channel chunks workgroups, each walking all B molecules one after another: a batch of many small
+ * molecules (1 024 poses of a ligand) leaves most of the card idle. With parts = K > 1 every summed call of the handle -
+ * mvx_forward_sum_batch, mvx_forward_views_sum (the views are the molecules) - cuts the CALL's B molecules into parts:
+ *   q = ceil(B / K); part g holds the molecules [g q, min(B, (g + 1) q)); G = ceil(B / q) parts exist
+ *   S_g = the grid the parts = 1 call gives, from zero, for the molecules of part g alone
+ *   out = the float32 chain r = (accumulate ? out : +0); r = r + S_0; r = r + S_1; ...; r = r + S_{G-1}
+ * one rounding per add, in that order. No atomics: the bits are a function of the atom order, B and K alone, and never of how
+ * the call is cut into molecule chunks - but they DIFFER from the bits of parts = 1 (other partial sums are rounded).
+ * Workspace: G partial grids of C * D^3 floats, handle-owned, zeroed at the start of every such call.
+ * MVX_ERR_INVALID for a NULL handle and for parts outside 1 ... 64.
+ */
+int mvx_set_sum_parts(mvx_handle *h, int32_t parts);
+
+/*
  * Gradients with respect to explicit rigid poses (MVX_XF_POSE_PTR records; no counterpart in the reference): the reduction of
  * the per-atom gradients a backward entry wrote for the same call (grad_coords = M^T dL/dp) to dL/dc, dL/dq and dL/dt of every
  * molecule, on the device. Per molecule with pose (c, q, t), M = M(q) the linear part of the sandwich product (it scales by

@@ -130,6 +130,10 @@ struct mvx_handle : NoCopy {
     // offsets, max channel radius, and - mvx_forward_views - the selected indices and the gathered rows handed to run()
     DevBuf view_xf, view_counts, view_base, view_off, view_aux, view_index, view_coords, view_chan, view_radii;
     DevBuf view_red_off; // mvx_views_reduce: the call's offsets
+    DevBuf view_w;       // mvx_forward_views_sum: the view weights expanded to one per selected atom
+    // mvx_set_sum_parts: K > 1 cuts the molecules of every summed call into parts with a partial grid each (G * C * D^3 floats)
+    int sum_parts = 1;
+    DevBuf sum_part_grids;
     int32_t layout = MVX_LAYOUT_NCDHW; // mvx_set_grid_layout
     mvx_plan last_plan{}; // the plan of the last forward call, debug options applied (mvx_debug_last_plan)
     bool has_plan = false;
@@ -547,6 +551,7 @@ struct Forward {
     bool lr_blocks = false, lane_range = false;
     Forward(mvx_handle *h_, const RunArgs &r_, const Extent &e, const SumCall *sum_ = nullptr) : h(h_), r(r_), ext(e), sum(sum_) {}
     hipStream_t staging_stream() const { return overlap ? pre : s; }
+    size_t g_D3() const { return (size_t)h->g.D * h->g.D * h->g.D; }
     // ---- how this call is executed: one pure function of its shape (mvx_plan.hip, pinned by tests/test_plan.py) ----
     int make_plan() {
         const Geom &g = h->g;
@@ -780,6 +785,15 @@ struct Forward {
             return MVX_OK;
         };
         const bool interleave = !side_stream && !f64 && nchunk > 1; // chunk by chunk: pre-pass, then its voxelize launch
+        // a summed call in parts (mvx_set_sum_parts): parts of q molecules of the CALL, whatever the molecule chunks are; the
+        // partial grids start from zero, every chunk's launch adds to those of the parts it meets, one reduction ends the call
+        const int part_q = sum && h->sum_parts > 1 ? (int)(((int64_t)r.B + h->sum_parts - 1) / h->sum_parts) : 0;
+        const int part_G = part_q ? (int)(((int64_t)r.B + part_q - 1) / part_q) : 0;
+        const size_t grid_voxels = (size_t)r.C * g_D3();
+        if (part_q) {
+            if ((rc = ensure(h->sum_part_grids, (size_t)part_G * grid_voxels * sizeof(float)))) return rc;
+            HIP_TRY(hipMemsetAsync(h->sum_part_grids.p, 0, (size_t)part_G * grid_voxels * sizeof(float), s));
+        }
         for (int k = 0; k < nchunk && !interleave; ++k)
             if ((rc = prepass(k))) return rc;
         if (f64) { // float64 grids: one launch over the whole batch
@@ -791,6 +805,11 @@ struct Forward {
                 if (interleave && (rc = prepass(k))) return rc;
                 if (side_stream) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
                 va.p.b0 = b0;
+                if (part_q) { // one launch per molecule chunk over the parts that meet it
+                    float *pg = static_cast<float *>(h->sum_part_grids.p);
+                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize_sum_parts(va, b1 - b0, gauss, pg, part_q, s); }))) return rc;
+                    continue;
+                }
                 if (sum) { // one launch per molecule chunk; chunk k > 0 continues the sums chunk k - 1 wrote
                     if ((rc = timed_launch(h, s, [&] { return launch_voxelize_sum(va, b1 - b0, gauss, sum->accumulate || k > 0, s); }))) return rc;
                     continue;
@@ -816,6 +835,9 @@ struct Forward {
                 }
             }
         }
+        if (part_q)
+            HIP_TRY(launch_sum_parts_reduce(static_cast<const float *>(h->sum_part_grids.p), static_cast<float *>(d_out), grid_voxels, part_G,
+                                            sum->accumulate, s));
         if (overlap) { // the next call but one refills this set
             HIP_TRY(hipEventRecord(w->ev_vox, s));
             w->vox_recorded = true;
@@ -859,6 +881,25 @@ int run(mvx_handle *h, const RunArgs &r) {
     return run_checked(h, r, ext, nullptr);
 }
 
+// What the summed kernel does not serve, each named, and the alignment of the grid: the rules of a summed call that read the handle.
+int sum_config(const mvx_handle *h, int mode, int radii_type, int C, const void *out) {
+    if (h->cfg.precision == 64) return fail(MVX_ERR_INVALID, "forward_sum: precision 64 is not supported (float32 sums only)");
+    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES)
+        return fail(MVX_ERR_INVALID, "forward_sum: channel-wise radii with features are not supported (the grouped launch)");
+    if (h->g.D % 4 != 0) return fail(MVX_ERR_INVALID, "forward_sum: a dimension that is no multiple of 4 is not supported (run-wise write-out)");
+    {
+        mvx_plan_query q{};
+        q.dimension = h->g.D;
+        q.blockdim = h->g.bd;
+        q.precision = 32;
+        q.C = C;
+        if (plan_call(q, PlanKnobs{}).lane_range)
+            return fail(MVX_ERR_INVALID, "forward_sum: a blockdim that needs per-lane ranges is not supported");
+    }
+    if (reinterpret_cast<uintptr_t>(out) & 15u) return fail(MVX_ERR_INVALID, "out must be 16-byte aligned");
+    return MVX_OK;
+}
+
 // ---- mvx_forward_sum_batch: its own checks (those of the backward entries for the same arguments, in their order, then what
 // the summed kernel does not serve), the calls without atoms, then the forward's steps with a SumCall ----
 int run_sum(mvx_handle *h, const RunArgs &r, int32_t accumulate, const float *atom_weights) {
@@ -881,20 +922,7 @@ int run_sum(mvx_handle *h, const RunArgs &r, int32_t accumulate, const float *at
         if (r.mode != MODE_SINGLE && !r.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
         if (!r.radii && r.radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
     }
-    if (h->cfg.precision == 64) return fail(MVX_ERR_INVALID, "forward_sum: precision 64 is not supported (float32 sums only)");
-    if (r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_FEATURES)
-        return fail(MVX_ERR_INVALID, "forward_sum: channel-wise radii with features are not supported (the grouped launch)");
-    if (h->g.D % 4 != 0) return fail(MVX_ERR_INVALID, "forward_sum: a dimension that is no multiple of 4 is not supported (run-wise write-out)");
-    {
-        mvx_plan_query q{};
-        q.dimension = h->g.D;
-        q.blockdim = h->g.bd;
-        q.precision = 32;
-        q.C = r.C;
-        if (plan_call(q, PlanKnobs{}).lane_range)
-            return fail(MVX_ERR_INVALID, "forward_sum: a blockdim that needs per-lane ranges is not supported");
-    }
-    if (reinterpret_cast<uintptr_t>(r.out) & 15u) return fail(MVX_ERR_INVALID, "out must be 16-byte aligned");
+    if (int rc = sum_config(h, r.mode, r.radii_type, r.C, r.out)) return rc;
     if (e.total == 0) { // no atoms: zeros, or - accumulating - nothing at all
         if (accumulate) return MVX_OK;
         CallScope scope(h, r.stream);
@@ -1241,6 +1269,50 @@ int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const v
     const int rc = run(h, r);
     h->overlap = overlap;
     return rc;
+}
+
+// The summed grid of B views: mvx_forward_views' selection and gather, then run_sum on the compact batch in place of run(). What
+// reads the handle (sum_config) is checked before a device is touched; run_sum checks the batch again, to no effect.
+int mvx_forward_views_sum(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
+                          double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                          const float *view_weights, float *out, int32_t accumulate, void *stream) {
+    const Call v{mode, coords, channels, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), MVX_DEVICE};
+    const char *own = (accumulate != 0 && accumulate != 1) ? "accumulate must be 0 or 1"
+                      : (B > 0 && !out) ? "out must not be null"
+                      : (B > 0 && N > 0 && mode != MODE_SINGLE && !channels) ? "channels must not be null" : nullptr;
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (B == 0) return MVX_OK;
+    if (int rc = sum_config(h, mode, radii_type, C, out)) return rc;
+    std::vector<int64_t> offsets((size_t)B + 1, 0);
+    RunArgs r{v, out, MVX_DEVICE}; // the views as a batch of B molecules
+    r.offsets = offsets.data();
+    if (N == 0) return run_sum(h, r, accumulate, nullptr); // B views without atoms: zeros, or nothing
+    ViewInputs in(v);
+    const float *atom_weights = nullptr;
+    {
+        CallScope scope(h, v.stream);
+        int rc = scope.rc;
+        if (rc) return rc;
+        if ((rc = stage_views(h, v, false, in))) return rc;
+        if ((rc = select_views(h, v, in, nullptr, 0, true, offsets.data()))) return rc;
+        const int64_t total = offsets[B];
+        if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+        if ((rc = gather_views(h, v, static_cast<const int64_t *>(h->view_index.p), total, r))) return rc;
+        if (view_weights && total > 0) { // one weight per selected atom, from the offsets select_views left on the device
+            if ((rc = ensure(h->view_w, (size_t)total * sizeof(float)))) return rc;
+            HIP_TRY(launch_view_weights(static_cast<float *>(h->view_w.p), view_weights, static_cast<const int64_t *>(h->view_off.p), B, total, v.stream));
+            atom_weights = static_cast<const float *>(h->view_w.p);
+        }
+    }
+    r.xforms = in.xforms_host.data();
+    return run_sum(h, r, accumulate, atom_weights); // (a summed call never overlaps its pre-pass: Forward::make_plan)
+}
+
+int mvx_set_sum_parts(mvx_handle *h, int32_t parts) {
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (parts < 1 || parts > SUM_PARTS_MAX) return fail(MVX_ERR_INVALID, "sum parts must be 1 ... 64");
+    h->sum_parts = parts;
+    return MVX_OK;
 }
 
 // mvx_backward_batch (BWD_PLAIN), mvx_backward_radii_batch (BWD_RADII: grad_radii as well) and mvx_backward_density_batch

@@ -16,6 +16,11 @@
 //                        the staging loads of every molecule but the first, which the one-molecule kernels avoid by staging
 //                        before the accumulators exist. One write per slab for the whole batch: no pacing.
 //   scale_rows_kernel    per-atom weights: the packed weight rows scaled in float32, u[n, c] = fl32(a_n * w[n, c]).
+//   voxelize_sum_parts_kernel  the same walk (mvx_sum_body.inc) with the call's molecules cut into G parts (mvx_set_sum_parts):
+//                        one workgroup per (slab, chunk, part) sums its part into a partial grid of its own, so a batch of many
+//                        small molecules fills the card with G times the workgroups. Still no atomics.
+//   sum_parts_reduce_kernel  once per call: out = (out | +0) + S_0 + S_1 + ... in part order, 16 bytes per load and store.
+//   view_weights_kernel  mvx_forward_views_sum: one weight per view expanded to one per selected atom from the device offsets.
 #include "mvx_sum.h"
 
 #include "mvx_device.h"
@@ -29,88 +34,46 @@ template <bool GAUSS, int MAXT>
 __global__ void __launch_bounds__(MAXT, 4)
     voxelize_sum_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
                         const uint2 *__restrict__ slist_ext, float *out, const int nb, const int accumulate, const VoxParams P) {
-    typedef OpsMx32<GAUSS, false, false, false, float> Ops;
-    constexpr bool BIG = MAXT > 512;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NW = P.NW;
-    unsigned *un = reinterpret_cast<unsigned *>(smem);
+    float *const grid = out;
+    const int mol0 = P.b0, nmol = nb, from_grid = accumulate;
+#include "mvx_sum_body.inc"
+}
 
-    // grid = (T, ncc): t = slab id, blockIdx.y = channel chunk
-    unsigned t = blockIdx.x;
-    const unsigned TS = P.nslab;
-    if (P.nzc > 1) { // consecutive blocks = consecutive x-slabs (mvx_slab_body.inc)
-        const unsigned per_x = (unsigned)(P.nsy * P.nzc), nsx = (unsigned)P.nsx;
-        const unsigned tq = __umulhi(t, P.nsx_inv);
-        t = (t - tq * nsx) * per_x + tq;
-    }
-    const int cc = (int)blockIdx.y;
-    int sx, sy, zc;
-    decode_slab(t, P, sx, sy, zc);
-    const int x0 = SUBX * sx, y0 = SUBY * sy, z0 = zc * SUBZ * NW;
-    const LaneCtx L = Ops::ctx(lane, wave, x0, y0, z0, zc * NW, cc * 32, P);
+// The same walk for one PART of the call's molecules (mvx_set_sum_parts, K > 1): blockIdx.z + g0 is the part g, which owns the
+// molecules [g q, min(B, (g + 1) q)) of the CALL (P.B of them) and the partial grid parts + g C D^3. The workgroup walks what of
+// its part lies in this launch's molecule chunk [P.b0, P.b0 + nb), continuing from the partial grid unless the chunk holds the
+// part's first molecule, and writes the partial grid back; a part that does not meet the chunk does nothing.
+template <bool GAUSS, int MAXT>
+__global__ void __launch_bounds__(MAXT, 4)
+    voxelize_sum_parts_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                              const uint2 *__restrict__ slist_ext, float *parts, const int nb, const int q, const int g0, const VoxParams P) {
+    const long long g = (long long)g0 + (long long)blockIdx.z; // (uniform)
+    const long long first = g * q, lo = first > P.b0 ? first : (long long)P.b0;
+    long long hi = first + q < (long long)P.B ? first + q : (long long)P.B;
+    if (hi > (long long)P.b0 + nb) hi = (long long)P.b0 + nb;
+    if (lo >= hi) return; // (the whole workgroup: before any barrier)
+    float *const grid = parts + (size_t)g * ((size_t)P.C * P.D * P.D * P.D);
+    const int mol0 = (int)lo, nmol = (int)(hi - lo), from_grid = lo > first ? 1 : 0;
+#include "mvx_sum_body.inc"
+}
 
-    typename Ops::Acc acc;
-    Ops::zero(acc);
-    if (accumulate) {
-        // read-in, the inverse of OpsMx32::write's map: register r of this lane is channel 8 (r / 4) + 4 (lane / 32) + r % 4 of
-        // the chunk at voxel (x0 | x0 + 1, iy, iz). Channels and voxels that do not exist keep their zeros (never written).
-        const int D = P.D, h = lane >> 5;
-        const size_t D2 = (size_t)D * D, D3 = D2 * D;
-        const bool yz = L.iy < D && L.iz < D;
-        const bool ok0 = yz && x0 < D, ok1 = yz && x0 + 1 < D;
-        const float *src = out + (size_t)(L.cbase + 4 * h) * D3 + (size_t)x0 * D2 + (size_t)L.iy * D + L.iz;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int c = 8 * (r / 4) + (r % 4);
-            if (L.cbase + 4 * h + c < P.C) {
-                if (ok0) acc.p0[r] = src[(size_t)c * D3];
-                if (ok1) acc.p1[r] = src[(size_t)c * D3 + D2];
-            }
+// out[v] = (accumulate ? out[v] : +0) + S_0[v] + S_1[v] + ... + S_{G-1}[v]: one float32 rounding per add, in part order; n4
+// quads of four voxels, partial g at parts + g n4 quads.
+__global__ void __launch_bounds__(256) sum_parts_reduce_kernel(const float4 *__restrict__ parts, float4 *__restrict__ out, size_t n4, int G,
+                                                               int accumulate) {
+    const size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += step) {
+        float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (accumulate) r = out[i];
+        for (int g = 0; g < G; ++g) {
+            const float4 p = parts[(size_t)g * n4 + i];
+            r.x = r.x + p.x;
+            r.y = r.y + p.y;
+            r.z = r.z + p.z;
+            r.w = r.w + p.w;
         }
+        out[i] = r;
     }
-
-    const RoundSrc<Ops> RS_ = round_src<Ops>(rec, w, lane, L, P);
-    const int RW = 8 * NW < 64 ? 8 * NW : 64; // rows staged per round
-    bool rows_live = false; // (uniform) the row region still holds the rows of the molecule before
-    for (int i = 0; i < nb; ++i) {
-        // the candidate line of (molecule b0 + i, this slab): {count, first atom}, then {atom index, packed ranges} per candidate
-        const size_t li = (size_t)(P.b0 + i) * (size_t)TS + t;
-        const uint2 *__restrict__ line = slist + li * SLOTS; // (uniform: scalar loads)
-        const uint2 hdr = line[0];
-        const unsigned n_hdr = __builtin_amdgcn_readfirstlane(hdr.x);
-        if (n_hdr == 0) continue; // an empty line costs its header: no barrier
-        const int64_t a0 = (int64_t)(unsigned)__builtin_amdgcn_readfirstlane(hdr.y);
-        const bool xl = __builtin_expect(n_hdr > (unsigned)LINE_CAP, 0); // the slab walks its (molecule, x-slab) list
-        const uint2 *__restrict__ ext = slist_ext + li * EXT_SLOTS;
-        int n = (int)n_hdr;
-        if (xl) { // (explicit scalar halves and the global address space keep every line entry on the scalar path: mvx_slab_body.inc)
-            const uint2 where = line[1];
-            const unsigned long long at = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)where.y) << 32) |
-                                          (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)where.x);
-            typedef const uint2 __attribute__((address_space(1))) *global_u2;
-            const global_u2 xlp = (global_u2)at;
-            n = __builtin_amdgcn_readfirstlane((int)xlp[0].x);
-            line = (const uint2 *)(xlp + (XL_HEADER - 1));
-            ext = line + SLOTS;
-        }
-        if (rows_live) __syncthreads(); // every wave is done with the rows of the molecule before
-        rows_live = true;
-        stage_first_rounds<Ops, BIG>(line, ext, n, RW, un, RS_, a0, lane, wave);
-        __syncthreads();
-        filter_walk<Ops>(xl, acc, 0, n, RW, un, lane, wave, L, P, nullptr, nullptr);
-        if (n >= RW) filter_walk<Ops>(xl, acc, RW, n, RW, un + RW * Ops::SW, lane, wave, L, P, nullptr, nullptr); // (staged with the first)
-        for (int e0 = 2 * RW; e0 <= n; e0 += RW) {
-            __syncthreads();
-            stage_round<Ops, BIG>(line, ext, e0, n, un, RS_, a0, lane, wave, NW);
-            __syncthreads();
-            filter_walk<Ops>(xl, acc, e0, n, RW, un, lane, wave, L, P, nullptr, nullptr);
-        }
-    }
-    // one ordinary write-out (it begins with a barrier); "molecule" 0: the grid is the call's only one
-    Ops::write(acc, 1, un, tid, lane, wave, NW, 0, L, x0, y0, z0, out, P);
 }
 
 __global__ void __launch_bounds__(256) scale_rows_kernel(float *__restrict__ w, const float *__restrict__ weights, int64_t first, int64_t count, int32_t cpad) {
@@ -118,6 +81,22 @@ __global__ void __launch_bounds__(256) scale_rows_kernel(float *__restrict__ w, 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += step) {
         const int64_t n = first + i / cpad;
         w[first * cpad + i] = weights[n] * w[first * cpad + i];
+    }
+}
+
+// Per-view weights as per-atom weights of the gathered batch: a[off[b] .. off[b + 1]) = view_weights[b], the view of row n found
+// by bisection of the B + 1 device offsets (views without atoms own no row).
+__global__ void __launch_bounds__(256) view_weights_kernel(float *__restrict__ a, const float *__restrict__ view_weights,
+                                                           const int64_t *__restrict__ off, int32_t B, int64_t total) {
+    const int64_t step = (int64_t)gridDim.x * 256;
+    for (int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x; n < total; n += step) {
+        int lo = 0, hi = B; // the last b with off[b] <= n (off[0] = 0 <= n < total = off[B])
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (off[mid] <= n) lo = mid;
+            else hi = mid;
+        }
+        a[n] = view_weights[lo];
     }
 }
 
@@ -147,6 +126,47 @@ hipError_t launch_voxelize_sum(const VoxArgs &a, int32_t nb, bool gauss, bool ac
     if (!a.p.vec_store || a.p.xcd_ranges || a.p.ncc < 1 || a.p.ncc > 65535 || a.p.NW < 1 || a.p.NW > 16 || nb < 0) return hipErrorInvalidValue;
     if (a.p.NW <= 8) return gauss ? launch_sum<true, 512>(a, nb, accumulate, s) : launch_sum<false, 512>(a, nb, accumulate, s);
     return gauss ? launch_sum<true, 1024>(a, nb, accumulate, s) : launch_sum<false, 1024>(a, nb, accumulate, s);
+}
+
+hipError_t launch_view_weights(float *a, const float *view_weights, const int64_t *off, int32_t B, int64_t total, hipStream_t s) {
+    if (total <= 0 || B <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(view_weights_kernel, dim3(blocks), dim3(256), 0, s, a, view_weights, off, B, total);
+    return hipGetLastError();
+}
+
+template <bool GAUSS, int MAXT>
+static hipError_t launch_sum_parts(const VoxArgs &a, int32_t nb, float *parts, int32_t q, int32_t g0, int32_t ng, hipStream_t s) {
+    const VoxParams &p = a.p;
+    const size_t lds = std::max(voxelize_lds_bytes(32, p.NW, MX_CR), (size_t)2 * 64 * cand_stride_words(32) * 4); // (launch_sum)
+    static LdsLimit raised;
+    auto kern = &voxelize_sum_parts_kernel<GAUSS, MAXT>;
+    hipError_t e = raise_lds_limit(kern, lds, raised);
+    if (e != hipSuccess) return e;
+    launch_profiled(kern, dim3(p.nslab, (unsigned)p.ncc, (unsigned)ng), dim3(p.NW * 64), lds, s, a.rec, a.w, a.slist, a.slist_ext, parts,
+                    (int)nb, (int)q, (int)g0, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_voxelize_sum_parts(const VoxArgs &a, int32_t nb, bool gauss, float *parts, int32_t q, hipStream_t s) {
+    if (!a.p.vec_store || a.p.xcd_ranges || a.p.ncc < 1 || a.p.ncc > 65535 || a.p.NW < 1 || a.p.NW > 16 || nb < 0 || q < 1 || !parts)
+        return hipErrorInvalidValue;
+    if (nb == 0) return hipSuccess;
+    // the parts that meet the chunk [b0, b0 + nb): at most MVX_SUM_PARTS_MAX of them, in gridDim.z
+    const int32_t g0 = a.p.b0 / q, ng = (a.p.b0 + nb - 1) / q - g0 + 1;
+    if (ng < 1 || ng > SUM_PARTS_MAX) return hipErrorInvalidValue;
+    if (a.p.NW <= 8) return gauss ? launch_sum_parts<true, 512>(a, nb, parts, q, g0, ng, s) : launch_sum_parts<false, 512>(a, nb, parts, q, g0, ng, s);
+    return gauss ? launch_sum_parts<true, 1024>(a, nb, parts, q, g0, ng, s) : launch_sum_parts<false, 1024>(a, nb, parts, q, g0, ng, s);
+}
+
+hipError_t launch_sum_parts_reduce(const float *parts, float *out, size_t voxels, int32_t G, bool accumulate, hipStream_t s) {
+    if (voxels % 4 != 0 || G < 1 || ((reinterpret_cast<uintptr_t>(parts) | reinterpret_cast<uintptr_t>(out)) & 15u)) return hipErrorInvalidValue;
+    const size_t n4 = voxels / 4;
+    if (n4 == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<size_t>((n4 + 255) / 256, 8192);
+    hipLaunchKernelGGL(sum_parts_reduce_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4 *>(parts),
+                       reinterpret_cast<float4 *>(out), n4, (int)G, accumulate ? 1 : 0);
+    return hipGetLastError();
 }
 
 } // namespace mvx

@@ -26,6 +26,8 @@ drawing random transforms; on a differentiable voxelizer the poses get their gra
 `forward_sum` / `forward_posed_sum` write ONE float32 grid, the (weighted) sum of a batch's grids, without the B grids
 (mvx_forward_sum_batch); `field_grad=True` (with `differentiable=True`) lets `score_batch` / `score_posed_batch` take a shared
 field that requires grad: dL/dfield is such a weighted sum.
+`forward_views_sum` / `forward_posed_views_sum` are that one grid for B views of ONE shared cloud (mvx_forward_views_sum);
+`set_sum_parts(K)` cuts every summed call into K parts with a partial grid each (mvx_set_sum_parts; other bits than K = 1).
 """
 from __future__ import annotations
 
@@ -337,11 +339,14 @@ class Voxelizer(BaseVoxelizer):
         idx = self._resolve_device(device)
         if idx != self._device_index:
             kw = {"sigma": self._sigma if self._sigma_src is None else self._sigma_src[0]} if self.is_density_type_gaussian else {}
-            return type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
-                              self.blockdim, idx, self.output, self.overlap_prepass,
-                              grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
-                              radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout,
-                              field_grad=getattr(self, "field_grad", False), **kw)
+            moved = type(self)(self._resolution, self._dimension, self._radii_type, self._density_type, self.precision,
+                               self.blockdim, idx, self.output, self.overlap_prepass,
+                               grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
+                               radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout,
+                               field_grad=getattr(self, "field_grad", False), **kw)
+            if self.sum_parts != 1:
+                moved.set_sum_parts(self.sum_parts)
+            return moved
         return self
 
     def cuda(self):
@@ -1077,6 +1082,88 @@ class Voxelizer(BaseVoxelizer):
             offsets.ctypes.data, None if xfs is None else C.addressof(xfs), B, C_, self._ptr(w), self._ptr(out),
             1 if accumulate else 0, self._stream()))
         return out
+
+    def forward_views_sum(self, coords, centers, channels, radii, weights=None, num_channels=None, out_grid=None, accumulate=False,
+                          random_translation=0.0, random_rotation=False):
+        """ONE (C,D,H,W) float32 grid: the sum over B boxes of ONE shared point cloud, weighted or not, of the grids forward_views
+        would write with the same arguments - without the B copies of the cloud and without the B grids (the occupancy map of
+        256 boxes of a pocket). Bit for bit forward_sum on the cloud repeated B times with the same centres and transforms:
+        each view's atoms are selected on the device (forward_views' selection: culled atoms add nothing), gathered into a
+        compact batch and summed by forward_sum's kernel in view and atom order.
+
+        Arguments, checks, RNG order and records are forward_views': coords (N,3), centers (B,3), channels (N,C) float | (N,) int
+        | None, radii per this voxelizer's radii_type; a random transform is drawn per view in view order, exactly as
+        forward_views draws it. Host arrays are moved to the device. Needs output="torch". weights: None or (B,) one per view,
+        converted to float32 and expanded per selected atom on the device, as (B,) molecule weights are in forward_sum.
+        out_grid / accumulate and the configurations that are not supported (NotImplementedError) are forward_sum's: a
+        contiguous float32 (C,D,H,W) tensor on this device, fully overwritten, or - accumulate=True, which needs out_grid - read
+        and updated; a cloud of no atoms, or views that select none, write zeros or leave an accumulated grid untouched.
+        Synchronises the stream once, as forward_views does. With set_sum_parts(K > 1) the views are cut into parts (see there).
+        Returns the grid. The result is NOT part of the autograd graph: inputs that require grad are read as values."""
+        return self._forward_views_sum(coords, centers, channels, radii, weights, num_channels, out_grid, accumulate,
+                                       random_translation, random_rotation)
+
+    def forward_posed_views_sum(self, coords, centers, quaternions, translations, channels, radii, weights=None, num_channels=None,
+                                out_grid=None, accumulate=False):
+        """forward_views_sum with one explicit rigid pose per view (forward_posed_views' arguments and records): the (weighted)
+        sum of the grids of B poses of ONE shared cloud - 1 024 docking poses of a ligand - in one float32 (C,D,H,W) grid, bit
+        for bit forward_posed_sum on the cloud repeated B times. Not part of the autograd graph."""
+        self._sum_guard(channels)
+        return self._forward_views_sum(coords, centers, channels, radii, weights, num_channels, out_grid, accumulate,
+                                       posed=(quaternions, translations))
+
+    def _forward_views_sum(self, coords, centers, channels, radii, weights=None, num_channels=None, out_grid=None, accumulate=False,
+                           random_translation=0.0, random_rotation=False, posed=None):
+        """forward_views_sum's body, in the order of _forward_sum and _forward_views. posed: (quaternions, translations)."""
+        self._sum_guard(channels)
+        kind, C_, cradii, _ = self._views_args(coords, centers, channels, radii, num_channels)
+        B = int(centers.shape[0])
+        if accumulate and out_grid is None:
+            raise ValueError("accumulate=True needs out_grid: there is nothing to add to")
+        if out_grid is not None:
+            assert tuple(getattr(out_grid, "shape", ())) == self.grid_dimension(C_), (
+                f"Output grid dimension incorrect: {tuple(getattr(out_grid, 'shape', ()))} vs {self.grid_dimension(C_)}")
+            if not (self._on_device(out_grid) and out_grid.dtype == torch.float32 and out_grid.is_contiguous()):
+                raise ValueError("out_grid of forward_sum must be a contiguous float32 tensor on this voxelizer's device")
+        with torch.no_grad():
+            w = None
+            if weights is not None:
+                w = (weights.detach() if _is_torch(weights) else torch.as_tensor(np.asarray(weights))).to(
+                    device=self.device, dtype=torch.float32).contiguous()
+                assert tuple(w.shape) == (B,), f"weights does not match dimension: {tuple(w.shape)} vs {(B,)}"
+            c, ch, r, in_kind, keep = self._views_inputs(self._device_coords(coords), channels, kind, cradii, C_)
+            if posed is None:
+                xfs, _ = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
+            else:
+                pose = self._pack_pose(B, centers, posed[0], posed[1], True)
+                keep.append(pose)
+                xfs = self._pose_xforms(pose, B)
+            out = out_grid
+            if out is None:
+                out = torch.empty(self.grid_dimension(C_), dtype=torch.float32, device=self.device)
+            rs = float(cradii) if _np_isscalar(cradii) else 0.0
+            _lib.check(self._lib.mvx_forward_views_sum(
+                self._handle, _lib.MODES[kind or "single"], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
+                int(c.shape[0]), C_, C.addressof(xfs), B, self._ptr(w), self._ptr(out), 1 if accumulate else 0, self._stream()))
+            return out
+
+    def set_sum_parts(self, parts: int):
+        """Opt-in split of every summed call of this voxelizer (forward_sum, forward_posed_sum, forward_views_sum,
+        forward_posed_views_sum and the field gradient of the score calls) into K = `parts` parts, 1 ... 64; 1, the default, is
+        the one-pass sum. A summed call runs one workgroup per (slab, 32 channels) that walks all B molecules: many small
+        molecules leave most of the card idle. With K > 1 the call's B molecules (views) are cut into parts of q = ceil(B / K)
+        molecules, part g = [g q, min(B, (g + 1) q)), each summed into a partial grid S_g of its own (G = ceil(B / q) extra
+        (C,D,H,W) float32 grids of workspace), and the result is the float32 chain (out_grid with accumulate=True, else 0)
+        + S_0 + S_1 + ... + S_{G-1}, one rounding per add in that order. Deterministic, no atomics, independent of how the call
+        is cut into molecule chunks - but the bits DIFFER from those of parts = 1, and therefore from the merged-molecule and
+        split-call identities forward_sum documents."""
+        _lib.check(self._lib.mvx_set_sum_parts(self._handle, int(parts)))
+        self._sum_parts = int(parts)
+
+    @property
+    def sum_parts(self) -> int:
+        """The number of parts summed calls are cut into (set_sum_parts); 1: the one-pass sum."""
+        return getattr(self, "_sum_parts", 1)
 
     # ------------------------------------------------------------------------------------------
     # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
