@@ -7,27 +7,29 @@ channel-count inference (:275-278), RNG draws for the random transform in the re
 hot path — centring, rigid transform, culls, distances, densities, accumulation — runs on the GPU.
 There is no CPU fallback: construction fails without the shared library or without a HIP device.
 
-Array arguments may be numpy arrays (host: staged through pinned memory by the library) or torch
-CUDA tensors on this voxelizer's device (zero-copy via data_ptr on the current torch stream).
-Grids this backend allocates are torch CUDA tensors by default (`output="torch"`), so results stay
-in HBM; pass `output="numpy"` (or a numpy `out_grid`) for host arrays. `grid_dtype="bfloat16"` makes the
-kernels write bfloat16 grids directly: the float32 grid rounded to nearest even as it is stored, bit for bit
-what `.to(torch.bfloat16)` of the float32 grid gives, at half the bytes. `differentiable=True` makes grids computed from device
-tensors that require grad (`coords`, `features`, `center`) part of the autograd graph: the backward pass runs on the GPU
-(mvx_backward_batch) and returns gradients with respect to those tensors. `radii_grad=True` (with `differentiable=True`)
-adds a radii tensor that requires grad to them (mvx_backward_radii_batch, atom-wise or channel-wise radii; on a scalar-radii
-voxelizer a one-element radii tensor, mvx_backward_density_batch). `grid_layout="channels_last"` makes the kernels write
-channels-last (NDHWC, `torch.channels_last_3d`) grids directly: same logical shape, same bits, the strides 3D convolutions want
-(faster than converting afterwards with bfloat16 grids; experimental with float32 grids: DESIGN.md section 14).
-`sigma_grad=True` (with `differentiable=True`) lets `sigma=`
-/ `set_sigma()` take a one-element tensor that gets dL/dsigma (mvx_backward_density_batch).
-`forward_posed_batch` / `forward_posed_views` / `select_posed_views` take explicit rigid poses p = q (x - c) conj(q) + t instead of
-drawing random transforms; on a differentiable voxelizer the poses get their gradients (mvx_pose_grad_batch).
-`forward_sum` / `forward_posed_sum` write ONE float32 grid, the (weighted) sum of a batch's grids, without the B grids
-(mvx_forward_sum_batch); `field_grad=True` (with `differentiable=True`) lets `score_batch` / `score_posed_batch` take a shared
-field that requires grad: dL/dfield is such a weighted sum.
-`forward_views_sum` / `forward_posed_views_sum` are that one grid for B views of ONE shared cloud (mvx_forward_views_sum);
-`set_sum_parts(K)` cuts every summed call into K parts with a partial grid each (mvx_set_sum_parts; other bits than K = 1).
+Array arguments may be numpy arrays (host: staged through pinned memory by the library) or torch CUDA tensors on this
+voxelizer's device (zero-copy via data_ptr on the current torch stream). Grids are torch CUDA tensors by default
+(`output="torch"`); `output="numpy"` (or a numpy `out_grid`) gives host arrays.
+
+Constructor options:
+  grid_dtype="bfloat16"        the kernels write bfloat16 grids: the float32 grid rounded to nearest even as it is stored
+  grid_layout="channels_last"  the kernels write NDHWC (`torch.channels_last_3d`) grids: same logical shape, same bits
+  differentiable=True          grids computed from device tensors that require grad (coords, features, centres) are part of
+                               the autograd graph; the backward pass runs on the GPU (mvx_backward_batch)
+  radii_grad / sigma_grad / field_grad (with differentiable)  gradients for a radii tensor (mvx_backward_radii_batch; a
+                               one-element tensor on a scalar-radii voxelizer), for a one-element `sigma=` / `set_sigma()`
+                               tensor (mvx_backward_density_batch), and for the shared field of `score_batch`
+  overlap_prepass=True         see `set_overlap_prepass`
+
+Entries, next to the reference's `forward_features / forward_types / forward_single`:
+  forward_batch                B molecules stored back to back, one launch
+  forward_views, select_views  B boxes of ONE shared point cloud, without B copies of it
+  forward_sum, forward_views_sum  one float32 grid, the (weighted) sum of a batch's or the views' grids; `set_sum_parts`
+  score_batch, score_views     sum(field * grid) per molecule or view without the grids, with gradients
+  forward_posed_* / select_posed_views / score_posed_*  the same with explicit rigid poses p = q (x - c) conj(q) + t
+                               instead of random transforms; on a differentiable voxelizer the poses get gradients
+
+Every batch and views entry builds one `_Call` - the call as the library reads it - and hands it to one C entry.
 """
 from __future__ import annotations
 
@@ -55,13 +57,50 @@ except Exception:  # pragma: no cover
     _raw_stream = None
 
 
-def _np_isscalar(x) -> bool:
-    return np.isscalar(x)
+class _Call:
+    """One batch or views call as the library reads it: what the builders (`Voxelizer._batch_call` / `_views_call`) make of
+    the caller's arguments, and the `spec` the autograd Functions keep for backward().
+
+    mode "features" | "types" | "single"; C, B, N (all atoms of the call); coords, channels, radii: the converted arrays
+    (radii None with scalar radii, which travel as `rs`); offsets: host int64 (B + 1,), None for a views call; xforms: the
+    B mvx_xform records or None; centers: the device centres the records point at, or None; pose: the packed (B, 10) poses
+    the records point at, or None; in_kind: MVX_HOST | MVX_DEVICE; keep: what must outlive the call; rten: the scalar-radius
+    tensor of a radii_grad call; fresh: with overlap_prepass, an input was made on the stream a moment ago; grad: the call
+    records an autograd graph. For backward(): settings (`Voxelizer._grad_settings` at the forward) and, for the scores of
+    views, index (the selection)."""
+
+    __slots__ = ("mode", "C", "B", "N", "coords", "channels", "radii", "rs", "offsets", "xforms", "centers", "pose", "in_kind",
+                 "keep", "rten", "fresh", "grad", "settings", "index")
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields.pop(name, None))
+        assert not fields, sorted(fields)
+
+    def batch_args(self, vox, coords=None, channels=None):
+        """The arguments mvx_backward_batch, mvx_backward_radii_batch, mvx_backward_density_batch, mvx_score_batch and
+        mvx_forward_sum_batch begin with. coords / channels: the tensors autograd saved, in backward()."""
+        return (vox._handle, _lib.MODES[self.mode], vox._ptr(self.coords if coords is None else coords),
+                vox._ptr(self.channels if channels is None else channels), vox._ptr(self.radii), self.rs, vox._radii_type_code(),
+                self.offsets.ctypes.data, None if self.xforms is None else C.addressof(self.xforms), self.B, self.C)
+
+    def views_args(self, vox):
+        """The arguments mvx_forward_views, mvx_forward_views_sum and mvx_score_views begin with (mvx_select_views takes the
+        same values with the mode behind radii_type: `Voxelizer._select`)."""
+        return (vox._handle, _lib.MODES[self.mode], vox._ptr(self.coords), vox._ptr(self.channels), vox._ptr(self.radii), self.rs,
+                vox._radii_type_code(), self.N, self.C, C.addressof(self.xforms), self.B)
 
 
 class Voxelizer(BaseVoxelizer):
     LIB = "HIP"
     transform_class = RandomTransform
+    # the constructor's defaults of what used to be read through getattr(self, ..., default): a Voxelizer made with __new__
+    # that sets only some attributes (host-test fakes written against earlier versions of this class) reads these
+    precision = 32
+    blockdim = 8
+    field_grad = False
+    _sum_parts = 1
+    _views_total = 0
 
     def __init__(
         self,
@@ -125,12 +164,14 @@ class Voxelizer(BaseVoxelizer):
         self._types_cache = None
         self._types_i32 = None
         self._types_fresh = False
+        self._sum_parts = 1  # (set_sum_parts)
+        self._views_total = 0  # the last selection's size: sizes the next index buffer (_select)
         self._xf = _lib.MvxXform()  # reused per call: the library copies it before the call returns
         self._xf_addr = C.addressof(self._xf)
         self._has_torch_cuda = torch is not None and torch.cuda.is_available()  # asked on every call otherwise
         cfg = _lib.MvxConfig(
             float(resolution),
-            float(getattr(self, "_sigma", 0.5)),
+            float(self._sigma) if density_type == "gaussian" else 0.5,  # (binary density stores no sigma: base class)
             int(dimension),
             int(self.blockdim),
             _lib.MVX_GAUSSIAN if density_type == "gaussian" else _lib.MVX_BINARY,
@@ -343,7 +384,7 @@ class Voxelizer(BaseVoxelizer):
                                self.blockdim, idx, self.output, self.overlap_prepass,
                                grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
                                radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout,
-                               field_grad=getattr(self, "field_grad", False), **kw)
+                               field_grad=self.field_grad, **kw)
             if self.sum_parts != 1:
                 moved.set_sum_parts(self.sum_parts)
             return moved
@@ -382,7 +423,7 @@ class Voxelizer(BaseVoxelizer):
                 t = chan if _is_torch(chan) else torch.as_tensor(np.asarray(chan), device=self.device)
                 ch = self._types_as_int32(t)
             r = None
-            if not _np_isscalar(radii):
+            if not np.isscalar(radii):
                 r = (radii if _is_torch(radii) else torch.as_tensor(np.asarray(radii), device=self.device)).to(
                     device=self.device, dtype=self._tfp).contiguous()
             keep += [c, ch, r]
@@ -398,7 +439,7 @@ class Voxelizer(BaseVoxelizer):
             t = chan.detach().cpu().numpy() if _is_torch(chan) else np.asarray(chan)
             ch = np.ascontiguousarray(t.astype(np.int16), dtype=np.int32)
         r = None
-        if not _np_isscalar(radii):
+        if not np.isscalar(radii):
             r = radii.detach().cpu().numpy() if _is_torch(radii) else np.asarray(radii)
             r = np.ascontiguousarray(r, dtype=self.fp)
         keep += [c, ch, r]
@@ -479,84 +520,102 @@ class Voxelizer(BaseVoxelizer):
         return _lib.MVX_RADII_CHANNEL
 
     # ------------------------------------------------------------------------------------------
-    # VECTOR  (replaces numpy/voxelizer.py:97-236)
+    # SINGLE MOLECULES  (replace numpy/voxelizer.py:97-236 VECTOR, :240-366 INDEX, :370-477 SINGLE)
     def forward_features(self, coords, center, features, radii, random_translation=0.0, random_rotation=False,
                          out_grid=None):
         """coords (V,3), center (3,) | None, features (V,C), radii scalar | (V,) | (C,); out (C,D,H,W)."""
-        if self._sigma_src is not None:
-            self._sync_sigma()
-        radii, rten = self._scalar_radius(radii)
-        self._check_args_features(coords, features, radii, out_grid)
-        C_ = features.shape[1]
-        grad = self._grad_wanted(coords, features, center, radii, out_grid, rten)
-        c, f, r, in_kind, keep = self._prepare_inputs(coords, features, "features", radii)
-        center = self._grad_center(center) if grad else center
-        xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
-        buf, out_kind, ret, how = self._resolve_out(out_grid, (C_,))
-        rs = float(radii) if r is None else 0.0
-        launch = lambda: self._lib.mvx_forward_features(  # noqa: E731
-            self._handle, self._ptr(c), self._ptr(f), self._ptr(r), rs, self._radii_type_code(), c.shape[0], C_,
-            xf, self._ptr(buf), in_kind, out_kind, self._stream())
-        if grad:
-            return self._autograd(launch, ret, "features", c, f, center, None, r, rs, np.array([0, c.shape[0]], np.int64),
-                                  self._xform_copy(xf), 1, C_, rten)
-        rc = launch()
-        if rc:
-            _lib.check(rc)
-        return self._finish_out(buf, ret, how) if how else ret
+        return self._forward_one("features", coords, center, features, radii, random_translation, random_rotation, out_grid)
 
-    def _check_args_features(self, coords, features, radii, out_grid=None):
-        V = coords.shape[0]
-        C_ = features.shape[1]
-        D = H = W = self.dimension
-        assert features.shape[0] == V, f"atom features does not match number of atoms: {features.shape[0]} vs {V}"
-        assert features.ndim == 2, f"atom features does not match dimension: {features.shape} vs {(V,'*')}"
-        if self.is_radii_type_scalar:
-            assert _np_isscalar(radii), "the radii type of voxelizer is `scalar`, radii should be scalar"
-        elif self.is_radii_type_channel_wise:
-            assert not _np_isscalar(radii), f"the radii type of voxelizer is `channel-wise`, radii should be Array[{C_},]"
-            assert tuple(radii.shape) == (C_,), f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(C_,)}"
-        else:
-            assert not _np_isscalar(radii), f"the radii type of voxelizer is `atom-wise`, radii should be Array[{V},]"
-            assert tuple(radii.shape) == (V,), f"radii does not match dimension (number of atoms,): {tuple(radii.shape)} vs {(V,)}"
-        if out_grid is not None:
-            assert tuple(out_grid.shape) == (C_, D, H, W), f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(C_,D,H,W)}"
-
-    # ------------------------------------------------------------------------------------------
-    # INDEX  (replaces numpy/voxelizer.py:240-366)
     def forward_types(self, coords, center, types, radii, random_translation=0.0, random_rotation=False,
                       out_grid=None):
         """coords (V,3), center (3,) | None, types (V,), radii scalar | (V,) | (C,); out (C,D,H,W)."""
+        return self._forward_one("types", coords, center, types, radii, random_translation, random_rotation, out_grid)
+
+    def forward_single(self, coords, center, radii, random_translation=0.0, random_rotation=False, out_grid=None):
+        """coords (V,3), center (3,) | None, radii scalar | (V,); out (1,D,H,W)."""
+        return self._forward_one("single", coords, center, None, radii, random_translation, random_rotation, out_grid)
+
+    def _forward_one(self, kind, coords, center, chan, radii, random_translation, random_rotation, out_grid):
+        """The body of the three single-molecule entries. They are host-bound: no _Call is built
+        unless the call records a graph."""
         if self._sigma_src is not None:
             self._sync_sigma()
         radii, rten = self._scalar_radius(radii)
-        n_types = self._check_args_types(coords, types, radii, out_grid)
-        if out_grid is not None:
-            C_ = out_grid.shape[0]  # extra channels stay zero (numpy/voxelizer.py:337)
-        elif self.is_radii_type_channel_wise:
-            C_ = radii.shape[0]  # numpy/voxelizer.py:275-276
-        else:
-            C_ = n_types  # max(types) + 1 over ALL atoms, numpy/voxelizer.py:278
-        grad = self._grad_wanted(coords, None, center, radii, out_grid, rten)
-        c, t, r, in_kind, keep = self._prepare_inputs(coords, types, "types", radii)
-        if self.is_radii_type_channel_wise and r is not None and r.shape[0] < C_:
-            # channel-wise radii are indexed by type only; pad so the (C,) contract of the ABI holds
-            pad = C_ - r.shape[0]
-            r = torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])
+        C_ = self._check_args_one(kind, coords, chan, radii, out_grid)
+        grad = self._grad_wanted(coords, chan if kind == "features" else None, center, radii, out_grid, rten)
+        c, ch, r, in_kind, keep = self._prepare_inputs(coords, chan, None if kind == "single" else kind, radii)
+        if r is not None and kind == "types":  # (out_grid may have more channels than there are types: numpy/voxelizer.py:337)
+            r, _ = self._pad_type_radii(r, kind, C_)
         center = self._grad_center(center) if grad else center
         xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
         buf, out_kind, ret, how = self._resolve_out(out_grid, (C_,))
         rs = float(radii) if r is None else 0.0
-        launch = lambda: self._lib.mvx_forward_types(  # noqa: E731
-            self._handle, self._ptr(c), self._ptr(t), self._ptr(r), rs, self._radii_type_code(), c.shape[0], int(C_),
-            xf, self._ptr(buf), in_kind, out_kind, self._stream())
+        n = c.shape[0]
+        if kind == "single":
+            launch = lambda: self._lib.mvx_forward_single(  # noqa: E731
+                self._handle, self._ptr(c), self._ptr(r), rs, self._radii_type_code(), n,
+                xf, self._ptr(buf), in_kind, out_kind, self._stream())
+        else:
+            entry = self._lib.mvx_forward_features if kind == "features" else self._lib.mvx_forward_types
+            launch = lambda: entry(  # noqa: E731
+                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(), n, C_,
+                xf, self._ptr(buf), in_kind, out_kind, self._stream())
         if grad:
-            return self._autograd(launch, ret, "types", c, None, center, t, r, rs, np.array([0, c.shape[0]], np.int64),
-                                  self._xform_copy(xf), 1, int(C_), rten)
+            return self._autograd(launch, ret, _Call(
+                mode=kind, C=C_, B=1, N=n, coords=c, channels=ch, radii=r, rs=rs, offsets=np.array([0, n], np.int64),
+                xforms=self._xform_copy(xf), centers=center if self._on_device(center) else None, in_kind=in_kind, keep=keep,
+                rten=rten, grad=True))
         rc = launch()
         if rc:
             _lib.check(rc)
         return self._finish_out(buf, ret, how) if how else ret
+
+    def _check_args_one(self, kind, coords, chan, radii, out_grid):
+        """The rules of the single-molecule entries, with the reference's texts; returns the channel count of the call."""
+        V = coords.shape[0]
+        D = H = W = self.dimension
+        if kind == "features":
+            C_ = chan.shape[1]
+            assert chan.shape[0] == V, f"atom features does not match number of atoms: {chan.shape[0]} vs {V}"
+            assert chan.ndim == 2, f"atom features does not match dimension: {chan.shape} vs {(V,'*')}"
+        elif kind == "types":
+            tmin, tmax = self._types_extent(chan)
+            C_ = tmax + 1  # max(types) + 1 over ALL atoms, numpy/voxelizer.py:278 (= the channel-wise radii's count, :275-276)
+            assert tuple(chan.shape) == (V,), f"types does not match dimension: {tuple(chan.shape)} vs {(V,)}"
+            assert tmin >= 0, "types must be non-negative channel indices"
+        else:
+            C_ = 1
+            assert not self.is_radii_type_channel_wise, "Channel-Wise Radii Type is not supported"
+        self._check_radii(radii, V, C_)
+        if out_grid is None:
+            return C_
+        if kind == "features":
+            assert tuple(out_grid.shape) == (C_, D, H, W), f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(C_,D,H,W)}"
+            return C_
+        if kind == "types":  # extra channels stay zero (numpy/voxelizer.py:337)
+            assert out_grid.shape[0] >= C_, f"Output channel is less than number of types: {out_grid.shape[0]} < {C_}"
+        else:
+            assert out_grid.shape[0] == 1, "Output channel should be 1"
+        assert tuple(out_grid.shape[1:]) == (D, H, W), f'Output grid dimension incorrect: {tuple(out_grid.shape)} vs {("*",D,H,W)}'
+        return int(out_grid.shape[0])
+
+    def _check_radii(self, radii, V, C_, batch_types=None):
+        """The scalar / channel-wise / atom-wise radii rules of every entry. batch_types: the types of a batch or views call,
+        whose channel-wise radii are gathered by type: every type below num_channels needs one, the rest are padded."""
+        if self.is_radii_type_scalar:
+            assert np.isscalar(radii), "the radii type of voxelizer is `scalar`, radii should be scalar"
+        elif self.is_radii_type_channel_wise:
+            assert not np.isscalar(radii), f"the radii type of voxelizer is `channel-wise`, radii should be Array[{C_},]"
+            if batch_types is None:
+                assert tuple(radii.shape) == (C_,), f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(C_,)}"
+            else:
+                assert radii.ndim == 1 and 0 < radii.shape[0] <= C_, f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(C_,)}"
+                if V > 0:
+                    tmax = int(batch_types.max())
+                    assert tmax < radii.shape[0], f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(tmax + 1,)}"
+        else:
+            assert not np.isscalar(radii), f"the radii type of voxelizer is `atom-wise`, radii should be Array[{V},]"
+            assert tuple(radii.shape) == (V,), f"radii does not match dimension (number of atoms,): {tuple(radii.shape)} vs {(V,)}"
 
     def _types_as_int32(self, t):
         """Device types in the ABI's int32, through int16 like the reference's cast (numpy/voxelizer.py:269).
@@ -584,140 +643,111 @@ class Voxelizer(BaseVoxelizer):
             hit = self._types_cache = (types, types._version, int(lo), int(hi))
         return hit[2], hit[3]
 
-    def _check_args_types(self, coords, types, radii, out_grid=None):
-        V = coords.shape[0]
-        tmin, tmax = self._types_extent(types)
-        C_ = tmax + 1
-        D = H = W = self.dimension
-        assert tuple(types.shape) == (V,), f"types does not match dimension: {tuple(types.shape)} vs {(V,)}"
-        assert tmin >= 0, "types must be non-negative channel indices"
-        if self.is_radii_type_scalar:
-            assert _np_isscalar(radii), "the radii type of voxelizer is `scalar`, radii should be scalar"
-        elif self.is_radii_type_channel_wise:
-            assert not _np_isscalar(radii), f"the radii type of voxelizer is `channel-wise`, radii should be Array[{C_},]"
-            assert tuple(radii.shape) == (C_,), f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(C_,)}"
-        else:
-            assert not _np_isscalar(radii), f"the radii type of voxelizer is `atom-wise`, radii should be Array[{V},]"
-            assert tuple(radii.shape) == (V,), f"radii does not match dimension (number of atoms,): {tuple(radii.shape)} vs {(V,)}"
-        if out_grid is not None:
-            assert out_grid.shape[0] >= C_, f"Output channel is less than number of types: {out_grid.shape[0]} < {C_}"
-            assert tuple(out_grid.shape[1:]) == (D, H, W), f'Output grid dimension incorrect: {tuple(out_grid.shape)} vs {("*",D,H,W)}'
-        return C_
-
     # ------------------------------------------------------------------------------------------
-    # SINGLE  (replaces numpy/voxelizer.py:370-477)
-    def forward_single(self, coords, center, radii, random_translation=0.0, random_rotation=False, out_grid=None):
-        """coords (V,3), center (3,) | None, radii scalar | (V,); out (1,D,H,W)."""
+    # THE CALL RECORD (every batch and views entry: guard, build, family-specific checks, outputs, one library call)
+    def _batch_call(self, coords, offsets, centers, channels, radii, num_channels=None, random_translation=0.0,
+                    random_rotation=False, posed=None, *, device=False, score=False, check=None, out_grid=None, drawn=None):
+        """The _Call of B molecules stored back to back, from forward_batch's arguments. posed: (quaternions, translations):
+        explicit poses instead of centres with random transforms; their rules fire before every other rule of the call.
+        device: host arrays are moved to the device (the sum and score entries). score: a score call, which gives no radius
+        or sigma gradient and tracks coords, features and centres (poses) only. check(B, C, offsets): the rules of the
+        entry's family that need the call's shape; they fire after the argument rules, before anything is converted or drawn.
+        out_grid: the caller's grid, which a recorded graph refuses. drawn: (records, device centres, packed poses) drawn
+        already for these molecules instead of new ones - the rows forward_views gathered on a differentiable voxelizer."""
+        pose = None
+        if posed is not None:
+            pose = self._pack_pose(np.asarray(offsets).shape[0] - 1, centers, posed[0], posed[1], device or self._on_device(coords))
+            centers = None
         if self._sigma_src is not None:
             self._sync_sigma()
         radii, rten = self._scalar_radius(radii)
-        self._check_args_single(coords, radii, out_grid)
-        grad = self._grad_wanted(coords, None, center, radii, out_grid, rten)
-        c, _, r, in_kind, keep = self._prepare_inputs(coords, None, None, radii)
-        center = self._grad_center(center) if grad else center
-        xf = self._make_xform(center, random_translation, random_rotation, in_kind == _lib.MVX_DEVICE, keep)
-        buf, out_kind, ret, how = self._resolve_out(out_grid, (1,))
-        rs = float(radii) if r is None else 0.0
-        launch = lambda: self._lib.mvx_forward_single(  # noqa: E731
-            self._handle, self._ptr(c), self._ptr(r), rs, self._radii_type_code(), c.shape[0],
-            xf, self._ptr(buf), in_kind, out_kind, self._stream())
-        if grad:
-            return self._autograd(launch, ret, "single", c, None, center, None, r, rs, np.array([0, c.shape[0]], np.int64),
-                                  self._xform_copy(xf), 1, 1, rten)
-        rc = launch()
-        if rc:
-            _lib.check(rc)
-        return self._finish_out(buf, ret, how) if how else ret
-
-    def _check_args_single(self, coords, radii, out_grid=None):
-        V = coords.shape[0]
-        D = H = W = self.dimension
-        assert not self.is_radii_type_channel_wise, "Channel-Wise Radii Type is not supported"
-        if self.is_radii_type_scalar:
-            assert _np_isscalar(radii), "the radii type of voxelizer is `scalar`, radii should be scalar"
-        else:
-            assert not _np_isscalar(radii), f"the radii type of voxelizer is `atom-wise`, radii should be Array[{V},]"
-            assert tuple(radii.shape) == (V,), f"radii does not match dimension (number of atoms,): {tuple(radii.shape)} vs {(V,)}"
-        if out_grid is not None:
-            assert out_grid.shape[0] == 1, "Output channel should be 1"
-            assert tuple(out_grid.shape[1:]) == (D, H, W), f'Output grid dimension incorrect: {tuple(out_grid.shape)} vs {("*",D,H,W)}'
-
-    # ------------------------------------------------------------------------------------------
-    # BATCH (the loop of test/test_time_numpy.py:11-15 as one launch; molecules are independent)
-    def forward_batch(self, coords, offsets, centers, channels, radii, num_channels=None, out_grid=None,
-                      random_translation=0.0, random_rotation=False):
-        """Voxelize B molecules stored back to back.
-
-        coords (sumN,3) float64; offsets (B+1,) int64 (host); centers (B,3) | None;
-        channels: (sumN,C) float -> features, (sumN,) int -> types, None -> single;
-        radii: python float | (sumN,) | (C,) per this voxelizer's radii_type.
-        out_grid: (B,C,D,H,W) of this voxelizer's grid_dtype (torch CUDA tensor on this device or numpy), fully overwritten.
-        A random transform, if requested, is drawn per molecule in molecule order.
-        """
-        return self._forward_batch(coords, offsets, centers, channels, radii, num_channels, out_grid, random_translation,
-                                   random_rotation)
-
-    def _forward_batch(self, coords, offsets, centers, channels, radii, num_channels=None, out_grid=None,
-                       random_translation=0.0, random_rotation=False, xforms=None, fresh_inputs=False, pose=None):
-        """forward_batch's body. xforms: (records, device centres) already drawn by the caller (forward_views on a
-        differentiable voxelizer, the posed forms) instead of new ones; fresh_inputs: the caller made the inputs on the current
-        stream a moment ago, so with overlap_prepass the stream is synchronised before the side stream may read them; pose: the
-        packed (B, 10) poses the records point at (the posed forms; `centers` is None then)."""
-        if self._sigma_src is not None:
-            self._sync_sigma()
-        radii, rten = self._scalar_radius(radii)
+        if score:
+            self._score_no_density_grads(radii, rten)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         B = offsets.shape[0] - 1
         assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
         kind, C_ = self._batch_kind(channels, radii, num_channels)
         self._check_args_batch(coords, channels, kind, radii, C_)
-        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, radii,
-                                 out_grid, rten)
+        if check is not None:
+            check(B, C_, offsets)
+        call = _Call(mode=kind or "single", C=C_, B=B, offsets=offsets, rten=rten, pose=pose)
+        return self._convert(call, coords, centers, channels, radii, random_translation, random_rotation,
+                             device=device, score=score, out_grid=out_grid, drawn=drawn)
+
+    def _views_call(self, coords, centers, channels, radii, num_channels=None, random_translation=0.0, random_rotation=False,
+                    posed=None, *, device=False, score=False, check=None, out_grid=None, features=True):
+        """The _Call of B views of ONE shared cloud, from forward_views' arguments: forward_batch's rules for one molecule of
+        N atoms. Keywords as _batch_call (check gets offsets = None); the poses are packed after the rules. features: are
+        the feature values read, and therefore converted - False: no (select_views); "without_graph": only by a call that
+        records no graph (forward_views, which otherwise selects, gathers and hands the rows to _batch_call)."""
+        if self._sigma_src is not None:
+            self._sync_sigma()
+        radii, rten = self._scalar_radius(radii)
+        kind, C_ = self._batch_kind(channels, radii, num_channels)
+        self._check_args_batch(coords, channels, kind, radii, C_)
+        assert centers is not None and centers.ndim == 2 and centers.shape[1] == 3, (
+            f"centers does not match dimension: {tuple(getattr(centers, 'shape', ()))} vs ('B', 3)")
+        if score:
+            self._score_no_density_grads(radii, rten)
+        B = int(centers.shape[0])
+        if check is not None:
+            check(B, C_, None)
+        call = _Call(mode=kind or "single", C=C_, B=B, rten=rten)
+        if posed is not None:
+            call.pose = self._pack_pose(B, centers, posed[0], posed[1], device or self._on_device(coords))
+        return self._convert(call, coords, centers, channels, radii, random_translation, random_rotation,
+                             device=device, score=score, out_grid=out_grid, features=features)
+
+    def _convert(self, call, coords, centers, channels, radii, random_translation, random_rotation, *, device, score, out_grid,
+                 drawn=None, features=True):
+        """The second half of both builders, behind the rules; fills in the _Call they began (mode, C, B, offsets, rten,
+        pose): does the call record a graph, the arrays as the library reads them, the records (drawn here, record by
+        record), and overlap_prepass's `fresh`. radii: behind _scalar_radius."""
+        kind = None if call.mode == "single" else call.mode
+        if drawn is not None:
+            call.xforms, centers, call.pose = drawn
+        pose = call.pose
+        tracked = (coords, channels if kind == "features" else None, centers if pose is None else pose)
+        if score:
+            call.grad = self._grad_wanted(*tracked, None, None)
+        else:
+            call.grad = self._grad_wanted(*tracked, radii, out_grid, call.rten)
         user_centers = centers  # (a conversion made below, for autograd or for the ABI, is "fresh")
-        if grad and centers is not None:
+        if call.grad and centers is not None:
             centers = self._grad_center(centers)
-        c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
+        if kind == "features" and (features is False or (features == "without_graph" and call.grad)):
+            channels = kind = None  # (feature values are not read: not converted either)
+        c, ch, r, in_kind, keep = self._prepare_inputs(self._device_coords(coords) if device else coords, channels, kind, radii)
         # With overlap_prepass the library's side stream reads the inputs without waiting for the caller's stream.
         # Arrays this layer had to convert just now (dtype / layout fixes, the int32 copy of `types`) were produced
         # ON that stream a moment ago: make them complete first (first call with a given tensor only: the copies are
-        # cached or the caller passes the right dtype)
-        fresh = self.overlap_prepass and in_kind == _lib.MVX_DEVICE and (
-            c is not coords or (kind == "features" and ch is not channels) or (r is not None and r is not radii)
-            or (kind == "types" and self._types_fresh))
-        r, padded = self._pad_type_radii(r, kind, C_)
-        fresh = fresh or (self.overlap_prepass and (padded or (fresh_inputs and in_kind == _lib.MVX_DEVICE)))
-        xfs, dev_cen = self._call_xforms(B, centers, in_kind, random_translation, random_rotation, keep, xforms)
-        if xforms is None and dev_cen is not None:
-            fresh = fresh or (self.overlap_prepass and dev_cen.data_ptr() != user_centers.data_ptr())
-        xf_ptr = None if xfs is None else C.addressof(xfs)
-        if out_grid is None:
-            out_grid = self.get_empty_grid(C_, batch_size=B)
-        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
-            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
-        buf, out_kind, ret, how = self._resolve_out(out_grid, None)
-        if fresh:
-            torch.cuda.current_stream(self._device_index).synchronize()
-        rs = float(radii) if _np_isscalar(radii) else 0.0
-        off_ptr = offsets.ctypes.data
-        rt = self._radii_type_code()
-        if kind == "features":
-            launch = lambda: self._lib.mvx_forward_features_batch(  # noqa: E731
-                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, C_,
-                self._ptr(buf), in_kind, out_kind, self._stream())
-        elif kind == "types":
-            launch = lambda: self._lib.mvx_forward_types_batch(  # noqa: E731
-                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, C_,
-                self._ptr(buf), in_kind, out_kind, self._stream())
-        else:
-            assert not self.is_radii_type_channel_wise, "Channel-Wise Radii Type is not supported"
-            launch = lambda: self._lib.mvx_forward_single_batch(  # noqa: E731
-                self._handle, self._ptr(c), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, self._ptr(buf), in_kind, out_kind,
-                self._stream())
-        if grad:
-            return self._autograd(launch, ret, kind or "single", c, ch if kind == "features" else None,
-                                  dev_cen, ch if kind == "types" else None, r, rs, offsets, xfs, B, C_, rten, pose)
-        _lib.check(launch())
-        return self._finish_out(buf, ret, how)
+        # cached or the caller passes the right dtype). The same holds for padded radii, for rows gathered and poses
+        # packed a moment ago (drawn, a pose tensor) and for a converted centres tensor.
+        on_stream = self.overlap_prepass and in_kind == _lib.MVX_DEVICE
+        fresh = on_stream and (c is not coords or (kind == "features" and ch is not channels) or (r is not None and r is not radii)
+                               or (kind == "types" and self._types_fresh) or drawn is not None or _is_torch(pose))
+        r, padded = self._pad_type_radii(r, kind, call.C)
+        if padded:
+            keep.append(r)
+            fresh = fresh or self.overlap_prepass
+        if drawn is None:
+            call.xforms, centers = self._records(call.B, centers, pose, in_kind, random_translation, random_rotation, keep)
+            if on_stream and centers is not None:
+                fresh = fresh or centers.data_ptr() != user_centers.data_ptr()
+        call.N, call.coords, call.channels, call.radii = int(c.shape[0]), c, ch, r
+        call.rs = float(radii) if np.isscalar(radii) else 0.0
+        call.centers, call.in_kind, call.keep, call.fresh = centers, in_kind, keep, fresh
+        return call
+
+    def _records(self, B, centers, pose, in_kind, random_translation, random_rotation, keep):
+        """The B records of a call as (records or None, device centres or None): from the packed poses, or from the centres
+        and the random transform, drawn now."""
+        if pose is not None:
+            keep.append(pose)
+            return self._pose_xforms(pose, B), None
+        if centers is not None or random_rotation or (random_translation and random_translation > 0.0):
+            return self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
+        return None, None
 
     def _batch_kind(self, channels, radii, num_channels):
         """(kind, C) of a batch or views call from its channels: None -> single, (sumN,) int -> types, (sumN, C) -> features."""
@@ -729,32 +759,41 @@ class Voxelizer(BaseVoxelizer):
             return "types", int(num_channels)
         return "types", int(radii.shape[0] if self.is_radii_type_channel_wise else int(channels.max()) + 1)
 
+    def _check_args_batch(self, coords, channels, kind, radii, C_):
+        """The per-molecule rules (_check_args_one) for atoms stored back to back: the library reads sumN rows of channels
+        and sumN | C radii, so every array must really have them."""
+        V = coords.shape[0]
+        assert coords.ndim == 2 and coords.shape[1] == 3, f"coords does not match dimension: {tuple(coords.shape)} vs {(V, 3)}"
+        if kind == "features":
+            assert channels.shape[0] == V, f"atom features does not match number of atoms: {channels.shape[0]} vs {V}"
+        elif kind == "types":
+            assert tuple(channels.shape) == (V,), f"types does not match dimension: {tuple(channels.shape)} vs {(V,)}"
+        else:
+            assert not self.is_radii_type_channel_wise, "Channel-Wise Radii Type is not supported"
+        self._check_radii(radii, V, C_, channels if kind == "types" else None)
+
+    def _views_inputs(self, coords, channels, kind, radii, C_):
+        """(coords, channels, radii, in_kind, keepalive) of a views call as the library reads them, channel-wise radii of a
+        types call padded: _convert's conversions, for a caller that brings its own records."""
+        c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
+        r, padded = self._pad_type_radii(r, kind, C_)
+        if padded:
+            keep.append(r)
+        return c, ch, r, in_kind, keep
+
     def _pad_type_radii(self, r, kind, C_):
-        """Channel-wise radii are indexed by type only: padded with ones so that the (C,) contract of the ABI holds (as
-        forward_types). Returns (radii, whether a new array was made)."""
+        """Channel-wise radii are indexed by type only: padded with ones so that the (C,) contract of the ABI holds.
+        Returns (radii, whether a new array was made)."""
         if not (kind == "types" and self.is_radii_type_channel_wise and r.shape[0] < C_):
             return r, False
         pad = C_ - r.shape[0]
         return (torch.cat([r, r.new_ones(pad)]) if _is_torch(r) else np.concatenate([r, np.ones(pad, self.fp)])), True
 
-    def _call_xforms(self, B, centers, in_kind, random_translation, random_rotation, keep, xforms):
-        """The records of a batch call as (records or None, device centres or None). xforms: the pair the caller drew already
-        (forward_views on a differentiable voxelizer, the posed forms) instead of new ones."""
-        if xforms is not None:
-            return xforms
-        if centers is not None or random_rotation or (random_translation and random_translation > 0.0):
-            return self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
-        return None, None
-
     def _device_coords(self, coords):
-        """coords on this voxelizer's device (the score entries take device arrays only): host arrays are moved there."""
+        """coords on this voxelizer's device (the sum and score entries take device arrays only): host arrays are moved there."""
         if self._on_device(coords):
             return coords
         return (coords.detach() if _is_torch(coords) else torch.as_tensor(np.asarray(coords, dtype=np.float64))).to(self.device)
-
-    def _field_tensor(self, field):
-        """The field of a score call as the library reads it: on this device, of the grid's dtype, contiguous."""
-        return (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
 
     def _make_xforms(self, B, centers, in_kind, random_translation, random_rotation, keep):
         """B mvx_xform records, one per molecule (forward_batch) or view (forward_views): centring + the random transform,
@@ -776,66 +815,120 @@ class Voxelizer(BaseVoxelizer):
             C.memmove(C.addressof(xfs) + b * C.sizeof(_lib.MvxXform), self._xf_addr, C.sizeof(_lib.MvxXform))
         return xfs, dev_cen
 
-    def _check_args_batch(self, coords, channels, kind, radii, C_):
-        """The per-molecule checks (_check_args_features / _types / _single) for atoms stored back to back: the
-        library reads sumN rows of channels and sumN | C radii, so every array must really have them."""
-        V = coords.shape[0]
-        assert coords.ndim == 2 and coords.shape[1] == 3, f"coords does not match dimension: {tuple(coords.shape)} vs {(V, 3)}"
-        if kind == "features":
-            assert channels.shape[0] == V, f"atom features does not match number of atoms: {channels.shape[0]} vs {V}"
-        elif kind == "types":
-            assert tuple(channels.shape) == (V,), f"types does not match dimension: {tuple(channels.shape)} vs {(V,)}"
+    def _pack_pose(self, B, centers, quaternions, translations, on_device):
+        """The (B, 10) float64 block [c | q | t] the records of a posed call point at. With coordinates on this device the block
+        is a tensor there: torch tensors are packed with torch ops (recorded by autograd; their values never visit the host and
+        nothing synchronises), numpy poses are packed on the host and uploaded. With host coordinates: a numpy array."""
+        Voxelizer._check_pose(B, centers, quaternions, translations)
+        parts = [centers, quaternions, translations]
+        if on_device and any(self._on_device(x) for x in parts):
+            dev = [torch.zeros((B, 3), dtype=torch.float64, device=self.device) if x is None else
+                   (x if _is_torch(x) else torch.as_tensor(np.asarray(x, dtype=np.float64))).to(device=self.device, dtype=torch.float64)
+                   for x in parts]
+            return torch.cat(dev, dim=1).contiguous()
+        host = [np.zeros((B, 3)) if x is None else
+                np.asarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float64) for x in parts]
+        block = np.ascontiguousarray(np.concatenate(host, axis=1), dtype=np.float64)
+        return torch.as_tensor(block, device=self.device) if on_device else block
+
+    @staticmethod
+    def _check_pose(B, centers, quaternions, translations):
+        """The shape rules of explicit poses (_pack_pose; the posed entries that refuse something else first apply them early)."""
+        def shape(x):
+            return tuple(getattr(x, "shape", ()))
+
+        assert shape(quaternions) == (B, 4), f"quaternions does not match dimension: {shape(quaternions)} vs {(B, 4)}"
+        assert shape(translations) == (B, 3), f"translations does not match dimension: {shape(translations)} vs {(B, 3)}"
+        assert centers is None or shape(centers) == (B, 3), f"centers does not match dimension: {shape(centers)} vs {(B, 3)}"
+
+    def _pose_xforms(self, pose, B):
+        """B MVX_XF_POSE_PTR records, record b pointing at row b of the packed poses."""
+        xfs = (_lib.MvxXform * B)()
+        base = self._ptr(pose)
+        for b in range(B):
+            xfs[b].flags = _lib.MVX_XF_POSE_PTR
+            xfs[b].center_ptr = base + 80 * b
+        return xfs
+
+    # ------------------------------------------------------------------------------------------
+    # BATCH (the loop of test/test_time_numpy.py:11-15 as one launch; molecules are independent)
+    def forward_batch(self, coords, offsets, centers, channels, radii, num_channels=None, out_grid=None,
+                      random_translation=0.0, random_rotation=False):
+        """Voxelize B molecules stored back to back.
+
+        coords (sumN,3) float64; offsets (B+1,) int64 (host); centers (B,3) | None;
+        channels: (sumN,C) float -> features, (sumN,) int -> types, None -> single;
+        radii: python float | (sumN,) | (C,) per this voxelizer's radii_type.
+        out_grid: (B,C,D,H,W) of this voxelizer's grid_dtype (torch CUDA tensor on this device or numpy), fully overwritten.
+        A random transform, if requested, is drawn per molecule in molecule order.
+        """
+        return self._forward_batch(coords, offsets, centers, channels, radii, num_channels, out_grid, random_translation,
+                                   random_rotation)
+
+    def forward_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, num_channels=None,
+                            out_grid=None):
+        """forward_batch with one explicit rigid pose per molecule instead of random transforms: atom x of molecule b lands at
+        p = q_b (x - c_b) conj(q_b) + t_b - the centre subtracted, the sandwich product in the random rotation's operation order
+        with q as given (the linear part scales by |q|^2: normalise q in torch beforehand for a pure rotation, autograd carries
+        the normalisation), then t, rounded to float32, added once.
+
+        quaternions (B,4) as (q0, q1, q2, q3); translations (B,3); centers (B,3) | None (c = 0); any float dtype, torch tensors
+        or numpy arrays. Tensors on this voxelizer's device are handed over by pointer: no host round trip, no synchronisation.
+        The other arguments are forward_batch's. On a differentiable voxelizer, `centers`, `quaternions` and `translations`
+        that require grad get dL/dc, dL/dq and dL/dt (mvx_pose_grad_batch; deterministic), next to the gradients of coords,
+        features, radii and sigma. q = 0 gives non-finite pose gradients."""
+        return self._forward_batch(coords, offsets, centers, channels, radii, num_channels, out_grid,
+                                   posed=(quaternions, translations))
+
+    def _forward_batch(self, coords, offsets, centers, channels, radii, num_channels=None, out_grid=None,
+                       random_translation=0.0, random_rotation=False, posed=None, drawn=None):
+        """forward_batch's body. posed, drawn: see _batch_call."""
+        call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
+                                posed, out_grid=out_grid, drawn=drawn)
+        B, C_ = call.B, call.C
+        if out_grid is None:
+            out_grid = self.get_empty_grid(C_, batch_size=B)
+        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
+            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
+        buf, out_kind, ret, how = self._resolve_out(out_grid, None)
+        if call.fresh:
+            torch.cuda.current_stream(self._device_index).synchronize()
+        # (the three mvx_forward_*_batch entries have an argument order of their own)
+        c, ch, r, rs, in_kind = call.coords, call.channels, call.radii, call.rs, call.in_kind
+        off_ptr = call.offsets.ctypes.data
+        xf_ptr = None if call.xforms is None else C.addressof(call.xforms)
+        rt = self._radii_type_code()
+        if call.mode == "single":
+            launch = lambda: self._lib.mvx_forward_single_batch(  # noqa: E731
+                self._handle, self._ptr(c), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, self._ptr(buf), in_kind, out_kind,
+                self._stream())
         else:
-            assert not self.is_radii_type_channel_wise, "Channel-Wise Radii Type is not supported"
-        if self.is_radii_type_scalar:
-            assert _np_isscalar(radii), "the radii type of voxelizer is `scalar`, radii should be scalar"
-        elif self.is_radii_type_channel_wise:
-            assert not _np_isscalar(radii), f"the radii type of voxelizer is `channel-wise`, radii should be Array[{C_},]"
-            if kind == "features":
-                assert tuple(radii.shape) == (C_,), f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(C_,)}"
-            else:  # types: radii are gathered by type; every type below num_channels needs one
-                assert radii.ndim == 1 and 0 < radii.shape[0] <= C_, f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(C_,)}"
-                if V > 0:
-                    tmax = int(channels.max())
-                    assert tmax < radii.shape[0], f"radii does not match dimension (number of channels,): {tuple(radii.shape)} vs {(tmax + 1,)}"
-        else:
-            assert not _np_isscalar(radii), f"the radii type of voxelizer is `atom-wise`, radii should be Array[{V},]"
-            assert tuple(radii.shape) == (V,), f"radii does not match dimension (number of atoms,): {tuple(radii.shape)} vs {(V,)}"
+            entry = self._lib.mvx_forward_features_batch if call.mode == "features" else self._lib.mvx_forward_types_batch
+            launch = lambda: entry(  # noqa: E731
+                self._handle, self._ptr(c), self._ptr(ch), self._ptr(r), rs, rt, off_ptr, xf_ptr, B, C_,
+                self._ptr(buf), in_kind, out_kind, self._stream())
+        if call.grad:
+            return self._autograd(launch, ret, call)
+        _lib.check(launch())
+        return self._finish_out(buf, ret, how)
 
     # ------------------------------------------------------------------------------------------
     # VIEWS (many boxes of one shared point cloud: mvx_select_views / mvx_forward_views)
-    def _views_args(self, coords, centers, channels, radii, num_channels):
-        """(kind, C, radii, scalar-radius tensor) of a views call: forward_batch's rules for one molecule of N atoms."""
-        if self._sigma_src is not None:
-            self._sync_sigma()
-        radii, rten = self._scalar_radius(radii)
-        kind, C_ = self._batch_kind(channels, radii, num_channels)
-        self._check_args_batch(coords, channels, kind, radii, C_)
-        assert centers is not None and centers.ndim == 2 and centers.shape[1] == 3, (
-            f"centers does not match dimension: {tuple(getattr(centers, 'shape', ()))} vs ('B', 3)")
-        return kind, C_, radii, rten
-
-    def _views_inputs(self, coords, channels, kind, radii, C_):
-        c, ch, r, in_kind, keep = self._prepare_inputs(coords, channels, kind, radii)
-        r, padded = self._pad_type_radii(r, kind, C_)
-        if padded:
-            keep.append(r)
-        return c, ch, r, in_kind, keep
-
-    def _select(self, c, types, r, rs, kind, C_, xfs, B, in_kind):
+    def _select(self, call):
         """mvx_select_views into an index buffer sized from the call's shape: B * N entries when that is small, else the
         last call's total with some room. One call (one synchronisation) unless the buffer turns out too small: the library
         then reports MVX_ERR_INVALID with the offsets filled in, and the call is repeated with the exact size."""
-        N = int(c.shape[0])
+        handle, mode, c, ch, r, rs, rt, N, C_, xfs, B = call.views_args(self)
+        args = (handle, c, ch if call.mode == "types" else None, r, rs, rt, mode, N, C_, xfs, B)  # (feature values are not read)
         offsets = np.full(B + 1, -1, dtype=np.int64)
-        args = (self._handle, self._ptr(c), self._ptr(types), self._ptr(r), rs, self._radii_type_code(),
-                _lib.MODES[kind or "single"], N, C_, C.addressof(xfs), B)
-        cap = B * N if B * N <= (1 << 20) else min(B * N, max(1 << 20, 2 * getattr(self, "_views_total", 0)))
+        cap = B * N if B * N <= (1 << 20) else min(B * N, max(1 << 20, 2 * self._views_total))
         index = torch.empty(cap, dtype=torch.int64, device=self.device)
-        rc = self._lib.mvx_select_views(*args, index.data_ptr() if cap else None, cap, offsets.ctypes.data, in_kind, self._stream())
+        rc = self._lib.mvx_select_views(*args, index.data_ptr() if cap else None, cap, offsets.ctypes.data, call.in_kind,
+                                        self._stream())
         if rc != 0 and offsets[-1] > cap:  # too small: size it from the offsets and call again
             index = torch.empty(int(offsets[-1]), dtype=torch.int64, device=self.device)
-            rc = self._lib.mvx_select_views(*args, index.data_ptr(), index.numel(), offsets.ctypes.data, in_kind, self._stream())
+            rc = self._lib.mvx_select_views(*args, index.data_ptr(), index.numel(), offsets.ctypes.data, call.in_kind,
+                                            self._stream())
         _lib.check(rc)
         self._views_total = int(offsets[-1])
         return index[:int(offsets[-1])], offsets
@@ -847,16 +940,17 @@ class Voxelizer(BaseVoxelizer):
         them). Arguments as forward_views; feature values are not read. Synchronises the stream (the offsets come to the host)."""
         return self._select_views(coords, centers, channels, radii, random_translation, random_rotation)
 
+    def select_posed_views(self, coords, centers, quaternions, translations, channels=None, radii=None):
+        """select_views for explicit poses: the atoms each pose of forward_posed_views keeps, as (index, offsets)."""
+        self._check_pose(int(centers.shape[0]), centers, quaternions, translations)  # (before the rules of the other arguments)
+        return self._select_views(coords, centers, channels, radii, posed=(quaternions, translations))
+
     def _select_views(self, coords, centers, channels, radii, random_translation=0.0, random_rotation=False, num_channels=None,
-                      xforms=None):
-        """select_views' body. num_channels: the channel count of a types call; xforms: records already drawn."""
-        kind, C_, radii, _ = self._views_args(coords, centers, channels, radii, num_channels)
-        B = int(centers.shape[0])
-        c, ch, r, in_kind, keep = self._views_inputs(coords, channels if kind == "types" else None, kind if kind == "types" else None,
-                                                     radii, C_)
-        xfs, _ = xforms if xforms is not None else self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
-        rs = float(radii) if _np_isscalar(radii) else 0.0
-        return self._select(c, ch, r, rs, kind, C_, xfs, B, in_kind)
+                      posed=None):
+        """select_views' body. num_channels: the channel count of a types call. (An index has no gradient: no graph.)"""
+        with torch.no_grad():
+            return self._select(self._views_call(coords, centers, channels, radii, num_channels, random_translation,
+                                                 random_rotation, posed, features=False))
 
     def forward_views(self, coords, centers, channels, radii, num_channels=None, out_grid=None, random_translation=0.0,
                       random_rotation=False):
@@ -876,103 +970,6 @@ class Voxelizer(BaseVoxelizer):
         """
         return self._forward_views(coords, centers, channels, radii, num_channels, out_grid, random_translation, random_rotation)
 
-    def _forward_views(self, coords, centers, channels, radii, num_channels=None, out_grid=None, random_translation=0.0,
-                       random_rotation=False, posed=None):
-        """forward_views' body. posed: (quaternions, translations) of forward_posed_views: the views' records are explicit
-        poses instead of centres with random transforms."""
-        kind, C_, cradii, rten = self._views_args(coords, centers, channels, radii, num_channels)
-        B = int(centers.shape[0])
-        pose = None
-        if posed is not None:
-            pose = self._pack_pose(B, centers, posed[0], posed[1], self._on_device(coords))
-        if self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, cradii, out_grid,
-                             rten):
-            keep = []
-            in_kind = _lib.MVX_DEVICE  # (_grad_wanted: coords live on this device)
-            if pose is None:
-                cen = self._grad_center(centers)
-                xforms = self._make_xforms(B, cen, in_kind, random_translation, random_rotation, keep)
-            else:
-                cen, xforms = None, (self._pose_xforms(pose, B), None)
-            with torch.no_grad():
-                index, offsets = self._select_views(coords, centers, channels, cradii,
-                                                    num_channels=C_ if kind == "types" else None, xforms=xforms)
-
-            def take(x):
-                if _is_torch(x):
-                    return x[index.to(x.device)]
-                return np.asarray(x)[index.cpu().numpy()]
-
-            r_sel = take(cradii) if self.is_radii_type_atom_wise else radii
-            # (the gathered rows are made on this stream just now: with overlap_prepass the side stream must not read them
-            # early - fresh_inputs makes _forward_batch synchronise first)
-            return self._forward_batch(coords[index], offsets, cen, None if channels is None else take(channels), r_sel,
-                                       num_channels=C_ if kind == "types" else None, xforms=xforms, fresh_inputs=True, pose=pose)
-        c, ch, r, in_kind, keep = self._views_inputs(coords, channels, kind, cradii, C_)
-        if pose is None:
-            xfs, _ = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
-        else:
-            xfs = self._pose_xforms(pose, B)
-        if out_grid is None:
-            out_grid = self.get_empty_grid(C_, batch_size=B)
-        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
-            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
-        buf, out_kind, ret, how = self._resolve_out(out_grid, None)
-        rs = float(cradii) if _np_isscalar(cradii) else 0.0
-        _lib.check(self._lib.mvx_forward_views(
-            self._handle, _lib.MODES[kind or "single"], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
-            int(c.shape[0]), C_, C.addressof(xfs), B, self._ptr(buf), in_kind, out_kind, self._stream()))
-        return self._finish_out(buf, ret, how)
-
-    # ------------------------------------------------------------------------------------------
-    # POSES (explicit rigid transforms: MVX_XF_POSE_PTR records, mvx_pose_grad_batch)
-    def _pack_pose(self, B, centers, quaternions, translations, on_device):
-        """The (B, 10) float64 block [c | q | t] the records of a posed call point at. With coordinates on this device the block
-        is a tensor there: torch tensors are packed with torch ops (recorded by autograd; their values never visit the host and
-        nothing synchronises), numpy poses are packed on the host and uploaded. With host coordinates: a numpy array."""
-        def shape(x):
-            return tuple(getattr(x, "shape", ()))
-
-        assert shape(quaternions) == (B, 4), f"quaternions does not match dimension: {shape(quaternions)} vs {(B, 4)}"
-        assert shape(translations) == (B, 3), f"translations does not match dimension: {shape(translations)} vs {(B, 3)}"
-        assert centers is None or shape(centers) == (B, 3), f"centers does not match dimension: {shape(centers)} vs {(B, 3)}"
-        parts = [centers, quaternions, translations]
-        if on_device and any(self._on_device(x) for x in parts):
-            dev = [torch.zeros((B, 3), dtype=torch.float64, device=self.device) if x is None else
-                   (x if _is_torch(x) else torch.as_tensor(np.asarray(x, dtype=np.float64))).to(device=self.device, dtype=torch.float64)
-                   for x in parts]
-            return torch.cat(dev, dim=1).contiguous()
-        host = [np.zeros((B, 3)) if x is None else
-                np.asarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float64) for x in parts]
-        block = np.ascontiguousarray(np.concatenate(host, axis=1), dtype=np.float64)
-        return torch.as_tensor(block, device=self.device) if on_device else block
-
-    def _pose_xforms(self, pose, B):
-        """B MVX_XF_POSE_PTR records, record b pointing at row b of the packed poses."""
-        xfs = (_lib.MvxXform * B)()
-        base = self._ptr(pose)
-        for b in range(B):
-            xfs[b].flags = _lib.MVX_XF_POSE_PTR
-            xfs[b].center_ptr = base + 80 * b
-        return xfs
-
-    def forward_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, num_channels=None,
-                            out_grid=None):
-        """forward_batch with one explicit rigid pose per molecule instead of random transforms: atom x of molecule b lands at
-        p = q_b (x - c_b) conj(q_b) + t_b - the centre subtracted, the sandwich product in the random rotation's operation order
-        with q as given (the linear part scales by |q|^2: normalise q in torch beforehand for a pure rotation, autograd carries
-        the normalisation), then t, rounded to float32, added once.
-
-        quaternions (B,4) as (q0, q1, q2, q3); translations (B,3); centers (B,3) | None (c = 0); any float dtype, torch tensors
-        or numpy arrays. Tensors on this voxelizer's device are handed over by pointer: no host round trip, no synchronisation.
-        The other arguments are forward_batch's. On a differentiable voxelizer, `centers`, `quaternions` and `translations`
-        that require grad get dL/dc, dL/dq and dL/dt (mvx_pose_grad_batch; deterministic), next to the gradients of coords,
-        features, radii and sigma. q = 0 gives non-finite pose gradients."""
-        B = np.asarray(offsets).shape[0] - 1
-        pose = self._pack_pose(B, centers, quaternions, translations, self._on_device(coords))
-        return self._forward_batch(coords, offsets, None, channels, radii, num_channels, out_grid,
-                                   xforms=(self._pose_xforms(pose, B), None), fresh_inputs=_is_torch(pose), pose=pose)
-
     def forward_posed_views(self, coords, centers, quaternions, translations, channels, radii, num_channels=None, out_grid=None):
         """forward_views with one explicit rigid pose per view instead of a centre and a random transform: B poses of ONE
         shared cloud (docking poses of a ligand, the 24 cube rotations, poses under refinement) without B copies of it - bit for
@@ -981,14 +978,35 @@ class Voxelizer(BaseVoxelizer):
         the shared tensors. Synchronises the stream once, as forward_views does."""
         return self._forward_views(coords, centers, channels, radii, num_channels, out_grid, posed=(quaternions, translations))
 
-    def select_posed_views(self, coords, centers, quaternions, translations, channels=None, radii=None):
-        """select_views for explicit poses: the atoms each pose of forward_posed_views keeps, as (index, offsets)."""
-        B = int(centers.shape[0])
-        pose = self._pack_pose(B, centers, quaternions, translations, self._on_device(coords))
-        return self._select_views(coords, centers, channels, radii, xforms=(self._pose_xforms(pose, B), None))
+    def _forward_views(self, coords, centers, channels, radii, num_channels=None, out_grid=None, random_translation=0.0,
+                       random_rotation=False, posed=None):
+        """forward_views' body. posed: (quaternions, translations) of forward_posed_views."""
+        call = self._views_call(coords, centers, channels, radii, num_channels, random_translation, random_rotation, posed,
+                                out_grid=out_grid, features="without_graph")
+        B, C_ = call.B, call.C
+        if call.grad:  # select, gather, forward_batch on the gathered rows with the records drawn above
+            with torch.no_grad():
+                index, offsets = self._select(call)
+
+            def take(x):
+                if _is_torch(x):
+                    return x[index.to(x.device)]
+                return np.asarray(x)[index.cpu().numpy()]
+
+            return self._forward_batch(coords[index], offsets, None, None if channels is None else take(channels),
+                                       take(radii) if self.is_radii_type_atom_wise else radii,
+                                       num_channels=C_ if call.mode == "types" else None,
+                                       drawn=(call.xforms, call.centers, call.pose))
+        if out_grid is None:
+            out_grid = self.get_empty_grid(C_, batch_size=B)
+        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
+            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
+        buf, out_kind, ret, how = self._resolve_out(out_grid, None)
+        _lib.check(self._lib.mvx_forward_views(*call.views_args(self), self._ptr(buf), call.in_kind, out_kind, self._stream()))
+        return self._finish_out(buf, ret, how)
 
     # ------------------------------------------------------------------------------------------
-    # SUMS (one grid for a whole batch: mvx_forward_sum_batch)
+    # SUMS (one grid for a whole batch or for the views of a cloud: mvx_forward_sum_batch / mvx_forward_views_sum)
     def forward_sum(self, coords, offsets, centers, channels, radii, weights=None, num_channels=None, out_grid=None,
                     accumulate=False, random_translation=0.0, random_rotation=False):
         """ONE (C,D,H,W) float32 grid: the sum over the B molecules, weighted or not, of the grids forward_batch would write
@@ -1012,52 +1030,36 @@ class Voxelizer(BaseVoxelizer):
                           num_channels=None, out_grid=None, accumulate=False):
         """forward_sum with one explicit rigid pose per molecule (forward_posed_batch's arguments and records): the (weighted)
         sum of the grids of B poses in one float32 (C,D,H,W) grid. Not part of the autograd graph."""
-        self._sum_guard(channels)
-        B = np.asarray(offsets).shape[0] - 1
-        pose = self._pack_pose(B, centers, quaternions, translations, True)
-        return self._forward_sum(coords, offsets, None, channels, radii, weights, num_channels, out_grid, accumulate,
-                                 xforms=(self._pose_xforms(pose, B), None), pose=pose)
+        return self._forward_sum(coords, offsets, centers, channels, radii, weights, num_channels, out_grid, accumulate,
+                                 posed=(quaternions, translations))
 
     def _sum_guard(self, channels):
         """What a summed call refuses before it looks at anything else: the configurations voxelize_sum_kernel does not serve."""
         if self.output != "torch":
             raise ValueError("forward_sum / forward_posed_sum need output='torch': the grid is a tensor on the voxelizer's device")
         alt = "use forward_batch(...).sum(0) (forward_posed_batch(...).sum(0)) instead"
-        if getattr(self, "precision", 32) == 64:
+        if self.precision == 64:
             raise NotImplementedError(f"forward_sum does not support precision 64 (float32 sums only): {alt}")
         if self.is_radii_type_channel_wise and channels is not None and getattr(channels, "ndim", 1) == 2:
             raise NotImplementedError(f"forward_sum does not support channel-wise radii with features: {alt}")
-        D, bd = int(self.dimension), int(getattr(self, "blockdim", None) or 8)
+        D, bd = int(self.dimension), int(self.blockdim)
         if D % 4 != 0:
             raise NotImplementedError(f"forward_sum does not support a dimension that is no multiple of 4 (got {D}): {alt}")
         if -(-D // bd) > 1 and bd % 8 != 0:  # (mvx_plan.lane_range: reference blocks that cut through 2 x 4 x 8 sub-tiles)
             raise NotImplementedError(f"forward_sum does not support blockdim={bd} at dimension {D} (per-lane ranges): {alt}")
 
-    def _sum_weights(self, weights, offsets, N):
-        """The weights of a summed call as the library reads them: None, or (sumN,) float32 on this device."""
-        if weights is None:
-            return None
-        B = offsets.shape[0] - 1
-        w = (weights.detach() if _is_torch(weights) else torch.as_tensor(np.asarray(weights))).to(device=self.device, dtype=torch.float32)
-        shape = tuple(w.shape)
-        assert shape in ((B,), (N,)), f"weights does not match dimension: {shape} vs {(B,)} or {(N,)}"
-        if shape == (B,):
-            lengths = torch.as_tensor(np.diff(offsets), device=self.device)
-            w = torch.repeat_interleave(w, lengths, output_size=N)
-        return w.contiguous()
+    def _sum_rules(self, out_grid, accumulate, weights):
+        """The family rules of a summed call, for the builders' `check`: out_grid / accumulate, then the weights - before
+        anything is converted or drawn. Returns (check, box); the weights as the library reads them land in box[0]."""
+        box = []
 
-    def _forward_sum(self, coords, offsets, centers, channels, radii, weights=None, num_channels=None, out_grid=None,
-                     accumulate=False, random_translation=0.0, random_rotation=False, xforms=None, pose=None):
-        """forward_sum's body, in the order of _forward_batch. xforms / pose: the posed form's records and packed poses."""
-        self._sum_guard(channels)
-        if self._sigma_src is not None:
-            self._sync_sigma()
-        radii, _ = self._scalar_radius(radii)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        B = offsets.shape[0] - 1
-        assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
-        kind, C_ = self._batch_kind(channels, radii, num_channels)
-        self._check_args_batch(coords, channels, kind, radii, C_)
+        def check(B, C_, offsets):
+            self._sum_out_rules(out_grid, accumulate, C_)
+            box.append(self._sum_weights(weights, B, offsets))
+
+        return check, box
+
+    def _sum_out_rules(self, out_grid, accumulate, C_):
         if accumulate and out_grid is None:
             raise ValueError("accumulate=True needs out_grid: there is nothing to add to")
         if out_grid is not None:
@@ -1065,22 +1067,41 @@ class Voxelizer(BaseVoxelizer):
                 f"Output grid dimension incorrect: {tuple(getattr(out_grid, 'shape', ()))} vs {self.grid_dimension(C_)}")
             if not (self._on_device(out_grid) and out_grid.dtype == torch.float32 and out_grid.is_contiguous()):
                 raise ValueError("out_grid of forward_sum must be a contiguous float32 tensor on this voxelizer's device")
-        with torch.no_grad():
-            w = self._sum_weights(weights, offsets, int(coords.shape[0]))
-            c, ch, r, in_kind, keep = self._prepare_inputs(self._device_coords(coords), channels, kind, radii)
-            r, _ = self._pad_type_radii(r, kind, C_)
-            xfs, _ = self._call_xforms(B, centers, in_kind, random_translation, random_rotation, keep, xforms)
-            rs = float(radii) if _np_isscalar(radii) else 0.0
-            return self._sum_call(kind or "single", c, ch, r, rs, offsets, xfs, B, C_, w, out_grid, accumulate)
 
-    def _sum_call(self, mode, c, ch, r, rs, offsets, xfs, B, C_, w, out, accumulate):
-        """One mvx_forward_sum_batch call on device arrays, on the current stream; out None: a new grid."""
+    def _sum_weights(self, weights, B, offsets=None):
+        """The weights of a summed call as the library reads them: None, or float32 on this device - for a batch (offsets
+        given) (sumN,), (B,) weights expanded per atom here; for views (B,) only, expanded on the device in the library."""
+        if weights is None:
+            return None
+        w = (weights.detach() if _is_torch(weights) else torch.as_tensor(np.asarray(weights))).to(device=self.device, dtype=torch.float32)
+        shape = tuple(w.shape)
+        if offsets is None:
+            assert shape == (B,), f"weights does not match dimension: {shape} vs {(B,)}"
+        else:
+            N = int(offsets[-1])
+            assert shape in ((B,), (N,)), f"weights does not match dimension: {shape} vs {(B,)} or {(N,)}"
+            if shape == (B,):
+                lengths = torch.as_tensor(np.diff(offsets), device=self.device)
+                w = torch.repeat_interleave(w, lengths, output_size=N)
+        return w.contiguous()
+
+    def _forward_sum(self, coords, offsets, centers, channels, radii, weights=None, num_channels=None, out_grid=None,
+                     accumulate=False, random_translation=0.0, random_rotation=False, posed=None):
+        """forward_sum's body. posed: (quaternions, translations) of forward_posed_sum."""
+        self._sum_guard(channels)
+        with torch.no_grad():
+            check, w = self._sum_rules(out_grid, accumulate, weights)
+            call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
+                                    posed, device=True, check=check)
+            return self._sum_call(call, w[0], out_grid, accumulate)
+
+    def _sum_call(self, call, w, out, accumulate, coords=None):
+        """One mvx_forward_sum_batch call on device arrays, on the current stream; out None: a new grid. coords: the tensor
+        autograd saved (the field gradient of a score call)."""
         if out is None:
-            out = torch.empty(self.grid_dimension(C_), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.mvx_forward_sum_batch(
-            self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
-            offsets.ctypes.data, None if xfs is None else C.addressof(xfs), B, C_, self._ptr(w), self._ptr(out),
-            1 if accumulate else 0, self._stream()))
+            out = torch.empty(self.grid_dimension(call.C), dtype=torch.float32, device=self.device)
+        _lib.check(self._lib.mvx_forward_sum_batch(*call.batch_args(self, coords), self._ptr(w), self._ptr(out),
+                                                   1 if accumulate else 0, self._stream()))
         return out
 
     def forward_views_sum(self, coords, centers, channels, radii, weights=None, num_channels=None, out_grid=None, accumulate=False,
@@ -1108,43 +1129,22 @@ class Voxelizer(BaseVoxelizer):
         """forward_views_sum with one explicit rigid pose per view (forward_posed_views' arguments and records): the (weighted)
         sum of the grids of B poses of ONE shared cloud - 1 024 docking poses of a ligand - in one float32 (C,D,H,W) grid, bit
         for bit forward_posed_sum on the cloud repeated B times. Not part of the autograd graph."""
-        self._sum_guard(channels)
         return self._forward_views_sum(coords, centers, channels, radii, weights, num_channels, out_grid, accumulate,
                                        posed=(quaternions, translations))
 
     def _forward_views_sum(self, coords, centers, channels, radii, weights=None, num_channels=None, out_grid=None, accumulate=False,
                            random_translation=0.0, random_rotation=False, posed=None):
-        """forward_views_sum's body, in the order of _forward_sum and _forward_views. posed: (quaternions, translations)."""
+        """forward_views_sum's body. posed: (quaternions, translations) of forward_posed_views_sum."""
         self._sum_guard(channels)
-        kind, C_, cradii, _ = self._views_args(coords, centers, channels, radii, num_channels)
-        B = int(centers.shape[0])
-        if accumulate and out_grid is None:
-            raise ValueError("accumulate=True needs out_grid: there is nothing to add to")
-        if out_grid is not None:
-            assert tuple(getattr(out_grid, "shape", ())) == self.grid_dimension(C_), (
-                f"Output grid dimension incorrect: {tuple(getattr(out_grid, 'shape', ()))} vs {self.grid_dimension(C_)}")
-            if not (self._on_device(out_grid) and out_grid.dtype == torch.float32 and out_grid.is_contiguous()):
-                raise ValueError("out_grid of forward_sum must be a contiguous float32 tensor on this voxelizer's device")
         with torch.no_grad():
-            w = None
-            if weights is not None:
-                w = (weights.detach() if _is_torch(weights) else torch.as_tensor(np.asarray(weights))).to(
-                    device=self.device, dtype=torch.float32).contiguous()
-                assert tuple(w.shape) == (B,), f"weights does not match dimension: {tuple(w.shape)} vs {(B,)}"
-            c, ch, r, in_kind, keep = self._views_inputs(self._device_coords(coords), channels, kind, cradii, C_)
-            if posed is None:
-                xfs, _ = self._make_xforms(B, centers, in_kind, random_translation, random_rotation, keep)
-            else:
-                pose = self._pack_pose(B, centers, posed[0], posed[1], True)
-                keep.append(pose)
-                xfs = self._pose_xforms(pose, B)
+            check, w = self._sum_rules(out_grid, accumulate, weights)
+            call = self._views_call(coords, centers, channels, radii, num_channels, random_translation, random_rotation, posed,
+                                    device=True, check=check)
             out = out_grid
             if out is None:
-                out = torch.empty(self.grid_dimension(C_), dtype=torch.float32, device=self.device)
-            rs = float(cradii) if _np_isscalar(cradii) else 0.0
-            _lib.check(self._lib.mvx_forward_views_sum(
-                self._handle, _lib.MODES[kind or "single"], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
-                int(c.shape[0]), C_, C.addressof(xfs), B, self._ptr(w), self._ptr(out), 1 if accumulate else 0, self._stream()))
+                out = torch.empty(self.grid_dimension(call.C), dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.mvx_forward_views_sum(*call.views_args(self), self._ptr(w[0]), self._ptr(out),
+                                                       1 if accumulate else 0, self._stream()))
             return out
 
     def set_sum_parts(self, parts: int):
@@ -1163,7 +1163,7 @@ class Voxelizer(BaseVoxelizer):
     @property
     def sum_parts(self) -> int:
         """The number of parts summed calls are cut into (set_sum_parts); 1: the one-pass sum."""
-        return getattr(self, "_sum_parts", 1)
+        return self._sum_parts
 
     # ------------------------------------------------------------------------------------------
     # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
@@ -1191,11 +1191,10 @@ class Voxelizer(BaseVoxelizer):
         """score_batch with one explicit rigid pose per molecule (forward_posed_batch's arguments and records): the scores of
         B poses against `field`. On a differentiable voxelizer `centers`, `quaternions` and `translations` that require grad get
         dS/dc, dS/dq and dS/dt (mvx_pose_grad_batch on the scaled per-atom gradients)."""
-        self._score_guard(field, True)
-        B = np.asarray(offsets).shape[0] - 1
-        pose = self._pack_pose(B, centers, quaternions, translations, True)
-        return self._score_batch(coords, offsets, None, channels, radii, field, num_channels, per_atom=per_atom,
-                                 xforms=(self._pose_xforms(pose, B), None), pose=pose)
+        self._score_guard(field, True)  # (the guard, then the poses' rules, then everything else)
+        self._check_pose(np.asarray(offsets).shape[0] - 1, centers, quaternions, translations)
+        return self._score_batch(coords, offsets, centers, channels, radii, field, num_channels, per_atom=per_atom,
+                                 posed=(quaternions, translations))
 
     def _score_guard(self, field, shared_field_grad=False):
         """What a score call refuses before it looks at anything else. shared_field_grad: the call is one of those that, on a
@@ -1203,7 +1202,7 @@ class Voxelizer(BaseVoxelizer):
         if self.output != "torch":
             raise ValueError("score_batch / score_posed_batch need output='torch': the scores are tensors on the voxelizer's device")
         if _is_torch(field) and field.requires_grad:
-            if shared_field_grad and getattr(self, "field_grad", False) and field.dim() == 4:
+            if shared_field_grad and self.field_grad and field.dim() == 4:
                 return  # dL/dfield = the weighted summed grid (forward_sum): _ScoreFunction.backward
             raise NotImplementedError("gradients with respect to the field are not supported: dS/dfield is the grid itself - "
                                       "use forward_batch (forward_posed_batch) and (grid * field).sum() for them")
@@ -1221,59 +1220,40 @@ class Voxelizer(BaseVoxelizer):
         shape = tuple(getattr(field, "shape", ()))
         one = self.grid_dimension(C_)
         assert shape in (one, (B,) + one), f"field does not match dimension: {shape} vs {one} or {(B,) + one}"
-        return len(shape) == 5
+
+    def _field_tensor(self, field):
+        """The field of a score call as the library reads it: on this device, of the grid's dtype, contiguous."""
+        return (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
 
     def _score_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, random_translation=0.0,
-                     random_rotation=False, per_atom=False, xforms=None, pose=None):
-        """score_batch's body, in the order of _forward_batch. xforms / pose: the posed form's records and packed poses."""
+                     random_rotation=False, per_atom=False, posed=None):
+        """score_batch's body. posed: (quaternions, translations) of score_posed_batch."""
         self._score_guard(field, True)
-        fgrad = (_is_torch(field) and field.requires_grad and getattr(self, "field_grad", False) and self.differentiable
-                 and torch.is_grad_enabled())
+        fgrad = (_is_torch(field) and field.requires_grad and self.field_grad and self.differentiable and torch.is_grad_enabled())
         if fgrad:  # (what forward_sum cannot serve is refused now, not in backward())
             self._sum_guard(channels)
-        if self._sigma_src is not None:
-            self._sync_sigma()
-        radii, rten = self._scalar_radius(radii)
-        self._score_no_density_grads(radii, rten)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        B = offsets.shape[0] - 1
-        assert offsets[0] == 0 and offsets[-1] == coords.shape[0], "offsets must span coords"
-        kind, C_ = self._batch_kind(channels, radii, num_channels)
-        self._check_args_batch(coords, channels, kind, radii, C_)
-        per_mol = self._check_args_score(field, B, C_)
-        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, None, None)
-        if grad and centers is not None:
-            centers = self._grad_center(centers)
-        c, ch, r, in_kind, keep = self._prepare_inputs(self._device_coords(coords), channels, kind, radii)
-        r, _ = self._pad_type_radii(r, kind, C_)
-        xfs, dev_cen = self._call_xforms(B, centers, in_kind, random_translation, random_rotation, keep, xforms)
+        call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
+                                posed, device=True, score=True, check=lambda B, C_, offsets: self._check_args_score(field, B, C_))
         F = self._field_tensor(field)
-        rs = float(radii) if _np_isscalar(radii) else 0.0
-        N = c.shape[0]
-        mode = kind or "single"
-        feat = ch if kind == "features" else None
+        B, C_, N, grad = call.B, call.C, call.N, call.grad
+        stride = C_ * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per molecule)
+        feat = call.channels if call.mode == "features" else None
         need_gf = grad and feat is not None and feat.requires_grad
 
-        def call():
+        def run():
             scores = torch.empty(B, dtype=torch.float64, device=self.device)
             atoms = torch.empty(N, dtype=torch.float64, device=self.device) if per_atom else None
             gc = torch.empty((N, 3), dtype=torch.float64, device=self.device) if grad else None
             gf = torch.empty((N, C_), dtype=self._tfp, device=self.device) if need_gf else None
-            _lib.check(self._lib.mvx_score_batch(
-                self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(),
-                offsets.ctypes.data, None if xfs is None else C.addressof(xfs), B, C_, self._ptr(F),
-                C_ * self.dimension ** 3 if per_mol else 0, self._ptr(scores), self._ptr(atoms), self._ptr(gc), self._ptr(gf),
-                self._stream()))
+            _lib.check(self._lib.mvx_score_batch(*call.batch_args(self), self._ptr(F), stride, self._ptr(scores), self._ptr(atoms),
+                                                 self._ptr(gc), self._ptr(gf), self._stream()))
             return scores, atoms, gc, gf
 
         if not grad and not fgrad:
-            scores, atoms, _, _ = call()
+            scores, atoms, _, _ = run()
             return (scores, atoms) if per_atom else scores
-        spec = dict(offsets=offsets, xforms=xfs, B=B)
-        if fgrad:  # the call as forward_sum repeats it in backward(): same offsets and records, the random draws included
-            spec.update(mode=mode, channels=ch, radii=r, rs=rs, C=C_, keep=keep)
-        cen = dev_cen if (_is_torch(dev_cen) and self._on_device(dev_cen)) else None
-        out = _ScoreFunction.apply(self, call, spec, per_atom, c, feat, cen, pose, field if fgrad else None)
+        # (with fgrad, backward() repeats the call as forward_sum: same offsets and records, the random draws included)
+        out = _ScoreFunction.apply(self, run, call, per_atom, call.coords, feat, call.centers, call.pose, field if fgrad else None)
         return out if per_atom else out[0]
 
     # ------------------------------------------------------------------------------------------
@@ -1302,7 +1282,6 @@ class Voxelizer(BaseVoxelizer):
         """score_views with one explicit rigid pose per view (forward_posed_views' arguments and records): the scores of B
         poses of ONE shared cloud against `field`. On a differentiable voxelizer `centers`, `quaternions` and `translations`
         that require grad get dS/dc, dS/dq and dS/dt per view (mvx_pose_grad_batch on the scaled rows)."""
-        self._score_guard(field)
         return self._score_views(coords, centers, channels, radii, field, num_channels, per_atom=per_atom,
                                  posed=(quaternions, translations))
 
@@ -1331,29 +1310,17 @@ class Voxelizer(BaseVoxelizer):
 
     def _score_views(self, coords, centers, channels, radii, field, num_channels=None, random_translation=0.0,
                      random_rotation=False, per_atom=False, posed=None):
-        """score_views' body, in the order of _score_batch. posed: (quaternions, translations) of score_posed_views."""
+        """score_views' body. posed: (quaternions, translations) of score_posed_views."""
         self._score_guard(field)
-        kind, C_, cradii, rten = self._views_args(coords, centers, channels, radii, num_channels)
-        self._score_no_density_grads(cradii, rten)
-        B = int(centers.shape[0])
-        per_view = self._check_args_score(field, B, C_)
-        pose = self._pack_pose(B, centers, posed[0], posed[1], True) if posed is not None else None
-        grad = self._grad_wanted(coords, channels if kind == "features" else None, centers if pose is None else pose, None, None)
-        c, ch, r, in_kind, keep = self._views_inputs(self._device_coords(coords), channels, kind, cradii, C_)
-        if pose is None:
-            xfs, dev_cen = self._make_xforms(B, self._grad_center(centers) if grad else centers, in_kind, random_translation,
-                                             random_rotation, keep)
-        else:
-            xfs, dev_cen = self._pose_xforms(pose, B), None
+        call = self._views_call(coords, centers, channels, radii, num_channels, random_translation, random_rotation, posed,
+                                device=True, score=True, check=lambda B, C_, offsets: self._check_args_score(field, B, C_))
         F = self._field_tensor(field)
-        rs = float(cradii) if _np_isscalar(cradii) else 0.0
-        N = int(c.shape[0])
-        mode = kind or "single"
-        feat = ch if kind == "features" else None
+        B, C_, grad = call.B, call.C, call.grad
+        stride = C_ * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per view)
+        feat = call.channels if call.mode == "features" else None
         need_gf = grad and feat is not None and feat.requires_grad
-        stride = C_ * self.dimension ** 3 if per_view else 0
 
-        def call(index, offsets):
+        def run(index, offsets):
             """One mvx_score_views call: with a selection, the per-row outputs this call needs; without, scores alone."""
             total = 0 if index is None else int(offsets[-1])
             scores = torch.empty(B, dtype=torch.float64, device=self.device)
@@ -1364,23 +1331,22 @@ class Voxelizer(BaseVoxelizer):
             some = index is not None and total > 0
             pad = torch.empty(1, dtype=torch.int64, device=self.device) if (index is not None and not some) else None
             _lib.check(self._lib.mvx_score_views(
-                self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), rs, self._radii_type_code(), N, C_,
-                C.addressof(xfs), B, None if index is None else (index if some else pad).data_ptr(),
+                *call.views_args(self), None if index is None else (index if some else pad).data_ptr(),
                 offsets.ctypes.data if index is not None else None, self._ptr(F), stride, self._ptr(scores),
                 self._ptr(atoms) if some else None, self._ptr(gc) if some else None, self._ptr(gf) if some else None,
                 self._stream()))
             return scores, atoms, gc, gf
 
         if not grad and not per_atom:
-            return call(None, None)[0]
+            return run(None, None)[0]
         with torch.no_grad():
-            index, offsets = self._select(c, ch if kind == "types" else None, r, rs, kind, C_, xfs, B, in_kind)
+            index, offsets = self._select(call)
         if not grad:
-            scores, atoms, _, _ = call(index, offsets)
+            scores, atoms, _, _ = run(index, offsets)
             return scores, atoms, index, offsets
-        spec = dict(offsets=offsets, xforms=xfs, B=B, N=N, index=index)
-        cen = dev_cen if (_is_torch(dev_cen) and self._on_device(dev_cen)) else None
-        out = _ScoreViewsFunction.apply(self, lambda: call(index, offsets), spec, per_atom, c, feat, cen, pose)
+        call.index, call.offsets = index, offsets  # (backward(): the rows are laid out in selection order)
+        out = _ScoreViewsFunction.apply(self, lambda: run(index, offsets), call, per_atom, call.coords, feat, call.centers,
+                                        call.pose)
         return (out[0], out[1], index, offsets) if per_atom else out[0]
 
     # ------------------------------------------------------------------------------------------
@@ -1419,47 +1385,43 @@ class Voxelizer(BaseVoxelizer):
         """The mvx_xform record of a single-molecule call (the voxelizer reuses its own), or None."""
         return None if xf is None else _lib.MvxXform.from_buffer_copy(_lib.MvxXform.from_address(xf))
 
-    def _autograd(self, launch, ret, mode, c, f, center, types, r, rs, offsets, xforms, B, C_, rten=None, pose=None):
-        cen = center if (_is_torch(center) and self._on_device(center)) else None
+    def _autograd(self, launch, ret, call):
+        """Run `launch` inside _VoxelizeFunction with the call's record as the backward's spec."""
+        r = call.radii
         # radii_grad: the radii as the call hands them to the library (dtype conversion / type padding recorded by autograd)
         rin = r if (self.radii_grad and _is_torch(r) and r.requires_grad) else None
-        spec = dict(mode=mode, types=types, radii=r, rs=rs, offsets=np.ascontiguousarray(offsets, np.int64), xforms=xforms,
-                    B=B, C=C_, settings=self._grad_settings())
+        call.settings = self._grad_settings()
         sig = self.sigma_tensor
         sig = sig if (sig is not None and sig.requires_grad) else None
-        rsc = rten if (rten is not None and rten.requires_grad) else None
-        return _VoxelizeFunction.apply(self, launch, ret, spec, c, f, cen, rin, sig, rsc, pose)
+        rsc = call.rten if (call.rten is not None and call.rten.requires_grad) else None
+        return _VoxelizeFunction.apply(self, launch, ret, call, call.coords, call.channels if call.mode == "features" else None,
+                                       call.centers, rin, sig, rsc, call.pose)
 
     def _grad_settings(self):
         """What the backward reads from the voxelizer rather than from the call: density, sigma and radii type."""
-        return (self.density_type, float(getattr(self, "_sigma", 0.5)) if self.is_density_type_gaussian else None,
-                self.radii_type)
+        return (self.density_type, float(self._sigma) if self.is_density_type_gaussian else None, self.radii_type)
 
     def _backward(self, spec, c, f, grad, need_features, need_radii=False, need_sigma=False, need_rscalar=False):
         """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None, dL/dradii shaped and typed like the call's radii or None,
-        dL/dsigma and dL/d(scalar radius) as 0-dim float64 device tensors or None) for dL/dgrid = grad, on the current stream."""
+        dL/dsigma and dL/d(scalar radius) as 0-dim float64 device tensors or None) for dL/dgrid = grad, on the current stream.
+        spec: the forward call's _Call; c, f: its coords and features as autograd saved them."""
         now = self._grad_settings()
-        if now != spec["settings"]:
+        if now != spec.settings:
             raise RuntimeError(
                 "the voxelizer's density / sigma / radii type changed between the forward call and backward() "
-                f"(forward: {spec['settings']}, now: {now}); the gradients would be those of another grid. Restore the "
+                f"(forward: {spec.settings}, now: {now}); the gradients would be those of another grid. Restore the "
                 "settings before backward(), or use one voxelizer per setting")
         g = grad.to(device=self.device, dtype=self._gdt).contiguous()
         gc = torch.empty((c.shape[0], 3), dtype=torch.float64, device=self.device)
-        gf = torch.empty((c.shape[0], spec["C"]), dtype=self._tfp, device=self.device) if need_features else None
-        r = spec["radii"]
+        gf = torch.empty((c.shape[0], spec.C), dtype=self._tfp, device=self.device) if need_features else None
+        r = spec.radii
         gr = torch.zeros(r.shape[0], dtype=torch.float64, device=self.device) if need_radii else None
         gs = torch.zeros(2, dtype=torch.float64, device=self.device) if (need_sigma or need_rscalar) else None  # [sigma, radius]
         gsig = gs[0] if need_sigma else None
         grs = gs[1] if need_rscalar else None
         if c.shape[0] == 0:  # no atoms: no gradient rows (the library would see null outputs); channel-wise radii get zeros
             return gc, gf, None if gr is None else gr.to(r.dtype), gsig, grs
-        mode = spec["mode"]
-        ch = f if mode == "features" else spec["types"]
-        xf = spec["xforms"]
-        args = (self._handle, _lib.MODES[mode], self._ptr(c), self._ptr(ch), self._ptr(r), spec["rs"],
-                self._radii_type_code(), spec["offsets"].ctypes.data, None if xf is None else C.addressof(xf), spec["B"],
-                spec["C"], self._ptr(g), self._ptr(gc), self._ptr(gf))
+        args = spec.batch_args(self, c, f if spec.mode == "features" else None) + (self._ptr(g), self._ptr(gc), self._ptr(gf))
         if gs is not None:  # the radius walk with its partials reduced over the call: dL/dsigma, dL/d(scalar radius)
             rc = self._lib.mvx_backward_density_batch(*args, self._ptr(gr), gs.data_ptr() if need_sigma else None,
                                                       gs.data_ptr() + 8 if need_rscalar else None, self._stream())
@@ -1472,11 +1434,11 @@ class Voxelizer(BaseVoxelizer):
 
     def _pose_backward(self, spec, c, gc):
         """dL/dpose (B, 10) float64 = [dL/dc | dL/dq | dL/dt] per molecule from the call's dL/dcoords, on the current stream."""
-        gp = torch.zeros((spec["B"], 10), dtype=torch.float64, device=self.device)
-        if c.shape[0] == 0 or spec["B"] == 0:
+        gp = torch.zeros((spec.B, 10), dtype=torch.float64, device=self.device)
+        if c.shape[0] == 0 or spec.B == 0:
             return gp
-        _lib.check(self._lib.mvx_pose_grad_batch(self._handle, self._ptr(c), self._ptr(gc), spec["offsets"].ctypes.data,
-                                                 C.addressof(spec["xforms"]), spec["B"], gp.data_ptr(), self._stream()))
+        _lib.check(self._lib.mvx_pose_grad_batch(self._handle, self._ptr(c), self._ptr(gc), spec.offsets.ctypes.data,
+                                                 C.addressof(spec.xforms), spec.B, gp.data_ptr(), self._stream()))
         return gp
 
     # ------------------------------------------------------------------------------------------
@@ -1531,12 +1493,21 @@ def _center_grad(g, cen, lengths):
     return -torch.segment_reduce(g, "sum", lengths=lengths, axis=0).reshape(cen.shape)
 
 
+def _rigid_grads(vox, spec, c, g, cen, lengths, need_cen, need_pose):
+    """The tail the three backward() share: (dL/dcentres, dL/d(packed poses)) from the per-atom dL/dcoords `g` of the rows
+    `c`. lengths: as _center_grad takes them."""
+    gcen = _center_grad(g, cen, lengths) if need_cen else None
+    # explicit poses: the per-atom gradients reduced to dL/dc, dL/dq, dL/dt per molecule (autograd splits the block)
+    gpose = vox._pose_backward(spec, c, g) if need_pose else None
+    return gcen, gpose
+
+
 if torch is not None:
 
     class _VoxelizeFunction(torch.autograd.Function):
         """grid = voxelize(coords, features, center, radii, sigma, scalar radius, packed poses): the forward call as it runs without autograd
         (same kernels, same bits); backward = mvx_backward_batch (mvx_backward_radii_batch with radii, mvx_backward_density_batch
-        with sigma or a scalar radius) from the saved inputs and the call's mvx_xform records."""
+        with sigma or a scalar radius) from the saved inputs and the call's record (`spec`, a _Call)."""
 
         @staticmethod
         def forward(ctx, vox, launch, ret, spec, c, f, cen, r, sig, rsc, pose):
@@ -1554,12 +1525,10 @@ if torch is not None:
             gc, gf, gr, gsig, grs = ctx.vox._backward(ctx.spec, c, f, grad, need_f, need_r, need_sig, need_rsc)
             like = lambda g, t: None if g is None else g.to(dtype=t.dtype).reshape(t.shape).to(t.device)  # noqa: E731
             gsig, grs = like(gsig, ctx.scalars[0]), like(grs, ctx.scalars[1])
-            gcen = None
-            if need_cen:
-                gcen = _center_grad(gc, cen, None if cen.numel() == 3 else
-                                    torch.as_tensor(np.diff(ctx.spec["offsets"]), device=gc.device))
-            # explicit poses: the per-atom gradients reduced to dL/dc, dL/dq, dL/dt per molecule (autograd splits the block)
-            gpose = ctx.vox._pose_backward(ctx.spec, c, gc) if need_pose else None
+            lengths = None
+            if need_cen and cen.numel() != 3:
+                lengths = torch.as_tensor(np.diff(ctx.spec.offsets), device=gc.device)
+            gcen, gpose = _rigid_grads(ctx.vox, ctx.spec, c, gc, cen, lengths, need_cen, need_pose)
             return None, None, None, None, gc if need_c else None, gf, gcen, gr, gsig, grs, gpose
 
 
@@ -1569,8 +1538,8 @@ if torch is not None:
         with per_atom, dL/ds_n) and reduces centres and poses as _VoxelizeFunction does. No second walk."""
 
         @staticmethod
-        def forward(ctx, vox, call, spec, per_atom, c, f, cen, pose, field=None):
-            scores, atoms, gc, gf = call()
+        def forward(ctx, vox, run, spec, per_atom, c, f, cen, pose, field=None):
+            scores, atoms, gc, gf = run()
             ctx.vox, ctx.spec = vox, spec
             ctx.save_for_backward(c, cen, pose, gc, gf)
             ctx.field_like = None if field is None else (field.dtype, field.device)
@@ -1583,18 +1552,16 @@ if torch is not None:
         def backward(ctx, gs, ga=None):
             c, cen, pose, gc, gf = ctx.saved_tensors
             need_c, need_f, need_cen, need_pose, need_field = ctx.needs_input_grad[4:9]
-            lengths = torch.as_tensor(np.diff(ctx.spec["offsets"]), device=c.device)
+            lengths = torch.as_tensor(np.diff(ctx.spec.offsets), device=c.device)
             up = _row_upstream(gs, ga, lengths, c.shape[0])
             gcs = gc * up[:, None] if gc is not None else None
             gfs = (gf * up[:, None].to(gf.dtype)) if (need_f and gf is not None) else None
-            gcen = _center_grad(gcs, cen, None if cen.numel() == 3 else lengths) if need_cen else None
-            gpose = ctx.vox._pose_backward(ctx.spec, c, gcs) if need_pose else None
+            gcen, gpose = _rigid_grads(ctx.vox, ctx.spec, c, gcs, cen, None if (need_cen and cen.numel() == 3) else lengths,
+                                       need_cen, need_pose)
             gfield = None
             if need_field and ctx.field_like is not None:
                 # dL/dfield[c, v] = sum_n up_n w[n,c] rho_{n,c}(v): the saved call's grids summed with one float32 weight per atom
-                sp = ctx.spec
-                gfield = ctx.vox._sum_call(sp["mode"], c, sp["channels"], sp["radii"], sp["rs"], sp["offsets"], sp["xforms"], sp["B"],
-                                           sp["C"], up.to(torch.float32), None, False)
+                gfield = ctx.vox._sum_call(ctx.spec, up.to(torch.float32), None, False, coords=c)
                 gfield = gfield.to(dtype=ctx.field_like[0]).to(ctx.field_like[1])
             return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose, gfield
 
@@ -1606,10 +1573,10 @@ if torch is not None:
         backward, no atomics), and reduces centres and poses per view. No second walk."""
 
         @staticmethod
-        def forward(ctx, vox, call, spec, per_atom, c, f, cen, pose):
-            scores, atoms, gc, gf = call()
+        def forward(ctx, vox, run, spec, per_atom, c, f, cen, pose):
+            scores, atoms, gc, gf = run()
             ctx.vox, ctx.spec = vox, spec
-            ctx.save_for_backward(c, cen, pose, gc, gf, spec["index"])
+            ctx.save_for_backward(c, cen, pose, gc, gf, spec.index)
             if per_atom:
                 return scores, atoms
             return (scores,)
@@ -1619,17 +1586,16 @@ if torch is not None:
         def backward(ctx, gs, ga=None):
             c, cen, pose, gc, gf, index = ctx.saved_tensors
             need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[4:8]
-            vox, spec = ctx.vox, ctx.spec
+            vox, spec = ctx.vox, ctx.spec  # (spec.offsets: the selection's; spec.N: the atoms of the shared cloud)
             # (through pinned memory: a pageable copy would synchronise the stream)
-            lengths = torch.from_numpy(np.diff(spec["offsets"])).pin_memory().to(gc.device, non_blocking=True)
+            lengths = torch.from_numpy(np.diff(spec.offsets)).pin_memory().to(gc.device, non_blocking=True)
             up = _row_upstream(gs, ga, lengths, gc.shape[0])  # dL/ds of every (view, atom) row
             gcs = gc * up[:, None]
-            gcoords = vox.views_reduce(gcs, index, spec["offsets"], spec["N"]) if need_c else None
+            gcoords = vox.views_reduce(gcs, index, spec.offsets, spec.N) if need_c else None
             gfeat = None
             if need_f and gf is not None:
-                gfeat = vox.views_reduce(gf * up[:, None].to(gf.dtype), index, spec["offsets"], spec["N"])
-            gcen = _center_grad(gcs, cen, lengths) if need_cen else None
-            gpose = vox._pose_backward(spec, c[index], gcs) if need_pose else None
+                gfeat = vox.views_reduce(gf * up[:, None].to(gf.dtype), index, spec.offsets, spec.N)
+            gcen, gpose = _rigid_grads(vox, spec, c[index] if need_pose else None, gcs, cen, lengths, need_cen, need_pose)
             return None, None, None, None, gcoords, gfeat, gcen, gpose
 
 

@@ -1,0 +1,174 @@
+"""What the Python layer hands to the C ABI, recorded without a device: a fake voxelizer (tests/fake_voxelizer.py,
+output="numpy") whose `_lib` is a stub that copies, inside every call, the scalars and what the pointers refer to. The table
+below runs the host-array entries; tools/record_abi_calls.py writes its record as JSON (tests/golden/abi_calls_host.json, taken
+from the commit before the Python layer was rebuilt) and tests/test_abi_calls_host.py compares the working tree with it.
+
+Arrays are kept as the hex of their bytes, so the comparison is bit for bit; an array that many calls share (the coords, the
+features) is stored once, under a name made of its dtype, length and digest, and the calls hold the name."""
+import ctypes as C
+import hashlib
+
+import numpy as np
+
+from molvoxel_amd.voxelizer.hip import _lib
+from tests.fake_voxelizer import fake
+
+D, N, B, CH = 16, 6, 2, 4
+OFFSETS = [0, 2, 6]
+
+_BATCH = ["h", "coords", "channels", "radii", "rs", "radii_type", "offsets", "xforms", "B", "C", "out", "in_kind", "out_kind",
+          "stream"]
+_ONE = ["h", "coords", "channels", "radii", "rs", "radii_type", "N", "C", "xforms", "out", "in_kind", "out_kind", "stream"]
+ARGS = {
+    "mvx_forward_features": _ONE,
+    "mvx_forward_types": _ONE,
+    "mvx_forward_single": [a for a in _ONE if a not in ("channels", "C")],
+    "mvx_forward_features_batch": _BATCH,
+    "mvx_forward_types_batch": _BATCH,
+    "mvx_forward_single_batch": [a for a in _BATCH if a not in ("channels", "C")],
+    "mvx_forward_views": ["h", "mode", "coords", "channels", "radii", "rs", "radii_type", "N", "C", "xforms", "B", "out", "in_kind",
+                          "out_kind", "stream"],
+    "mvx_select_views": ["h", "coords", "channels", "radii", "rs", "radii_type", "mode", "N", "C", "xforms", "B", "index", "cap",
+                         "offsets_out", "in_kind", "stream"],
+}
+_MODE_OF = {"features": 0, "types": 1, "single": 2}
+
+
+ARRAYS = {}  # name -> hex of the bytes, for every array the calls of record() referred to
+
+
+def _read(addr, dtype, count):
+    """A copy of `count` elements at `addr`, put into ARRAYS; returns its name."""
+    nbytes = int(count) * np.dtype(dtype).itemsize
+    raw = C.string_at(addr, nbytes) if nbytes else b""
+    name = f"{np.dtype(dtype).name}x{int(count)}:{hashlib.sha1(raw).hexdigest()[:12]}"
+    ARRAYS[name] = raw.hex()
+    return name
+
+
+def _records(addr, count):
+    """The fields of `count` mvx_xform records that their flags tell the library to read."""
+    out = []
+    for b in range(count):
+        xf = _lib.MvxXform.from_address(addr + b * C.sizeof(_lib.MvxXform))
+        rec = {"flags": int(xf.flags), "center_ptr": bool(xf.center_ptr)}
+        if xf.flags & _lib.MVX_XF_POSE_PTR:
+            rec["pose"] = _read(xf.center_ptr, np.float64, 10)
+        if xf.flags & _lib.MVX_XF_CENTER and not xf.flags & _lib.MVX_XF_CENTER_PTR:
+            rec["center"] = _read(C.addressof(xf.center), np.float64, 3)
+        if xf.flags & _lib.MVX_XF_ROTATE:
+            rec["quat"] = _read(C.addressof(xf.quat), np.float64, 4)
+        if xf.flags & _lib.MVX_XF_TRANSLATE:
+            rec["trans"] = _read(C.addressof(xf.trans), np.float32, 3)
+        out.append(rec)
+    return out
+
+
+class StubLib:
+    """Stands in for the loaded library: every entry records its call and returns 0."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        names = ARGS[name]
+        types = _lib.SIGNATURES[name][1]
+        assert len(names) == len(types), name
+
+        def entry(*values):
+            assert len(values) == len(names), (name, len(values))
+            a = dict(zip(names, values))
+            call = {"entry": name}
+            for n, t, v in zip(names, types, values):
+                if t is C.c_void_p:  # (the handle and the stream among them)
+                    call[n] = "null" if not v else "set"
+                elif t is C.c_double:
+                    call[n] = float(v).hex()
+                else:
+                    call[n] = int(v)
+            mode = a["mode"] if "mode" in a else next(m for k, m in _MODE_OF.items() if k in name)
+            nb = a.get("B", 1)
+            if a.get("offsets"):
+                call["offsets@"] = _read(a["offsets"], np.int64, nb + 1)
+                n_atoms = int(np.frombuffer(bytes.fromhex(ARRAYS[call["offsets@"]]), np.int64)[-1])
+            else:
+                n_atoms = a["N"]
+            nc = a.get("C", 1)
+            call["coords@"] = _read(a["coords"], np.float64, 3 * n_atoms)
+            if a.get("channels"):
+                call["channels@"] = _read(a["channels"], *((np.float32, n_atoms * nc) if mode == 0 else (np.int32, n_atoms)))
+            if a["radii"]:
+                call["radii@"] = _read(a["radii"], np.float32, n_atoms if a["radii_type"] == _lib.MVX_RADII_ATOM else nc)
+            if a["xforms"]:
+                call["xforms@"] = _records(a["xforms"], nb)
+            self.calls.append(call)
+            return 0
+
+        return entry
+
+
+def _data():
+    rng = np.random.default_rng(20260)
+    return dict(coords=rng.uniform(-3, 3, (N, 3)), features=rng.standard_normal((N, CH)).astype(np.float32),
+                types=np.array([0, 3, 1, 2, 3, 1]), low_types=np.array([0, 2, 1, 2, 0, 1]), center=rng.uniform(-1, 1, 3),
+                centers=rng.uniform(-1, 1, (B, 3)), quats=rng.standard_normal((B, 4)), trans=rng.uniform(-1, 1, (B, 3)).astype(np.float32))
+
+
+def _radii(radii_type, kind):
+    if radii_type == "scalar":
+        return 1.25
+    n = N if radii_type == "atom-wise" else (CH if kind != "single" else 1)
+    return np.linspace(0.75, 1.75, n)  # (float64: the layer converts)
+
+
+def table():
+    """[(row id, seed, radii_type, method name, keyword arguments)]"""
+    d = _data()
+    chan = {"features": d["features"], "types": d["types"], "single": None}
+    rand = dict(random_translation=0.5, random_rotation=True)
+    rows = []
+    for kind in ("features", "types", "single"):
+        for rt in ("scalar", "atom-wise", "channel-wise")[:2 if kind == "single" else 3]:
+            r = _radii(rt, kind)
+            one = dict(coords=d["coords"], radii=r)
+            if kind != "single":
+                one[kind] = chan[kind]
+            for tag, kw in (("plain", dict(center=None)), ("center", dict(center=d["center"])),
+                            ("random", dict(center=None, **rand)), ("center_random", dict(center=d["center"], **rand))):
+                rows.append((f"forward_{kind}-{rt}-{tag}", rt, f"forward_{kind}", dict(one, **kw)))
+            bat = dict(coords=d["coords"], offsets=np.array(OFFSETS), channels=chan[kind], radii=r)
+            for tag, kw in (("plain", dict(centers=None)), ("centers", dict(centers=d["centers"])),
+                            ("random", dict(centers=d["centers"], **rand)), ("random_only", dict(centers=None, **rand))):
+                rows.append((f"forward_batch-{kind}-{rt}-{tag}", rt, "forward_batch", dict(bat, **kw)))
+            pose = dict(quaternions=d["quats"], translations=d["trans"])
+            bat.pop("offsets")
+            for tag, cen in (("centers", d["centers"]), ("origin", None)):
+                rows.append((f"forward_posed_batch-{kind}-{rt}-{tag}", rt, "forward_posed_batch",
+                             dict(bat, offsets=np.array(OFFSETS), centers=cen, **pose)))
+            rows.append((f"forward_views-{kind}-{rt}-plain", rt, "forward_views", dict(bat, centers=d["centers"])))
+            rows.append((f"forward_views-{kind}-{rt}-random", rt, "forward_views", dict(bat, centers=d["centers"], **rand)))
+            rows.append((f"forward_posed_views-{kind}-{rt}", rt, "forward_posed_views", dict(bat, centers=d["centers"], **pose)))
+    # channel-wise radii shorter than the channel count: padded with ones
+    short = np.array([0.9, 1.1, 1.3])
+    rows.append(("forward_types-padded", "channel-wise", "forward_types",
+                 dict(coords=d["coords"], center=d["center"], types=d["low_types"], radii=short,
+                      out_grid=np.empty((CH, D, D, D), np.float32))))
+    bat = dict(coords=d["coords"], channels=d["low_types"], radii=short, num_channels=CH)
+    rows.append(("forward_batch-padded", "channel-wise", "forward_batch", dict(bat, offsets=np.array(OFFSETS), centers=d["centers"])))
+    rows.append(("forward_views-padded", "channel-wise", "forward_views", dict(bat, centers=d["centers"])))
+    return [(rid, 1000 + i, rt, method, kw) for i, (rid, rt, method, kw) in enumerate(rows)]
+
+
+def record():
+    """{"rows": {row id: the calls, the grid's shape, the RNG's next draw}, "arrays": ARRAYS} of the whole table on the
+    imported Python layer."""
+    ARRAYS.clear()
+    out = {}
+    for rid, seed, rt, method, kw in table():
+        stub = StubLib()
+        vox = fake(rt, D, output="numpy", _lib=stub)
+        np.random.seed(seed)
+        grid = getattr(vox, method)(**kw)
+        assert isinstance(grid, np.ndarray), rid
+        out[rid] = dict(calls=stub.calls, shape=list(grid.shape), rng_after=float(np.random.random()).hex())
+    return {"rows": out, "arrays": dict(ARRAYS)}

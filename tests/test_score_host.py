@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MVX_ERR_INVALID = -1
@@ -106,20 +107,6 @@ def test_ctypes_prototype_matches_the_header():
 
 
 # ---- the Python layer ------------------------------------------------------------------------------------------------------
-def _fake(radii_type="scalar", **attrs):
-    """A voxelizer without a handle: enough of one for the checks that fire before the library is needed."""
-    from molvoxel_amd.voxelizer.contract import BaseVoxelizer
-    from molvoxel_amd.voxelizer.hip.voxelizer import Voxelizer
-
-    v = Voxelizer.__new__(Voxelizer)
-    BaseVoxelizer.__init__(v, 0.5, 16, radii_type, "gaussian")
-    v._handle = None
-    for k, val in dict(dict(output="torch", differentiable=False, radii_grad=False, sigma_grad=False, _sigma_src=None,
-                            _rscalar_src=None), **attrs).items():
-        setattr(v, k, val)
-    return v
-
-
 def _args(N=6, C_=4, B=2):
     rng = np.random.default_rng(0)
     return dict(coords=rng.uniform(-2, 2, (N, 3)), offsets=np.array([0, 2, N][:B + 1]), centers=None,

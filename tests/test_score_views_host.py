@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 from tests import views_reduce_reference as vr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -160,20 +161,6 @@ def test_ctypes_prototypes_match_the_header(name, names):
 
 
 # ---- the Python layer ------------------------------------------------------------------------------------------------------
-def _fake(radii_type="scalar", **attrs):
-    """A voxelizer without a handle: enough of one for the checks that fire before the library is needed."""
-    from molvoxel_amd.voxelizer.contract import BaseVoxelizer
-    from molvoxel_amd.voxelizer.hip.voxelizer import Voxelizer
-
-    v = Voxelizer.__new__(Voxelizer)
-    BaseVoxelizer.__init__(v, 0.5, 16, radii_type, "gaussian")
-    v._handle = None
-    for k, val in dict(dict(output="torch", differentiable=False, radii_grad=False, sigma_grad=False, _sigma_src=None,
-                            _rscalar_src=None), **attrs).items():
-        setattr(v, k, val)
-    return v
-
-
 def _args(N=6, C_=4, B=2):
     rng = np.random.default_rng(0)
     return dict(coords=rng.uniform(-2, 2, (N, 3)), centers=np.zeros((B, 3)), channels=rng.standard_normal((N, C_)).astype(np.float32),

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 from tests import sum_rows as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -106,20 +107,6 @@ def test_channel_chunks_and_waves_per_slab():
 
 
 # ---- the method surface ------------------------------------------------------------------------------------------------------
-def _fake(radii_type="scalar", dimension=16, **attrs):
-    """A voxelizer without a handle (as tests/test_score_host.py builds it)."""
-    from molvoxel_amd.voxelizer.contract import BaseVoxelizer
-    from molvoxel_amd.voxelizer.hip.voxelizer import Voxelizer
-
-    v = Voxelizer.__new__(Voxelizer)
-    BaseVoxelizer.__init__(v, 0.5, dimension, radii_type, "gaussian")
-    v._handle = None
-    for k, val in dict(dict(output="torch", differentiable=False, radii_grad=False, sigma_grad=False, _sigma_src=None,
-                            _rscalar_src=None), **attrs).items():
-        setattr(v, k, val)
-    return v
-
-
 def _args(N=6, C_=4, B=2):
     rng = np.random.default_rng(0)
     return dict(coords=rng.uniform(-2, 2, (N, 3)), offsets=np.array([0, 2, N][:B + 1]), centers=None,

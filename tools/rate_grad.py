@@ -63,7 +63,7 @@ def setup(wl, B, order):
     G = torch.randn_like(grid)
     fn = grid.grad_fn
     spec = fn.spec
-    cs, fs, _ = fn.saved_tensors
+    cs, fs = spec.coords, (spec.channels if spec.mode == "features" else None)  # the call's record: the arrays as the library read them
     fwd = lambda: vox.forward_batch(c.detach(), offsets, None, chan.detach(), radii, num_channels=wl.num_channels)
     bwd = lambda: vox._backward(spec, cs, fs, G, wl.mode == "features")
     return vox, fwd, bwd, G.numel() * G.element_size()

@@ -51,8 +51,9 @@ def setup(wl, B, kind):
     grid = vox.forward_batch(c, offsets, None, chan, radii)
     G = torch.randn_like(grid)
     fn = grid.grad_fn
-    cs, fs, _ = fn.saved_tensors
-    call = lambda *need: (lambda: vox._backward(fn.spec, cs, fs, G, True, *need))  # noqa: E731
+    spec = fn.spec
+    cs, fs = spec.coords, (spec.channels if spec.mode == "features" else None)  # the call's record: the arrays as the library read them
+    call = lambda *need: (lambda: vox._backward(spec, cs, fs, G, True, *need))  # noqa: E731
     # (need_radii, need_sigma, need_rscalar)
     if kind == "scalar":
         return C_, call(), {"sigma": call(False, True, False), "radius": call(False, False, True), "sigma+radius": call(False, True, True)}

@@ -58,7 +58,7 @@ def setup(wl, B, kind):
     G = torch.randn_like(grid)
     fn = grid.grad_fn
     spec = fn.spec
-    cs, fs, _ = fn.saved_tensors
+    cs, fs = spec.coords, (spec.channels if spec.mode == "features" else None)  # the call's record: the arrays as the library read them
     feat = wl.mode == "features"
     bwd = lambda: vox._backward(spec, cs, fs, G, feat)  # noqa: E731
     bwd_r = lambda: vox._backward(spec, cs, fs, G, feat, True)  # noqa: E731
