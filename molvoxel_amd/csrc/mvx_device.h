@@ -20,6 +20,7 @@
 #include "mvx_tuning.h"
 
 #include <math.h>
+#include <atomic>
 #include <type_traits>
 #include <hip/hip_bf16.h>
 #include <hip/hip_ext.h>
@@ -1129,22 +1130,28 @@ __device__ __forceinline__ void filter_walk(const bool xl, typename Ops::Acc &ac
 // launch helpers (host)
 // ------------------------------------------------------------------------------------------------
 // Dynamic LDS above the default 64 KB limit needs an opt-in per kernel and per device.
+// What has been opted in is remembered per kernel (lds_state<Kern>: one state per instantiation, never shared by two kernels)
+// and per device. Relaxed atomics: two threads that race both set the attribute, which is harmless.
 constexpr int MAX_DEVICES = 64;
 struct LdsLimit {
-    size_t raised[MAX_DEVICES] = {};
+    std::atomic<size_t> raised[MAX_DEVICES] = {};
 };
+template <auto Kern>
+static LdsLimit &lds_state() {
+    static LdsLimit state;
+    return state;
+}
 
-template <typename K>
-static hipError_t raise_lds_limit(K kernel, size_t lds, LdsLimit &state) {
+static hipError_t raise_lds_limit(const void *kernel, size_t lds, LdsLimit &state) {
     if (lds <= 64 * 1024) return hipSuccess;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidDevice;
-    if (lds > state.raised[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > state.raised[dev].load(std::memory_order_relaxed)) {
+        e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
-        state.raised[dev] = lds;
+        state.raised[dev].store(lds, std::memory_order_relaxed);
     }
     return hipSuccess;
 }
@@ -1165,6 +1172,28 @@ static void launch_profiled(K kern, dim3 grid, dim3 block, size_t lds, hipStream
     ev.start = ev.stop = nullptr;
     if (e0) hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, s, e0, e1, 0u, args...);
     else hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+}
+
+// The one launch sequence of the voxelize kernels: opt in to `lds` bytes of dynamic LDS where this kernel on this device has
+// not yet, launch (with the pending profiling events, if any), report the launch error.
+template <auto Kern, typename... A>
+static hipError_t launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+    const hipError_t e = raise_lds_limit(reinterpret_cast<const void *>(Kern), lds, lds_state<Kern>());
+    if (e != hipSuccess) return e;
+    launch_profiled(Kern, grid, block, lds, s, args...);
+    return hipGetLastError();
+}
+
+// The grid type of a call (VoxArgs::bf16, ::ndhwc) as the kernels' OT parameter: fn(GridType<OT>{}), OT = float | __bf16 |
+// Ndhwc<float> | Ndhwc<__bf16>.
+template <typename OT>
+struct GridType {
+    typedef OT type;
+};
+template <typename Fn>
+static hipError_t for_grid_type(bool bf16, bool ndhwc, Fn &&fn) {
+    if (ndhwc) return bf16 ? fn(GridType<Ndhwc<__bf16>>{}) : fn(GridType<Ndhwc<float>>{});
+    return bf16 ? fn(GridType<__bf16>{}) : fn(GridType<float>{});
 }
 
 // blocks per molecule of the slab kernels

@@ -545,15 +545,10 @@ static hipError_t for_kernel64(const KernelKey64 &k, Fn &&fn) {
 
 template <typename Ops, int MAXT = 1024, int WPE = 1>
 static hipError_t launch_dense(const VoxArgs &a, size_t lds, unsigned grid, unsigned total, hipStream_t s) {
-    static LdsLimit raised;
     const VoxParams &p = a.p;
     if (p.NW * 64 > MAXT) return hipErrorInvalidConfiguration;
-    auto kern = &voxelize_dense_kernel<Ops, MAXT, WPE>;
-    hipError_t e = raise_lds_limit(kern, lds, raised);
-    if (e != hipSuccess) return e;
-    launch_profiled(kern, dim3(grid), dim3(p.NW * 64), lds, s, a.rec, a.w, a.xlist, a.slist, a.slist_ext, a.offsets, a.n_one, a.Tc, a.kc,
-                    a.out, a.p, (unsigned)(p.nzc * p.nsy * p.nsx), total);
-    return hipGetLastError();
+    return launch_kernel<voxelize_dense_kernel<Ops, MAXT, WPE>>(dim3(grid), dim3(p.NW * 64), lds, s, a.rec, a.w, a.xlist, a.slist, a.slist_ext,
+                                                                a.offsets, a.n_one, a.Tc, a.kc, a.out, a.p, (unsigned)(p.nzc * p.nsy * p.nsx), total);
 }
 
 struct Dense64Fn {
@@ -579,20 +574,15 @@ struct Dense64Fn {
 
 template <bool GAUSS, bool LANE_RANGE>
 static hipError_t launch_mx64(const VoxArgs &a, hipStream_t s) {
-    static LdsLimit raised;
     VoxParams p = a.p;
     const size_t main_lds = voxelize_mx64_lds_bytes(p.NW), lds = main_lds + 512;
     p.dcap = (int32_t)main_lds; // where the kernel keeps its copy of the 2^(j/64) table
-    auto kern = &voxelize64_kernel<GAUSS, LANE_RANGE, 512>;
-    hipError_t e = raise_lds_limit(kern, lds, raised);
-    if (e != hipSuccess) return e;
     const int per = 65535 / p.ncc; // molecules per launch (gridDim.y limit); the profiling bracket rides on the first launch
     for (int m0 = 0; m0 < p.B; m0 += per) {
         p.b0 = m0;
         const int nb = p.B - m0 < per ? p.B - m0 : per;
-        launch_profiled(kern, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), lds, s, a.rec, a.w, a.slist,
-                        a.slist_ext, static_cast<double *>(a.out), p);
-        e = hipGetLastError();
+        const hipError_t e = launch_kernel<voxelize64_kernel<GAUSS, LANE_RANGE, 512>>(dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), lds, s,
+                                                                                      a.rec, a.w, a.slist, a.slist_ext, static_cast<double *>(a.out), p);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

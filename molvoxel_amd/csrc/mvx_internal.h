@@ -131,8 +131,8 @@ struct VoxArgs {
     const double *Tc;      // channel-wise features: per-channel d2 thresholds (float64 grids: the radii themselves)
     const float *kc;       //                        per-channel gaussian coefficients
     void *out;             // (B, C, D, D, D) float, or double for float64 grids, or bfloat16 (bf16)
-    int32_t bf16;          // 1: a bfloat16 grid (mvx_config.grid_type = MVX_GRID_BF16): the bfloat16 twins of the float32 kernels
-    int32_t ndhwc;         // 1: a channels-last grid (mvx_set_grid_layout, C > 1): the kernels' channels-last twins; p.vec_store then says
+    int32_t bf16;          // 1: a bfloat16 grid (mvx_config.grid_type = MVX_GRID_BF16): the float32 kernels' __bf16 instantiations
+    int32_t ndhwc;         // 1: a channels-last grid (mvx_set_grid_layout, C > 1): their Ndhwc<...> instantiations; p.vec_store then says
                            // whether the channel runs are 16-byte aligned
     int32_t narrow_sub;    // test / A-B switch ("narrow_sub"): sub-tiles per wave of narrow chunks - 1 (voxelize_kernel), 2, 4; 0 = the rule
     VoxParams p;
@@ -160,7 +160,7 @@ hipError_t launch_voxelize_grouped(const VoxArgs &a, int32_t nb, bool gauss, boo
 hipError_t launch_voxelize64(const VoxArgs &a, int32_t ct, bool gauss, bool chanwise, bool lane_range, hipStream_t s);
 // the whole call in one launch (voxelize_pair_kernel, mvx_pair.hip: float32 grids, NW <= 8): no workspace, no pre-pass.
 // max_atoms: the largest molecule of the call (sizes the per-wave candidate lists); lane_range: sub-tiles cut by reference blocks
-// bf16: out is a bfloat16 grid (the bfloat16 twin of the kernel), else float; ndhwc: a channels-last grid (the channels-last twins)
+// bf16: out is a bfloat16 grid, else float; ndhwc: a channels-last grid (the kernel's instantiation for that grid type)
 hipError_t launch_voxelize_direct(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, void *out, bool bf16, bool ndhwc, int32_t ct,
                                   bool gauss, bool lane_range, hipStream_t s);
 void scalar_radius_constants(double radius_scalar, float sigma32, bool gauss, double *T, float *k);
@@ -172,6 +172,7 @@ hipError_t set_diag_buffer(void *p);
 hipError_t set_diag_buffer_xb(void *p);
 #endif
 size_t voxelize_lds_bytes(int32_t ct, int32_t NW, int32_t crmax);
+size_t voxelize_mx_lds_bytes(int32_t NW); // the matrix-core kernels: rows of two rounds or the write-out tile of eight channels, whichever is larger
 int32_t voxelize_dcap(int32_t ct, int32_t NW);
 
 } // namespace mvx

@@ -107,52 +107,24 @@ __device__ __forceinline__ int row_prefix16(int v) {
     return v;
 }
 
-template <int CT, bool GAUSS, bool XF, bool LR = false>
-__global__ void __launch_bounds__(1024) voxelize_pair_kernel(const DirectArgs A, float *__restrict__ out, const VoxParams P) {
-    typedef typename PairOps<CT, GAUSS, LR>::type Ops;
+// OT: the grid type (float, __bf16, or a channels-last tag Ndhwc<...>): the same body with that type's write-out (Ops<..., OT>)
+template <int CT, bool GAUSS, bool XF, bool LR = false, typename OT = float>
+__global__ void __launch_bounds__(1024)
+    voxelize_pair_kernel(const DirectArgs A, typename grid_elem<OT>::type *__restrict__ out, const VoxParams P) {
+    typedef typename PairOps<CT, GAUSS, LR, OT>::type Ops;
 #include "mvx_pair_body.inc"
 }
-// bfloat16 grids: the same body with the bfloat16 write-out (Ops<..., __bf16>), under a name of its own
-template <int CT, bool GAUSS, bool XF, bool LR = false>
-__global__ void __launch_bounds__(1024) voxelize_pair_bf16_kernel(const DirectArgs A, __bf16 *__restrict__ out, const VoxParams P) {
-    typedef typename PairOps<CT, GAUSS, LR, __bf16>::type Ops;
-#include "mvx_pair_body.inc"
-}
-// channels-last (NDHWC) grids: the same body with the channels-last write-out (Ops<..., Ndhwc<...>>), under names of their own
-template <int CT, bool GAUSS, bool XF, bool LR = false>
-__global__ void __launch_bounds__(1024) voxelize_pair_ndhwc_kernel(const DirectArgs A, float *__restrict__ out, const VoxParams P) {
-    typedef typename PairOps<CT, GAUSS, LR, Ndhwc<float>>::type Ops;
-#include "mvx_pair_body.inc"
-}
-template <int CT, bool GAUSS, bool XF, bool LR = false>
-__global__ void __launch_bounds__(1024) voxelize_pair_bf16_ndhwc_kernel(const DirectArgs A, __bf16 *__restrict__ out, const VoxParams P) {
-    typedef typename PairOps<CT, GAUSS, LR, Ndhwc<__bf16>>::type Ops;
-#include "mvx_pair_body.inc"
-}
-template <int CT, bool G, bool XF, bool LR>
-static auto pair_kernel(Ndhwc<float> *) { return &voxelize_pair_ndhwc_kernel<CT, G, XF, LR>; }
-template <int CT, bool G, bool XF, bool LR>
-static auto pair_kernel(Ndhwc<__bf16> *) { return &voxelize_pair_bf16_ndhwc_kernel<CT, G, XF, LR>; }
-template <int CT, bool G, bool XF, bool LR>
-static auto pair_kernel(float *) { return &voxelize_pair_kernel<CT, G, XF, LR>; }
-template <int CT, bool G, bool XF, bool LR>
-static auto pair_kernel(__bf16 *) { return &voxelize_pair_bf16_kernel<CT, G, XF, LR>; }
 
 // ------------------------------------------------------------------------------------------------
 // dispatch
 // ------------------------------------------------------------------------------------------------
 template <int CT, bool GAUSS, bool XF, bool LR, typename OT>
-static hipError_t launch_pair_t(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, OT *out_, hipStream_t s) {
-    typename grid_elem<OT>::type *out = reinterpret_cast<typename grid_elem<OT>::type *>(out_); // (OT: the element type or its channels-last tag)
-    static LdsLimit raised;
+static hipError_t launch_pair_t(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, void *out, hipStream_t s) {
     VoxParams q = p;
     q.dcap = pair_segw(max_atoms, p.NW);
-    const size_t lds = pair_lds_bytes(CT, p.NW, q.dcap);
-    auto kern = pair_kernel<CT, GAUSS, XF, LR>(out_);
-    hipError_t e = raise_lds_limit(kern, lds, raised);
-    if (e != hipSuccess) return e;
-    launch_profiled(kern, dim3((unsigned)(p.nsy * ((p.nsx + 1) / 2)), (unsigned)(p.B * p.ncc)), dim3(p.NW * 128), lds, s, d, out, q);
-    return hipGetLastError();
+    return launch_kernel<voxelize_pair_kernel<CT, GAUSS, XF, LR, OT>>(dim3((unsigned)(p.nsy * ((p.nsx + 1) / 2)), (unsigned)(p.B * p.ncc)),
+                                                                      dim3(p.NW * 128), pair_lds_bytes(CT, p.NW, q.dcap), s, d,
+                                                                      static_cast<typename grid_elem<OT>::type *>(out), q);
 }
 
 // The whole call in one launch: float32 grids with whole rows per slab (NW <= 8); rows of whole 16-byte quads or not (run-wise
@@ -160,19 +132,19 @@ static hipError_t launch_pair_t(const DirectArgs &d, const VoxParams &p, int64_t
 // cut by reference blocks (blockdim 4, 5, 12, ...) - built with the transform-capable instantiation only (an identity
 // transform costs that rare case little and keeps the number of kernels down).
 template <typename OT>
-static hipError_t launch_direct_t(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, OT *out, int32_t ct, bool gauss,
+static hipError_t launch_direct_t(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, void *out, int32_t ct, bool gauss,
                                   bool lane_range, hipStream_t s) {
     if (p.B <= 0) return hipSuccess;
     if (p.NW > 8 || p.nzc != 1 || (long long)p.B * p.ncc > 65535) return hipErrorInvalidConfiguration;
     if (max_atoms > (int64_t)100000000) return hipErrorInvalidConfiguration; // (24-byte rows addressed with 32-bit offsets; plan_call stops at 131 072 atoms)
     const bool xf = d.pa.xforms != nullptr || d.pa.xf_one.flags != 0;
-#define MVX_CASE(CT_)                                                                                                       \
-    if (ct == CT_) {                                                                                                        \
-        if (lane_range)                                                                                                     \
-            return gauss ? launch_pair_t<CT_, true, true, true>(d, p, max_atoms, out, s) : launch_pair_t<CT_, false, true, true>(d, p, max_atoms, out, s); \
-        if (gauss)                                                                                                          \
-            return xf ? launch_pair_t<CT_, true, true, false>(d, p, max_atoms, out, s) : launch_pair_t<CT_, true, false, false>(d, p, max_atoms, out, s); \
-        return xf ? launch_pair_t<CT_, false, true, false>(d, p, max_atoms, out, s) : launch_pair_t<CT_, false, false, false>(d, p, max_atoms, out, s);   \
+#define MVX_CASE(CT_)                                                                                                                   \
+    if (ct == CT_) {                                                                                                                    \
+        if (lane_range)                                                                                                                 \
+            return gauss ? launch_pair_t<CT_, true, true, true, OT>(d, p, max_atoms, out, s) : launch_pair_t<CT_, false, true, true, OT>(d, p, max_atoms, out, s); \
+        if (gauss)                                                                                                                      \
+            return xf ? launch_pair_t<CT_, true, true, false, OT>(d, p, max_atoms, out, s) : launch_pair_t<CT_, true, false, false, OT>(d, p, max_atoms, out, s); \
+        return xf ? launch_pair_t<CT_, false, true, false, OT>(d, p, max_atoms, out, s) : launch_pair_t<CT_, false, false, false, OT>(d, p, max_atoms, out, s);   \
     }
     MVX_CASE(1)
     MVX_CASE(4)
@@ -184,11 +156,7 @@ static hipError_t launch_direct_t(const DirectArgs &d, const VoxParams &p, int64
 }
 hipError_t launch_voxelize_direct(const DirectArgs &d, const VoxParams &p, int64_t max_atoms, void *out, bool bf16, bool ndhwc, int32_t ct,
                                   bool gauss, bool lane_range, hipStream_t s) {
-    if (ndhwc)
-        return bf16 ? launch_direct_t(d, p, max_atoms, static_cast<Ndhwc<__bf16> *>(out), ct, gauss, lane_range, s)
-                    : launch_direct_t(d, p, max_atoms, static_cast<Ndhwc<float> *>(out), ct, gauss, lane_range, s);
-    return bf16 ? launch_direct_t(d, p, max_atoms, static_cast<__bf16 *>(out), ct, gauss, lane_range, s)
-                : launch_direct_t(d, p, max_atoms, static_cast<float *>(out), ct, gauss, lane_range, s);
+    return for_grid_type(bf16, ndhwc, [&](auto g) { return launch_direct_t<typename decltype(g)::type>(d, p, max_atoms, out, ct, gauss, lane_range, s); });
 }
 
 void scalar_radius_constants(double radius_scalar, float sigma32, bool gauss, double *T, float *k) {

@@ -1,5 +1,5 @@
-// mvx_pair_body.inc - the body of voxelize_pair_kernel (mvx_pair.hip), included by the float32 kernel and by its bfloat16 twin
-// voxelize_pair_bf16_kernel: one text, two kernels whose names and float32 code stay apart. Expects the typedef Ops (PairOps<...>)
+// mvx_pair_body.inc - the body of voxelize_pair_kernel (mvx_pair.hip), kept as an included text as mvx_slab_body.inc is: one
+// instantiation per grid type (the kernel's OT parameter) whose float32 code stays apart. Expects the typedef Ops (PairOps<...>)
 // and the kernel parameters A, out, P; CT, GAUSS, XF, LR are the kernel's template parameters.
     constexpr int SW = Ops::SW;
     constexpr int WW = Ops::WW; // weight words per row

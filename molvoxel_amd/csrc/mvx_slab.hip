@@ -31,7 +31,7 @@ size_t voxelize_lds_bytes(int32_t ct, int32_t NW, int32_t crmax) {
 }
 
 // (the matrix-core kernels keep the rows of TWO rounds: stage_first_rounds)
-static size_t voxelize_mx_lds_bytes(int32_t NW) { return std::max(voxelize_lds_bytes(32, NW, MX_CR), (size_t)2 * 64 * cand_stride_words(32) * 4); }
+size_t voxelize_mx_lds_bytes(int32_t NW) { return std::max(voxelize_lds_bytes(32, NW, MX_CR), (size_t)2 * 64 * cand_stride_words(32) * 4); }
 
 // voxelize_kernel's arithmetic: 32-channel chunks go to the matrix cores (OpsMx32), narrower chunks to the vector ALU in
 // candidate pairs (OpsPair); the per-lane-range variants keep one voxel per lane and candidate (OpsF32)
@@ -59,42 +59,16 @@ struct SlabOps<32, GAUSS, true, true, OT> {
     typedef OpsMx32<GAUSS, true, true, true, OT> type;
 };
 
-template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
+// OT: the grid type - float, __bf16 (bfloat16 grids, mvx_config.grid_type = MVX_GRID_BF16: only the store of the write-out differs)
+// or a channels-last tag (Ndhwc<float>, Ndhwc<__bf16>, mvx_set_grid_layout: every lane stores its voxel's channel run from
+// registers; slabs of at most 8 waves only - plan_call cuts longer rows: a cut costs that layout nothing, a voxel's channels are
+// whole 16-byte groups). One instantiation per grid type over the same slab body; grid_elem<OT> is the element type of `out`.
+template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false, typename OT = float>
 __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
     voxelize_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                    const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc, float *__restrict__ out,
-                    const VoxParams P) {
-    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED>::type Ops;
-#include "mvx_slab_body.inc"
-}
-// bfloat16 grids (mvx_config.grid_type = MVX_GRID_BF16): the same slab body; only the store of the write-out differs (Ops<..., __bf16>).
-// Every float32 slab kernel has such a twin of its own name: the float32 kernels and their names stay as they are.
-template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
-__global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
-    voxelize_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                         const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
-                         __bf16 *__restrict__ out, const VoxParams P) {
-    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED, __bf16>::type Ops;
-#include "mvx_slab_body.inc"
-}
-
-// channels-last (NDHWC) grids (mvx_set_grid_layout): the same slab body with the channels-last write-out (Ops<..., Ndhwc<float>> /
-// Ops<..., Ndhwc<__bf16>>: every lane stores its voxel's channel run from registers), under names of their own. Slabs of at most
-// 8 waves only (plan_call cuts longer rows: a cut costs this layout nothing, a voxel's channels are whole 16-byte groups).
-template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
-__global__ void __launch_bounds__(MAXT, 8)
-    voxelize_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                          const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc, float *__restrict__ out,
-                          const VoxParams P) {
-    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED, Ndhwc<float>>::type Ops;
-#include "mvx_slab_body.inc"
-}
-template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT, bool GROUPED = false>
-__global__ void __launch_bounds__(MAXT, 8)
-    voxelize_bf16_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                               const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
-                               __bf16 *__restrict__ out, const VoxParams P) {
-    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED, Ndhwc<__bf16>>::type Ops;
+                    const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
+                    typename grid_elem<OT>::type *__restrict__ out, const VoxParams P) {
+    typedef typename SlabOps<CT, GAUSS, LANE_RANGE, GROUPED, OT>::type Ops;
 #include "mvx_slab_body.inc"
 }
 
@@ -110,7 +84,6 @@ __global__ void __launch_bounds__(MAXT, 8)
 // Waves per SIMD the kernel is compiled for: its natural register need with two sub-tiles is 66 / 72 / 80 for 1 / 4 / 8
 // channels (accumulator sets, eight row loads in flight); at the 64 of voxelize_kernel it spilled 1 ... 17 registers.
 // (16 channels: 96 registers and no gain over one sub-tile per wave, 0.228 ms both - they keep voxelize_kernel.)
-constexpr int narrow_waves_per_simd(int ct, int nsub) { return 8; }
 template <int CT, bool GAUSS, int NSUB, typename OT>
 __device__ __forceinline__ void narrow_body(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
                                             const uint2 *__restrict__ slist_ext, typename grid_elem<OT>::type *__restrict__ out, const VoxParams &P) {
@@ -282,50 +255,22 @@ __device__ __forceinline__ void narrow_body(const unsigned *__restrict__ rec, co
         }
     }
 }
-template <int CT, bool GAUSS, int NSUB>
-__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
+template <int CT, bool GAUSS, int NSUB, typename OT = float>
+__global__ void __launch_bounds__(512, 8)
     voxelize_narrow_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                           const uint2 *__restrict__ slist_ext, float *__restrict__ out, const VoxParams P) {
-    narrow_body<CT, GAUSS, NSUB, float>(rec, w, slist, slist_ext, out, P);
-}
-template <int CT, bool GAUSS, int NSUB>
-__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
-    voxelize_narrow_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                                const uint2 *__restrict__ slist_ext, __bf16 *__restrict__ out, const VoxParams P) {
-    narrow_body<CT, GAUSS, NSUB, __bf16>(rec, w, slist, slist_ext, out, P);
-}
-template <int CT, bool GAUSS, int NSUB>
-__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
-    voxelize_narrow_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                                 const uint2 *__restrict__ slist_ext, float *__restrict__ out, const VoxParams P) {
-    narrow_body<CT, GAUSS, NSUB, Ndhwc<float>>(rec, w, slist, slist_ext, out, P);
-}
-template <int CT, bool GAUSS, int NSUB>
-__global__ void __launch_bounds__(512, narrow_waves_per_simd(CT, NSUB))
-    voxelize_narrow_bf16_ndhwc_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                                      const uint2 *__restrict__ slist_ext, __bf16 *__restrict__ out, const VoxParams P) {
-    narrow_body<CT, GAUSS, NSUB, Ndhwc<__bf16>>(rec, w, slist, slist_ext, out, P);
+                           const uint2 *__restrict__ slist_ext, typename grid_elem<OT>::type *__restrict__ out, const VoxParams P) {
+    narrow_body<CT, GAUSS, NSUB, OT>(rec, w, slist, slist_ext, out, P);
 }
 
 // 32-channel chunks of float32 grids whose rows are not whole 16-byte quads (odd dimensions, unaligned grid slices): the
 // matrix-core walk with the run-wise write-out (store_runs). A kernel of its own: compiled into voxelize_kernel<32, ...>
 // the extra write-out path costs the aligned-grid kernels six more spilled registers and 0.5 % of the headline rate.
-template <bool GAUSS, int MAXT>
+template <bool GAUSS, int MAXT, typename OT = float>
 __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
     voxelize_runs_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
                          const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
-                         float *__restrict__ out, const VoxParams P) {
-    typedef OpsMx32<GAUSS, false, false, true> Ops;
-    constexpr int CT = 32;
-    constexpr bool GROUPED = false;
-#include "mvx_slab_body.inc"
-}
-template <bool GAUSS, int MAXT>
-__global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
-    voxelize_runs_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                              const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
-                              __bf16 *__restrict__ out, const VoxParams P) {
-    typedef OpsMx32<GAUSS, false, false, true, __bf16> Ops;
+                         typename grid_elem<OT>::type *__restrict__ out, const VoxParams P) {
+    typedef OpsMx32<GAUSS, false, false, true, OT> Ops;
     constexpr int CT = 32;
     constexpr bool GROUPED = false;
 #include "mvx_slab_body.inc"
@@ -335,21 +280,12 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
 // round 4 these launches went to the per-lane-range kernels (OpsF32: one candidate and one voxel per lane step, six index
 // comparisons per voxel), the only narrow ones that carried store_runs: D = 49 / 50 / 63 ran at half the rate of D = 48 / 64
 // (C = 4, kernel ms: 0.238 / 0.228 / 0.200 against 0.120 / 0.099 - profiles/r04_slab_plans.txt).
-template <int CT, bool GAUSS, int MAXT>
+template <int CT, bool GAUSS, int MAXT, typename OT = float>
 __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
     voxelize_pair_runs_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
                               const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
-                              float *__restrict__ out, const VoxParams P) {
-    typedef OpsPair<CT, GAUSS, true> Ops;
-    constexpr bool GROUPED = false;
-#include "mvx_slab_body.inc"
-}
-template <int CT, bool GAUSS, int MAXT>
-__global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 8 : BIG_WAVES_PER_SIMD))
-    voxelize_pair_runs_bf16_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                                   const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
-                                   __bf16 *__restrict__ out, const VoxParams P) {
-    typedef OpsPair<CT, GAUSS, true, __bf16> Ops;
+                              typename grid_elem<OT>::type *__restrict__ out, const VoxParams P) {
+    typedef OpsPair<CT, GAUSS, true, OT> Ops;
     constexpr bool GROUPED = false;
 #include "mvx_slab_body.inc"
 }
@@ -399,32 +335,6 @@ constexpr bool mx_kernel() {
     return std::is_same<typename SlabOps<CT, GAUSS, LANE_RANGE, false>::type, OpsMx32<GAUSS, LANE_RANGE, false>>::value;
 }
 
-// the kernel of a grid element type: float -> the float32 kernels, __bf16 -> their bfloat16 twins
-template <int CT, bool G, bool LR, int MT, bool GR = false>
-static auto slab_kernel(float *) { return &voxelize_kernel<CT, G, LR, MT, GR>; }
-template <int CT, bool G, bool LR, int MT, bool GR = false>
-static auto slab_kernel(__bf16 *) { return &voxelize_bf16_kernel<CT, G, LR, MT, GR>; }
-template <int CT, bool G, bool LR, int MT, bool GR = false>
-static auto slab_kernel(Ndhwc<float> *) { return &voxelize_ndhwc_kernel<CT, G, LR, MT, GR>; }
-template <int CT, bool G, bool LR, int MT, bool GR = false>
-static auto slab_kernel(Ndhwc<__bf16> *) { return &voxelize_bf16_ndhwc_kernel<CT, G, LR, MT, GR>; }
-template <bool G, int MT>
-static auto runs_kernel(float *) { return &voxelize_runs_kernel<G, MT>; }
-template <bool G, int MT>
-static auto runs_kernel(__bf16 *) { return &voxelize_runs_bf16_kernel<G, MT>; }
-template <int CT, bool G, int MT>
-static auto pair_runs_kernel(float *) { return &voxelize_pair_runs_kernel<CT, G, MT>; }
-template <int CT, bool G, int MT>
-static auto pair_runs_kernel(__bf16 *) { return &voxelize_pair_runs_bf16_kernel<CT, G, MT>; }
-template <int CT, bool G, int NSUB>
-static auto narrow_kernel(float *) { return &voxelize_narrow_kernel<CT, G, NSUB>; }
-template <int CT, bool G, int NSUB>
-static auto narrow_kernel(__bf16 *) { return &voxelize_narrow_bf16_kernel<CT, G, NSUB>; }
-template <int CT, bool G, int NSUB>
-static auto narrow_kernel(Ndhwc<float> *) { return &voxelize_narrow_ndhwc_kernel<CT, G, NSUB>; }
-template <int CT, bool G, int NSUB>
-static auto narrow_kernel(Ndhwc<__bf16> *) { return &voxelize_narrow_bf16_ndhwc_kernel<CT, G, NSUB>; }
-
 template <typename OT>
 struct GroupedFn {
     const VoxArgs &a;
@@ -438,15 +348,11 @@ struct GroupedFn {
             VoxParams p = a.p;
             if (nb <= 0) return hipSuccess;
             if ((long long)nb * p.ncc > 65535) return hipErrorInvalidConfiguration;
-            static LdsLimit raised;
             const size_t main_lds = voxelize_mx_lds_bytes(p.NW);
             p.dcap = (int32_t)main_lds; // where the slots' {T, k} table sits in LDS
-            auto kern = slab_kernel<CT, GAUSS, LANE_RANGE, MAXT, true>((OT *)nullptr);
-            hipError_t e = raise_lds_limit(kern, main_lds + 16 * CHAN_GROUP_SLOTS, raised);
-            if (e != hipSuccess) return e;
-            launch_profiled(kern, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), main_lds + 16 * CHAN_GROUP_SLOTS, s, a.rec, a.w,
-                            a.slist, a.slist_ext, a.Tc, a.kc, static_cast<typename grid_elem<OT>::type *>(a.out), p);
-            return hipGetLastError();
+            return launch_kernel<voxelize_kernel<CT, GAUSS, LANE_RANGE, MAXT, true, OT>>(
+                dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), main_lds + 16 * CHAN_GROUP_SLOTS, s, a.rec, a.w, a.slist,
+                a.slist_ext, a.Tc, a.kc, static_cast<typename grid_elem<OT>::type *>(a.out), p);
         }
     }
 };
@@ -459,16 +365,16 @@ struct LaunchFn {
     template <int CT, bool GAUSS, bool LANE_RANGE, int MAXT>
     hipError_t operator()() const {
         constexpr bool NDHWC = grid_elem<OT>::NDHWC;
-        typedef typename grid_elem<OT>::type ET;
         if constexpr (NDHWC && MAXT > 512) return hipErrorInvalidValue; // (channels-last: slabs of at most 8 waves, plan_call)
         else {
         const VoxParams &p = a.p;
         if (nb <= 0) return hipSuccess;
         if ((long long)nb * p.ncc > 65535) return hipErrorInvalidConfiguration;
-        static LdsLimit raised;
         constexpr bool mx = mx_kernel<CT, GAUSS, LANE_RANGE>();
         size_t lds = mx ? voxelize_mx_lds_bytes(p.NW) : voxelize_lds_bytes(CT, p.NW, CR_F32);
         if (CT < 32 && !LANE_RANGE) lds = std::max(lds, (size_t)65 * cand_stride_words(CT) * 4); // (the vector staging's dump row: stage_round_v)
+        const dim3 grid(slab_grid_x(p), (unsigned)(nb * p.ncc));
+        typename grid_elem<OT>::type *const out = static_cast<typename grid_elem<OT>::type *>(a.out);
         if constexpr (CT < 16 && !LANE_RANGE) { // narrow chunks: several sub-tiles per wave (voxelize_narrow_kernel)
             // four where the accumulator sets fit (1 or 4 channels) and the row is a multiple of four sub-tiles, else two
             // (channels-last: four sub-tiles for one channel only - four sets of four accumulators and their channel runs need
@@ -476,53 +382,39 @@ struct LaunchFn {
             constexpr int CT4 = NDHWC ? 1 : 4; // widest chunk served with four sub-tiles per wave
             const int nsub = a.narrow_sub > 0 ? a.narrow_sub : ((CT <= CT4 && p.NW % 4 == 0) ? 4 : 2);
             if (nsub > 1 && p.NW % nsub == 0 && (p.vec_store || NDHWC)) { // (the channels-last write-out has both store forms)
-                static LdsLimit raised_n;
-                const size_t lds_n = lds; // (64 rows + the staging's dump row)
-                auto launch_n = [&](auto kn) {
-                    hipError_t en = raise_lds_limit(kn, lds_n, raised_n);
-                    if (en != hipSuccess) return en;
-                    launch_profiled(kn, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW / nsub * 64), lds_n, s, a.rec, a.w, a.slist,
-                                    a.slist_ext, static_cast<ET *>(a.out), a.p);
-                    return hipGetLastError();
-                };
+                // (lds: 64 rows + the staging's dump row)
                 if constexpr (CT <= CT4) {
-                    if (nsub == 4) return launch_n(narrow_kernel<CT, GAUSS, 4>((OT *)nullptr));
+                    if (nsub == 4)
+                        return launch_kernel<voxelize_narrow_kernel<CT, GAUSS, 4, OT>>(grid, dim3(p.NW / 4 * 64), lds, s, a.rec, a.w, a.slist,
+                                                                                        a.slist_ext, out, a.p);
                 }
-                if (nsub == 2) return launch_n(narrow_kernel<CT, GAUSS, 2>((OT *)nullptr));
+                if (nsub == 2)
+                    return launch_kernel<voxelize_narrow_kernel<CT, GAUSS, 2, OT>>(grid, dim3(p.NW / 2 * 64), lds, s, a.rec, a.w, a.slist,
+                                                                                    a.slist_ext, out, a.p);
             }
         }
-        auto kern = slab_kernel<CT, GAUSS, LANE_RANGE, MAXT>((OT *)nullptr);
-        LdsLimit *state = &raised;
-        if constexpr (!NDHWC) if (!p.vec_store) {
-            if constexpr (mx) {
-                static LdsLimit raised_runs;
-                kern = runs_kernel<GAUSS, MAXT>((OT *)nullptr);
-                state = &raised_runs;
-            } else if constexpr (!LANE_RANGE) { // narrow chunks: the pair walk with store_runs
-                static LdsLimit raised_pair_runs;
-                kern = pair_runs_kernel<CT, GAUSS, MAXT>((OT *)nullptr);
-                state = &raised_pair_runs;
-            }
+        const dim3 block(p.NW * 64);
+        if constexpr (!NDHWC) if (!p.vec_store) { // rows that are not whole 16-byte quads: the kernels with the run-wise write-out
+            if constexpr (mx)
+                return launch_kernel<voxelize_runs_kernel<GAUSS, MAXT, OT>>(grid, block, lds, s, a.rec, a.w, a.slist, a.slist_ext, a.Tc, a.kc, out, a.p);
+            else if constexpr (!LANE_RANGE) // narrow chunks: the pair walk with store_runs
+                return launch_kernel<voxelize_pair_runs_kernel<CT, GAUSS, MAXT, OT>>(grid, block, lds, s, a.rec, a.w, a.slist, a.slist_ext, a.Tc, a.kc,
+                                                                                      out, a.p);
         }
-        hipError_t e = raise_lds_limit(kern, lds, *state);
-        if (e != hipSuccess) return e;
-        launch_profiled(kern, dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), lds, s, a.rec, a.w,
-                        a.slist, a.slist_ext, a.Tc, a.kc, static_cast<ET *>(a.out), a.p);
-        return hipGetLastError();
+        return launch_kernel<voxelize_kernel<CT, GAUSS, LANE_RANGE, MAXT, false, OT>>(grid, block, lds, s, a.rec, a.w, a.slist, a.slist_ext, a.Tc,
+                                                                                       a.kc, out, a.p);
         }
     }
 };
 
 hipError_t launch_voxelize(const VoxArgs &a, int32_t nb, int32_t ct, bool gauss, bool lane_range, hipStream_t s) {
     KernelKey k{ct, gauss, lane_range, a.p.NW <= 8 ? 512 : 1024};
-    if (a.ndhwc) return a.bf16 ? for_kernel(k, LaunchFn<Ndhwc<__bf16>>{a, nb, s}) : for_kernel(k, LaunchFn<Ndhwc<float>>{a, nb, s});
-    return a.bf16 ? for_kernel(k, LaunchFn<__bf16>{a, nb, s}) : for_kernel(k, LaunchFn<float>{a, nb, s});
+    return for_grid_type(a.bf16, a.ndhwc, [&](auto g) { return for_kernel(k, LaunchFn<typename decltype(g)::type>{a, nb, s}); });
 }
 
 hipError_t launch_voxelize_grouped(const VoxArgs &a, int32_t nb, bool gauss, bool lane_range, hipStream_t s) {
     KernelKey k{32, gauss, lane_range, a.p.NW <= 8 ? 512 : 1024};
-    if (a.ndhwc) return a.bf16 ? for_kernel(k, GroupedFn<Ndhwc<__bf16>>{a, nb, s}) : for_kernel(k, GroupedFn<Ndhwc<float>>{a, nb, s});
-    return a.bf16 ? for_kernel(k, GroupedFn<__bf16>{a, nb, s}) : for_kernel(k, GroupedFn<float>{a, nb, s});
+    return for_grid_type(a.bf16, a.ndhwc, [&](auto g) { return for_kernel(k, GroupedFn<typename decltype(g)::type>{a, nb, s}); });
 }
 
 } // namespace mvx

@@ -111,15 +111,8 @@ hipError_t launch_scale_rows(float *w, const float *weights, int64_t first, int6
 template <bool GAUSS, int MAXT>
 static hipError_t launch_sum(const VoxArgs &a, int32_t nb, bool accumulate, hipStream_t s) {
     const VoxParams &p = a.p;
-    // rows of two rounds (stage_first_rounds) or the write-out tile of eight channels, whichever is larger
-    const size_t lds = std::max(voxelize_lds_bytes(32, p.NW, MX_CR), (size_t)2 * 64 * cand_stride_words(32) * 4);
-    static LdsLimit raised;
-    auto kern = &voxelize_sum_kernel<GAUSS, MAXT>;
-    hipError_t e = raise_lds_limit(kern, lds, raised);
-    if (e != hipSuccess) return e;
-    launch_profiled(kern, dim3(p.nslab, (unsigned)p.ncc), dim3(p.NW * 64), lds, s, a.rec, a.w, a.slist, a.slist_ext,
-                    static_cast<float *>(a.out), (int)nb, accumulate ? 1 : 0, p);
-    return hipGetLastError();
+    return launch_kernel<voxelize_sum_kernel<GAUSS, MAXT>>(dim3(p.nslab, (unsigned)p.ncc), dim3(p.NW * 64), voxelize_mx_lds_bytes(p.NW), s, a.rec, a.w,
+                                                           a.slist, a.slist_ext, static_cast<float *>(a.out), (int)nb, accumulate ? 1 : 0, p);
 }
 
 hipError_t launch_voxelize_sum(const VoxArgs &a, int32_t nb, bool gauss, bool accumulate, hipStream_t s) {
@@ -138,14 +131,8 @@ hipError_t launch_view_weights(float *a, const float *view_weights, const int64_
 template <bool GAUSS, int MAXT>
 static hipError_t launch_sum_parts(const VoxArgs &a, int32_t nb, float *parts, int32_t q, int32_t g0, int32_t ng, hipStream_t s) {
     const VoxParams &p = a.p;
-    const size_t lds = std::max(voxelize_lds_bytes(32, p.NW, MX_CR), (size_t)2 * 64 * cand_stride_words(32) * 4); // (launch_sum)
-    static LdsLimit raised;
-    auto kern = &voxelize_sum_parts_kernel<GAUSS, MAXT>;
-    hipError_t e = raise_lds_limit(kern, lds, raised);
-    if (e != hipSuccess) return e;
-    launch_profiled(kern, dim3(p.nslab, (unsigned)p.ncc, (unsigned)ng), dim3(p.NW * 64), lds, s, a.rec, a.w, a.slist, a.slist_ext, parts,
-                    (int)nb, (int)q, (int)g0, p);
-    return hipGetLastError();
+    return launch_kernel<voxelize_sum_parts_kernel<GAUSS, MAXT>>(dim3(p.nslab, (unsigned)p.ncc, (unsigned)ng), dim3(p.NW * 64), voxelize_mx_lds_bytes(p.NW),
+                                                                 s, a.rec, a.w, a.slist, a.slist_ext, parts, (int)nb, (int)q, (int)g0, p);
 }
 
 hipError_t launch_voxelize_sum_parts(const VoxArgs &a, int32_t nb, bool gauss, float *parts, int32_t q, hipStream_t s) {

@@ -102,7 +102,7 @@ def grad_res():
 
 def test_float32_gaussian_feature_gradient_kernel_has_no_scratch(grad_res):
     # the headline shape (C = 32, features, Gaussian, one radius per atom): float32 and bfloat16 grids
-    hot = [k for k in grad_res if ("<float, 0, true, false>" in k or "IDF16bLi0ELb1ELb0E" in k)]
+    hot = [k for k in grad_res if ("<float, 0, true, false>" in k or "<__bf16, 0, true, false>" in k)]
     assert len(hot) == 2, sorted(grad_res)
     for k in hot:
         assert grad_res[k]["scratch"] == 0 and grad_res[k]["vspill"] == 0, (k, grad_res[k])

@@ -5,8 +5,6 @@ Every case runs one float32 and one bfloat16 voxelizer on the same inputs and co
 must be written. Routes (one launch / binned), kernels (matrix-core, candidate pairs, narrow, per-lane ranges, grouped
 channel-wise radii, run-wise write-out) and write-out paths (vector stores, runs, unaligned grids) are all reached.
 """
-import re
-
 import numpy as np
 import pytest
 
@@ -297,22 +295,17 @@ def test_bf16_kernel_resources():
     * no scratch wherever the float32 twin has none;
     * twins without the run-wise write-out (aligned-grid slab kernels, narrow kernels): exactly the float32 spills and scratch;
     * twins that carry the bfloat16 store_runs (run-wise, per-lane-range and pair kernels) spill more scalar registers
-      (16-17 in the slab kernels, up to 34 in the pair kernels; to VGPR lanes, no scratch) and voxelize_bf16_kernel<32, false, true, 1024, false> 13 more
+      (16-17 in the slab kernels, up to 34 in the pair kernels; to VGPR lanes, no scratch) and voxelize_kernel<32, false, true, 1024, false, __bf16> 13 more
       VGPRs (8 -> 56 B of scratch): pinned at the measured bound (rates: profiles/r05_bf16.txt)."""
     import os
-    import subprocess
     import sys
 
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import regs
 
     res = regs.kernel_resources()
-    # bfloat16 kernel -> its float32 twin's name. (c++filt does not know the __bf16 mangling DF16b: the names arrive mangled;
-    # with the out parameter's type read as float they demangle to the twin's signature)
-    mangled = [k for k in res if "_bf16_kernel" in k]
-    plain = subprocess.run(["c++filt"], input="\n".join(k.replace("DF16b", "f") for k in mangled), capture_output=True,
-                           text=True).stdout.splitlines()
-    twins = {m: re.sub(r"\(.*", "", n).replace("void mvx::", "").replace("_bf16_kernel", "_kernel") for m, n in zip(mangled, plain)}
+    # bfloat16 kernel -> its float32 twin: the same instantiation with the grid type float
+    twins = {k: k[: -len("__bf16>")] + "float>" for k in res if k.startswith("voxelize_") and k.endswith(", __bf16>")}
     assert len(twins) >= 100, len(twins)
     for k, twin in twins.items():
         r, t = res[k], res[twin]

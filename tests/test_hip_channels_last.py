@@ -416,23 +416,14 @@ def test_backward_matches_the_contiguous_voxelizer_bit_for_bit(radii_type):
 
 # ---- resources --------------------------------------------------------------------------------------------------------------------
 def _kernel_resources():
-    """tools/regs.py's table with the bfloat16 kernels' names demangled (c++filt does not know the __bf16 mangling DF16b)."""
+    """tools/regs.py's table: the grid type is every kernel's last template argument."""
     import os
-    import re
-    import subprocess
 
     from tools import regs
 
     if not all(os.path.exists(o) for o in regs.KERNEL_OBJECTS):
         pytest.skip("kernel objects not built")
-    res = regs.kernel_resources()
-    mangled = [k for k in res if k.startswith("_Z") and "_bf16_" in k]
-    plain = subprocess.run(["c++filt"], input="\n".join(k.replace("DF16b", "f") for k in mangled), capture_output=True,
-                           text=True).stdout.splitlines()
-    out = {k: v for k, v in res.items() if k not in mangled}
-    for m, n in zip(mangled, plain):
-        out[re.sub(r"\(.*", "", n).replace("void mvx::", "")] = res[m]
-    return out
+    return regs.kernel_resources()
 
 
 def test_channels_last_kernels_keep_their_accumulators_in_registers():
@@ -442,27 +433,27 @@ def test_channels_last_kernels_keep_their_accumulators_in_registers():
     are staged (tests/test_kernel_resources.py: scratch <= 32, <= 6 registers) and nothing more. No 1024-thread variants exist
     in this layout. The per-molecule kernel: the bounds of voxelize_pair_kernel."""
     res = _kernel_resources()
-    for tag in ("voxelize_ndhwc_kernel<", "voxelize_bf16_ndhwc_kernel<"):
-        ks = {k: v for k, v in res.items() if k.startswith(tag)}
+    for tag in (", Ndhwc<float>>", ", Ndhwc<__bf16>>"):
+        ks = {k: v for k, v in res.items() if k.startswith("voxelize_kernel<") and k.endswith(tag)}
         assert len(ks) == 24 and all(", 512, " in k for k in ks), sorted(ks)  # 5 widths x {gaussian, binary} x {plain, lane ranges} + 4 grouped
         for name, r in ks.items():
             assert r["vgpr"] <= 64, (name, r)
         for gauss in ("true", "false"):
             for ct in (1, 4, 8, 16):
-                r = res[f"{tag}{ct}, {gauss}, false, 512, false>"]
+                r = res[f"voxelize_kernel<{ct}, {gauss}, false, 512, false{tag}"]
                 assert r["scratch"] == 0 and r["vspill"] == 0, (tag, ct, gauss, r)
-            r = res[f"{tag}32, {gauss}, false, 512, false>"]
-            twin = res[f"voxelize_kernel<32, {gauss}, false, 512, false>"]
+            r = res[f"voxelize_kernel<32, {gauss}, false, 512, false{tag}"]
+            twin = res[f"voxelize_kernel<32, {gauss}, false, 512, false, float>"]
             assert r["scratch"] <= 32 and r["vspill"] <= 6, (tag, gauss, r)
             assert r["vspill"] <= twin["vspill"] + 1, (tag, gauss, r, twin)
-    for tag in ("voxelize_narrow_ndhwc_kernel<", "voxelize_narrow_bf16_ndhwc_kernel<"):
-        ks = {k: v for k, v in res.items() if k.startswith(tag)}
+    for tag in (", Ndhwc<float>>", ", Ndhwc<__bf16>>"):
+        ks = {k: v for k, v in res.items() if k.startswith("voxelize_narrow_kernel<") and k.endswith(tag)}
         assert len(ks) == 8  # 1 channel x {2, 4} sub-tiles, 4 and 8 channels x 2, Gaussian and binary
         for name, r in ks.items():
             assert r["vspill"] == 0 and r["scratch"] == 0 and r["vgpr"] <= 64, (name, r)
-    for tag in ("voxelize_pair_ndhwc_kernel<", "voxelize_pair_bf16_ndhwc_kernel<"):
-        ks = {k: v for k, v in res.items() if k.startswith(tag)}
+    for tag in (", Ndhwc<float>>", ", Ndhwc<__bf16>>"):
+        ks = {k: v for k, v in res.items() if k.startswith("voxelize_pair_kernel<") and k.endswith(tag)}
         assert len(ks) == 30
         for name, r in ks.items():
             assert r["vgpr"] <= 128, (name, r)
-            assert r["scratch"] <= (0 if ", false, false>" in name else 128), (name, r)
+            assert r["scratch"] <= (0 if f", false, false{tag}" in name else 128), (name, r)

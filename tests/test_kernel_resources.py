@@ -11,6 +11,9 @@ import os
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The grid type is the kernels' last template argument (float, __bf16, Ndhwc<float>, Ndhwc<__bf16>). This module pins the float32
+# kernels of the contiguous layout; tests/test_hip_bf16.py and tests/test_hip_channels_last.py pin the other grid types.
+F32 = ", float>"
 
 
 @pytest.fixture(scope="module")
@@ -23,17 +26,17 @@ def res():
 
 
 def test_batched_voxelize_kernels_fit_their_occupancy(res):
-    ks = {k: v for k, v in res.items() if k.startswith("voxelize_kernel<") and ", 512, " in k}
+    ks = {k: v for k, v in res.items() if k.startswith("voxelize_kernel<") and ", 512, " in k and k.endswith(F32)}
     assert len(ks) >= 24
     for name, r in ks.items():
         assert r["vgpr"] <= 64, (name, r)  # 8 waves per SIMD
     # the headline kernel (32 channels, gaussian, matrix-core walk) and its binary twin: no scratch in the first round
-    for name in ("voxelize_kernel<32, true, false, 512, false>", "voxelize_kernel<32, false, false, 512, false>"):
+    for name in ("voxelize_kernel<32, true, false, 512, false, float>", "voxelize_kernel<32, false, false, 512, false, float>"):
         assert res[name]["scratch"] <= 32 and res[name]["vspill"] <= 6, (name, res[name])
     # narrower chunks (ligand batches, forward_types, forward_single): none at all
     for ct in (1, 4, 8, 16):
         for gauss in ("true", "false"):
-            r = res[f"voxelize_kernel<{ct}, {gauss}, false, 512, false>"]
+            r = res[f"voxelize_kernel<{ct}, {gauss}, false, 512, false, float>"]
             assert r["scratch"] == 0 and r["vspill"] == 0, (ct, gauss, r)
     # per-lane-range variants (blockdim 4, 5, 12, ...) and the grouped launch (channel-wise radii): a handful of spills in
     # the cold rounds, never the accumulators
@@ -45,11 +48,11 @@ def test_batched_voxelize_kernels_fit_their_occupancy(res):
 def test_whole_row_slabs_of_long_rows_keep_two_workgroups_per_unit(res):
     """Rows of 65 ... 128 voxels stay in one slab of 9 ... 16 waves (plan_slabs): the 1024-thread variants are compiled for
     64 registers so that two or three such workgroups fit a compute unit (D = 72: 4.16 against 3.75 TB/s with 128)."""
-    ks = {k: v for k, v in res.items() if (k.startswith("voxelize_kernel<") and ", 1024, " in k) or k.startswith("voxelize_runs_kernel<")}
+    ks = {k: v for k, v in res.items() if k.endswith(F32) and ((k.startswith("voxelize_kernel<") and ", 1024, " in k) or k.startswith("voxelize_runs_kernel<"))}
     assert len(ks) >= 24
     for name, r in ks.items():
         assert r["vgpr"] <= 64, (name, r)
-    for name in ("voxelize_kernel<32, true, false, 1024, false>", "voxelize_kernel<32, false, false, 1024, false>"):
+    for name in ("voxelize_kernel<32, true, false, 1024, false, float>", "voxelize_kernel<32, false, false, 1024, false, float>"):
         assert res[name]["scratch"] <= 32 and res[name]["vspill"] <= 6, (name, res[name])
 
 
@@ -58,7 +61,7 @@ def test_run_wise_write_out_lives_in_its_own_kernels(res):
     per-lane-range variants only: inside the headline kernel it cost six more spilled registers and 0.5 % of its rate."""
     for maxt in (512, 1024):
         for gauss in ("true", "false"):
-            r = res[f"voxelize_runs_kernel<{gauss}, {maxt}>"]
+            r = res[f"voxelize_runs_kernel<{gauss}, {maxt}, float>"]
             assert r["vgpr"] <= 64 and r["vspill"] <= 12 and r["scratch"] <= 48, (gauss, maxt, r)
 
 
@@ -82,11 +85,13 @@ def test_no_per_channel_float32_kernels_are_left(res):
     """Channel-wise radii for features run grouped by radius, one table per chunk of 32 channels (at most 32 distinct radii
     per chunk): the per-channel kernels of rounds 1-3 (200 spilled registers at 32 channels) are gone, and with them every
     float32 instantiation that carried a `chanwise` parameter."""
-    assert sum(k.startswith("voxelize_kernel<") for k in res) == 48  # 5 widths x {gaussian, binary} x {plain, lane ranges} x 2 sizes + 8 grouped
+    assert sum(k.startswith("voxelize_kernel<") and k.endswith(F32) for k in res) == 48  # 5 widths x {gaussian, binary} x {plain, lane ranges} x 2 sizes + 8 grouped
     # per-molecule launches: voxelize_pair_kernel alone - 5 widths x {gaussian, binary} x {no transform, transform} plus, for
     # blockdims that cut through sub-tiles (per-lane ranges), the transform-capable instantiation once more
-    assert sum(k.startswith("voxelize_pair_kernel<") for k in res) == 30
+    assert sum(k.startswith("voxelize_pair_kernel<") and k.endswith(F32) for k in res) == 30
     assert sum(k.startswith("voxelize_direct_kernel<") for k in res) == 0
+    # ... and no kernel of another grid type under a name of its own: the grid type is a template argument
+    assert not [k for k in res if "_bf16_kernel" in k or "_ndhwc_kernel" in k]
 
 
 def test_pair_kernel_fits_one_workgroup_of_sixteen_waves(res):
@@ -94,10 +99,10 @@ def test_pair_kernel_fits_one_workgroup_of_sixteen_waves(res):
     no scratch at all in the variants without a transform (the cold multi-round / multi-segment code uses lighter scan and
     stage variants beside the live accumulators), a few dozen bytes with one. The disassembly
     (tools/disasm.sh voxelize_pair_kernelILi32ELb1ELb0E molvoxel_amd/csrc/mvx_pair.o) shows where the scratch accesses sit."""
-    ks = {k: v for k, v in res.items() if k.startswith("voxelize_pair_kernel<")}
+    ks = {k: v for k, v in res.items() if k.startswith("voxelize_pair_kernel<") and k.endswith(F32)}
     for name, r in ks.items():
         assert r["vgpr"] <= 128, (name, r)
-        no_transform = ", false, false>" in name  # <CT, gauss, transform, lane ranges>
+        no_transform = ", false, false, float>" in name  # <CT, gauss, transform, lane ranges, grid type>
         assert r["scratch"] <= (0 if no_transform else 128), (name, r)  # (452 B once cost the cfg-2 call 30 %: profiles/r04_single_calls.txt)
 
 
@@ -105,7 +110,7 @@ def test_narrow_kernels_hold_their_accumulator_sets_in_registers(res):
     """voxelize_narrow_kernel (1 ... 8 channels, two or four sub-tiles per wave): the NSUB accumulator sets and the eight row
     loads in flight stay in registers, and since the staging became branch-free with one add per slot every variant fits the
     64 registers of 8 waves per SIMD (it needed 66 ... 84 and was compiled for 7 / 6 / 5 before; profiles/r04_narrow.txt)."""
-    ks = {k: v for k, v in res.items() if k.startswith("voxelize_narrow_kernel<")}
+    ks = {k: v for k, v in res.items() if k.startswith("voxelize_narrow_kernel<") and k.endswith(F32)}
     assert len(ks) == 10  # {1, 4} channels x {2, 4} sub-tiles + 8 channels x 2, Gaussian and binary
     for name, r in ks.items():
         assert r["vspill"] == 0 and r["scratch"] == 0 and r["vgpr"] <= 64, (name, r)

@@ -205,17 +205,10 @@ VGPR_SLACK = 6  # (every float kernel then still fits two waves per SIMD: 512 / 
 
 
 def _variant(name):
-    """('float' | 'bf16' | 'double', mode, gauss, chanwise) of a score_kernel name, demangled or not (c++filt does not know
-    __bf16 in every version)."""
-    m = re.search(r"score_kernel<(float|double), (\d), (true|false), (true|false)>", name)
-    if m:
-        return m.group(1), int(m.group(2)), m.group(3) == "true", m.group(4) == "true"
-    m = re.search(r"score_kernelIDF16bLi(\d)ELb(\d)ELb(\d)E", name)
-    if m:
-        return "bf16", int(m.group(1)), m.group(2) == "1", m.group(3) == "1"
-    m = re.search(r"score_kernel<.*?, (true|false), (true|false)>", name)  # (a half-demangled bfloat16 name: types mode)
+    """('float' | 'bf16' | 'double', mode, gauss, chanwise) of a score_kernel name (tools/regs.py demangles __bf16 too)."""
+    m = re.search(r"score_kernel<(float|double|__bf16), (\d), (true|false), (true|false)>", name)
     assert m, name
-    return "bf16", 1, m.group(1) == "true", m.group(2) == "true"
+    return m.group(1).strip("_"), int(m.group(2)), m.group(3) == "true", m.group(4) == "true"
 
 
 def test_score_kernels_keep_their_registers():

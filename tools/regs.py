@@ -13,7 +13,8 @@ KERNEL_OBJECTS = [os.path.join(CSRC, f"mvx_{name}.o") for name in ("prep", "slab
 
 def kernel_resources(obj=None):
     """{demangled kernel name (without 'void mvx::' and the argument list): dict(vgpr, sgpr, vspill, sspill, scratch, lds)}
-    obj = None: every kernel object of the library (one per kernel family)."""
+    obj = None: every kernel object of the library (one per kernel family). The voxelize kernels' grid type is their last template
+    argument: voxelize_kernel<32, true, false, 512, false, float>, <..., __bf16>, voxelize_narrow_kernel<1, true, 4, Ndhwc<__bf16>>."""
     if obj is None:
         out = {}
         for o in KERNEL_OBJECTS:
@@ -28,13 +29,16 @@ def kernel_resources(obj=None):
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True).stdout
     blocks = re.split(r"\n\s*- \.agpr_count:", notes)[1:]
     names = [re.search(r"\.name:\s*(\S+)", b).group(1) for b in blocks]
-    demangled = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
+    # (c++filt does not know __bf16's mangling DF16b and leaves such names mangled: they go through as half - Dh, a builtin type
+    # code as well, so substitution indices stay what they are - and come back as __bf16)
+    demangled = subprocess.run(["c++filt"], input="\n".join(n.replace("DF16b", "Dh") for n in names), capture_output=True,
+                               text=True).stdout.replace("half", "__bf16").splitlines()
     out = {}
     for blk, name in zip(blocks, demangled):
         def g(key):
             m = re.search(rf"\.{key}:\s*(\d+)", blk)
             return int(m.group(1)) if m else -1
-        short = re.sub(r"\(.*", "", name).replace("void mvx::", "").replace("mvx::", "")
+        short = re.sub(r"\(.*", "", name).replace("void mvx::", "").replace("mvx::", "").replace("> >", ">>")
         out[short] = dict(vgpr=g("vgpr_count"), sgpr=g("sgpr_count"), vspill=g("vgpr_spill_count"), sspill=g("sgpr_spill_count"),
                           scratch=g("private_segment_fixed_size"), lds=g("group_segment_fixed_size"))
     return out

@@ -4,7 +4,7 @@
 Stamps per workgroup (s_memtime = shader cycles; only deltas inside a workgroup are meaningful):
   0 start | 1 line arrived | 2 rows staged by wave 0 | 3 staging barrier passed | 8+w walk end of wave w |
   4 barrier after the walk | 5 write-out round 0 (4 channels) done | 6 all stores issued | 7 = candidates in the line
-GRID=bfloat16 in the environment: the same calls on a bfloat16 grid (voxelize_bf16_kernel, the same stamps).
+GRID=bfloat16 in the environment: the same calls on a bfloat16 grid (voxelize_kernel<..., __bf16>, the same stamps).
 """
 import ctypes as C
 import os
