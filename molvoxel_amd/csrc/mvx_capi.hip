@@ -1410,9 +1410,10 @@ struct Backward {
     const GradOut &o;
     const int64_t total;
     const hipStream_t s = c.stream;
-    const bool f64 = h->cfg.precision == 64, gauss = h->cfg.density == MVX_GAUSSIAN;
-    const bool chanwise = c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES;
-    const int32_t grid_kind = h->cfg.grid_type == MVX_GRID_BF16 ? 1 : (f64 ? 2 : 0);
+    const bool f64 = h->cfg.precision == 64;
+    // which instantiation every walk of this call takes; key.chanwise: channel-wise radii for features, with their tables
+    const WalkKey key{h->cfg.grid_type == MVX_GRID_BF16 ? 1 : (f64 ? 2 : 0), c.mode, h->cfg.density == MVX_GAUSSIAN,
+                      c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES};
     void *d_kc = nullptr; // channel-wise features: the per-channel coefficients (ga.kc)
     DeviceInputs in{c};   // the caller's arrays; stage(): the device copy of offsets and records, the slot they went through
     GradArgs ga;
@@ -1425,12 +1426,12 @@ struct Backward {
         if ((rc = ensure(h->grad_xp, (size_t)total * sizeof(uint2)))) return rc;
         void *d_rmax = nullptr;
         double *d_Tc = nullptr;
-        if (chanwise) {
+        if (key.chanwise) {
             if ((rc = ensure(h->grad_aux, chan_kc_off(c.C) + (size_t)c.C * sizeof(double)))) return rc;
             d_rmax = h->grad_aux.p;
             d_Tc = reinterpret_cast<double *>((char *)h->grad_aux.p + CHAN_TC_OFF);
             d_kc = (char *)h->grad_aux.p + chan_kc_off(c.C);
-            HIP_TRY(launch_grad_chan(c.radii, c.C, f64, gauss, h->sigma32, h->cfg.sigma, d_rmax, d_Tc, d_kc, s));
+            HIP_TRY(launch_grad_chan(c.radii, c.C, f64, key.gauss, h->sigma32, h->cfg.sigma, d_rmax, d_Tc, d_kc, s));
         }
         PrepArgs pa = prep_args(h, c, total, in); // (no packed weights: the gradient kernel reads the feature rows in place)
         pa.Cpad = c.C;
@@ -1469,7 +1470,7 @@ struct Backward {
     }
 
     int plain() { // BWD_PLAIN
-        HIP_TRY(launch_grad(ga, c.mode, grid_kind, gauss, chanwise, s));
+        HIP_TRY(launch_grad(ga, key, s));
         return MVX_OK;
     }
     // BWD_SCORE: one walk over the field: the per-atom scores (the caller's array, or workspace), dS/dcoords and dS/dfeatures
@@ -1482,7 +1483,7 @@ struct Backward {
             if (int rc = ensure(h->score_atoms, (size_t)total * sizeof(double))) return rc;
             sa.atom_scores = reinterpret_cast<double *>(h->score_atoms.p);
         }
-        HIP_TRY(launch_score(ga, sa, c.mode, grid_kind, gauss, chanwise, s));
+        HIP_TRY(launch_score(ga, sa, key, s));
         HIP_TRY(launch_score_reduce(sa.atom_scores, in.offsets, c.B, o.score.scores, s));
         return MVX_OK;
     }
@@ -1492,12 +1493,12 @@ struct Backward {
         return (o.grad_coords || o.grad_features) ? plain() : MVX_OK;
     }
     // bytes of the radius partials, one per atom or per (channel, atom), in front of the stage sums in grad_rpart
-    size_t part_bytes() const { return align_up((chanwise ? (size_t)c.C * (size_t)total : (size_t)total) * sizeof(double), 256); }
+    size_t part_bytes() const { return align_up((key.chanwise ? (size_t)c.C * (size_t)total : (size_t)total) * sizeof(double), 256); }
     // BWD_DENSITY: the radius walk with its partials kept per atom (or per channel and atom) in grad_rpart, whatever the radii
     // type: [partials | channel-wise: stage sums of grad_radii_reduce, C doubles for a grad_radii nobody asked for | the chunk
     // sums of all atoms]. One walk feeds grad_radii, grad_sigma and grad_rscalar.
     int density() {
-        if (!gauss) return binary();
+        if (!key.gauss) return binary();
         const bool by_channel = c.radii_type == MVX_RADII_CHANNEL;
         const size_t rstage_bytes = by_channel ? align_up((grad_radii_stage_doubles(total, c.C) + (size_t)c.C) * sizeof(double), 256) : 0;
         if (int rc = ensure(h->grad_rpart, part_bytes() + rstage_bytes + grad_density_stage_doubles(total) * sizeof(double))) return rc;
@@ -1510,13 +1511,13 @@ struct Backward {
         // sigma and the scalar radius as the forward used them
         const double sigma = f64 ? h->cfg.sigma : (double)h->sigma32;
         const double rsc = f64 ? c.radius_scalar : (double)(float)c.radius_scalar;
-        HIP_TRY(launch_grad_radii(ga, ra, c.mode, grid_kind, chanwise, s));
-        if (by_channel && (o.grad_radii || chanwise)) { // (features: grad_sigma needs the stage sums of this reduction)
+        HIP_TRY(launch_grad_radii(ga, ra, key, s));
+        if (by_channel && (o.grad_radii || key.chanwise)) { // (features: grad_sigma needs the stage sums of this reduction)
             double *gr = o.grad_radii ? o.grad_radii : rstage + grad_radii_stage_doubles(total, c.C);
-            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(c.channels), c.radii,
-                                             chanwise ? d_kc : nullptr, f64, total, c.C, rstage, gr, s));
+            HIP_TRY(launch_grad_radii_reduce(ra.part, key.chanwise ? nullptr : static_cast<const int32_t *>(c.channels), c.radii,
+                                             key.chanwise ? d_kc : nullptr, f64, total, c.C, rstage, gr, s));
         }
-        if (chanwise) {
+        if (key.chanwise) {
             if (o.grad_sigma) HIP_TRY(launch_grad_density_chan(rstage, total, c.C, d_kc, f64, sigma, o.grad_sigma, s));
         } else if (o.grad_sigma || o.grad_rscalar || !by_channel) {
             HIP_TRY(launch_grad_density_sum(ra.part, total, c.radii, f64, by_channel ? nullptr : o.grad_radii, rsc, sigma, dstage,
@@ -1527,7 +1528,7 @@ struct Backward {
     // BWD_RADII: radius partials straight into grad_radii (one radius per atom), or per atom / per (channel, atom) into
     // grad_rpart and reduced over all atoms of the call in a fixed order (channel-wise radii: one radius vector for the batch)
     int radii() {
-        if (!gauss) return binary();
+        if (!key.gauss) return binary();
         RadiiArgs ra;
         ra.radii = c.radii;
         ra.grad_radii = o.grad_radii;
@@ -1538,10 +1539,10 @@ struct Backward {
             ra.part = reinterpret_cast<double *>(h->grad_rpart.p);
             stage = reinterpret_cast<double *>((char *)h->grad_rpart.p + part_bytes());
         }
-        HIP_TRY(launch_grad_radii(ga, ra, c.mode, grid_kind, chanwise, s));
+        HIP_TRY(launch_grad_radii(ga, ra, key, s));
         if (c.radii_type == MVX_RADII_CHANNEL)
-            HIP_TRY(launch_grad_radii_reduce(ra.part, chanwise ? nullptr : static_cast<const int32_t *>(c.channels), c.radii,
-                                             chanwise ? d_kc : nullptr, f64, total, c.C, stage, o.grad_radii, s));
+            HIP_TRY(launch_grad_radii_reduce(ra.part, key.chanwise ? nullptr : static_cast<const int32_t *>(c.channels), c.radii,
+                                             key.chanwise ? d_kc : nullptr, f64, total, c.C, stage, o.grad_radii, s));
         return MVX_OK;
     }
 };

@@ -1,8 +1,53 @@
-// mvx_grad.h - what the C-ABI TU (mvx_capi.hip) needs of the backward pass (mvx_grad.hip).
+// mvx_grad.h - what the C-ABI TU (mvx_capi.hip) needs of the backward family: the argument records and launchers of the
+// three walks (mvx_grad.hip, mvx_grad_radii.hip, mvx_score.hip) and of the reductions (mvx_grad_radii.hip,
+// mvx_grad_density.hip), and the host-side dispatch (WalkKey / for_walk, for_real) those files launch through. Included by
+// mvx_capi.hip and, through mvx_grad_device.h, by the six kernel files of the family (those five, mvx_pose.hip and
+// mvx_views_reduce.hip). WalkKey, for_walk and for_real are plain host C++: tests/test_walk_dispatch_host.py compiles them alone.
 #pragma once
+#include <type_traits>
+
 #include "mvx_internal.h"
 
 namespace mvx {
+
+// Which instantiation of a walk kernel (grad_kernel, grad_radii_kernel, score_kernel <GT, MODE, GAUSS, CHANWISE>) a call takes.
+struct WalkKey {
+    int32_t grid_kind, mode; // grid_kind: 0 float, 1 bfloat16, 2 double. mode: Mode
+    bool gauss, chanwise;    // Gaussian density; channel-wise radii (features only)
+};
+
+template <typename T>
+struct TypeTag {
+    typedef T type;
+};
+template <typename GT>
+using GridTag = TypeTag<GT>;
+template <int MODE>
+using ModeTag = std::integral_constant<int, MODE>;
+
+// fn(GridTag<GT>, ModeTag<MODE>, gauss constant, chanwise constant) for the key's instantiation, and the one place that knows
+// which exist: per grid type, features x one radius / channel-wise x Gaussian / binary, and MODE_TYPES x Gaussian / binary
+// for types and single mode alike (single: the records carry type 0) - 18 in all. CHANWISE occurs with MODE_FEATURES only.
+template <typename Fn>
+static hipError_t for_walk(const WalkKey &k, Fn &&fn) {
+    auto grid = [&](auto gt) {
+        auto density = [&](auto mode, auto chanwise) {
+            return k.gauss ? fn(gt, mode, std::true_type{}, chanwise) : fn(gt, mode, std::false_type{}, chanwise);
+        };
+        if (k.mode == MODE_FEATURES)
+            return k.chanwise ? density(ModeTag<MODE_FEATURES>{}, std::true_type{}) : density(ModeTag<MODE_FEATURES>{}, std::false_type{});
+        return density(ModeTag<MODE_TYPES>{}, std::false_type{});
+    };
+    if (k.grid_kind == 2) return grid(GridTag<double>{});
+    if (k.grid_kind == 1) return grid(GridTag<__bf16>{});
+    return grid(GridTag<float>{});
+}
+
+// fn(TypeTag<real>): the handle's real type (float, or double at precision 64) of the arrays a launcher takes as void *
+template <typename Fn>
+static hipError_t for_real(bool f64, Fn &&fn) {
+    return f64 ? fn(TypeTag<double>{}) : fn(TypeTag<float>{});
+}
 
 struct GradArgs {
     const AtomRec *rec;      // prep_kernel's records of the call
@@ -43,29 +88,31 @@ hipError_t launch_grad_chan(const void *radii, int32_t C, bool f64, bool gauss, 
 size_t grad_order_bytes(int64_t total, int B, int D);
 hipError_t launch_grad_order(const AtomRec *rec, const int64_t *offsets, int B, int64_t total, int D, void *ws, size_t ws_bytes,
                              const uint32_t **order, hipStream_t s);
-// grid_kind: 0 float, 1 bfloat16, 2 double. mode: Mode (single: the records carry type 0). One wave per atom record.
-hipError_t launch_grad(const GradArgs &a, int32_t mode, int32_t grid_kind, bool gauss, bool chanwise, hipStream_t s);
-// The same walk with the radius partials (Gaussian density only: a binary density has zero radius gradients), in one pass
-// with the coordinate and feature gradients, which are grad_kernel's bits.
-hipError_t launch_grad_radii(const GradArgs &a, const RadiiArgs &r, int32_t mode, int32_t grid_kind, bool chanwise, hipStream_t s);
+// One wave per atom record; nothing is launched without atoms.
+hipError_t launch_grad(const GradArgs &a, const WalkKey &key, hipStream_t s);
+// The same walk with the radius partials, in one pass with the coordinate and feature gradients, which are grad_kernel's
+// bits. Gaussian density only (a binary density has zero radius gradients): hipErrorInvalidValue for a key without gauss.
+hipError_t launch_grad_radii(const GradArgs &a, const RadiiArgs &r, const WalkKey &key, hipStream_t s);
 // The same walk over a constant field F (mvx_score.hip): s_n = sum_v sum_c F[c,v] w[n,c] rho_{n,c}(v) per atom into
 // ScoreArgs::atom_scores, in one pass with the coordinate and feature gradients, which are grad_kernel's bits for G = F laid
 // out per molecule. Binary density walks the box too (it scores, though its coordinate gradients are zero).
-hipError_t launch_score(const GradArgs &a, const ScoreArgs &sa, int32_t mode, int32_t grid_kind, bool gauss, bool chanwise,
-                        hipStream_t s);
+hipError_t launch_score(const GradArgs &a, const ScoreArgs &sa, const WalkKey &key, hipStream_t s);
 // scores[b] = sum of atom_scores over molecule b in a fixed order (one workgroup per molecule, no atomics); 0 without atoms
 hipError_t launch_score_reduce(const double *atom_scores, const int64_t *offsets, int32_t B, double *scores, hipStream_t s);
+// Both reductions over the atoms of a call sum chunks of GRAD_CHUNK atoms first (one block per chunk), then the chunks in order.
+constexpr int GRAD_CHUNK = 4096;
+inline int32_t grad_nchunk(int64_t total) { return (int32_t)((total + GRAD_CHUNK - 1) / GRAD_CHUNK); }
 // Channel-wise radii: dL/dr_c from RadiiArgs::part in a fixed order (no atomics). types: the atoms' (total,) partials of type c,
 // scaled by -1/r_c; else the (C, total) partials, scaled by -(kfac_c / r_c) with kc from launch_grad_chan. `stage` holds
 // grad_radii_stage_doubles(total, C) doubles.
-size_t grad_radii_stage_doubles(int64_t total, int32_t C);
+inline size_t grad_radii_stage_doubles(int64_t total, int32_t C) { return (size_t)grad_nchunk(total) * (size_t)C; }
 hipError_t launch_grad_radii_reduce(const double *part, const int32_t *types, const void *radii, const void *kc, bool f64, int64_t total,
                                     int32_t C, double *stage, double *grad_radii, hipStream_t s);
 // Sigma and scalar-radius gradients (mvx_backward_density_batch, mvx_grad_density.hip): the (total,) per-atom partials of
 // RadiiArgs::part summed over the call in a fixed order (no atomics), then grad_sigma[0] = -sum / sigma and grad_radius[0] =
 // -sum / r (each or NULL). With `grad_radii` (one radius per atom, `radii` the call's array) also dL/dr_n = -part[n] / radii[n],
 // the bits the walk writes itself without RadiiArgs::part. `stage` holds grad_density_stage_doubles(total) doubles.
-size_t grad_density_stage_doubles(int64_t total);
+inline size_t grad_density_stage_doubles(int64_t total) { return (size_t)grad_nchunk(total); }
 hipError_t launch_grad_density_sum(const double *part, int64_t total, const void *radii, bool f64, double *grad_radii, double r,
                                    double sigma, double *stage, double *grad_sigma, double *grad_radius, hipStream_t s);
 // Channel-wise radii for features: grad_sigma[0] = -(1/sigma) sum_c kfac_c S_c from launch_grad_radii_reduce's `stage` sums

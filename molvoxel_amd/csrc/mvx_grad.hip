@@ -55,13 +55,12 @@ __global__ void grad_chan_kernel(const real *radii, int C, int gauss, float sigm
 
 hipError_t launch_grad_chan(const void *radii, int32_t C, bool f64, bool gauss, float sigma32, double sigma64, void *rmax, double *Tc,
                             void *kc, hipStream_t s) {
-    if (f64)
-        hipLaunchKernelGGL(grad_chan_kernel<double>, dim3(1), dim3(256), 0, s, static_cast<const double *>(radii), C, gauss ? 1 : 0,
-                           sigma32, sigma64, static_cast<double *>(rmax), Tc, static_cast<double *>(kc));
-    else
-        hipLaunchKernelGGL(grad_chan_kernel<float>, dim3(1), dim3(256), 0, s, static_cast<const float *>(radii), C, gauss ? 1 : 0,
-                           sigma32, sigma64, static_cast<float *>(rmax), Tc, static_cast<float *>(kc));
-    return hipGetLastError();
+    return for_real(f64, [&](auto t) {
+        typedef typename decltype(t)::type real;
+        hipLaunchKernelGGL(grad_chan_kernel<real>, dim3(1), dim3(256), 0, s, static_cast<const real *>(radii), C, gauss ? 1 : 0,
+                           sigma32, sigma64, static_cast<real *>(rmax), Tc, static_cast<real *>(kc));
+        return hipGetLastError();
+    });
 }
 
 // Spatial order of the atoms: key = (molecule, 4^3-voxel cell of the admitted box's low corner), cells x-major, sorted
@@ -109,33 +108,10 @@ hipError_t launch_grad_order(const AtomRec *rec, const int64_t *offsets, int B, 
     return e;
 }
 
-template <typename GT, int MODE>
-static hipError_t launch_grad_mode(const GradArgs &a, bool gauss, bool chanwise, hipStream_t s) {
-    const unsigned nblk = (unsigned)((a.total + 3) / 4);
-    const dim3 grid(a.xcd_span ? 8u * (unsigned)a.xcd_span : nblk), block(256);
-    if constexpr (MODE == MODE_FEATURES) {
-        if (chanwise) {
-            if (gauss) hipLaunchKernelGGL((grad_kernel<GT, MODE, true, true>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((grad_kernel<GT, MODE, false, true>), grid, block, 0, s, a);
-            return hipGetLastError();
-        }
-    }
-    if (gauss) hipLaunchKernelGGL((grad_kernel<GT, MODE, true, false>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((grad_kernel<GT, MODE, false, false>), grid, block, 0, s, a);
-    return hipGetLastError();
-}
-
-template <typename GT>
-static hipError_t launch_grad_grid(const GradArgs &a, int32_t mode, bool gauss, bool chanwise, hipStream_t s) {
-    if (mode == MODE_FEATURES) return launch_grad_mode<GT, MODE_FEATURES>(a, gauss, chanwise, s);
-    return launch_grad_mode<GT, MODE_TYPES>(a, gauss, false, s); // (single mode: type 0 in every record)
-}
-
-hipError_t launch_grad(const GradArgs &a, int32_t mode, int32_t grid_kind, bool gauss, bool chanwise, hipStream_t s) {
-    if (a.total <= 0) return hipSuccess;
-    if (grid_kind == 2) return launch_grad_grid<double>(a, mode, gauss, chanwise, s);
-    if (grid_kind == 1) return launch_grad_grid<__bf16>(a, mode, gauss, chanwise, s);
-    return launch_grad_grid<float>(a, mode, gauss, chanwise, s);
+hipError_t launch_grad(const GradArgs &a, const WalkKey &key, hipStream_t s) {
+    return for_walk(key, [&](auto gt, auto mode, auto gauss, auto chanwise) {
+        return launch_walk(grad_kernel<typename decltype(gt)::type, mode, gauss, chanwise>, a, s); // (the tags convert as constants)
+    });
 }
 
 } // namespace mvx

@@ -1,6 +1,7 @@
 // mvx_grad_body.inc - the body of the gradient walk, included by grad_kernel (mvx_grad.hip, RADII = false), by its twin
 // grad_radii_kernel (mvx_grad_radii.hip, RADII = true) and by score_kernel (mvx_score.hip, SCORE = true): one text, three
-// kernels whose names stay apart and whose coordinate and feature gradients are the same bits. Expects the kernel parameters
+// kernels whose names stay apart and whose coordinate and feature gradients are the same bits; for_walk (mvx_grad.h) names their
+// instantiations and launch_walk (mvx_grad_device.h) launches each of them. Expects the kernel parameters
 // A (GradArgs), RA (RadiiArgs) and SA (ScoreArgs), the template parameters GT, MODE, GAUSS, CHANWISE and the constexpr bools
 // RADII and SCORE. With SCORE, A.g is a constant field F (one per molecule, or one for all: SA.mol_stride) and the walk also
 // forms the atom's score s_n = sum_v sum_c F[c,v] w[n,c] rho_{n,c}(v) - e without kfac - in float64 from the float32 products

@@ -10,8 +10,8 @@
 //   dL/dsigma = -(1/sigma) sum_n P_n          one radius per atom, radii by type, scalar radius
 //   dL/dsigma = -(1/sigma) sum_c kfac_c S_c   channel-wise features, S_c = sum_n S[c, n]: grad_radii_reduce's stage sums
 //
-//   density_sum_kernel          block = chunk of DCHUNK atoms: thread t adds atoms t, t + 256, ... in order, a butterfly per
-//                               wave, the four waves in a fixed order -> stage[chunk]
+//   density_sum_kernel          block = chunk of GRAD_CHUNK atoms: thread t adds atoms t, t + 256, ... in order, then
+//                               block_sum4 (a butterfly per wave, the four waves in a fixed order) -> stage[chunk]
 //   density_finish_kernel       one thread adds the chunks in order and writes -(1/sigma) s and -(1/r) s
 //   density_chan_finish_kernel  channel-wise features: thread t adds kfac_c S_c (S_c: the chunks in order) of channels t,
 //                               t + 256, ... in order, a butterfly per wave, the waves in order, then -(1/sigma)
@@ -20,15 +20,12 @@
 
 namespace mvx {
 
-constexpr int DCHUNK = 4096; // atoms per block of the first stage
-
 template <typename real>
 __global__ void __launch_bounds__(256) density_sum_kernel(const double *__restrict__ part, int64_t total,
                                                           const real *__restrict__ radii, double *__restrict__ grad_radii,
                                                           double *__restrict__ stage) {
-    __shared__ double wsum[4];
-    const int64_t lo = (int64_t)blockIdx.x * DCHUNK;
-    const int64_t hi = lo + DCHUNK < total ? lo + DCHUNK : total;
+    const int64_t lo = (int64_t)blockIdx.x * GRAD_CHUNK;
+    const int64_t hi = lo + GRAD_CHUNK < total ? lo + GRAD_CHUNK : total;
     double s = 0.0;
     for (int64_t a = lo + threadIdx.x; a < hi; a += 256) {
         const double S = part[a];
@@ -38,10 +35,7 @@ __global__ void __launch_bounds__(256) density_sum_kernel(const double *__restri
             grad_radii[a] = S != 0.0 ? -S / r : 0.0;
         }
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) stage[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    block_sum4(s, [&](double sum) { stage[blockIdx.x] = sum; });
 }
 
 // r, sigma: the values the forward used (float32 handles: the float widened)
@@ -59,7 +53,6 @@ template <typename real>
 __global__ void __launch_bounds__(256) density_chan_finish_kernel(const double *__restrict__ stage, int32_t nchunk, int32_t C,
                                                                   const real *__restrict__ kc, double sigma,
                                                                   double *__restrict__ grad_sigma) {
-    __shared__ double wsum[4];
     double acc = 0.0;
     for (int c = threadIdx.x; c < C; c += 256) {
         double s = 0.0;
@@ -67,27 +60,18 @@ __global__ void __launch_bounds__(256) density_chan_finish_kernel(const double *
         const double kfac = std::is_same<real, double>::value ? 2.0 * (double)kc[c] : 2.0 * LN2 * (double)kc[c];
         acc += kfac * s;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double s = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        grad_sigma[0] = s != 0.0 ? -s / sigma : 0.0;
-    }
+    block_sum4(acc, [&](double s) { grad_sigma[0] = s != 0.0 ? -s / sigma : 0.0; });
 }
-
-size_t grad_density_stage_doubles(int64_t total) { return (size_t)((total + DCHUNK - 1) / DCHUNK); }
 
 hipError_t launch_grad_density_sum(const double *part, int64_t total, const void *radii, bool f64, double *grad_radii, double r,
                                    double sigma, double *stage, double *grad_sigma, double *grad_radius, hipStream_t s) {
-    const int32_t nchunk = (int32_t)grad_density_stage_doubles(total);
-    if (f64)
-        hipLaunchKernelGGL(density_sum_kernel<double>, dim3((unsigned)nchunk), dim3(256), 0, s, part, total,
-                           static_cast<const double *>(radii), grad_radii, stage);
-    else
-        hipLaunchKernelGGL(density_sum_kernel<float>, dim3((unsigned)nchunk), dim3(256), 0, s, part, total,
-                           static_cast<const float *>(radii), grad_radii, stage);
-    hipError_t e = hipGetLastError();
+    const int32_t nchunk = grad_nchunk(total);
+    const hipError_t e = for_real(f64, [&](auto t) {
+        typedef typename decltype(t)::type real;
+        hipLaunchKernelGGL(density_sum_kernel<real>, dim3((unsigned)nchunk), dim3(256), 0, s, part, total,
+                           static_cast<const real *>(radii), grad_radii, stage);
+        return hipGetLastError();
+    });
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(density_finish_kernel, dim3(1), dim3(64), 0, s, stage, nchunk, r, sigma, grad_sigma, grad_radius);
     return hipGetLastError();
@@ -95,14 +79,12 @@ hipError_t launch_grad_density_sum(const double *part, int64_t total, const void
 
 hipError_t launch_grad_density_chan(const double *stage, int64_t total, int32_t C, const void *kc, bool f64, double sigma,
                                     double *grad_sigma, hipStream_t s) {
-    const int32_t nchunk = (int32_t)(grad_radii_stage_doubles(total, C) / (size_t)C);
-    if (f64)
-        hipLaunchKernelGGL(density_chan_finish_kernel<double>, dim3(1), dim3(256), 0, s, stage, nchunk, C,
-                           static_cast<const double *>(kc), sigma, grad_sigma);
-    else
-        hipLaunchKernelGGL(density_chan_finish_kernel<float>, dim3(1), dim3(256), 0, s, stage, nchunk, C,
-                           static_cast<const float *>(kc), sigma, grad_sigma);
-    return hipGetLastError();
+    return for_real(f64, [&](auto t) {
+        typedef typename decltype(t)::type real;
+        hipLaunchKernelGGL(density_chan_finish_kernel<real>, dim3(1), dim3(256), 0, s, stage, grad_nchunk(total), C,
+                           static_cast<const real *>(kc), sigma, grad_sigma);
+        return hipGetLastError();
+    });
 }
 
 } // namespace mvx

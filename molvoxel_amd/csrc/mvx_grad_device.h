@@ -1,5 +1,6 @@
-// mvx_grad_device.h - device helpers of the backward pass, shared by mvx_grad.hip (grad_kernel) and mvx_grad_radii.hip
-// (grad_radii_kernel and the radius reductions).
+// mvx_grad_device.h - device helpers and the walk launch of the backward family, included by its six kernel files:
+// mvx_grad.hip, mvx_grad_radii.hip and mvx_score.hip (the walks of mvx_grad_body.inc, launch_walk), mvx_grad_radii.hip and
+// mvx_grad_density.hip (the reductions over a call: block_sum4, sum4), mvx_pose.hip and mvx_views_reduce.hip (wave sums, sum4).
 #pragma once
 #include "mvx_device.h"
 #include "mvx_grad.h"
@@ -39,6 +40,22 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The fixed order in which four waves' sums are added - part of the contract "no atomics: the same bits in any batch and in
+// every run" of every reduction here
+__device__ __forceinline__ double sum4(double w0, double w1, double w2, double w3) { return (w0 + w1) + (w2 + w3); }
+
+// Sum of v over a workgroup of four waves: a butterfly per wave, lane 0 of each wave hands its sum over in LDS, a barrier,
+// then thread 0 alone gets sum4 of the four: thread0(sum). Every thread of the workgroup must call it (the barrier). The two
+// density reductions call it; grad_radii_reduce_kernel and score_reduce_kernel spell the same steps out (see there).
+template <typename Fn>
+__device__ __forceinline__ void block_sum4(double v, Fn &&thread0) {
+    __shared__ double wsum[4];
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) thread0(sum4(wsum[0], wsum[1], wsum[2], wsum[3]));
+}
+
 // 32 per-lane channel partials -> lane l holds the wave's sum of channel l / 2 (31 exchanges instead of 32 x 6): each step
 // halves the channels a lane keeps - the lane with the mask bit set keeps the upper half - and adds its partner's copy of
 // them. a + b and b + a are the same bits, so both lanes of a pair agree and the order is fixed.
@@ -73,6 +90,17 @@ __device__ __forceinline__ T wave_sum32_regs(T (&v)[32], int lane) {
         }
     }
     return v[0] + __shfl_xor(v[0], 1, 64);
+}
+
+// The launch of a walk kernel (one of for_walk's instantiations; extra: its RadiiArgs or ScoreArgs): four atoms per block of
+// 256 in atom order, or 8 a.xcd_span blocks under the spatial order; nothing without atoms. Not launch_kernel<Kern>
+// (mvx_device.h): that one consumes timed_launch's pending profiling events, which the backward entries must not.
+template <typename Kern, typename... Extra>
+static hipError_t launch_walk(Kern kern, const GradArgs &a, hipStream_t s, const Extra &...extra) {
+    if (a.total <= 0) return hipSuccess;
+    const unsigned nblk = (unsigned)((a.total + 3) / 4);
+    hipLaunchKernelGGL(kern, dim3(a.xcd_span ? 8u * (unsigned)a.xcd_span : nblk), dim3(256), 0, s, a, extra...);
+    return hipGetLastError();
 }
 
 } // namespace mvx

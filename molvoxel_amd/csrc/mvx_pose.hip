@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(64 * POSE_WAVES) pose_grad_kernel(const double
     }
     double t[12];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) t[i] = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
+    for (int i = 0; i < 12; ++i) t[i] = sum4(part[0][i], part[1][i], part[2][i], part[3][i]);
     const double q0 = pose[3], q1 = pose[4], q2 = pose[5], q3 = pose[6];
     const double n2 = ((q0 * q0 + q1 * q1) + q2 * q2) + q3 * q3;
     const double n4 = n2 * n2; // (q = 0: 0 / 0 below, a non-finite row)

@@ -35,40 +35,18 @@ __global__ void __launch_bounds__(64 * SCORE_WAVES) score_reduce_kernel(const do
     const int64_t a0 = offsets[b], a1 = offsets[b + 1];
     double s = 0.0;
     for (int64_t a = a0 + 64 * wave + lane; a < a1; a += 64 * SCORE_WAVES) s += atom_scores[a];
+    // (block_sum4's steps spelled out: through the helper this kernel compiles to another body, one instruction less in the
+    // hand-over's address; switch when a changed body may be measured - DESIGN.md section 13)
     s = wave_sum(s);
     if (lane == 0) part[wave] = s;
     __syncthreads();
-    if (threadIdx.x == 0) scores[b] = (part[0] + part[1]) + (part[2] + part[3]); // (no atoms: an exact zero)
+    if (threadIdx.x == 0) scores[b] = sum4(part[0], part[1], part[2], part[3]); // (no atoms: an exact zero)
 }
 
-template <typename GT, int MODE>
-static hipError_t launch_score_mode(const GradArgs &a, const ScoreArgs &sa, bool gauss, bool chanwise, hipStream_t s) {
-    const unsigned nblk = (unsigned)((a.total + 3) / 4);
-    const dim3 grid(a.xcd_span ? 8u * (unsigned)a.xcd_span : nblk), block(256);
-    if constexpr (MODE == MODE_FEATURES) {
-        if (chanwise) {
-            if (gauss) hipLaunchKernelGGL((score_kernel<GT, MODE, true, true>), grid, block, 0, s, a, sa);
-            else hipLaunchKernelGGL((score_kernel<GT, MODE, false, true>), grid, block, 0, s, a, sa);
-            return hipGetLastError();
-        }
-    }
-    if (gauss) hipLaunchKernelGGL((score_kernel<GT, MODE, true, false>), grid, block, 0, s, a, sa);
-    else hipLaunchKernelGGL((score_kernel<GT, MODE, false, false>), grid, block, 0, s, a, sa);
-    return hipGetLastError();
-}
-
-template <typename GT>
-static hipError_t launch_score_grid(const GradArgs &a, const ScoreArgs &sa, int32_t mode, bool gauss, bool chanwise, hipStream_t s) {
-    if (mode == MODE_FEATURES) return launch_score_mode<GT, MODE_FEATURES>(a, sa, gauss, chanwise, s);
-    return launch_score_mode<GT, MODE_TYPES>(a, sa, gauss, false, s); // (single mode: type 0 in every record)
-}
-
-hipError_t launch_score(const GradArgs &a, const ScoreArgs &sa, int32_t mode, int32_t grid_kind, bool gauss, bool chanwise,
-                        hipStream_t s) {
-    if (a.total <= 0) return hipSuccess;
-    if (grid_kind == 2) return launch_score_grid<double>(a, sa, mode, gauss, chanwise, s);
-    if (grid_kind == 1) return launch_score_grid<__bf16>(a, sa, mode, gauss, chanwise, s);
-    return launch_score_grid<float>(a, sa, mode, gauss, chanwise, s);
+hipError_t launch_score(const GradArgs &a, const ScoreArgs &sa, const WalkKey &key, hipStream_t s) {
+    return for_walk(key, [&](auto gt, auto mode, auto gauss, auto chanwise) {
+        return launch_walk(score_kernel<typename decltype(gt)::type, mode, gauss, chanwise>, a, s, sa);
+    });
 }
 
 hipError_t launch_score_reduce(const double *atom_scores, const int64_t *offsets, int32_t B, double *scores, hipStream_t s) {

@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(64 * RED_WAVES) view_reduce_kernel(const int64
     }
     __syncthreads();
     const int j = (int)threadIdx.x;
-    if (j < nc) out[(size_t)n * (size_t)width + c0 + j] = (T)((part[0][j] + part[1][j]) + (part[2][j] + part[3][j]));
+    if (j < nc) out[(size_t)n * (size_t)width + c0 + j] = (T)sum4(part[0][j], part[1][j], part[2][j], part[3][j]);
 }
 
 template <typename T>
@@ -90,8 +90,7 @@ static hipError_t launch_reduce_t(const int64_t *index, const int64_t *offsets, 
 hipError_t launch_view_reduce(const int64_t *index, const int64_t *offsets, int32_t B, int64_t N, const void *rows, int32_t width,
                               bool rows_f64, void *out, hipStream_t s) {
     if (B <= 0 || N <= 0 || width <= 0) return hipSuccess;
-    return rows_f64 ? launch_reduce_t<double>(index, offsets, B, N, rows, width, out, s)
-                    : launch_reduce_t<float>(index, offsets, B, N, rows, width, out, s);
+    return for_real(rows_f64, [&](auto t) { return launch_reduce_t<typename decltype(t)::type>(index, offsets, B, N, rows, width, out, s); });
 }
 
 } // namespace mvx
