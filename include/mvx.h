@@ -444,6 +444,41 @@ int mvx_forward_views_sum(mvx_handle *h, int32_t mode, const double *coords, con
 int mvx_set_sum_parts(mvx_handle *h, int32_t parts);
 
 /*
+ * Per-channel sums and norms of every molecule's grid, without the grids (no counterpart in the reference): what normalised
+ * cross-correlation, shape Tanimoto, MSE against a target and the occupied volume need. For molecule b and channel c, with
+ * g = g_b[c, v] the float32 value the forward entries store at voxel v for the same arguments (whatever the handle's grid_type
+ * and layout: the moments are those of the float32 values):
+ *   moments[b, c, 0] = sum_v (double)g
+ *   moments[b, c, 1] = sum_v (double)g * (double)g
+ *   moments[b, c, 2] = sum_v (double)g * (double)target[c, v]        (only with a target)
+ *   target:  (C, D, D, D) float32 NCDHW on the device, 16-byte aligned, shared by all molecules, or NULL
+ *   moments: (B, C, K) doubles on the device, K = target ? 3 : 2, fully overwritten. mode: 0 features, 1 types, 2 single (C = 1).
+ * The plan is mvx_forward_sum_batch's (the binned route, chunks of 32 channels on zero-padded weight rows, radii[types] as
+ * per-atom radii), run for one molecule per workgroup: the accumulators are bit for bit the values the forward writes. The
+ * products are exact in float64 (a float32 times a float32 fits 53 bits), so the summation is the only rounding: each
+ * moment lies within (n - 1) 2^-53 sum|term| of the exact sum of its n = D^3 terms, and sums of small integers (binary
+ * density with types or one channel) are exact.
+ * Deterministic, no atomics: per slab the two x planes of a register, a fixed butterfly over the 32 lanes of each half of a
+ * wave, the waves in order; then a molecule's slabs in slab order (a second kernel). The slab decomposition depends on the
+ * dimension alone, so a molecule's bits do not depend on its batch, on how the batch is cut into molecule chunks, or on the
+ * presence of a target (moments 0 and 1). A molecule without atoms, or with none inside the box, gets exact zeros; B == 0:
+ * MVX_OK, nothing written; a call without atoms writes zeros to all of `moments`.
+ * Workspace: the forward's pre-pass buffers and, handle-owned, one partial per (molecule, slab, moment, channel) of the
+ * largest molecule chunk (cut as the forward cuts it), not of the call.
+ * Device pointers except offsets / xforms (host; MVX_XF_CENTER_PTR and MVX_XF_POSE_PTR records included), exactly as in
+ * mvx_forward_sum_batch. Asynchronous on `stream`.
+ * MVX_ERR_INVALID before any device is touched, in this order: a bad mode; C <= 0; single mode with C != 1; B < 0; NULL
+ * moments with B > 0; a bad radii_type; channel-wise radii in single mode; NULL or non-monotone offsets; a NULL handle; a bad
+ * pose record; too many atoms; NULL arrays with atoms present; then the four configurations the walk does not serve, each
+ * named in a message that begins with "moments:": a precision-64 handle; channel-wise radii with features; a dimension that
+ * is no multiple of 4; a blockdim that needs per-lane ranges (mvx_plan.lane_range = 1); and a target that is not 16-byte aligned.
+ */
+int mvx_moments_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                      double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                      int32_t B, int32_t C, const float *target /* (C, D, D, D) device, or NULL */,
+                      double *moments /* (B, C, K) device, K = target ? 3 : 2 */, void *stream);
+
+/*
  * Gradients with respect to explicit rigid poses (MVX_XF_POSE_PTR records; no counterpart in the reference): the reduction of
  * the per-atom gradients a backward entry wrote for the same call (grad_coords = M^T dL/dp) to dL/dc, dL/dq and dL/dt of every
  * molecule, on the device. Per molecule with pose (c, q, t), M = M(q) the linear part of the sandwich product (it scales by

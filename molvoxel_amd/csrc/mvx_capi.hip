@@ -6,6 +6,7 @@
 // fallback in this library: without a usable HIP device mvx_create fails.
 #include "mvx_grad.h"
 #include "mvx_internal.h"
+#include "mvx_moments.h"
 #include "mvx_plan.h"
 #include "mvx_pose.h"
 #include "mvx_sum.h"
@@ -134,6 +135,7 @@ struct mvx_handle : NoCopy {
     // mvx_set_sum_parts: K > 1 cuts the molecules of every summed call into parts with a partial grid each (G * C * D^3 floats)
     int sum_parts = 1;
     DevBuf sum_part_grids;
+    DevBuf moments_part; // mvx_moments_batch: the slab partials of one molecule chunk
     int32_t layout = MVX_LAYOUT_NCDHW; // mvx_set_grid_layout
     mvx_plan last_plan{}; // the plan of the last forward call, debug options applied (mvx_debug_last_plan)
     bool has_plan = false;
@@ -253,6 +255,9 @@ struct RunArgs : Call {
 struct SumCall {
     const float *atom_weights; // (sumN,) device, or null
     bool accumulate;           // the sums start from the values in `out`
+    // mvx_moments_batch: the same plan, pre-pass and walk, but per molecule, and (B, C, K) moments instead of a grid
+    double *moments = nullptr;
+    const float *target = nullptr; // (C, D, D, D) device, or null (K = 2)
 };
 
 // Orders this call after the previous call's work when the caller switched streams (see mvx_handle::last_stream).
@@ -588,6 +593,7 @@ struct Forward {
             q.mode = MODE_FEATURES;
             if (q.radii_type == MVX_RADII_CHANNEL) q.radii_type = MVX_RADII_ATOM; // (radii[types]: one radius per atom, no grouped launch)
             q.C = (r.C + 31) / 32 * 32;
+            if (sum->moments) q.out_aligned16 = 1; // (no grid is written: the plan of an aligned one, whatever `moments` points at)
             plan = plan_call(q, k, MVX_LAYOUT_NCDHW, 4);
             if (r.mode != MODE_FEATURES || q.C != r.C || sum->atom_weights) plan.weights_in_place = 0;
         }
@@ -787,7 +793,14 @@ struct Forward {
         const bool interleave = !side_stream && !f64 && nchunk > 1; // chunk by chunk: pre-pass, then its voxelize launch
         // a summed call in parts (mvx_set_sum_parts): parts of q molecules of the CALL, whatever the molecule chunks are; the
         // partial grids start from zero, every chunk's launch adds to those of the parts it meets, one reduction ends the call
-        const int part_q = sum && h->sum_parts > 1 ? (int)(((int64_t)r.B + h->sum_parts - 1) / h->sum_parts) : 0;
+        const bool moments = sum && sum->moments;
+        const int moments_K = moments && sum->target ? 3 : 2;
+        if (moments) { // the partials of the largest molecule chunk
+            int nb_max = 0;
+            for (int k = 0; k < nchunk; ++k) nb_max = std::max(nb_max, chunk_begin(k + 1) - chunk_begin(k));
+            if ((rc = ensure(h->moments_part, moments_part_doubles(va.p, nb_max, moments_K) * sizeof(double)))) return rc;
+        }
+        const int part_q = sum && !moments && h->sum_parts > 1 ? (int)(((int64_t)r.B + h->sum_parts - 1) / h->sum_parts) : 0;
         const int part_G = part_q ? (int)(((int64_t)r.B + part_q - 1) / part_q) : 0;
         const size_t grid_voxels = (size_t)r.C * g_D3();
         if (part_q) {
@@ -805,6 +818,11 @@ struct Forward {
                 if (interleave && (rc = prepass(k))) return rc;
                 if (side_stream) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
                 va.p.b0 = b0;
+                if (moments) { // one walk and one finish per molecule chunk: the partials are the chunk's
+                    double *pw = static_cast<double *>(h->moments_part.p);
+                    if ((rc = timed_launch(h, s, [&] { return launch_moments(va, b1 - b0, gauss, sum->target, pw, sum->moments, s); }))) return rc;
+                    continue;
+                }
                 if (part_q) { // one launch per molecule chunk over the parts that meet it
                     float *pg = static_cast<float *>(h->sum_part_grids.p);
                     if ((rc = timed_launch(h, s, [&] { return launch_voxelize_sum_parts(va, b1 - b0, gauss, pg, part_q, s); }))) return rc;
@@ -932,6 +950,59 @@ int run_sum(mvx_handle *h, const RunArgs &r, int32_t accumulate, const float *at
         return MVX_OK;
     }
     const SumCall sc{atom_weights, accumulate != 0};
+    return run_checked(h, r, e, &sc);
+}
+
+// What the moments kernel - the summed kernel's walk - does not serve, each named: sum_config's rules with texts of their own, and
+// the alignment of the target (read 16 bytes at a time).
+int moments_config(const mvx_handle *h, int mode, int radii_type, int C, const float *target) {
+    if (h->cfg.precision == 64) return fail(MVX_ERR_INVALID, "moments: precision 64 is not supported (moments of float32 grids only)");
+    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES)
+        return fail(MVX_ERR_INVALID, "moments: channel-wise radii with features are not supported (the grouped launch)");
+    if (h->g.D % 4 != 0) return fail(MVX_ERR_INVALID, "moments: a dimension that is no multiple of 4 is not supported (run-wise write-out)");
+    mvx_plan_query q{};
+    q.dimension = h->g.D;
+    q.blockdim = h->g.bd;
+    q.precision = 32;
+    q.C = C;
+    if (plan_call(q, PlanKnobs{}).lane_range) return fail(MVX_ERR_INVALID, "moments: a blockdim that needs per-lane ranges is not supported");
+    if (reinterpret_cast<uintptr_t>(target) & 15u) return fail(MVX_ERR_INVALID, "target must be 16-byte aligned");
+    return MVX_OK;
+}
+
+// ---- mvx_moments_batch: run_sum's checks in run_sum's order (`moments` in the place of `out`, no accumulate), the calls without
+// molecules or atoms, then the forward's steps with a SumCall that asks for moments ----
+int run_moments(mvx_handle *h, const Call &c, const float *target, double *moments) {
+    if (c.mode < MODE_FEATURES || c.mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
+    if (c.C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
+    if (c.mode == MODE_SINGLE && c.C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
+    if (c.B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (!moments && c.B > 0) return fail(MVX_ERR_INVALID, "moments must not be null");
+    if (c.radii_type < MVX_RADII_SCALAR || c.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
+    if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
+    if (c.B > 0 && !c.offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
+    Extent e;
+    if (const char *bad = check_offsets(c.offsets, c.B, e)) return fail(MVX_ERR_INVALID, bad);
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (int rc = check_pose_records(c.xforms, c.B)) return rc;
+    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (e.total > 0) {
+        if (!c.coords) return fail(MVX_ERR_INVALID, "coords must not be null");
+        if (c.mode != MODE_SINGLE && !c.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
+        if (!c.radii && c.radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
+    }
+    if (int rc = moments_config(h, c.mode, c.radii_type, c.C, target)) return rc;
+    if (c.B == 0) return MVX_OK;
+    if (e.total == 0) { // no atoms: every moment is zero
+        CallScope scope(h, c.stream);
+        if (scope.rc) return scope.rc;
+        HIP_TRY(hipMemsetAsync(moments, 0, (size_t)c.B * c.C * (target ? 3 : 2) * sizeof(double), c.stream));
+        return MVX_OK;
+    }
+    const RunArgs r{c, moments, MVX_DEVICE};
+    SumCall sc{nullptr, false};
+    sc.moments = moments;
+    sc.target = target;
     return run_checked(h, r, e, &sc);
 }
 
@@ -1080,6 +1151,13 @@ int mvx_forward_sum_batch(mvx_handle *h, int32_t mode, const double *coords, con
     const RunArgs r{{mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
                      reinterpret_cast<hipStream_t>(stream), MVX_DEVICE}, out, MVX_DEVICE};
     return run_sum(h, r, accumulate, atom_weights);
+}
+
+int mvx_moments_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii, double radius_scalar,
+                      int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B, int32_t C, const float *target,
+                      double *moments, void *stream) {
+    return run_moments(h, Call{mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
+                               reinterpret_cast<hipStream_t>(stream), MVX_DEVICE}, target, moments);
 }
 
 // ---- views of one shared cloud (mvx_views.hip) ----------------------------------------------------------------------------

@@ -30,6 +30,10 @@
 
 namespace mvx {
 
+// how both kernels end the walk of mvx_sum_body.inc: one ordinary write-out (it begins with a barrier); "molecule" 0: the grid is
+// the only one behind `grid`
+#define MVX_SUM_WRITE Ops::write(acc, 1, un, tid, lane, wave, NW, 0, L, x0, y0, z0, grid, P)
+
 template <bool GAUSS, int MAXT>
 __global__ void __launch_bounds__(MAXT, 4)
     voxelize_sum_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
@@ -37,6 +41,7 @@ __global__ void __launch_bounds__(MAXT, 4)
     float *const grid = out;
     const int mol0 = P.b0, nmol = nb, from_grid = accumulate;
 #include "mvx_sum_body.inc"
+    MVX_SUM_WRITE;
 }
 
 // The same walk for one PART of the call's molecules (mvx_set_sum_parts, K > 1): blockIdx.z + g0 is the part g, which owns the
@@ -55,6 +60,7 @@ __global__ void __launch_bounds__(MAXT, 4)
     float *const grid = parts + (size_t)g * ((size_t)P.C * P.D * P.D * P.D);
     const int mol0 = (int)lo, nmol = (int)(hi - lo), from_grid = lo > first ? 1 : 0;
 #include "mvx_sum_body.inc"
+    MVX_SUM_WRITE;
 }
 
 // out[v] = (accumulate ? out[v] : +0) + S_0[v] + S_1[v] + ... + S_{G-1}[v]: one float32 rounding per add, in part order; n4

@@ -1,6 +1,6 @@
 // mvx_sum_body.inc - the walk of the summed-grid kernels (mvx_sum.hip), textually included into each __global__ as
 // mvx_slab_body.inc is: one workgroup per (output slab, chunk of 32 channels) walks the candidate lines of its slab molecule
-// after molecule with the accumulators in registers and writes the slab once.
+// after molecule with the accumulators in registers; what becomes of them is the including kernel's last statement.
 //
 // The including kernel provides: GAUSS, MAXT (template arguments); rec, w, slist, slist_ext, P (kernel arguments); and
 //   float *grid       the (C, D, D, D) float32 NCDHW grid this workgroup reads (from_grid) and writes
@@ -87,5 +87,5 @@
             filter_walk<Ops>(xl, acc, e0, n, RW, un, lane, wave, L, P, nullptr, nullptr);
         }
     }
-    // one ordinary write-out (it begins with a barrier); "molecule" 0: the grid is the only one behind `grid`
-    Ops::write(acc, 1, un, tid, lane, wave, NW, 0, L, x0, y0, z0, grid, P);
+    // The including kernel ends the walk: MVX_SUM_WRITE (the summed-grid kernels) or an epilogue of its own over acc (mvx_moments.hip:
+    // rows_live says whether any line had candidates).

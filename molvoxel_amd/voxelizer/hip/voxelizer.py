@@ -78,8 +78,8 @@ class _Call:
         assert not fields, sorted(fields)
 
     def batch_args(self, vox, coords=None, channels=None):
-        """The arguments mvx_backward_batch, mvx_backward_radii_batch, mvx_backward_density_batch, mvx_score_batch and
-        mvx_forward_sum_batch begin with. coords / channels: the tensors autograd saved, in backward()."""
+        """The arguments mvx_backward_batch, mvx_backward_radii_batch, mvx_backward_density_batch, mvx_score_batch,
+        mvx_forward_sum_batch and mvx_moments_batch begin with. coords / channels: the tensors autograd saved, in backward()."""
         return (vox._handle, _lib.MODES[self.mode], vox._ptr(self.coords if coords is None else coords),
                 vox._ptr(self.channels if channels is None else channels), vox._ptr(self.radii), self.rs, vox._radii_type_code(),
                 self.offsets.ctypes.data, None if self.xforms is None else C.addressof(self.xforms), self.B, self.C)
@@ -1033,20 +1033,21 @@ class Voxelizer(BaseVoxelizer):
         return self._forward_sum(coords, offsets, centers, channels, radii, weights, num_channels, out_grid, accumulate,
                                  posed=(quaternions, translations))
 
-    def _sum_guard(self, channels):
-        """What a summed call refuses before it looks at anything else: the configurations voxelize_sum_kernel does not serve."""
+    def _sum_guard(self, channels, what="forward_sum", entries="forward_sum / forward_posed_sum", result="the grid is a tensor",
+                   alt="use forward_batch(...).sum(0) (forward_posed_batch(...).sum(0)) instead"):
+        """What a summed call refuses before it looks at anything else: the configurations voxelize_sum_kernel does not serve.
+        what, entries, result, alt: the texts of another family on the same walk (moments_batch)."""
         if self.output != "torch":
-            raise ValueError("forward_sum / forward_posed_sum need output='torch': the grid is a tensor on the voxelizer's device")
-        alt = "use forward_batch(...).sum(0) (forward_posed_batch(...).sum(0)) instead"
+            raise ValueError(f"{entries} need output='torch': {result} on the voxelizer's device")
         if self.precision == 64:
-            raise NotImplementedError(f"forward_sum does not support precision 64 (float32 sums only): {alt}")
+            raise NotImplementedError(f"{what} does not support precision 64 (float32 sums only): {alt}")
         if self.is_radii_type_channel_wise and channels is not None and getattr(channels, "ndim", 1) == 2:
-            raise NotImplementedError(f"forward_sum does not support channel-wise radii with features: {alt}")
+            raise NotImplementedError(f"{what} does not support channel-wise radii with features: {alt}")
         D, bd = int(self.dimension), int(self.blockdim)
         if D % 4 != 0:
-            raise NotImplementedError(f"forward_sum does not support a dimension that is no multiple of 4 (got {D}): {alt}")
+            raise NotImplementedError(f"{what} does not support a dimension that is no multiple of 4 (got {D}): {alt}")
         if -(-D // bd) > 1 and bd % 8 != 0:  # (mvx_plan.lane_range: reference blocks that cut through 2 x 4 x 8 sub-tiles)
-            raise NotImplementedError(f"forward_sum does not support blockdim={bd} at dimension {D} (per-lane ranges): {alt}")
+            raise NotImplementedError(f"{what} does not support blockdim={bd} at dimension {D} (per-lane ranges): {alt}")
 
     def _sum_rules(self, out_grid, accumulate, weights):
         """The family rules of a summed call, for the builders' `check`: out_grid / accumulate, then the weights - before
@@ -1164,6 +1165,59 @@ class Voxelizer(BaseVoxelizer):
     def sum_parts(self) -> int:
         """The number of parts summed calls are cut into (set_sum_parts); 1: the one-pass sum."""
         return self._sum_parts
+
+    # ------------------------------------------------------------------------------------------
+    # MOMENTS (per-channel sums and norms of every molecule's grid without the grids: mvx_moments_batch)
+    def moments_batch(self, coords, offsets, centers, channels, radii, target=None, num_channels=None,
+                      random_translation=0.0, random_rotation=False):
+        """Per-channel sums and norms of the B grids forward_batch would write with the same arguments - without writing them.
+        With g = grid[b, c] as float32 values (whatever this voxelizer's grid_dtype / grid_layout) and float64 sums over the voxels:
+
+            m[b, c, 0] = sum g        m[b, c, 1] = sum g * g        m[b, c, 2] = sum g * target[c]    (only with a target)
+
+        What sits on top of them: normalised cross-correlation m2 / sqrt(m1 * sum(target ** 2)), shape Tanimoto
+        O_ab / (O_aa + O_bb - O_ab) with the self-overlaps m1, MSE against the target (m1 - 2 m2 + sum(target ** 2)) / D^3, and
+        occupied volume or total mass m0 (binary density: the voxel count).
+
+        Arguments, checks, RNG order and records are forward_batch's; host arrays are moved to the device. Needs
+        output="torch". target: None or one (C,D,H,W) array shared by all molecules, converted with
+        `.to(device, torch.float32).contiguous()`. Returns a (B, C, 2) - with a target (B, C, 3) - float64 tensor on this device.
+        The products are exact in float64, so each moment lies within (D^3 - 1) * 2^-53 * sum|term| of the exact sum; sums of
+        small integers (binary density with types or one channel) are exact. Deterministic, no atomics: a molecule's values do
+        not depend on its batch, and the first two do not depend on the target. Molecules without atoms inside the box give
+        exact zeros. The result is NOT part of the autograd graph: inputs that require grad are read as values.
+        Not supported (NotImplementedError; use forward_batch(...) and reduce the grids): precision 64, channel-wise radii with
+        features, dimensions that are no multiple of 4, and blockdims that cut through the kernels' 2 x 4 x 8 sub-tiles."""
+        return self._moments_batch(coords, offsets, centers, channels, radii, target, num_channels, random_translation,
+                                   random_rotation)
+
+    def moments_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, target=None,
+                            num_channels=None):
+        """moments_batch with one explicit rigid pose per molecule (forward_posed_batch's arguments and records): the moments
+        of the grids of B poses - every pose's cross-correlation with a map in one call. Not part of the autograd graph."""
+        return self._moments_batch(coords, offsets, centers, channels, radii, target, num_channels,
+                                   posed=(quaternions, translations))
+
+    def _moments_batch(self, coords, offsets, centers, channels, radii, target=None, num_channels=None, random_translation=0.0,
+                       random_rotation=False, posed=None):
+        """moments_batch's body. posed: (quaternions, translations) of moments_posed_batch."""
+        self._sum_guard(channels, "moments_batch", "moments_batch / moments_posed_batch", "the moments are a tensor",
+                        "use forward_batch(...) (forward_posed_batch(...)) and reduce the grids instead")
+
+        def check(B, C_, offsets):
+            if target is not None:
+                shape = tuple(getattr(target, "shape", ()))
+                assert shape == self.grid_dimension(C_), f"target does not match dimension: {shape} vs {self.grid_dimension(C_)}"
+
+        with torch.no_grad():
+            call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
+                                    posed, device=True, check=check)
+            T = None
+            if target is not None:
+                T = (target if _is_torch(target) else torch.as_tensor(np.asarray(target))).to(device=self.device, dtype=torch.float32).contiguous()
+            out = torch.empty((call.B, call.C, 2 if T is None else 3), dtype=torch.float64, device=self.device)
+            _lib.check(self._lib.mvx_moments_batch(*call.batch_args(self), self._ptr(T), self._ptr(out), self._stream()))
+            return out
 
     # ------------------------------------------------------------------------------------------
     # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
