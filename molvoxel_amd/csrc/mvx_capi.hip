@@ -31,6 +31,9 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
+// How an entry ends a chain of rules that each give the text of what they found wrong, or null.
+int reject(const char *bad) { return bad ? fail(MVX_ERR_INVALID, bad) : MVX_OK; }
+
 int fail_hip(hipError_t e, const char *what) {
     g_err = std::string(what) + ": " + hipGetErrorString(e);
     return MVX_ERR_HIP;
@@ -246,17 +249,31 @@ struct Call {
     int in_kind; // MVX_HOST | MVX_DEVICE: where coords, channels, radii and the memory behind the records' pointers live
 };
 
+// The Call of an entry that takes a batch (B molecules behind host offsets), and of one that takes B views of one cloud of N atoms.
+Call batch_call(int mode, const double *coords, const void *channels, const void *radii, double radius_scalar, int radii_type,
+                const int64_t *offsets, const mvx_xform *xforms, int B, int C, void *stream, int in_kind = MVX_DEVICE) {
+    return {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C, reinterpret_cast<hipStream_t>(stream), in_kind};
+}
+
+Call views_call(int mode, const double *coords, const void *channels, const void *radii, double radius_scalar, int radii_type, int64_t N,
+                const mvx_xform *xforms, int B, int C, void *stream, int in_kind = MVX_DEVICE) {
+    return {mode, coords, channels, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), in_kind};
+}
+
 struct RunArgs : Call {
     void *out;
     int out_kind;
+    // the arrays were produced on the caller's stream a moment ago (the gathered rows of mvx_forward_views): the pre-pass must
+    // not run ahead of them on the side stream, so cross-call overlap (mvx_set_overlap) does not apply to this call
+    bool no_overlap = false;
 };
 
 // mvx_forward_sum_batch: what a forward call that sums its molecules into ONE (C, D, D, D) float32 grid brings next to its RunArgs
 struct SumCall {
     const float *atom_weights; // (sumN,) device, or null
     bool accumulate;           // the sums start from the values in `out`
-    // mvx_moments_batch: the same plan, pre-pass and walk, but per molecule, and (B, C, K) moments instead of a grid
-    double *moments = nullptr;
+    // mvx_moments_batch: the same plan, pre-pass and walk, but per molecule, and `out` takes (B, C, K) float64 moments instead of a grid
+    bool moments = false;
     const float *target = nullptr; // (C, D, D, D) device, or null (K = 2)
 };
 
@@ -291,11 +308,11 @@ struct CallScope {
 };
 
 // Explicit poses (MVX_XF_POSE_PTR): the other flag bits of such a record are clear and its pointer is set.
-int check_pose_records(const mvx_xform *xf, int n) {
+const char *check_pose_records(const mvx_xform *xf, int n) {
     for (int i = 0; xf && i < n; ++i)
         if ((xf[i].flags & MVX_XF_POSE_PTR) && (xf[i].flags != MVX_XF_POSE_PTR || !xf[i].center_ptr))
-            return fail(MVX_ERR_INVALID, "a MVX_XF_POSE_PTR record must have every other flag bit clear and a non-null center_ptr");
-    return MVX_OK;
+            return "a MVX_XF_POSE_PTR record must have every other flag bit clear and a non-null center_ptr";
+    return nullptr;
 }
 
 bool has_pose_records(const mvx_xform *xf, int n) {
@@ -304,15 +321,32 @@ bool has_pose_records(const mvx_xform *xf, int n) {
     return false;
 }
 
-// All atoms of a call and its largest molecule; too_many: the total does not fit (each entry reports it where it always did).
+// All atoms of a call and its largest molecule.
 struct Extent {
     int64_t total = 0, max_atoms = 0;
-    bool too_many() const { return total >= (int64_t)1 << 31; }
 };
 
-// The rules for host offsets (B + 1 entries, not null; B <= 0: nothing to check): the text of the first broken one, or null.
+// ---- the rules that more than one entry applies, each stated once: the text of the first broken one, or null. The entries
+// compose them around rules of their own, whose places differ (tests/test_reject_order_host.py pins every entry's order) ----
+// An atom count (of a batch, a cloud or a selection) that does not fit; each entry reports it where it always did.
+const char *too_many_atoms(int64_t n) { return n >= (int64_t)1 << 31 ? "too many atoms" : nullptr; }
+
+const char *bad_mode(int mode) { return mode < MODE_FEATURES || mode > MODE_SINGLE ? "bad mode (0 features, 1 types, 2 single)" : nullptr; }
+
+const char *bad_channel_count(const Call &c) {
+    if (c.C <= 0) return "C must be > 0";
+    return c.mode == MODE_SINGLE && c.C != 1 ? "single mode has one channel (C = 1)" : nullptr;
+}
+
+const char *bad_radii_type(const Call &c) {
+    if (c.radii_type < MVX_RADII_SCALAR || c.radii_type > MVX_RADII_CHANNEL) return "bad radii_type";
+    return c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE ? "Channel-Wise Radii Type is not supported" : nullptr; // numpy/voxelizer.py:443
+}
+
+// The rules for host offsets (B + 1 entries; B <= 0: nothing to check).
 const char *check_offsets(const int64_t *offsets, int B, Extent &e) {
     if (B <= 0) return nullptr;
+    if (!offsets) return "offsets must not be null";
     if (offsets[0] != 0) return "offsets[0] must be 0";
     for (int b = 0; b < B; ++b) {
         if (offsets[b + 1] < offsets[b]) return "offsets must be non-decreasing";
@@ -328,10 +362,7 @@ int validate(const mvx_handle *h, const RunArgs &r, Extent &e) {
     if (r.B < 0 || r.C <= 0) return fail(MVX_ERR_INVALID, "B must be >= 0 and C > 0");
     if (r.B == 0) return MVX_OK;
     if (!r.offsets || !r.out) return fail(MVX_ERR_INVALID, "offsets/out must not be null");
-    if (r.radii_type < MVX_RADII_SCALAR || r.radii_type > MVX_RADII_CHANNEL)
-        return fail(MVX_ERR_INVALID, "bad radii_type");
-    if (r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_SINGLE)
-        return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported"); // numpy/voxelizer.py:443
+    if (const char *bad = bad_radii_type(r)) return fail(MVX_ERR_INVALID, bad);
     if ((r.in_kind != MVX_HOST && r.in_kind != MVX_DEVICE) || (r.out_kind != MVX_HOST && r.out_kind != MVX_DEVICE))
         return fail(MVX_ERR_INVALID, "bad memory kind");
     if (const char *bad = check_offsets(r.offsets, r.B, e)) return fail(MVX_ERR_INVALID, bad);
@@ -340,8 +371,29 @@ int validate(const mvx_handle *h, const RunArgs &r, Extent &e) {
     if (!r.radii && (r.radii_type == MVX_RADII_CHANNEL || (r.radii_type == MVX_RADII_ATOM && e.total > 0)))
         return fail(MVX_ERR_INVALID, "radii array required");
     if (e.total > 0 && r.mode != MODE_SINGLE && !r.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
-    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
-    return check_pose_records(r.xforms, r.B);
+    if (const char *bad = too_many_atoms(e.total)) return fail(MVX_ERR_INVALID, bad);
+    return reject(check_pose_records(r.xforms, r.B));
+}
+
+// The chain that the summed, moments, backward and score entries share, from the number of molecules to the records.
+// `after_B`: what the entry found wrong with an argument of its own whose rule sits behind "B must be >= 0" (null: nothing).
+const char *check_batch(const mvx_handle *h, const Call &c, const char *after_B, Extent &e) {
+    if (c.B < 0) return "B must be >= 0";
+    if (after_B) return after_B;
+    if (const char *bad = bad_radii_type(c)) return bad;
+    if (const char *bad = check_offsets(c.offsets, c.B, e)) return bad;
+    if (!h) return "null handle";
+    return check_pose_records(c.xforms, c.B); // (the first rule that reads the records)
+}
+
+// ... and behind it: the atom count, then what a call with atoms must bring. `with_coords`: an array of the entry's own that
+// shares `coords_text` with the coordinates (the backward's grad_out, the score's field), or the coordinates again.
+const char *check_atoms(const Call &c, const Extent &e, const void *with_coords, const char *coords_text) {
+    if (e.total == 0) return nullptr;
+    if (const char *bad = too_many_atoms(e.total)) return bad;
+    if (!c.coords || !with_coords) return coords_text;
+    if (c.mode != MODE_SINGLE && !c.channels) return "channels must not be null";
+    return !c.radii && c.radii_type != MVX_RADII_SCALAR ? "radii array required" : nullptr;
 }
 
 // ---- 2. inputs and metadata on the device ---------------------------------------------------------------------------
@@ -525,6 +577,11 @@ PrepArgs prep_args(const mvx_handle *h, const Call &c, int64_t total, const Devi
 constexpr size_t CHAN_TC_OFF = 16;
 inline size_t chan_kc_off(int C) { return CHAN_TC_OFF + align_up((size_t)C * sizeof(double), 16); }
 
+// What the voxelize launches of a binned forward call are (Forward::make_plan settles it, Forward::launch_binned switches on it):
+// B grids by voxelize_kernel and its kin, by the grouped launch of channel-wise features, float64 grids in one launch; one summed
+// grid, one in parts (mvx_set_sum_parts), or no grid at all but every molecule's moments.
+enum Walk { WALK_GRIDS, WALK_GROUPED, WALK_F64, WALK_SUM, WALK_SUM_PARTS, WALK_MOMENTS };
+
 // One forward call: what the steps of run() hand to each other, and the steps themselves in the order run() takes them.
 struct Forward {
     mvx_handle *h;
@@ -539,6 +596,7 @@ struct Forward {
     size_t out_bytes = 0;
     void *d_out = nullptr;
     mvx_plan plan{};
+    Walk walk = WALK_GRIDS;
     Workspace *w = nullptr;
     // order_prepass: the pre-pass's stream - the caller's (s), or the side stream
     hipStream_t s = r.stream, pre = s;
@@ -599,12 +657,14 @@ struct Forward {
         }
         h->last_plan = plan;
         h->has_plan = true;
+        walk = sum ? (sum->moments ? WALK_MOMENTS : (h->sum_parts > 1 ? WALK_SUM_PARTS : WALK_SUM))
+                   : (f64 ? WALK_F64 : (plan.grouped ? WALK_GROUPED : WALK_GRIDS));
         const bool forced_pipeline = h->knobs.pipeline > 1 && r.B >= 4 * h->knobs.pipeline;
         // Cross-call overlap (mvx_set_overlap): this call's pre-pass fills the other workspace set on the side stream,
         // under the previous call's voxelize launches. Device-resident inputs and outputs only.
         // Batches only (mvx.h: "the batched three-launch path"): a per-molecule call hands over arrays its Python layer may
         // have converted on the caller's stream a moment ago, which the side stream would not wait for.
-        overlap = !sum && h->overlap && plan.route != MVX_ROUTE_DIRECT && r.B > 1 && plan.nchunk == 1 && !forced_pipeline &&
+        overlap = !sum && h->overlap && !r.no_overlap && plan.route != MVX_ROUTE_DIRECT && r.B > 1 && plan.nchunk == 1 && !forced_pipeline &&
                   r.in_kind == MVX_DEVICE && r.out_kind == MVX_DEVICE;
         if (overlap) h->cur ^= 1;
         w = &h->ws[h->cur];
@@ -701,6 +761,12 @@ struct Forward {
         va.n_one = ext.total;
         va.Tc = d_Tc;
         va.kc = d_kc;
+        if (walk == WALK_GROUPED) {
+            // channels grouped by radius (chan_aux_kernel): chunks of 32 channels on the matrix-core path, one
+            // threshold test and one density per radius slot and candidate, feature rows read in place
+            va.Tc = reinterpret_cast<const double *>(d_groups);
+            va.kc = reinterpret_cast<const float *>(d_chan_slot);
+        }
         va.out = d_out;
         va.bf16 = bf16 ? 1 : 0;
         va.ndhwc = ndhwc ? 1 : 0;
@@ -793,69 +859,60 @@ struct Forward {
         const bool interleave = !side_stream && !f64 && nchunk > 1; // chunk by chunk: pre-pass, then its voxelize launch
         // a summed call in parts (mvx_set_sum_parts): parts of q molecules of the CALL, whatever the molecule chunks are; the
         // partial grids start from zero, every chunk's launch adds to those of the parts it meets, one reduction ends the call
-        const bool moments = sum && sum->moments;
-        const int moments_K = moments && sum->target ? 3 : 2;
-        if (moments) { // the partials of the largest molecule chunk
+        const int part_q = (int)(((int64_t)r.B + h->sum_parts - 1) / h->sum_parts), part_G = (int)(((int64_t)r.B + part_q - 1) / part_q);
+        const size_t grid_voxels = (size_t)r.C * g_D3();
+        float *part_grids = nullptr;
+        if (walk == WALK_SUM_PARTS) {
+            if ((rc = ensure(h->sum_part_grids, (size_t)part_G * grid_voxels * sizeof(float)))) return rc;
+            part_grids = static_cast<float *>(h->sum_part_grids.p);
+            HIP_TRY(hipMemsetAsync(part_grids, 0, (size_t)part_G * grid_voxels * sizeof(float), s));
+        }
+        if (walk == WALK_MOMENTS) { // the partials of the largest molecule chunk
             int nb_max = 0;
             for (int k = 0; k < nchunk; ++k) nb_max = std::max(nb_max, chunk_begin(k + 1) - chunk_begin(k));
-            if ((rc = ensure(h->moments_part, moments_part_doubles(va.p, nb_max, moments_K) * sizeof(double)))) return rc;
+            if ((rc = ensure(h->moments_part, moments_part_doubles(va.p, nb_max, sum->target ? 3 : 2) * sizeof(double)))) return rc;
         }
-        const int part_q = sum && !moments && h->sum_parts > 1 ? (int)(((int64_t)r.B + h->sum_parts - 1) / h->sum_parts) : 0;
-        const int part_G = part_q ? (int)(((int64_t)r.B + part_q - 1) / part_q) : 0;
-        const size_t grid_voxels = (size_t)r.C * g_D3();
-        if (part_q) {
-            if ((rc = ensure(h->sum_part_grids, (size_t)part_G * grid_voxels * sizeof(float)))) return rc;
-            HIP_TRY(hipMemsetAsync(h->sum_part_grids.p, 0, (size_t)part_G * grid_voxels * sizeof(float), s));
-        }
+        double *moments_part = static_cast<double *>(h->moments_part.p);
         for (int k = 0; k < nchunk && !interleave; ++k)
             if ((rc = prepass(k))) return rc;
-        if (f64) { // float64 grids: one launch over the whole batch
-            for (int k = 0; k < nchunk && side_stream; ++k) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
-            if ((rc = timed_launch(h, s, [&] { return launch_voxelize64(va, ct, gauss, chanwise, lr_blocks, s); }))) return rc;
-        } else {
-            for (int k = 0; k < nchunk; ++k) {
-                const int b0 = chunk_begin(k), b1 = chunk_begin(k + 1);
-                if (interleave && (rc = prepass(k))) return rc;
-                if (side_stream) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
-                va.p.b0 = b0;
-                if (moments) { // one walk and one finish per molecule chunk: the partials are the chunk's
-                    double *pw = static_cast<double *>(h->moments_part.p);
-                    if ((rc = timed_launch(h, s, [&] { return launch_moments(va, b1 - b0, gauss, sum->target, pw, sum->moments, s); }))) return rc;
-                    continue;
-                }
-                if (part_q) { // one launch per molecule chunk over the parts that meet it
-                    float *pg = static_cast<float *>(h->sum_part_grids.p);
-                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize_sum_parts(va, b1 - b0, gauss, pg, part_q, s); }))) return rc;
-                    continue;
-                }
-                if (sum) { // one launch per molecule chunk; chunk k > 0 continues the sums chunk k - 1 wrote
-                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize_sum(va, b1 - b0, gauss, sum->accumulate || k > 0, s); }))) return rc;
-                    continue;
-                }
-                if (plan.grouped) {
-                    // channels grouped by radius (chan_aux_kernel): chunks of 32 channels on the matrix-core path, one
-                    // threshold test and one density per radius slot and candidate, feature rows read in place
-                    VoxArgs vg = va;
-                    vg.Tc = reinterpret_cast<const double *>(d_groups);
-                    vg.kc = reinterpret_cast<const float *>(d_chan_slot);
-                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize_grouped(vg, b1 - b0, gauss, lane_range, s); }))) return rc;
-                    continue;
-                }
+        for (int k = 0; k < nchunk; ++k) {
+            const int b0 = chunk_begin(k), nb = chunk_begin(k + 1) - b0;
+            if (interleave && (rc = prepass(k))) return rc;
+            if (side_stream) HIP_TRY(hipStreamWaitEvent(s, overlap ? w->ev_pre : h->ev_pre[k], 0));
+            va.p.b0 = walk == WALK_F64 ? 0 : b0;
+            rc = MVX_OK;
+            switch (walk) {
+            case WALK_F64: // float64 grids: one launch over the whole batch, behind the pre-pass of every chunk
+                if (k == nchunk - 1) rc = timed_launch(h, s, [&] { return launch_voxelize64(va, ct, gauss, chanwise, lr_blocks, s); });
+                break;
+            case WALK_MOMENTS: // one walk and one finish per molecule chunk: the partials are the chunk's
+                rc = timed_launch(h, s, [&] { return launch_moments(va, nb, gauss, sum->target, moments_part, static_cast<double *>(d_out), s); });
+                break;
+            case WALK_SUM_PARTS: // one launch per molecule chunk over the parts that meet it
+                rc = timed_launch(h, s, [&] { return launch_voxelize_sum_parts(va, nb, gauss, part_grids, part_q, s); });
+                break;
+            case WALK_SUM: // one launch per molecule chunk; chunk k > 0 continues the sums chunk k - 1 wrote
+                rc = timed_launch(h, s, [&] { return launch_voxelize_sum(va, nb, gauss, sum->accumulate || k > 0, s); });
+                break;
+            case WALK_GROUPED: // (the groups and radius slots travel in va.Tc / va.kc: kernel_args)
+                rc = timed_launch(h, s, [&] { return launch_voxelize_grouped(va, nb, gauss, lane_range, s); });
+                break;
+            case WALK_GRIDS:
                 va.p.ncc = plan.nfull;
                 va.p.ncc_inv = umulhi_inverse(plan.nfull); // (the main launch of a call with a remainder launch has nfull, not ncc, chunks per molecule)
                 va.p.c0 = 0;
                 // the bracket holds voxelize_kernel alone (what rocprofv3 reports under that name)
-                if ((rc = timed_launch(h, s, [&] { return launch_voxelize(va, b1 - b0, ct, gauss, lr_blocks, s); }))) return rc;
-                if (plan.ct_rem) { // the remainder channels [nfull * ct, C) with a narrower kernel
+                rc = timed_launch(h, s, [&] { return launch_voxelize(va, nb, ct, gauss, lr_blocks, s); });
+                if (!rc && plan.ct_rem) { // the remainder channels [nfull * ct, C) with a narrower kernel
                     va.p.ncc = 1;
                     va.p.c0 = plan.nfull * ct;
-                    if ((rc = timed_launch(h, s, [&] { return launch_voxelize(va, b1 - b0, plan.ct_rem, gauss, lr_blocks, s); }))) return rc;
+                    rc = timed_launch(h, s, [&] { return launch_voxelize(va, nb, plan.ct_rem, gauss, lr_blocks, s); });
                 }
+                break;
             }
+            if (rc) return rc;
         }
-        if (part_q)
-            HIP_TRY(launch_sum_parts_reduce(static_cast<const float *>(h->sum_part_grids.p), static_cast<float *>(d_out), grid_voxels, part_G,
-                                            sum->accumulate, s));
+        if (walk == WALK_SUM_PARTS) HIP_TRY(launch_sum_parts_reduce(part_grids, static_cast<float *>(d_out), grid_voxels, part_G, sum->accumulate, s));
         if (overlap) { // the next call but one refills this set
             HIP_TRY(hipEventRecord(w->ev_vox, s));
             w->vox_recorded = true;
@@ -899,110 +956,47 @@ int run(mvx_handle *h, const RunArgs &r) {
     return run_checked(h, r, ext, nullptr);
 }
 
-// What the summed kernel does not serve, each named, and the alignment of the grid: the rules of a summed call that read the handle.
-int sum_config(const mvx_handle *h, int mode, int radii_type, int C, const void *out) {
-    if (h->cfg.precision == 64) return fail(MVX_ERR_INVALID, "forward_sum: precision 64 is not supported (float32 sums only)");
-    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES)
-        return fail(MVX_ERR_INVALID, "forward_sum: channel-wise radii with features are not supported (the grouped launch)");
-    if (h->g.D % 4 != 0) return fail(MVX_ERR_INVALID, "forward_sum: a dimension that is no multiple of 4 is not supported (run-wise write-out)");
-    {
-        mvx_plan_query q{};
-        q.dimension = h->g.D;
-        q.blockdim = h->g.bd;
-        q.precision = 32;
-        q.C = C;
-        if (plan_call(q, PlanKnobs{}).lane_range)
-            return fail(MVX_ERR_INVALID, "forward_sum: a blockdim that needs per-lane ranges is not supported");
-    }
-    if (reinterpret_cast<uintptr_t>(out) & 15u) return fail(MVX_ERR_INVALID, "out must be 16-byte aligned");
-    return MVX_OK;
-}
-
-// ---- mvx_forward_sum_batch: its own checks (those of the backward entries for the same arguments, in their order, then what
-// the summed kernel does not serve), the calls without atoms, then the forward's steps with a SumCall ----
-int run_sum(mvx_handle *h, const RunArgs &r, int32_t accumulate, const float *atom_weights) {
-    if (r.mode < MODE_FEATURES || r.mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
-    if (r.C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
-    if (r.mode == MODE_SINGLE && r.C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
-    if (!r.out) return fail(MVX_ERR_INVALID, "out must not be null");
-    if (accumulate != 0 && accumulate != 1) return fail(MVX_ERR_INVALID, "accumulate must be 0 or 1");
-    if (r.B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
-    if (r.radii_type < MVX_RADII_SCALAR || r.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
-    if (r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
-    if (r.B > 0 && !r.offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
-    Extent e;
-    if (const char *bad = check_offsets(r.offsets, r.B, e)) return fail(MVX_ERR_INVALID, bad);
-    if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    if (int rc = check_pose_records(r.xforms, r.B)) return rc;
-    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
-    if (e.total > 0) {
-        if (!r.coords) return fail(MVX_ERR_INVALID, "coords must not be null");
-        if (r.mode != MODE_SINGLE && !r.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
-        if (!r.radii && r.radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
-    }
-    if (int rc = sum_config(h, r.mode, r.radii_type, r.C, r.out)) return rc;
-    if (e.total == 0) { // no atoms: zeros, or - accumulating - nothing at all
-        if (accumulate) return MVX_OK;
-        CallScope scope(h, r.stream);
-        if (scope.rc) return scope.rc;
-        const size_t D = (size_t)h->g.D;
-        HIP_TRY(hipMemsetAsync(r.out, 0, (size_t)r.C * D * D * D * sizeof(float), r.stream));
-        return MVX_OK;
-    }
-    const SumCall sc{atom_weights, accumulate != 0};
-    return run_checked(h, r, e, &sc);
-}
-
-// What the moments kernel - the summed kernel's walk - does not serve, each named: sum_config's rules with texts of their own, and
-// the alignment of the target (read 16 bytes at a time).
-int moments_config(const mvx_handle *h, int mode, int radii_type, int C, const float *target) {
-    if (h->cfg.precision == 64) return fail(MVX_ERR_INVALID, "moments: precision 64 is not supported (moments of float32 grids only)");
-    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES)
-        return fail(MVX_ERR_INVALID, "moments: channel-wise radii with features are not supported (the grouped launch)");
-    if (h->g.D % 4 != 0) return fail(MVX_ERR_INVALID, "moments: a dimension that is no multiple of 4 is not supported (run-wise write-out)");
+// What the summed kernel and the moments kernel on its walk do not serve, each named, and the alignment of what the kernel reads or
+// writes 16 bytes at a time (the grid; the target of the moments): the rules of these calls that read the handle.
+int sum_config(const mvx_handle *h, const Call &c, bool moments, const void *aligned) {
+    const std::string who = moments ? "moments" : "forward_sum";
+    if (h->cfg.precision == 64)
+        return fail(MVX_ERR_INVALID, moments ? "moments: precision 64 is not supported (moments of float32 grids only)"
+                                             : "forward_sum: precision 64 is not supported (float32 sums only)");
+    if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES)
+        return fail(MVX_ERR_INVALID, who + ": channel-wise radii with features are not supported (the grouped launch)");
+    if (h->g.D % 4 != 0) return fail(MVX_ERR_INVALID, who + ": a dimension that is no multiple of 4 is not supported (run-wise write-out)");
     mvx_plan_query q{};
     q.dimension = h->g.D;
     q.blockdim = h->g.bd;
     q.precision = 32;
-    q.C = C;
-    if (plan_call(q, PlanKnobs{}).lane_range) return fail(MVX_ERR_INVALID, "moments: a blockdim that needs per-lane ranges is not supported");
-    if (reinterpret_cast<uintptr_t>(target) & 15u) return fail(MVX_ERR_INVALID, "target must be 16-byte aligned");
+    q.C = c.C;
+    if (plan_call(q, PlanKnobs{}).lane_range) return fail(MVX_ERR_INVALID, who + ": a blockdim that needs per-lane ranges is not supported");
+    if (reinterpret_cast<uintptr_t>(aligned) & 15u) return fail(MVX_ERR_INVALID, moments ? "target must be 16-byte aligned" : "out must be 16-byte aligned");
     return MVX_OK;
 }
 
-// ---- mvx_moments_batch: run_sum's checks in run_sum's order (`moments` in the place of `out`, no accumulate), the calls without
-// molecules or atoms, then the forward's steps with a SumCall that asks for moments ----
-int run_moments(mvx_handle *h, const Call &c, const float *target, double *moments) {
-    if (c.mode < MODE_FEATURES || c.mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
-    if (c.C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
-    if (c.mode == MODE_SINGLE && c.C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
-    if (c.B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
-    if (!moments && c.B > 0) return fail(MVX_ERR_INVALID, "moments must not be null");
-    if (c.radii_type < MVX_RADII_SCALAR || c.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
-    if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
-    if (c.B > 0 && !c.offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
+// ---- mvx_forward_sum_batch (r.out: the grid) and mvx_moments_batch (sc.moments; r.out: the moments): the checks (the shared ones in the
+// backward entries' order; before_B / after_B: what the entry found wrong with its own arguments, on either side of "B must be
+// >= 0"; then what the kernel does not serve), the calls without atoms, then the forward's steps with the SumCall ----
+int run_summed(mvx_handle *h, const RunArgs &r, const SumCall &sc, const char *before_B, const char *after_B) {
     Extent e;
-    if (const char *bad = check_offsets(c.offsets, c.B, e)) return fail(MVX_ERR_INVALID, bad);
-    if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    if (int rc = check_pose_records(c.xforms, c.B)) return rc;
-    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
-    if (e.total > 0) {
-        if (!c.coords) return fail(MVX_ERR_INVALID, "coords must not be null");
-        if (c.mode != MODE_SINGLE && !c.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
-        if (!c.radii && c.radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
-    }
-    if (int rc = moments_config(h, c.mode, c.radii_type, c.C, target)) return rc;
-    if (c.B == 0) return MVX_OK;
-    if (e.total == 0) { // no atoms: every moment is zero
-        CallScope scope(h, c.stream);
+    const char *bad = bad_mode(r.mode);
+    if (!bad) bad = bad_channel_count(r);
+    if (!bad) bad = before_B;
+    if (!bad) bad = check_batch(h, r, after_B, e);
+    if (!bad) bad = check_atoms(r, e, r.coords, "coords must not be null");
+    if (bad) return fail(MVX_ERR_INVALID, bad);
+    if (int rc = sum_config(h, r, sc.moments, sc.moments ? static_cast<const void *>(sc.target) : r.out)) return rc;
+    if (e.total == 0) { // no atoms: every moment is zero (no molecules: there are none); a grid of zeros, or - accumulating - as it was
+        const size_t bytes = sc.moments ? (size_t)r.B * r.C * (sc.target ? 3 : 2) * sizeof(double)
+                                        : (sc.accumulate ? 0 : (size_t)r.C * h->g.D * h->g.D * h->g.D * sizeof(float));
+        if (bytes == 0) return MVX_OK;
+        CallScope scope(h, r.stream);
         if (scope.rc) return scope.rc;
-        HIP_TRY(hipMemsetAsync(moments, 0, (size_t)c.B * c.C * (target ? 3 : 2) * sizeof(double), c.stream));
+        HIP_TRY(hipMemsetAsync(r.out, 0, bytes, r.stream));
         return MVX_OK;
     }
-    const RunArgs r{c, moments, MVX_DEVICE};
-    SumCall sc{nullptr, false};
-    sc.moments = moments;
-    sc.target = target;
     return run_checked(h, r, e, &sc);
 }
 
@@ -1102,23 +1096,20 @@ int mvx_forward_features_batch(mvx_handle *h, const double *coords, const void *
                                double radius_scalar, int32_t radii_type, const int64_t *offsets,
                                const mvx_xform *xforms, int32_t B, int32_t C, void *out, int32_t in_kind,
                                int32_t out_kind, void *stream) {
-    return run(h, RunArgs{{MODE_FEATURES, coords, features, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                           reinterpret_cast<hipStream_t>(stream), in_kind}, out, out_kind});
+    return run(h, {batch_call(MODE_FEATURES, coords, features, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream, in_kind), out, out_kind});
 }
 
 int mvx_forward_types_batch(mvx_handle *h, const double *coords, const int32_t *types, const void *radii,
                             double radius_scalar, int32_t radii_type, const int64_t *offsets,
                             const mvx_xform *xforms, int32_t B, int32_t C, void *out, int32_t in_kind,
                             int32_t out_kind, void *stream) {
-    return run(h, RunArgs{{MODE_TYPES, coords, types, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                           reinterpret_cast<hipStream_t>(stream), in_kind}, out, out_kind});
+    return run(h, {batch_call(MODE_TYPES, coords, types, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream, in_kind), out, out_kind});
 }
 
 int mvx_forward_single_batch(mvx_handle *h, const double *coords, const void *radii, double radius_scalar,
                              int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                              void *out, int32_t in_kind, int32_t out_kind, void *stream) {
-    return run(h, RunArgs{{MODE_SINGLE, coords, nullptr, radii, radius_scalar, radii_type, offsets, 0, xforms, B, 1,
-                           reinterpret_cast<hipStream_t>(stream), in_kind}, out, out_kind});
+    return run(h, {batch_call(MODE_SINGLE, coords, nullptr, radii, radius_scalar, radii_type, offsets, xforms, B, 1, stream, in_kind), out, out_kind});
 }
 
 int mvx_forward_features(mvx_handle *h, const double *coords, const void *features, const void *radii,
@@ -1148,16 +1139,16 @@ int mvx_forward_single(mvx_handle *h, const double *coords, const void *radii, d
 int mvx_forward_sum_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                           double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                           int32_t C, const float *atom_weights, float *out, int32_t accumulate, void *stream) {
-    const RunArgs r{{mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                     reinterpret_cast<hipStream_t>(stream), MVX_DEVICE}, out, MVX_DEVICE};
-    return run_sum(h, r, accumulate, atom_weights);
+    const char *own = !out ? "out must not be null" : ((accumulate != 0 && accumulate != 1) ? "accumulate must be 0 or 1" : nullptr);
+    return run_summed(h, {batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream), out, MVX_DEVICE},
+                      SumCall{atom_weights, accumulate != 0}, own, nullptr);
 }
 
 int mvx_moments_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii, double radius_scalar,
                       int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B, int32_t C, const float *target,
                       double *moments, void *stream) {
-    return run_moments(h, Call{mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                               reinterpret_cast<hipStream_t>(stream), MVX_DEVICE}, target, moments);
+    return run_summed(h, {batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream), moments, MVX_DEVICE},
+                      SumCall{nullptr, false, true, target}, nullptr, (!moments && B > 0) ? "moments must not be null" : nullptr);
 }
 
 // ---- views of one shared cloud (mvx_views.hip) ----------------------------------------------------------------------------
@@ -1180,10 +1171,10 @@ int validate_views(const mvx_handle *h, const Call &v, const char *own) {
     if (!v.radii && (v.radii_type == MVX_RADII_CHANNEL || (v.radii_type == MVX_RADII_ATOM && v.N > 0)))
         return fail(MVX_ERR_INVALID, "radii array required");
     if (v.N > 0 && v.mode == MODE_TYPES && !v.channels) return fail(MVX_ERR_INVALID, "types must not be null");
-    if (v.N >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
+    if (const char *bad = too_many_atoms(v.N)) return fail(MVX_ERR_INVALID, bad);
     if (own) return fail(MVX_ERR_INVALID, own);
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    return check_pose_records(v.xforms, v.B); // (the first rule that reads the records)
+    return reject(check_pose_records(v.xforms, v.B)); // (the first rule that reads the records)
 }
 
 // the cloud and the views' transforms as device arrays
@@ -1290,12 +1281,47 @@ int gather_views(mvx_handle *h, const Call &cloud, const int64_t *index, int64_t
     return MVX_OK;
 }
 
+// The views of a call as a batch of B molecules: the Call that run(), run_summed() or backward_impl() takes, with the host offsets
+// and records it points at. As constructed: B molecules without atoms (what a cloud of no atoms is); compact_views fills it.
+struct ViewBatch : Call {
+    std::vector<int64_t> own_offsets; // B + 1
+    std::vector<mvx_xform> records;   // as stage_views left them (host centres and poses folded in)
+    explicit ViewBatch(const Call &v) : Call(v), own_offsets((size_t)v.B + 1, 0) { offsets = own_offsets.data(); }
+};
+
+// The compact batch of the views `v` of a cloud with atoms (N > 0, B > 0), on the device: scope, staging and selection - or the
+// caller's `index` with its host offsets `index_offsets` (mvx_score_views), and nothing staged -, "too many atoms", gather.
+// `features`: the call after it reads the feature rows of a host-resident cloud. Synchronises the stream once (select_views).
+int compact_views(mvx_handle *h, const Call &v, bool features, const int64_t *index, const int64_t *index_offsets, ViewBatch &b) {
+    CallScope scope(h, v.stream);
+    int rc = scope.rc;
+    if (rc) return rc;
+    Call cloud = v; // ... as device arrays
+    if (index) {
+        b.offsets = index_offsets;
+    } else {
+        ViewInputs in(v);
+        if ((rc = stage_views(h, v, !features, in))) return rc;
+        if ((rc = select_views(h, v, in, nullptr, 0, true, b.own_offsets.data()))) return rc;
+        index = static_cast<const int64_t *>(h->view_index.p);
+        cloud.coords = in.coords;
+        cloud.channels = in.channels;
+        cloud.radii = in.radii;
+        b.records.swap(in.xforms_host);
+        b.xforms = b.records.data();
+    }
+    const int64_t total = b.offsets[v.B];
+    if (const char *bad = too_many_atoms(total)) return fail(MVX_ERR_INVALID, bad);
+    b.in_kind = MVX_DEVICE;
+    return gather_views(h, cloud, index, total, b);
+}
+
 } // namespace
 
 int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types, const void *radii, double radius_scalar,
                      int32_t radii_type, int32_t mode, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                      int64_t *index_out, int64_t index_capacity, int64_t *offsets_out_host, int32_t in_kind, void *stream) {
-    const Call v{mode, coords, types, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), in_kind};
+    const Call v = views_call(mode, coords, types, radii, radius_scalar, radii_type, N, xforms, B, C, stream, in_kind);
     const char *own = !offsets_out_host ? "offsets_out_host must not be null"
                       : (index_capacity < 0 || (index_capacity > 0 && !index_out)) ? "index_out must not be null" : nullptr;
     if (int rc = validate_views(h, v, own)) return rc;
@@ -1313,77 +1339,45 @@ int mvx_select_views(mvx_handle *h, const double *coords, const int32_t *types, 
 int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                       double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                       void *out, int32_t in_kind, int32_t out_kind, void *stream) {
-    const Call v{mode, coords, channels, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), in_kind};
+    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream, in_kind);
     const char *own = (out_kind != MVX_HOST && out_kind != MVX_DEVICE) ? "bad memory kind"
                       : (B > 0 && !out) ? "out must not be null"
                       : (B > 0 && N > 0 && mode != MODE_SINGLE && !channels) ? "channels must not be null" : nullptr;
     if (int rc = validate_views(h, v, own)) return rc;
     if (B == 0) return MVX_OK;
-    std::vector<int64_t> offsets((size_t)B + 1, 0);
-    RunArgs r{v, out, out_kind}; // the views as a batch of B molecules
-    r.offsets = offsets.data();
-    if (N == 0) return run(h, r); // B molecules without atoms: zero grids
-    ViewInputs in(v);
-    {
-        CallScope scope(h, v.stream);
-        int rc = scope.rc;
-        if (rc) return rc;
-        if ((rc = stage_views(h, v, false, in))) return rc;
-        if ((rc = select_views(h, v, in, nullptr, 0, true, offsets.data()))) return rc;
-        const int64_t total = offsets[B];
-        if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
-        Call cloud = v; // ... as device arrays
-        cloud.coords = in.coords;
-        cloud.channels = in.channels;
-        cloud.radii = in.radii;
-        if ((rc = gather_views(h, cloud, static_cast<const int64_t *>(h->view_index.p), total, r))) return rc;
-    }
-    r.xforms = in.xforms_host.data();
-    r.in_kind = MVX_DEVICE;
-    // (the gathered rows are produced on the caller's stream just now: the pre-pass must not run ahead of them on the side
-    // stream, so cross-call overlap does not apply to this entry)
-    const bool overlap = h->overlap;
-    h->overlap = false;
-    const int rc = run(h, r);
-    h->overlap = overlap;
-    return rc;
+    ViewBatch batch(v); // (N == 0: B molecules without atoms, zero grids)
+    if (N > 0)
+        if (int rc = compact_views(h, v, true, nullptr, nullptr, batch)) return rc;
+    return run(h, {batch, out, out_kind, N > 0}); // (a compact batch does not overlap its pre-pass: RunArgs::no_overlap)
 }
 
-// The summed grid of B views: mvx_forward_views' selection and gather, then run_sum on the compact batch in place of run(). What
-// reads the handle (sum_config) is checked before a device is touched; run_sum checks the batch again, to no effect.
+// The summed grid of B views: mvx_forward_views' selection and gather, then run_summed on the compact batch in place of run(). What
+// reads the handle (sum_config) is checked before a device is touched; run_summed checks the batch again, to no effect.
 int mvx_forward_views_sum(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                           double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                           const float *view_weights, float *out, int32_t accumulate, void *stream) {
-    const Call v{mode, coords, channels, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), MVX_DEVICE};
+    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream);
     const char *own = (accumulate != 0 && accumulate != 1) ? "accumulate must be 0 or 1"
                       : (B > 0 && !out) ? "out must not be null"
                       : (B > 0 && N > 0 && mode != MODE_SINGLE && !channels) ? "channels must not be null" : nullptr;
     if (int rc = validate_views(h, v, own)) return rc;
     if (B == 0) return MVX_OK;
-    if (int rc = sum_config(h, mode, radii_type, C, out)) return rc;
-    std::vector<int64_t> offsets((size_t)B + 1, 0);
-    RunArgs r{v, out, MVX_DEVICE}; // the views as a batch of B molecules
-    r.offsets = offsets.data();
-    if (N == 0) return run_sum(h, r, accumulate, nullptr); // B views without atoms: zeros, or nothing
-    ViewInputs in(v);
-    const float *atom_weights = nullptr;
-    {
-        CallScope scope(h, v.stream);
-        int rc = scope.rc;
+    if (int rc = sum_config(h, v, false, out)) return rc;
+    ViewBatch batch(v); // (N == 0: B views without atoms, zeros or nothing)
+    SumCall sc{nullptr, accumulate != 0};
+    if (N > 0) {
+        int rc = compact_views(h, v, true, nullptr, nullptr, batch);
         if (rc) return rc;
-        if ((rc = stage_views(h, v, false, in))) return rc;
-        if ((rc = select_views(h, v, in, nullptr, 0, true, offsets.data()))) return rc;
-        const int64_t total = offsets[B];
-        if (total >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
-        if ((rc = gather_views(h, v, static_cast<const int64_t *>(h->view_index.p), total, r))) return rc;
+        const int64_t total = batch.offsets[B];
         if (view_weights && total > 0) { // one weight per selected atom, from the offsets select_views left on the device
+            CallScope scope(h, v.stream);
+            if (scope.rc) return scope.rc;
             if ((rc = ensure(h->view_w, (size_t)total * sizeof(float)))) return rc;
             HIP_TRY(launch_view_weights(static_cast<float *>(h->view_w.p), view_weights, static_cast<const int64_t *>(h->view_off.p), B, total, v.stream));
-            atom_weights = static_cast<const float *>(h->view_w.p);
+            sc.atom_weights = static_cast<const float *>(h->view_w.p);
         }
     }
-    r.xforms = in.xforms_host.data();
-    return run_sum(h, r, accumulate, atom_weights); // (a summed call never overlaps its pre-pass: Forward::make_plan)
+    return run_summed(h, {batch, out, MVX_DEVICE}, sc, nullptr, nullptr); // (a summed call never overlaps its pre-pass: Forward::make_plan)
 }
 
 int mvx_set_sum_parts(mvx_handle *h, int32_t parts) {
@@ -1418,10 +1412,9 @@ namespace {
 
 // ---- what is checked before any device is touched, up to the first rule that needs the atom count ----
 int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent &e) {
-    if (c.mode < MODE_FEATURES || c.mode > MODE_SINGLE) return fail(MVX_ERR_INVALID, "bad mode (0 features, 1 types, 2 single)");
+    if (const char *bad = bad_mode(c.mode)) return fail(MVX_ERR_INVALID, bad);
     if (o.grad_features && c.mode != MODE_FEATURES) return fail(MVX_ERR_INVALID, "grad_features exists in features mode only");
-    if (c.C <= 0) return fail(MVX_ERR_INVALID, "C must be > 0");
-    if (c.mode == MODE_SINGLE && c.C != 1) return fail(MVX_ERR_INVALID, "single mode has one channel (C = 1)");
+    if (const char *bad = bad_channel_count(c)) return fail(MVX_ERR_INVALID, bad);
     if (o.kind == BWD_RADII) { // (grad_coords and grad_features may both be null: grad_radii is an output)
         if (!o.grad_radii) return fail(MVX_ERR_INVALID, "grad_radii must not be null");
         if (c.radii_type == MVX_RADII_SCALAR)
@@ -1443,21 +1436,12 @@ int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent 
     } else if (!o.grad_coords && !o.grad_features) {
         return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
     }
-    if (c.B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
-    if (c.radii_type < MVX_RADII_SCALAR || c.radii_type > MVX_RADII_CHANNEL) return fail(MVX_ERR_INVALID, "bad radii_type");
-    if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE) return fail(MVX_ERR_INVALID, "Channel-Wise Radii Type is not supported");
-    if (c.B > 0 && !c.offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
-    if (const char *bad = check_offsets(c.offsets, c.B, e)) return fail(MVX_ERR_INVALID, bad);
-    if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    return check_pose_records(c.xforms, c.B); // (the first rule that reads the records)
+    return reject(check_batch(h, c, nullptr, e));
 }
 
-// ---- ... and what a call with atoms must bring ----
-int check_backward_arrays(const mvx_handle *h, const Call &c, const GradOut &o) {
+// ---- ... and, behind check_atoms, what a call with atoms must bring that reads the handle ----
+int check_backward_grid(const mvx_handle *h, const Call &c, const GradOut &o) {
     const bool score = o.kind == BWD_SCORE;
-    if (!c.coords || !o.grad_out) return fail(MVX_ERR_INVALID, score ? "coords / field must not be null" : "coords / grad_out must not be null");
-    if (c.mode != MODE_SINGLE && !c.channels) return fail(MVX_ERR_INVALID, "channels must not be null");
-    if (!c.radii && c.radii_type != MVX_RADII_SCALAR) return fail(MVX_ERR_INVALID, "radii array required");
     const size_t gsz = h->cfg.grid_type == MVX_GRID_BF16 ? 2 : (h->cfg.precision == 64 ? 8 : 4);
     const size_t D = (size_t)h->g.D;
     if (D * D * D * gsz >= ((size_t)1 << 32)) return fail(MVX_ERR_INVALID, "one channel of the grid must stay below 4 GiB");
@@ -1631,8 +1615,8 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
     if (rc) return rc;
     const bool radii_by_channel = o.grad_radii && c.radii_type == MVX_RADII_CHANNEL;
     if (e.total == 0 && !radii_by_channel && o.kind != BWD_DENSITY && !(o.kind == BWD_SCORE && c.B > 0)) return MVX_OK;
-    if (e.too_many()) return fail(MVX_ERR_INVALID, "too many atoms");
-    if (e.total > 0 && (rc = check_backward_arrays(h, c, o))) return rc;
+    if ((rc = reject(check_atoms(c, e, o.grad_out, o.kind == BWD_SCORE ? "coords / field must not be null" : "coords / grad_out must not be null")))) return rc;
+    if (e.total > 0 && (rc = check_backward_grid(h, c, o))) return rc;
     CallScope scope(h, c.stream);
     if (scope.rc) return scope.rc;
     if (e.total == 0) return backward_no_atoms(c, o);
@@ -1651,7 +1635,7 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
 const char *bad_view_offsets(const int64_t *offsets, int32_t B, Extent &e) {
     if (!offsets) return "offsets_host must not be null with an index";
     if (const char *bad = check_offsets(offsets, B, e)) return bad;
-    return e.too_many() ? "too many atoms: offsets[B] must stay below 2^31" : nullptr;
+    return too_many_atoms(e.total) ? "too many atoms: offsets[B] must stay below 2^31" : nullptr;
 }
 
 } // namespace
@@ -1659,8 +1643,7 @@ const char *bad_view_offsets(const int64_t *offsets, int32_t B, Extent &e) {
 int mvx_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii,
                        double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                        int32_t C, const void *grad_out, double *grad_coords, void *grad_features, void *stream) {
-    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+    return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream),
                          {BWD_PLAIN, grad_out, grad_coords, grad_features, nullptr, nullptr, nullptr, {}});
 }
 
@@ -1668,8 +1651,7 @@ int mvx_backward_radii_batch(mvx_handle *h, int32_t mode, const double *coords, 
                              double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                              int32_t C, const void *grad_out, double *grad_coords, void *grad_features, double *grad_radii,
                              void *stream) {
-    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+    return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream),
                          {BWD_RADII, grad_out, grad_coords, grad_features, grad_radii, nullptr, nullptr, {}});
 }
 
@@ -1677,8 +1659,7 @@ int mvx_backward_density_batch(mvx_handle *h, int32_t mode, const double *coords
                                double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
                                int32_t C, const void *grad_out, double *grad_coords, void *grad_features, double *grad_radii,
                                double *grad_sigma, double *grad_radius_scalar, void *stream) {
-    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+    return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream),
                          {BWD_DENSITY, grad_out, grad_coords, grad_features, grad_radii, grad_sigma, grad_radius_scalar, {}});
 }
 
@@ -1686,8 +1667,7 @@ int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const voi
                     double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B, int32_t C,
                     const void *field, int64_t field_mol_stride, double *scores, double *atom_scores, double *grad_coords,
                     void *grad_features, void *stream) {
-    return backward_impl(h, {mode, coords, channels, radii, radius_scalar, radii_type, offsets, 0, xforms, B, C,
-                             reinterpret_cast<hipStream_t>(stream), MVX_DEVICE},
+    return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream),
                          {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_mol_stride, scores, atom_scores}});
 }
 
@@ -1697,22 +1677,16 @@ int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_
     if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
     if (B > 0 && !grad_pose) return fail(MVX_ERR_INVALID, "grad_pose must not be null");
     if (B > 0 && !xforms) return fail(MVX_ERR_INVALID, "xforms must not be null");
-    if (B > 0 && !offsets) return fail(MVX_ERR_INVALID, "offsets must not be null");
     Extent e;
     if (const char *bad = check_offsets(offsets, B, e)) return fail(MVX_ERR_INVALID, bad);
     if (e.total > 0 && (!coords || !grad_coords)) return fail(MVX_ERR_INVALID, "coords / grad_coords must not be null");
     for (int b = 0; b < B; ++b)
         if (!(xforms[b].flags & MVX_XF_POSE_PTR)) return fail(MVX_ERR_INVALID, "every record must be a MVX_XF_POSE_PTR record");
-    if (int prc = check_pose_records(xforms, B)) return prc;
+    if (const char *bad = check_pose_records(xforms, B)) return fail(MVX_ERR_INVALID, bad);
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
     if (B == 0) return MVX_OK;
 
-    Call c{}; // (what stage_meta reads)
-    c.offsets = offsets;
-    c.xforms = xforms;
-    c.B = B;
-    c.stream = reinterpret_cast<hipStream_t>(stream);
-    c.in_kind = MVX_DEVICE;
+    const Call c = batch_call(0, nullptr, nullptr, nullptr, 0.0, 0, offsets, xforms, B, 0, stream); // (what stage_meta reads)
     CallScope scope(h, c.stream);
     if (scope.rc) return scope.rc;
     // offsets and records through a pinned slot, as the backward entries stage them (the records stay as they are: the
@@ -1727,7 +1701,7 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
                     double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                     const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
                     double *scores, double *atom_scores, double *grad_coords, void *grad_features, void *stream) {
-    const Call v{mode, coords, channels, radii, radius_scalar, radii_type, nullptr, N, xforms, B, C, reinterpret_cast<hipStream_t>(stream), MVX_DEVICE};
+    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream);
     // ---- what is checked before any device is touched ----
     const bool per_row = atom_scores || grad_coords || grad_features;
     Extent e; // of the caller's selection
@@ -1747,28 +1721,9 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
         return fail(MVX_ERR_INVALID, "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)");
     if (B == 0) return MVX_OK;
     // the compact batch through the walk of mvx_score_batch: the records as the caller gave them (device centres and poses)
-    Call batch = v;
-    batch.coords = nullptr;
-    batch.channels = batch.radii = nullptr;
-    batch.offsets = offsets_host;
-    std::vector<int64_t> own_offsets;
-    if (N == 0 || !index) { // (N == 0: B views without atoms score 0, whatever the caller's selection says)
-        own_offsets.assign((size_t)B + 1, 0);
-        batch.offsets = own_offsets.data();
-    }
-    if (N > 0) {
-        CallScope scope(h, v.stream);
-        int rc = scope.rc;
-        if (rc) return rc;
-        if (!index) { // the selection itself: one stream synchronisation
-            ViewInputs in(v);
-            if ((rc = stage_views(h, v, true, in))) return rc;
-            if ((rc = select_views(h, v, in, nullptr, 0, true, own_offsets.data()))) return rc;
-            if (own_offsets[B] >= (int64_t)1 << 31) return fail(MVX_ERR_INVALID, "too many atoms");
-            index = static_cast<const int64_t *>(h->view_index.p);
-        }
-        if ((rc = gather_views(h, v, index, batch.offsets[B], batch))) return rc;
-    }
+    ViewBatch batch(v); // (N == 0: B views without atoms score 0, whatever the caller's selection says)
+    if (N > 0) // (no index: the selection itself, one stream synchronisation)
+        if (int rc = compact_views(h, v, false, index, offsets_host, batch)) return rc;
     return backward_impl(h, batch, {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_view_stride, scores, atom_scores}});
 }
 
@@ -1787,11 +1742,7 @@ int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
     if (N == 0) return MVX_OK;
 
-    Call c{}; // (what stage_meta reads)
-    c.offsets = offsets_host;
-    c.B = B;
-    c.stream = reinterpret_cast<hipStream_t>(stream);
-    c.in_kind = MVX_DEVICE;
+    const Call c = batch_call(0, nullptr, nullptr, nullptr, 0.0, 0, offsets_host, nullptr, B, 0, stream); // (what stage_meta reads)
     CallScope scope(h, c.stream);
     if (scope.rc) return scope.rc;
     const bool f64 = row_type == MVX_ROW_DOUBLE;
@@ -1809,14 +1760,10 @@ int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,
                          int32_t in_kind, int32_t out_kind, void *stream) {
     if (!h || !xform || (N > 0 && (!coords || !out))) return fail(MVX_ERR_INVALID, "null argument");
-    if (int prc = check_pose_records(xform, 1)) return prc;
+    if (const char *bad = check_pose_records(xform, 1)) return fail(MVX_ERR_INVALID, bad);
     if (N <= 0) return MVX_OK;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    Call c{}; // (what stage_meta reads: one record, no offsets)
-    c.xforms = xform;
-    c.B = 1;
-    c.stream = s;
-    c.in_kind = in_kind;
+    const Call c = batch_call(0, nullptr, nullptr, nullptr, 0.0, 0, nullptr, xform, 1, 0, stream, in_kind); // (what stage_meta reads: one record, no offsets)
+    hipStream_t s = c.stream;
     CallScope scope(h, s);
     if (scope.rc) return scope.rc;
     const size_t co_bytes = (size_t)N * 3 * sizeof(double);

@@ -7,9 +7,12 @@ with backward, scores of a batch, the reduction of views, a transform, then the 
 and host arrays through the same ring of pinned slots and keep device copies of them in buffers of their own; a call that
 wrote another entry's buffer (the forward's cached offsets above all), or reused a slot a copy still reads, would change some
 later result. Every result and gradient must equal, bit for bit, the same call made on a fresh voxelizer of its own.
+On the float32 handle the entries on the summed walk run in between: forward_sum (plain; accumulating with atom weights; in two
+parts under set_sum_parts(2)), forward_views_sum with view weights and moments_batch with a target - they take the forward's
+workspace, its cached offsets and the views' buffers, and own the partial grids and the moments' partials.
 
-D = 16 at 0.5 A, three molecules of 40 / 0 / 25 atoms with C = 4 features, five views of the 150-atom cloud of
-tests/test_hip_score_views.py."""
+D = 16 at 0.5 A, three molecules of 40 / 0 / 25 atoms with C = 4 features (C = 5 on the summed walk: one chunk of 32 channels,
+zero padded), five views of the 150-atom cloud of tests/test_hip_score_views.py."""
 import ctypes as C
 
 import numpy as np
@@ -20,6 +23,7 @@ from tests.test_hip_score_views import _data
 pytestmark = pytest.mark.gpu
 
 D, RES, C_ = 16, 0.5, 4
+C_SUM = 5
 SIZES = (40, 0, 25)
 
 
@@ -40,8 +44,13 @@ def _inputs(kind):
     q = rng.standard_normal((B, 4))
     q /= np.linalg.norm(q, axis=1)[:, None]
     cloud = _data(5, 150, 5, C_, "features", "scalar", kind)
-    return dict(offsets=offsets, xyz=xyz, cen=cen, feat=rng.standard_normal((N, C_)).astype(fp), q=q, t=rng.uniform(-0.3, 0.3, (B, 3)),
-                field=rng.standard_normal((C_, D, D, D)).astype(fp), cloud=cloud, rows=rng.standard_normal((150, 3)))
+    a = dict(offsets=offsets, xyz=xyz, cen=cen, feat=rng.standard_normal((N, C_)).astype(fp), q=q, t=rng.uniform(-0.3, 0.3, (B, 3)),
+             field=rng.standard_normal((C_, D, D, D)).astype(fp), cloud=cloud, rows=rng.standard_normal((150, 3)), kind=kind)
+    # the summed and moments entries (float32 only): C_SUM channels are one chunk of 32, zero padded
+    a.update(feat5=rng.standard_normal((N, C_SUM)).astype(np.float32), cloud5=rng.standard_normal((150, C_SUM)).astype(np.float32),
+             w_atoms=rng.uniform(0.5, 1.5, N).astype(np.float32), w_views=rng.uniform(0.5, 1.5, 5).astype(np.float32),
+             grid5=rng.standard_normal((C_SUM, D, D, D)).astype(np.float32))
+    return a
 
 
 def _steps(a):
@@ -105,18 +114,50 @@ def _steps(a):
                                                     _lib.MVX_DEVICE, _lib.MVX_DEVICE, torch.cuda.current_stream().cuda_stream))
         return (out,)
 
-    return [("forward_batch from numpy, centres", from_host), ("forward_batch from device tensors, centres", from_device),
-            ("device tensors, centres, again", from_device),
-            ("no records, device tensors (offsets uploaded)", plain_device),
-            ("no records, device tensors again (skipped upload)", plain_device),
-            ("no records, numpy (skipped upload, a slot for the arrays alone)", plain_host), ("no records, numpy again", plain_host),
-            ("forward_posed_batch + backward", posed), ("forward_views", views),
-            ("score_views per_atom + backward", score_views), ("score_batch", score_batch), ("views_reduce", reduce),
-            ("transform on the handle", transform),
-            ("no records, device tensors, after the other entries (offsets uploaded)", plain_device),
-            ("no records, device tensors, after the other entries, again (skipped upload)", plain_device),
-            ("no records, numpy, after the other entries (skipped upload)", plain_host),
-            ("forward_batch from numpy, centres, again", from_host)]
+    steps = [("forward_batch from numpy, centres", from_host), ("forward_batch from device tensors, centres", from_device),
+             ("device tensors, centres, again", from_device),
+             ("no records, device tensors (offsets uploaded)", plain_device),
+             ("no records, device tensors again (skipped upload)", plain_device),
+             ("no records, numpy (skipped upload, a slot for the arrays alone)", plain_host), ("no records, numpy again", plain_host),
+             ("forward_posed_batch + backward", posed), ("forward_views", views),
+             ("score_views per_atom + backward", score_views), ("score_batch", score_batch), ("views_reduce", reduce),
+             ("transform on the handle", transform),
+             ("no records, device tensors, after the other entries (offsets uploaded)", plain_device),
+             ("no records, device tensors, after the other entries, again (skipped upload)", plain_device),
+             ("no records, numpy, after the other entries (skipped upload)", plain_host),
+             ("forward_batch from numpy, centres, again", from_host)]
+    if a["kind"] == "f64":  # (the summed and moments entries serve float32 handles only)
+        return steps
+
+    # ---- the entries on the summed walk, in between the steps above: they use the forward's workspace, offsets cache and slots ----
+    feat5, cloud5, grid5 = dev(a["feat5"]), dev(a["cloud5"]), dev(a["grid5"])
+    w_atoms, w_views = dev(a["w_atoms"]), dev(a["w_views"])
+
+    def fsum(v):
+        return (v.forward_sum(xyz, off, cen, feat5, 1.25),)
+
+    def fsum_accumulate(v):
+        return (v.forward_sum(xyz, off, cen, feat5, 1.25, weights=w_atoms, out_grid=grid5.clone(), accumulate=True),)
+
+    def fsum_parts(v):
+        v.set_sum_parts(2)
+        out = v.forward_sum(xyz, off, cen, feat5, 1.25)
+        v.set_sum_parts(1)
+        return (out,)
+
+    def views_sum(v):
+        return (v.forward_views_sum(dev(cl["xyz"]), dev(cl["cen"]), cloud5, 1.25, weights=w_views),)
+
+    def moments(v):
+        return (v.moments_batch(xyz, off, cen, feat5, 1.25, target=grid5),)
+
+    for after, name, step in [("device tensors, centres, again", "forward_sum", fsum),
+                              ("no records, numpy again", "forward_sum, accumulate with weights", fsum_accumulate),
+                              ("forward_views", "forward_views_sum with weights", views_sum),
+                              ("score_batch", "moments_batch with a target", moments),
+                              ("transform on the handle", "forward_sum in two parts", fsum_parts)]:  # (never inside a skipped-upload pair)
+        steps.insert([n for n, _ in steps].index(after) + 1, (name, step))
+    return steps
 
 
 def _host(x):
@@ -142,6 +183,11 @@ def test_one_handle_through_every_entry_gives_the_bits_of_fresh_handles(kind):
             assert np.array_equal(x, y, equal_nan=True), (name, i, float(np.abs(x.astype(np.float64) - y.astype(np.float64)).max()))
     by_name = {name: mine for (name, _), mine in zip(steps, got)}
     assert len(by_name) == len(steps)
+    summed = ("forward_sum", "forward_sum, accumulate with weights", "forward_views_sum with weights", "moments_batch with a target",
+              "forward_sum in two parts")
+    assert all((name in by_name) == (kind == "f32") for name in summed)
     for name in ("forward_batch from numpy, centres", "no records, device tensors again (skipped upload)",
-                 "no records, numpy, after the other entries (skipped upload)", "score_views per_atom + backward"):
-        assert np.abs(_host(by_name[name][0])).max() > 0, name  # (the grids and the scores are not all zero)
+                 "no records, numpy, after the other entries (skipped upload)", "score_views per_atom + backward") + summed * (kind == "f32"):
+        assert np.abs(_host(by_name[name][0])).max() > 0, name  # (the grids, the scores and the moments are not all zero)
+    if kind == "f32":  # the accumulated sum started from its grid, and the two parts are a sum of their own
+        assert not np.array_equal(_host(by_name["forward_sum, accumulate with weights"][0]), _host(by_name["forward_sum"][0]))

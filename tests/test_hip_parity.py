@@ -983,6 +983,52 @@ def test_overlapped_prepass_equals_serial_calls(mv):
         assert torch.equal(fast.forward_batch(dev[1][0], dev[1][2], None, dev[1][1], dev[1][3], num_channels=dev[1][4]), want[1])
 
 
+def test_views_between_overlapped_batches_leave_the_overlap_as_it_was(mv):
+    """forward_views on a handle with mvx_set_overlap: its compact batch must not overlap its pre-pass (the gathered rows are made
+    on the caller's stream a moment before), and that is a property of the one call - the forward_batch calls around it overlap
+    as before, on alternating workspace sets. forward_batch and forward_views alternate on device tensors with no host
+    synchronisation by the caller in between; every result must equal the serial handle's.
+
+    D = 16 at 0.5 A, C = 8 features; two batches of 4 molecules of 40 ... 120 atoms (B > 1, one chunk, the one-launch route
+    switched off: the smallest batch on the overlapped binned route); 4 views of a 300-atom cloud, one of them empty."""
+    import torch
+
+    rng = np.random.default_rng(7)
+    D, C_ = 16, 8
+    half = 0.5 * (D - 1) / 2
+    serial = mv.create_voxelizer(0.5, D, "scalar", "gaussian", "hip", sigma=0.6)
+    fast = mv.create_voxelizer(0.5, D, "scalar", "gaussian", "hip", sigma=0.6, overlap_prepass=True)
+    for v in (serial, fast):
+        v.debug_option("direct", 0)
+    batches = []
+    for sizes in ([40, 120, 75, 90], [110, 45, 60, 100]):
+        n = sum(sizes)
+        batches.append((serial.asarray(rng.uniform(-half - 1, half + 1, (n, 3)), "coords"),
+                        serial.asarray(rng.random((n, C_)).astype(np.float32), "features"), np.cumsum([0] + sizes)))
+    cloud = rng.uniform(-10.0, 10.0, (300, 3))
+    centers = cloud[rng.integers(0, 300, 4)] + rng.normal(0.0, 0.5, (4, 3))
+    centers[2] = 60.0  # (a view of empty space)
+    cloud, centers = serial.asarray(cloud, "coords"), torch.tensor(centers, device="cuda")
+    cloud_feat = serial.asarray(rng.random((300, C_)).astype(np.float32), "features")
+    torch.cuda.synchronize()  # the inputs are complete before the loop starts: the overlap contract
+
+    def run(v, job):
+        if job == "views":
+            return v.forward_views(cloud, centers, cloud_feat, 1.2).clone()
+        coords, feat, off = batches[job]
+        return v.forward_batch(coords, off, None, feat, 1.2).clone()
+
+    order = [0, "views", 1, "views", 0, 0, "views", "views", 1, 0]
+    want = [run(serial, job) for job in order]
+    got = [run(fast, job) for job in order]
+    torch.cuda.synchronize()
+    assert fast.last_plan() == serial.last_plan()
+    for k, (a, b) in enumerate(zip(want, got)):
+        assert a.shape == ((4, C_, D, D, D)) and torch.equal(a, b), (k, order[k])
+    views = want[1]
+    assert not views[2].any() and all(views[i].any() for i in (0, 1, 3)) and all(w.any() for w in want)
+
+
 @pytest.mark.parametrize("C_,distinct,D,blockdim", [(32, 4, 32, None), (40, 2, 32, None), (12, 9, 24, None), (32, 1, 32, None),
                                                     (7, 3, 27, 5), (64, 8, 16, None), (33, 33, 16, None), (32, 32, 24, None),
                                                     (70, 31, 16, None), (40, 40, 16, None), (96, 96, 16, None), (45, 45, 20, 5)])

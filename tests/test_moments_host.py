@@ -178,6 +178,13 @@ def test_moments_batch_reports_the_earlier_of_two_mistakes():
         (dict(h=P, coords=None, channels=None), M_COORDS),
         (dict(h=P, channels=None, rt=1), M_CHANNELS),
         (dict(h=P, rt=1), M_RADII),
+        # across the seams between the entry's own rule (moments, behind B) and the chains it shares with the other entries
+        (dict(C_=0, moments=None), M_C),
+        (dict(mode=2, C_=3, moments=None), M_SINGLE),
+        (dict(B=-1, moments=None, rt=7), M_B),
+        (dict(moments=None, mode=2, C_=1, rt=2, radii=P), M_OUT),
+        (dict(moments=None, offsets=None), M_OUT),
+        (dict(moments=None, offsets=(1, 3)), M_OUT),
     ]
     for kw, want in rows:
         rc, msg = _moments(**kw)

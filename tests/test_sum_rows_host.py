@@ -287,6 +287,13 @@ def test_forward_sum_batch_reports_the_earlier_of_two_mistakes():
         (dict(h=P, coords=None, channels=None), M_COORDS),
         (dict(h=P, channels=None, rt=1), M_CHANNELS),
         (dict(h=P, rt=1), M_RADII),
+        # across the seams between the entry's own rules (out, accumulate) and the chains it shares with the other entries
+        (dict(mode=2, C_=3, accumulate=2), M_SINGLE),
+        (dict(out=None, B=-1), M_OUT),
+        (dict(out=None, rt=7), M_OUT),
+        (dict(accumulate=2, rt=7), M_ACC),
+        (dict(accumulate=2, offsets=None), M_ACC),
+        (dict(B=-1, offsets=None), M_B),
     ]
     for kw, want in rows:
         rc, msg = _sum(**kw)
