@@ -479,6 +479,41 @@ int mvx_moments_batch(mvx_handle *h, int32_t mode, const double *coords, const v
                       double *moments /* (B, C, K) device, K = target ? 3 : 2 */, void *stream);
 
 /*
+ * Gradients through mvx_moments_batch (no counterpart in the reference): dL/dcoords and dL/dfeatures of a loss that reads the
+ * grids through their moments only, without B grids of g and without any grid of dL/dgrid. With G0, G1, G2 =
+ * grad_moments[b, c, 0..2] = dL/dm[b, c, 0..2] the upstream of the backward walk is
+ *   dL/dgrid[b, c, v] = G0 + 2 G1 g[b, c, v] + G2 target[c, v]
+ * and the walk forms it per voxel, in float32, from the three coefficients of its (molecule, channel):
+ *   a0 = (float)G0, a1 = (float)(2.0 * G1), a2 = (float)G2
+ *   u  = fmaf(a1, g, fmaf(a2, target[c, v], a0))          without a target: u = fmaf(a1, g, a0)
+ * g is the float32 value mvx_forward_*_batch stores for the same arguments (whatever the handle's grid_type and layout: the
+ * grids are written as float32 NCDHW into handle-owned scratch). Everything behind the upstream is mvx_backward_batch's walk:
+ * grad_coords and grad_features are, bit for bit, what mvx_backward_batch gives for grad_out = u on a float32 NCDHW handle.
+ * So grad_moments = (0, 0, 1) everywhere gives mvx_score_batch's gradients for field = target, (0, 0.5, 0) those of
+ * mvx_backward_batch for grad_out = the grids themselves, (1, 0) without a target those for grad_out = 1.
+ *   target:        (C, D, D, D) float32 NCDHW on the device, 16-byte aligned, shared by all molecules, or NULL
+ *   grad_moments:  (B, C, K) doubles on the device, K = target ? 3 : 2
+ *   grad_coords:   (sumN, 3) doubles or NULL; grad_features: (sumN, C) floats or NULL (features mode only); not both NULL. Fully
+ *                  overwritten; binary density gives zero coordinate gradients; an atom of a type outside [0, C) gets zeros.
+ * The call runs molecule chunk by molecule chunk, cut as the forward cuts a batch (Infinity Cache budget, gridDim.y limit, the
+ * "chunks" and "mall_budget_kb" debug options) and then further, until the float32 grids of a chunk fit 1 GiB (one molecule
+ * per chunk at least; the "mgrad_scratch_kb" option); mvx_debug_last_plan reports the cut. Per chunk the forward into the
+ * scratch, then the backward's pre-pass and the walk over the chunk's atoms ("grad_order" applies per chunk). Deterministic,
+ * no atomics; a molecule's rows do not depend on its batch or on the cut.
+ * Workspace, handle-owned: the float32 grids of the largest chunk (nb * C * D^3 floats: at most 1 GiB, or one molecule's),
+ * (B, C, 3) floats of coefficients, and the buffers of the forward and backward entries.
+ * Device pointers except offsets / xforms (host), as in mvx_moments_batch. Asynchronous on `stream`.
+ * MVX_ERR_INVALID before any device is touched: the rules of mvx_moments_batch in its order, up to and including the four
+ * configurations named "moments:" and the target's alignment; then NULL grad_moments with B > 0; grad_features outside
+ * features mode; grad_coords and grad_features both NULL. B == 0: MVX_OK; a call without atoms launches nothing.
+ */
+int mvx_moments_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                               double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                               int32_t B, int32_t C, const float *target /* (C, D, D, D) device, or NULL */,
+                               const double *grad_moments /* (B, C, K) device, K = target ? 3 : 2 */,
+                               double *grad_coords, mvx_real *grad_features, void *stream);
+
+/*
  * Gradients with respect to explicit rigid poses (MVX_XF_POSE_PTR records; no counterpart in the reference): the reduction of
  * the per-atom gradients a backward entry wrote for the same call (grad_coords = M^T dL/dp) to dL/dc, dL/dq and dL/dt of every
  * molecule, on the device. Per molecule with pose (c, q, t), M = M(q) the linear part of the sandwich product (it scales by
@@ -587,6 +622,8 @@ int mvx_debug_read_records(mvx_handle *h, void *host_dst, int64_t n, void *strea
  *   "nw" = 1..16: waves (8-voxel z sub-tiles) per slab instead of the plan's (0 = the plan); measurement aid;
  *   "grad_order" = 0 / 1: mvx_backward_batch runs the atoms in the caller's order (0, the default) or in spatial order,
  *              each XCD one contiguous range of it (1); results are the same bits either way. Measurement aid;
+ *   "mgrad_scratch_kb" = k: mvx_moments_backward_batch cuts its call until the float32 grids of a molecule chunk fit k KiB
+ *              (production: 1 GiB; 0 restores it), so that small test batches exercise that cut;
  *   "dense_grid": accepted and ignored (round 2's second voxelize launch no longer exists). */
 int mvx_debug_set_option(mvx_handle *h, const char *name, int32_t value);
 

@@ -139,6 +139,9 @@ struct mvx_handle : NoCopy {
     int sum_parts = 1;
     DevBuf sum_part_grids;
     DevBuf moments_part; // mvx_moments_batch: the slab partials of one molecule chunk
+    // mvx_moments_backward_batch: the float32 NCDHW grids of the largest molecule chunk, and the call's (B, C, 3) coefficients
+    DevBuf mgrad_grids, mgrad_coef;
+    double mgrad_scratch = MOMENTS_GRAD_SCRATCH; // "mgrad_scratch_kb" option: bytes of grids a chunk of that call may hold
     int32_t layout = MVX_LAYOUT_NCDHW; // mvx_set_grid_layout
     mvx_plan last_plan{}; // the plan of the last forward call, debug options applied (mvx_debug_last_plan)
     bool has_plan = false;
@@ -266,6 +269,8 @@ struct RunArgs : Call {
     // the arrays were produced on the caller's stream a moment ago (the gathered rows of mvx_forward_views): the pre-pass must
     // not run ahead of them on the side stream, so cross-call overlap (mvx_set_overlap) does not apply to this call
     bool no_overlap = false;
+    // `out` takes float32 NCDHW grids whatever the handle's grid type and layout (the chunk scratch of mvx_moments_backward_batch)
+    bool f32_plain = false;
 };
 
 // mvx_forward_sum_batch: what a forward call that sums its molecules into ONE (C, D, D, D) float32 grid brings next to its RunArgs
@@ -588,7 +593,7 @@ struct Forward {
     const RunArgs &r;
     const Extent ext;
     const SumCall *const sum; // not null: one summed float32 NCDHW grid (mvx_forward_sum_batch) instead of B grids
-    const bool f64 = h->cfg.precision == 64, bf16 = !sum && h->cfg.grid_type == MVX_GRID_BF16, gauss = h->cfg.density == MVX_GAUSSIAN;
+    const bool f64 = h->cfg.precision == 64, bf16 = !sum && !r.f32_plain && h->cfg.grid_type == MVX_GRID_BF16, gauss = h->cfg.density == MVX_GAUSSIAN;
     const bool chanwise = r.radii_type == MVX_RADII_CHANNEL && r.mode == MODE_FEATURES;
     const size_t esz = f64 ? sizeof(double) : sizeof(float); // element size of features, radii and the grid (but bfloat16 grids: 2)
     // make_plan:
@@ -636,7 +641,7 @@ struct Forward {
         q.C = r.C;
         // (a bfloat16 grid's vector store is 8 bytes: mvx_plan_call_grid)
         // channels-last grids (C > 1; one channel IS the contiguous layout): 16-byte channel runs for either element type
-        ndhwc = !sum && h->layout == MVX_LAYOUT_NDHWC && !f64 && r.C > 1;
+        ndhwc = !sum && !r.f32_plain && h->layout == MVX_LAYOUT_NDHWC && !f64 && r.C > 1;
         q.out_aligned16 = (reinterpret_cast<uintptr_t>(d_out) & ((bf16 && !ndhwc) ? 7u : 15u)) == 0 ? 1 : 0;
         q.total_atoms = ext.total;
         q.max_atoms = ext.max_atoms;
@@ -976,18 +981,25 @@ int sum_config(const mvx_handle *h, const Call &c, bool moments, const void *ali
     return MVX_OK;
 }
 
-// ---- mvx_forward_sum_batch (r.out: the grid) and mvx_moments_batch (sc.moments; r.out: the moments): the checks (the shared ones in the
-// backward entries' order; before_B / after_B: what the entry found wrong with its own arguments, on either side of "B must be
-// >= 0"; then what the kernel does not serve), the calls without atoms, then the forward's steps with the SumCall ----
+// The checks of a summed or moments call: the shared ones in the backward entries' order (before_B / after_B: what the entry found
+// wrong with its own arguments, on either side of "B must be >= 0"), then what the kernel does not serve. mvx_moments_backward_batch
+// applies mvx_moments_batch's through here too.
+int check_summed(const mvx_handle *h, const Call &c, bool moments, const void *aligned, const char *before_B, const char *after_B,
+                 Extent &e) {
+    const char *bad = bad_mode(c.mode);
+    if (!bad) bad = bad_channel_count(c);
+    if (!bad) bad = before_B;
+    if (!bad) bad = check_batch(h, c, after_B, e);
+    if (!bad) bad = check_atoms(c, e, c.coords, "coords must not be null");
+    if (bad) return fail(MVX_ERR_INVALID, bad);
+    return sum_config(h, c, moments, aligned);
+}
+
+// ---- mvx_forward_sum_batch (r.out: the grid) and mvx_moments_batch (sc.moments; r.out: the moments): the checks, the calls
+// without atoms, then the forward's steps with the SumCall ----
 int run_summed(mvx_handle *h, const RunArgs &r, const SumCall &sc, const char *before_B, const char *after_B) {
     Extent e;
-    const char *bad = bad_mode(r.mode);
-    if (!bad) bad = bad_channel_count(r);
-    if (!bad) bad = before_B;
-    if (!bad) bad = check_batch(h, r, after_B, e);
-    if (!bad) bad = check_atoms(r, e, r.coords, "coords must not be null");
-    if (bad) return fail(MVX_ERR_INVALID, bad);
-    if (int rc = sum_config(h, r, sc.moments, sc.moments ? static_cast<const void *>(sc.target) : r.out)) return rc;
+    if (int rc = check_summed(h, r, sc.moments, sc.moments ? static_cast<const void *>(sc.target) : r.out, before_B, after_B, e)) return rc;
     if (e.total == 0) { // no atoms: every moment is zero (no molecules: there are none); a grid of zeros, or - accumulating - as it was
         const size_t bytes = sc.moments ? (size_t)r.B * r.C * (sc.target ? 3 : 2) * sizeof(double)
                                         : (sc.accumulate ? 0 : (size_t)r.C * h->g.D * h->g.D * h->g.D * sizeof(float));
@@ -1389,8 +1401,10 @@ int mvx_set_sum_parts(mvx_handle *h, int32_t parts) {
 
 // mvx_backward_batch (BWD_PLAIN), mvx_backward_radii_batch (BWD_RADII: grad_radii as well) and mvx_backward_density_batch
 // (BWD_DENSITY: grad_sigma / grad_rscalar / grad_radii, each or NULL); mvx_score_batch (BWD_SCORE: `grad_out` is the constant
-// field, ScoreCall its stride and the score outputs; grad_coords and grad_features each or NULL)
-enum BackwardKind { BWD_PLAIN, BWD_RADII, BWD_DENSITY, BWD_SCORE };
+// field, ScoreCall its stride and the score outputs; grad_coords and grad_features each or NULL); mvx_moments_backward_batch
+// (BWD_MOMENTS, one Backward per molecule chunk: `grad_out` is the chunk's float32 grids in handle-owned scratch, `moments` its
+// coefficients and the target)
+enum BackwardKind { BWD_PLAIN, BWD_RADII, BWD_DENSITY, BWD_SCORE, BWD_MOMENTS };
 
 struct ScoreCall {
     int64_t mol_stride;  // 0 (one field for all molecules) or C * D^3
@@ -1406,6 +1420,7 @@ struct GradOut {
     void *grad_features;
     double *grad_radii, *grad_sigma, *grad_rscalar;
     ScoreCall score; // BWD_SCORE only
+    MomentsArgs moments{}; // BWD_MOMENTS only
 };
 
 namespace {
@@ -1474,7 +1489,8 @@ struct Backward {
     const hipStream_t s = c.stream;
     const bool f64 = h->cfg.precision == 64;
     // which instantiation every walk of this call takes; key.chanwise: channel-wise radii for features, with their tables
-    const WalkKey key{h->cfg.grid_type == MVX_GRID_BF16 ? 1 : (f64 ? 2 : 0), c.mode, h->cfg.density == MVX_GAUSSIAN,
+    // (the scratch grids of the moments walk are float32 whatever the handle's grid type)
+    const WalkKey key{o.kind == BWD_MOMENTS ? 0 : (h->cfg.grid_type == MVX_GRID_BF16 ? 1 : (f64 ? 2 : 0)), c.mode, h->cfg.density == MVX_GAUSSIAN,
                       c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES};
     void *d_kc = nullptr; // channel-wise features: the per-channel coefficients (ga.kc)
     DeviceInputs in{c};   // the caller's arrays; stage(): the device copy of offsets and records, the slot they went through
@@ -1547,6 +1563,11 @@ struct Backward {
         }
         HIP_TRY(launch_score(ga, sa, key, s));
         HIP_TRY(launch_score_reduce(sa.atom_scores, in.offsets, c.B, o.score.scores, s));
+        return MVX_OK;
+    }
+    // BWD_MOMENTS: the walk over the chunk's grids with the upstream formed from them, the coefficients and the target
+    int moments() {
+        HIP_TRY(launch_moments_grad(ga, o.moments, key, s));
         return MVX_OK;
     }
     // binary density: zero radius and sigma gradients (the a.e. derivative), the walk for the other outputs only
@@ -1627,8 +1648,73 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
     case BWD_SCORE: rc = b.score(); break;
     case BWD_RADII: rc = b.radii(); break;
     case BWD_DENSITY: rc = b.density(); break;
+    case BWD_MOMENTS: rc = b.moments(); break; // (not reached: moments_backward runs its chunks itself)
     }
     return rc ? rc : release_slot(b.in.slot, c.stream);
+}
+
+// ---- mvx_moments_backward_batch behind its checks, with atoms: the molecule chunks the forward cuts, one after the other. Per chunk
+// the forward as a call of its own into the float32 NCDHW scratch (rebased offsets: a molecule's bits do not depend on its
+// batch), then the backward's pre-pass and the moments walk over the chunk's atoms. The scratch holds the largest chunk. ----
+int moments_backward(mvx_handle *h, const Call &c, const Extent &e, const float *target, const double *grad_moments,
+                     double *grad_coords, void *grad_features) {
+    CallScope scope(h, c.stream);
+    if (scope.rc) return scope.rc;
+    int rc;
+    // the cut: the plan of the forward call that would write all B float32 grids
+    RunArgs whole{c, nullptr, MVX_DEVICE};
+    whole.no_overlap = whole.f32_plain = true;
+    Forward cut(h, whole, e);
+    if ((rc = cut.make_plan())) return rc;
+    mvx_plan plan = cut.plan;
+    // ... and further, until the grids of a chunk fit the scratch bound (the forward's cut counts pre-pass bytes, not grids)
+    const size_t D3 = (size_t)h->g.D * h->g.D * h->g.D, K = target ? 3 : 2;
+    const double mol_bytes = (double)c.C * (double)D3 * sizeof(float);
+    const int64_t fit = std::max<int64_t>(1, (int64_t)(h->mgrad_scratch / mol_bytes));
+    plan.nchunk = (int32_t)std::max<int64_t>(plan.nchunk, (c.B + fit - 1) / fit);
+    const int nchunk = plan.nchunk;
+    auto chunk_begin = [&](int k) { return (int)((int64_t)c.B * k / nchunk); }; // (Forward::launch_binned's)
+    int nb_max = 0;
+    for (int k = 0; k < nchunk; ++k) nb_max = std::max(nb_max, chunk_begin(k + 1) - chunk_begin(k));
+    if ((rc = ensure(h->mgrad_grids, (size_t)nb_max * c.C * D3 * sizeof(float)))) return rc;
+    if ((rc = ensure(h->mgrad_coef, (size_t)c.B * c.C * 3 * sizeof(float)))) return rc;
+    float *coef = static_cast<float *>(h->mgrad_coef.p);
+    HIP_TRY(launch_moments_coef(grad_moments, (int64_t)c.B * c.C, (int32_t)K, coef, c.stream));
+    const bool profiling = h->profiling; // (the chunks' forward launches are no timed launches of the caller's)
+    h->profiling = false;
+    const size_t chan_elem = c.mode == MODE_FEATURES ? (size_t)c.C * sizeof(float) : (c.mode == MODE_TYPES ? sizeof(int32_t) : 0);
+    std::vector<int64_t> off;
+    for (int k = 0; k < nchunk && !rc; ++k) {
+        const int b0 = chunk_begin(k), nb = chunk_begin(k + 1) - b0;
+        const int64_t a0 = c.offsets[b0], n = c.offsets[b0 + nb] - a0;
+        if (n == 0) continue; // (no atoms: no gradient rows)
+        Call sub = c;
+        Extent se;
+        off.assign(c.offsets + b0, c.offsets + b0 + nb + 1);
+        for (int64_t &v : off) v -= a0;
+        for (int b = 0; b < nb; ++b) se.max_atoms = std::max(se.max_atoms, off[b + 1] - off[b]);
+        se.total = n;
+        sub.offsets = off.data();
+        sub.B = nb;
+        sub.coords = c.coords + 3 * a0;
+        sub.channels = c.channels ? static_cast<const char *>(c.channels) + (size_t)a0 * chan_elem : nullptr;
+        sub.radii = (c.radii && c.radii_type == MVX_RADII_ATOM) ? static_cast<const char *>(c.radii) + (size_t)a0 * sizeof(float) : c.radii;
+        sub.xforms = c.xforms ? c.xforms + b0 : nullptr;
+        RunArgs fwd{sub, h->mgrad_grids.p, MVX_DEVICE};
+        fwd.no_overlap = fwd.f32_plain = true;
+        if ((rc = run_checked(h, fwd, se, nullptr))) break;
+        GradOut o{BWD_MOMENTS, h->mgrad_grids.p, grad_coords ? grad_coords + 3 * a0 : nullptr,
+                  grad_features ? static_cast<float *>(grad_features) + (size_t)a0 * c.C : nullptr, nullptr, nullptr, nullptr, {},
+                  {coef + (size_t)b0 * c.C * 3, target}};
+        Backward b(h, sub, o, n);
+        if ((rc = b.stage())) break;
+        if ((rc = b.moments())) break;
+        rc = release_slot(b.in.slot, c.stream);
+    }
+    h->profiling = profiling;
+    h->last_plan = plan; // (mvx_debug_last_plan: the cut of this call, not the plan of its last chunk)
+    h->has_plan = true;
+    return rc;
 }
 
 // what is wrong with the offsets of a selection handed back by the caller (B + 1 entries), or null
@@ -1669,6 +1755,22 @@ int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const voi
                     void *grad_features, void *stream) {
     return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream),
                          {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_mol_stride, scores, atom_scores}});
+}
+
+int mvx_moments_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                               double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                               int32_t B, int32_t C, const float *target, const double *grad_moments, double *grad_coords,
+                               mvx_real *grad_features, void *stream) {
+    const Call c = batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream);
+    Extent e;
+    // mvx_moments_batch's rules (it has no `moments` to miss here), then this entry's own; all before a device is touched
+    if (int rc = check_summed(h, c, true, target, nullptr, nullptr, e)) return rc;
+    if (B > 0 && !grad_moments) return fail(MVX_ERR_INVALID, "grad_moments must not be null");
+    if (grad_features && mode != MODE_FEATURES) return fail(MVX_ERR_INVALID, "grad_features exists in features mode only");
+    if (!grad_coords && !grad_features) return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
+    if (B == 0 || e.total == 0) return MVX_OK; // (no atoms: no gradient rows, nothing is launched)
+    // (one channel of a float32 grid stays below 4 GiB at every dimension mvx_create admits: the walk's 32-bit byte offsets hold)
+    return moments_backward(h, c, e, target, grad_moments, grad_coords, grad_features);
 }
 
 int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_coords, const int64_t *offsets,
@@ -1849,6 +1951,7 @@ int mvx_debug_set_option(mvx_handle *h, const char *name, int32_t value) {
     else if (n == "dense_grid") (void)value; // (accepted and ignored: there is no second voxelize launch any more)
     else if (n == "nw") k.force_nw = (value >= 1 && value <= 16) ? value : 0; // waves (8-voxel z sub-tiles) per slab; 0 = the default plan
     else if (n == "mall_budget_kb") k.mall_budget = value > 0 ? 1024.0 * (double)value : MALL_BUDGET;
+    else if (n == "mgrad_scratch_kb") h->mgrad_scratch = value > 0 ? 1024.0 * (double)value : MOMENTS_GRAD_SCRATCH;
 #ifdef MVX_DIAG
     else if (n == "dbg") h->dbg = value;
     else if (n == "vk_stamps") { // value = workgroups to make room for (0: off); read back with mvx_debug_read_diag

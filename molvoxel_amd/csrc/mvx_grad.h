@@ -1,7 +1,7 @@
 // mvx_grad.h - what the C-ABI TU (mvx_capi.hip) needs of the backward family: the argument records and launchers of the
-// three walks (mvx_grad.hip, mvx_grad_radii.hip, mvx_score.hip) and of the reductions (mvx_grad_radii.hip,
-// mvx_grad_density.hip), and the host-side dispatch (WalkKey / for_walk, for_real) those files launch through. Included by
-// mvx_capi.hip and, through mvx_grad_device.h, by the six kernel files of the family (those five, mvx_pose.hip and
+// four walks (mvx_grad.hip, mvx_grad_radii.hip, mvx_score.hip, mvx_moments_grad.hip) and of the reductions (mvx_grad_radii.hip,
+// mvx_grad_density.hip), and the host-side dispatch (WalkKey / for_walk, for_moments_walk, for_real) those files launch through.
+// Included by mvx_capi.hip and, through mvx_grad_device.h, by the seven kernel files of the family (those six, mvx_pose.hip and
 // mvx_views_reduce.hip). WalkKey, for_walk and for_real are plain host C++: tests/test_walk_dispatch_host.py compiles them alone.
 #pragma once
 #include <type_traits>
@@ -43,6 +43,19 @@ static hipError_t for_walk(const WalkKey &k, Fn &&fn) {
     return grid(GridTag<float>{});
 }
 
+// fn(ModeTag<MODE>, gauss constant, target constant) for the moments walk (moments_grad_kernel<MODE, GAUSS, TARGET>): what
+// mvx_moments_batch serves - float32 grids, features and MODE_TYPES (types and single) x Gaussian / binary x with / without a
+// target, 8 in all. hipErrorInvalidValue for a key of another grid type or with channel-wise radii for features.
+template <typename Fn>
+static hipError_t for_moments_walk(const WalkKey &k, bool target, Fn &&fn) {
+    if (k.grid_kind != 0 || k.chanwise) return hipErrorInvalidValue;
+    auto mode = [&](auto m) {
+        auto density = [&](auto gauss) { return target ? fn(m, gauss, std::true_type{}) : fn(m, gauss, std::false_type{}); };
+        return k.gauss ? density(std::true_type{}) : density(std::false_type{});
+    };
+    return k.mode == MODE_FEATURES ? mode(ModeTag<MODE_FEATURES>{}) : mode(ModeTag<MODE_TYPES>{});
+}
+
 // fn(TypeTag<real>): the handle's real type (float, or double at precision 64) of the arrays a launcher takes as void *
 template <typename Fn>
 static hipError_t for_real(bool f64, Fn &&fn) {
@@ -80,6 +93,13 @@ struct ScoreArgs {
     int64_t mol_stride;  // elements between the fields of two molecules: 0 (one field shared by all) or C * D^3
 };
 
+// gradients of the moments (mvx_moments_backward_batch, moments_grad_kernel): GradArgs::g holds the float32 NCDHW grids g of the
+// launch's molecules, and the walk forms the upstream itself: u[b,c,v] = fmaf(a1, g[b,c,v], fmaf(a2, t[c,v], a0)) in float32
+struct MomentsArgs {
+    const float *coef;   // (B, C, 3): a0 = (float)G0, a1 = (float)(2 G1), a2 = (float)G2 of the launch's molecules (launch_moments_coef)
+    const float *target; // t: (C, D, D, D) float32 NCDHW, one for all molecules, or null (then u = fmaf(a1, g, a0))
+};
+
 // channel-wise radii for features: rmax[0] = max(radii) (what prep_kernel culls with), per-channel thresholds Tc and
 // coefficients kc (float, or double for f64), from the forward's d2_threshold / gauss_coeff (float64: their *64 forms)
 hipError_t launch_grad_chan(const void *radii, int32_t C, bool f64, bool gauss, float sigma32, double sigma64, void *rmax, double *Tc,
@@ -99,6 +119,12 @@ hipError_t launch_grad_radii(const GradArgs &a, const RadiiArgs &r, const WalkKe
 hipError_t launch_score(const GradArgs &a, const ScoreArgs &sa, const WalkKey &key, hipStream_t s);
 // scores[b] = sum of atom_scores over molecule b in a fixed order (one workgroup per molecule, no atomics); 0 without atoms
 hipError_t launch_score_reduce(const double *atom_scores, const int64_t *offsets, int32_t B, double *scores, hipStream_t s);
+// The coefficients of the moments walk from dL/dm: grad_moments (n, K) doubles, K = 3 | 2 (no target: a2 = 0) -> coef (n, 3)
+// floats, n = B * C: a0 = (float)G0, a1 = (float)(2.0 * G1), a2 = (float)G2.
+hipError_t launch_moments_coef(const double *grad_moments, int64_t n, int32_t K, float *coef, hipStream_t s);
+// The same walk over the float32 grids g in GradArgs::g with the upstream formed from them (mvx_moments_grad.hip): the
+// coordinate and feature gradients are grad_kernel's bits for G = u. `key`: grid_kind 0 and no channel-wise radii for features.
+hipError_t launch_moments_grad(const GradArgs &a, const MomentsArgs &ma, const WalkKey &key, hipStream_t s);
 // Both reductions over the atoms of a call sum chunks of GRAD_CHUNK atoms first (one block per chunk), then the chunks in order.
 constexpr int GRAD_CHUNK = 4096;
 inline int32_t grad_nchunk(int64_t total) { return (int32_t)((total + GRAD_CHUNK - 1) / GRAD_CHUNK); }

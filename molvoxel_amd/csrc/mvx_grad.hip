@@ -30,6 +30,8 @@ __global__ void __launch_bounds__(256) grad_kernel(GradArgs A) {
     constexpr RadiiArgs RA{}; // (no radius partials: never read)
     constexpr bool SCORE = false;
     constexpr ScoreArgs SA{}; // (no scores: never read)
+    constexpr bool MOMENTS = false, TARGET = false;
+    constexpr MomentsArgs MA{}; // (the upstream is read, not formed: never read)
 #include "mvx_grad_body.inc"
 }
 

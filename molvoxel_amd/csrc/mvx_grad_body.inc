@@ -1,9 +1,12 @@
 // mvx_grad_body.inc - the body of the gradient walk, included by grad_kernel (mvx_grad.hip, RADII = false), by its twin
-// grad_radii_kernel (mvx_grad_radii.hip, RADII = true) and by score_kernel (mvx_score.hip, SCORE = true): one text, three
-// kernels whose names stay apart and whose coordinate and feature gradients are the same bits; for_walk (mvx_grad.h) names their
-// instantiations and launch_walk (mvx_grad_device.h) launches each of them. Expects the kernel parameters
-// A (GradArgs), RA (RadiiArgs) and SA (ScoreArgs), the template parameters GT, MODE, GAUSS, CHANWISE and the constexpr bools
-// RADII and SCORE. With SCORE, A.g is a constant field F (one per molecule, or one for all: SA.mol_stride) and the walk also
+// grad_radii_kernel (mvx_grad_radii.hip, RADII = true), by score_kernel (mvx_score.hip, SCORE = true) and by moments_grad_kernel
+// (mvx_moments_grad.hip, MOMENTS = true): one text, four kernels whose names stay apart and whose coordinate and feature
+// gradients are the same bits for the same upstream; for_walk and for_moments_walk (mvx_grad.h) name their instantiations and
+// launch_walk (mvx_grad_device.h) launches each of them. Expects the kernel parameters A (GradArgs), RA (RadiiArgs),
+// SA (ScoreArgs) and MA (MomentsArgs), the template parameters GT, MODE, GAUSS, CHANWISE and the constexpr bools RADII, SCORE,
+// MOMENTS and TARGET. With MOMENTS, A.g holds the float32 grids g of the call's molecules and the upstream of voxel v in
+// channel c is formed here, in float32: u = fmaf(a1, g[c,v], fmaf(a2, t[c,v], a0)) - without TARGET fmaf(a1, g[c,v], a0) -
+// from the three coefficients MA.coef keeps per (molecule, channel) and the one shared target MA.target. With SCORE, A.g is a constant field F (one per molecule, or one for all: SA.mol_stride) and the walk also
 // forms the atom's score s_n = sum_v sum_c F[c,v] w[n,c] rho_{n,c}(v) - e without kfac - in float64 from the float32 products
 // of the coordinate path, for binary density too. With RADII the walk also forms the radius partials
 // (kfac: dk/dr = -2k/r, so d rho / d r = -(kfac / r) d2 rho):
@@ -64,6 +67,20 @@
     if constexpr (!FEAT) {
         const int ch = MODE == MODE_TYPES ? R.type : 0; // (an atom of type >= C has no admitted box)
         const GT *gc = gm + (size_t)(ch < A.C ? ch : 0) * D3;
+        // the upstream at a voxel of this atom's channel; MOMENTS: formed from g, the target and the channel's coefficients
+        const float *mc = nullptr, *tc = nullptr;
+        if constexpr (MOMENTS) {
+            mc = MA.coef + ((size_t)bm * A.C + (size_t)(ch < A.C ? ch : 0)) * 3;
+            if constexpr (TARGET) tc = MA.target + (size_t)(ch < A.C ? ch : 0) * D3;
+        }
+        auto upstream = [&](size_t off) -> real {
+            if constexpr (MOMENTS) {
+                if constexpr (TARGET) return __builtin_fmaf(mc[1], load_grad(gc + off), __builtin_fmaf(mc[2], tc[off], mc[0]));
+                else return __builtin_fmaf(mc[1], load_grad(gc + off), mc[0]);
+            } else {
+                return load_grad(gc + off);
+            }
+        };
         if (GAUSS || SCORE) { // (binary density has no coordinate gradient, but it scores)
             for (int v0 = 0; v0 < nbox; v0 += 64) {
                 const int v = v0 + lane;
@@ -74,13 +91,13 @@
                 const real rho = density(d2, T, k32, c64, v < nbox);
                 if (rho != (real)0) { // (binary density: no coordinate gradient, nothing to read)
                     if constexpr (GAUSS) {
-                        const double e = (double)(load_grad(gc + off) * rho) * kfac;
+                        const double e = (double)(upstream(off) * rho) * kfac;
                         cp0 += e * dx;
                         cp1 += e * dy;
                         cp2 += e * dz;
                         if constexpr (RADII) rp += e * d2;
                     }
-                    if constexpr (SCORE) sp += (double)(load_grad(gc + off) * rho);
+                    if constexpr (SCORE) sp += (double)(upstream(off) * rho);
                 }
             }
         }
@@ -110,8 +127,28 @@
                         // all 32 loads in flight before the first use: the kernel is bound by the latency of these
                         // round trips (groups of eight, one after the other, cost the same registers and 4x the waits)
                         real gv[32];
+                        if constexpr (MOMENTS) {
+                            // the grids' values and, with a target, its values: up to 64 loads in flight, then u in their place
+                            real tv[TARGET ? 32 : 1];
 #pragma unroll
-                        for (int c = 0; c < 32; ++c) gv[c] = c < nc ? gload(c) : (real)0;
+                            for (int c = 0; c < 32; ++c) gv[c] = c < nc ? gload(c) : (real)0;
+                            if constexpr (TARGET) {
+#pragma unroll
+                                for (int c = 0; c < 32; ++c)
+                                    tv[c] = c < nc ? *reinterpret_cast<const float *>(reinterpret_cast<const char *>(MA.target + (size_t)(c0 + c) * D3) + boff) : 0.0f;
+                            }
+                            const float *mc = MA.coef + ((size_t)bm * A.C + (size_t)c0) * 3;
+#pragma unroll
+                            for (int c = 0; c < 32; ++c) {
+                                if (c < nc) {
+                                    if constexpr (TARGET) gv[c] = __builtin_fmaf(mc[3 * c + 1], gv[c], __builtin_fmaf(mc[3 * c + 2], tv[c], mc[3 * c]));
+                                    else gv[c] = __builtin_fmaf(mc[3 * c + 1], gv[c], mc[3 * c]);
+                                }
+                            }
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 32; ++c) gv[c] = c < nc ? gload(c) : (real)0;
+                        }
 #pragma unroll
                         for (int c = 0; c < 32; ++c) {
                             if (c < nc) {

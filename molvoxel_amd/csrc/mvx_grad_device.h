@@ -1,5 +1,5 @@
-// mvx_grad_device.h - device helpers and the walk launch of the backward family, included by its six kernel files:
-// mvx_grad.hip, mvx_grad_radii.hip and mvx_score.hip (the walks of mvx_grad_body.inc, launch_walk), mvx_grad_radii.hip and
+// mvx_grad_device.h - device helpers and the walk launch of the backward family, included by its seven kernel files:
+// mvx_grad.hip, mvx_grad_radii.hip, mvx_score.hip and mvx_moments_grad.hip (the walks of mvx_grad_body.inc, launch_walk), mvx_grad_radii.hip and
 // mvx_grad_density.hip (the reductions over a call: block_sum4, sum4), mvx_pose.hip and mvx_views_reduce.hip (wave sums, sum4).
 #pragma once
 #include "mvx_device.h"
@@ -92,7 +92,7 @@ __device__ __forceinline__ T wave_sum32_regs(T (&v)[32], int lane) {
     return v[0] + __shfl_xor(v[0], 1, 64);
 }
 
-// The launch of a walk kernel (one of for_walk's instantiations; extra: its RadiiArgs or ScoreArgs): four atoms per block of
+// The launch of a walk kernel (one of for_walk's or for_moments_walk's instantiations; extra: its RadiiArgs, ScoreArgs or MomentsArgs): four atoms per block of
 // 256 in atom order, or 8 a.xcd_span blocks under the spatial order; nothing without atoms. Not launch_kernel<Kern>
 // (mvx_device.h): that one consumes timed_launch's pending profiling events, which the backward entries must not.
 template <typename Kern, typename... Extra>

@@ -20,6 +20,8 @@ __global__ void __launch_bounds__(256) grad_radii_kernel(GradArgs A, RadiiArgs R
     constexpr bool RADII = true;
     constexpr bool SCORE = false;
     constexpr ScoreArgs SA{}; // (no scores: never read)
+    constexpr bool MOMENTS = false, TARGET = false;
+    constexpr MomentsArgs MA{}; // (the upstream is read, not formed: never read)
 #include "mvx_grad_body.inc"
 }
 

@@ -21,6 +21,8 @@ __global__ void __launch_bounds__(256) score_kernel(GradArgs A, ScoreArgs SA) {
     constexpr bool RADII = false;
     constexpr RadiiArgs RA{}; // (no radius partials: never read)
     constexpr bool SCORE = true;
+    constexpr bool MOMENTS = false, TARGET = false;
+    constexpr MomentsArgs MA{}; // (the upstream is the field, read as it is: never read)
 #include "mvx_grad_body.inc"
 }
 

@@ -60,6 +60,10 @@ constexpr int BIG_WAVES_PER_SIMD = 8;
 // bytes of pre-pass data (records, keys, feature rows, slab lines: re-read ~20 times) per voxelize launch: what stays in
 // the 256 MiB Infinity Cache. One launch over 512 cfg-2 molecules (544 MB) ran at 0.654 of peak, in two chunks at 0.755.
 constexpr double MALL_BUDGET = 288.0e6;
+// bytes of float32 grids one molecule chunk of mvx_moments_backward_batch may leave in scratch: the forward's own cut counts
+// pre-pass bytes, not grid bytes (cfg-2 x 256 is ONE chunk: 8.6 GB of grids), so the entry cuts further until a chunk's grids
+// fit (one molecule per chunk at least). profiles/r16_moments_grad.txt has the step with this value and without the bound.
+constexpr double MOMENTS_GRAD_SCRATCH = 1024.0 * 1024.0 * 1024.0;
 // One launch for the whole call (voxelize_pair_kernel: two slabs per workgroup, one workgroup per compute unit at a time)
 // instead of prep -> xbin -> voxelize. us per call binned / one launch (tools/route_sweep.py, profiles/r04_route_sweep.txt);
 // "workgroups" below counts slabs as plan_call does (a pair kernel workgroup serves two). One molecule on a 64^3 grid, C = 32

@@ -100,6 +100,7 @@ SIGNATURES = {
     "mvx_forward_views_sum": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
     "mvx_set_sum_parts": (C.c_int, [Handle, _i32]),
     "mvx_moments_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "mvx_moments_backward_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mvx_score_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                   _vp, _vp]),
     "mvx_views_reduce": (C.c_int, [Handle, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp]),

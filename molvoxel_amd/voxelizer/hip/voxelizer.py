@@ -19,6 +19,9 @@ Constructor options:
   radii_grad / sigma_grad / field_grad (with differentiable)  gradients for a radii tensor (mvx_backward_radii_batch; a
                                one-element tensor on a scalar-radii voxelizer), for a one-element `sigma=` / `set_sigma()`
                                tensor (mvx_backward_density_batch), and for the shared field of `score_batch`
+  moments_grad=True (with differentiable)  `moments_batch` / `moments_posed_batch` record an autograd graph: coords, features,
+                               centres and poses that require grad get their gradients through the moments
+                               (mvx_moments_backward_batch), without B grids and without any grid of dL/dgrid
   overlap_prepass=True         see `set_overlap_prepass`
 
 Entries, next to the reference's `forward_features / forward_types / forward_single`:
@@ -99,6 +102,7 @@ class Voxelizer(BaseVoxelizer):
     precision = 32
     blockdim = 8
     field_grad = False
+    _mgrad = False  # (the constructor's moments_grad)
     _sum_parts = 1
     _views_total = 0
 
@@ -119,6 +123,7 @@ class Voxelizer(BaseVoxelizer):
         sigma_grad: bool = False,
         grid_layout=None,
         field_grad: bool = False,
+        moments_grad: bool = False,
         **kwargs,
     ):
         # sigma as a tensor (sigma_grad): kept as `sigma_tensor`; `_sigma` stays the python float the base class stores
@@ -142,8 +147,11 @@ class Voxelizer(BaseVoxelizer):
             raise ValueError("sigma_grad=True needs differentiable=True: the sigma gradient is part of the autograd graph")
         if field_grad and not differentiable:
             raise ValueError("field_grad=True needs differentiable=True: the field gradient is part of the autograd graph")
+        if moments_grad and not differentiable:
+            raise ValueError("moments_grad=True needs differentiable=True: the gradients of the moments are part of the autograd graph")
         self.differentiable = bool(differentiable)
         self.field_grad = bool(field_grad)
+        self._mgrad = bool(moments_grad)
         self.radii_grad = bool(radii_grad)
         self.sigma_grad = bool(sigma_grad)
         self._sigma_src = sigma_src
@@ -384,7 +392,7 @@ class Voxelizer(BaseVoxelizer):
                                self.blockdim, idx, self.output, self.overlap_prepass,
                                grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
                                radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout,
-                               field_grad=self.field_grad, **kw)
+                               field_grad=self.field_grad, moments_grad=self._mgrad, **kw)
             if self.sum_parts != 1:
                 moved.set_sum_parts(self.sum_parts)
             return moved
@@ -1185,7 +1193,12 @@ class Voxelizer(BaseVoxelizer):
         The products are exact in float64, so each moment lies within (D^3 - 1) * 2^-53 * sum|term| of the exact sum; sums of
         small integers (binary density with types or one channel) are exact. Deterministic, no atomics: a molecule's values do
         not depend on its batch, and the first two do not depend on the target. Molecules without atoms inside the box give
-        exact zeros. The result is NOT part of the autograd graph: inputs that require grad are read as values.
+        exact zeros. The result is NOT part of the autograd graph: inputs that require grad are read as values - unless the
+        voxelizer was made with moments_grad=True (and differentiable=True). Then, with grad mode on and coords, features or
+        centers that require grad, the same call - the same bits - records a graph, and backward() gives their gradients through
+        the moments (mvx_moments_backward_batch: dL/dgrid = dL/dm0 + 2 dL/dm1 g + dL/dm2 target is formed inside the backward
+        walk, molecule chunk by molecule chunk, without B grids and without any grid of dL/dgrid). A target, radii or a sigma
+        tensor that requires grad raises ValueError there: no gradients with respect to them.
         Not supported (NotImplementedError; use forward_batch(...) and reduce the grids): precision 64, channel-wise radii with
         features, dimensions that are no multiple of 4, and blockdims that cut through the kernels' 2 x 4 x 8 sub-tiles."""
         return self._moments_batch(coords, offsets, centers, channels, radii, target, num_channels, random_translation,
@@ -1194,9 +1207,21 @@ class Voxelizer(BaseVoxelizer):
     def moments_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, target=None,
                             num_channels=None):
         """moments_batch with one explicit rigid pose per molecule (forward_posed_batch's arguments and records): the moments
-        of the grids of B poses - every pose's cross-correlation with a map in one call. Not part of the autograd graph."""
+        of the grids of B poses - every pose's cross-correlation with a map in one call. Not part of the autograd graph, unless
+        the voxelizer was made with moments_grad=True: then `centers`, `quaternions` and `translations` that require grad get
+        their gradients too (mvx_pose_grad_batch on the per-atom gradients), next to coords and features."""
         return self._moments_batch(coords, offsets, centers, channels, radii, target, num_channels,
                                    posed=(quaternions, translations))
+
+    def _moments_grad_guard(self, radii, target):
+        """What a moments call on a moments_grad voxelizer refuses while grad mode is on: gradients it does not provide."""
+        if _is_torch(target) and target.requires_grad:
+            raise ValueError("moments_grad gives no gradient with respect to the target: detach it (dL/dtarget[c] is "
+                             "sum_b dL/dm[b, c, 2] * grid[b, c]: use forward_batch (forward_posed_batch) for it)")
+        for what, x in (("radii", radii), ("sigma", self.sigma_tensor)):
+            if _is_torch(x) and x.requires_grad:
+                raise ValueError(f"moments_grad gives no gradient with respect to {what}: detach it, or use forward_batch "
+                                 "(forward_posed_batch) and reduce the grids for that gradient")
 
     def _moments_batch(self, coords, offsets, centers, channels, radii, target=None, num_channels=None, random_translation=0.0,
                        random_rotation=False, posed=None):
@@ -1209,15 +1234,42 @@ class Voxelizer(BaseVoxelizer):
                 shape = tuple(getattr(target, "shape", ()))
                 assert shape == self.grid_dimension(C_), f"target does not match dimension: {shape} vs {self.grid_dimension(C_)}"
 
-        with torch.no_grad():
+        # moments_grad: the call is built with grad mode as it is (the conversions and the packed poses are recorded), tracking
+        # what a score call tracks: coords, features and centres (poses)
+        record = self._mgrad and torch.is_grad_enabled()
+        if record:
+            self._moments_grad_guard(radii, target)
+        with torch.enable_grad() if record else torch.no_grad():
             call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
-                                    posed, device=True, check=check)
-            T = None
-            if target is not None:
-                T = (target if _is_torch(target) else torch.as_tensor(np.asarray(target))).to(device=self.device, dtype=torch.float32).contiguous()
-            out = torch.empty((call.B, call.C, 2 if T is None else 3), dtype=torch.float64, device=self.device)
-            _lib.check(self._lib.mvx_moments_batch(*call.batch_args(self), self._ptr(T), self._ptr(out), self._stream()))
-            return out
+                                    posed, device=True, score=record, check=check)
+
+        def run():
+            with torch.no_grad():
+                T = None
+                if target is not None:
+                    T = (target if _is_torch(target) else torch.as_tensor(np.asarray(target))).to(device=self.device, dtype=torch.float32).contiguous()
+                out = torch.empty((call.B, call.C, 2 if T is None else 3), dtype=torch.float64, device=self.device)
+                _lib.check(self._lib.mvx_moments_batch(*call.batch_args(self), self._ptr(T), self._ptr(out), self._stream()))
+                return out, T
+
+        if not (record and call.grad):
+            return run()[0]
+        call.settings = self._grad_settings()
+        return _MomentsFunction.apply(self, run, call, call.coords, call.channels if call.mode == "features" else None,
+                                      call.centers, call.pose)
+
+    def _moments_backward(self, spec, c, f, T, gm, need_features):
+        """(dL/dcoords (N, 3) float64, dL/dfeatures (N, C) or None) for dL/dm = gm (B, C, K), on the current stream. spec: the
+        forward call's _Call; c, f: its coords and features as autograd saved them; T: the target as the forward read it."""
+        self._same_settings(spec)
+        g = gm.to(device=self.device, dtype=torch.float64).contiguous()
+        gc = torch.empty((c.shape[0], 3), dtype=torch.float64, device=self.device)
+        gf = torch.empty((c.shape[0], spec.C), dtype=self._tfp, device=self.device) if need_features else None
+        if c.shape[0] == 0 or spec.B == 0:  # no atoms: no gradient rows
+            return gc, gf
+        _lib.check(self._lib.mvx_moments_backward_batch(*spec.batch_args(self, c, f if spec.mode == "features" else None),
+                                                        self._ptr(T), self._ptr(g), self._ptr(gc), self._ptr(gf), self._stream()))
+        return gc, gf
 
     # ------------------------------------------------------------------------------------------
     # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
@@ -1455,16 +1507,20 @@ class Voxelizer(BaseVoxelizer):
         """What the backward reads from the voxelizer rather than from the call: density, sigma and radii type."""
         return (self.density_type, float(self._sigma) if self.is_density_type_gaussian else None, self.radii_type)
 
-    def _backward(self, spec, c, f, grad, need_features, need_radii=False, need_sigma=False, need_rscalar=False):
-        """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None, dL/dradii shaped and typed like the call's radii or None,
-        dL/dsigma and dL/d(scalar radius) as 0-dim float64 device tensors or None) for dL/dgrid = grad, on the current stream.
-        spec: the forward call's _Call; c, f: its coords and features as autograd saved them."""
+    def _same_settings(self, spec):
+        """backward() of a recorded call: the settings it reads from the voxelizer must be the forward's."""
         now = self._grad_settings()
         if now != spec.settings:
             raise RuntimeError(
                 "the voxelizer's density / sigma / radii type changed between the forward call and backward() "
                 f"(forward: {spec.settings}, now: {now}); the gradients would be those of another grid. Restore the "
                 "settings before backward(), or use one voxelizer per setting")
+
+    def _backward(self, spec, c, f, grad, need_features, need_radii=False, need_sigma=False, need_rscalar=False):
+        """(dL/dcoords (N,3) float64, dL/dfeatures (N,C) or None, dL/dradii shaped and typed like the call's radii or None,
+        dL/dsigma and dL/d(scalar radius) as 0-dim float64 device tensors or None) for dL/dgrid = grad, on the current stream.
+        spec: the forward call's _Call; c, f: its coords and features as autograd saved them."""
+        self._same_settings(spec)
         g = grad.to(device=self.device, dtype=self._gdt).contiguous()
         gc = torch.empty((c.shape[0], 3), dtype=torch.float64, device=self.device)
         gf = torch.empty((c.shape[0], spec.C), dtype=self._tfp, device=self.device) if need_features else None
@@ -1618,6 +1674,32 @@ if torch is not None:
                 gfield = ctx.vox._sum_call(ctx.spec, up.to(torch.float32), None, False, coords=c)
                 gfield = gfield.to(dtype=ctx.field_like[0]).to(ctx.field_like[1])
             return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose, gfield
+
+
+    class _MomentsFunction(torch.autograd.Function):
+        """moments = moments(coords, features, centres, packed poses) on a moments_grad voxelizer: the forward call as it runs
+        without autograd (same kernels, same bits); backward = mvx_moments_backward_batch from the saved inputs, the target as
+        the forward read it and the call's record (`spec`: a random transform's records are reused, not redrawn), then centres
+        and poses reduced as _VoxelizeFunction does."""
+
+        @staticmethod
+        def forward(ctx, vox, run, spec, c, f, cen, pose):
+            out, T = run()
+            ctx.vox, ctx.spec = vox, spec
+            ctx.save_for_backward(c, f, cen, pose, T)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, gm):
+            c, f, cen, pose, T = ctx.saved_tensors
+            need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[3:7]
+            gc, gf = ctx.vox._moments_backward(ctx.spec, c, f, T, gm, need_f)
+            lengths = None
+            if need_cen and cen.numel() != 3:
+                lengths = torch.as_tensor(np.diff(ctx.spec.offsets), device=gc.device)
+            gcen, gpose = _rigid_grads(ctx.vox, ctx.spec, c, gc, cen, lengths, need_cen, need_pose)
+            return None, None, None, gc if need_c else None, gf, gcen, gpose
 
 
     class _ScoreViewsFunction(torch.autograd.Function):
