@@ -759,11 +759,8 @@ struct Forward {
         pa.xp = reinterpret_cast<uint2 *>(w->xp.p);
         va.rec = reinterpret_cast<const unsigned *>(w->rec.p);
         va.w = reinterpret_cast<const unsigned *>(direct_w ? in.channels : w->wbuf.p);
-        va.xlist = reinterpret_cast<uint2 *>(w->xlist.p);
         va.slist = d_slist;
         va.slist_ext = d_slist ? d_slist + nslabs * SLAB_LINE_ENTRIES : nullptr; // extension lines live behind the primary lines
-        va.offsets = in.offsets;
-        va.n_one = ext.total;
         va.Tc = d_Tc;
         va.kc = d_kc;
         if (walk == WALK_GROUPED) {
@@ -794,7 +791,7 @@ struct Forward {
         va.p.NW = plan.nw;
         va.p.nslab = (uint32_t)(plan.nsx * plan.nsy * plan.nzc);
         va.p.w_stride = plan.grouped ? r.C : plan.cpad;
-        va.p.dcap = f64 ? (plan.route == MVX_ROUTE_F64_MX ? 0 : 64) : 0; // (float64: rows per round of the general slab loop, 0 selects the matrix-core kernel)
+        va.p.dcap = 0; // (set by the launchers that keep a table behind the rows / tile region)
         va.p.vec_store = plan.vec_store;
         va.p.xcd_ranges = plan.xcd_ranges;
         va.p.pace = plan.pace;

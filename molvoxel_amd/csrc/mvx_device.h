@@ -410,12 +410,9 @@ static_assert(SLOTS == SLAB_LINE_ENTRIES && EXT_SLOTS == SLAB_EXT_ENTRIES, "slab
 //   Channel-wise radii for features: the GROUPED instantiation (one threshold / density per distinct radius and candidate);
 //   the CHANWISE instantiation (one per channel) only when there are more than 32 distinct radii.
 // voxelize64_kernel: the same slab body for float64 grids with chunks of 32 channels (OpsMx64, v_mfma_f64_16x16x4_f64).
-// voxelize_dense_kernel (the general slab loop, float64 grids of <= 16 channels or with channel-wise radii: grid-stride
-//   over all slabs). Per slab: rounds of 64 entries over the primary + extension line (<= 255 candidates), or, beyond
-//   that, wave 0 compacts the (molecule, x-slab) list in rounds of LCAP entries into an LDS list and the rows are staged
-//   in rounds of dcap; same walk and write-out.
-// LDS map (dynamic, 16-B aligned): voxelize_kernel: union { 64 x SW words of rows ; (CR*RPC rows) x RS floats tile };
-//   dense kernel: int list[LCAP] | uint32 zr[LCAP] | int nlist | union { dcap rows ; tile }, LCAP = 64 * min(NW, 4).
+// voxelize64_vec_kernel: ... and for float64 grids of <= 16 channels per chunk or with channel-wise radii (OpsF64, one voxel per
+//   lane on the vector ALU).
+// LDS map (dynamic, 16-B aligned): union { 64 x SW words of rows ; (CR*RPC rows) x RS floats tile }.
 
 // 16-B output store: non-temporal. Output bytes are written once and never re-read here; nt keeps them from displacing
 // the re-read inputs in L2 (0.69 -> 0.54 ms, cfg-2; sc1 = plain).

@@ -3,23 +3,19 @@
 //
 //   voxelize64_kernel      chunks of 32 channels, scalar / atom-wise radii: the slab body (mvx_slab_body.inc) with OpsMx64 -
 //                          v_mfma_f64_16x16x4_f64, four candidates per instruction, bit for bit the fma chain in candidate order.
-//   voxelize_dense_kernel  the general slab loop (<= 16 channels, or channel-wise radii): grid-stride over all slabs. Per
-//                          slab: rounds of 64 entries over the primary + extension line (<= 255 candidates), or, beyond
-//                          that, wave 0 compacts the (molecule, x-slab) list in rounds of LCAP entries into an LDS list and
-//                          the rows are staged in rounds of dcap; same walk and write-out.
-//   LDS map of the dense kernel (dynamic, 16-B aligned): int list[LCAP] | uint32 zr[LCAP] | int nlist |
-//                          union { dcap rows ; tile }, LCAP = 64 * min(NW, 4).
+//   voxelize64_vec_kernel  chunks of 1 / 4 / 8 / 16 channels, or channel-wise radii: the same slab body with OpsF64 - one voxel
+//                          per lane on the vector ALU, the library's exp, the fma chain in candidate order.
 #include "mvx_device.h"
 
 namespace mvx {
 
 __host__ __device__ __forceinline__ int row_stride_doubles(int NW) { return SUBZ * NW + 8; }
-// general slab loop: rows of 16 + 2*ct words, 64 per round (p.dcap = 64), or the write-out tile
-static size_t dense64_lds_bytes(int32_t ct, int32_t NW) {
-    const int lcap = 64 * (NW < 4 ? NW : 4);
-    const size_t rows = (size_t)64 * (16 + 2 * ct) * 4;
+// LDS of either float64 kernel: the 64 rows of a round (sw words each) or the write-out tile (min(ct, CR64) channels),
+// whichever is larger
+static size_t voxelize64_lds_bytes(int32_t sw, int32_t ct, int32_t NW) {
+    const size_t rows = (size_t)64 * sw * 4;
     const size_t tile = (size_t)(ct < CR64 ? ct : CR64) * RPC * row_stride_doubles(NW) * 8;
-    return (size_t)8 * lcap + 16 + (rows > tile ? rows : tile);
+    return rows > tile ? rows : tile;
 }
 
 // float64 write-out: the same transposition through an LDS tile, 8 channels per round, rows of SUBZ*NW doubles read
@@ -152,11 +148,6 @@ __device__ __forceinline__ double exp_nonpos64(double x, const double *__restric
     return ldexp(fma(t, p, t), ki >> 6);
 }
 constexpr int MX64_SW = 84; // 16 + 64 words, padded to an odd number of 16-B quads (one row per lane in the row filter)
-static size_t voxelize_mx64_lds_bytes(int32_t NW) {
-    const size_t rows = (size_t)64 * MX64_SW * 4;
-    const size_t tile = (size_t)CR64 * RPC * row_stride_doubles(NW) * 8;
-    return rows > tile ? rows : tile;
-}
 
 template <bool GAUSS, bool LANE_RANGE>
 struct OpsMx64 {
@@ -311,21 +302,37 @@ struct OpsMx64 {
 template <int CT_, bool GAUSS, bool CHANWISE, bool LANE_RANGE>
 struct OpsF64 {
     static constexpr bool RUNS = false;
-    static constexpr bool PRESTAGE = false;
     static constexpr int CT = CT_;
+    static constexpr bool GROUPED = false;
+    static constexpr bool VSTAGE = false;
+    static constexpr bool CULL = false; // (every wave walks the rows whose z range meets its sub-tile, hit or not)
+    static constexpr bool PRESTAGE = false;
     typedef double Acc[CT];
     static constexpr int WORDS = 2;
     static constexpr int WW = 2 * CT;
     static constexpr int SW = 16 + 2 * CT;
-    static_assert(16 + WW <= 128, "a row is staged by at most two wave-wide loads");
+    static_assert(16 + WW <= 64, "a row is staged by one wave-wide load");
     static __device__ __forceinline__ void zero(Acc &acc) {
 #pragma unroll
         for (int c = 0; c < CT; ++c) acc[c] = 0.0;
     }
+    static __device__ __forceinline__ LaneCtx ctx(int lane, int wave, int x0, int y0, int z0, int zt_lo, int cbase, const VoxParams &P) {
+        return make_lane_ctx(lane, wave, x0, y0, z0, zt_lo, cbase, P);
+    }
+    static __device__ __forceinline__ void tables(LaneCtx &, char *, const VoxParams &, int) {}
     static __device__ __forceinline__ void accumulate(Acc &acc, const unsigned *r, const LaneCtx &L, const VoxParams &P,
                                                       const double *__restrict__ Tc, const float *__restrict__ kc) {
         // (float64 handles keep float64 per-channel coefficients behind the `kc` pointer)
         accumulate_row64<CT, GAUSS, CHANWISE, LANE_RANGE>(acc, r, L, P.C, Tc, reinterpret_cast<const double *>(kc));
+    }
+    // the rows of `mask` (one bit per staged row, atom order) into the accumulators
+    static __device__ __forceinline__ void walk(Acc &acc, unsigned long long mask, const unsigned *un, int lane, const LaneCtx &L,
+                                                const VoxParams &P, const double *__restrict__ Tc, const float *__restrict__ kc) {
+        while (mask) {
+            const int sl = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            accumulate(acc, un + sl * SW, L, P, Tc, kc);
+        }
     }
     static __device__ __forceinline__ void write(const Acc &acc, bool, unsigned *un, int tid, int lane, int wave, int NW, int b,
                                                  const LaneCtx &L, int x0, int y0, int z0, void *out, const VoxParams &P) {
@@ -333,55 +340,6 @@ struct OpsF64 {
                          static_cast<double *>(out), P);
     }
 };
-
-// One round of the line path: entries [e0, e0 + RW) of a slab line sit in the lanes of Er (lane l = entry e0 + l);
-// candidates are entries 1..n_line. Stages their rows (slot = lane index) and walks them. Ends without a barrier.
-template <typename Ops>
-__device__ __forceinline__ void line_round(typename Ops::Acc &acc, const uint2 Er, int e0, int n_line, int RW,
-                                           unsigned *un, const unsigned *__restrict__ rec, const unsigned *__restrict__ w,
-                                           int64_t a0, int lane, int wave,
-                                           int NW, const LaneCtx &L, const VoxParams &P, const double *__restrict__ Tc,
-                                           const float *__restrict__ kc) {
-    constexpr int SW = Ops::SW;
-    // lanes 0-15 fetch the record, lanes 16.. the channel weights of the chunk: one load instruction per row
-    const unsigned *src = lane < 16 ? rec + lane : w + (Ops::WORDS * L.cbase + lane - 16);
-    const size_t stride = lane < 16 ? (size_t)16 : (size_t)(Ops::WORDS * P.w_stride);
-    const bool stager = lane < 16 + Ops::WW;
-    // rows wider than a wave (float64, 32 channels: 16 + 64 words): lanes 0.. fetch words 64.. with a second load
-    constexpr int TAIL = 16 + Ops::WW > 64 ? 16 + Ops::WW - 64 : 0;
-    const unsigned *src2 = w + (Ops::WORDS * L.cbase + lane + 48);
-    unsigned v[8], v2[TAIL ? 8 : 1];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int sl = wave + u * NW; // row slot staged by this wave (wave-uniform) <-> entry e0 + sl
-        v[u] = 0u;
-        if (TAIL) v2[u] = 0u;
-        if (sl < RW && e0 + sl >= 1 && e0 + sl <= n_line) {
-            const int ai = __builtin_amdgcn_readlane((int)Er.x, sl & 63);
-            if (stager) v[u] = src[(size_t)(a0 + ai) * stride];
-            if (TAIL && lane < TAIL) v2[u] = src2[(size_t)(a0 + ai) * (size_t)(Ops::WORDS * P.w_stride)];
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int sl = wave + u * NW;
-        if (sl < RW && e0 + sl >= 1 && e0 + sl <= n_line && stager) un[sl * SW + lane] = v[u];
-        if (TAIL && sl < RW && e0 + sl >= 1 && e0 + sl <= n_line && lane < TAIL) un[sl * SW + 64 + lane] = v2[u];
-    }
-    VK_STAMP(2);
-    __syncthreads();
-    VK_STAMP(3);
-    const unsigned pk = Er.y;
-    const bool ok = (lane < RW) && (e0 + lane >= 1) && (e0 + lane <= n_line) && ((int)((pk >> 16) & 0xff) <= L.zt_w) &&
-                    ((int)(pk >> 24) >= L.zt_w);
-    unsigned long long mask = __ballot(ok);
-    while (mask) {
-        const int sl = __builtin_ctzll(mask);
-        mask &= mask - 1;
-        Ops::accumulate(acc, un + sl * SW, L, P, Tc, kc);
-    }
-    VK_STAMP(8 + wave); // every wave's own walk end
-}
 
 // float64 grids, chunks of 32 channels, scalar / atom-wise radii: the slab body with OpsMx64 (128 registers)
 template <bool GAUSS, bool LANE_RANGE, int MAXT>
@@ -396,121 +354,19 @@ __global__ void __launch_bounds__(MAXT, (MAXT <= 512 ? 4 : 2))
 #include "mvx_slab_body.inc"
 }
 
-// The general slab loop (float64 grids that do not take voxelize64_kernel): all `total` (molecule, chunk, slab) ids,
-// grid-stride. (Until round 3 it also served the float32 overflow list.)
-template <typename Ops, int MAXT, int WPE>
-__global__ void __launch_bounds__(MAXT, WPE)
-    voxelize_dense_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ xlist,
-                          const uint2 *__restrict__ slist, const uint2 *__restrict__ slist_ext,
-                          const int64_t *__restrict__ offsets, int64_t n_one, const double *__restrict__ Tc,
-                          const float *__restrict__ kc, void *__restrict__ out, const VoxParams P, unsigned T, unsigned total) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int SW = Ops::SW;
-    constexpr int CT = Ops::CT;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NW = P.NW;
-    const int SB = NW < 4 ? NW : 4; // x-list entries per lane and scan round
-    const int LCAP = 64 * SB;
-    int *list = reinterpret_cast<int *>(smem);
-    unsigned *zr_l = reinterpret_cast<unsigned *>(smem + 4 * LCAP);
-    int *nlist_s = reinterpret_cast<int *>(smem + 8 * LCAP);
-    unsigned *un = reinterpret_cast<unsigned *>(smem + 8 * LCAP + 16);
-    const int RW = 8 * NW < 64 ? 8 * NW : 64;
-
-    for (unsigned id = blockIdx.x; id < total; id += gridDim.x) {
-        const unsigned z = id / T, t = id - z * T;
-        int b = (int)z, cc = 0;
-        if (P.ncc > 1) {
-            b = (int)z / P.ncc;
-            cc = (int)z - b * P.ncc;
-        }
-        int sx, sy, zc;
-        decode_slab(t, P, sx, sy, zc);
-        const int x0 = SUBX * sx, y0 = SUBY * sy, z0 = zc * SUBZ * NW;
-        const int zt_lo = zc * NW, zt_hi = zt_lo + NW - 1;
-        const LaneCtx L = make_lane_ctx(lane, wave, x0, y0, z0, zt_lo, cc * CT, P);
-        const uint2 *__restrict__ line = slist + ((size_t)b * T + t) * SLOTS;
-        const uint2 *__restrict__ ext = slist_ext + ((size_t)b * T + t) * EXT_SLOTS;
-        const uint2 hdr = line[0];
-        const int64_t a0 = (int64_t)hdr.y;
-        typename Ops::Acc acc;
-        Ops::zero(acc);
-        bool any = false;
-
-        if (hdr.x != LINE_OVERFLOW) {
-            // rounds of RW entries over the primary line and its extension
-            const int n_line = (int)hdr.x;
-            any = n_line > 0;
-            for (int e0 = 0; e0 <= n_line && n_line > 0; e0 += RW) {
-                if (e0 > 0) __syncthreads(); // rows of the previous round consumed
-                const int e = e0 + lane;
-                uint2 Er = make_uint2(0u, EMPTY_ENTRY);
-                if (lane < RW && e <= n_line) Er = (e < SLOTS) ? line[e] : ext[e - SLOTS];
-                line_round<Ops>(acc, Er, e0, n_line, RW, un, rec, w, a0, lane, wave, NW, L, P, Tc, kc);
-            }
-        } else {
-            // x-list path: more candidates than a line and its extension hold
-            const int64_t nmol = offsets ? offsets[b + 1] - offsets[b] : n_one;
-            const uint2 *__restrict__ xl = xlist + ((size_t)a0 + 2 * (size_t)b) * P.nsx + (size_t)sx * (size_t)(nmol + XL_HEADER);
-            const int nx = (int)xl[0].x + XL_HEADER;
-            const unsigned *src = lane < 16 ? rec + lane : w + (Ops::WORDS * L.cbase + lane - 16);
-            const size_t stride = lane < 16 ? (size_t)16 : (size_t)(Ops::WORDS * P.w_stride);
-            const bool stager = lane < 16 + Ops::WW;
-            constexpr int TAIL = 16 + Ops::WW > 64 ? 16 + Ops::WW - 64 : 0;
-            for (int base = 0; base < nx; base += LCAP) {
-                __syncthreads(); // list / candidate rows of the previous round consumed
-                if (wave == 0) { // ordered compaction of LCAP entries against the slab's y/z box
-                    int n = 0;
-                    for (int u = 0; u < SB; ++u) {
-                        const int i = base + u * 64 + lane;
-                        const uint2 en = (i < nx) ? xl[i] : make_uint2(0u, EMPTY_ENTRY);
-                        // (the two header entries carry EMPTY_ENTRY and never match)
-                        const bool m = ((int)(en.y & 0xff) <= sy) && ((int)((en.y >> 8) & 0xff) >= sy) &&
-                                       ((int)((en.y >> 16) & 0xff) <= zt_hi) && ((int)(en.y >> 24) >= zt_lo);
-                        const unsigned long long mask = __ballot(m);
-                        if (m) {
-                            const int pos = n + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-                            list[pos] = (int)en.x;
-                            zr_l[pos] = en.y;
-                        }
-                        n += __popcll(mask);
-                    }
-                    if (lane == 0) nlist_s[0] = n;
-                }
-                __syncthreads();
-                const int nl = nlist_s[0];
-                any = any || nl > 0;
-                for (int c0 = 0; c0 < nl; c0 += P.dcap) {
-                    const int n = (nl - c0) < P.dcap ? (nl - c0) : P.dcap; // rows staged this round
-                    if (c0 > 0) __syncthreads();
-                    for (int j = wave; j < n; j += NW) {
-                        if (stager) un[j * SW + lane] = src[(size_t)(a0 + list[c0 + j]) * stride];
-                        if (TAIL && lane < TAIL) // (rows wider than a wave: float64, 32 channels)
-                            un[j * SW + 64 + lane] = (w + (Ops::WORDS * L.cbase + lane + 48))[(size_t)(a0 + list[c0 + j]) * (size_t)(Ops::WORDS * P.w_stride)];
-                    }
-                    __syncthreads();
-                    for (int jb = 0; jb < n; jb += 64) {
-                        const int j = jb + lane;
-                        bool ok = false;
-                        if (j < n) {
-                            const unsigned zr = zr_l[c0 + j];
-                            ok = ((int)((zr >> 16) & 0xff) <= L.zt_w) && ((int)(zr >> 24) >= L.zt_w);
-                        }
-                        unsigned long long mask = __ballot(ok);
-                        while (mask) {
-                            const int jj = jb + __builtin_ctzll(mask);
-                            mask &= mask - 1;
-                            Ops::accumulate(acc, un + jj * SW, L, P, Tc, kc);
-                        }
-                    }
-                }
-            }
-        }
-        Ops::write(acc, any, un, tid, lane, wave, NW, b, L, x0, y0, z0, out, P);
-        __syncthreads(); // rows / tile consumed before the next slab's rows land in the union region
-    }
+// float64 grids, chunks of 1 / 4 / 8 / 16 channels, any radii: the slab body with OpsF64. One instantiation per key, compiled
+// for workgroups of up to 16 waves (the plan's slabs have at most 8; debug_option("nw") asks for more): no key needs more
+// registers for that.
+template <int CT_, bool GAUSS, bool CHANWISE, bool LANE_RANGE>
+__global__ void __launch_bounds__(1024, 1)
+    voxelize64_vec_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
+                          const uint2 *__restrict__ slist_ext, const double *__restrict__ Tc, const float *__restrict__ kc,
+                          double *__restrict__ out, const VoxParams P) {
+    typedef OpsF64<CT_, GAUSS, CHANWISE, LANE_RANGE> Ops;
+    constexpr int CT = CT_;
+    constexpr bool GROUPED = false;
+    constexpr int MAXT = 1024;
+#include "mvx_slab_body.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -521,81 +377,63 @@ struct KernelKey64 {
     bool gauss, chanwise, lane_range;
 };
 
-// Calls fn.template operator()<CT, GAUSS, CHANWISE, LANE_RANGE>() for the instantiation `k` names.
+// fn(ct constant, gauss constant, chanwise constant, lane_range constant) for the key's instantiation of the vector family, and
+// the one place that knows which exist: CT 1 / 4 / 8 / 16 x Gaussian / binary x {wave-uniform block cull, per-lane ranges,
+// channel-wise radii (always with per-lane ranges)} - 24 in all.
 template <typename Fn>
 static hipError_t for_kernel64(const KernelKey64 &k, Fn &&fn) {
-#define MVX_CASE(CT_, G_, CW_, LR_) \
-    if (k.ct == CT_ && k.gauss == G_ && k.chanwise == CW_ && k.lane_range == LR_) return fn.template operator()<CT_, G_, CW_, LR_>();
-#define MVX_CASES_CT(CT_)             \
-    MVX_CASE(CT_, true, false, false)  \
-    MVX_CASE(CT_, false, false, false) \
-    MVX_CASE(CT_, true, false, true)   \
-    MVX_CASE(CT_, false, false, true)  \
-    MVX_CASE(CT_, true, true, true)    \
-    MVX_CASE(CT_, false, true, true)
-    MVX_CASES_CT(1)
-    MVX_CASES_CT(4)
-    MVX_CASES_CT(8)
-    MVX_CASES_CT(16)
-    MVX_CASES_CT(32)
-#undef MVX_CASES_CT
-#undef MVX_CASE
+    auto width = [&](auto ct) {
+        auto density = [&](auto chanwise, auto lane_range) {
+            return k.gauss ? fn(ct, std::true_type{}, chanwise, lane_range) : fn(ct, std::false_type{}, chanwise, lane_range);
+        };
+        if (k.chanwise) return density(std::true_type{}, std::true_type{});
+        return k.lane_range ? density(std::false_type{}, std::true_type{}) : density(std::false_type{}, std::false_type{});
+    };
+    if (k.ct == 1) return width(std::integral_constant<int, 1>{});
+    if (k.ct == 4) return width(std::integral_constant<int, 4>{});
+    if (k.ct == 8) return width(std::integral_constant<int, 8>{});
+    if (k.ct == 16) return width(std::integral_constant<int, 16>{});
     return hipErrorInvalidValue;
 }
 
-template <typename Ops, int MAXT = 1024, int WPE = 1>
-static hipError_t launch_dense(const VoxArgs &a, size_t lds, unsigned grid, unsigned total, hipStream_t s) {
-    const VoxParams &p = a.p;
-    if (p.NW * 64 > MAXT) return hipErrorInvalidConfiguration;
-    return launch_kernel<voxelize_dense_kernel<Ops, MAXT, WPE>>(dim3(grid), dim3(p.NW * 64), lds, s, a.rec, a.w, a.xlist, a.slist, a.slist_ext,
-                                                                a.offsets, a.n_one, a.Tc, a.kc, a.out, a.p, (unsigned)(p.nzc * p.nsy * p.nsx), total);
-}
-
-struct Dense64Fn {
-    const VoxArgs &a;
-    hipStream_t s;
-    template <int CT, bool GAUSS, bool CHANWISE, bool LANE_RANGE>
-    hipError_t operator()() const {
-        const VoxParams &p = a.p;
-        const long long total = (long long)p.B * p.ncc * p.nzc * p.nsy * p.nsx;
-        if (total <= 0) return hipSuccess;
-        if (total > 0xffffffffll) return hipErrorInvalidConfiguration;
-        const unsigned grid = (unsigned)(total < 4096 ? total : 4096);
-        if constexpr (CT > 16) {
-            // 32 float64 accumulators per lane: 512-thread workgroups (the plan's slabs have at most 8 waves), so the
-            // kernel may use 256 VGPRs; one chunk instead of two halves the staging, distance and exp work per slab
-            if (p.NW > 8) return hipErrorInvalidValue;
-            return launch_dense<OpsF64<CT, GAUSS, CHANWISE, LANE_RANGE>, 512>(a, dense64_lds_bytes(CT, p.NW), grid, (unsigned)total, s);
-        } else {
-            return launch_dense<OpsF64<CT, GAUSS, CHANWISE, LANE_RANGE>>(a, dense64_lds_bytes(CT, p.NW), grid, (unsigned)total, s);
-        }
-    }
-};
-
-template <bool GAUSS, bool LANE_RANGE>
-static hipError_t launch_mx64(const VoxArgs &a, hipStream_t s) {
-    VoxParams p = a.p;
-    const size_t main_lds = voxelize_mx64_lds_bytes(p.NW), lds = main_lds + 512;
-    p.dcap = (int32_t)main_lds; // where the kernel keeps its copy of the 2^(j/64) table
-    const int per = 65535 / p.ncc; // molecules per launch (gridDim.y limit); the profiling bracket rides on the first launch
+// The one launch sequence of both float64 kernels: one workgroup per (slab, molecule, channel chunk), 65535 / ncc molecules per
+// launch (gridDim.y limit); the profiling bracket rides on the first launch. extra: the kernel's arguments between the lines
+// and the grid.
+template <auto Kern, typename... A>
+static hipError_t launch_slabs64(const VoxArgs &a, VoxParams p, size_t lds, hipStream_t s, A... extra) {
+    if (p.NW > 16) return hipErrorInvalidConfiguration;
+    const int per = 65535 / p.ncc;
     for (int m0 = 0; m0 < p.B; m0 += per) {
         p.b0 = m0;
         const int nb = p.B - m0 < per ? p.B - m0 : per;
-        const hipError_t e = launch_kernel<voxelize64_kernel<GAUSS, LANE_RANGE, 512>>(dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), lds, s,
-                                                                                      a.rec, a.w, a.slist, a.slist_ext, static_cast<double *>(a.out), p);
+        const hipError_t e = launch_kernel<Kern>(dim3(slab_grid_x(p), (unsigned)(nb * p.ncc)), dim3(p.NW * 64), lds, s, a.rec, a.w, a.slist,
+                                                 a.slist_ext, extra..., static_cast<double *>(a.out), p);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
+template <bool GAUSS, bool LANE_RANGE>
+static hipError_t launch_mx64(const VoxArgs &a, hipStream_t s) {
+    VoxParams p = a.p;
+    const size_t main_lds = voxelize64_lds_bytes(MX64_SW, 32, p.NW);
+    p.dcap = (int32_t)main_lds; // where the kernel keeps its copy of the 2^(j/64) table
+    return launch_slabs64<voxelize64_kernel<GAUSS, LANE_RANGE, 512>>(a, p, main_lds + 512, s);
+}
+
 hipError_t launch_voxelize64(const VoxArgs &a, int32_t ct, bool gauss, bool chanwise, bool lane_range, hipStream_t s) {
-    // chunks of 32 channels with scalar / atom-wise radii on 8-wave slabs: the matrix-core slab kernel
-    if (ct == 32 && !chanwise && a.p.NW <= 8 && a.p.dcap == 0) {
+    if (ct == 32) { // chunks of 32 channels with scalar / atom-wise radii on slabs of at most 8 waves: the matrix-core kernel
+        if (chanwise || a.p.NW > 8) return hipErrorInvalidValue;
         if (gauss) return lane_range ? launch_mx64<true, true>(a, s) : launch_mx64<true, false>(a, s);
         return lane_range ? launch_mx64<false, true>(a, s) : launch_mx64<false, false>(a, s);
     }
-    KernelKey64 k{ct, gauss, chanwise, chanwise ? true : lane_range};
-    return for_kernel64(k, Dense64Fn{a, s});
+    const KernelKey64 k{ct, gauss, chanwise, chanwise ? true : lane_range};
+    return for_kernel64(k, [&](auto ct_, auto gauss_, auto chanwise_, auto lane_range_) {
+        constexpr int CT = decltype(ct_)::value;
+        constexpr bool GAUSS = decltype(gauss_)::value, CHANWISE = decltype(chanwise_)::value, LANE_RANGE = decltype(lane_range_)::value;
+        return launch_slabs64<voxelize64_vec_kernel<CT, GAUSS, CHANWISE, LANE_RANGE>>(
+            a, a.p, voxelize64_lds_bytes(OpsF64<CT, GAUSS, CHANWISE, LANE_RANGE>::SW, CT, a.p.NW), s, a.Tc, a.kc);
+    });
 }
 
 } // namespace mvx

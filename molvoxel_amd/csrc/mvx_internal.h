@@ -87,7 +87,8 @@ struct VoxParams { // by-value kernel parameters (scalars only: pointers are sep
     uint32_t nslab;        // nsx * nsy * nzc: slabs per molecule (the kernels' line index; not gridDim.x - an implicit argument, one more
                            // scalar round trip in front of the line's header)
     int32_t w_stride;      // floats between the channel weights of consecutive atoms
-    int32_t dcap;          // candidate rows staged per round
+    int32_t dcap;          // set by the launcher: bytes of the rows / tile region in LDS, where the kernel's table starts (grouped launches,
+                           // float64 matrix-core kernel); voxelize_pair_kernel: atoms per wave and segment
     int32_t vec_store;     // D % 4 == 0 and out 16-B aligned
     int32_t pace;          // 1: empty slabs hold their stores back ~1.7 us (launches of more than 4096 workgroups); 2: light slabs pace their write-out rounds too (>= 49 152)
     int32_t xcd_ranges;    // 1: every XCD takes a contiguous range of slabs (run-wise write-out of whole-row slabs; gridDim.x = 8 ceil(T / 8))
@@ -123,11 +124,8 @@ struct ChanGroups {
 struct VoxArgs {
     const unsigned *rec;   // per-atom records (16 words each)
     const unsigned *w;     // channel weights: the caller's feature rows or prep's packed copy (p.w_stride apart)
-    const uint2 *xlist;    // x-slab lists (xbin_kernel)
     const uint2 *slist;    // per-slab candidate lines (xbin_kernel), SLOTS entries each
     const uint2 *slist_ext; // their extensions (entries 64..255), EXT_SLOTS entries each
-    const int64_t *offsets; // device copy of the batch offsets (x-list path only), or null: one molecule of n_one atoms
-    int64_t n_one;
     const double *Tc;      // channel-wise features: per-channel d2 thresholds (float64 grids: the radii themselves)
     const float *kc;       //                        per-channel gaussian coefficients
     void *out;             // (B, C, D, D, D) float, or double for float64 grids, or bfloat16 (bf16)
@@ -156,7 +154,8 @@ hipError_t launch_voxelize(const VoxArgs &a, int32_t nb, int32_t ct, bool gauss,
 // channel-wise features, grouped by radius: a.Tc must point at the chunks' ChanGroups tables, a.kc at the channels' slots;
 // chunks of 32 channels (a.p.ncc = ceil(C / 32)), feature rows read in place
 hipError_t launch_voxelize_grouped(const VoxArgs &a, int32_t nb, bool gauss, bool lane_range, hipStream_t s);
-// float64 grids: every slab of the whole batch through the general slab loop (ct <= 16; a.p.dcap must be 64)
+// float64 grids, the whole batch: ct == 32 (scalar / atom-wise radii, a.p.NW <= 8) takes the matrix-core kernel, ct 1 / 4 / 8 / 16
+// the vector kernels
 hipError_t launch_voxelize64(const VoxArgs &a, int32_t ct, bool gauss, bool chanwise, bool lane_range, hipStream_t s);
 // the whole call in one launch (voxelize_pair_kernel, mvx_pair.hip: float32 grids, NW <= 8): no workspace, no pre-pass.
 // max_atoms: the largest molecule of the call (sizes the per-wave candidate lists); lane_range: sub-tiles cut by reference blocks
@@ -173,6 +172,5 @@ hipError_t set_diag_buffer_xb(void *p);
 #endif
 size_t voxelize_lds_bytes(int32_t ct, int32_t NW, int32_t crmax);
 size_t voxelize_mx_lds_bytes(int32_t NW); // the matrix-core kernels: rows of two rounds or the write-out tile of eight channels, whichever is larger
-int32_t voxelize_dcap(int32_t ct, int32_t NW);
 
 } // namespace mvx

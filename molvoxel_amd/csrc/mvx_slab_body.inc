@@ -1,7 +1,7 @@
 // mvx_slab_body.inc - one workgroup = one slab: the body shared by voxelize_kernel / voxelize_runs_kernel (float32 grids,
-// 64 registers, four 8-wave workgroups per compute unit) and voxelize64_kernel (float64 grids on the matrix cores, 128
-// registers, two). Included inside the kernel definitions, which provide: the type Ops, the constants CT, GROUPED, MAXT and
-// the kernel parameters rec, w, slist, slist_ext, Tc, kc, out, P.
+// 64 registers, four 8-wave workgroups per compute unit), voxelize64_kernel (float64 grids on the matrix cores, 128
+// registers, two) and voxelize64_vec_kernel (float64 grids on the vector ALU). Included inside the kernel definitions, which
+// provide: the type Ops, the constants CT, GROUPED, MAXT and the kernel parameters rec, w, slist, slist_ext, Tc, kc, out, P.
 // (Textual inclusion, not a __device__ function: with the body in an inlined function template the per-lane-range
 // 32-channel variant kept its accumulators in scratch - 193 spilled registers against 4 - whatever the parameter passing.)
     extern __shared__ __attribute__((aligned(16))) char smem[];

@@ -301,9 +301,9 @@ def big_host_plan(case: Big) -> dict:
 
 
 def big_cut_points(case: Big, plan: dict) -> list:
-    """First molecules of the launches a call is cut into. float32: chunk_begin of the plan's chunks. float64 matrix-core:
-    launch_mx64's own loop, 65535 // ncc molecules per launch. float64 dense: one grid-stride launch - the molecules at which
-    (molecule, chunk) ids cross 65 535 stand in for a cut."""
+    """First molecules of the launches a call is cut into. float32: chunk_begin of the plan's chunks. float64, either kernel:
+    launch_slabs64's own loop, 65535 // ncc molecules per launch (the vector kernels' rows also keep the molecule after the
+    first cut, from when they were one launch whose (molecule, chunk) ids crossed 65 535 there)."""
     if plan["route"] == F64_MX or plan["route"] == F64_DENSE:
         per = GRID_Y_MAX // plan["ncc"]
         return [k * per for k in range(1, -(-case.B // per))] + ([per + 1] if plan["route"] == F64_DENSE else [])

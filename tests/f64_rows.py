@@ -75,7 +75,7 @@ class Row:
 
     @property
     def ncc16(self) -> int:
-        """Channel chunks of the same call under debug_option("max_ct64", 16): the general slab loop, 16 channels per chunk."""
+        """Channel chunks of the same call under debug_option("max_ct64", 16): the vector kernels, 16 channels per chunk."""
         return -(-self.C // 16)
 
 
@@ -88,7 +88,7 @@ def _r(geom, C, route, ct, ncc, mode="features", radii="scalar", density="gaussi
 
 DN, MX = F64_DENSE, F64_MX
 ROWS = [
-    # ---- general slab loop, scalar / atom-wise radii, wave-uniform block cull: OpsF64<CT, GAUSS, false, false> -----------------------
+    # ---- vector kernels, scalar / atom-wise radii, wave-uniform block cull: OpsF64<CT, GAUSS, false, false> --------------------------
     _r("A", 1, DN, 1, 1, batch=True),
     _r("B", 1, DN, 1, 1, mode="single", radii="atom-wise", density="binary"),
     _r("C", 4, DN, 4, 1, mode="types", batch=True),
@@ -118,7 +118,7 @@ ROWS = [
     # (several chunks: the last chunk's channels are clamped at C - 1)
     _r("B", 40, DN, 16, 3, radii="channel-wise"),
     _r("A", 17, DN, 16, 2, radii="channel-wise", density="binary", blockdim=5, lane_range=1),
-    # ---- matrix-core kernel: voxelize64_kernel<GAUSS, false> (each again as the general slab loop with ncc 2 ... 4) -------------------------
+    # ---- matrix-core kernel: voxelize64_kernel<GAUSS, false> (each again through the vector kernels with ncc 2 ... 4) ---------------------
     _r("A", 32, MX, 32, 1, batch=True),
     _r("B", 17, MX, 32, 1, radii="atom-wise", batch=True),
     _r("C", 33, MX, 32, 2, batch=True),

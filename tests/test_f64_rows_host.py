@@ -4,7 +4,7 @@
 * its molecule reaches the line form it names - one round, extension line, x-list, an x-list beyond xbin_kernel's LDS copy - by
   two host-side bounds on the candidates per slab, so that neither a plan change nor a thinner geometry can empty the sweep;
 * every instantiation for_kernel64 / launch_mx64 can reach has a row on a geometry that leaves the one-round case;
-* ct = 32 comes with the matrix-core route only (why OpsF64<32, ...> cannot be reached).
+* ct = 32 comes with the matrix-core route only (why there is no OpsF64<32, ...>).
 """
 import itertools
 
@@ -118,9 +118,8 @@ def test_the_bounds_bracket_a_brute_force_count():
 
 
 def test_chunks_of_32_channels_come_with_the_matrix_core_route_only():
-    """OpsF64<32, ...> (the staging of rows wider than a wave in the general slab loop) is compiled but not reached: the plan
-    gives ct = 32 at precision 64 only on the matrix-core route, whose slabs have at most 8 waves (launch_voxelize64 then takes
-    launch_mx64: not channel-wise, NW <= 8, dcap = 0)."""
+    """There is no OpsF64<32, ...> (for_kernel64 names CT 1 / 4 / 8 / 16 only): the plan gives ct = 32 at precision 64 only on the
+    matrix-core route, whose slabs have at most 8 waves (launch_voxelize64 then takes launch_mx64: not channel-wise, NW <= 8)."""
     n32 = 0
     for D, C_, radii, mode, bd in itertools.product((5, 16, 24, 33, 64, 72, 130, 1020), (1, 4, 16, 17, 32, 33, 64, 200),
                                                     ("scalar", "atom-wise", "channel-wise"), ("features", "types"), (8, 5)):

@@ -12,8 +12,9 @@ one family writes a plausible grid of the wrong molecule or leaves channels stal
 3. the call really was cut: last_plan() (mvx_debug_last_plan: the plan the call took, debug options applied) has the expected
    nchunk >= 2 and the row's family fields, and with profiling on read_kernel_times_ms() has one entry per voxelize launch -
    nchunk * (1 + remainder launch) on the float32 binned route, which must exceed the uncut run's. A float64 call times ONE
-   bracket whatever its cut (the dense kernel is one grid-stride launch behind all pre-passes; launch_mx64's bracket rides on its
-   first launch only), so the profile hook cannot count float64 cuts: there the test asserts the one entry and the plan's nchunk.
+   bracket whatever its cut (both float64 kernels launch behind all pre-passes, 65535 // ncc molecules per launch, and the bracket
+   rides on the first launch only), so the profile hook cannot count float64 cuts: there the test asserts the one entry and the
+   plan's nchunk.
 
 Before every cut call the same handle voxelizes a mirrored copy of the batch, so the workspace holds another batch's candidate
 lines of the same shape: a pre-pass that fills the wrong molecules' lines leaves wrong, never uninitialised, data behind.

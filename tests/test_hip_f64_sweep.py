@@ -1,12 +1,13 @@
 """The float64 forward kernels (precision = 64, mvx_f64.hip) swept the way the float32 ones are.
 
-The float64 path is separate text - its own walk (OpsF64, OpsMx64 on v_mfma_f64_16x16x4_f64), its own exp, its own write-out
-tile, and in voxelize_dense_kernel its own decode of (molecule, chunk, slab) and its own compaction of long x-lists - and no other
-route gives the same bits, so nothing cross-checks it for free. Here:
+The float64 kernels share the slab body of the float32 ones (mvx_slab_body.inc) but bring their own walks (OpsF64 on the vector
+ALU, OpsMx64 on v_mfma_f64_16x16x4_f64), their own exp and their own write-out tile - and no other route gives the same bits, so
+nothing cross-checks them for free. Here:
 
 * test_row / test_row_in_a_batch: every instantiation the dispatch can reach (tests/f64_rows.py; tests/test_f64_rows_host.py proves
   on the host that each row reaches its kernel and its line form: one round, extension line, x-list, x-list beyond 1024 entries,
   rows cut along z, misaligned odd grids), alone and as molecule 1 of a ragged batch, device and host staging;
+* test_nine_waves_per_slab: a row of nine z sub-tiles in one slab (the "nw" knob), bit for bit the 8 + 1 cut of the plan;
 * the fuzz draws of tests/test_hip_fuzz.py at precision 64: 64 configurations, 16 with the in-call random transform, 24 batches;
 * exp_nonpos64 and the library's exp against exact values, down to subnormal results and underflow.
 
@@ -68,7 +69,7 @@ def _assert_routes_agree(mx, dense, what):
     assert np.array_equal(mx != 0, dense != 0), what
     d = float((np.abs(mx - dense) / np.maximum(1.0, np.abs(mx))).max()) if mx.size else 0.0
     print(f"f64-sweep route-diff {what} {d:.3g}")
-    assert d <= ROUTE_TOL, f"{what}: matrix-core and general slab loop differ by {d:.3g} relative"
+    assert d <= ROUTE_TOL, f"{what}: matrix-core and vector kernels differ by {d:.3g} relative"
 
 
 def _device_inputs(v, mol, mode):
@@ -108,7 +109,7 @@ def test_row(row):
     _assert_bars(first.cpu().numpy(), ref, exact, row.id)
     grid.fill_(3.0)
     assert torch.equal(v.forward(coords, None, chan, radii, out_grid=grid), first), "two runs of the same call differ"
-    if row.route == R.F64_MX:  # the same call through the general slab loop: 16 channels per chunk, the library's exp
+    if row.route == R.F64_MX:  # the same call through the vector kernels: 16 channels per chunk, the library's exp
         v.debug_option("max_ct64", 16)
         grid.fill_(5.0)
         dense = v.forward(coords, None, chan, radii, out_grid=grid)
@@ -155,6 +156,40 @@ def test_row_in_a_batch(row):
     hgrid.fill(7.0)
     hout = vh.forward_batch(xyz, batch["offsets"], batch["centers"], chan, radii, num_channels=row.nch, out_grid=hgrid)
     assert hout is hgrid and np.array_equal(hout, out.cpu().numpy()), row.id
+
+
+# ---- b2. slabs of more than 8 waves: the rows of a round are staged by waves 0 ... 7 alone ---------------------------------------------------
+@pytest.mark.parametrize("C_, radii_type, density, blockdim", [(4, "scalar", "gaussian", None), (16, "channel-wise", "binary", 12)],
+                         ids=["C4-scalar-gaussian", "C16-channel-wise-binary-bd12"])
+def test_nine_waves_per_slab(C_, radii_type, density, blockdim):
+    """D = 72 is nine z sub-tiles: the plan cuts a row 8 + 1; debug_option("nw", 9) keeps it in one slab of nine waves, which the
+    rows above (nw <= 8) never launch. Geometry B's blob (600 atoms, radius 2.0) puts more than 63 candidates on its central slabs,
+    so they take several rounds, each staged by eight of the nine waves. Same candidates in the same order either way: the two
+    cuts must give the same bits."""
+    import torch
+
+    D, radius = 72, R.GEOMS["B"].radius
+    xyz = R.positions("B")
+    n = xyz.shape[0]
+    rng = np.random.default_rng(72_009 + C_)
+    chan = rng.random((n, C_))
+    radii = radius
+    if radii_type == "channel-wise":
+        radii = radius * rng.uniform(0.8, 1.0, C_)
+        radii[C_ // 2] = radius
+    lower = R.slab_counts(xyz, np.full(n, radius), D, 9, blockdim)[0]
+    assert lower.max() > R.ONE_ROUND, int(lower.max())
+    v = _voxelizer(D, radii_type, density, R.SIGMA, blockdim, "torch")
+    coords, d_chan = v.asarray(xyz, "coords"), v.asarray(chan, "features")
+    d_radii = radii if np.isscalar(radii) else v.asarray(radii, "radii")
+    cut = v.forward(coords, None, d_chan, d_radii, out_grid=v.get_empty_grid(C_).fill_(7.0)).clone()
+    assert _plan_of(v, ("route", "ct", "nw", "nzc")) == dict(route=R.F64_DENSE, ct=C_, nw=8, nzc=2), v.last_plan()
+    v.debug_option("nw", 9)
+    whole = v.forward(coords, None, d_chan, d_radii, out_grid=v.get_empty_grid(C_).fill_(3.0))
+    assert _plan_of(v, ("route", "ct", "nw", "nzc")) == dict(route=R.F64_DENSE, ct=C_, nw=9, nzc=1), v.last_plan()
+    assert torch.equal(whole, cut), "nine waves per slab and the 8 + 1 cut differ"
+    ref = _ref(D, blockdim, xyz, chan, radii, radii_type, density, C_)
+    _assert_bars(whole.cpu().numpy(), ref, False, f"nw9-C{C_}-{radii_type}-{density}")
 
 
 # ---- c. the fuzz draws at precision 64 --------------------------------------------------------------------------------------------------------------

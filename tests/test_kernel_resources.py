@@ -74,6 +74,25 @@ def test_float64_matrix_core_kernel_keeps_two_workgroups_per_unit(res):
         assert res[name]["scratch"] == 0, (name, res[name])
 
 
+def test_float64_vector_kernels_are_one_family_over_the_slab_body(res):
+    """voxelize64_vec_kernel<CT, GAUSS, CHANWISE, LANE_RANGE>: CT 1 / 4 / 8 / 16 x Gaussian / binary x {plain, lane ranges,
+    channel-wise + lane ranges}, one 1024-thread instantiation each. No scratch; registers at most the occupancy step the widest
+    key of each width sits on (measured maxima 56 / 64 / 74 / 91), each at or above the occupancy of the grid-stride kernel these
+    replaced (its worst: 66 / 82 / 94 / 109 registers). That kernel and its never-launched 32-channel instantiations are gone."""
+    assert not [k for k in res if "voxelize_dense_kernel" in k]
+    ks = {k: v for k, v in res.items() if k.startswith("voxelize64_vec_kernel<")}
+    assert len(ks) == 24
+    budget = {1: 64, 4: 64, 8: 80, 16: 96}
+    for ct in budget:
+        for gauss in ("true", "false"):
+            for tail in ("false, false", "false, true", "true, true"):  # <CHANWISE, LANE_RANGE>
+                assert f"voxelize64_vec_kernel<{ct}, {gauss}, {tail}>" in ks
+    for name, r in ks.items():
+        ct = int(name.split("<")[1].split(",")[0])
+        assert r["scratch"] == 0 and r["vspill"] == 0, (name, r)
+        assert r["vgpr"] <= budget[ct], (name, r)
+
+
 def test_prepass_kernels_do_not_spill_vector_registers(res):
     assert res["prep_kernel"]["vspill"] == 0 and res["prep_kernel"]["scratch"] == 0
     for name, r in res.items():
