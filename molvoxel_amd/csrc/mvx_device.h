@@ -717,10 +717,15 @@ __device__ __forceinline__ void store_runs(const OT *tile, const RunLayout &R, i
 // RUNS: the kernel also serves grids whose rows are not whole 16-byte quads (store_runs). Compiled into the per-lane-range
 // kernels and the run-wise kernels (voxelize_runs_kernel, voxelize_pair_runs_kernel) only: the aligned-grid kernels keep their
 // register budget. OT: grid element type (store_q); a bfloat16 grid's run-wise path keeps a bfloat16 tile (store_runs).
-template <int CT, bool RUNS, int CRMAX = CR_F32, typename OT = float>
-__device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], bool any, float *tile, int tid, int lane,
+// NSUB: accumulator sets per wave (voxelize_narrow_kernel: wave w holds sub-tiles NSUB w ... NSUB w + NSUB - 1 of the slab's NW,
+// acc[s] the set of sub-tile NSUB w + s; a single set is passed as &acc). The workgroup then has NW / NSUB waves: a read-back pass
+// covers 32 / NSUB tile rows, i.e. CPP = 4 / NSUB channels.
+template <int CT, bool RUNS, int CRMAX = CR_F32, typename OT = float, int NSUB = 1>
+__device__ __forceinline__ void write_slab(const float2v (*acc)[(CT + 1) / 2], bool any, float *tile, int tid, int lane,
                                            int wave, int NW, int b, int cbase, int x0, int y0, int z0, OT *out,
                                            const VoxParams &P) {
+    static_assert(NSUB == 1 || ((NSUB == 2 || NSUB == 4) && !RUNS), "read-back passes of whole channels; store_runs: one set per wave");
+    constexpr int CPP = 32 / NSUB / RPC; // channels per read-back pass
     constexpr int G = 16 / sizeof(OT); // elements per 16-byte group (run-wise path)
     constexpr int CR = CT < CRMAX ? CT : CRMAX; // channels per write-out round
     constexpr int NROUND = CT / CR;
@@ -728,7 +733,7 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
     const int RS = row_stride_floats(NW);
     const size_t D2 = (size_t)D * D, D3 = D2 * D;
     const int F4 = (SUBZ / 4) * NW; // float4 slots per row
-    // row of this thread in pass 0 (rows advance by 4 channels = 4*RPC rows per pass) and its float4 slot inside the row.
+    // row of this thread in pass 0 (rows advance by CPP channels = CPP * RPC rows per pass) and its float4 slot inside the row.
     // (tid / F4 by a float reciprocal: (tid + 0.5) / F4 lies at least 1 / 64 away from every integer for tid < 1024, F4 <= 32 -
     // the integer division by a run-time value is ~40 instructions per wave)
     const int rfirst = (int)(((float)tid + 0.5f) * __frcp_rn((float)F4));
@@ -751,20 +756,20 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
         }
         if (vox_ok) {
 #pragma unroll
-            for (int p = 0; p < (CT + 3) / 4; ++p) {
-                const int c = cfirst + 4 * p;
-                if (c < CT && cbase + c < P.C) store_q(dst0 + (size_t)(4 * p) * D3, make_float4(0.f, 0.f, 0.f, 0.f));
-                // ... and the fill itself goes out in pieces of two store instructions (16 KB per workgroup) ~1300 cycles
+            for (int p = 0; p < (CT + CPP - 1) / CPP; ++p) {
+                const int c = cfirst + CPP * p;
+                if (c < CT && cbase + c < P.C) store_q(dst0 + (size_t)(CPP * p) * D3, make_float4(0.f, 0.f, 0.f, 0.f));
+                // ... and the fill itself goes out in pieces of eight channels (two store instructions, 16 KB per workgroup) ~1300 cycles
                 // apart, like the write-out rounds of OpsMx32::write: ligand batches 6.55 -> 6.83 TB/s (0.85 of peak;
                 // 512 / 1024 / 1536 / 2048 cycles: +2 / +3.5 / +4.3 / +3.6 %; with a first wait of 2048 instead of 4096
                 // cycles: -1 / +1 %)
-                if (P.pace && (p & 1) && p + 1 < (CT + 3) / 4) __builtin_amdgcn_s_sleep(pacing<OT>::empty_split);
+                if (P.pace && ((p + 1) * CPP) % 8 == 0 && p + 1 < (CT + CPP - 1) / CPP) __builtin_amdgcn_s_sleep(pacing<OT>::empty_split);
             }
         }
         return;
     }
     const int lz = lane & (SUBZ - 1), ly = (lane >> SUBZ_SH) & (SUBY - 1), lx = lane >> (SUBZ_SH + SUBY_SH);
-    const int col = SUBZ * wave + lz;
+    const int col = SUBZ * NSUB * wave + lz; // (of set 0; set s: SUBZ * s further)
     const int rxy = lx * SUBY + ly;
     if (RUNS && !P.vec_store) { // rows that are not whole 16-byte quads: the tile holds the slab's runs as they lie in memory (store_runs)
         const RunLayout R = run_layout<G>(NW, x0, y0, z0, P);
@@ -781,7 +786,7 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
 #pragma unroll
                 for (int c = 0; c < CR; ++c) {
                     const int cg = rd * CR + c;
-                    rtile[L0 + c * R.SC + mine] = (OT)((cg & 1) ? acc[cg / 2].y : acc[cg / 2].x);
+                    rtile[L0 + c * R.SC + mine] = (OT)((cg & 1) ? acc[0][cg / 2].y : acc[0][cg / 2].x);
                 }
             }
             __syncthreads();
@@ -795,19 +800,19 @@ __device__ __forceinline__ void write_slab(const float2v (&acc)[(CT + 1) / 2], b
         if (rd == 0) VK_STAMP(4); // every wave's walk is done
         if (rd == 1) VK_STAMP(5); // round 0 transposed and its stores issued
 #pragma unroll
-        for (int c = 0; c < CR; ++c) {
-            const int cg = rd * CR + c;
-            const float v = (cg & 1) ? acc[cg / 2].y : acc[cg / 2].x;
-            tile[(c * RPC + rxy) * RS + col] = v;
+        for (int i = 0; i < NSUB * CR; ++i) { // (one loop over sets and channels: a loop of one trip around the channels' is not free)
+            const int s = i / CR, c = i % CR, cg = rd * CR + c;
+            const float v = (cg & 1) ? acc[s][cg / 2].y : acc[s][cg / 2].x;
+            tile[(c * RPC + rxy) * RS + col + SUBZ * s] = v;
         }
         __syncthreads();
         if (vox_ok) {
 #pragma unroll
-            for (int p = 0; p < (CR + 3) / 4; ++p) {
-                const int c = cfirst + 4 * p; // channel inside the round
+            for (int p = 0; p < (CR + CPP - 1) / CPP; ++p) {
+                const int c = cfirst + CPP * p; // channel inside the round
                 if (c < CR && cbase + rd * CR + c < P.C) {
-                    const float4 v = *reinterpret_cast<const float4 *>(tile + (rfirst + 4 * RPC * p) * RS + 4 * q);
-                    store_q(dst0 + (size_t)(rd * CR + 4 * p) * D3, v);
+                    const float4 v = *reinterpret_cast<const float4 *>(tile + (rfirst + CPP * RPC * p) * RS + 4 * q);
+                    store_q(dst0 + (size_t)(rd * CR + CPP * p) * D3, v);
                 }
             }
         }
@@ -845,6 +850,7 @@ template <int CT_, bool GAUSS, bool LANE_RANGE, typename OT = float>
 struct OpsF32 {
     static constexpr bool RUNS = LANE_RANGE; // carries the run-wise write-out (store_runs)
     static constexpr int CT = CT_;
+    static constexpr int NSUB = 1; // sub-tiles (accumulator sets) per wave
     static constexpr bool GROUPED = false;
     static constexpr bool VSTAGE = false;
     static constexpr bool PRESTAGE = false;
@@ -878,7 +884,7 @@ struct OpsF32 {
         if constexpr (grid_elem<OT>::NDHWC)
             write_ndhwc<CT>(acc, lane, wave, b, L.cbase, x0, y0, z0, static_cast<typename grid_elem<OT>::type *>(out), P);
         else
-            write_slab<CT, LANE_RANGE, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0,
+            write_slab<CT, LANE_RANGE, CR_F32, OT>(&acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0,
                                                    z0, static_cast<OT *>(out), P);
     }
 };
@@ -1062,11 +1068,16 @@ __device__ __forceinline__ void stage_first_rounds(const uint2 *__restrict__ lin
 // none of stage_round's scalar work (eight s_loads, eight 64-bit scalar multiply-adds, the per-slot branches): the narrow
 // launches are bound by the compute unit's one scalar unit, not - like the 32-channel kernel, which keeps the scalar path -
 // by a vector memory pipeline full of stores.
+// NWV: the workgroup's waves, which share the round's RW = min(8 NW, 64) rows. With one sub-tile per wave (NWV = NW) a lane's
+// four slots are the round; with Ops::NSUB sub-tiles per wave a trip takes eight (eight row loads in flight), which is the round
+// for NSUB = 2 and half of it for NSUB = 4.
 template <typename Ops, bool BIG>
 __device__ __forceinline__ void stage_round_v(const uint2 *__restrict__ line, const uint2 *__restrict__ ext, int e0, int n_line,
                                               unsigned *un, const unsigned *__restrict__ rec, const unsigned *__restrict__ w, int64_t a0,
-                                              int lane, int wave, int NW, const LaneCtx &L, const VoxParams &P) {
+                                              int lane, int wave, int NWV, int RW, const LaneCtx &L, const VoxParams &P) {
     constexpr int SW = Ops::SW;
+    constexpr int U = Ops::NSUB == 1 ? 4 : 8;  // slots per lane and trip: a trip covers 2 U NWV rows
+    constexpr bool ONE_TRIP = Ops::NSUB <= 2;  // ... and 2 U NWV >= RW
     const int e = e0 + lane;
     int ai = 0;
     if (e >= 1 && e <= n_line) ai = (int)(e < SLOTS ? line[e].x : ext[e - SLOTS].x);
@@ -1079,48 +1090,64 @@ __device__ __forceinline__ void stage_round_v(const uint2 *__restrict__ line, co
     // a dump row behind the 64 rows of a round (the launcher allocates it) - eight exec-mask branches per wave before
     const int lo = (1 - e0) > 0 ? (1 - e0) : 0, hi = (n_line - e0) < 63 ? (n_line - e0) : 63;
     const unsigned span = (unsigned)(hi - lo);
-    unsigned a[4], v[4];
-    int slot[4];
-    int sl = wave + NW * half; // this lane's row slot <-> entry e0 + sl
+    int sl = wave + NWV * half; // this lane's row slot <-> entry e0 + sl
+    int left = RW;              // rows of the round not yet covered
+    do {
+        unsigned a[U], v[U];
+        int slot[U];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const unsigned ar = (unsigned)__builtin_amdgcn_ds_bpermute(4 * sl, ai); // (slots beyond the round read some other lane's entry: masked)
-        const bool in = (unsigned)(sl - lo) <= span;
-        a[u] = in ? ar : 0u;
-        slot[u] = in ? sl : 64;
-        sl += 2 * NW;
-        asm volatile("" : "+v"(sl)); // (one add per slot instead of a quarter-rate multiply)
-    }
-    if (used) {
+        for (int u = 0; u < U; ++u) { // (every lane takes part: ds_bpermute reads nothing from a masked-off source lane)
+            const unsigned ar = (unsigned)__builtin_amdgcn_ds_bpermute(4 * sl, ai); // (slots beyond the round read some other lane's entry: masked)
+            const bool in = (unsigned)(sl - lo) <= span;
+            a[u] = in ? ar : 0u;
+            slot[u] = in ? sl : 64;
+            sl += 2 * NWV;
+            asm volatile("" : "+v"(sl)); // (one add per slot instead of a quarter-rate multiply)
+        }
+        if (used) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = base[(size_t)(first + a[u]) * stride];
+            for (int u = 0; u < U; ++u) v[u] = base[(size_t)(first + a[u]) * stride];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) un[slot[u] * SW + wd] = v[u];
-    }
+            for (int u = 0; u < U; ++u) un[slot[u] * SW + wd] = v[u];
+        }
+    } while (!ONE_TRIP && (left -= 2 * U * NWV) > 0);
 }
 
 // One lane per staged row decides whether this wave walks it; then the walk. xl (workgroup-uniform, rare): the entries
 // come from a (molecule, x-slab) list instead of a slab line (LINE_OVERFLOW slabs, below): they have not been filtered
-// against the slab's y rows, so the row filter also tests the record's admitted y range.
-template <typename Ops>
+// against the slab's y rows, so the row filter also tests the record's admitted y range. L is the context of the wave's first
+// sub-tile; Ops::NSUB > 1: acc holds one accumulator set per sub-tile, filtered and walked one after the other.
+// (S: the sub-tile's turn. A compile-time recursion, not a loop: a loop of one trip around this body changed the register
+// allocation of every kernel that has one sub-tile per wave.)
+template <typename Ops, int S = 0>
 __device__ __forceinline__ void filter_walk(const bool xl, typename Ops::Acc &acc, int e0, int n_line, int RW, const unsigned *un,
                                             int lane, int wave, const LaneCtx &L, const VoxParams &P, const double *__restrict__ Tc,
                                             const float *__restrict__ kc) {
     constexpr int SW = Ops::SW;
+    LaneCtx Lz; // sub-tile S > 0: same x and y, SUBZ * S voxels further along z
+    if constexpr (S > 0) {
+        Lz = L;
+        Lz.zt_w = L.zt_w + S;
+        Lz.iz = L.iz + SUBZ * S;
+        Lz.gz = (double)Lz.iz * P.res - P.half;
+    }
+    const LaneCtx &Ls = S > 0 ? Lz : L;
     bool ok = false;
     if (lane < RW && e0 + lane >= 1 && e0 + lane <= n_line) {
         const unsigned *r = un + lane * SW;
         const unsigned zr = r[12];
-        ok = ((int)((zr & 0xffff) >> SUBZ_SH) <= L.zt_w) && ((int)((zr >> 16) >> SUBZ_SH) >= L.zt_w);
-        if constexpr (Ops::CULL) ok = ok && reaches_subtile(r, lane, L, P);
+        ok = ((int)((zr & 0xffff) >> SUBZ_SH) <= Ls.zt_w) && ((int)((zr >> 16) >> SUBZ_SH) >= Ls.zt_w);
+        if constexpr (Ops::CULL) ok = ok && reaches_subtile(r, lane, Ls, P);
         if (xl) {
             const unsigned yr = r[11];
             const int sy = L.iy >> SUBY_SH; // (the slab's y index: the same for every lane)
             ok = ok && ((int)((yr & 0xffff) >> SUBY_SH) <= sy) && ((int)((yr >> 16) >> SUBY_SH) >= sy);
         }
     }
-    Ops::walk(acc, __ballot(ok), un, lane, L, P, Tc, kc);
-    VK_STAMP(8 + wave); // every wave's own walk end
+    if constexpr (Ops::NSUB == 1) Ops::walk(acc, __ballot(ok), un, lane, Ls, P, Tc, kc);
+    else Ops::walk(acc[S], __ballot(ok), un, lane, Ls, P, Tc, kc);
+    if constexpr (S + 1 < Ops::NSUB) filter_walk<Ops, S + 1>(xl, acc, e0, n_line, RW, un, lane, wave, L, P, Tc, kc);
+    else VK_STAMP(8 + wave); // every wave's own walk end
 }
 
 // ------------------------------------------------------------------------------------------------

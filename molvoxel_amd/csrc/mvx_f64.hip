@@ -153,6 +153,7 @@ template <bool GAUSS, bool LANE_RANGE>
 struct OpsMx64 {
     static constexpr bool RUNS = false;
     static constexpr int CT = 32;
+    static constexpr int NSUB = 1;
     static constexpr bool GROUPED = false;
     static constexpr bool VSTAGE = false;
     static constexpr bool CULL = true;
@@ -303,6 +304,7 @@ template <int CT_, bool GAUSS, bool CHANWISE, bool LANE_RANGE>
 struct OpsF64 {
     static constexpr bool RUNS = false;
     static constexpr int CT = CT_;
+    static constexpr int NSUB = 1;
     static constexpr bool GROUPED = false;
     static constexpr bool VSTAGE = false;
     static constexpr bool CULL = false; // (every wave walks the rows whose z range meets its sub-tile, hit or not)

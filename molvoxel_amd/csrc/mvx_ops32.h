@@ -33,6 +33,7 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 template <bool GAUSS, bool LANE_RANGE, bool GROUPED_ = false, bool RUNS_ = LANE_RANGE, typename OT = float>
 struct OpsMx32 {
     static constexpr int CT = 32;
+    static constexpr int NSUB = 1; // sub-tiles (accumulator sets) per wave
     static constexpr bool RUNS = RUNS_; // carries the run-wise write-out (store_runs)
     static constexpr bool GROUPED = GROUPED_;
     static constexpr bool VSTAGE = false;
@@ -182,7 +183,7 @@ struct OpsMx32 {
         }
         if (!any) { // zero fill without the LDS round trip: the one-voxel-per-lane code (no accumulator is read)
             float2v zero[16];
-            write_slab<32, RUNS, CR_F32, ET>(zero, false, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0, out, P);
+            write_slab<32, RUNS, CR_F32, ET>(&zero, false, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0, out, P);
             return;
         }
         float *tile = reinterpret_cast<float *>(un);
@@ -280,9 +281,12 @@ struct OpsMx32 {
 // fma(0, w, acc) = acc). Its rows (<= 32 words) are staged two per load instruction with addresses formed on the
 // vector ALU (stage_round_v): the eight scalar index loads and 64-bit scalar address computations per wave were
 // half of the scalar instructions.
-template <int CT_, bool GAUSS, bool RUNS_ = false, typename OT = float>
+// NSUB_ > 1 (voxelize_narrow_kernel): the wave serves NSUB consecutive sub-tiles of the slab, one accumulator set each - one
+// prologue, one share of the staging, one write-out for NSUB walks (filter_walk takes the sets in turn).
+template <int CT_, bool GAUSS, bool RUNS_ = false, typename OT = float, int NSUB_ = 1>
 struct OpsPair {
     static constexpr int CT = CT_;
+    static constexpr int NSUB = NSUB_;
     static constexpr bool RUNS = RUNS_; // carries the run-wise write-out (store_runs): the per-molecule kernel and voxelize_pair_runs_kernel
     static constexpr bool GROUPED = false;
     static constexpr bool VSTAGE = true;
@@ -291,31 +295,40 @@ struct OpsPair {
     // 1-2 of a wave's ~8 candidates at 17 (Gaussian) or 12 (binary) instructions each - same box, culled -> not culled,
     // kernel: forward_single 0.121 -> 0.118 ms, 8 types 0.173 -> 0.167, cfg-3 x 256 0.238 -> 0.217 (profiles/r04_narrow.txt)
     static constexpr bool CULL = false;
-    typedef float2v Acc[(CT + 1) / 2];
+    typedef float2v Set[(CT + 1) / 2];
+    typedef typename std::conditional<NSUB == 1, Set, Set[NSUB]>::type Acc;
+    template <typename A> // (Acc | const Acc)
+    static __device__ __forceinline__ auto sets(A &acc) { // the sets as rows, one or several
+        if constexpr (NSUB == 1) return &acc;
+        else return &acc[0];
+    }
     static constexpr int WORDS = 1;
     static constexpr int WW = CT < 4 ? 4 : CT;       // weight words staged per row (prep pads rows of fewer than 4 channels)
     static constexpr int SW = cand_stride_words(CT); // row stride in LDS, words
     static_assert(16 + WW <= 32, "two rows per load instruction");
     static __device__ __forceinline__ void zero(Acc &acc) {
 #pragma unroll
-        for (int c = 0; c < (CT + 1) / 2; ++c) acc[c] = (float2v){0.0f, 0.0f};
+        for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+            for (int c = 0; c < (CT + 1) / 2; ++c) sets(acc)[s][c] = (float2v){0.0f, 0.0f};
     }
+    // (the wave's first sub-tile: NSUB * wave)
     static __device__ __forceinline__ LaneCtx ctx(int lane, int wave, int x0, int y0, int z0, int zt_lo, int cbase, const VoxParams &P) {
         const int lz = lane & (SUBZ - 1), ly = (lane >> SUBZ_SH) & (SUBY - 1);
         LaneCtx L;
         L.ix = x0; // (x0 is a multiple of SUBX: every lane evaluates the x0 and the x0 + 1 plane)
         L.iy = y0 + ly;
-        L.iz = z0 + SUBZ * wave + lz;
+        L.iz = z0 + SUBZ * NSUB * wave + lz;
         L.gx = (double)L.ix * P.res - P.half;
         L.gx1 = (double)(L.ix + 1) * P.res - P.half;
         L.gy = (double)L.iy * P.res - P.half;
         L.gz = (double)L.iz * P.res - P.half;
-        L.zt_w = zt_lo + wave;
+        L.zt_w = zt_lo + NSUB * wave;
         L.cbase = cbase;
         return L;
     }
     static __device__ __forceinline__ void tables(LaneCtx &, char *, const VoxParams &, int) {}
-    static __device__ __forceinline__ void walk(Acc &acc, unsigned long long mask, const unsigned *un, int lane, const LaneCtx &L,
+    static __device__ __forceinline__ void walk(Set &acc, unsigned long long mask, const unsigned *un, int lane, const LaneCtx &L,
                                                 const VoxParams &, const double *__restrict__, const float *__restrict__) {
         const bool upper = lane >= 32; // this lane evaluates the pair's second candidate
         while (mask) {
@@ -364,11 +377,14 @@ struct OpsPair {
     }
     static __device__ __forceinline__ void write(const Acc &acc, bool any, unsigned *un, int tid, int lane, int wave, int NW,
                                                  int b, const LaneCtx &L, int x0, int y0, int z0, void *out, const VoxParams &P) {
-        if constexpr (grid_elem<OT>::NDHWC)
-            write_ndhwc<CT>(acc, lane, wave, b, L.cbase, x0, y0, z0, static_cast<typename grid_elem<OT>::type *>(out), P);
-        else
-            write_slab<CT, RUNS, CR_F32, OT>(acc, any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0, z0,
-                                             static_cast<OT *>(out), P);
+        if constexpr (grid_elem<OT>::NDHWC) { // channels-last grids: every lane stores its voxels' channel runs from registers
+            typename grid_elem<OT>::type *o = static_cast<typename grid_elem<OT>::type *>(out);
+            if constexpr (NSUB == 1) write_ndhwc<CT>(acc, lane, wave, b, L.cbase, x0, y0, z0, o, P);
+            else write_ndhwc_sets<CT, NSUB>(acc, lane, NSUB * wave, b, L.cbase, x0, y0, z0, o, P);
+        } else {
+            write_slab<CT, RUNS, CR_F32, OT, NSUB>(sets(acc), any, reinterpret_cast<float *>(un), tid, lane, wave, NW, b, L.cbase, x0, y0,
+                                                   z0, static_cast<OT *>(out), P);
+        }
     }
 };
 

@@ -1,14 +1,16 @@
 // mvx_slab_body.inc - one workgroup = one slab: the body shared by voxelize_kernel / voxelize_runs_kernel (float32 grids,
-// 64 registers, four 8-wave workgroups per compute unit), voxelize64_kernel (float64 grids on the matrix cores, 128
-// registers, two) and voxelize64_vec_kernel (float64 grids on the vector ALU). Included inside the kernel definitions, which
-// provide: the type Ops, the constants CT, GROUPED, MAXT and the kernel parameters rec, w, slist, slist_ext, Tc, kc, out, P.
+// 64 registers, four 8-wave workgroups per compute unit), voxelize_narrow_kernel (narrow chunks, Ops::NSUB sub-tiles per wave),
+// voxelize64_kernel (float64 grids on the matrix cores, 128 registers, two) and voxelize64_vec_kernel (float64 grids on the
+// vector ALU). Included inside the kernel definitions, which provide: the type Ops, the constants CT, GROUPED, MAXT and the
+// kernel parameters rec, w, slist, slist_ext, Tc, kc, out, P.
 // (Textual inclusion, not a __device__ function: with the body in an inlined function template the per-lane-range
 // 32-channel variant kept its accumulators in scratch - 193 spilled registers against 4 - whatever the parameter passing.)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int NW = P.NW;
+    const int NW = P.NW;             // sub-tiles per slab: z0, the rows of a round, the lane context
+    const int NWV = NW / Ops::NSUB;  // waves per workgroup (one sub-tile each but for the narrow kernels): the staging's shares
     unsigned *un = reinterpret_cast<unsigned *>(smem);
 
     // grid = (T, Z): t = slab id, z = (molecule - b0) * ncc + channel chunk
@@ -109,7 +111,7 @@
         const RoundSrc<Ops> RS_ = round_src<Ops>(rec, w, lane, L, P);
         // (narrow rows - OpsPair - are staged two per load with vector-ALU addresses; written out twice, not as a lambda: the
         // 32-channel kernel then kept ten more registers in scratch)
-        if constexpr (Ops::VSTAGE) stage_round_v<Ops, BIG>(line, ext, 0, n, un, rec, w, a0, lane, wave, NW, L, P);
+        if constexpr (Ops::VSTAGE) stage_round_v<Ops, BIG>(line, ext, 0, n, un, rec, w, a0, lane, wave, NWV, RW, L, P);
         else if constexpr (Ops::PRESTAGE) stage_first_rounds<Ops, BIG>(line, ext, n, RW, un, RS_, a0, lane, wave);
         else stage_round<Ops, BIG>(line, ext, 0, n, un, RS_, a0, lane, wave, NW);
         VK_STAMP(2);
@@ -123,7 +125,7 @@
         if (Ops::PRESTAGE && n >= RW) filter_walk<Ops>(xl, acc, RW, n, RW, un + RW * Ops::SW, lane, wave, L, P, Tc, kc); // (staged with the first)
         for (int e0 = Ops::PRESTAGE ? 2 * RW : RW; e0 <= n; e0 += RW) {
             __syncthreads(); // every wave is done with the previous round's rows
-            if constexpr (Ops::VSTAGE) stage_round_v<Ops, BIG>(line, ext, e0, n, un, rec, w, a0, lane, wave, NW, L, P);
+            if constexpr (Ops::VSTAGE) stage_round_v<Ops, BIG>(line, ext, e0, n, un, rec, w, a0, lane, wave, NWV, RW, L, P);
             else stage_round<Ops, BIG>(line, ext, e0, n, un, RS_, a0, lane, wave, NW);
             __syncthreads();
             filter_walk<Ops>(xl, acc, e0, n, RW, un, lane, wave, L, P, Tc, kc);

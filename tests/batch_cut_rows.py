@@ -62,7 +62,7 @@ ROWS = [
        device=False),
     _r("grouped-C40-binary", 32, 40, dict(route=BINNED, grouped=1, ct=32, ncc=2), radii="channel-wise", density="binary", n_radii=3),
     _r("grouped-C72", 32, 72, dict(route=BINNED, grouped=1, ct=32, ncc=3), radii="channel-wise", chunks=(2,)),
-    # ---- narrow multi-sub-tile kernel (its own copy of the decode in mvx_slab.hip) ---------------------------------------------
+    # ---- narrow multi-sub-tile kernel (the shared decode of mvx_slab_body.inc with NW / NSUB waves per workgroup) ---------------
     _r("narrow-single-D32", 32, 1, dict(route=BINNED, ct=1, ncc=1, nw=4, nzc=1, vec_store=1, lane_range=0), mode="single", narrow=4),
     _r("narrow-single-D40", 40, 1, dict(route=BINNED, ct=1, ncc=1, nw=4, nzc=2, vec_store=1, lane_range=0), mode="single",
        radii="atom-wise", narrow=4, device=False),
@@ -261,8 +261,8 @@ BIG = [
     Big("f32-types-C4-65535", 8, 4, 65535, mode="types", density="binary", narrow=0, plan=dict(route=BINNED, ct=4, ncc=1)),
     Big("f32-types-C4-65536", 8, 4, 65536, mode="types", narrow=0, plan=dict(route=BINNED, ct=4, ncc=1)),
     Big("f32-types-C4-70001", 8, 4, 70001, mode="types", radii="atom-wise", narrow=0, plan=dict(route=BINNED, ct=4, ncc=1)),
-    # voxelize_narrow_kernel has its own copy of the decode (blockIdx.y, b0, slab line address): rows of one sub-tile (D = 8) never
-    # reach it, rows of two (D = 16) do, two sub-tiles per wave
+    # voxelize_narrow_kernel takes the decode of mvx_slab_body.inc (blockIdx.y, b0, slab line address) with fewer waves than the
+    # slab has sub-tiles: rows of one sub-tile (D = 8) never reach it, rows of two (D = 16) do, two sub-tiles per wave
     Big("f32-narrow-single-D16-65536", 16, 1, 65536, mode="single", narrow=2, plan=dict(route=BINNED, ct=1, ncc=1, nw=2, nzc=1, vec_store=1,
                                                                                      lane_range=0)),
     Big("f32-narrow-single-D16-70001", 16, 1, 70001, mode="single", radii="atom-wise", density="binary", narrow=2,

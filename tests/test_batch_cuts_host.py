@@ -69,8 +69,9 @@ def test_big_case_crosses_the_grid_limit(case):
 
 
 def test_the_narrow_kernel_crosses_the_grid_limit():
-    """voxelize_narrow_kernel decodes blockIdx.y and b0 on its own: at least two of the big cases must reach it beyond 65 535
-    molecules, and the one-sub-tile rows must not claim to."""
+    """voxelize_narrow_kernel decodes blockIdx.y and b0 as every slab kernel does (mvx_slab_body.inc) but is the one whose workgroups
+    have fewer waves than the slab has sub-tiles: at least two of the big cases must reach it beyond 65 535 molecules, and the
+    one-sub-tile rows must not claim to."""
     narrow = [c for c in R.BIG if c.narrow > 0]
     assert len(narrow) >= 2 and all(c.B > R.GRID_Y_MAX and R.big_host_plan(c)["nchunk"] >= 2 for c in narrow)
     assert all(c.narrow == 0 for c in R.BIG if c.D == 8)

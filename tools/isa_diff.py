@@ -4,7 +4,8 @@
 
 Every kernel's disassembly is hashed with comments and <symbol> references stripped, and the two MULTISETS of hashes are
 compared: a kernel that was renamed, or became another instantiation of a template, still matches. Prints the kernel counts
-and the number of bodies without a partner per pair of objects; exit status 1 if any pair differs.
+and the number of bodies without a partner per pair of objects, then the demangled names of the kernels those bodies belong
+to ("-" old object, "+" new object); exit status 1 if any pair differs.
 """
 import collections, hashlib, os, re, subprocess, sys, tempfile
 
@@ -13,7 +14,8 @@ from regs import LLVM
 
 
 def kernel_bodies(obj):
-    """Counter of the body hashes of the kernels (functions with a .kd descriptor) in obj's gfx950 code object."""
+    """Counter of the body hashes of the kernels (functions with a .kd descriptor) in obj's gfx950 code object, and the
+    kernels' (mangled) names by hash."""
     with tempfile.TemporaryDirectory() as td:
         co, fat = os.path.join(td, "k.co"), os.path.join(td, "fat.bin")
         subprocess.check_call([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj, os.path.join(td, "ignored")])
@@ -22,17 +24,25 @@ def kernel_bodies(obj):
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
         text = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
     kernels = set(re.findall(r"\.symbol:\s*(\S+)\.kd", notes))
-    bodies = collections.Counter()
+    bodies, names = collections.Counter(), collections.defaultdict(list)
     for chunk in re.split(r"\n(?=[0-9a-f]+ <[^>]+>:\n)", text):
         head, _, body = chunk.partition("\n")
         m = re.match(r"[0-9a-f]+ <([^>]+)>:$", head)
         if m and m.group(1) in kernels:
             lines = [re.sub(r"\s*<[^>]*>", "", re.sub(r"\s*//.*", "", line)).strip() for line in body.splitlines()]
-            bodies[hashlib.sha256("\n".join(filter(None, lines)).encode()).hexdigest()] += 1
+            h = hashlib.sha256("\n".join(filter(None, lines)).encode()).hexdigest()
+            bodies[h] += 1
+            names[h].append(m.group(1))
         else:
             assert not m, (obj, m.group(1))  # (device code outside the kernels: nothing here is built that way)
     assert sum(bodies.values()) == len(kernels), (obj, sum(bodies.values()), len(kernels))
-    return bodies
+    return bodies, names
+
+
+def demangle(mangled):
+    """(c++filt does not know __bf16's mangling: tools/regs.py)"""
+    out = subprocess.run(["c++filt"], input="\n".join(n.replace("DF16b", "Dh") for n in mangled), capture_output=True, text=True).stdout
+    return [re.sub(r"^void mvx::|\(.*$", "", line) for line in out.replace("half", "__bf16").splitlines()]
 
 
 if __name__ == "__main__":
@@ -40,8 +50,11 @@ if __name__ == "__main__":
         sys.exit(__doc__)
     differ = False
     for old, new in zip(sys.argv[1::2], sys.argv[2::2]):
-        a, b = kernel_bodies(old), kernel_bodies(new)
+        (a, a_names), (b, b_names) = kernel_bodies(old), kernel_bodies(new)
         unmatched = sum(((a - b) + (b - a)).values())
         differ |= unmatched != 0 or sum(a.values()) != sum(b.values())
         print(f"{os.path.basename(new):22s} kernels {sum(a.values()):4d} -> {sum(b.values()):4d}   distinct bodies {len(a):4d} -> {len(b):4d}   unmatched {unmatched}")
+        for sign, left, names in (("-", a - b, a_names), ("+", b - a, b_names)):
+            for name in sorted(demangle([n for h in left for n in names[h]])):  # (all kernels that share an unmatched body)
+                print(f"    {sign} {name}")
     sys.exit(1 if differ else 0)
