@@ -24,7 +24,8 @@ MVX_ERR_INVALID = -1
 
 
 def _make(row_id):
-    return S.make(row_id) if row_id in S.BY_ID else R.make(row_id)
+    """A row of tests/sum_rows.py, or a row or a draw ("draw<seed>") of tests/sum_sweep_rows.py."""
+    return S.make(row_id) if (row_id in S.BY_ID or row_id.startswith("draw")) else R.make(row_id)
 
 
 @functools.lru_cache(maxsize=None)

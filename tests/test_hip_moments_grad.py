@@ -21,6 +21,7 @@ from tests import grad_reference as GR
 from tests import moments_grad_reference as MG
 from tests import pose_reference as PR
 from tests import sum_rows as R
+from tests import sum_sweep_rows as S
 from tests.tolerance import GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -32,6 +33,11 @@ SEED = 77      # the rotated leg seeds numpy's global generator, as tests/test_h
 SAMPLE = 96    # atoms per case that go through the float64 reference
 
 
+def _make(row_id):
+    """A row of tests/sum_rows.py or of tests/sum_sweep_rows.py (these carry a blockdim and a z shift of their own)."""
+    return S.make(row_id) if row_id in S.BY_ID else R.make(row_id)
+
+
 @functools.lru_cache(maxsize=None)
 def _vox(row_id, **kw):
     return _new_vox(row_id, **kw)
@@ -40,8 +46,8 @@ def _vox(row_id, **kw):
 def _new_vox(row_id, **kw):
     import molvoxel_amd as mv
 
-    row = R.make(row_id)["row"]
-    return mv.create_voxelizer(0.5, row.D, row.radii_type, row.density, library="hip", **kw)
+    row = _make(row_id)["row"]
+    return mv.create_voxelizer(0.5, row.D, row.radii_type, row.density, library="hip", blockdim=getattr(row, "blockdim", None), **kw)
 
 
 def _dev(x, grad=False):
@@ -66,7 +72,7 @@ def _args(d, lo=0, hi=None):
 @functools.lru_cache(maxsize=None)
 def _target(row_id):
     """A seeded float32 target of mixed signs, (C, D, D, D) (never modified)."""
-    row = R.make(row_id)["row"]
+    row = _make(row_id)["row"]
     t = np.random.default_rng(row.seed + 5000).standard_normal((row.C,) + (row.D,) * 3).astype(np.float32)
     t.setflags(write=False)
     return t
@@ -75,7 +81,7 @@ def _target(row_id):
 @functools.lru_cache(maxsize=None)
 def _dm(row_id, K):
     """Seeded dL/dm of mixed signs, different for every molecule and channel: (B, C, K) float64 (never modified)."""
-    d = R.make(row_id)
+    d = _make(row_id)
     g = np.random.default_rng(d["row"].seed + 9000 + K).standard_normal((d["B"], d["row"].C, K))
     g.setflags(write=False)
     return g
@@ -167,7 +173,7 @@ def test_the_third_moment_alone_is_score_batch_over_the_target(row_id, leg):
 
     from molvoxel_amd.voxelizer.hip import _lib
 
-    d = R.make(row_id)
+    d = _make(row_id)
     vox = _vox(row_id)
     call = _spec(vox, d, leg)
     t = _dev(_target(row_id))
@@ -182,7 +188,7 @@ def test_the_third_moment_alone_is_score_batch_over_the_target(row_id, leg):
 
 @pytest.mark.parametrize("row_id", ROW_IDS)
 def test_the_second_moment_alone_is_backward_batch_with_the_grids_as_upstream(row_id):
-    d = R.make(row_id)
+    d = _make(row_id)
     vox = _vox(row_id)
     call = _spec(vox, d, "posed")
     grids = _forward(vox, d, "posed")
@@ -195,7 +201,7 @@ def test_the_second_moment_alone_is_backward_batch_with_the_grids_as_upstream(ro
 def test_the_first_moment_alone_is_backward_batch_with_an_upstream_of_ones(row_id):
     import torch
 
-    d = R.make(row_id)
+    d = _make(row_id)
     row = d["row"]
     vox = _vox(row_id)
     call = _spec(vox, d, "centred")
@@ -234,7 +240,8 @@ def _reference(d, leg, grids, gm, target, atoms, pre_rotation=False):
         else:
             p = PR.positions(d["xyz"][lo:hi], d["cen"][b], q[b], t[b])
         G, Gabs = MG.upstream(grids[b], gm[b], target)
-        kw = dict(mode=row.mode, density=row.density, atoms=mine, rot=None if (leg == "centred" or pre_rotation) else PR.rotation(q[b]))
+        kw = dict(mode=row.mode, density=row.density, atoms=mine, blockdim=getattr(row, "blockdim", None),
+                  rot=None if (leg == "centred" or pre_rotation) else PR.rotation(q[b]))
         if row.mode == "features":
             kw["w"] = d["chan"][lo:hi]
         elif row.mode == "types":  # (a type outside [0, C) - here -1 - reaches no channel: the reference knows it as "beyond C")
@@ -250,7 +257,7 @@ def _reference(d, leg, grids, gm, target, atoms, pre_rotation=False):
 
 @functools.lru_cache(maxsize=None)
 def _grids(row_id, leg):
-    g = _forward(_vox(row_id), R.make(row_id), leg).cpu().numpy()
+    g = _forward(_vox(row_id), _make(row_id), leg).cpu().numpy()
     assert g.dtype == np.float32
     g.setflags(write=False)
     return g
@@ -259,7 +266,7 @@ def _grids(row_id, leg):
 @pytest.mark.parametrize("leg", LEGS)
 @pytest.mark.parametrize("row_id", ROW_IDS)
 def test_general_coefficients_match_the_float64_reference(row_id, leg):
-    d = R.make(row_id)
+    d = _make(row_id)
     row = d["row"]
     vox = _vox(row_id)
     call = _spec(vox, d, leg)
@@ -295,14 +302,14 @@ def test_general_coefficients_match_the_float64_reference(row_id, leg):
 # ---- 3. batch and chunk identities, to the bit ----------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _uncut(row_id, with_target):
-    d = R.make(row_id)
+    d = _make(row_id)
     vox = _vox(row_id)
     return _entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3 if with_target else 2), _dev(_target(row_id)) if with_target else None)
 
 
 @pytest.mark.parametrize("row_id", ROW_IDS)
 def test_a_molecule_alone_and_two_runs_give_the_batchs_bits(row_id):
-    d = R.make(row_id)
+    d = _make(row_id)
     vox = _vox(row_id)
     t = _dev(_target(row_id))
     whole = _uncut(row_id, True)
@@ -323,7 +330,7 @@ def test_a_molecule_alone_and_two_runs_give_the_batchs_bits(row_id):
     ("carry", "mgrad_scratch_kb", 1024, 6), ("light", "mgrad_scratch_kb", 1, 7), ("chunks", "mgrad_scratch_kb", 4000, 5),
 ])
 def test_molecule_chunks_give_the_uncut_bits(row_id, option, value, nchunk):
-    d = R.make(row_id)
+    d = _make(row_id)
     vox = _new_vox(row_id)  # (a voxelizer of its own: the option stays with the handle)
     vox.debug_option(option, value)
     for with_target in (True, False):
@@ -337,7 +344,7 @@ def test_the_spatial_order_applies_per_chunk_and_keeps_the_bits():
     vox = _new_vox("carry")
     vox.debug_option("grad_order", 1)
     vox.debug_option("chunks", 2)
-    d = R.make("carry")
+    d = _make("carry")
     assert _same(_entry(vox, _spec(vox, d, "centred"), _dm("carry", 3), _dev(_target("carry"))), _uncut("carry", True))
     assert vox.last_plan()["nchunk"] == 2
 
@@ -347,7 +354,7 @@ def test_the_spatial_order_applies_per_chunk_and_keeps_the_bits():
 def test_bfloat16_and_channels_last_voxelizers_give_the_float32_bits(row_id, kw):
     import torch
 
-    d = R.make(row_id)
+    d = _make(row_id)
     vox = _vox(row_id, **kw)
     assert vox.forward_batch(**_args(d, 0, 1)).dtype == (torch.bfloat16 if "grid_dtype" in kw else torch.float32)
     for with_target in (True, False):
@@ -387,7 +394,7 @@ def test_autograd_gives_coordinate_and_feature_gradients_of_the_ncc_loss():
     import torch
 
     row_id = "light"
-    d = R.make(row_id)
+    d = _make(row_id)
     vox = _new_vox(row_id, differentiable=True, moments_grad=True)
     plain = _new_vox(row_id, differentiable=True)
     T = _dev(_target(row_id))
@@ -436,7 +443,7 @@ def test_autograd_gives_pose_gradients_of_the_ncc_loss():
     import torch
 
     row_id = "chunks"
-    d = R.make(row_id)
+    d = _make(row_id)
     B = d["B"]
     vox = _new_vox(row_id, differentiable=True, moments_grad=True)
     plain = _new_vox(row_id, differentiable=True)
@@ -475,7 +482,7 @@ def test_autograd_gives_pose_gradients_of_the_ncc_loss():
 def test_a_change_of_density_between_forward_and_backward_is_refused():
     import torch
 
-    d = R.make("light")
+    d = _make("light")
     vox = _new_vox("light", differentiable=True, moments_grad=True)
     a = _args(d)
     a["coords"] = a["coords"].clone().requires_grad_()
