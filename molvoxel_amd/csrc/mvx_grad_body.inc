@@ -230,6 +230,9 @@
     if (A.grad_coords) {
         double g0 = wave_sum(cp0), g1 = wave_sum(cp1), g2 = wave_sum(cp2);
         if (A.xforms) apply_xform_transpose(A.xforms[bm], g0, g1, g2);
+        // an atom without admitted voxels has a zero row whatever its molecule's pose: M^T 0 is NaN under a non-finite quaternion.
+        // Under a finite one it is +-0, which passes the compares: no bit changes.
+        if (nbox == 0 && !(g0 == g0 && g1 == g1 && g2 == g2)) g0 = g1 = g2 = 0.0;
         if (lane == 0) {
             A.grad_coords[3 * a] = g0;
             A.grad_coords[3 * a + 1] = g1;

@@ -48,6 +48,9 @@ __global__ void __launch_bounds__(64 * POSE_WAVES) pose_grad_kernel(const double
     double u00 = 0.0, u01 = 0.0, u02 = 0.0, u10 = 0.0, u11 = 0.0, u12 = 0.0, u20 = 0.0, u21 = 0.0, u22 = 0.0;
     for (int64_t a = a0 + 64 * wave + lane; a < a1; a += 64 * POSE_WAVES) {
         const double g0 = grad_coords[3 * a], g1 = grad_coords[3 * a + 1], g2 = grad_coords[3 * a + 2];
+        // an atom that reaches no voxel has a zero row, and its x may be NaN or infinite: 0 * x would poison U. For finite x the
+        // skipped terms are +-0 added to sums that start at +0: no bit changes.
+        if (g0 == 0.0 && g1 == 0.0 && g2 == 0.0) continue;
         const double x0 = coords[3 * a] - c0, x1 = coords[3 * a + 1] - c1, x2 = coords[3 * a + 2] - c2;
         s0 += g0;
         s1 += g1;
