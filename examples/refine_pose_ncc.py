@@ -1,7 +1,7 @@
 """Pose refinement on normalised cross-correlation, without a grid: the 10GS ligand, rotated and shifted, is moved back onto
 its own density map.
 
-    python examples/refine_pose_ncc.py [steps]
+    python examples/refine_pose_ncc.py [steps] [--views]
 
 examples/refine_pose.py with another loss. The target is the ligand's grid in its crystal pose; the start is that pose perturbed
 by a rotation of about 20 degrees and a shift of about 0.7 A. `torch.optim.Adam([q, t])` minimises -NCC, and NCC is built from the
@@ -12,6 +12,9 @@ moments of the posed ligand's grid, m = `moments_posed_batch(..., target=target)
 Every step is one `moments_posed_batch` and one `backward()`. No grid of the posed ligand is written for autograd and no grid of
 dL/dgrid exists: the backward walk forms its upstream from the moments' gradients (mvx_moments_backward_batch). The quaternion is
 normalised in torch before the call (autograd carries the normalisation). Needs an MI355X (the HIP backend has no CPU path).
+
+--views: the same refinement through `moments_posed_views`, which takes the ligand as ONE shared cloud and the pose as a view of
+it (here a single one; B poses under refinement are B rows of `centers`, `q` and `t`, and the ligand is still handed over once).
 """
 import math
 import os
@@ -26,7 +29,7 @@ import molvoxel_amd  # noqa: E402
 from molvoxel_amd.etc import mol as M  # noqa: E402
 
 
-def main(steps=300):
+def main(steps=300, views=False):
     import torch
 
     ligand = M.read_sdf(os.path.join(ROOT, "tests", "golden", "10gs", "10gs_ligand.sdf"))[0]
@@ -44,7 +47,11 @@ def main(steps=300):
     tt = (target.double() ** 2).sum()
 
     def ncc_of(q, t):
-        m = vox.moments_posed_batch(xyz, offsets, center, q / q.norm(dim=1, keepdim=True), t, None, 1.5, target=target)
+        qn = q / q.norm(dim=1, keepdim=True)
+        if views:
+            m = vox.moments_posed_views(xyz, center, qn, t, None, 1.5, target=target)
+        else:
+            m = vox.moments_posed_batch(xyz, offsets, center, qn, t, None, 1.5, target=target)
         return (m[..., 2] / torch.sqrt(m[..., 1] * tt)).sum()
 
     angle = math.radians(20.0)
@@ -65,4 +72,4 @@ def main(steps=300):
 
 
 if __name__ == "__main__":
-    main(*(int(a) for a in sys.argv[1:2]))
+    main(*[int(a) for a in sys.argv[1:] if a != "--views"][:1], views="--views" in sys.argv[1:])

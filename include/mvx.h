@@ -563,6 +563,57 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
                     double *scores, double *atom_scores, double *grad_coords, mvx_real *grad_features, void *stream);
 
 /*
+ * The moments of B views of ONE shared cloud, without the grids and without B copies of the cloud (no counterpart in the
+ * reference): mvx_moments_batch on the compact batch mvx_forward_views voxelizes. The cloud, `mode`, radii and the B host records
+ * are those of mvx_forward_views; every array is a device array (centre and pose pointers point into device memory).
+ *   index == NULL:  the entry selects the views' atoms itself (ONE stream synchronisation) and ignores offsets_host.
+ *   index != NULL:  index (device) and offsets_host (B + 1 entries, host) are a selection mvx_select_views returned for the same
+ *                   cloud, radii and records; the entry does not synchronise.
+ *   target:             float32 NCDHW on the device, 16-byte aligned, or NULL (K = 2).
+ *   target_view_stride: elements between the targets of two views: 0 = one (C, D, D, D) target for all views, C * D^3 = one
+ *                       per view, (B, C, D, D, D): view b is multiplied with target + b * target_view_stride. The target lives in
+ *                       box coordinates, so views of different boxes want one each. Ignored without a target.
+ *   moments:            (B, C, K) doubles on the device, K = target ? 3 : 2, fully overwritten.
+ * Every value is the bit mvx_moments_batch gives for coords[index], the gathered channels and radii, the offsets and the same
+ * records - with a target per view, the bit of the call that shares that view's target among all; the bits do not depend on how
+ * the call is cut into chunks of views. B == 0: MVX_OK, nothing written; N == 0, or no atom selected: exact zeros.
+ * MVX_ERR_INVALID before any device is touched, in this order: what mvx_select_views rejects for the cloud and the records up to
+ * "too many atoms"; NULL moments with B > 0; a negative target_view_stride; an index without offsets_host, offsets_host[0] != 0,
+ * decreasing offsets or offsets_host[B] >= 2^31; features mode without channels; a NULL handle; a bad pose record; a
+ * target_view_stride that is neither 0 nor C * D^3; then, with B > 0, the configurations mvx_moments_batch names "moments:" and
+ * the target's alignment.
+ */
+int mvx_moments_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                      double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                      const int64_t *index, const int64_t *offsets_host, const float *target, int64_t target_view_stride,
+                      double *moments /* (B, C, K) device, K = target ? 3 : 2 */, void *stream);
+
+/*
+ * Gradients through mvx_moments_views: mvx_moments_backward_batch on the compact batch of a selection, each view against its own
+ * target where target_view_stride says so (dL/dgrid[b, c, v] = G0 + 2 G1 g[b, c, v] + G2 target_b[c, v]). The rows come out per
+ * (view, atom) in selection order, so the selection is required: index (device) and offsets_host (B + 1 entries, host) as
+ * mvx_select_views returned them for the same cloud, radii and records. With total = offsets_host[B]:
+ *   grad_moments:       (B, C, K) doubles on the device, K = target ? 3 : 2
+ *   grad_coords_rows:   (total, 3) doubles or NULL; grad_features_rows: (total, C) floats or NULL (features mode only); not both
+ *                       NULL. Row k belongs to atom index[k] of its view; mvx_views_reduce sums such rows onto the shared atoms,
+ *                       mvx_pose_grad_batch reduces them to the views' poses. Fully overwritten.
+ * Bit for bit mvx_moments_backward_batch's rows for coords[index], the gathered channels and radii, the offsets and the same
+ * records; the call runs chunk by chunk of views exactly as that entry does (the same options, mvx_debug_last_plan reports the
+ * cut), the target moving with the chunk, and the rows do not depend on the cut. Does not synchronise.
+ * MVX_ERR_INVALID before any device is touched, in this order: what mvx_select_views rejects for the cloud and the records up to
+ * "too many atoms"; NULL grad_moments with B > 0; grad_features_rows outside features mode; both row outputs NULL; a negative
+ * target_view_stride; a NULL index (the text mvx_score_views has for per-row outputs without an index); what is wrong with
+ * offsets_host; features mode without channels; a NULL handle; a bad pose record; a target_view_stride that is neither 0 nor
+ * C * D^3; then, with B > 0, the configurations named "moments:" and the target's alignment. B == 0: MVX_OK; a selection
+ * without atoms launches nothing.
+ */
+int mvx_moments_backward_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                               double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                               const int64_t *index, const int64_t *offsets_host, const float *target, int64_t target_view_stride,
+                               const double *grad_moments /* (B, C, K) device */, double *grad_coords_rows,
+                               mvx_real *grad_features_rows, void *stream);
+
+/*
  * Rows of a selection summed back onto the shared atoms (the backward step of anything computed per (view, atom) row):
  *   out[n, j] = sum over the views b whose segment index[offsets[b] .. offsets[b + 1]) holds atom n of rows[slot(b, n), j]
  * index (device) and offsets_host (B + 1 entries, host) as mvx_select_views returns them: every segment ascending, entries in

@@ -280,6 +280,7 @@ struct SumCall {
     // mvx_moments_batch: the same plan, pre-pass and walk, but per molecule, and `out` takes (B, C, K) float64 moments instead of a grid
     bool moments = false;
     const float *target = nullptr; // (C, D, D, D) device, or null (K = 2)
+    int64_t target_stride = 0;     // elements between the targets of two molecules: 0 (one for all) or C * D^3 (mvx_moments_views)
 };
 
 // Orders this call after the previous call's work when the caller switched streams (see mvx_handle::last_stream).
@@ -888,7 +889,7 @@ struct Forward {
                 if (k == nchunk - 1) rc = timed_launch(h, s, [&] { return launch_voxelize64(va, ct, gauss, chanwise, lr_blocks, s); });
                 break;
             case WALK_MOMENTS: // one walk and one finish per molecule chunk: the partials are the chunk's
-                rc = timed_launch(h, s, [&] { return launch_moments(va, nb, gauss, sum->target, moments_part, static_cast<double *>(d_out), s); });
+                rc = timed_launch(h, s, [&] { return launch_moments(va, nb, gauss, sum->target, sum->target_stride, moments_part, static_cast<double *>(d_out), s); });
                 break;
             case WALK_SUM_PARTS: // one launch per molecule chunk over the parts that meet it
                 rc = timed_launch(h, s, [&] { return launch_voxelize_sum_parts(va, nb, gauss, part_grids, part_q, s); });
@@ -1652,8 +1653,10 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
 
 // ---- mvx_moments_backward_batch behind its checks, with atoms: the molecule chunks the forward cuts, one after the other. Per chunk
 // the forward as a call of its own into the float32 NCDHW scratch (rebased offsets: a molecule's bits do not depend on its
-// batch), then the backward's pre-pass and the moments walk over the chunk's atoms. The scratch holds the largest chunk. ----
-int moments_backward(mvx_handle *h, const Call &c, const Extent &e, const float *target, const double *grad_moments,
+// batch), then the backward's pre-pass and the moments walk over the chunk's atoms. The scratch holds the largest chunk. With one
+// target per molecule (target_stride = C * D^3: mvx_moments_backward_views) the target base moves with the chunk, as the
+// coefficients' does: the walk's molecule index is chunk-relative. ----
+int moments_backward(mvx_handle *h, const Call &c, const Extent &e, const float *target, int64_t target_stride, const double *grad_moments,
                      double *grad_coords, void *grad_features) {
     CallScope scope(h, c.stream);
     if (scope.rc) return scope.rc;
@@ -1702,7 +1705,7 @@ int moments_backward(mvx_handle *h, const Call &c, const Extent &e, const float 
         if ((rc = run_checked(h, fwd, se, nullptr))) break;
         GradOut o{BWD_MOMENTS, h->mgrad_grids.p, grad_coords ? grad_coords + 3 * a0 : nullptr,
                   grad_features ? static_cast<float *>(grad_features) + (size_t)a0 * c.C : nullptr, nullptr, nullptr, nullptr, {},
-                  {coef + (size_t)b0 * c.C * 3, target}};
+                  {coef + (size_t)b0 * c.C * 3, target ? target + (size_t)b0 * (size_t)target_stride : nullptr, target_stride}};
         Backward b(h, sub, o, n);
         if ((rc = b.stage())) break;
         if ((rc = b.moments())) break;
@@ -1719,6 +1722,16 @@ const char *bad_view_offsets(const int64_t *offsets, int32_t B, Extent &e) {
     if (!offsets) return "offsets_host must not be null with an index";
     if (const char *bad = check_offsets(offsets, B, e)) return bad;
     return too_many_atoms(e.total) ? "too many atoms: offsets[B] must stay below 2^31" : nullptr;
+}
+
+// what the views entries say when an output laid out per (view, atom) row comes without the selection that orders the rows
+const char *const ROWS_NEED_INDEX =
+    "atom_scores, grad_coords and grad_features need an index: their rows are laid out in selection order (mvx_select_views)";
+
+// the target stride of the moments entries for views, without the handle (the sign) and against it (0 or C * D^3)
+const char *const BAD_TARGET_STRIDE = "target_view_stride must be 0 (one shared target) or C * D^3 (one target per view)";
+bool target_stride_fits(const mvx_handle *h, int32_t C, int64_t stride) {
+    return stride == 0 || (uint64_t)stride == (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D;
 }
 
 } // namespace
@@ -1767,7 +1780,7 @@ int mvx_moments_backward_batch(mvx_handle *h, int32_t mode, const double *coords
     if (!grad_coords && !grad_features) return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
     if (B == 0 || e.total == 0) return MVX_OK; // (no atoms: no gradient rows, nothing is launched)
     // (one channel of a float32 grid stays below 4 GiB at every dimension mvx_create admits: the walk's 32-bit byte offsets hold)
-    return moments_backward(h, c, e, target, grad_moments, grad_coords, grad_features);
+    return moments_backward(h, c, e, target, 0, grad_moments, grad_coords, grad_features);
 }
 
 int mvx_pose_grad_batch(mvx_handle *h, const double *coords, const double *grad_coords, const int64_t *offsets,
@@ -1808,8 +1821,7 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
     if (grad_features && mode != MODE_FEATURES) own = "grad_features exists in features mode only";
     else if (field_view_stride < 0) own = "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)";
     else if (B > 0 && !scores) own = "scores must not be null";
-    else if (!index && per_row)
-        own = "atom_scores, grad_coords and grad_features need an index: their rows are laid out in selection order (mvx_select_views)";
+    else if (!index && per_row) own = ROWS_NEED_INDEX;
     else if (index && B > 0) own = bad_view_offsets(offsets_host, B, e);
     if (!own && B > 0 && N > 0) {
         if (mode == MODE_FEATURES && !channels) own = "channels must not be null";
@@ -1824,6 +1836,58 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
     if (N > 0) // (no index: the selection itself, one stream synchronisation)
         if (int rc = compact_views(h, v, false, index, offsets_host, batch)) return rc;
     return backward_impl(h, batch, {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_view_stride, scores, atom_scores}});
+}
+
+// The moments of B views: the selection (the caller's, or made here) and the gather of mvx_score_views, then mvx_moments_batch's
+// walk on the compact batch, each view against its own target where the stride says so. What reads the handle (the stride against
+// C * D^3, sum_config) is checked before a device is touched; run_summed checks the batch again, to no effect.
+int mvx_moments_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const void *radii, double radius_scalar,
+                      int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B, const int64_t *index,
+                      const int64_t *offsets_host, const float *target, int64_t target_view_stride, double *moments, void *stream) {
+    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream);
+    Extent e; // of the caller's selection
+    const char *own = nullptr;
+    if (B > 0 && !moments) own = "moments must not be null";
+    else if (target_view_stride < 0) own = BAD_TARGET_STRIDE;
+    else if (index && B > 0) own = bad_view_offsets(offsets_host, B, e);
+    if (!own && B > 0 && N > 0 && mode == MODE_FEATURES && !channels) own = "channels must not be null";
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (!target_stride_fits(h, C, target_view_stride)) return fail(MVX_ERR_INVALID, BAD_TARGET_STRIDE);
+    if (B == 0) return MVX_OK;
+    if (int rc = sum_config(h, v, true, target)) return rc;
+    ViewBatch batch(v); // (N == 0: B views without atoms, exact zeros, whatever the caller's selection says)
+    if (N > 0) // (no index: the selection itself, one stream synchronisation)
+        if (int rc = compact_views(h, v, true, index, offsets_host, batch)) return rc;
+    // (a compact batch does not overlap its pre-pass, and a summed call never does: Forward::make_plan)
+    return run_summed(h, {batch, moments, MVX_DEVICE, N > 0}, SumCall{nullptr, false, true, target, target ? target_view_stride : 0}, nullptr, nullptr);
+}
+
+// dL/dcoords and dL/dfeatures per (view, atom) row of a selection, through the moments of the views: the gather of
+// mvx_moments_views with the caller's index, then mvx_moments_backward_batch's chunks on the compact batch.
+int mvx_moments_backward_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                               double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                               const int64_t *index, const int64_t *offsets_host, const float *target, int64_t target_view_stride,
+                               const double *grad_moments, double *grad_coords_rows, mvx_real *grad_features_rows, void *stream) {
+    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream);
+    Extent e; // of the caller's selection
+    // mvx_moments_backward_batch's own rules, then this entry's; validate_views puts them in front of the handle
+    const char *own = nullptr;
+    if (B > 0 && !grad_moments) own = "grad_moments must not be null";
+    else if (grad_features_rows && mode != MODE_FEATURES) own = "grad_features exists in features mode only";
+    else if (!grad_coords_rows && !grad_features_rows) own = "grad_coords and grad_features are both null";
+    else if (target_view_stride < 0) own = BAD_TARGET_STRIDE;
+    else if (!index) own = ROWS_NEED_INDEX;
+    else if (B > 0) own = bad_view_offsets(offsets_host, B, e);
+    if (!own && B > 0 && N > 0 && mode == MODE_FEATURES && !channels) own = "channels must not be null";
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (!target_stride_fits(h, C, target_view_stride)) return fail(MVX_ERR_INVALID, BAD_TARGET_STRIDE);
+    if (B == 0) return MVX_OK;
+    if (int rc = sum_config(h, v, true, target)) return rc;
+    if (N == 0 || e.total == 0) return MVX_OK; // (no selected atom: no gradient rows, nothing is launched)
+    ViewBatch batch(v);
+    if (int rc = compact_views(h, v, true, index, offsets_host, batch)) return rc;
+    // (one channel of a float32 grid stays below 4 GiB at every dimension mvx_create admits: the walk's 32-bit byte offsets hold)
+    return moments_backward(h, batch, e, target, target ? target_view_stride : 0, grad_moments, grad_coords_rows, grad_features_rows);
 }
 
 int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets_host, int32_t B, int64_t N, const void *rows,

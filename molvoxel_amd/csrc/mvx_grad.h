@@ -97,7 +97,8 @@ struct ScoreArgs {
 // launch's molecules, and the walk forms the upstream itself: u[b,c,v] = fmaf(a1, g[b,c,v], fmaf(a2, t[c,v], a0)) in float32
 struct MomentsArgs {
     const float *coef;   // (B, C, 3): a0 = (float)G0, a1 = (float)(2 G1), a2 = (float)G2 of the launch's molecules (launch_moments_coef)
-    const float *target; // t: (C, D, D, D) float32 NCDHW, one for all molecules, or null (then u = fmaf(a1, g, a0))
+    const float *target; // t: (C, D, D, D) float32 NCDHW of the launch's first molecule, or null (then u = fmaf(a1, g, a0))
+    int64_t mol_stride;  // elements between the targets of two molecules: 0 (one target shared by all) or C * D^3
 };
 
 // channel-wise radii for features: rmax[0] = max(radii) (what prep_kernel culls with), per-channel thresholds Tc and

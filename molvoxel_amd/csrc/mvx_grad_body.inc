@@ -6,7 +6,8 @@
 // SA (ScoreArgs) and MA (MomentsArgs), the template parameters GT, MODE, GAUSS, CHANWISE and the constexpr bools RADII, SCORE,
 // MOMENTS and TARGET. With MOMENTS, A.g holds the float32 grids g of the call's molecules and the upstream of voxel v in
 // channel c is formed here, in float32: u = fmaf(a1, g[c,v], fmaf(a2, t[c,v], a0)) - without TARGET fmaf(a1, g[c,v], a0) -
-// from the three coefficients MA.coef keeps per (molecule, channel) and the one shared target MA.target. With SCORE, A.g is a constant field F (one per molecule, or one for all: SA.mol_stride) and the walk also
+// from the three coefficients MA.coef keeps per (molecule, channel) and the target MA.target (one per molecule, or one for all:
+// MA.mol_stride). With SCORE, A.g is a constant field F (one per molecule, or one for all: SA.mol_stride) and the walk also
 // forms the atom's score s_n = sum_v sum_c F[c,v] w[n,c] rho_{n,c}(v) - e without kfac - in float64 from the float32 products
 // of the coordinate path, for binary density too. With RADII the walk also forms the radius partials
 // (kfac: dk/dr = -2k/r, so d rho / d r = -(kfac / r) d2 rho):
@@ -71,7 +72,7 @@
         const float *mc = nullptr, *tc = nullptr;
         if constexpr (MOMENTS) {
             mc = MA.coef + ((size_t)bm * A.C + (size_t)(ch < A.C ? ch : 0)) * 3;
-            if constexpr (TARGET) tc = MA.target + (size_t)(ch < A.C ? ch : 0) * D3;
+            if constexpr (TARGET) tc = MA.target + (size_t)bm * (size_t)MA.mol_stride + (size_t)(ch < A.C ? ch : 0) * D3;
         }
         auto upstream = [&](size_t off) -> real {
             if constexpr (MOMENTS) {
@@ -133,9 +134,11 @@
 #pragma unroll
                             for (int c = 0; c < 32; ++c) gv[c] = c < nc ? gload(c) : (real)0;
                             if constexpr (TARGET) {
+                                // (this molecule's target: a wave-uniform base, as gm is - stride 0: the one shared target)
+                                const float *tm = MA.target + (size_t)bm * (size_t)MA.mol_stride;
 #pragma unroll
                                 for (int c = 0; c < 32; ++c)
-                                    tv[c] = c < nc ? *reinterpret_cast<const float *>(reinterpret_cast<const char *>(MA.target + (size_t)(c0 + c) * D3) + boff) : 0.0f;
+                                    tv[c] = c < nc ? *reinterpret_cast<const float *>(reinterpret_cast<const char *>(tm + (size_t)(c0 + c) * D3) + boff) : 0.0f;
                             }
                             const float *mc = MA.coef + ((size_t)bm * A.C + (size_t)c0) * 3;
 #pragma unroll

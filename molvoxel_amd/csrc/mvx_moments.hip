@@ -14,6 +14,7 @@
 //                          channel) to the workspace. A slab whose line is empty writes zeros without the reduction. No atomics.
 //                          The target is read as the grid is written - eight channels of the slab per round through the
 //                          write-out's tile in LDS, 16 bytes per lane - and its moment comes last; the waves' sums then sit behind the tile.
+//                          One target for all molecules, or one per molecule of the call (target_stride; mvx_moments_views).
 //   moments_finish_kernel  one thread per (molecule, moment, channel): the partials of the molecule's slabs added in slab-id order.
 #include "mvx_moments.h"
 
@@ -61,7 +62,8 @@ __host__ __device__ __forceinline__ size_t moments_tile_bytes(int NW) { return (
 template <bool GAUSS, int MAXT, bool TARGET>
 __global__ void __launch_bounds__(MAXT, 4)
     moments_kernel(const unsigned *__restrict__ rec, const unsigned *__restrict__ w, const uint2 *__restrict__ slist,
-                   const uint2 *__restrict__ slist_ext, const float *__restrict__ target, double *__restrict__ part, const VoxParams P) {
+                   const uint2 *__restrict__ slist_ext, const float *__restrict__ target0, const int64_t target_stride,
+                   double *__restrict__ part, const VoxParams P) {
     // blockIdx.z: the molecule of this launch's chunk [P.b0, P.b0 + gridDim.z); nothing is read from or written to a grid
     float *const grid = nullptr;
     const int mol0 = P.b0 + (int)blockIdx.z, nmol = 1, from_grid = 0;
@@ -114,6 +116,10 @@ __global__ void __launch_bounds__(MAXT, 4)
         // call took 4.26 ms at cfg-2 x 256 instead of 3.27.) Tile entries of voxels or channels that do not
         // exist are never written and never used. Last of the moments: the accumulators die round by round as the
         // products take their registers.
+        // The target of this molecule OF THE CALL (mol0 = P.b0 + blockIdx.z, not the launch's blockIdx.z alone), target_stride
+        // elements apart: 0 is the one shared target. A workgroup-uniform base from kernel arguments and blockIdx alone, so it
+        // is formed in scalar registers and costs the lanes nothing.
+        const float *const target = target0 + (size_t)mol0 * (size_t)target_stride;
         float *tile = reinterpret_cast<float *>(un);
         const int RS = row_stride_floats(NW);
         const int F4 = (SUBZ / 4) * NW;
@@ -183,26 +189,27 @@ __global__ void __launch_bounds__(256) moments_finish_kernel(const double *__res
 }
 
 template <bool GAUSS, int MAXT>
-static hipError_t launch_moments_walk(const VoxArgs &a, int32_t nb, const float *target, double *part, hipStream_t s) {
+static hipError_t launch_moments_walk(const VoxArgs &a, int32_t nb, const float *target, int64_t target_stride, double *part, hipStream_t s) {
     const VoxParams &p = a.p;
     const dim3 grid(p.nslab, (unsigned)p.ncc, (unsigned)nb), block(p.NW * 64);
     const size_t lds = voxelize_mx_lds_bytes(p.NW); // (the waves' partials, 16 * 2 * 32 doubles at most, fit the row region)
     if (target) // ... and sit behind the tile in the kernels that read a target
         return launch_kernel<moments_kernel<GAUSS, MAXT, true>>(grid, block, std::max(lds, moments_tile_bytes(p.NW) + (size_t)p.NW * 3 * 32 * sizeof(double)),
-                                                                s, a.rec, a.w, a.slist, a.slist_ext, target, part, p);
-    return launch_kernel<moments_kernel<GAUSS, MAXT, false>>(grid, block, lds, s, a.rec, a.w, a.slist, a.slist_ext, target, part, p);
+                                                                s, a.rec, a.w, a.slist, a.slist_ext, target, target_stride, part, p);
+    return launch_kernel<moments_kernel<GAUSS, MAXT, false>>(grid, block, lds, s, a.rec, a.w, a.slist, a.slist_ext, target, (int64_t)0, part, p);
 }
 
-hipError_t launch_moments(const VoxArgs &a, int32_t nb, bool gauss, const float *target, double *part, double *moments, hipStream_t s) {
+hipError_t launch_moments(const VoxArgs &a, int32_t nb, bool gauss, const float *target, int64_t target_stride, double *part, double *moments,
+                          hipStream_t s) {
     const VoxParams &p = a.p;
     if (!p.vec_store || p.xcd_ranges || p.ncc < 1 || p.ncc > 65535 || p.NW < 1 || p.NW > 16 || nb < 0 || nb > 65535 || !part || !moments ||
-        (reinterpret_cast<uintptr_t>(target) & 15u))
+        (reinterpret_cast<uintptr_t>(target) & 15u) || target_stride < 0 || (target_stride & 3))
         return hipErrorInvalidValue;
     if (nb == 0) return hipSuccess;
     static_assert(16 * 2 * 32 * sizeof(double) <= (size_t)2 * 64 * cand_stride_words(32) * 4, "the waves' partials must fit the row region");
     hipError_t e;
-    if (p.NW <= 8) e = gauss ? launch_moments_walk<true, 512>(a, nb, target, part, s) : launch_moments_walk<false, 512>(a, nb, target, part, s);
-    else e = gauss ? launch_moments_walk<true, 1024>(a, nb, target, part, s) : launch_moments_walk<false, 1024>(a, nb, target, part, s);
+    if (p.NW <= 8) e = gauss ? launch_moments_walk<true, 512>(a, nb, target, target_stride, part, s) : launch_moments_walk<false, 512>(a, nb, target, target_stride, part, s);
+    else e = gauss ? launch_moments_walk<true, 1024>(a, nb, target, target_stride, part, s) : launch_moments_walk<false, 1024>(a, nb, target, target_stride, part, s);
     if (e != hipSuccess) return e;
     const int K = target ? 3 : 2;
     const size_t n = (size_t)nb * K * p.C;

@@ -103,6 +103,9 @@ SIGNATURES = {
     "mvx_moments_backward_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mvx_score_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                   _vp, _vp]),
+    "mvx_moments_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mvx_moments_backward_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp,
+                                             _vp, _vp, _vp]),
     "mvx_views_reduce": (C.c_int, [Handle, _vp, _vp, _i32, _i64, _vp, _i32, _i32, _vp, _vp]),
     "mvx_pose_grad_batch":(C.c_int, [Handle, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "mvx_transform_coords": (C.c_int, [Handle, _vp, _i64, _vp, _vp, _i32, _i32, _vp]),

@@ -87,10 +87,12 @@ class _Call:
                 vox._ptr(self.channels if channels is None else channels), vox._ptr(self.radii), self.rs, vox._radii_type_code(),
                 self.offsets.ctypes.data, None if self.xforms is None else C.addressof(self.xforms), self.B, self.C)
 
-    def views_args(self, vox):
-        """The arguments mvx_forward_views, mvx_forward_views_sum and mvx_score_views begin with (mvx_select_views takes the
-        same values with the mode behind radii_type: `Voxelizer._select`)."""
-        return (vox._handle, _lib.MODES[self.mode], vox._ptr(self.coords), vox._ptr(self.channels), vox._ptr(self.radii), self.rs,
+    def views_args(self, vox, coords=None, channels=None):
+        """The arguments mvx_forward_views, mvx_forward_views_sum, mvx_score_views, mvx_moments_views and
+        mvx_moments_backward_views begin with (mvx_select_views takes the same values with the mode behind radii_type:
+        `Voxelizer._select`). coords / channels: the tensors autograd saved, in backward()."""
+        return (vox._handle, _lib.MODES[self.mode], vox._ptr(self.coords if coords is None else coords),
+                vox._ptr(self.channels if channels is None else channels), vox._ptr(self.radii), self.rs,
                 vox._radii_type_code(), self.N, self.C, C.addressof(self.xforms), self.B)
 
 
@@ -1272,6 +1274,95 @@ class Voxelizer(BaseVoxelizer):
         return gc, gf
 
     # ------------------------------------------------------------------------------------------
+    # MOMENTS OF VIEWS (many poses or boxes of one shared cloud, each against its own target: mvx_moments_views)
+    def moments_views(self, coords, centers, channels, radii, target=None, num_channels=None, random_translation=0.0,
+                      random_rotation=False):
+        """The moments of the B grids forward_views would write with the same arguments - without the grids and without B copies
+        of the cloud: each view's atoms are selected on the device, gathered into a compact batch and walked once
+        (mvx_moments_views). The values are moments_batch's, bit for bit, on coords[index], the gathered channels and radii and
+        the offsets of select_views.
+
+        coords (N,3), centers (B,3), channels and radii as forward_views (transforms drawn per view in its RNG order); host
+        arrays are moved to the device. Needs output="torch". target: None, one (C,D,H,W) array shared by all views, or a
+        (B,C,D,H,W) array with one target per view (a target lives in box coordinates: views of different boxes want one
+        each), converted as moments_batch converts it. Returns a (B, C, 2) - with a target (B, C, 3) - float64 tensor on this
+        device; row b of a per-view call is, bit for bit, row b of the call that shares target[b]. A view that keeps no atom
+        gives exact zeros. Without a recorded graph the call is one library call (one stream synchronisation, for the
+        selection). Not part of the autograd graph unless the voxelizer was made with moments_grad=True: then, with grad mode on
+        and coords, features or centers that require grad, the views are selected once, the same call records a graph, and
+        backward() forms the per-(view, atom) rows (mvx_moments_backward_views) and sums them onto the shared atoms with
+        mvx_views_reduce - deterministic, no atomics. A target, radii or a sigma tensor that requires grad raises ValueError.
+        Not supported: what moments_batch does not support (use forward_views(...) and reduce the grids)."""
+        return self._moments_views(coords, centers, channels, radii, target, num_channels, random_translation, random_rotation)
+
+    def moments_posed_views(self, coords, centers, quaternions, translations, channels, radii, target=None, num_channels=None):
+        """moments_views with one explicit rigid pose per view (forward_posed_views' arguments and records): the moments of B
+        poses of ONE shared cloud - every pose's cross-correlation with a map in one call, the cloud handed over once. On a
+        moments_grad voxelizer `centers`, `quaternions` and `translations` that require grad get their gradients per view
+        (mvx_pose_grad_batch on the rows), next to coords and features."""
+        return self._moments_views(coords, centers, channels, radii, target, num_channels, posed=(quaternions, translations))
+
+    def _moments_views(self, coords, centers, channels, radii, target=None, num_channels=None, random_translation=0.0,
+                       random_rotation=False, posed=None):
+        """moments_views' body. posed: (quaternions, translations) of moments_posed_views."""
+        self._sum_guard(channels, "moments_views", "moments_views / moments_posed_views", "the moments are a tensor",
+                        "use forward_views(...) (forward_posed_views(...)) and reduce the grids instead")
+
+        def check(B, C_, offsets):
+            if target is not None:
+                shape, one = tuple(getattr(target, "shape", ())), self.grid_dimension(C_)
+                assert shape in (one, (B,) + one), f"target does not match dimension: {shape} vs {one} or {(B,) + one}"
+
+        record = self._mgrad and torch.is_grad_enabled()  # (as _moments_batch builds its call)
+        if record:
+            self._moments_grad_guard(radii, target)
+        with torch.enable_grad() if record else torch.no_grad():
+            call = self._views_call(coords, centers, channels, radii, num_channels, random_translation, random_rotation, posed,
+                                    device=True, score=record, check=check)
+
+        def run(index, offsets):
+            """One mvx_moments_views call, with the selection made before it or - index None - its own."""
+            with torch.no_grad():
+                T, stride = None, 0
+                if target is not None:
+                    T = (target if _is_torch(target) else torch.as_tensor(np.asarray(target))).to(device=self.device, dtype=torch.float32).contiguous()
+                    stride = call.C * int(self.dimension) ** 3 if T.dim() == 5 else 0  # (one target per view)
+                out = torch.empty((call.B, call.C, 2 if T is None else 3), dtype=torch.float64, device=self.device)
+                # (an empty selection: an empty tensor has no address, but a non-null index is what says "selected" to the library)
+                some = index is not None and int(offsets[-1]) > 0
+                pad = torch.empty(1, dtype=torch.int64, device=self.device) if (index is not None and not some) else None
+                _lib.check(self._lib.mvx_moments_views(
+                    *call.views_args(self), None if index is None else (index if some else pad).data_ptr(),
+                    offsets.ctypes.data if index is not None else None, self._ptr(T), stride, self._ptr(out), self._stream()))
+                return out, T
+
+        if not (record and call.grad):
+            return run(None, None)[0]
+        with torch.no_grad():
+            index, offsets = self._select(call)
+        call.index, call.offsets = index, offsets  # (backward(): the rows are laid out in selection order)
+        call.settings = self._grad_settings()
+        return _MomentsViewsFunction.apply(self, lambda: run(index, offsets), call, call.coords,
+                                           call.channels if call.mode == "features" else None, call.centers, call.pose)
+
+    def _moments_backward_views(self, spec, c, f, T, index, gm, need_features):
+        """(dL/dcoords (total, 3) float64, dL/dfeatures (total, C) or None) per (view, atom) row of the forward's selection for
+        dL/dm = gm (B, C, K), on the current stream. spec: the forward call's _Call with its selection; c, f: the shared
+        cloud's coords and features as autograd saved them; T: the target as the forward read it."""
+        self._same_settings(spec)
+        total = int(spec.offsets[-1])
+        g = gm.to(device=self.device, dtype=torch.float64).contiguous()
+        gc = torch.empty((total, 3), dtype=torch.float64, device=self.device)
+        gf = torch.empty((total, spec.C), dtype=self._tfp, device=self.device) if need_features else None
+        if total == 0 or spec.B == 0:  # no selected atom: no gradient rows
+            return gc, gf
+        stride = spec.C * int(self.dimension) ** 3 if (T is not None and T.dim() == 5) else 0
+        _lib.check(self._lib.mvx_moments_backward_views(
+            *spec.views_args(self, c, f if spec.mode == "features" else None), index.data_ptr(), spec.offsets.ctypes.data,
+            self._ptr(T), stride, self._ptr(g), self._ptr(gc), self._ptr(gf), self._stream()))
+        return gc, gf
+
+    # ------------------------------------------------------------------------------------------
     # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
     def score_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, random_translation=0.0,
                     random_rotation=False, per_atom=False):
@@ -1733,6 +1824,35 @@ if torch is not None:
                 gfeat = vox.views_reduce(gf * up[:, None].to(gf.dtype), index, spec.offsets, spec.N)
             gcen, gpose = _rigid_grads(vox, spec, c[index] if need_pose else None, gcs, cen, lengths, need_cen, need_pose)
             return None, None, None, None, gcoords, gfeat, gcen, gpose
+
+
+    class _MomentsViewsFunction(torch.autograd.Function):
+        """moments of B views of one shared cloud = moments(coords, features, centres, packed poses) on a moments_grad voxelizer:
+        the forward call as it runs without autograd, with the selection made before it (same kernels, same bits); backward =
+        mvx_moments_backward_views from the saved inputs, the target as the forward read it and the call's record, whose rows per
+        (view, atom) are summed onto the shared atoms with mvx_views_reduce, as _ScoreViewsFunction sums its own, and reduced to
+        centres and poses per view."""
+
+        @staticmethod
+        def forward(ctx, vox, run, spec, c, f, cen, pose):
+            out, T = run()
+            ctx.vox, ctx.spec = vox, spec
+            ctx.save_for_backward(c, f, cen, pose, T, spec.index)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, gm):
+            c, f, cen, pose, T, index = ctx.saved_tensors
+            need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[3:7]
+            vox, spec = ctx.vox, ctx.spec  # (spec.offsets: the selection's; spec.N: the atoms of the shared cloud)
+            gc, gf = vox._moments_backward_views(spec, c, f, T, index, gm, need_f)
+            # (through pinned memory: a pageable copy would synchronise the stream)
+            lengths = torch.from_numpy(np.diff(spec.offsets)).pin_memory().to(gc.device, non_blocking=True)
+            gcoords = vox.views_reduce(gc, index, spec.offsets, spec.N) if need_c else None
+            gfeat = vox.views_reduce(gf, index, spec.offsets, spec.N) if gf is not None else None
+            gcen, gpose = _rigid_grads(vox, spec, c[index] if need_pose else None, gc, cen, lengths, need_cen, need_pose)
+            return None, None, None, gcoords, gfeat, gcen, gpose
 
 
 def transform_on_device(coords, center, translation, quaternion):
