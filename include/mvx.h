@@ -370,6 +370,45 @@ int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const voi
                     double *scores, double *atom_scores, double *grad_coords, mvx_real *grad_features, void *stream);
 
 /*
+ * Second-order information of the scores of mvx_score_batch (no counterpart in the reference): per atom the gradient and the
+ * 3x3 Hessian of S_b with respect to the atom's position, and per molecule the gradient and the 6x6 Hessian of S_b under a rigid
+ * twist - what a Newton or Levenberg-Marquardt step on a pose needs. Everything is in the GRID frame: p_n is the position the
+ * pre-pass record holds for atom n, after centring and transform, relative to the box centre. The score splits by atom, so its
+ * Hessian with respect to the positions is block diagonal. With d = p_n - voxel centre, rho the density, u(v) = sum_c F[c,v]
+ * w[n,c] (types / single: F[type,v]), kfac with d rho / d p = kfac rho d, and e(v) = (double)(u rho) kfac - the product u rho in
+ * the handle's real type, as the gradient walk forms it - over the admitted voxels v of atom n:
+ *   s_n = sum_v (double)(u rho)                    mvx_score_batch's atom_scores, bit for bit
+ *   g_n = dS/dp_n = sum_v e d                      mvx_score_batch's grad_coords before the rotation is transposed onto it:
+ *                                                  the same bits on a call without rotation
+ *   H_n = (sum_v e) I + kfac sum_v e d d^T         symmetric, stored as (xx, xy, xz, yy, yz, zz), accumulated in float64
+ * The admitted set is held fixed: the truncation at the radius is not differentiated, as in every gradient of this library.
+ * Binary density gives g = 0 and H = 0 but scores. An atom with no admitted voxel gets exact zero rows. A twist xi = (tau,
+ * omega) about the pivot o_b moves the molecule's posed atoms to p' = R(omega) (p - o_b) + o_b + tau, R = exp([omega]x). With
+ * r_n = p_n - o_b, at xi = 0:
+ *   twist_grad[b] = (sum_n g_n, sum_n r_n x g_n)                                     (tau first, then omega)
+ *   twist_hess[b] = sum_n J_n^T H_n J_n, J_n = [ I | -[r_n]x ], plus sum_n 0.5 (g_n r_n^T + r_n g_n^T) - (g_n . r_n) I
+ *                   on the omega-omega block: symmetric to the bit, written in full, row-major
+ *   field, field_mol_stride, scores: as for mvx_score_batch
+ *   pivots:     (B, 3) double, device, grid frame, or NULL: the box centre (0, 0, 0) for every molecule. Under an explicit
+ *               pose (MVX_XF_POSE_PTR) the image of the centre is the translation rounded to float32.
+ *   atom_grad:  (sumN, 3) double or NULL; atom_hess: (sumN, 6) double or NULL
+ *   twist_grad: (B, 6) double or NULL; twist_hess: (B, 36) double or NULL (needs twist_grad)
+ * One walk of the atoms' boxes (one wave per atom record, eleven float64 lane partials, one fixed butterfly each), then one
+ * workgroup per molecule sums its atoms in a fixed order (each wave takes chunks of 64 atoms in order, a butterfly per wave,
+ * the waves in order): no atomics, a molecule's rows and values are bit for bit the same in any batch and across runs. In the
+ * reduction an atom whose g and H rows are all zero is skipped: its position may be NaN or infinite. A molecule without atoms
+ * gets zeros. Rows that are not handed out live in handle-owned workspace (80 bytes per atom). Outputs are fully overwritten.
+ * Pointers, staging and buffers as for mvx_score_batch; asynchronous on `stream`. MVX_ERR_INVALID before any device is touched
+ * for what mvx_score_batch rejects, in its order, then for channel-wise radii in features mode (not supported: the first-order
+ * mvx_score_batch serves them) and for twist_hess without twist_grad.
+ */
+int mvx_score_hessian_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                            double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                            int32_t B, int32_t C, const void *field, int64_t field_mol_stride, const double *pivots,
+                            double *scores, double *atom_grad, double *atom_hess, double *twist_grad, double *twist_hess,
+                            void *stream);
+
+/*
  * ONE grid for a whole batch (no counterpart in the reference): the sum, weighted or not, of the B grids the forward entries
  * would write for the same arguments, without those grids. With rho and w as for mvx_backward_batch and the atoms
  * n = 0 .. sumN-1 in the caller's order (molecule boundaries from offsets, a transform per molecule):

@@ -5,6 +5,7 @@
 // fully asynchronous on the caller's stream (no hidden device synchronisation). There is no CPU
 // fallback in this library: without a usable HIP device mvx_create fails.
 #include "mvx_grad.h"
+#include "mvx_hess.h"
 #include "mvx_internal.h"
 #include "mvx_moments.h"
 #include "mvx_plan.h"
@@ -126,6 +127,7 @@ struct mvx_handle : NoCopy {
     DevBuf pose_meta;  // mvx_pose_grad_batch: the call's offsets and records
     DevBuf grad_rpart; // radius gradients: per-atom / per-(channel, atom) partials of channel-wise radii and their stage sums
     DevBuf score_atoms; // mvx_score_batch without atom_scores: the per-atom scores its reduction reads, 8 bytes per atom
+    DevBuf hess_rows;   // mvx_score_hessian_batch: [s_n | g_n | H_n], 8 + 24 + 48 bytes per atom; rows handed out are not used
     // "grad_order" option: 0 atoms in the caller's order (the default), 1 in spatial order, XCD by XCD. The spatial order cuts
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
     // more than it saves (profiles/r05_grad.txt)
@@ -1401,13 +1403,20 @@ int mvx_set_sum_parts(mvx_handle *h, int32_t parts) {
 // (BWD_DENSITY: grad_sigma / grad_rscalar / grad_radii, each or NULL); mvx_score_batch (BWD_SCORE: `grad_out` is the constant
 // field, ScoreCall its stride and the score outputs; grad_coords and grad_features each or NULL); mvx_moments_backward_batch
 // (BWD_MOMENTS, one Backward per molecule chunk: `grad_out` is the chunk's float32 grids in handle-owned scratch, `moments` its
-// coefficients and the target)
-enum BackwardKind { BWD_PLAIN, BWD_RADII, BWD_DENSITY, BWD_SCORE, BWD_MOMENTS };
+// coefficients and the target); mvx_score_hessian_batch (BWD_HESS: mvx_score_batch's field, stride and scores in ScoreCall, its own
+// outputs and the pivots in HessCall; no grad_coords and no grad_features)
+enum BackwardKind { BWD_PLAIN, BWD_RADII, BWD_DENSITY, BWD_SCORE, BWD_MOMENTS, BWD_HESS };
 
 struct ScoreCall {
     int64_t mol_stride;  // 0 (one field for all molecules) or C * D^3
     double *scores;      // (B,)
     double *atom_scores; // (total,) or null: handle-owned workspace
+};
+
+struct HessCall {
+    const double *pivots;                 // (B, 3) device or null: the origin
+    double *atom_grad, *atom_hess;        // (total, 3), (total, 6), each or null: handle-owned workspace
+    double *twist_grad, *twist_hess;      // (B, 6), (B, 36), each or null
 };
 
 // What a backward call reads next to its Call and where its results go (outputs a kind does not have are null).
@@ -1419,6 +1428,8 @@ struct GradOut {
     double *grad_radii, *grad_sigma, *grad_rscalar;
     ScoreCall score; // BWD_SCORE only
     MomentsArgs moments{}; // BWD_MOMENTS only
+    HessCall hess{};       // BWD_HESS only
+    bool scoring() const { return kind == BWD_SCORE || kind == BWD_HESS; } // walks a constant field: ScoreCall is filled
 };
 
 namespace {
@@ -1443,7 +1454,7 @@ int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent 
             return fail(MVX_ERR_INVALID, "radii_type: scalar radii have no radius array for grad_radii (grad_radius_scalar gives dL/dr)");
         if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE)
             return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode");
-    } else if (o.kind == BWD_SCORE) { // (grad_coords, grad_features and atom_scores may all be null: scores alone)
+    } else if (o.scoring()) { // (grad_coords, grad_features and atom_scores may all be null: scores alone)
         if (o.score.mol_stride < 0) return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
         if (c.B > 0 && !o.score.scores) return fail(MVX_ERR_INVALID, "scores must not be null");
     } else if (!o.grad_coords && !o.grad_features) {
@@ -1454,7 +1465,7 @@ int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent 
 
 // ---- ... and, behind check_atoms, what a call with atoms must bring that reads the handle ----
 int check_backward_grid(const mvx_handle *h, const Call &c, const GradOut &o) {
-    const bool score = o.kind == BWD_SCORE;
+    const bool score = o.scoring();
     const size_t gsz = h->cfg.grid_type == MVX_GRID_BF16 ? 2 : (h->cfg.precision == 64 ? 8 : 4);
     const size_t D = (size_t)h->g.D;
     if (D * D * D * gsz >= ((size_t)1 << 32)) return fail(MVX_ERR_INVALID, "one channel of the grid must stay below 4 GiB");
@@ -1474,7 +1485,9 @@ int zero_density_grads(const GradOut &o, size_t nradii, hipStream_t s) {
 // ---- no atoms: no gradient rows; channel-wise radii still get their C zeros, sigma and a scalar radius their zero ----
 int backward_no_atoms(const Call &c, const GradOut &o) {
     if (int rc = zero_density_grads(o, c.radii_type == MVX_RADII_CHANNEL ? (size_t)c.C : 0, c.stream)) return rc;
-    if (o.kind == BWD_SCORE) HIP_TRY(hipMemsetAsync(o.score.scores, 0, (size_t)c.B * sizeof(double), c.stream)); // (every molecule scores 0)
+    if (o.scoring()) HIP_TRY(hipMemsetAsync(o.score.scores, 0, (size_t)c.B * sizeof(double), c.stream)); // (every molecule scores 0)
+    if (o.hess.twist_grad) HIP_TRY(hipMemsetAsync(o.hess.twist_grad, 0, (size_t)c.B * 6 * sizeof(double), c.stream));
+    if (o.hess.twist_hess) HIP_TRY(hipMemsetAsync(o.hess.twist_hess, 0, (size_t)c.B * 36 * sizeof(double), c.stream));
     return MVX_OK;
 }
 
@@ -1563,6 +1576,23 @@ struct Backward {
         HIP_TRY(launch_score_reduce(sa.atom_scores, in.offsets, c.B, o.score.scores, s));
         return MVX_OK;
     }
+    // BWD_HESS: one walk over the field writes s_n, g_n and H_n of every atom (the caller's arrays, or workspace), then every
+    // molecule's atoms are summed in a fixed order: the scores as mvx_score_batch sums them, and the twist gradient and Hessian
+    int hess() {
+        if (int rc = ensure(h->hess_rows, (size_t)total * 10 * sizeof(double))) return rc;
+        double *ws = reinterpret_cast<double *>(h->hess_rows.p);
+        HessArgs ha;
+        ha.atom_scores = ws;
+        ha.atom_grad = o.hess.atom_grad ? o.hess.atom_grad : ws + (size_t)total;
+        ha.atom_hess = o.hess.atom_hess ? o.hess.atom_hess : ws + (size_t)total * 4;
+        ha.mol_stride = o.score.mol_stride;
+        HIP_TRY(launch_score_hess(ga, ha, key, s));
+        HIP_TRY(launch_score_reduce(ha.atom_scores, in.offsets, c.B, o.score.scores, s));
+        if (o.hess.twist_grad)
+            HIP_TRY(launch_twist_reduce(ga.rec, ha.atom_grad, ha.atom_hess, in.offsets, o.hess.pivots, c.B, o.hess.twist_grad,
+                                        o.hess.twist_hess, s));
+        return MVX_OK;
+    }
     // BWD_MOMENTS: the walk over the chunk's grids with the upstream formed from them, the coefficients and the target
     int moments() {
         HIP_TRY(launch_moments_grad(ga, o.moments, key, s));
@@ -1633,9 +1663,15 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
     int rc = check_backward(h, c, o, e);
     if (rc) return rc;
     const bool radii_by_channel = o.grad_radii && c.radii_type == MVX_RADII_CHANNEL;
-    if (e.total == 0 && !radii_by_channel && o.kind != BWD_DENSITY && !(o.kind == BWD_SCORE && c.B > 0)) return MVX_OK;
-    if ((rc = reject(check_atoms(c, e, o.grad_out, o.kind == BWD_SCORE ? "coords / field must not be null" : "coords / grad_out must not be null")))) return rc;
+    if (e.total == 0 && !radii_by_channel && o.kind != BWD_DENSITY && o.kind != BWD_HESS && !(o.kind == BWD_SCORE && c.B > 0)) return MVX_OK;
+    if ((rc = reject(check_atoms(c, e, o.grad_out, o.scoring() ? "coords / field must not be null" : "coords / grad_out must not be null")))) return rc;
     if (e.total > 0 && (rc = check_backward_grid(h, c, o))) return rc;
+    if (o.kind == BWD_HESS) { // its own rules, behind every rule of mvx_score_batch
+        if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES)
+            return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii in features mode are not supported by mvx_score_hessian_batch (mvx_score_batch gives their first-order gradients)");
+        if (o.hess.twist_hess && !o.hess.twist_grad) return fail(MVX_ERR_INVALID, "twist_hess needs twist_grad");
+        if (c.B == 0) return MVX_OK;
+    }
     CallScope scope(h, c.stream);
     if (scope.rc) return scope.rc;
     if (e.total == 0) return backward_no_atoms(c, o);
@@ -1647,6 +1683,7 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
     case BWD_RADII: rc = b.radii(); break;
     case BWD_DENSITY: rc = b.density(); break;
     case BWD_MOMENTS: rc = b.moments(); break; // (not reached: moments_backward runs its chunks itself)
+    case BWD_HESS: rc = b.hess(); break;
     }
     return rc ? rc : release_slot(b.in.slot, c.stream);
 }
@@ -1765,6 +1802,15 @@ int mvx_score_batch(mvx_handle *h, int32_t mode, const double *coords, const voi
                     void *grad_features, void *stream) {
     return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream),
                          {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_mol_stride, scores, atom_scores}});
+}
+
+int mvx_score_hessian_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                            double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms, int32_t B,
+                            int32_t C, const void *field, int64_t field_mol_stride, const double *pivots, double *scores,
+                            double *atom_grad, double *atom_hess, double *twist_grad, double *twist_hess, void *stream) {
+    GradOut o{BWD_HESS, field, nullptr, nullptr, nullptr, nullptr, nullptr, {field_mol_stride, scores, nullptr}};
+    o.hess = {pivots, atom_grad, atom_hess, twist_grad, twist_hess};
+    return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream), o);
 }
 
 int mvx_moments_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,

@@ -1,8 +1,8 @@
 // mvx_grad.h - what the C-ABI TU (mvx_capi.hip) needs of the backward family: the argument records and launchers of the
 // four walks (mvx_grad.hip, mvx_grad_radii.hip, mvx_score.hip, mvx_moments_grad.hip) and of the reductions (mvx_grad_radii.hip,
 // mvx_grad_density.hip), and the host-side dispatch (WalkKey / for_walk, for_moments_walk, for_real) those files launch through.
-// Included by mvx_capi.hip and, through mvx_grad_device.h, by the seven kernel files of the family (those six, mvx_pose.hip and
-// mvx_views_reduce.hip). WalkKey, for_walk and for_real are plain host C++: tests/test_walk_dispatch_host.py compiles them alone.
+// Included by mvx_capi.hip and, through mvx_grad_device.h, by the eight kernel files of the family (those six, mvx_pose.hip,
+// mvx_views_reduce.hip and mvx_hess.hip, whose own records and launchers are in mvx_hess.h). WalkKey, for_walk and for_real are plain host C++: tests/test_walk_dispatch_host.py compiles them alone.
 #pragma once
 #include <type_traits>
 

@@ -96,6 +96,8 @@ SIGNATURES = {
     "mvx_backward_density_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp]),
     "mvx_score_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mvx_score_hessian_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp]),
     "mvx_forward_sum_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp]),
     "mvx_forward_views_sum": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
     "mvx_set_sum_parts": (C.c_int, [Handle, _i32]),

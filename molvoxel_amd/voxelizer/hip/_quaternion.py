@@ -38,3 +38,25 @@ def rotate(points: np.ndarray, quaternion) -> np.ndarray:
     conj = (quaternion[0], quaternion[1] * -1, quaternion[2] * -1, quaternion[3] * -1)
     _, rx, ry, rz = _hamilton(_hamilton(quaternion, (np.zeros_like(x), x, y, z)), conj)
     return np.stack([rx, ry, rz], axis=-1)
+
+
+def apply_twist(quaternions, translations, twist):
+    """(q', t') of the poses (quaternions (B, 4), translations (B, 3)) moved by the twists xi = (tau, omega) (B, 6) that
+    score_hessian_posed_batch differentiates along: q' = u (x) q with u = (cos(|w|/2), sin(|w|/2) w/|w|) the unit quaternion of
+    the rotation vector w = omega, and t' = t + tau. With the pivot at the image of the centre (the default of
+    score_hessian_posed_batch) the posed atoms move to p' = exp([omega]x) (p - t) + t + tau exactly; q is used as given (an
+    unnormalised q keeps its norm). Torch ops in float64 on the inputs' device; safe at |w| = 0."""
+    import torch
+
+    def as_f64(x, like=None):
+        x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+        return x.to(dtype=torch.float64) if like is None else x.to(device=like.device, dtype=torch.float64)
+
+    q = as_f64(quaternions)
+    t, xi = as_f64(translations, q), as_f64(twist, q)
+    tau, w = xi[:, :3], xi[:, 3:]
+    half = 0.5 * torch.linalg.vector_norm(w, dim=1, keepdim=True)
+    # sin(|w|/2) w/|w| = 0.5 sinc(|w|/2) w, with torch.sinc(x) = sin(pi x) / (pi x) and sinc(0) = 1
+    v = 0.5 * torch.sinc(half / math.pi) * w
+    u = (torch.cos(half)[:, 0], v[:, 0], v[:, 1], v[:, 2])
+    return torch.stack(_hamilton(u, (q[:, 0], q[:, 1], q[:, 2], q[:, 3])), dim=1), t + tau

@@ -29,6 +29,7 @@ Entries, next to the reference's `forward_features / forward_types / forward_sin
   forward_views, select_views  B boxes of ONE shared point cloud, without B copies of it
   forward_sum, forward_views_sum  one float32 grid, the (weighted) sum of a batch's or the views' grids; `set_sum_parts`
   score_batch, score_views     sum(field * grid) per molecule or view without the grids, with gradients
+  score_hessian_batch          the scores with their gradient and Hessian under a rigid twist, per-atom Hessians (apply_twist moves poses)
   forward_posed_* / select_posed_views / score_posed_*  the same with explicit rigid poses p = q (x - c) conj(q) + t
                                instead of random transforms; on a differentiable voxelizer the poses get gradients
 
@@ -42,6 +43,7 @@ import numpy as np
 
 from ..contract import BaseVoxelizer
 from . import _lib
+from ._quaternion import apply_twist  # noqa: F401  (exported here, beside transform_on_device)
 from .transform import RandomTransform, draw_forward_transform
 
 try:  # torch is plumbing (device memory + streams); the library also works without it
@@ -1452,6 +1454,76 @@ class Voxelizer(BaseVoxelizer):
         # (with fgrad, backward() repeats the call as forward_sum: same offsets and records, the random draws included)
         out = _ScoreFunction.apply(self, run, call, per_atom, call.coords, feat, call.centers, call.pose, field if fgrad else None)
         return out if per_atom else out[0]
+
+    # ------------------------------------------------------------------------------------------
+    # SECOND ORDER (per-atom and rigid-twist Hessians of the scores: mvx_score_hessian_batch)
+    def score_hessian_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False):
+        """The scores of score_batch with what a Newton step on a rigid pose needs: per molecule the gradient (B, 6) and the
+        Hessian (B, 6, 6) of S_b under a twist xi = (tau, omega) about a pivot o_b, which moves the molecule's atoms in the grid
+        frame (after centring, relative to the box centre) to p' = exp([omega]x) (p - o_b) + o_b + tau. One more walk of the
+        atoms' boxes: the score splits by atom, so its Hessian with respect to the positions is one symmetric 3x3 block per
+        atom, H_n = (sum_v e) I + kfac sum_v e d d^T over the voxels and with the terms e of the gradient walk; the admitted set
+        is held fixed, as for every gradient here. The 6x6 is sum_n J_n^T H_n J_n with J_n = [I | -[r_n]x], r_n = p_n - o_b, plus
+        sum_n 0.5 (g_n r_n^T + r_n g_n^T) - (g_n . r_n) I on the omega-omega block; it is symmetric to the bit.
+
+        coords ... field, num_channels: score_batch's arguments, without random transforms - a Newton step needs the pose the
+        caller knows. pivots: (B, 3) in the grid frame, or None: the box centre. Needs output="torch".
+        Returns (scores (B,), twist_grad (B, 6), twist_hess (B, 6, 6)), float64 on this device; with per_atom=True also
+        (atom_grad (N, 3), atom_hess (N, 6)): dS/dp_n and H_n as (xx, xy, xz, yy, yz, zz), in the grid frame. The scores are
+        score_batch's bits, atom_grad those of its dS/dcoords on an unrotated call. Binary density gives zero derivatives but
+        scores; an atom that reaches no voxel has exact zero rows and does not enter the sums. Deterministic, no atomics: a
+        molecule's values do not depend on its batch. Plain values, NOT part of the autograd graph: inputs that require grad are
+        read as values. Channel-wise radii with features raise NotImplementedError."""
+        return self._score_hessian(coords, offsets, centers, channels, radii, field, num_channels, pivots, per_atom)
+
+    def score_hessian_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, field,
+                                  num_channels=None, pivots=None, per_atom=False):
+        """score_hessian_batch with one explicit rigid pose per molecule (forward_posed_batch's arguments and records).
+        pivots=None: `translations` rounded to float32 and widened - the point the record maps the centre to - so that
+        `apply_twist(quaternions, translations, xi)` realises the twist xi exactly."""
+        self._hessian_guard(channels)
+        self._check_pose(np.asarray(offsets).shape[0] - 1, centers, quaternions, translations)
+        return self._score_hessian(coords, offsets, centers, channels, radii, field, num_channels, pivots, per_atom,
+                                   posed=(quaternions, translations))
+
+    def _hessian_guard(self, channels):
+        """What a Hessian call refuses before it looks at anything else."""
+        if self.output != "torch":
+            raise ValueError("score_hessian_batch / score_hessian_posed_batch need output='torch': the results are tensors on the "
+                             "voxelizer's device")
+        if self.is_radii_type_channel_wise and channels is not None and channels.ndim != 1:
+            raise NotImplementedError("score_hessian_batch does not support channel-wise radii with features: score_posed_batch "
+                                      "(score_batch) on a differentiable voxelizer gives their first-order gradients")
+
+    def _score_hessian(self, coords, offsets, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False,
+                       posed=None):
+        """score_hessian_batch's body. posed: (quaternions, translations) of score_hessian_posed_batch."""
+        self._hessian_guard(channels)
+
+        def check(B, C_, offsets):
+            self._check_args_score(field, B, C_)
+            if pivots is not None:
+                assert tuple(pivots.shape) == (B, 3), f"pivots does not match dimension: {tuple(pivots.shape)} vs {(B, 3)}"
+
+        with torch.no_grad():  # (plain values: inputs that require grad are read as values)
+            call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, posed=posed, device=True, check=check)
+            F = self._field_tensor(field)
+            B, N = call.B, call.N
+            stride = call.C * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per molecule)
+            piv = pivots
+            if piv is None and posed is not None:  # the image of the centre: the translation as the record holds it
+                piv = (posed[1] if _is_torch(posed[1]) else torch.as_tensor(np.asarray(posed[1], dtype=np.float64))).to(torch.float32)
+            if piv is not None:
+                piv = (piv if _is_torch(piv) else torch.as_tensor(np.asarray(piv, dtype=np.float64)))
+                piv = piv.to(device=self.device, dtype=torch.float64).contiguous()
+            scores = torch.empty(B, dtype=torch.float64, device=self.device)
+            tg = torch.empty((B, 6), dtype=torch.float64, device=self.device)
+            th = torch.empty((B, 6, 6), dtype=torch.float64, device=self.device)
+            ag = torch.empty((N, 3), dtype=torch.float64, device=self.device) if per_atom else None
+            ah = torch.empty((N, 6), dtype=torch.float64, device=self.device) if per_atom else None
+            _lib.check(self._lib.mvx_score_hessian_batch(*call.batch_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores),
+                                                         self._ptr(ag), self._ptr(ah), self._ptr(tg), self._ptr(th), self._stream()))
+        return (scores, tg, th, ag, ah) if per_atom else (scores, tg, th)
 
     # ------------------------------------------------------------------------------------------
     # SCORES OF VIEWS (many poses or boxes of one shared cloud against a field: mvx_score_views / mvx_views_reduce)
