@@ -602,6 +602,31 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
                     double *scores, double *atom_scores, double *grad_coords, mvx_real *grad_features, void *stream);
 
 /*
+ * Second-order information of the scores of B views of ONE shared cloud (no counterpart in the reference): mvx_score_hessian_batch
+ * on the compact batch mvx_score_views walks - what a Newton or Levenberg-Marquardt step on each of B poses of one ligand needs,
+ * without B copies of the ligand. The cloud, `mode`, radii, the B host records, index, offsets_host, field and field_view_stride
+ * are those of mvx_score_views; pivots and the outputs follow mvx_score_hessian_batch, per view instead of per molecule.
+ *   index == NULL:  the entry selects the views' atoms itself (ONE stream synchronisation) and ignores offsets_host. Only the
+ *                   per-view outputs may be asked for: atom_grad and atom_hess must be NULL.
+ *   index != NULL:  a selection mvx_select_views returned for the same cloud, radii and records; the entry does not synchronise.
+ *                   With total = offsets_host[B]: atom_grad (total, 3) double, atom_hess (total, 6) double, each or NULL, in
+ *                   selection order: row k belongs to atom index[k] of its view. mvx_views_reduce sums such rows onto the atoms.
+ *   pivots:         (B, 3) double, device, grid frame, one per view, or NULL: the box centre.
+ *   scores (B,), twist_grad (B, 6) or NULL, twist_hess (B, 36) or NULL (needs twist_grad): double, device, fully overwritten.
+ * Every value is the bit mvx_score_hessian_batch gives for coords[index], the gathered channels and radii, the selection's
+ * offsets and the same records; against the cloud repeated B times the rows of kept atoms are the same bits, and a view's scores,
+ * twist_grad and twist_hess are the same bits when the view keeps the whole cloud. A view that keeps no atom gets exact zeros;
+ * N == 0 writes zeros; B == 0 writes nothing. Deterministic, asynchronous on `stream` (apart from the selection).
+ * MVX_ERR_INVALID before any device is touched for what mvx_score_views rejects, in its order - atom_grad and atom_hess in the
+ * place of its per-row outputs -, then for channel-wise radii in features mode and for twist_hess without twist_grad.
+ */
+int mvx_score_hessian_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                            double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                            const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
+                            const double *pivots, double *scores, double *atom_grad, double *atom_hess, double *twist_grad,
+                            double *twist_hess, void *stream);
+
+/*
  * The moments of B views of ONE shared cloud, without the grids and without B copies of the cloud (no counterpart in the
  * reference): mvx_moments_batch on the compact batch mvx_forward_views voxelizes. The cloud, `mode`, radii and the B host records
  * are those of mvx_forward_views; every array is a device array (centre and pose pointers point into device memory).
@@ -668,6 +693,30 @@ int mvx_moments_backward_views(mvx_handle *h, int32_t mode, const double *coords
 enum mvx_row_type { MVX_ROW_FLOAT = 0, MVX_ROW_DOUBLE = 1 };
 int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets_host, int32_t B, int64_t N, const void *rows,
                      int32_t width, int32_t row_type, void *out, void *stream);
+
+/*
+ * One Levenberg-Marquardt bookkeeping step for B rigid poses in one launch (no counterpart in the reference): what lies between
+ * two evaluations of mvx_score_hessian_batch / mvx_score_hessian_views in a damped Newton refinement that maximises the scores.
+ * One thread per pose, float64, no atomics, no host read. Every array is a device array. The current state, read and written:
+ *   q (B, 4), t (B, 3): the pose; S (B,), G (B, 6), H (B, 36): its score, twist gradient and twist Hessian; lam (B,): the damping;
+ *   taken, dropped (B,) int32: the accepted steps, and the steps dropped in a row.
+ * The trial: q2 (B, 4), t2 (B, 3): written, and read first when have_trial is set; S2 (B,), G2 (B, 6), H2 (B, 36): the evaluation
+ * at (q2, t2), read when have_trial is set, NULL otherwise. xi: (B, 6) or NULL, the twist of the new trial. Per pose, in order:
+ *   1. with have_trial and dropped < max_dropped: S2 > S (false for a NaN: a non-finite trial is dropped) makes the trial the
+ *      state - q, t, S, G, H copied bit for bit, lam *= lam_down, taken += 1, dropped = 0; otherwise lam *= lam_up, dropped += 1.
+ *   2. dropped >= max_dropped: the pose is finished: q2 = q, t2 = t, xi = 0; nothing else changes, on this or any later call.
+ *   3. otherwise (-H + lam I) xi = G by Gaussian elimination with partial pivoting on the full 6x6, and (q2, t2) the pose moved by
+ *      the twist xi = (tau, omega): q2 = u (x) q with u = (cos(|omega|/2), sin(|omega|/2) omega/|omega|), t2 = t + tau; omega = 0
+ *      gives q2 = q exactly. A zero pivot, or a non-finite component of xi, q, t, lam, q2 or t2: xi = 0 and (q2, t2) = (q, t) - the
+ *      next call sees S2 == S, drops the step and raises lam, so that a singular or NaN system damps itself out.
+ * With the pivots at their default (the translation rounded to float32) the trial realises the twist exactly. A pose's values do
+ * not depend on its batch; two runs give the same bits. Asynchronous on `stream`. MVX_ERR_INVALID before any device is touched
+ * for: B < 0; a NULL q, t, S, G, H, lam, taken, dropped, q2 or t2 with B > 0; a NULL S2, G2 or H2 with have_trial and B > 0;
+ * max_dropped < 1; lam_down or lam_up not finite or <= 0; a NULL handle. B == 0: MVX_OK.
+ */
+int mvx_lm_step(mvx_handle *h, int32_t B, int32_t have_trial, double lam_down, double lam_up, int32_t max_dropped, double *q,
+                double *t, double *S, double *G, double *H, double *lam, int32_t *taken, int32_t *dropped, double *q2, double *t2,
+                const double *S2, const double *G2, const double *H2, double *xi, void *stream);
 
 /*
  * Replaces do_transform on an (N,3) fp64 point cloud (numpy/transform.py:44-60): out = transformed coords.

@@ -7,6 +7,7 @@
 #include "mvx_grad.h"
 #include "mvx_hess.h"
 #include "mvx_internal.h"
+#include "mvx_lm.h"
 #include "mvx_moments.h"
 #include "mvx_plan.h"
 #include "mvx_pose.h"
@@ -14,6 +15,7 @@
 #include "mvx_views.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1884,6 +1886,42 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
     return backward_impl(h, batch, {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_view_stride, scores, atom_scores}});
 }
 
+// The Hessians of B views: mvx_score_views' rules, selection and gather, then mvx_score_hessian_batch's walk and reductions on the
+// compact batch. The two rules of that entry are judged here, behind the stride and before a device is touched: backward_impl
+// would find them only behind the gather.
+int mvx_score_hessian_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                            double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
+                            const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
+                            const double *pivots, double *scores, double *atom_grad, double *atom_hess, double *twist_grad,
+                            double *twist_hess, void *stream) {
+    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream);
+    // ---- what is checked before any device is touched ----
+    const bool per_row = atom_grad || atom_hess;
+    Extent e; // of the caller's selection
+    const char *own = nullptr;
+    if (field_view_stride < 0) own = "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)";
+    else if (B > 0 && !scores) own = "scores must not be null";
+    else if (!index && per_row) own = ROWS_NEED_INDEX;
+    else if (index && B > 0) own = bad_view_offsets(offsets_host, B, e);
+    if (!own && B > 0 && N > 0) {
+        if (mode == MODE_FEATURES && !channels) own = "channels must not be null";
+        else if (!field && (!index || e.total > 0)) own = "field must not be null";
+    }
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (field_view_stride != 0 && (uint64_t)field_view_stride != (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D)
+        return fail(MVX_ERR_INVALID, "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)");
+    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES)
+        return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii in features mode are not supported by mvx_score_hessian_views (mvx_score_views gives their first-order gradients)");
+    if (twist_hess && !twist_grad) return fail(MVX_ERR_INVALID, "twist_hess needs twist_grad");
+    if (B == 0) return MVX_OK;
+    ViewBatch batch(v); // (N == 0: B views without atoms, exact zeros, whatever the caller's selection says)
+    if (N > 0) // (no index: the selection itself, one stream synchronisation)
+        if (int rc = compact_views(h, v, false, index, offsets_host, batch)) return rc;
+    GradOut o{BWD_HESS, field, nullptr, nullptr, nullptr, nullptr, nullptr, {field_view_stride, scores, nullptr}};
+    o.hess = {pivots, atom_grad, atom_hess, twist_grad, twist_hess};
+    return backward_impl(h, batch, o);
+}
+
 // The moments of B views: the selection (the caller's, or made here) and the gather of mvx_score_views, then mvx_moments_batch's
 // walk on the compact batch, each view against its own target where the stride says so. What reads the handle (the stride against
 // C * D^3, sum_config) is checked before a device is touched; run_summed checks the batch again, to no effect.
@@ -1964,6 +2002,27 @@ int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets
     if (int rc = stage_meta(h, h->view_red_off, c, false, 0, in)) return rc;
     HIP_TRY(launch_view_reduce(index, in.offsets, B, N, rows, width, f64, out, c.stream));
     return release_slot(in.slot, c.stream);
+}
+
+int mvx_lm_step(mvx_handle *h, int32_t B, int32_t have_trial, double lam_down, double lam_up, int32_t max_dropped, double *q,
+                double *t, double *S, double *G, double *H, double *lam, int32_t *taken, int32_t *dropped, double *q2, double *t2,
+                const double *S2, const double *G2, const double *H2, double *xi, void *stream) {
+    // ---- what is checked before any device is touched ----
+    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (B > 0 && (!q || !t || !S || !G || !H || !lam || !taken || !dropped || !q2 || !t2))
+        return fail(MVX_ERR_INVALID, "q, t, S, G, H, lam, taken, dropped, q2 and t2 must not be null");
+    if (B > 0 && have_trial && (!S2 || !G2 || !H2)) return fail(MVX_ERR_INVALID, "S2, G2 and H2 must not be null with have_trial");
+    if (max_dropped < 1) return fail(MVX_ERR_INVALID, "max_dropped must be >= 1");
+    if (!(lam_down > 0.0) || !(lam_up > 0.0) || !std::isfinite(lam_down) || !std::isfinite(lam_up))
+        return fail(MVX_ERR_INVALID, "lam_down and lam_up must be finite and > 0");
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (B == 0) return MVX_OK;
+
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    CallScope scope(h, s);
+    if (scope.rc) return scope.rc;
+    HIP_TRY(launch_lm_step({B, have_trial != 0, max_dropped, lam_down, lam_up, q, t, S, G, H, lam, taken, dropped, q2, t2, S2, G2, H2, xi}, s));
+    return MVX_OK;
 }
 
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,

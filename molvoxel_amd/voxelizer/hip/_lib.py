@@ -105,6 +105,10 @@ SIGNATURES = {
     "mvx_moments_backward_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mvx_score_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                   _vp, _vp]),
+    "mvx_score_hessian_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp,
+                                          _vp, _vp, _vp, _vp, _vp]),
+    "mvx_lm_step": (C.c_int, [Handle, _i32, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp]),
     "mvx_moments_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mvx_moments_backward_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp,
                                              _vp, _vp, _vp]),

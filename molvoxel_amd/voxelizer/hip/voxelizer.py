@@ -30,6 +30,8 @@ Entries, next to the reference's `forward_features / forward_types / forward_sin
   forward_sum, forward_views_sum  one float32 grid, the (weighted) sum of a batch's or the views' grids; `set_sum_parts`
   score_batch, score_views     sum(field * grid) per molecule or view without the grids, with gradients
   score_hessian_batch          the scores with their gradient and Hessian under a rigid twist, per-atom Hessians (apply_twist moves poses)
+  score_hessian_views          the same for B views of ONE shared cloud
+  lm_step, refine_posed_batch, refine_posed_views  damped Newton refinement of B poses together, each step decided on the device
   forward_posed_* / select_posed_views / score_posed_*  the same with explicit rigid poses p = q (x - c) conj(q) + t
                                instead of random transforms; on a differentiable voxelizer the poses get gradients
 
@@ -96,6 +98,22 @@ class _Call:
         return (vox._handle, _lib.MODES[self.mode], vox._ptr(self.coords if coords is None else coords),
                 vox._ptr(self.channels if channels is None else channels), vox._ptr(self.radii), self.rs,
                 vox._radii_type_code(), self.N, self.C, C.addressof(self.xforms), self.B)
+
+
+class LMState:
+    """The state lm_step works on, B poses as tensors on the voxelizer's device: q (B, 4), t (B, 3): the poses; S (B,), G (B, 6),
+    H (B, 6, 6): their scores, twist gradients and twist Hessians (float64, contiguous); lam (B,): the damping; taken, dropped
+    (B,) int32: accepted steps, and steps dropped in a row (zeros when not given). q2, t2, xi: the trial poses and their twists,
+    made by the first lm_step and reused."""
+
+    __slots__ = ("q", "t", "S", "G", "H", "lam", "taken", "dropped", "q2", "t2", "xi")
+
+    def __init__(self, q, t, S, G, H, lam, taken=None, dropped=None):
+        B = int(q.shape[0])
+        self.q, self.t, self.S, self.G, self.H, self.lam = q, t, S, G, H, lam
+        self.taken = torch.zeros(B, dtype=torch.int32, device=q.device) if taken is None else taken
+        self.dropped = torch.zeros(B, dtype=torch.int32, device=q.device) if dropped is None else dropped
+        self.q2 = self.t2 = self.xi = None
 
 
 class Voxelizer(BaseVoxelizer):
@@ -1524,6 +1542,168 @@ class Voxelizer(BaseVoxelizer):
             _lib.check(self._lib.mvx_score_hessian_batch(*call.batch_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores),
                                                          self._ptr(ag), self._ptr(ah), self._ptr(tg), self._ptr(th), self._stream()))
         return (scores, tg, th, ag, ah) if per_atom else (scores, tg, th)
+
+    def score_hessian_views(self, coords, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False):
+        """score_hessian_batch for B views of ONE shared cloud, without B copies of it: each view's atoms are selected on the
+        device, gathered into a compact batch and walked once (mvx_score_hessian_views). The values are score_hessian_batch's,
+        bit for bit, on coords[index], the gathered channels and the offsets of select_views.
+
+        coords (N,3), centers (B,3), channels and radii as score_views, without random transforms; field (C,D,H,W), shared, or
+        (B,C,D,H,W), one per view; pivots (B,3) in the grid frame, or None: the box centre. Needs output="torch".
+        Returns (scores (B,), twist_grad (B, 6), twist_hess (B, 6, 6)), float64 on this device: one library call, one stream
+        synchronisation (the selection). With per_atom=True the call selects first and also returns (atom_grad (total, 3),
+        atom_hess (total, 6), index, offsets): the rows in selection order - row k belongs to atom index[k] of its view;
+        views_reduce sums them onto the shared atoms - and (index, offsets) as select_views returns them. Plain values, NOT part
+        of the autograd graph. Channel-wise radii with features raise NotImplementedError."""
+        return self._score_hessian_views(coords, centers, channels, radii, field, num_channels, pivots, per_atom)
+
+    def score_hessian_posed_views(self, coords, centers, quaternions, translations, channels, radii, field, num_channels=None,
+                                  pivots=None, per_atom=False):
+        """score_hessian_views with one explicit rigid pose per view (forward_posed_views' arguments and records): the scores,
+        twist gradients and twist Hessians of B poses of ONE shared cloud. pivots=None: `translations` rounded to float32 and
+        widened, so that `apply_twist(quaternions, translations, xi)` - or lm_step - realises the twist xi exactly."""
+        self._hessian_guard(channels)
+        self._check_pose(int(getattr(centers, "shape", (0,))[0]), centers, quaternions, translations)
+        return self._score_hessian_views(coords, centers, channels, radii, field, num_channels, pivots, per_atom,
+                                         posed=(quaternions, translations))
+
+    def _hessian_pivots(self, pivots, posed):
+        """The pivots of a Hessian call as the library reads them, or None (the box centre). posed without pivots: the image of
+        the centre, the translation as the record holds it."""
+        piv = pivots
+        if piv is None and posed is not None:
+            piv = (posed[1] if _is_torch(posed[1]) else torch.as_tensor(np.asarray(posed[1], dtype=np.float64))).to(torch.float32)
+        if piv is None:
+            return None
+        piv = piv if _is_torch(piv) else torch.as_tensor(np.asarray(piv, dtype=np.float64))
+        return piv.to(device=self.device, dtype=torch.float64).contiguous()
+
+    def _score_hessian_views(self, coords, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False,
+                             posed=None):
+        """score_hessian_views' body. posed: (quaternions, translations) of score_hessian_posed_views."""
+        self._hessian_guard(channels)
+
+        def check(B, C_, offsets):
+            self._check_args_score(field, B, C_)
+            if pivots is not None:
+                assert tuple(pivots.shape) == (B, 3), f"pivots does not match dimension: {tuple(pivots.shape)} vs {(B, 3)}"
+
+        with torch.no_grad():  # (plain values: inputs that require grad are read as values)
+            call = self._views_call(coords, centers, channels, radii, num_channels, posed=posed, device=True, check=check)
+            F = self._field_tensor(field)
+            B = call.B
+            stride = call.C * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per view)
+            piv = self._hessian_pivots(pivots, posed)
+            index = offsets = None
+            total = 0
+            if per_atom:
+                index, offsets = self._select(call)
+                total = int(offsets[-1])
+            f64 = dict(dtype=torch.float64, device=self.device)
+            scores, tg, th = torch.empty(B, **f64), torch.empty((B, 6), **f64), torch.empty((B, 6, 6), **f64)
+            ag = torch.empty((total, 3), **f64) if per_atom else None
+            ah = torch.empty((total, 6), **f64) if per_atom else None
+            # (an empty selection: an empty tensor has no address, but a non-null index is what says "selected" to the library)
+            some = per_atom and total > 0
+            pad = torch.empty(1, dtype=torch.int64, device=self.device) if (per_atom and not some) else None
+            _lib.check(self._lib.mvx_score_hessian_views(
+                *call.views_args(self), None if index is None else (index if some else pad).data_ptr(),
+                offsets.ctypes.data if index is not None else None, self._ptr(F), stride, self._ptr(piv), self._ptr(scores),
+                self._ptr(ag) if some else None, self._ptr(ah) if some else None, self._ptr(tg), self._ptr(th), self._stream()))
+        return (scores, tg, th, ag, ah, index, offsets) if per_atom else (scores, tg, th)
+
+    # ------------------------------------------------------------------------------------------
+    # DAMPED NEWTON REFINEMENT OF POSES (mvx_lm_step between two Hessian evaluations; nothing comes to the host in between)
+    def lm_step(self, state, trial=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3):
+        """One Levenberg-Marquardt bookkeeping step for the B poses of `state` (an LMState), on the device and without a host
+        read (mvx_lm_step). trial: (S2, G2, H2), the evaluation at (state.q2, state.t2), or None before the first trial. Per
+        pose: a trial with S2 > S becomes the state (lam *= lam_down, taken += 1, dropped = 0), any other is dropped
+        (lam *= lam_up, dropped += 1); a pose with dropped >= max_dropped is finished and stays; every other pose gets
+        xi = solve(-H + lam I, G) and the next trial (q2, t2) = apply_twist(q, t, xi) (a singular or non-finite system: xi = 0).
+        state.q2, state.t2 and state.xi are allocated on the first call and reused. Returns state."""
+        B = int(state.q.shape[0])
+        for name, shape, dt in (("q", (B, 4), torch.float64), ("t", (B, 3), torch.float64), ("S", (B,), torch.float64),
+                                ("G", (B, 6), torch.float64), ("H", (B, 6, 6), torch.float64), ("lam", (B,), torch.float64),
+                                ("taken", (B,), torch.int32), ("dropped", (B,), torch.int32)):
+            x = getattr(state, name)
+            assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == dt and x.is_contiguous() and self._on_device(x), (
+                f"state.{name} should be a contiguous {dt} tensor of shape {shape} on this voxelizer's device")
+        if trial is not None:
+            assert state.q2 is not None, "a trial needs the trial pose of an earlier lm_step"
+            S2, G2, H2 = trial
+            for name, x, shape in (("S2", S2, (B,)), ("G2", G2, (B, 6)), ("H2", H2, (B, 6, 6))):
+                assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == torch.float64 and x.is_contiguous() and self._on_device(x), (
+                    f"trial {name} should be a contiguous float64 tensor of shape {shape} on this voxelizer's device")
+        else:
+            S2 = G2 = H2 = None
+        if state.q2 is None:
+            state.q2, state.t2, state.xi = torch.empty_like(state.q), torch.empty_like(state.t), torch.empty_like(state.G)
+        _lib.check(self._lib.mvx_lm_step(
+            self._handle, B, 0 if trial is None else 1, float(lam_down), float(lam_up), int(max_dropped), self._ptr(state.q),
+            self._ptr(state.t), self._ptr(state.S), self._ptr(state.G), self._ptr(state.H), self._ptr(state.lam), self._ptr(state.taken),
+            self._ptr(state.dropped), self._ptr(state.q2), self._ptr(state.t2), self._ptr(S2), self._ptr(G2), self._ptr(H2),
+            self._ptr(state.xi), self._stream()))
+        return state
+
+    def refine_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, field, num_channels=None,
+                           steps=40, lam0=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3, stop_when_done=False):
+        """B rigid poses refined together by damped Newton (Levenberg-Marquardt) steps that raise S_b = sum(field * grid_b):
+        score_hessian_posed_batch at the start poses, then `steps` rounds of lm_step and an evaluation at the trial poses, and
+        a last lm_step that decides on the last trial. Each pose has its own damping and is accepted or dropped on the device;
+        nothing is read back inside the loop (stop_when_done=True reads one flag per round and stops once every pose has
+        dropped max_dropped steps in a row). A finished pose keeps being evaluated where it stands.
+
+        coords ... field, num_channels: score_hessian_posed_batch's arguments; the pose tensors are not modified. lam0: the
+        first damping, a float or (B,), or None: 1e-3 * max|H_b| per pose.
+        Returns (quaternions (B, 4), translations (B, 3), scores (B,), info): info["lam"], info["taken"], info["dropped"] per
+        pose, info["evaluations"], info["score_history"] (rounds + 1, B): the accepted score of every pose after each round."""
+        self._hessian_guard(channels)
+        self._check_pose(np.asarray(offsets).shape[0] - 1, centers, quaternions, translations)
+        return self._refine(lambda q, t: self.score_hessian_posed_batch(coords, offsets, centers, q, t, channels, radii, field, num_channels),
+                            quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
+
+    def refine_posed_views(self, coords, centers, quaternions, translations, channels, radii, field, num_channels=None, steps=40,
+                           lam0=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3, stop_when_done=False):
+        """refine_posed_batch for B poses of ONE shared cloud (score_hessian_posed_views: every evaluation selects the poses'
+        atoms, one stream synchronisation each)."""
+        self._hessian_guard(channels)
+        self._check_pose(int(getattr(centers, "shape", (0,))[0]), centers, quaternions, translations)
+        return self._refine(lambda q, t: self.score_hessian_posed_views(coords, centers, q, t, channels, radii, field, num_channels),
+                            quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
+
+    def _refine(self, evaluate, quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done):
+        """The loop of refine_posed_batch / refine_posed_views. evaluate(q, t) -> (S, G, H)."""
+        assert int(steps) >= 0, "steps must be >= 0"
+        with torch.no_grad():
+            def own(x):  # a float64 copy on this device: the caller's poses are not modified
+                x = x if _is_torch(x) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+                return x.detach().to(device=self.device, dtype=torch.float64).clone().contiguous()
+
+            S, G, H = evaluate(quaternions, translations)  # (the rules of the arguments fire here, before anything is copied)
+            q, t = own(quaternions), own(translations)
+            B = int(q.shape[0])
+            if lam0 is None:
+                lam = 1e-3 * H.abs().reshape(B, 36).amax(dim=1) if B else torch.zeros(0, dtype=torch.float64, device=self.device)
+            else:
+                lam = (lam0.detach().to(device=self.device, dtype=torch.float64) if _is_torch(lam0) else
+                       torch.as_tensor(np.asarray(lam0, dtype=np.float64), device=self.device)).expand(B).clone()
+            state = LMState(q, t, S.clone(), G.clone(), H.clone(), lam.contiguous())
+            history = torch.empty((int(steps) + 1, B), dtype=torch.float64, device=self.device)
+            history[0] = state.S
+            kw = dict(lam_down=lam_down, lam_up=lam_up, max_dropped=max_dropped)
+            self.lm_step(state, **kw)
+            evaluations, rounds = 1, 0
+            for r in range(int(steps)):
+                trial = evaluate(state.q2, state.t2)
+                evaluations += 1
+                self.lm_step(state, trial, **kw)
+                history[r + 1] = state.S
+                rounds = r + 1
+                if stop_when_done and bool((state.dropped >= max_dropped).all()):
+                    break
+            info = dict(lam=state.lam, taken=state.taken, dropped=state.dropped, evaluations=evaluations,
+                        score_history=history[:rounds + 1])
+        return state.q, state.t, state.S, info
 
     # ------------------------------------------------------------------------------------------
     # SCORES OF VIEWS (many poses or boxes of one shared cloud against a field: mvx_score_views / mvx_views_reduce)
