@@ -1303,10 +1303,12 @@ struct ViewBatch : Call {
     explicit ViewBatch(const Call &v) : Call(v), own_offsets((size_t)v.B + 1, 0) { offsets = own_offsets.data(); }
 };
 
-// The compact batch of the views `v` of a cloud with atoms (N > 0, B > 0), on the device: scope, staging and selection - or the
-// caller's `index` with its host offsets `index_offsets` (mvx_score_views), and nothing staged -, "too many atoms", gather.
-// `features`: the call after it reads the feature rows of a host-resident cloud. Synchronises the stream once (select_views).
+// The compact batch of the views `v` (B > 0) of a cloud, on the device: scope, staging and selection - or the caller's `index`
+// with its host offsets `index_offsets` (mvx_score_views), and nothing staged -, "too many atoms", gather. A cloud without atoms
+// leaves `b` as constructed, whatever the caller's selection says, and touches no device. `features`: the call after it reads the
+// feature rows of a host-resident cloud. Synchronises the stream once (select_views; not with the caller's index).
 int compact_views(mvx_handle *h, const Call &v, bool features, const int64_t *index, const int64_t *index_offsets, ViewBatch &b) {
+    if (v.N == 0) return MVX_OK;
     CallScope scope(h, v.stream);
     int rc = scope.rc;
     if (rc) return rc;
@@ -1360,8 +1362,7 @@ int mvx_forward_views(mvx_handle *h, int32_t mode, const double *coords, const v
     if (int rc = validate_views(h, v, own)) return rc;
     if (B == 0) return MVX_OK;
     ViewBatch batch(v); // (N == 0: B molecules without atoms, zero grids)
-    if (N > 0)
-        if (int rc = compact_views(h, v, true, nullptr, nullptr, batch)) return rc;
+    if (int rc = compact_views(h, v, true, nullptr, nullptr, batch)) return rc;
     return run(h, {batch, out, out_kind, N > 0}); // (a compact batch does not overlap its pre-pass: RunArgs::no_overlap)
 }
 
@@ -1379,17 +1380,15 @@ int mvx_forward_views_sum(mvx_handle *h, int32_t mode, const double *coords, con
     if (int rc = sum_config(h, v, false, out)) return rc;
     ViewBatch batch(v); // (N == 0: B views without atoms, zeros or nothing)
     SumCall sc{nullptr, accumulate != 0};
-    if (N > 0) {
-        int rc = compact_views(h, v, true, nullptr, nullptr, batch);
-        if (rc) return rc;
-        const int64_t total = batch.offsets[B];
-        if (view_weights && total > 0) { // one weight per selected atom, from the offsets select_views left on the device
-            CallScope scope(h, v.stream);
-            if (scope.rc) return scope.rc;
-            if ((rc = ensure(h->view_w, (size_t)total * sizeof(float)))) return rc;
-            HIP_TRY(launch_view_weights(static_cast<float *>(h->view_w.p), view_weights, static_cast<const int64_t *>(h->view_off.p), B, total, v.stream));
-            sc.atom_weights = static_cast<const float *>(h->view_w.p);
-        }
+    int rc = compact_views(h, v, true, nullptr, nullptr, batch);
+    if (rc) return rc;
+    const int64_t total = batch.offsets[B];
+    if (view_weights && total > 0) { // one weight per selected atom, from the offsets select_views left on the device
+        CallScope scope(h, v.stream);
+        if (scope.rc) return scope.rc;
+        if ((rc = ensure(h->view_w, (size_t)total * sizeof(float)))) return rc;
+        HIP_TRY(launch_view_weights(static_cast<float *>(h->view_w.p), view_weights, static_cast<const int64_t *>(h->view_off.p), B, total, v.stream));
+        sc.atom_weights = static_cast<const float *>(h->view_w.p);
     }
     return run_summed(h, {batch, out, MVX_DEVICE}, sc, nullptr, nullptr); // (a summed call never overlaps its pre-pass: Forward::make_plan)
 }
@@ -1436,6 +1435,15 @@ struct GradOut {
 
 namespace {
 
+// The stride between the fields or targets of two molecules or views: 0 (one for all) or C * D^3. Its sign is judged without the
+// handle, stride_fits against it; one text per argument name.
+const char *const BAD_FIELD_MOL_STRIDE = "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)";
+const char *const BAD_FIELD_VIEW_STRIDE = "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)";
+const char *const BAD_TARGET_STRIDE = "target_view_stride must be 0 (one shared target) or C * D^3 (one target per view)";
+bool stride_fits(const mvx_handle *h, int32_t C, int64_t stride) {
+    return stride == 0 || (uint64_t)stride == (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D;
+}
+
 // ---- what is checked before any device is touched, up to the first rule that needs the atom count ----
 int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent &e) {
     if (const char *bad = bad_mode(c.mode)) return fail(MVX_ERR_INVALID, bad);
@@ -1457,7 +1465,7 @@ int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent 
         if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_SINGLE)
             return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii are not supported in single mode");
     } else if (o.scoring()) { // (grad_coords, grad_features and atom_scores may all be null: scores alone)
-        if (o.score.mol_stride < 0) return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
+        if (o.score.mol_stride < 0) return fail(MVX_ERR_INVALID, BAD_FIELD_MOL_STRIDE);
         if (c.B > 0 && !o.score.scores) return fail(MVX_ERR_INVALID, "scores must not be null");
     } else if (!o.grad_coords && !o.grad_features) {
         return fail(MVX_ERR_INVALID, "grad_coords and grad_features are both null");
@@ -1467,12 +1475,20 @@ int check_backward(const mvx_handle *h, const Call &c, const GradOut &o, Extent 
 
 // ---- ... and, behind check_atoms, what a call with atoms must bring that reads the handle ----
 int check_backward_grid(const mvx_handle *h, const Call &c, const GradOut &o) {
-    const bool score = o.scoring();
     const size_t gsz = h->cfg.grid_type == MVX_GRID_BF16 ? 2 : (h->cfg.precision == 64 ? 8 : 4);
     const size_t D = (size_t)h->g.D;
     if (D * D * D * gsz >= ((size_t)1 << 32)) return fail(MVX_ERR_INVALID, "one channel of the grid must stay below 4 GiB");
-    if (score && o.score.mol_stride != 0 && (uint64_t)o.score.mol_stride != (uint64_t)c.C * D * D * D)
-        return fail(MVX_ERR_INVALID, "field_mol_stride must be 0 (one shared field) or C * D^3 (one field per molecule)");
+    if (o.scoring() && !stride_fits(h, c.C, o.score.mol_stride)) return fail(MVX_ERR_INVALID, BAD_FIELD_MOL_STRIDE);
+    return MVX_OK;
+}
+
+// ---- the two rules of the Hessian entries (`form`: "batch" | "views", for the names in the text), behind every rule of the score
+// entry of that form ----
+int check_hessian(const Call &c, const GradOut &o, const char *form) {
+    if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES)
+        return fail(MVX_ERR_INVALID, std::string("radii_type: channel-wise radii in features mode are not supported by mvx_score_hessian_") +
+                                         form + " (mvx_score_" + form + " gives their first-order gradients)");
+    if (o.hess.twist_hess && !o.hess.twist_grad) return fail(MVX_ERR_INVALID, "twist_hess needs twist_grad");
     return MVX_OK;
 }
 
@@ -1669,9 +1685,7 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
     if ((rc = reject(check_atoms(c, e, o.grad_out, o.scoring() ? "coords / field must not be null" : "coords / grad_out must not be null")))) return rc;
     if (e.total > 0 && (rc = check_backward_grid(h, c, o))) return rc;
     if (o.kind == BWD_HESS) { // its own rules, behind every rule of mvx_score_batch
-        if (c.radii_type == MVX_RADII_CHANNEL && c.mode == MODE_FEATURES)
-            return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii in features mode are not supported by mvx_score_hessian_batch (mvx_score_batch gives their first-order gradients)");
-        if (o.hess.twist_hess && !o.hess.twist_grad) return fail(MVX_ERR_INVALID, "twist_hess needs twist_grad");
+        if ((rc = check_hessian(c, o, "batch"))) return rc;
         if (c.B == 0) return MVX_OK;
     }
     CallScope scope(h, c.stream);
@@ -1767,10 +1781,37 @@ const char *bad_view_offsets(const int64_t *offsets, int32_t B, Extent &e) {
 const char *const ROWS_NEED_INDEX =
     "atom_scores, grad_coords and grad_features need an index: their rows are laid out in selection order (mvx_select_views)";
 
-// the target stride of the moments entries for views, without the handle (the sign) and against it (0 or C * D^3)
-const char *const BAD_TARGET_STRIDE = "target_view_stride must be 0 (one shared target) or C * D^3 (one target per view)";
-bool target_stride_fits(const mvx_handle *h, int32_t C, int64_t stride) {
-    return stride == 0 || (uint64_t)stride == (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D;
+// What is wrong with the caller's selection of a views entry, or null: `rows` (the call has outputs laid out per row) needs one,
+// and an index comes with its host offsets, whose extent lands in `e`.
+const char *bad_selection(const int64_t *index, const int64_t *offsets_host, int32_t B, bool rows, Extent &e) {
+    if (!index) return rows ? ROWS_NEED_INDEX : nullptr;
+    return B > 0 ? bad_view_offsets(offsets_host, B, e) : nullptr;
+}
+
+// mvx_score_views (BWD_SCORE) and mvx_score_hessian_views (BWD_HESS) behind their argument lists: the rules that are checked
+// before any device is touched, the selection (the caller's, or made here: one stream synchronisation) and the gather, then the
+// walk of the batch entry on the compact batch, with the records as the caller gave them (device centres and poses). The two
+// rules of the Hessian are judged here, behind the stride: backward_impl would find them only behind the gather.
+int score_views_impl(mvx_handle *h, const Call &v, const int64_t *index, const int64_t *offsets_host, const GradOut &o) {
+    const bool rows = o.score.atom_scores || o.grad_coords || o.grad_features || o.hess.atom_grad || o.hess.atom_hess;
+    Extent e; // of the caller's selection
+    const char *own = nullptr;
+    if (o.grad_features && v.mode != MODE_FEATURES) own = "grad_features exists in features mode only";
+    else if (o.score.mol_stride < 0) own = BAD_FIELD_VIEW_STRIDE;
+    else if (v.B > 0 && !o.score.scores) own = "scores must not be null";
+    else own = bad_selection(index, offsets_host, v.B, rows, e);
+    if (!own && v.B > 0 && v.N > 0) {
+        if (v.mode == MODE_FEATURES && !v.channels) own = "channels must not be null";
+        else if (!o.grad_out && (!index || e.total > 0)) own = "field must not be null";
+    }
+    if (int rc = validate_views(h, v, own)) return rc;
+    if (!stride_fits(h, v.C, o.score.mol_stride)) return fail(MVX_ERR_INVALID, BAD_FIELD_VIEW_STRIDE);
+    if (o.kind == BWD_HESS)
+        if (int rc = check_hessian(v, o, "views")) return rc;
+    if (v.B == 0) return MVX_OK;
+    ViewBatch batch(v); // (N == 0: B views without atoms, exact zeros, whatever the caller's selection says)
+    if (int rc = compact_views(h, v, false, index, offsets_host, batch)) return rc;
+    return backward_impl(h, batch, o);
 }
 
 } // namespace
@@ -1861,65 +1902,20 @@ int mvx_score_views(mvx_handle *h, int32_t mode, const double *coords, const voi
                     double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                     const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
                     double *scores, double *atom_scores, double *grad_coords, void *grad_features, void *stream) {
-    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream);
-    // ---- what is checked before any device is touched ----
-    const bool per_row = atom_scores || grad_coords || grad_features;
-    Extent e; // of the caller's selection
-    const char *own = nullptr;
-    if (grad_features && mode != MODE_FEATURES) own = "grad_features exists in features mode only";
-    else if (field_view_stride < 0) own = "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)";
-    else if (B > 0 && !scores) own = "scores must not be null";
-    else if (!index && per_row) own = ROWS_NEED_INDEX;
-    else if (index && B > 0) own = bad_view_offsets(offsets_host, B, e);
-    if (!own && B > 0 && N > 0) {
-        if (mode == MODE_FEATURES && !channels) own = "channels must not be null";
-        else if (!field && (!index || e.total > 0)) own = "field must not be null";
-    }
-    if (int rc = validate_views(h, v, own)) return rc;
-    if (field_view_stride != 0 && (uint64_t)field_view_stride != (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D)
-        return fail(MVX_ERR_INVALID, "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)");
-    if (B == 0) return MVX_OK;
-    // the compact batch through the walk of mvx_score_batch: the records as the caller gave them (device centres and poses)
-    ViewBatch batch(v); // (N == 0: B views without atoms score 0, whatever the caller's selection says)
-    if (N > 0) // (no index: the selection itself, one stream synchronisation)
-        if (int rc = compact_views(h, v, false, index, offsets_host, batch)) return rc;
-    return backward_impl(h, batch, {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_view_stride, scores, atom_scores}});
+    return score_views_impl(h, views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream), index, offsets_host,
+                            {BWD_SCORE, field, grad_coords, grad_features, nullptr, nullptr, nullptr, {field_view_stride, scores, atom_scores}});
 }
 
 // The Hessians of B views: mvx_score_views' rules, selection and gather, then mvx_score_hessian_batch's walk and reductions on the
-// compact batch. The two rules of that entry are judged here, behind the stride and before a device is touched: backward_impl
-// would find them only behind the gather.
+// compact batch.
 int mvx_score_hessian_views(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
                             double radius_scalar, int32_t radii_type, int64_t N, int32_t C, const mvx_xform *xforms, int32_t B,
                             const int64_t *index, const int64_t *offsets_host, const void *field, int64_t field_view_stride,
                             const double *pivots, double *scores, double *atom_grad, double *atom_hess, double *twist_grad,
                             double *twist_hess, void *stream) {
-    const Call v = views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream);
-    // ---- what is checked before any device is touched ----
-    const bool per_row = atom_grad || atom_hess;
-    Extent e; // of the caller's selection
-    const char *own = nullptr;
-    if (field_view_stride < 0) own = "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)";
-    else if (B > 0 && !scores) own = "scores must not be null";
-    else if (!index && per_row) own = ROWS_NEED_INDEX;
-    else if (index && B > 0) own = bad_view_offsets(offsets_host, B, e);
-    if (!own && B > 0 && N > 0) {
-        if (mode == MODE_FEATURES && !channels) own = "channels must not be null";
-        else if (!field && (!index || e.total > 0)) own = "field must not be null";
-    }
-    if (int rc = validate_views(h, v, own)) return rc;
-    if (field_view_stride != 0 && (uint64_t)field_view_stride != (uint64_t)C * (uint64_t)h->g.D * (uint64_t)h->g.D * (uint64_t)h->g.D)
-        return fail(MVX_ERR_INVALID, "field_view_stride must be 0 (one shared field) or C * D^3 (one field per view)");
-    if (radii_type == MVX_RADII_CHANNEL && mode == MODE_FEATURES)
-        return fail(MVX_ERR_INVALID, "radii_type: channel-wise radii in features mode are not supported by mvx_score_hessian_views (mvx_score_views gives their first-order gradients)");
-    if (twist_hess && !twist_grad) return fail(MVX_ERR_INVALID, "twist_hess needs twist_grad");
-    if (B == 0) return MVX_OK;
-    ViewBatch batch(v); // (N == 0: B views without atoms, exact zeros, whatever the caller's selection says)
-    if (N > 0) // (no index: the selection itself, one stream synchronisation)
-        if (int rc = compact_views(h, v, false, index, offsets_host, batch)) return rc;
     GradOut o{BWD_HESS, field, nullptr, nullptr, nullptr, nullptr, nullptr, {field_view_stride, scores, nullptr}};
     o.hess = {pivots, atom_grad, atom_hess, twist_grad, twist_hess};
-    return backward_impl(h, batch, o);
+    return score_views_impl(h, views_call(mode, coords, channels, radii, radius_scalar, radii_type, N, xforms, B, C, stream), index, offsets_host, o);
 }
 
 // The moments of B views: the selection (the caller's, or made here) and the gather of mvx_score_views, then mvx_moments_batch's
@@ -1933,15 +1929,14 @@ int mvx_moments_views(mvx_handle *h, int32_t mode, const double *coords, const v
     const char *own = nullptr;
     if (B > 0 && !moments) own = "moments must not be null";
     else if (target_view_stride < 0) own = BAD_TARGET_STRIDE;
-    else if (index && B > 0) own = bad_view_offsets(offsets_host, B, e);
+    else own = bad_selection(index, offsets_host, B, false, e);
     if (!own && B > 0 && N > 0 && mode == MODE_FEATURES && !channels) own = "channels must not be null";
     if (int rc = validate_views(h, v, own)) return rc;
-    if (!target_stride_fits(h, C, target_view_stride)) return fail(MVX_ERR_INVALID, BAD_TARGET_STRIDE);
+    if (!stride_fits(h, C, target_view_stride)) return fail(MVX_ERR_INVALID, BAD_TARGET_STRIDE);
     if (B == 0) return MVX_OK;
     if (int rc = sum_config(h, v, true, target)) return rc;
     ViewBatch batch(v); // (N == 0: B views without atoms, exact zeros, whatever the caller's selection says)
-    if (N > 0) // (no index: the selection itself, one stream synchronisation)
-        if (int rc = compact_views(h, v, true, index, offsets_host, batch)) return rc;
+    if (int rc = compact_views(h, v, true, index, offsets_host, batch)) return rc; // (no index: the selection itself, one stream synchronisation)
     // (a compact batch does not overlap its pre-pass, and a summed call never does: Forward::make_plan)
     return run_summed(h, {batch, moments, MVX_DEVICE, N > 0}, SumCall{nullptr, false, true, target, target ? target_view_stride : 0}, nullptr, nullptr);
 }
@@ -1960,11 +1955,10 @@ int mvx_moments_backward_views(mvx_handle *h, int32_t mode, const double *coords
     else if (grad_features_rows && mode != MODE_FEATURES) own = "grad_features exists in features mode only";
     else if (!grad_coords_rows && !grad_features_rows) own = "grad_coords and grad_features are both null";
     else if (target_view_stride < 0) own = BAD_TARGET_STRIDE;
-    else if (!index) own = ROWS_NEED_INDEX;
-    else if (B > 0) own = bad_view_offsets(offsets_host, B, e);
+    else own = bad_selection(index, offsets_host, B, true, e); // (every output is laid out per row)
     if (!own && B > 0 && N > 0 && mode == MODE_FEATURES && !channels) own = "channels must not be null";
     if (int rc = validate_views(h, v, own)) return rc;
-    if (!target_stride_fits(h, C, target_view_stride)) return fail(MVX_ERR_INVALID, BAD_TARGET_STRIDE);
+    if (!stride_fits(h, C, target_view_stride)) return fail(MVX_ERR_INVALID, BAD_TARGET_STRIDE);
     if (B == 0) return MVX_OK;
     if (int rc = sum_config(h, v, true, target)) return rc;
     if (N == 0 || e.total == 0) return MVX_OK; // (no selected atom: no gradient rows, nothing is launched)

@@ -69,20 +69,58 @@ class _Call:
     the caller's arguments, and the `spec` the autograd Functions keep for backward().
 
     mode "features" | "types" | "single"; C, B, N (all atoms of the call); coords, channels, radii: the converted arrays
-    (radii None with scalar radii, which travel as `rs`); offsets: host int64 (B + 1,), None for a views call; xforms: the
+    (radii None with scalar radii, which travel as `rs`); views: a views call (N atoms of one shared cloud, B views of it);
+    offsets: host int64 (B + 1,) - a batch's, or those of a views call's selection; index: the selection a views call
+    attached (`Voxelizer._select_rows`: its per-row outputs are laid out in selection order), or None; xforms: the
     B mvx_xform records or None; centers: the device centres the records point at, or None; pose: the packed (B, 10) poses
     the records point at, or None; in_kind: MVX_HOST | MVX_DEVICE; keep: what must outlive the call; rten: the scalar-radius
     tensor of a radii_grad call; fresh: with overlap_prepass, an input was made on the stream a moment ago; grad: the call
-    records an autograd graph. For backward(): settings (`Voxelizer._grad_settings` at the forward) and, for the scores of
-    views, index (the selection)."""
+    records an autograd graph. For backward(): settings (`Voxelizer._grad_settings` at the forward)."""
 
     __slots__ = ("mode", "C", "B", "N", "coords", "channels", "radii", "rs", "offsets", "xforms", "centers", "pose", "in_kind",
-                 "keep", "rten", "fresh", "grad", "settings", "index")
+                 "keep", "rten", "fresh", "grad", "settings", "views", "index")
 
     def __init__(self, **fields):
         for name in self.__slots__:
             setattr(self, name, fields.pop(name, None))
         assert not fields, sorted(fields)
+
+    def pick(self, batch, views):
+        """Of a family's two forms - entries, argument builders - the one of this call's kind."""
+        return views if self.views else batch
+
+    @property
+    def rows(self):
+        """The number of per-row outputs of the call: N for a batch, the selection's total for views with a selection, None
+        for views without one (no per-row outputs)."""
+        if not self.views:
+            return self.N
+        return None if self.index is None else int(self.offsets[-1])
+
+    def entry_args(self, vox, coords=None, channels=None):
+        """The arguments the call's entry begins with: batch_args, or views_args and the selection (index, host offsets; two
+        nulls without one: the library selects itself). coords / channels: as batch_args takes them."""
+        if not self.views:
+            return self.batch_args(vox, coords, channels)
+        if self.index is None:
+            return self.views_args(vox, coords, channels) + (None, None)
+        index = self.index
+        if not self.rows:  # an empty tensor has no address, but a non-null index is what says "selected" to the library
+            index = torch.empty(1, dtype=torch.int64, device=vox.device)
+            self.keep.append(index)
+        return self.views_args(vox, coords, channels) + (index.data_ptr(), self.offsets.ctypes.data)
+
+    def target_args(self, vox, T, stride):
+        """The target of a moments entry: the views entries take a stride with it (one target per view), the batch entries
+        take one shared target."""
+        return (vox._ptr(T), stride) if self.views else (vox._ptr(T),)
+
+    def row_lengths(self, device):
+        """The rows of every molecule (view) as an int64 tensor on `device`, for backward()."""
+        lengths = np.diff(self.offsets)
+        if self.views:  # (through pinned memory: a pageable copy would synchronise the stream)
+            return torch.from_numpy(lengths).pin_memory().to(device, non_blocking=True)
+        return torch.as_tensor(lengths, device=device)
 
     def batch_args(self, vox, coords=None, channels=None):
         """The arguments mvx_backward_batch, mvx_backward_radii_batch, mvx_backward_density_batch, mvx_score_batch,
@@ -532,6 +570,14 @@ class Voxelizer(BaseVoxelizer):
         tmp = np.empty(out_grid.shape, dtype=self.fp)
         return tmp, _lib.MVX_HOST, out_grid, "copy_numpy"
 
+    def _resolve_out_batch(self, out_grid, B, C_):
+        """_resolve_out for the B grids of a batch or views call: the caller's out_grid, checked, or a new one."""
+        if out_grid is None:
+            out_grid = self.get_empty_grid(C_, batch_size=B)
+        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
+            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
+        return self._resolve_out(out_grid, None)
+
     @staticmethod
     def _finish_out(buf, ret, how):
         if how == "copy_torch":
@@ -686,7 +732,7 @@ class Voxelizer(BaseVoxelizer):
         already for these molecules instead of new ones - the rows forward_views gathered on a differentiable voxelizer."""
         pose = None
         if posed is not None:
-            pose = self._pack_pose(np.asarray(offsets).shape[0] - 1, centers, posed[0], posed[1], device or self._on_device(coords))
+            pose = self._pack_pose(self._pose_count(offsets), centers, posed[0], posed[1], device or self._on_device(coords))
             centers = None
         if self._sigma_src is not None:
             self._sync_sigma()
@@ -706,8 +752,8 @@ class Voxelizer(BaseVoxelizer):
 
     def _views_call(self, coords, centers, channels, radii, num_channels=None, random_translation=0.0, random_rotation=False,
                     posed=None, *, device=False, score=False, check=None, out_grid=None, features=True):
-        """The _Call of B views of ONE shared cloud, from forward_views' arguments: forward_batch's rules for one molecule of
-        N atoms. Keywords as _batch_call (check gets offsets = None); the poses are packed after the rules. features: are
+        """The _Call of B views of ONE shared cloud (`views` set), from forward_views' arguments: forward_batch's rules for one
+        molecule of N atoms. Keywords as _batch_call (check gets offsets = None); the poses are packed after the rules. features: are
         the feature values read, and therefore converted - False: no (select_views); "without_graph": only by a call that
         records no graph (forward_views, which otherwise selects, gathers and hands the rows to _batch_call)."""
         if self._sigma_src is not None:
@@ -722,7 +768,7 @@ class Voxelizer(BaseVoxelizer):
         B = int(centers.shape[0])
         if check is not None:
             check(B, C_, None)
-        call = _Call(mode=kind or "single", C=C_, B=B, rten=rten)
+        call = _Call(mode=kind or "single", C=C_, B=B, rten=rten, views=True)
         if posed is not None:
             call.pose = self._pack_pose(B, centers, posed[0], posed[1], device or self._on_device(coords))
         return self._convert(call, coords, centers, channels, radii, random_translation, random_rotation,
@@ -871,6 +917,14 @@ class Voxelizer(BaseVoxelizer):
         assert shape(translations) == (B, 3), f"translations does not match dimension: {shape(translations)} vs {(B, 3)}"
         assert centers is None or shape(centers) == (B, 3), f"centers does not match dimension: {shape(centers)} vs {(B, 3)}"
 
+    @staticmethod
+    def _pose_count(offsets, centers=None):
+        """B as the pose rules need it before the call is built: from a batch's offsets, or - offsets None - from the centres
+        of a views call."""
+        if offsets is None:
+            return int(getattr(centers, "shape", (0,))[0])
+        return np.asarray(offsets).shape[0] - 1
+
     def _pose_xforms(self, pose, B):
         """B MVX_XF_POSE_PTR records, record b pointing at row b of the packed poses."""
         xfs = (_lib.MvxXform * B)()
@@ -916,11 +970,7 @@ class Voxelizer(BaseVoxelizer):
         call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
                                 posed, out_grid=out_grid, drawn=drawn)
         B, C_ = call.B, call.C
-        if out_grid is None:
-            out_grid = self.get_empty_grid(C_, batch_size=B)
-        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
-            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
-        buf, out_kind, ret, how = self._resolve_out(out_grid, None)
+        buf, out_kind, ret, how = self._resolve_out_batch(out_grid, B, C_)
         if call.fresh:
             torch.cuda.current_stream(self._device_index).synchronize()
         # (the three mvx_forward_*_batch entries have an argument order of their own)
@@ -972,7 +1022,7 @@ class Voxelizer(BaseVoxelizer):
 
     def select_posed_views(self, coords, centers, quaternions, translations, channels=None, radii=None):
         """select_views for explicit poses: the atoms each pose of forward_posed_views keeps, as (index, offsets)."""
-        self._check_pose(int(centers.shape[0]), centers, quaternions, translations)  # (before the rules of the other arguments)
+        self._check_pose(self._pose_count(None, centers), centers, quaternions, translations)  # (before the rules of the other arguments)
         return self._select_views(coords, centers, channels, radii, posed=(quaternions, translations))
 
     def _select_views(self, coords, centers, channels, radii, random_translation=0.0, random_rotation=False, num_channels=None,
@@ -1027,11 +1077,7 @@ class Voxelizer(BaseVoxelizer):
                                        take(radii) if self.is_radii_type_atom_wise else radii,
                                        num_channels=C_ if call.mode == "types" else None,
                                        drawn=(call.xforms, call.centers, call.pose))
-        if out_grid is None:
-            out_grid = self.get_empty_grid(C_, batch_size=B)
-        assert tuple(out_grid.shape) == (B,) + self.grid_dimension(C_), (
-            f"Output grid dimension incorrect: {tuple(out_grid.shape)} vs {(B,) + self.grid_dimension(C_)}")
-        buf, out_kind, ret, how = self._resolve_out(out_grid, None)
+        buf, out_kind, ret, how = self._resolve_out_batch(out_grid, B, C_)
         _lib.check(self._lib.mvx_forward_views(*call.views_args(self), self._ptr(buf), call.in_kind, out_kind, self._stream()))
         return self._finish_out(buf, ret, how)
 
@@ -1127,12 +1173,13 @@ class Voxelizer(BaseVoxelizer):
             return self._sum_call(call, w[0], out_grid, accumulate)
 
     def _sum_call(self, call, w, out, accumulate, coords=None):
-        """One mvx_forward_sum_batch call on device arrays, on the current stream; out None: a new grid. coords: the tensor
-        autograd saved (the field gradient of a score call)."""
+        """One mvx_forward_sum_batch or mvx_forward_views_sum call on device arrays, on the current stream; out None: a new
+        grid. coords: the tensor autograd saved (the field gradient of a score call)."""
         if out is None:
             out = torch.empty(self.grid_dimension(call.C), dtype=torch.float32, device=self.device)
-        _lib.check(self._lib.mvx_forward_sum_batch(*call.batch_args(self, coords), self._ptr(w), self._ptr(out),
-                                                   1 if accumulate else 0, self._stream()))
+        entry = call.pick(self._lib.mvx_forward_sum_batch, self._lib.mvx_forward_views_sum)
+        args = call.pick(call.batch_args, call.views_args)(self, coords)  # (a summed call takes no selection)
+        _lib.check(entry(*args, self._ptr(w), self._ptr(out), 1 if accumulate else 0, self._stream()))
         return out
 
     def forward_views_sum(self, coords, centers, channels, radii, weights=None, num_channels=None, out_grid=None, accumulate=False,
@@ -1171,12 +1218,7 @@ class Voxelizer(BaseVoxelizer):
             check, w = self._sum_rules(out_grid, accumulate, weights)
             call = self._views_call(coords, centers, channels, radii, num_channels, random_translation, random_rotation, posed,
                                     device=True, check=check)
-            out = out_grid
-            if out is None:
-                out = torch.empty(self.grid_dimension(call.C), dtype=torch.float32, device=self.device)
-            _lib.check(self._lib.mvx_forward_views_sum(*call.views_args(self), self._ptr(w[0]), self._ptr(out),
-                                                       1 if accumulate else 0, self._stream()))
-            return out
+            return self._sum_call(call, w[0], out_grid, accumulate)
 
     def set_sum_parts(self, parts: int):
         """Opt-in split of every summed call of this voxelizer (forward_sum, forward_posed_sum, forward_views_sum,
@@ -1235,8 +1277,12 @@ class Voxelizer(BaseVoxelizer):
         return self._moments_batch(coords, offsets, centers, channels, radii, target, num_channels,
                                    posed=(quaternions, translations))
 
-    def _moments_grad_guard(self, radii, target):
-        """What a moments call on a moments_grad voxelizer refuses while grad mode is on: gradients it does not provide."""
+    def _moments_record(self, radii, target):
+        """Does a moments call build its _Call with grad mode as it is (moments_grad, grad mode on: the conversions and the
+        packed poses are recorded, tracking what a score call tracks: coords, features and centres (poses))? Refuses the
+        gradients such a call does not provide."""
+        if not (self._mgrad and torch.is_grad_enabled()):
+            return False
         if _is_torch(target) and target.requires_grad:
             raise ValueError("moments_grad gives no gradient with respect to the target: detach it (dL/dtarget[c] is "
                              "sum_b dL/dm[b, c, 2] * grid[b, c]: use forward_batch (forward_posed_batch) for it)")
@@ -1244,54 +1290,62 @@ class Voxelizer(BaseVoxelizer):
             if _is_torch(x) and x.requires_grad:
                 raise ValueError(f"moments_grad gives no gradient with respect to {what}: detach it, or use forward_batch "
                                  "(forward_posed_batch) and reduce the grids for that gradient")
+        return True
 
     def _moments_batch(self, coords, offsets, centers, channels, radii, target=None, num_channels=None, random_translation=0.0,
                        random_rotation=False, posed=None):
-        """moments_batch's body. posed: (quaternions, translations) of moments_posed_batch."""
+        """moments_batch's call. posed: (quaternions, translations) of moments_posed_batch."""
         self._sum_guard(channels, "moments_batch", "moments_batch / moments_posed_batch", "the moments are a tensor",
                         "use forward_batch(...) (forward_posed_batch(...)) and reduce the grids instead")
-
-        def check(B, C_, offsets):
-            if target is not None:
-                shape = tuple(getattr(target, "shape", ()))
-                assert shape == self.grid_dimension(C_), f"target does not match dimension: {shape} vs {self.grid_dimension(C_)}"
-
-        # moments_grad: the call is built with grad mode as it is (the conversions and the packed poses are recorded), tracking
-        # what a score call tracks: coords, features and centres (poses)
-        record = self._mgrad and torch.is_grad_enabled()
-        if record:
-            self._moments_grad_guard(radii, target)
+        record = self._moments_record(radii, target)
         with torch.enable_grad() if record else torch.no_grad():
             call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
-                                    posed, device=True, score=record, check=check)
+                                    posed, device=True, score=record, check=self._target_rule(target, per_row=False))
+        return self._moments(call, target)
+
+    def _target_rule(self, target, per_row):
+        """For the builders' `check`: the shape rule of a moments call's target, where there is one."""
+        if target is None:
+            return None
+        return lambda B, C_, offsets: self._check_grid_operand(target, "target", B, C_, per_row)
+
+    def _moments(self, call, target):
+        """The body of the moments entries: one mvx_moments_batch or mvx_moments_views call, inside _MomentsFunction where the
+        call records a graph (it then was built with grad mode on: _moments_record)."""
+        self._select_rows(call, call.grad)
+        entry = call.pick(self._lib.mvx_moments_batch, self._lib.mvx_moments_views)
 
         def run():
             with torch.no_grad():
-                T = None
-                if target is not None:
-                    T = (target if _is_torch(target) else torch.as_tensor(np.asarray(target))).to(device=self.device, dtype=torch.float32).contiguous()
+                T, stride = self._grid_operand(target, call.C, torch.float32)
                 out = torch.empty((call.B, call.C, 2 if T is None else 3), dtype=torch.float64, device=self.device)
-                _lib.check(self._lib.mvx_moments_batch(*call.batch_args(self), self._ptr(T), self._ptr(out), self._stream()))
+                _lib.check(entry(*call.entry_args(self), *call.target_args(self, T, stride), self._ptr(out), self._stream()))
                 return out, T
 
-        if not (record and call.grad):
+        if not call.grad:
             return run()[0]
         call.settings = self._grad_settings()
         return _MomentsFunction.apply(self, run, call, call.coords, call.channels if call.mode == "features" else None,
                                       call.centers, call.pose)
 
     def _moments_backward(self, spec, c, f, T, gm, need_features):
-        """(dL/dcoords (N, 3) float64, dL/dfeatures (N, C) or None) for dL/dm = gm (B, C, K), on the current stream. spec: the
-        forward call's _Call; c, f: its coords and features as autograd saved them; T: the target as the forward read it."""
+        """(dL/dcoords (rows, 3) float64, dL/dfeatures (rows, C) or None) for dL/dm = gm (B, C, K), on the current stream: one
+        row per atom of a batch, per (view, atom) of the selection of a views call. spec: the forward call's _Call; c, f: its
+        coords and features as autograd saved them; T: the target as the forward read it."""
         self._same_settings(spec)
+        rows = spec.rows
         g = gm.to(device=self.device, dtype=torch.float64).contiguous()
-        gc = torch.empty((c.shape[0], 3), dtype=torch.float64, device=self.device)
-        gf = torch.empty((c.shape[0], spec.C), dtype=self._tfp, device=self.device) if need_features else None
-        if c.shape[0] == 0 or spec.B == 0:  # no atoms: no gradient rows
+        gc = torch.empty((rows, 3), dtype=torch.float64, device=self.device)
+        gf = torch.empty((rows, spec.C), dtype=self._tfp, device=self.device) if need_features else None
+        if rows == 0 or spec.B == 0:  # no atoms: no gradient rows
             return gc, gf
-        _lib.check(self._lib.mvx_moments_backward_batch(*spec.batch_args(self, c, f if spec.mode == "features" else None),
-                                                        self._ptr(T), self._ptr(g), self._ptr(gc), self._ptr(gf), self._stream()))
+        entry = spec.pick(self._lib.mvx_moments_backward_batch, self._lib.mvx_moments_backward_views)
+        _lib.check(entry(*spec.entry_args(self, c, f if spec.mode == "features" else None),
+                         *spec.target_args(self, *self._grid_operand(T, spec.C, torch.float32)), self._ptr(g), self._ptr(gc),
+                         self._ptr(gf), self._stream()))
         return gc, gf
+
+    _moments_backward_views = _moments_backward  # (the name the rows of views went by)
 
     # ------------------------------------------------------------------------------------------
     # MOMENTS OF VIEWS (many poses or boxes of one shared cloud, each against its own target: mvx_moments_views)
@@ -1324,63 +1378,14 @@ class Voxelizer(BaseVoxelizer):
 
     def _moments_views(self, coords, centers, channels, radii, target=None, num_channels=None, random_translation=0.0,
                        random_rotation=False, posed=None):
-        """moments_views' body. posed: (quaternions, translations) of moments_posed_views."""
+        """moments_views' call. posed: (quaternions, translations) of moments_posed_views."""
         self._sum_guard(channels, "moments_views", "moments_views / moments_posed_views", "the moments are a tensor",
                         "use forward_views(...) (forward_posed_views(...)) and reduce the grids instead")
-
-        def check(B, C_, offsets):
-            if target is not None:
-                shape, one = tuple(getattr(target, "shape", ())), self.grid_dimension(C_)
-                assert shape in (one, (B,) + one), f"target does not match dimension: {shape} vs {one} or {(B,) + one}"
-
-        record = self._mgrad and torch.is_grad_enabled()  # (as _moments_batch builds its call)
-        if record:
-            self._moments_grad_guard(radii, target)
+        record = self._moments_record(radii, target)
         with torch.enable_grad() if record else torch.no_grad():
             call = self._views_call(coords, centers, channels, radii, num_channels, random_translation, random_rotation, posed,
-                                    device=True, score=record, check=check)
-
-        def run(index, offsets):
-            """One mvx_moments_views call, with the selection made before it or - index None - its own."""
-            with torch.no_grad():
-                T, stride = None, 0
-                if target is not None:
-                    T = (target if _is_torch(target) else torch.as_tensor(np.asarray(target))).to(device=self.device, dtype=torch.float32).contiguous()
-                    stride = call.C * int(self.dimension) ** 3 if T.dim() == 5 else 0  # (one target per view)
-                out = torch.empty((call.B, call.C, 2 if T is None else 3), dtype=torch.float64, device=self.device)
-                # (an empty selection: an empty tensor has no address, but a non-null index is what says "selected" to the library)
-                some = index is not None and int(offsets[-1]) > 0
-                pad = torch.empty(1, dtype=torch.int64, device=self.device) if (index is not None and not some) else None
-                _lib.check(self._lib.mvx_moments_views(
-                    *call.views_args(self), None if index is None else (index if some else pad).data_ptr(),
-                    offsets.ctypes.data if index is not None else None, self._ptr(T), stride, self._ptr(out), self._stream()))
-                return out, T
-
-        if not (record and call.grad):
-            return run(None, None)[0]
-        with torch.no_grad():
-            index, offsets = self._select(call)
-        call.index, call.offsets = index, offsets  # (backward(): the rows are laid out in selection order)
-        call.settings = self._grad_settings()
-        return _MomentsViewsFunction.apply(self, lambda: run(index, offsets), call, call.coords,
-                                           call.channels if call.mode == "features" else None, call.centers, call.pose)
-
-    def _moments_backward_views(self, spec, c, f, T, index, gm, need_features):
-        """(dL/dcoords (total, 3) float64, dL/dfeatures (total, C) or None) per (view, atom) row of the forward's selection for
-        dL/dm = gm (B, C, K), on the current stream. spec: the forward call's _Call with its selection; c, f: the shared
-        cloud's coords and features as autograd saved them; T: the target as the forward read it."""
-        self._same_settings(spec)
-        total = int(spec.offsets[-1])
-        g = gm.to(device=self.device, dtype=torch.float64).contiguous()
-        gc = torch.empty((total, 3), dtype=torch.float64, device=self.device)
-        gf = torch.empty((total, spec.C), dtype=self._tfp, device=self.device) if need_features else None
-        if total == 0 or spec.B == 0:  # no selected atom: no gradient rows
-            return gc, gf
-        stride = spec.C * int(self.dimension) ** 3 if (T is not None and T.dim() == 5) else 0
-        _lib.check(self._lib.mvx_moments_backward_views(
-            *spec.views_args(self, c, f if spec.mode == "features" else None), index.data_ptr(), spec.offsets.ctypes.data,
-            self._ptr(T), stride, self._ptr(g), self._ptr(gc), self._ptr(gf), self._stream()))
-        return gc, gf
+                                    device=True, score=record, check=self._target_rule(target, per_row=True))
+        return self._moments(call, target)
 
     # ------------------------------------------------------------------------------------------
     # SCORES (poses against a constant field grid without the grids: mvx_score_batch)
@@ -1409,7 +1414,7 @@ class Voxelizer(BaseVoxelizer):
         B poses against `field`. On a differentiable voxelizer `centers`, `quaternions` and `translations` that require grad get
         dS/dc, dS/dq and dS/dt (mvx_pose_grad_batch on the scaled per-atom gradients)."""
         self._score_guard(field, True)  # (the guard, then the poses' rules, then everything else)
-        self._check_pose(np.asarray(offsets).shape[0] - 1, centers, quaternions, translations)
+        self._check_pose(self._pose_count(offsets), centers, quaternions, translations)
         return self._score_batch(coords, offsets, centers, channels, radii, field, num_channels, per_atom=per_atom,
                                  posed=(quaternions, translations))
 
@@ -1433,37 +1438,61 @@ class Voxelizer(BaseVoxelizer):
                 raise NotImplementedError(f"score calls give no gradient with respect to {what}: detach it, or use forward_batch "
                                           "and (grid * field).sum() for that gradient")
 
-    def _check_args_score(self, field, B, C_):
-        shape = tuple(getattr(field, "shape", ()))
-        one = self.grid_dimension(C_)
-        assert shape in (one, (B,) + one), f"field does not match dimension: {shape} vs {one} or {(B,) + one}"
+    def _check_grid_operand(self, x, what, B, C_, per_row=True):
+        """The shape rule of a field or a target: (C,D,H,W), one for all, or - per_row - (B,C,D,H,W), one per molecule or view."""
+        shape, one = tuple(getattr(x, "shape", ())), self.grid_dimension(C_)
+        if per_row:
+            assert shape in (one, (B,) + one), f"{what} does not match dimension: {shape} vs {one} or {(B,) + one}"
+        else:
+            assert shape == one, f"{what} does not match dimension: {shape} vs {one}"
 
-    def _field_tensor(self, field):
-        """The field of a score call as the library reads it: on this device, of the grid's dtype, contiguous."""
-        return (field if _is_torch(field) else torch.as_tensor(np.asarray(field))).to(device=self.device, dtype=self._gdt).contiguous()
+    def _grid_operand(self, x, C_, dtype):
+        """(tensor, stride) of a field (dtype: the grid's) or a target (float32) as the library reads it: on this device,
+        contiguous; stride: the elements between the grids of two molecules or views, C * D^3, or 0: one (C,D,H,W) grid for
+        all. None: (None, 0)."""
+        if x is None:
+            return None, 0
+        t = (x if _is_torch(x) else torch.as_tensor(np.asarray(x))).to(device=self.device, dtype=dtype).contiguous()
+        return t, C_ * int(self.dimension) ** 3 if t.dim() == 5 else 0
+
+    def _select_rows(self, call, wanted):
+        """The selection step of a body, which only views calls take: `wanted` (the call has outputs laid out per (view, atom)
+        row, or records a graph) attaches the selection to the call, for the entry and for backward()."""
+        if call.views and wanted:
+            with torch.no_grad():
+                call.index, call.offsets = self._select(call)
 
     def _score_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, random_translation=0.0,
                      random_rotation=False, per_atom=False, posed=None):
-        """score_batch's body. posed: (quaternions, translations) of score_posed_batch."""
+        """score_batch's call. posed: (quaternions, translations) of score_posed_batch."""
         self._score_guard(field, True)
         fgrad = (_is_torch(field) and field.requires_grad and self.field_grad and self.differentiable and torch.is_grad_enabled())
         if fgrad:  # (what forward_sum cannot serve is refused now, not in backward())
             self._sum_guard(channels)
         call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, random_translation, random_rotation,
-                                posed, device=True, score=True, check=lambda B, C_, offsets: self._check_args_score(field, B, C_))
-        F = self._field_tensor(field)
-        B, C_, N, grad = call.B, call.C, call.N, call.grad
-        stride = C_ * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per molecule)
+                                posed, device=True, score=True,
+                                check=lambda B, C_, offsets: self._check_grid_operand(field, "field", B, C_))
+        return self._score(call, field, per_atom, fgrad)
+
+    def _score(self, call, field, per_atom, fgrad=False):
+        """The body of the score entries: one mvx_score_batch or mvx_score_views call, inside _ScoreFunction where the call
+        records a graph or - fgrad - the shared field of a batch gets its gradient. Returns scores, with per_atom
+        (scores, atom_scores): one row per atom of a batch, per (view, atom) of the selection of a views call."""
+        F, stride = self._grid_operand(field, call.C, self._gdt)
+        B, C_, grad = call.B, call.C, call.grad
         feat = call.channels if call.mode == "features" else None
         need_gf = grad and feat is not None and feat.requires_grad
+        self._select_rows(call, per_atom or grad)
+        entry = call.pick(self._lib.mvx_score_batch, self._lib.mvx_score_views)
 
         def run():
+            n = call.rows
             scores = torch.empty(B, dtype=torch.float64, device=self.device)
-            atoms = torch.empty(N, dtype=torch.float64, device=self.device) if per_atom else None
-            gc = torch.empty((N, 3), dtype=torch.float64, device=self.device) if grad else None
-            gf = torch.empty((N, C_), dtype=self._tfp, device=self.device) if need_gf else None
-            _lib.check(self._lib.mvx_score_batch(*call.batch_args(self), self._ptr(F), stride, self._ptr(scores), self._ptr(atoms),
-                                                 self._ptr(gc), self._ptr(gf), self._stream()))
+            atoms = torch.empty(n, dtype=torch.float64, device=self.device) if per_atom else None
+            gc = torch.empty((n, 3), dtype=torch.float64, device=self.device) if grad else None
+            gf = torch.empty((n, C_), dtype=self._tfp, device=self.device) if need_gf else None
+            _lib.check(entry(*call.entry_args(self), self._ptr(F), stride, self._ptr(scores), self._ptr(atoms), self._ptr(gc),
+                             self._ptr(gf), self._stream()))
             return scores, atoms, gc, gf
 
         if not grad and not fgrad:
@@ -1492,7 +1521,7 @@ class Voxelizer(BaseVoxelizer):
         scores; an atom that reaches no voxel has exact zero rows and does not enter the sums. Deterministic, no atomics: a
         molecule's values do not depend on its batch. Plain values, NOT part of the autograd graph: inputs that require grad are
         read as values. Channel-wise radii with features raise NotImplementedError."""
-        return self._score_hessian(coords, offsets, centers, channels, radii, field, num_channels, pivots, per_atom)
+        return self._score_hessian_batch(coords, offsets, centers, channels, radii, field, num_channels, pivots, per_atom)
 
     def score_hessian_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, field,
                                   num_channels=None, pivots=None, per_atom=False):
@@ -1500,9 +1529,9 @@ class Voxelizer(BaseVoxelizer):
         pivots=None: `translations` rounded to float32 and widened - the point the record maps the centre to - so that
         `apply_twist(quaternions, translations, xi)` realises the twist xi exactly."""
         self._hessian_guard(channels)
-        self._check_pose(np.asarray(offsets).shape[0] - 1, centers, quaternions, translations)
-        return self._score_hessian(coords, offsets, centers, channels, radii, field, num_channels, pivots, per_atom,
-                                   posed=(quaternions, translations))
+        self._check_pose(self._pose_count(offsets), centers, quaternions, translations)
+        return self._score_hessian_batch(coords, offsets, centers, channels, radii, field, num_channels, pivots, per_atom,
+                                         posed=(quaternions, translations))
 
     def _hessian_guard(self, channels):
         """What a Hessian call refuses before it looks at anything else."""
@@ -1513,34 +1542,39 @@ class Voxelizer(BaseVoxelizer):
             raise NotImplementedError("score_hessian_batch does not support channel-wise radii with features: score_posed_batch "
                                       "(score_batch) on a differentiable voxelizer gives their first-order gradients")
 
-    def _score_hessian(self, coords, offsets, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False,
-                       posed=None):
-        """score_hessian_batch's body. posed: (quaternions, translations) of score_hessian_posed_batch."""
-        self._hessian_guard(channels)
-
+    def _hessian_rules(self, field, pivots):
+        """For the builders' `check`: the family rules of a Hessian call, the field's shape and the pivots'."""
         def check(B, C_, offsets):
-            self._check_args_score(field, B, C_)
+            self._check_grid_operand(field, "field", B, C_)
             if pivots is not None:
                 assert tuple(pivots.shape) == (B, 3), f"pivots does not match dimension: {tuple(pivots.shape)} vs {(B, 3)}"
 
+        return check
+
+    def _score_hessian_batch(self, coords, offsets, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False,
+                             posed=None):
+        """score_hessian_batch's call. posed: (quaternions, translations) of score_hessian_posed_batch."""
+        self._hessian_guard(channels)
         with torch.no_grad():  # (plain values: inputs that require grad are read as values)
-            call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, posed=posed, device=True, check=check)
-            F = self._field_tensor(field)
-            B, N = call.B, call.N
-            stride = call.C * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per molecule)
-            piv = pivots
-            if piv is None and posed is not None:  # the image of the centre: the translation as the record holds it
-                piv = (posed[1] if _is_torch(posed[1]) else torch.as_tensor(np.asarray(posed[1], dtype=np.float64))).to(torch.float32)
-            if piv is not None:
-                piv = (piv if _is_torch(piv) else torch.as_tensor(np.asarray(piv, dtype=np.float64)))
-                piv = piv.to(device=self.device, dtype=torch.float64).contiguous()
-            scores = torch.empty(B, dtype=torch.float64, device=self.device)
-            tg = torch.empty((B, 6), dtype=torch.float64, device=self.device)
-            th = torch.empty((B, 6, 6), dtype=torch.float64, device=self.device)
-            ag = torch.empty((N, 3), dtype=torch.float64, device=self.device) if per_atom else None
-            ah = torch.empty((N, 6), dtype=torch.float64, device=self.device) if per_atom else None
-            _lib.check(self._lib.mvx_score_hessian_batch(*call.batch_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores),
-                                                         self._ptr(ag), self._ptr(ah), self._ptr(tg), self._ptr(th), self._stream()))
+            call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, posed=posed, device=True,
+                                    check=self._hessian_rules(field, pivots))
+            return self._score_hessian(call, field, pivots, posed, per_atom)
+
+    def _score_hessian(self, call, field, pivots, posed, per_atom):
+        """The body of the Hessian entries, under no_grad: one mvx_score_hessian_batch or mvx_score_hessian_views call. Returns
+        (scores, twist_grad, twist_hess), with per_atom also (atom_grad, atom_hess): one row per atom of a batch, per
+        (view, atom) of the selection of a views call."""
+        F, stride = self._grid_operand(field, call.C, self._gdt)
+        piv = self._hessian_pivots(pivots, posed)
+        self._select_rows(call, per_atom)
+        B, n = call.B, call.rows
+        f64 = dict(dtype=torch.float64, device=self.device)
+        scores, tg, th = torch.empty(B, **f64), torch.empty((B, 6), **f64), torch.empty((B, 6, 6), **f64)
+        ag = torch.empty((n, 3), **f64) if per_atom else None
+        ah = torch.empty((n, 6), **f64) if per_atom else None
+        entry = call.pick(self._lib.mvx_score_hessian_batch, self._lib.mvx_score_hessian_views)
+        _lib.check(entry(*call.entry_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores), self._ptr(ag),
+                         self._ptr(ah), self._ptr(tg), self._ptr(th), self._stream()))
         return (scores, tg, th, ag, ah) if per_atom else (scores, tg, th)
 
     def score_hessian_views(self, coords, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False):
@@ -1563,7 +1597,7 @@ class Voxelizer(BaseVoxelizer):
         twist gradients and twist Hessians of B poses of ONE shared cloud. pivots=None: `translations` rounded to float32 and
         widened, so that `apply_twist(quaternions, translations, xi)` - or lm_step - realises the twist xi exactly."""
         self._hessian_guard(channels)
-        self._check_pose(int(getattr(centers, "shape", (0,))[0]), centers, quaternions, translations)
+        self._check_pose(self._pose_count(None, centers), centers, quaternions, translations)
         return self._score_hessian_views(coords, centers, channels, radii, field, num_channels, pivots, per_atom,
                                          posed=(quaternions, translations))
 
@@ -1580,37 +1614,13 @@ class Voxelizer(BaseVoxelizer):
 
     def _score_hessian_views(self, coords, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False,
                              posed=None):
-        """score_hessian_views' body. posed: (quaternions, translations) of score_hessian_posed_views."""
+        """score_hessian_views' call. posed: (quaternions, translations) of score_hessian_posed_views."""
         self._hessian_guard(channels)
-
-        def check(B, C_, offsets):
-            self._check_args_score(field, B, C_)
-            if pivots is not None:
-                assert tuple(pivots.shape) == (B, 3), f"pivots does not match dimension: {tuple(pivots.shape)} vs {(B, 3)}"
-
         with torch.no_grad():  # (plain values: inputs that require grad are read as values)
-            call = self._views_call(coords, centers, channels, radii, num_channels, posed=posed, device=True, check=check)
-            F = self._field_tensor(field)
-            B = call.B
-            stride = call.C * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per view)
-            piv = self._hessian_pivots(pivots, posed)
-            index = offsets = None
-            total = 0
-            if per_atom:
-                index, offsets = self._select(call)
-                total = int(offsets[-1])
-            f64 = dict(dtype=torch.float64, device=self.device)
-            scores, tg, th = torch.empty(B, **f64), torch.empty((B, 6), **f64), torch.empty((B, 6, 6), **f64)
-            ag = torch.empty((total, 3), **f64) if per_atom else None
-            ah = torch.empty((total, 6), **f64) if per_atom else None
-            # (an empty selection: an empty tensor has no address, but a non-null index is what says "selected" to the library)
-            some = per_atom and total > 0
-            pad = torch.empty(1, dtype=torch.int64, device=self.device) if (per_atom and not some) else None
-            _lib.check(self._lib.mvx_score_hessian_views(
-                *call.views_args(self), None if index is None else (index if some else pad).data_ptr(),
-                offsets.ctypes.data if index is not None else None, self._ptr(F), stride, self._ptr(piv), self._ptr(scores),
-                self._ptr(ag) if some else None, self._ptr(ah) if some else None, self._ptr(tg), self._ptr(th), self._stream()))
-        return (scores, tg, th, ag, ah, index, offsets) if per_atom else (scores, tg, th)
+            call = self._views_call(coords, centers, channels, radii, num_channels, posed=posed, device=True,
+                                    check=self._hessian_rules(field, pivots))
+            out = self._score_hessian(call, field, pivots, posed, per_atom)
+        return out + (call.index, call.offsets) if per_atom else out
 
     # ------------------------------------------------------------------------------------------
     # DAMPED NEWTON REFINEMENT OF POSES (mvx_lm_step between two Hessian evaluations; nothing comes to the host in between)
@@ -1658,7 +1668,7 @@ class Voxelizer(BaseVoxelizer):
         Returns (quaternions (B, 4), translations (B, 3), scores (B,), info): info["lam"], info["taken"], info["dropped"] per
         pose, info["evaluations"], info["score_history"] (rounds + 1, B): the accepted score of every pose after each round."""
         self._hessian_guard(channels)
-        self._check_pose(np.asarray(offsets).shape[0] - 1, centers, quaternions, translations)
+        self._check_pose(self._pose_count(offsets), centers, quaternions, translations)
         return self._refine(lambda q, t: self.score_hessian_posed_batch(coords, offsets, centers, q, t, channels, radii, field, num_channels),
                             quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
 
@@ -1667,7 +1677,7 @@ class Voxelizer(BaseVoxelizer):
         """refine_posed_batch for B poses of ONE shared cloud (score_hessian_posed_views: every evaluation selects the poses'
         atoms, one stream synchronisation each)."""
         self._hessian_guard(channels)
-        self._check_pose(int(getattr(centers, "shape", (0,))[0]), centers, quaternions, translations)
+        self._check_pose(self._pose_count(None, centers), centers, quaternions, translations)
         return self._refine(lambda q, t: self.score_hessian_posed_views(coords, centers, q, t, channels, radii, field, num_channels),
                             quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
 
@@ -1759,44 +1769,13 @@ class Voxelizer(BaseVoxelizer):
 
     def _score_views(self, coords, centers, channels, radii, field, num_channels=None, random_translation=0.0,
                      random_rotation=False, per_atom=False, posed=None):
-        """score_views' body. posed: (quaternions, translations) of score_posed_views."""
+        """score_views' call. posed: (quaternions, translations) of score_posed_views."""
         self._score_guard(field)
         call = self._views_call(coords, centers, channels, radii, num_channels, random_translation, random_rotation, posed,
-                                device=True, score=True, check=lambda B, C_, offsets: self._check_args_score(field, B, C_))
-        F = self._field_tensor(field)
-        B, C_, grad = call.B, call.C, call.grad
-        stride = C_ * self.dimension ** 3 if F.dim() == 5 else 0  # (one field per view)
-        feat = call.channels if call.mode == "features" else None
-        need_gf = grad and feat is not None and feat.requires_grad
-
-        def run(index, offsets):
-            """One mvx_score_views call: with a selection, the per-row outputs this call needs; without, scores alone."""
-            total = 0 if index is None else int(offsets[-1])
-            scores = torch.empty(B, dtype=torch.float64, device=self.device)
-            atoms = torch.empty(total, dtype=torch.float64, device=self.device) if (per_atom and index is not None) else None
-            gc = torch.empty((total, 3), dtype=torch.float64, device=self.device) if (grad and index is not None) else None
-            gf = torch.empty((total, C_), dtype=self._tfp, device=self.device) if (need_gf and index is not None) else None
-            # (an empty selection: an empty tensor has no address, but a non-null index is what says "selected" to the library)
-            some = index is not None and total > 0
-            pad = torch.empty(1, dtype=torch.int64, device=self.device) if (index is not None and not some) else None
-            _lib.check(self._lib.mvx_score_views(
-                *call.views_args(self), None if index is None else (index if some else pad).data_ptr(),
-                offsets.ctypes.data if index is not None else None, self._ptr(F), stride, self._ptr(scores),
-                self._ptr(atoms) if some else None, self._ptr(gc) if some else None, self._ptr(gf) if some else None,
-                self._stream()))
-            return scores, atoms, gc, gf
-
-        if not grad and not per_atom:
-            return run(None, None)[0]
-        with torch.no_grad():
-            index, offsets = self._select(call)
-        if not grad:
-            scores, atoms, _, _ = run(index, offsets)
-            return scores, atoms, index, offsets
-        call.index, call.offsets = index, offsets  # (backward(): the rows are laid out in selection order)
-        out = _ScoreViewsFunction.apply(self, lambda: run(index, offsets), call, per_atom, call.coords, feat, call.centers,
-                                        call.pose)
-        return (out[0], out[1], index, offsets) if per_atom else out[0]
+                                device=True, score=True,
+                                check=lambda B, C_, offsets: self._check_grid_operand(field, "field", B, C_))
+        out = self._score(call, field, per_atom)
+        return out + (call.index, call.offsets) if per_atom else out
 
     # ------------------------------------------------------------------------------------------
     # autograd (differentiable=True): the forward call runs inside _VoxelizeFunction, the backward is mvx_backward_batch
@@ -1946,13 +1925,34 @@ def _center_grad(g, cen, lengths):
     return -torch.segment_reduce(g, "sum", lengths=lengths, axis=0).reshape(cen.shape)
 
 
-def _rigid_grads(vox, spec, c, g, cen, lengths, need_cen, need_pose):
-    """The tail the three backward() share: (dL/dcentres, dL/d(packed poses)) from the per-atom dL/dcoords `g` of the rows
-    `c`. lengths: as _center_grad takes them."""
-    gcen = _center_grad(g, cen, lengths) if need_cen else None
-    # explicit poses: the per-atom gradients reduced to dL/dc, dL/dq, dL/dt per molecule (autograd splits the block)
-    gpose = vox._pose_backward(spec, c, g) if need_pose else None
-    return gcen, gpose
+def _input_grads(vox, spec, c, index, gc, gf, cen, need_c, need_cen, need_pose, up=None, lengths=None):
+    """The tail the three backward() share, from the rows to the inputs: (dL/dcoords, dL/dfeatures, dL/dcentres,
+    dL/d(packed poses)) from the per-row dL/dcoords `gc` and dL/dfeatures `gf` (each or None). A batch's rows are its atoms'.
+    The rows of views (`index`: their selection, as autograd saved it) are summed onto the shared atoms with mvx_views_reduce -
+    no autograd index backward, no atomics - and reduced to centres and poses per view. up: the upstream of every row of a
+    score call, which scales its saved rows first (the scaled feature rows live only as long as their reduction takes).
+    lengths: spec.row_lengths where the caller has them."""
+    scaled = (lambda g: g) if up is None else (lambda g: g * up[:, None].to(g.dtype))
+    if gc is not None:
+        gc = scaled(gc)
+    if spec.views:
+        gcoords = vox.views_reduce(gc, index, spec.offsets, spec.N) if need_c else None
+        gfeat = vox.views_reduce(scaled(gf), index, spec.offsets, spec.N) if gf is not None else None
+        c = c[index] if need_pose else None
+        one_centre = False
+    else:
+        gcoords, gfeat = gc if need_c else None, None if gf is None else scaled(gf)
+        one_centre = need_cen and cen.numel() == 3  # (a single-molecule call: all rows belong to the one centre)
+    gcen = None
+    if need_cen:
+        if one_centre:
+            lengths = None
+        elif lengths is None:
+            lengths = spec.row_lengths(gc.device)
+        gcen = _center_grad(gc, cen, lengths)
+    # explicit poses: the per-row gradients reduced to dL/dc, dL/dq, dL/dt per molecule (autograd splits the block)
+    gpose = vox._pose_backward(spec, c, gc) if need_pose else None
+    return gcoords, gfeat, gcen, gpose
 
 
 if torch is not None:
@@ -1978,23 +1978,22 @@ if torch is not None:
             gc, gf, gr, gsig, grs = ctx.vox._backward(ctx.spec, c, f, grad, need_f, need_r, need_sig, need_rsc)
             like = lambda g, t: None if g is None else g.to(dtype=t.dtype).reshape(t.shape).to(t.device)  # noqa: E731
             gsig, grs = like(gsig, ctx.scalars[0]), like(grs, ctx.scalars[1])
-            lengths = None
-            if need_cen and cen.numel() != 3:
-                lengths = torch.as_tensor(np.diff(ctx.spec.offsets), device=gc.device)
-            gcen, gpose = _rigid_grads(ctx.vox, ctx.spec, c, gc, cen, lengths, need_cen, need_pose)
-            return None, None, None, None, gc if need_c else None, gf, gcen, gr, gsig, grs, gpose
+            gc, gf, gcen, gpose = _input_grads(ctx.vox, ctx.spec, c, None, gc, gf, cen, need_c, need_cen, need_pose)
+            return None, None, None, None, gc, gf, gcen, gr, gsig, grs, gpose
 
 
     class _ScoreFunction(torch.autograd.Function):
-        """scores (and atom_scores) = score(coords, features, center, packed poses): the one walk of mvx_score_batch also writes
-        dS/dcoords and dS/dfeatures, which are saved; backward scales each atom's rows by its upstream (dL/dS of its molecule plus,
-        with per_atom, dL/ds_n) and reduces centres and poses as _VoxelizeFunction does. No second walk."""
+        """scores (and atom_scores) = score(coords, features, centres, packed poses, field) of a batch, or of B views of one
+        shared cloud (no field gradient: `field` is None): the one walk of mvx_score_batch / mvx_score_views also writes
+        dS/dcoords and dS/dfeatures per row, which are saved; backward scales each row by its upstream (dL/dS of its molecule or
+        view plus, with per_atom, dL/ds_n) and takes the rows to the inputs as _VoxelizeFunction does (_input_grads). No second
+        walk."""
 
         @staticmethod
-        def forward(ctx, vox, run, spec, per_atom, c, f, cen, pose, field=None):
+        def forward(ctx, vox, run, spec, per_atom, c, f, cen, pose, field):
             scores, atoms, gc, gf = run()
             ctx.vox, ctx.spec = vox, spec
-            ctx.save_for_backward(c, cen, pose, gc, gf)
+            ctx.save_for_backward(c, cen, pose, gc, gf, spec.index)
             ctx.field_like = None if field is None else (field.dtype, field.device)
             if per_atom:
                 return scores, atoms
@@ -2003,87 +2002,27 @@ if torch is not None:
         @staticmethod
         @torch.autograd.function.once_differentiable
         def backward(ctx, gs, ga=None):
-            c, cen, pose, gc, gf = ctx.saved_tensors
+            c, cen, pose, gc, gf, index = ctx.saved_tensors
             need_c, need_f, need_cen, need_pose, need_field = ctx.needs_input_grad[4:9]
-            lengths = torch.as_tensor(np.diff(ctx.spec.offsets), device=c.device)
-            up = _row_upstream(gs, ga, lengths, c.shape[0])
-            gcs = gc * up[:, None] if gc is not None else None
-            gfs = (gf * up[:, None].to(gf.dtype)) if (need_f and gf is not None) else None
-            gcen, gpose = _rigid_grads(ctx.vox, ctx.spec, c, gcs, cen, None if (need_cen and cen.numel() == 3) else lengths,
-                                       need_cen, need_pose)
+            vox, spec = ctx.vox, ctx.spec
+            lengths = spec.row_lengths(c.device)
+            up = _row_upstream(gs, ga, lengths, spec.rows)  # dL/ds of every row
+            gcoords, gfeat, gcen, gpose = _input_grads(vox, spec, c, index, gc, gf if need_f else None, cen, need_c, need_cen,
+                                                       need_pose, up, lengths)
             gfield = None
             if need_field and ctx.field_like is not None:
                 # dL/dfield[c, v] = sum_n up_n w[n,c] rho_{n,c}(v): the saved call's grids summed with one float32 weight per atom
-                gfield = ctx.vox._sum_call(ctx.spec, up.to(torch.float32), None, False, coords=c)
+                gfield = vox._sum_call(spec, up.to(torch.float32), None, False, coords=c)
                 gfield = gfield.to(dtype=ctx.field_like[0]).to(ctx.field_like[1])
-            return None, None, None, None, gcs if need_c else None, gfs, gcen, gpose, gfield
+            return None, None, None, None, gcoords, gfeat, gcen, gpose, gfield
 
 
     class _MomentsFunction(torch.autograd.Function):
-        """moments = moments(coords, features, centres, packed poses) on a moments_grad voxelizer: the forward call as it runs
-        without autograd (same kernels, same bits); backward = mvx_moments_backward_batch from the saved inputs, the target as
-        the forward read it and the call's record (`spec`: a random transform's records are reused, not redrawn), then centres
-        and poses reduced as _VoxelizeFunction does."""
-
-        @staticmethod
-        def forward(ctx, vox, run, spec, c, f, cen, pose):
-            out, T = run()
-            ctx.vox, ctx.spec = vox, spec
-            ctx.save_for_backward(c, f, cen, pose, T)
-            return out
-
-        @staticmethod
-        @torch.autograd.function.once_differentiable
-        def backward(ctx, gm):
-            c, f, cen, pose, T = ctx.saved_tensors
-            need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[3:7]
-            gc, gf = ctx.vox._moments_backward(ctx.spec, c, f, T, gm, need_f)
-            lengths = None
-            if need_cen and cen.numel() != 3:
-                lengths = torch.as_tensor(np.diff(ctx.spec.offsets), device=gc.device)
-            gcen, gpose = _rigid_grads(ctx.vox, ctx.spec, c, gc, cen, lengths, need_cen, need_pose)
-            return None, None, None, gc if need_c else None, gf, gcen, gpose
-
-
-    class _ScoreViewsFunction(torch.autograd.Function):
-        """scores (and atom_scores) of B views of one shared cloud = score(coords, features, centres, packed poses): the one walk of
-        mvx_score_views also writes dS/dcoords and dS/dfeatures per (view, atom) row, which are saved. backward scales each row by
-        its upstream, as _ScoreFunction does, sums the rows onto the shared atoms with mvx_views_reduce (no autograd index
-        backward, no atomics), and reduces centres and poses per view. No second walk."""
-
-        @staticmethod
-        def forward(ctx, vox, run, spec, per_atom, c, f, cen, pose):
-            scores, atoms, gc, gf = run()
-            ctx.vox, ctx.spec = vox, spec
-            ctx.save_for_backward(c, cen, pose, gc, gf, spec.index)
-            if per_atom:
-                return scores, atoms
-            return (scores,)
-
-        @staticmethod
-        @torch.autograd.function.once_differentiable
-        def backward(ctx, gs, ga=None):
-            c, cen, pose, gc, gf, index = ctx.saved_tensors
-            need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[4:8]
-            vox, spec = ctx.vox, ctx.spec  # (spec.offsets: the selection's; spec.N: the atoms of the shared cloud)
-            # (through pinned memory: a pageable copy would synchronise the stream)
-            lengths = torch.from_numpy(np.diff(spec.offsets)).pin_memory().to(gc.device, non_blocking=True)
-            up = _row_upstream(gs, ga, lengths, gc.shape[0])  # dL/ds of every (view, atom) row
-            gcs = gc * up[:, None]
-            gcoords = vox.views_reduce(gcs, index, spec.offsets, spec.N) if need_c else None
-            gfeat = None
-            if need_f and gf is not None:
-                gfeat = vox.views_reduce(gf * up[:, None].to(gf.dtype), index, spec.offsets, spec.N)
-            gcen, gpose = _rigid_grads(vox, spec, c[index] if need_pose else None, gcs, cen, lengths, need_cen, need_pose)
-            return None, None, None, None, gcoords, gfeat, gcen, gpose
-
-
-    class _MomentsViewsFunction(torch.autograd.Function):
-        """moments of B views of one shared cloud = moments(coords, features, centres, packed poses) on a moments_grad voxelizer:
-        the forward call as it runs without autograd, with the selection made before it (same kernels, same bits); backward =
-        mvx_moments_backward_views from the saved inputs, the target as the forward read it and the call's record, whose rows per
-        (view, atom) are summed onto the shared atoms with mvx_views_reduce, as _ScoreViewsFunction sums its own, and reduced to
-        centres and poses per view."""
+        """moments = moments(coords, features, centres, packed poses) of a batch, or of B views of one shared cloud, on a
+        moments_grad voxelizer: the forward call as it runs without autograd (same kernels, same bits; for views with the
+        selection made before it); backward = mvx_moments_backward_batch / mvx_moments_backward_views from the saved inputs, the
+        target as the forward read it and the call's record (`spec`: a random transform's records are reused, not redrawn),
+        then the rows taken to the inputs as _VoxelizeFunction does (_input_grads)."""
 
         @staticmethod
         def forward(ctx, vox, run, spec, c, f, cen, pose):
@@ -2097,14 +2036,8 @@ if torch is not None:
         def backward(ctx, gm):
             c, f, cen, pose, T, index = ctx.saved_tensors
             need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[3:7]
-            vox, spec = ctx.vox, ctx.spec  # (spec.offsets: the selection's; spec.N: the atoms of the shared cloud)
-            gc, gf = vox._moments_backward_views(spec, c, f, T, index, gm, need_f)
-            # (through pinned memory: a pageable copy would synchronise the stream)
-            lengths = torch.from_numpy(np.diff(spec.offsets)).pin_memory().to(gc.device, non_blocking=True)
-            gcoords = vox.views_reduce(gc, index, spec.offsets, spec.N) if need_c else None
-            gfeat = vox.views_reduce(gf, index, spec.offsets, spec.N) if gf is not None else None
-            gcen, gpose = _rigid_grads(vox, spec, c[index] if need_pose else None, gc, cen, lengths, need_cen, need_pose)
-            return None, None, None, gcoords, gfeat, gcen, gpose
+            gc, gf = ctx.vox._moments_backward(ctx.spec, c, f, T, gm, need_f)
+            return (None, None, None) + _input_grads(ctx.vox, ctx.spec, c, index, gc, gf, cen, need_c, need_cen, need_pose)
 
 
 def transform_on_device(coords, center, translation, quaternion):
