@@ -719,6 +719,69 @@ int mvx_lm_step(mvx_handle *h, int32_t B, int32_t have_trial, double lam_down, d
                 const double *S2, const double *G2, const double *H2, double *xi, void *stream);
 
 /*
+ * TORSION COORDINATES (no counterpart in the reference): rotatable bonds next to the rigid twist, for B molecules of T torsions
+ * each, 0 <= T <= 32 (a molecule with fewer pads with axes of -1). Torsion k of a molecule has an axis from atom a_k to atom b_k
+ * (indices local to the molecule) and a moving set M_k, bit k of the per-atom mask moves[n]. The sets form a tree: b_k in M_k,
+ * a_k not in M_k; for k < l either M_l is a proper subset of M_k (then a_l, b_l in M_k) or the two are disjoint; parents come
+ * before children - so "k is l or an ancestor of l" is bit k of moves[b_l]. The library does not check the tree (the Python
+ * layer's check_torsions does). A torsion is INERT when a_k or b_k is outside [0, N_b), or the axis has zero or no finite
+ * length: it turns nothing, its gradient entry and its Hessian row and column are exact zeros. No axis index is used unchecked.
+ *
+ * mvx_apply_torsions: the conformer C(theta): for k = 0 .. T-1 in order, the atoms of M_k are turned by angles[b, k] about the
+ * CURRENT axis (a_k, b_k) through b_k (Rodrigues' formula, sin and cos in float64). One workgroup per molecule.
+ *   coords, out: (sumN, 3) double, device; out may be coords. offsets: (B + 1,) int64, host. axes: (B, T, 2) int32, device.
+ *   moves: (sumN,) int32, device, read as 32 bits. angles: (B, T) double, device.
+ * An angle of exactly 0 and an inert torsion turn nothing; atoms in no turned set are copied bit for bit. Asynchronous on
+ * `stream`. MVX_ERR_INVALID before any device is touched for, in order: B < 0; T outside 0 .. 32; NULL offsets with B > 0,
+ * offsets[0] != 0 or decreasing offsets; offsets[B] >= 2^31; NULL coords or out with atoms; NULL axes, moves or angles with
+ * atoms and T > 0; a NULL handle. No molecules or no atoms: MVX_OK.
+ */
+int mvx_apply_torsions(mvx_handle *h, const double *coords, const int64_t *offsets, int32_t B, int32_t T, const int32_t *axes,
+                       const int32_t *moves, const double *angles, double *out, void *stream);
+
+/*
+ * mvx_score_hessian_batch with torsions: the gradient and Hessian of the scores in the coordinates x = (tau, omega, theta_0 ..
+ * theta_{T-1}), n = 6 + T, at x = 0, where p_n(x) = exp([omega]x) (C(theta)_n - o_b) + o_b + tau in the grid frame and the
+ * caller's coords are the conformer the angles are counted from. The same walk and reductions as mvx_score_hessian_batch - its
+ * arguments, rules and outputs, each bit for bit -, then per (molecule, torsion) one workgroup sums over the atoms of M_k, in
+ * twist_hess's order and skipping atoms whose g and H rows are all zero, with r_n = p_n - o_b and J_n = [I | -[r_n]x]:
+ *   F_k = sum g_n   N_k = sum r_n x g_n   X_k = sum J_n^T H_n J_n (6x6)   K_k = sum r_n g_n^T (3x3)
+ * and with u_k the unit axis, s_k = (tau_k, u_k) = ((p_{b_k} - o_b) x u_k, u_k) and c_k = tau_k x F_k + (K_k - tr(K_k) I) u_k:
+ *   flex_grad[b]: (n,)    [twist_grad | s_k . (F_k, N_k)]
+ *   flex_hess[b]: (n, n)  [:6, :6] = twist_hess; [:6, 6 + k] = X_k s_k with c_k added to the omega rows; [6 + k, 6 + l] =
+ *                         s_k^T X_l s_l + u_k . c_l where k is l or an ancestor of l, 0 for unrelated torsions; mirrored:
+ *                         symmetric to the bit, written in full, row-major
+ *   T, axes (B, T, 2) int32, moves (sumN,) int32: as for mvx_apply_torsions, device; NULL allowed with T == 0.
+ *   flex_grad: (B, n) double; flex_hess: (B, n, n) double or NULL; atom_pos: (sumN, 3) double or NULL: the grid-frame positions
+ *   p_n the records hold, copied out.
+ * T == 0 gives the twist values. The subset sums live in handle-owned workspace (B * T * 36 doubles, and the twist values where
+ * the caller passed NULL for them). No atomics; a molecule's values do not depend on its batch. MVX_ERR_INVALID before any device
+ * is touched for what mvx_score_hessian_batch rejects, in its order, then for T outside 0 .. 32, for NULL axes with T > 0
+ * and B > 0 or NULL moves with T > 0 and atoms, and for a NULL flex_grad with B > 0.
+ */
+int mvx_score_hessian_flex_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                                 double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                                 int32_t B, int32_t C, const void *field, int64_t field_mol_stride, const double *pivots,
+                                 double *scores, double *atom_grad, double *atom_hess, double *twist_grad, double *twist_hess,
+                                 int32_t T, const int32_t *axes, const int32_t *moves, double *flex_grad, double *flex_hess,
+                                 double *atom_pos, void *stream);
+
+/*
+ * mvx_lm_step in n = 6 + T coordinates: the same state machine per pose, statement for statement, with G, H, G2, H2 and x of
+ * width n ((B, n), (B, n, n)) and the torsion angles theta, theta2 (B, T) next to the pose. One wave per pose, the n x (n + 1)
+ * system in LDS; the same pivot rule (the first row at or below k with the largest |entry|), the same element operations and
+ * back substitution in ascending column order: with T == 0 the results are mvx_lm_step's bits. An accepted trial also copies
+ * theta2 -> theta; the next trial is theta2 = theta + x[6:]. A zero pivot or a non-finite component of x, q, t, theta, lam, q2,
+ * t2 or theta2: x = 0 and the trial is the state. MVX_ERR_INVALID before any device is touched for: B < 0; T outside 0 .. 32; a
+ * NULL q, t, S, G, H, lam, taken, dropped, q2 or t2 with B > 0, or a NULL theta or theta2 with B > 0 and T > 0; a NULL S2, G2 or
+ * H2 with have_trial and B > 0; max_dropped < 1; lam_down or lam_up not finite or <= 0; a NULL handle. B == 0: MVX_OK.
+ */
+int mvx_flex_lm_step(mvx_handle *h, int32_t B, int32_t T, int32_t have_trial, double lam_down, double lam_up, int32_t max_dropped,
+                     double *q, double *t, double *theta, double *S, double *G, double *H, double *lam, int32_t *taken,
+                     int32_t *dropped, double *q2, double *t2, double *theta2, const double *S2, const double *G2, const double *H2,
+                     double *x, void *stream);
+
+/*
  * Replaces do_transform on an (N,3) fp64 point cloud (numpy/transform.py:44-60): out = transformed coords.
  * Exposed so that RandomTransform/T objects can run on device-resident coordinates.
  */

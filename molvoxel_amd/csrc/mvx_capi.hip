@@ -5,6 +5,7 @@
 // fully asynchronous on the caller's stream (no hidden device synchronisation). There is no CPU
 // fallback in this library: without a usable HIP device mvx_create fails.
 #include "mvx_grad.h"
+#include "mvx_flex.h"
 #include "mvx_hess.h"
 #include "mvx_internal.h"
 #include "mvx_lm.h"
@@ -130,6 +131,9 @@ struct mvx_handle : NoCopy {
     DevBuf grad_rpart; // radius gradients: per-atom / per-(channel, atom) partials of channel-wise radii and their stage sums
     DevBuf score_atoms; // mvx_score_batch without atom_scores: the per-atom scores its reduction reads, 8 bytes per atom
     DevBuf hess_rows;   // mvx_score_hessian_batch: [s_n | g_n | H_n], 8 + 24 + 48 bytes per atom; rows handed out are not used
+    // mvx_score_hessian_flex_batch: [subset sums, B * T * 36 doubles | twist_grad, B * 6 | twist_hess, B * 36] (the twist values
+    // only where the caller passed null for them); mvx_apply_torsions: the call's offsets
+    DevBuf flex_ws, flex_off;
     // "grad_order" option: 0 atoms in the caller's order (the default), 1 in spatial order, XCD by XCD. The spatial order cuts
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
     // more than it saves (profiles/r05_grad.txt)
@@ -1420,6 +1424,15 @@ struct HessCall {
     double *twist_grad, *twist_hess;      // (B, 6), (B, 36), each or null
 };
 
+// mvx_score_hessian_flex_batch next to its HessCall (`on`: the call is that entry)
+struct FlexCall {
+    bool on;
+    int32_t T;
+    const int32_t *axes, *moves; // (B, T, 2), (total,)
+    double *flex_grad, *flex_hess; // (B, n), (B, n, n) or null, n = 6 + T
+    double *atom_pos;              // (total, 3) or null
+};
+
 // What a backward call reads next to its Call and where its results go (outputs a kind does not have are null).
 struct GradOut {
     BackwardKind kind;
@@ -1430,6 +1443,7 @@ struct GradOut {
     ScoreCall score; // BWD_SCORE only
     MomentsArgs moments{}; // BWD_MOMENTS only
     HessCall hess{};       // BWD_HESS only
+    FlexCall flex{};       // BWD_HESS only: mvx_score_hessian_flex_batch
     bool scoring() const { return kind == BWD_SCORE || kind == BWD_HESS; } // walks a constant field: ScoreCall is filled
 };
 
@@ -1492,6 +1506,17 @@ int check_hessian(const Call &c, const GradOut &o, const char *form) {
     return MVX_OK;
 }
 
+// ---- ... and the three of mvx_score_hessian_flex_batch behind them (`atoms`: the call has any) ----
+int check_flex(const Call &c, const GradOut &o, bool atoms) {
+    if (!o.flex.on) return MVX_OK;
+    if (o.flex.T < 0 || o.flex.T > FLEX_MAX_T) return fail(MVX_ERR_INVALID, "T must be 0 ... 32");
+    // (a batch without atoms has no masks: its moves may be null)
+    if (o.flex.T > 0 && c.B > 0 && (!o.flex.axes || (atoms && !o.flex.moves)))
+        return fail(MVX_ERR_INVALID, "axes and moves must not be null with T > 0");
+    if (c.B > 0 && !o.flex.flex_grad) return fail(MVX_ERR_INVALID, "flex_grad must not be null");
+    return MVX_OK;
+}
+
 // zeros for `nradii` radius gradients, for sigma and for a scalar radius, where the call has these outputs
 int zero_density_grads(const GradOut &o, size_t nradii, hipStream_t s) {
     if (o.grad_radii && nradii) HIP_TRY(hipMemsetAsync(o.grad_radii, 0, nradii * sizeof(double), s));
@@ -1506,6 +1531,11 @@ int backward_no_atoms(const Call &c, const GradOut &o) {
     if (o.scoring()) HIP_TRY(hipMemsetAsync(o.score.scores, 0, (size_t)c.B * sizeof(double), c.stream)); // (every molecule scores 0)
     if (o.hess.twist_grad) HIP_TRY(hipMemsetAsync(o.hess.twist_grad, 0, (size_t)c.B * 6 * sizeof(double), c.stream));
     if (o.hess.twist_hess) HIP_TRY(hipMemsetAsync(o.hess.twist_hess, 0, (size_t)c.B * 36 * sizeof(double), c.stream));
+    if (o.flex.on) { // (no atoms: every torsion is inert)
+        const size_t n = 6 + (size_t)o.flex.T;
+        HIP_TRY(hipMemsetAsync(o.flex.flex_grad, 0, (size_t)c.B * n * sizeof(double), c.stream));
+        if (o.flex.flex_hess) HIP_TRY(hipMemsetAsync(o.flex.flex_hess, 0, (size_t)c.B * n * n * sizeof(double), c.stream));
+    }
     return MVX_OK;
 }
 
@@ -1606,9 +1636,21 @@ struct Backward {
         ha.mol_stride = o.score.mol_stride;
         HIP_TRY(launch_score_hess(ga, ha, key, s));
         HIP_TRY(launch_score_reduce(ha.atom_scores, in.offsets, c.B, o.score.scores, s));
-        if (o.hess.twist_grad)
-            HIP_TRY(launch_twist_reduce(ga.rec, ha.atom_grad, ha.atom_hess, in.offsets, o.hess.pivots, c.B, o.hess.twist_grad,
-                                        o.hess.twist_hess, s));
+        double *tg = o.hess.twist_grad, *th = o.hess.twist_hess;
+        double *subset = nullptr;
+        if (o.flex.on) { // the twist values are the first six rows and columns: workspace where the caller wants none
+            const size_t nsub = (size_t)c.B * (size_t)o.flex.T * FLEX_SUBSET;
+            if (int rc = ensure(h->flex_ws, (nsub + (size_t)c.B * 42) * sizeof(double))) return rc;
+            subset = reinterpret_cast<double *>(h->flex_ws.p);
+            if (!tg) tg = subset + nsub;
+            if (!th) th = subset + nsub + (size_t)c.B * 6;
+        }
+        if (tg) HIP_TRY(launch_twist_reduce(ga.rec, ha.atom_grad, ha.atom_hess, in.offsets, o.hess.pivots, c.B, tg, th, s));
+        if (o.flex.on) {
+            FlexArgs fa{ga.rec, ha.atom_grad, ha.atom_hess, in.offsets, o.hess.pivots, o.flex.axes, o.flex.moves, tg, th, subset,
+                        o.flex.flex_grad, o.flex.flex_hess, o.flex.atom_pos, total, c.B, o.flex.T};
+            HIP_TRY(launch_flex(fa, s));
+        }
         return MVX_OK;
     }
     // BWD_MOMENTS: the walk over the chunk's grids with the upstream formed from them, the coefficients and the target
@@ -1686,6 +1728,7 @@ int backward_impl(mvx_handle *h, const Call &c, const GradOut &o) {
     if (e.total > 0 && (rc = check_backward_grid(h, c, o))) return rc;
     if (o.kind == BWD_HESS) { // its own rules, behind every rule of mvx_score_batch
         if ((rc = check_hessian(c, o, "batch"))) return rc;
+        if ((rc = check_flex(c, o, e.total > 0))) return rc;
         if (c.B == 0) return MVX_OK;
     }
     CallScope scope(h, c.stream);
@@ -1856,6 +1899,18 @@ int mvx_score_hessian_batch(mvx_handle *h, int32_t mode, const double *coords, c
     return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream), o);
 }
 
+int mvx_score_hessian_flex_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
+                                 double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
+                                 int32_t B, int32_t C, const void *field, int64_t field_mol_stride, const double *pivots,
+                                 double *scores, double *atom_grad, double *atom_hess, double *twist_grad, double *twist_hess,
+                                 int32_t T, const int32_t *axes, const int32_t *moves, double *flex_grad, double *flex_hess,
+                                 double *atom_pos, void *stream) {
+    GradOut o{BWD_HESS, field, nullptr, nullptr, nullptr, nullptr, nullptr, {field_mol_stride, scores, nullptr}};
+    o.hess = {pivots, atom_grad, atom_hess, twist_grad, twist_hess};
+    o.flex = {true, T, axes, moves, flex_grad, flex_hess, atom_pos};
+    return backward_impl(h, batch_call(mode, coords, channels, radii, radius_scalar, radii_type, offsets, xforms, B, C, stream), o);
+}
+
 int mvx_moments_backward_batch(mvx_handle *h, int32_t mode, const double *coords, const void *channels, const mvx_real *radii,
                                double radius_scalar, int32_t radii_type, const int64_t *offsets, const mvx_xform *xforms,
                                int32_t B, int32_t C, const float *target, const double *grad_moments, double *grad_coords,
@@ -2017,6 +2072,53 @@ int mvx_lm_step(mvx_handle *h, int32_t B, int32_t have_trial, double lam_down, d
     if (scope.rc) return scope.rc;
     HIP_TRY(launch_lm_step({B, have_trial != 0, max_dropped, lam_down, lam_up, q, t, S, G, H, lam, taken, dropped, q2, t2, S2, G2, H2, xi}, s));
     return MVX_OK;
+}
+
+int mvx_flex_lm_step(mvx_handle *h, int32_t B, int32_t T, int32_t have_trial, double lam_down, double lam_up, int32_t max_dropped,
+                     double *q, double *t, double *theta, double *S, double *G, double *H, double *lam, int32_t *taken,
+                     int32_t *dropped, double *q2, double *t2, double *theta2, const double *S2, const double *G2, const double *H2,
+                     double *x, void *stream) {
+    // ---- what is checked before any device is touched: mvx_lm_step's rules, T behind B ----
+    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (T < 0 || T > FLEX_MAX_T) return fail(MVX_ERR_INVALID, "T must be 0 ... 32");
+    if (B > 0 && (!q || !t || !S || !G || !H || !lam || !taken || !dropped || !q2 || !t2))
+        return fail(MVX_ERR_INVALID, "q, t, S, G, H, lam, taken, dropped, q2 and t2 must not be null");
+    if (B > 0 && T > 0 && (!theta || !theta2)) return fail(MVX_ERR_INVALID, "theta and theta2 must not be null with T > 0");
+    if (B > 0 && have_trial && (!S2 || !G2 || !H2)) return fail(MVX_ERR_INVALID, "S2, G2 and H2 must not be null with have_trial");
+    if (max_dropped < 1) return fail(MVX_ERR_INVALID, "max_dropped must be >= 1");
+    if (!(lam_down > 0.0) || !(lam_up > 0.0) || !std::isfinite(lam_down) || !std::isfinite(lam_up))
+        return fail(MVX_ERR_INVALID, "lam_down and lam_up must be finite and > 0");
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (B == 0) return MVX_OK;
+
+    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    CallScope scope(h, s);
+    if (scope.rc) return scope.rc;
+    HIP_TRY(launch_flex_lm_step({B, T, have_trial != 0, max_dropped, lam_down, lam_up, q, t, theta, S, G, H, lam, taken, dropped, q2, t2,
+                                 theta2, S2, G2, H2, x}, s));
+    return MVX_OK;
+}
+
+int mvx_apply_torsions(mvx_handle *h, const double *coords, const int64_t *offsets, int32_t B, int32_t T, const int32_t *axes,
+                       const int32_t *moves, const double *angles, double *out, void *stream) {
+    // ---- what is checked before any device is touched ----
+    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (T < 0 || T > FLEX_MAX_T) return fail(MVX_ERR_INVALID, "T must be 0 ... 32");
+    Extent e;
+    if (const char *bad = check_offsets(offsets, B, e)) return fail(MVX_ERR_INVALID, bad);
+    if (const char *bad = too_many_atoms(e.total)) return fail(MVX_ERR_INVALID, bad);
+    if (e.total > 0 && (!coords || !out)) return fail(MVX_ERR_INVALID, "coords / out must not be null");
+    if (e.total > 0 && T > 0 && (!axes || !moves || !angles)) return fail(MVX_ERR_INVALID, "axes, moves and angles must not be null with T > 0");
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (e.total == 0) return MVX_OK;
+
+    const Call c = batch_call(0, nullptr, nullptr, nullptr, 0.0, 0, offsets, nullptr, B, 0, stream); // (what stage_meta reads)
+    CallScope scope(h, c.stream);
+    if (scope.rc) return scope.rc;
+    DeviceInputs in; // the offsets through a pinned slot, as the backward entries stage theirs
+    if (int rc = stage_meta(h, h->flex_off, c, false, 0, in)) return rc;
+    HIP_TRY(launch_torsion_apply(coords, in.offsets, B, T, axes, moves, angles, out, c.stream));
+    return release_slot(in.slot, c.stream);
 }
 
 int mvx_transform_coords(mvx_handle *h, const double *coords, int64_t N, const mvx_xform *xform, double *out,

@@ -154,6 +154,71 @@ def as_molecule(mol) -> Molecule:
     raise TypeError(f"expected a Molecule or an RDKit Mol, got {type(mol).__name__}")
 
 
+def torsion_tree(molecule, root=None):
+    """The rotatable bonds of a molecule as the torsion entries of the hip voxelizer read them (apply_torsions,
+    score_hessian_flex_batch): (axes (T, 2) int32, moves (N,) int32). A torsion is a SINGLE bond that lies on no ring and has
+    further neighbours at both ends (a terminal bond turns nothing). Cutting them leaves rigid fragments; the root fragment is the
+    one that holds atom `root` (default: the largest, the lowest atom index among equals) and stays where the pose puts it.
+    Torsion k has its axis from axes[k, 0], on the root's side, to axes[k, 1]; it turns every atom beyond the bond - bit k of
+    moves[n] -, so the sets are nested or disjoint, and parents come before children (depth first from the root, neighbours
+    in index order). Atoms not connected to the root fragment are in no set. Raises ValueError for more than 32 torsions."""
+    mol = as_molecule(molecule)
+    N = mol.num_atoms
+    nbrs = [[] for _ in range(N)]
+    for j, (a, b) in enumerate(mol.bonds):
+        nbrs[int(a)].append((int(b), j))
+        nbrs[int(b)].append((int(a), j))
+    for lst in nbrs:
+        lst.sort()
+
+    def beyond(start, barred):
+        """The atoms reached from `start` without crossing the bonds `barred`."""
+        seen, stack = {start}, [start]
+        while stack:
+            for v, j in nbrs[stack.pop()]:
+                if j not in barred and v not in seen:
+                    seen.add(v)
+                    stack.append(v)
+        return seen
+
+    cut = set()
+    for j, (a, b) in enumerate(mol.bonds):
+        a, b = int(a), int(b)
+        if int(mol.bond_types[j]) != BondType.SINGLE or len(nbrs[a]) < 2 or len(nbrs[b]) < 2:
+            continue
+        if a not in beyond(b, {j}):  # (acyclic: without the bond its ends fall apart)
+            cut.add(j)
+    if root is None:
+        best, left = None, set(range(N))
+        while left:
+            frag = beyond(min(left), cut)
+            left -= frag
+            if best is None or len(frag) > len(best):
+                best = frag
+        start = min(best) if best else 0
+    else:
+        start = int(root)
+        assert 0 <= start < N, "root out of range"
+    axes, moves = [], np.zeros(N, dtype=np.uint32)
+
+    def walk(atom, came_by):
+        """One rigid fragment, then the fragments behind each of its cut bonds but the one it was entered by, each as a torsion."""
+        frag = beyond(atom, cut)
+        for a in sorted(frag):
+            for b, j in nbrs[a]:
+                if j in cut and j != came_by and b not in frag:
+                    k = len(axes)
+                    if k >= 32:
+                        raise ValueError("more than 32 torsions")
+                    axes.append((a, b))
+                    moves[sorted(beyond(b, {j}))] |= np.uint32(1 << k)
+                    walk(b, j)
+
+    if N:
+        walk(start, -1)
+    return np.array(axes, dtype=np.int32).reshape(-1, 2), moves.view(np.int32)
+
+
 # ---------------------------------------------------------------------------------------------------
 # readers
 # ---------------------------------------------------------------------------------------------------

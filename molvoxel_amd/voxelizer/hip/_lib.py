@@ -109,6 +109,11 @@ SIGNATURES = {
                                           _vp, _vp, _vp, _vp, _vp]),
     "mvx_lm_step": (C.c_int, [Handle, _i32, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp]),
+    "mvx_apply_torsions": (C.c_int, [Handle, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mvx_score_hessian_flex_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp,
+                                               _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvx_flex_lm_step": (C.c_int, [Handle, _i32, _i32, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvx_moments_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mvx_moments_backward_views": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp,
                                              _vp, _vp, _vp]),

@@ -154,6 +154,68 @@ class LMState:
         self.q2 = self.t2 = self.xi = None
 
 
+class FlexLMState:
+    """The state flex_lm_step works on: LMState's tensors for n = 6 + T coordinates - G (B, n), H (B, n, n) - with the torsion
+    angles theta (B, T) next to the pose. q2, t2, theta2, x (B, n): the trial and its step, made by the first flex_lm_step and
+    reused."""
+
+    __slots__ = ("q", "t", "theta", "S", "G", "H", "lam", "taken", "dropped", "q2", "t2", "theta2", "x")
+
+    def __init__(self, q, t, theta, S, G, H, lam, taken=None, dropped=None):
+        B = int(q.shape[0])
+        self.q, self.t, self.theta, self.S, self.G, self.H, self.lam = q, t, theta, S, G, H, lam
+        self.taken = torch.zeros(B, dtype=torch.int32, device=q.device) if taken is None else taken
+        self.dropped = torch.zeros(B, dtype=torch.int32, device=q.device) if dropped is None else dropped
+        self.q2 = self.t2 = self.theta2 = self.x = None
+
+
+def _host_array(x, dtype):
+    return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x), dtype=dtype)
+
+
+def check_torsions(offsets, axes, moves):
+    """The tree rules of the torsion entries, asserted on host copies (device tensors are copied: one synchronisation).
+    offsets (B + 1,); axes (B, T, 2): the axis atoms (a_k, b_k) of every torsion, local to the molecule, T <= 32; moves (N,)
+    int32: bit k set = the atom turns with torsion k. A torsion with an axis atom outside [0, N_b) - padding - or with the same atom
+    at both ends is inert and is skipped.
+    For the others: b_k turns and a_k does not; two sets are nested - the inner one behind the outer one, with both its axis
+    atoms inside it - or disjoint; no two sets are the same. The message names the first offending (molecule, torsion)."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    axes, moves = _host_array(axes, np.int32), _host_array(moves, np.int32).view(np.uint32)
+    B = offsets.shape[0] - 1
+    assert axes.ndim == 3 and axes.shape[0] == B and axes.shape[2] == 2, (
+        f"axes does not match dimension: {tuple(axes.shape)} vs {(B, 'T', 2)}")
+    T = axes.shape[1]
+    assert T <= 32, f"at most 32 torsions per molecule: {T}"
+    assert moves.ndim == 1 and moves.shape[0] == offsets[-1], f"moves does not match dimension: {tuple(moves.shape)} vs {(int(offsets[-1]),)}"
+    seen = set()  # (many poses of one molecule: a tree is checked once)
+    for b in range(B):
+        a0, N = int(offsets[b]), int(offsets[b + 1] - offsets[b])
+        key = (N, axes[b].tobytes(), moves[a0:a0 + N].tobytes())
+        if key in seen:
+            continue
+        seen.add(key)
+        ax = axes[b].astype(np.int64)
+        live = np.flatnonzero(((ax >= 0) & (ax < N)).all(axis=1) & (ax[:, 0] != ax[:, 1]))
+        if live.size == 0:
+            continue
+        sets = ((moves[a0:a0 + N, None] >> live[None, :].astype(np.uint32)) & 1).astype(np.int64)  # (N, live)
+        for j, k in enumerate(live):
+            assert sets[ax[k, 1], j], f"molecule {b}, torsion {k}: the axis atom b = {ax[k, 1]} must turn with it"
+            assert not sets[ax[k, 0], j], f"molecule {b}, torsion {k}: the axis atom a = {ax[k, 0]} must not turn with it"
+        common, size = sets.T @ sets, sets.sum(axis=0)
+        for j in range(1, live.size):  # torsion live[j] against every one before it
+            for i in range(j):
+                k, l, c = live[i], live[j], common[i, j]
+                if c == 0:
+                    continue
+                assert not (c == size[i] == size[j]), f"molecule {b}, torsion {l}: the same set as torsion {k}"
+                assert not (c == size[i] and size[i] < size[j]), f"molecule {b}, torsion {l}: contains the set of torsion {k}, which comes before it (parents come before children)"
+                assert c == size[j], f"molecule {b}, torsion {l}: its set overlaps the set of torsion {k} without lying inside it"
+                assert sets[ax[l, 0], i] and sets[ax[l, 1], i], (
+                    f"molecule {b}, torsion {l}: both axis atoms must lie in the set of torsion {k} around it")
+
+
 class Voxelizer(BaseVoxelizer):
     LIB = "HIP"
     transform_class = RandomTransform
@@ -1681,39 +1743,208 @@ class Voxelizer(BaseVoxelizer):
         return self._refine(lambda q, t: self.score_hessian_posed_views(coords, centers, q, t, channels, radii, field, num_channels),
                             quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
 
-    def _refine(self, evaluate, quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done):
-        """The loop of refine_posed_batch / refine_posed_views. evaluate(q, t) -> (S, G, H)."""
+    def _refine(self, evaluate, quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done, angles=None):
+        """The loop of refine_posed_batch / refine_posed_views, evaluate(q, t) -> (S, G, H), and - with angles (B, T) - of
+        refine_flex_posed_batch, evaluate(q, t, theta) -> (S, G (B, n), H (B, n, n)): flex_lm_step in place of lm_step, and the
+        angles returned behind the poses."""
+        flex = angles is not None
         assert int(steps) >= 0, "steps must be >= 0"
         with torch.no_grad():
             def own(x):  # a float64 copy on this device: the caller's poses are not modified
                 x = x if _is_torch(x) else torch.as_tensor(np.asarray(x, dtype=np.float64))
                 return x.detach().to(device=self.device, dtype=torch.float64).clone().contiguous()
 
-            S, G, H = evaluate(quaternions, translations)  # (the rules of the arguments fire here, before anything is copied)
+            # (the rules of the arguments fire here, before anything is copied)
+            S, G, H = evaluate(quaternions, translations, angles) if flex else evaluate(quaternions, translations)
             q, t = own(quaternions), own(translations)
             B = int(q.shape[0])
             if lam0 is None:
-                lam = 1e-3 * H.abs().reshape(B, 36).amax(dim=1) if B else torch.zeros(0, dtype=torch.float64, device=self.device)
+                lam = (1e-3 * H.abs().reshape(B, int(G.shape[1]) ** 2).amax(dim=1) if B else
+                       torch.zeros(0, dtype=torch.float64, device=self.device))
             else:
                 lam = (lam0.detach().to(device=self.device, dtype=torch.float64) if _is_torch(lam0) else
                        torch.as_tensor(np.asarray(lam0, dtype=np.float64), device=self.device)).expand(B).clone()
-            state = LMState(q, t, S.clone(), G.clone(), H.clone(), lam.contiguous())
+            if flex:
+                state = FlexLMState(q, t, own(angles), S.clone(), G.clone(), H.clone(), lam.contiguous())
+                step, at_trial = self.flex_lm_step, lambda: evaluate(state.q2, state.t2, state.theta2)
+            else:
+                state = LMState(q, t, S.clone(), G.clone(), H.clone(), lam.contiguous())
+                step, at_trial = self.lm_step, lambda: evaluate(state.q2, state.t2)
             history = torch.empty((int(steps) + 1, B), dtype=torch.float64, device=self.device)
             history[0] = state.S
             kw = dict(lam_down=lam_down, lam_up=lam_up, max_dropped=max_dropped)
-            self.lm_step(state, **kw)
+            step(state, **kw)
             evaluations, rounds = 1, 0
             for r in range(int(steps)):
-                trial = evaluate(state.q2, state.t2)
+                trial = at_trial()
                 evaluations += 1
-                self.lm_step(state, trial, **kw)
+                step(state, trial, **kw)
                 history[r + 1] = state.S
                 rounds = r + 1
                 if stop_when_done and bool((state.dropped >= max_dropped).all()):
                     break
             info = dict(lam=state.lam, taken=state.taken, dropped=state.dropped, evaluations=evaluations,
                         score_history=history[:rounds + 1])
-        return state.q, state.t, state.S, info
+        return (state.q, state.t, state.theta, state.S, info) if flex else (state.q, state.t, state.S, info)
+
+    # ------------------------------------------------------------------------------------------
+    # TORSION COORDINATES (rotatable bonds next to the rigid twist: mvx_apply_torsions, mvx_score_hessian_flex_batch,
+    # mvx_flex_lm_step; batch form only - views cull atoms, and an axis atom may be culled)
+    def _flex_guard(self, channels, what):
+        if self.output != "torch":
+            raise ValueError(f"{what} needs output='torch': the results are tensors on the voxelizer's device")
+        if channels is not None:
+            self._hessian_guard(channels)
+
+    def _torsion_arrays(self, offsets, axes, moves, angles=None, convert=True):
+        """(B, T, axes, moves, angles) as the library reads them: int32 and float64 tensors on this device, behind their shape
+        rules. convert=False: the rules alone."""
+        def shape(x):
+            return tuple(getattr(x, "shape", ()))
+
+        off = np.asarray(offsets, dtype=np.int64)
+        B, N = off.shape[0] - 1, int(off[-1]) if off.shape[0] else 0
+        assert len(shape(axes)) == 3 and shape(axes)[0] == B and shape(axes)[2] == 2, (
+            f"axes does not match dimension: {shape(axes)} vs {(B, 'T', 2)}")
+        T = int(shape(axes)[1])
+        assert T <= 32, f"at most 32 torsions per molecule: {T}"
+        assert shape(moves) == (N,), f"moves does not match dimension: {shape(moves)} vs {(N,)}"
+        assert angles is None or shape(angles) == (B, T), f"angles does not match dimension: {shape(angles)} vs {(B, T)}"
+        if not convert:
+            return B, T, None, None, None
+
+        def dev(x, dt):
+            x = x.detach() if _is_torch(x) else torch.from_numpy(np.array(x))  # (a copy: the caller's array may be read-only)
+            return x.to(device=self.device, dtype=dt).contiguous()
+
+        return B, T, dev(axes, torch.int32), dev(moves, torch.int32), None if angles is None else dev(angles, torch.float64)
+
+    def apply_torsions(self, coords, offsets, axes, moves, angles):
+        """The conformers C(theta) of B molecules stored back to back, on the device (mvx_apply_torsions): for k = 0 .. T-1 in
+        order the atoms with bit k of `moves` set are turned by angles[b, k] about the current axis from atom axes[b, k, 0] to
+        atom axes[b, k, 1] (local indices), through the latter. coords (N, 3); offsets (B + 1,); axes (B, T, 2) int32, padded
+        with -1; moves (N,) int32; angles (B, T) radians. Applying angles and then more angles to the result is the same as
+        applying their sum. An angle of exactly 0 and an inert torsion (padding, an index outside the molecule, coincident
+        axis atoms) turn nothing. Returns the new coordinates (N, 3), float64 on this device; outside autograd. The tree rules
+        are not checked here: check_torsions."""
+        self._flex_guard(None, "apply_torsions")
+        assert len(getattr(coords, "shape", ())) == 2 and coords.shape[1] == 3, "coords should be (N, 3)"
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        assert off[0] == 0 and off[-1] == coords.shape[0], "offsets must span coords"
+        B, T, ax, mv, th = self._torsion_arrays(off, axes, moves, angles)
+        with torch.no_grad():
+            c = self._device_coords(coords).to(torch.float64).contiguous()
+            out = torch.empty_like(c)
+            _lib.check(self._lib.mvx_apply_torsions(self._handle, self._ptr(c), off.ctypes.data, B, T, self._ptr(ax), self._ptr(mv),
+                                                    self._ptr(th), self._ptr(out), self._stream()))
+        return out
+
+    def score_hessian_flex_batch(self, coords, offsets, centers, channels, radii, field, axes, moves, num_channels=None, pivots=None,
+                                 per_atom=False):
+        """score_hessian_batch in the coordinates x = (tau, omega, theta_0 .. theta_{T-1}), n = 6 + T: torsion angles about
+        rotatable bonds next to the rigid twist (mvx_score_hessian_flex_batch). coords is the conformer the angles are counted
+        from: p_n(x) = exp([omega]x) (C(theta)_n - o_b) + o_b + tau in the grid frame, C as apply_torsions.
+
+        coords ... field, num_channels, pivots: score_hessian_batch's arguments; axes (B, T, 2) int32 and moves (N,) int32 as
+        apply_torsions takes them, checked by check_torsions on host copies. Returns (scores (B,), G (B, n), H (B, n, n)),
+        float64 on this device; G[:, :6] and H[:, :6, :6] are score_hessian_batch's twist_grad and twist_hess, bit for bit;
+        H is symmetric to the bit; an inert torsion has a zero entry, row and column. With per_atom=True also (atom_grad
+        (N, 3), atom_hess (N, 6), atom_pos (N, 3)): the walk's rows and the grid-frame positions they belong to.
+        Deterministic, no atomics; plain values outside autograd. Batch form only: views cull atoms, and an axis atom may be
+        culled - repeat the cloud per pose instead. Channel-wise radii with features raise NotImplementedError."""
+        self._flex_guard(channels, "score_hessian_flex_batch / score_hessian_flex_posed_batch")
+        return self._score_hessian_flex(coords, offsets, centers, channels, radii, field, axes, moves, num_channels, pivots, per_atom)
+
+    def score_hessian_flex_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, field, axes, moves,
+                                       num_channels=None, pivots=None, per_atom=False):
+        """score_hessian_flex_batch with one explicit rigid pose per molecule (score_hessian_posed_batch's arguments, records
+        and default pivots: the translations rounded to float32)."""
+        self._flex_guard(channels, "score_hessian_flex_batch / score_hessian_flex_posed_batch")
+        self._check_pose(self._pose_count(offsets), centers, quaternions, translations)
+        return self._score_hessian_flex(coords, offsets, centers, channels, radii, field, axes, moves, num_channels, pivots, per_atom,
+                                        posed=(quaternions, translations))
+
+    def _score_hessian_flex(self, coords, offsets, centers, channels, radii, field, axes, moves, num_channels=None, pivots=None,
+                            per_atom=False, posed=None, checked=False):
+        """The call of the two flex Hessian entries, behind their guard. checked: the tree rules were asserted already (the
+        refinement loop)."""
+        if not checked:  # (the torsions' own rules first: they need neither the library nor a device)
+            self._torsion_arrays(offsets, axes, moves, convert=False)
+            check_torsions(offsets, axes, moves)
+        with torch.no_grad():  # (plain values: inputs that require grad are read as values)
+            call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, posed=posed, device=True,
+                                    check=self._hessian_rules(field, pivots))
+            _, T, ax, mv, _ = self._torsion_arrays(call.offsets, axes, moves)
+            F, stride = self._grid_operand(field, call.C, self._gdt)
+            piv = self._hessian_pivots(pivots, posed)
+            B, N, n = call.B, call.N, 6 + T
+            f64 = dict(dtype=torch.float64, device=self.device)
+            scores, G, H = torch.empty(B, **f64), torch.empty((B, n), **f64), torch.empty((B, n, n), **f64)
+            ag, ah, ap = ((torch.empty((N, 3), **f64), torch.empty((N, 6), **f64), torch.empty((N, 3), **f64)) if per_atom
+                          else (None, None, None))
+            _lib.check(self._lib.mvx_score_hessian_flex_batch(
+                *call.entry_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores), self._ptr(ag), self._ptr(ah), None,
+                None, T, self._ptr(ax), self._ptr(mv), self._ptr(G), self._ptr(H), self._ptr(ap), self._stream()))
+        return (scores, G, H, ag, ah, ap) if per_atom else (scores, G, H)
+
+    def flex_lm_step(self, state, trial=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3):
+        """lm_step for the B poses of a FlexLMState, in n = 6 + T coordinates (mvx_flex_lm_step): the same decisions, damping and
+        solve, x = solve(-H + lam I, G); an accepted trial also makes theta2 the state's theta, and the next trial is
+        (q2, t2) = apply_twist(q, t, x[:6]), theta2 = theta + x[6:]. trial: (S2, G2 (B, n), H2 (B, n, n)) evaluated at
+        (state.q2, state.t2, state.theta2), or None before the first trial. With T = 0 the values are lm_step's bits.
+        Returns state."""
+        B = int(state.q.shape[0])
+        assert _is_torch(state.theta) and state.theta.ndim == 2 and state.theta.shape[0] == B and state.theta.shape[1] <= 32, (
+            f"state.theta should be a (B, T) tensor with T <= 32")
+        T = int(state.theta.shape[1])
+        n = 6 + T
+        for name, shape, dt in (("q", (B, 4), torch.float64), ("t", (B, 3), torch.float64), ("theta", (B, T), torch.float64),
+                                ("S", (B,), torch.float64), ("G", (B, n), torch.float64), ("H", (B, n, n), torch.float64),
+                                ("lam", (B,), torch.float64), ("taken", (B,), torch.int32), ("dropped", (B,), torch.int32)):
+            x = getattr(state, name)
+            assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == dt and x.is_contiguous() and self._on_device(x), (
+                f"state.{name} should be a contiguous {dt} tensor of shape {shape} on this voxelizer's device")
+        if trial is not None:
+            assert state.q2 is not None, "a trial needs the trial pose of an earlier flex_lm_step"
+            S2, G2, H2 = trial
+            for name, x, shape in (("S2", S2, (B,)), ("G2", G2, (B, n)), ("H2", H2, (B, n, n))):
+                assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == torch.float64 and x.is_contiguous() and self._on_device(x), (
+                    f"trial {name} should be a contiguous float64 tensor of shape {shape} on this voxelizer's device")
+        else:
+            S2 = G2 = H2 = None
+        if state.q2 is None:
+            state.q2, state.t2, state.theta2 = torch.empty_like(state.q), torch.empty_like(state.t), torch.empty_like(state.theta)
+            state.x = torch.empty_like(state.G)
+        _lib.check(self._lib.mvx_flex_lm_step(
+            self._handle, B, T, 0 if trial is None else 1, float(lam_down), float(lam_up), int(max_dropped), self._ptr(state.q),
+            self._ptr(state.t), self._ptr(state.theta), self._ptr(state.S), self._ptr(state.G), self._ptr(state.H),
+            self._ptr(state.lam), self._ptr(state.taken), self._ptr(state.dropped), self._ptr(state.q2), self._ptr(state.t2),
+            self._ptr(state.theta2), self._ptr(S2), self._ptr(G2), self._ptr(H2), self._ptr(state.x), self._stream()))
+        return state
+
+    def refine_flex_posed_batch(self, coords, offsets, centers, quaternions, translations, angles, channels, radii, field, axes, moves,
+                                num_channels=None, steps=40, lam0=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3,
+                                stop_when_done=False):
+        """refine_posed_batch with rotatable bonds: B poses and their torsion angles refined together by damped Newton steps in
+        n = 6 + T coordinates. Every evaluation is apply_torsions from the caller's reference conformer `coords` with the
+        state's total angles, then score_hessian_flex_posed_batch at the trial poses; flex_lm_step decides on the device.
+        angles (B, T): the start angles, counted from `coords`; the other arguments as refine_posed_batch and
+        score_hessian_flex_posed_batch; nothing the caller passed is modified. Batch form only (views cull atoms).
+        Returns (quaternions (B, 4), translations (B, 3), angles (B, T), scores (B,), info), info as refine_posed_batch."""
+        self._flex_guard(channels, "refine_flex_posed_batch")
+        self._check_pose(self._pose_count(offsets), centers, quaternions, translations)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        self._torsion_arrays(off, axes, moves, angles, convert=False)
+        check_torsions(off, axes, moves)
+        _, _, ax, mv, _ = self._torsion_arrays(off, axes, moves)
+
+        def evaluate(q, t, theta):
+            conformer = self.apply_torsions(coords, off, ax, mv, theta)
+            return self._score_hessian_flex(conformer, off, centers, channels, radii, field, ax, mv, num_channels, None, False,
+                                            posed=(q, t), checked=True)
+
+        return self._refine(evaluate, quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done,
+                            angles=angles)
 
     # ------------------------------------------------------------------------------------------
     # SCORES OF VIEWS (many poses or boxes of one shared cloud against a field: mvx_score_views / mvx_views_reduce)
