@@ -2053,50 +2053,49 @@ int mvx_views_reduce(mvx_handle *h, const int64_t *index, const int64_t *offsets
     return release_slot(in.slot, c.stream);
 }
 
-int mvx_lm_step(mvx_handle *h, int32_t B, int32_t have_trial, double lam_down, double lam_up, int32_t max_dropped, double *q,
-                double *t, double *S, double *G, double *H, double *lam, int32_t *taken, int32_t *dropped, double *q2, double *t2,
-                const double *S2, const double *G2, const double *H2, double *xi, void *stream) {
+namespace {
+
+// The two step entries: the rules of a step record in their order, then its launch. `flex`: the whole record when `a` is the
+// base of one, else null; `after_B` and `after_state`: what the flex entry found wrong with T, behind "B must be >= 0", and with
+// its angles, behind the state pointers (null: nothing, as in check_batch).
+int run_lm_step(mvx_handle *h, const LmArgs &a, const FlexLmArgs *flex, const char *after_B, const char *after_state, void *stream) {
     // ---- what is checked before any device is touched ----
-    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
-    if (B > 0 && (!q || !t || !S || !G || !H || !lam || !taken || !dropped || !q2 || !t2))
+    if (a.B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (after_B) return fail(MVX_ERR_INVALID, after_B);
+    if (a.B > 0 && (!a.q || !a.t || !a.S || !a.G || !a.H || !a.lam || !a.taken || !a.dropped || !a.q2 || !a.t2))
         return fail(MVX_ERR_INVALID, "q, t, S, G, H, lam, taken, dropped, q2 and t2 must not be null");
-    if (B > 0 && have_trial && (!S2 || !G2 || !H2)) return fail(MVX_ERR_INVALID, "S2, G2 and H2 must not be null with have_trial");
-    if (max_dropped < 1) return fail(MVX_ERR_INVALID, "max_dropped must be >= 1");
-    if (!(lam_down > 0.0) || !(lam_up > 0.0) || !std::isfinite(lam_down) || !std::isfinite(lam_up))
+    if (after_state) return fail(MVX_ERR_INVALID, after_state);
+    if (a.B > 0 && a.have_trial && (!a.S2 || !a.G2 || !a.H2)) return fail(MVX_ERR_INVALID, "S2, G2 and H2 must not be null with have_trial");
+    if (a.max_dropped < 1) return fail(MVX_ERR_INVALID, "max_dropped must be >= 1");
+    if (!(a.lam_down > 0.0) || !(a.lam_up > 0.0) || !std::isfinite(a.lam_down) || !std::isfinite(a.lam_up))
         return fail(MVX_ERR_INVALID, "lam_down and lam_up must be finite and > 0");
     if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    if (B == 0) return MVX_OK;
+    if (a.B == 0) return MVX_OK;
 
     const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     CallScope scope(h, s);
     if (scope.rc) return scope.rc;
-    HIP_TRY(launch_lm_step({B, have_trial != 0, max_dropped, lam_down, lam_up, q, t, S, G, H, lam, taken, dropped, q2, t2, S2, G2, H2, xi}, s));
+    HIP_TRY(flex ? launch_flex_lm_step(*flex, s) : launch_lm_step(a, s));
     return MVX_OK;
+}
+
+} // namespace
+
+int mvx_lm_step(mvx_handle *h, int32_t B, int32_t have_trial, double lam_down, double lam_up, int32_t max_dropped, double *q,
+                double *t, double *S, double *G, double *H, double *lam, int32_t *taken, int32_t *dropped, double *q2, double *t2,
+                const double *S2, const double *G2, const double *H2, double *xi, void *stream) {
+    const LmArgs a{B, have_trial != 0, max_dropped, lam_down, lam_up, q, t, S, G, H, lam, taken, dropped, q2, t2, S2, G2, H2, xi};
+    return run_lm_step(h, a, nullptr, nullptr, nullptr, stream);
 }
 
 int mvx_flex_lm_step(mvx_handle *h, int32_t B, int32_t T, int32_t have_trial, double lam_down, double lam_up, int32_t max_dropped,
                      double *q, double *t, double *theta, double *S, double *G, double *H, double *lam, int32_t *taken,
                      int32_t *dropped, double *q2, double *t2, double *theta2, const double *S2, const double *G2, const double *H2,
                      double *x, void *stream) {
-    // ---- what is checked before any device is touched: mvx_lm_step's rules, T behind B ----
-    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
-    if (T < 0 || T > FLEX_MAX_T) return fail(MVX_ERR_INVALID, "T must be 0 ... 32");
-    if (B > 0 && (!q || !t || !S || !G || !H || !lam || !taken || !dropped || !q2 || !t2))
-        return fail(MVX_ERR_INVALID, "q, t, S, G, H, lam, taken, dropped, q2 and t2 must not be null");
-    if (B > 0 && T > 0 && (!theta || !theta2)) return fail(MVX_ERR_INVALID, "theta and theta2 must not be null with T > 0");
-    if (B > 0 && have_trial && (!S2 || !G2 || !H2)) return fail(MVX_ERR_INVALID, "S2, G2 and H2 must not be null with have_trial");
-    if (max_dropped < 1) return fail(MVX_ERR_INVALID, "max_dropped must be >= 1");
-    if (!(lam_down > 0.0) || !(lam_up > 0.0) || !std::isfinite(lam_down) || !std::isfinite(lam_up))
-        return fail(MVX_ERR_INVALID, "lam_down and lam_up must be finite and > 0");
-    if (!h) return fail(MVX_ERR_INVALID, "null handle");
-    if (B == 0) return MVX_OK;
-
-    const hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    CallScope scope(h, s);
-    if (scope.rc) return scope.rc;
-    HIP_TRY(launch_flex_lm_step({B, T, have_trial != 0, max_dropped, lam_down, lam_up, q, t, theta, S, G, H, lam, taken, dropped, q2, t2,
-                                 theta2, S2, G2, H2, x}, s));
-    return MVX_OK;
+    const FlexLmArgs a{{B, have_trial != 0, max_dropped, lam_down, lam_up, q, t, S, G, H, lam, taken, dropped, q2, t2, S2, G2, H2, x},
+                       theta, theta2, T};
+    return run_lm_step(h, a, &a, T < 0 || T > FLEX_MAX_T ? "T must be 0 ... 32" : nullptr,
+                       B > 0 && T > 0 && (!theta || !theta2) ? "theta and theta2 must not be null with T > 0" : nullptr, stream);
 }
 
 int mvx_apply_torsions(mvx_handle *h, const double *coords, const int64_t *offsets, int32_t B, int32_t T, const int32_t *axes,

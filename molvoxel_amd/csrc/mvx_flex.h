@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "mvx_internal.h"
+#include "mvx_lm.h"
 
 namespace mvx {
 
@@ -35,15 +36,11 @@ struct FlexArgs {
 };
 hipError_t launch_flex(const FlexArgs &a, hipStream_t s);
 
-// mvx_flex_lm_step: LmArgs of mvx_lm.h for n = 6 + T coordinates, with the torsion angles next to the pose
-struct FlexLmArgs {
-    int32_t B, T, have_trial, max_dropped;
-    double lam_down, lam_up;
-    double *q, *t, *theta, *S, *G, *H, *lam; // (B, 4) (B, 3) (B, T) (B,) (B, n) (B, n, n) (B,)
-    int32_t *taken, *dropped;                // (B,) (B,)
-    double *q2, *t2, *theta2;                // (B, 4) (B, 3) (B, T): the trial, read on an accepted trial, then written
-    const double *S2, *G2, *H2;              // (B,) (B, n) (B, n, n)
-    double *x;                               // (B, n) or null
+// mvx_flex_lm_step: LmArgs (mvx_lm.h) for n = 6 + T coordinates - G, G2 and xi (B, n), H and H2 (B, n, n) - with the torsion angles next
+// to the pose
+struct FlexLmArgs : LmArgs {
+    double *theta, *theta2; // (B, T): the state's angles, and the trial's, read on an accepted trial, then written
+    int32_t T;              // (behind the pointers: in front of them flex_lm_step_kernel needs one more scalar load)
 };
 // One wave per pose: the decision on the trial, then the damped Newton step in n dimensions and the trial it leads to.
 hipError_t launch_flex_lm_step(const FlexLmArgs &a, hipStream_t s);

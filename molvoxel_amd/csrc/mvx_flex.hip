@@ -8,23 +8,26 @@
 //   F_k = sum g_n   N_k = sum r_n x g_n   X_k = sum J_n^T H_n J_n   K_k = sum r_n g_n^T      over the atoms n of set k
 //   c_k = tau_k x F_k + (K_k - tr(K_k) I) u_k
 //   G[6 + k] = s_k . (F_k, N_k)      H[:6, 6 + k] = X_k s_k + (0, c_k)      H[6 + k, 6 + l] = s_k^T X_l s_l + u_k . c_l  (k <= l related)
-// and 0 for unrelated pairs. G[:6] and H[:6, :6] are twist_reduce_kernel's values, copied.
+// and 0 for unrelated pairs. G[:6] and H[:6, :6] are the rigid twist sums (launch_twist_reduce), copied. One atom's terms of
+// F, N, X and K, the rule for an atom without rows, the decision on a trial and the twist onto the pose are mvx_newton_device.h's.
 //
 //   torsion_apply_kernel  one workgroup per molecule; the positions are worked on in the output array. Per torsion in order: every
 //                         thread reads the current axis atoms, a barrier, the atoms of the set are turned (Rodrigues), a barrier.
 //                         An angle of exactly 0 and an inert torsion turn nothing: those atoms keep their bits.
-//   flex_subset_kernel    grid (B, T), one workgroup (4 waves) per (torsion, molecule) in the shape of twist_reduce_kernel: wave w
-//                         takes the chunks w, w + 4, ... of 64 atoms in order, 36 float64 lane partials, a fixed butterfly per
-//                         wave, the four waves through sum4. An atom whose g and H rows are all zero is skipped.
+//   flex_subset_kernel    grid (B, T), one workgroup (4 waves) per (torsion, molecule): wave w takes the chunks w, w + 4, ... of 64
+//                         atoms in order and keeps the atoms of the set, 36 float64 lane partials (the twist sum with K kept
+//                         apart), a fixed butterfly per wave, the four waves through sum4, one thread per value writes.
 //   flex_assemble_kernel  one workgroup per molecule: thread l forms s_l, X_l s_l, c_l and G[6 + l]; then every entry of G and H
 //                         is written once, entry (i, j) and (j, i) from the same expression: H is symmetric to the bit.
-//   flex_lm_step_kernel   lm_step_kernel's state machine for n = 6 + T, one wave per pose, the n x (n + 1) system in LDS.
+//   flex_lm_step_kernel   the damped Newton step for n = 6 + T, one wave per pose: every lane decides on the trial alike and lane
+//                         0 writes; (-H + lam I) x = G by Gaussian elimination with partial pivoting on the n x (n + 1) system
+//                         in LDS, one row per lane; the twist x[:6] onto the pose, theta2 = theta + x[6:], lane j holding angle j.
 //
 // A torsion is inert when an axis index is outside [0, N_b) (padding: -1), or the axis has no or no finite length: zero gradient
 // entry, zero Hessian row and column; no axis index is used before it is checked. No atomics, no scratch
 // (tests/test_flex_host.py pins it), no host read; a molecule's values do not depend on its batch.
 #include "mvx_flex.h"
-#include "mvx_grad_device.h"
+#include "mvx_newton_device.h"
 
 #include <math.h>
 
@@ -32,10 +35,7 @@ namespace mvx {
 
 namespace {
 
-constexpr int FLEX_WAVES = 4;
-// where entry (i, j), i <= j, of the 6x6 X sits among the 36 (twist_reduce_kernel's order, behind F and N)
-__host__ __device__ constexpr int x_slot(int i, int j) { return 6 + 6 * i - i * (i - 1) / 2 + (j - i); }
-constexpr int K_SLOT = 27;
+static_assert(FLEX_SUBSET == TWIST_K_SLOT + 9, "F, N, the upper triangle of X, K");
 
 // The unit axis u from pa to pb, or false: no length, or none that is finite (then pa and pb are not both finite).
 __device__ __forceinline__ bool unit_axis(const double (&pa)[3], const double (&pb)[3], double (&u)[3]) {
@@ -109,8 +109,8 @@ __global__ void __launch_bounds__(256) torsion_apply_kernel(const double *coords
     }
 }
 
-__global__ void __launch_bounds__(64 * FLEX_WAVES) flex_subset_kernel(const FlexArgs a) {
-    __shared__ double part[FLEX_WAVES][FLEX_SUBSET];
+__global__ void __launch_bounds__(64 * TWIST_WAVES) flex_subset_kernel(const FlexArgs a) {
+    __shared__ double part[TWIST_WAVES][FLEX_SUBSET];
     const int b = (int)blockIdx.x, k = (int)blockIdx.y;
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
     const int64_t a0 = a.offsets[b], a1 = a.offsets[b + 1];
@@ -124,52 +124,16 @@ __global__ void __launch_bounds__(64 * FLEX_WAVES) flex_subset_kernel(const Flex
     double acc[FLEX_SUBSET];
 #pragma unroll
     for (int i = 0; i < FLEX_SUBSET; ++i) acc[i] = 0.0;
-    for (int64_t n = a0 + 64 * wave + lane; n < a1; n += 64 * FLEX_WAVES) {
+    for (int64_t n = a0 + 64 * wave + lane; n < a1; n += 64 * TWIST_WAVES) {
         if (!(((uint32_t)a.moves[n] >> k) & 1u)) continue;
         const double g[3] = {a.atom_grad[3 * n], a.atom_grad[3 * n + 1], a.atom_grad[3 * n + 2]};
-        const double hxx = a.atom_hess[6 * n], hxy = a.atom_hess[6 * n + 1], hxz = a.atom_hess[6 * n + 2];
-        const double hyy = a.atom_hess[6 * n + 3], hyz = a.atom_hess[6 * n + 4], hzz = a.atom_hess[6 * n + 5];
-        // (as twist_reduce_kernel: an atom that reaches no voxel has zero rows, and its position may be NaN)
-        if (g[0] == 0.0 && g[1] == 0.0 && g[2] == 0.0 && hxx == 0.0 && hxy == 0.0 && hxz == 0.0 && hyy == 0.0 && hyz == 0.0 && hzz == 0.0)
-            continue;
+        const double h[6] = {a.atom_hess[6 * n],     a.atom_hess[6 * n + 1], a.atom_hess[6 * n + 2],
+                             a.atom_hess[6 * n + 3], a.atom_hess[6 * n + 4], a.atom_hess[6 * n + 5]};
+        if (twist_rows_zero(g, h)) continue;
         const double r[3] = {a.rec[n].px - o0, a.rec[n].py - o1, a.rec[n].pz - o2};
-        const double H[3][3] = {{hxx, hxy, hxz}, {hxy, hyy, hyz}, {hxz, hyz, hzz}};
-        const double A[3][3] = {{0.0, r[2], -r[1]}, {-r[2], 0.0, r[0]}, {r[1], -r[0], 0.0}}; // -[r]x: J = [I | A]
-        acc[0] += g[0];
-        acc[1] += g[1];
-        acc[2] += g[2];
-        acc[3] += r[1] * g[2] - r[2] * g[1];
-        acc[4] += r[2] * g[0] - r[0] * g[2];
-        acc[5] += r[0] * g[1] - r[1] * g[0];
-        double HAm[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) HAm[i][j] = (H[i][0] * A[0][j] + H[i][1] * A[1][j]) + H[i][2] * A[2][j];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = i; j < 3; ++j) acc[x_slot(i, j)] += H[i][j];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[x_slot(i, 3 + j)] += HAm[i][j];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = i; j < 3; ++j)
-                acc[x_slot(3 + i, 3 + j)] += (A[0][i] * HAm[0][j] + A[1][i] * HAm[1][j]) + A[2][i] * HAm[2][j];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[K_SLOT + 3 * i + j] += r[i] * g[j];
+        twist_accumulate<true>(g, h, r, acc);
     }
-#pragma unroll
-    for (int i = 0; i < FLEX_SUBSET; ++i) {
-        const double v = wave_sum(acc[i]);
-        if (lane == 0) part[wave][i] = v;
-    }
-    __syncthreads();
+    twist_wave_partials(acc, part, lane, wave);
     if (threadIdx.x < FLEX_SUBSET) {
         const int i = (int)threadIdx.x;
         out[i] = sum4(part[0][i], part[1][i], part[2][i], part[3][i]);
@@ -207,12 +171,12 @@ __global__ void __launch_bounds__(256) flex_assemble_kernel(const FlexArgs a) {
 #pragma unroll
             for (int i = 0; i < 6; ++i)
 #pragma unroll
-                for (int j = i; j < 6; ++j) X[i][j] = X[j][i] = v[x_slot(i, j)];
+                for (int j = i; j < 6; ++j) X[i][j] = X[j][i] = v[twist_slot(i, j)];
             double K[3][3];
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
-                for (int j = 0; j < 3; ++j) K[i][j] = v[K_SLOT + 3 * i + j];
+                for (int j = 0; j < 3; ++j) K[i][j] = v[TWIST_K_SLOT + 3 * i + j];
             const double trK = (K[0][0] + K[1][1]) + K[2][2];
             // c_l = tau_l x F_l + (K_l - tr(K_l) I) u_l
             const double tF[3] = {s[1] * F[2] - s[2] * F[1], s[2] * F[0] - s[0] * F[2], s[0] * F[1] - s[1] * F[0]};
@@ -279,19 +243,9 @@ __global__ void __launch_bounds__(64) flex_lm_step_kernel(const FlexLmArgs a) {
     int32_t dropped = a.dropped[i];
     // ---- 1. the decision on the trial (every lane decides alike, lane 0 writes) ----
     bool accept = false;
-    if (a.have_trial && dropped < a.max_dropped) {
-        const double S2 = a.S2[i];
-        accept = S2 > S; // (a NaN compares false: a non-finite trial is dropped)
-        int32_t taken = a.taken[i];
-        if (accept) {
-            S = S2;
-            lam *= a.lam_down;
-            dropped = 0;
-            taken += 1;
-        } else {
-            lam *= a.lam_up;
-            dropped += 1;
-        }
+    if (lm_has_trial(a, dropped)) {
+        accept = lm_decide(a, a.S2[i], S, lam, dropped, [] {}); // (nothing is written in the accepting branch: lane 0, below)
+        const int32_t taken = a.taken[i] + 1; // (read by every lane, written on an accepted trial)
         __syncthreads(); // every lane has read the state before lane 0 changes it
         if (lane == 0) {
             if (accept) {
@@ -382,24 +336,13 @@ __global__ void __launch_bounds__(64) flex_lm_step_kernel(const FlexLmArgs a) {
             ok = ok && isfinite(s);
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ok = ok && isfinite(q[k]);
+        for (int k = 0; k < 4; ++k) ok = ok && isfinite(q[k]); // (spelled out: see mvx_newton_device.h)
 #pragma unroll
         for (int k = 0; k < 3; ++k) ok = ok && isfinite(t[k]);
         ok = ok && isfinite(lam);
         ok = ok && __all(isfinite(th) ? 1 : 0);
         if (ok) {
-            const double wx = xs[3], wy = xs[4], wz = xs[5];
-            const double half = 0.5 * sqrt(wx * wx + wy * wy + wz * wz);
-            if (half != 0.0) { // (w = 0: u = (1, 0, 0, 0), the quaternion itself)
-                const double u0 = cos(half), f = 0.5 * (sin(half) / half);
-                const double u1 = f * wx, u2 = f * wy, u3 = f * wz;
-                q2[0] = u0 * q[0] - u1 * q[1] - u2 * q[2] - u3 * q[3];
-                q2[1] = u0 * q[1] + u1 * q[0] + u2 * q[3] - u3 * q[2];
-                q2[2] = u0 * q[2] - u1 * q[3] + u2 * q[0] + u3 * q[1];
-                q2[3] = u0 * q[3] + u1 * q[2] - u2 * q[1] + u3 * q[0];
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) t2[k] = t[k] + xs[k];
+            apply_twist(q, t, xs, q2, t2);
             if (lane < T) th2 = th + xs[6 + lane];
 #pragma unroll
             for (int k = 0; k < 4; ++k) ok = ok && isfinite(q2[k]);
@@ -423,8 +366,8 @@ __global__ void __launch_bounds__(64) flex_lm_step_kernel(const FlexLmArgs a) {
         for (int k = 0; k < 3; ++k) a.t2[3 * i + k] = t2[k];
     }
     if (lane < T) a.theta2[(size_t)T * i + lane] = th2;
-    if (a.x) {
-        for (int r = lane; r < n; r += 64) a.x[(size_t)n * i + r] = step ? xs[r] : 0.0;
+    if (a.xi) {
+        for (int r = lane; r < n; r += 64) a.xi[(size_t)n * i + r] = step ? xs[r] : 0.0;
     }
 }
 
@@ -438,7 +381,7 @@ hipError_t launch_torsion_apply(const double *coords, const int64_t *offsets, in
 hipError_t launch_flex(const FlexArgs &a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
     if (a.T > 0) {
-        hipLaunchKernelGGL(flex_subset_kernel, dim3((unsigned)a.B, (unsigned)a.T), dim3(64 * FLEX_WAVES), 0, s, a);
+        hipLaunchKernelGGL(flex_subset_kernel, dim3((unsigned)a.B, (unsigned)a.T), dim3(64 * TWIST_WAVES), 0, s, a);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(flex_assemble_kernel, dim3((unsigned)a.B), dim3(256), 0, s, a);

@@ -1,7 +1,8 @@
 // mvx_grad_device.h - device helpers and the walk launch of the backward family, included by its eight kernel files:
 // mvx_grad.hip, mvx_grad_radii.hip, mvx_score.hip and mvx_moments_grad.hip (the walks of mvx_grad_body.inc, launch_walk), mvx_hess.hip
 // (a walk of its own through launch_walk, wave sums, sum4), mvx_grad_radii.hip and mvx_grad_density.hip (the reductions over a call:
-// block_sum4, sum4), mvx_pose.hip and mvx_views_reduce.hip (wave sums, sum4).
+// block_sum4, sum4), mvx_pose.hip and mvx_views_reduce.hip (wave sums, sum4); and by mvx_newton_device.h (wave sums), through
+// which mvx_flex.hip and mvx_lm.hip get it.
 #pragma once
 #include "mvx_device.h"
 #include "mvx_grad.h"

@@ -15,9 +15,11 @@
 //   twist_reduce_kernel  one workgroup (4 waves) per molecule, in the shape of pose_grad_kernel: wave w takes the chunks w, w + 4,
 //                        ... of 64 atoms in order, each lane keeps 6 + 21 double partials (G and the upper triangle of Hxi); a
 //                        fixed butterfly per wave, the four waves in a fixed order through LDS; thread 0 writes G and the full
-//                        symmetric Hxi. An atom whose g and H rows are all zero is skipped (its position may be NaN).
+//                        symmetric Hxi. One atom's terms, the rule for an atom without rows and the hand-over of the partials
+//                        are mvx_newton_device.h's, with the K term folded into the angular block.
 #include "mvx_grad_device.h"
 #include "mvx_hess.h"
+#include "mvx_newton_device.h"
 
 namespace mvx {
 
@@ -151,11 +153,6 @@ __global__ void __launch_bounds__(256) score_hess_kernel(GradArgs A, HessArgs HA
     H[5] = e + kq(Q[5]);
 }
 
-constexpr int TWIST_WAVES = 4;
-constexpr int TWIST_VALUES = 6 + 21; // G, then the upper triangle of Hxi row by row
-// where entry (i, j), i <= j, of the 6x6 sits among them
-__host__ __device__ constexpr int twist_slot(int i, int j) { return 6 + 6 * i - i * (i - 1) / 2 + (j - i); }
-
 __global__ void __launch_bounds__(64 * TWIST_WAVES) twist_reduce_kernel(const AtomRec *__restrict__ rec, const double *__restrict__ atom_grad,
                                                                         const double *__restrict__ atom_hess,
                                                                         const int64_t *__restrict__ offsets,
@@ -171,55 +168,13 @@ __global__ void __launch_bounds__(64 * TWIST_WAVES) twist_reduce_kernel(const At
     for (int i = 0; i < TWIST_VALUES; ++i) acc[i] = 0.0;
     for (int64_t a = a0 + 64 * wave + lane; a < a1; a += 64 * TWIST_WAVES) {
         const double g[3] = {atom_grad[3 * a], atom_grad[3 * a + 1], atom_grad[3 * a + 2]};
-        const double hxx = atom_hess[6 * a], hxy = atom_hess[6 * a + 1], hxz = atom_hess[6 * a + 2];
-        const double hyy = atom_hess[6 * a + 3], hyz = atom_hess[6 * a + 4], hzz = atom_hess[6 * a + 5];
-        // an atom that reaches no voxel has zero rows, and its position may be NaN or infinite: 0 * r would poison the sums.
-        // For a finite position the skipped terms are +-0 added to sums that start at +0: no bit changes.
-        if (g[0] == 0.0 && g[1] == 0.0 && g[2] == 0.0 && hxx == 0.0 && hxy == 0.0 && hxz == 0.0 && hyy == 0.0 && hyz == 0.0 && hzz == 0.0)
-            continue;
-        const double r0 = rec[a].px - o0, r1 = rec[a].py - o1, r2 = rec[a].pz - o2;
-        const double H[3][3] = {{hxx, hxy, hxz}, {hxy, hyy, hyz}, {hxz, hyz, hzz}};
-        // J = [ I | A ], A = -[r]x: its columns
-        const double A[3][3] = {{0.0, r2, -r1}, {-r2, 0.0, r0}, {r1, -r0, 0.0}}; // A[i][j]: row i, column j
-        // G = (sum g, sum r x g) = J^T g
-        acc[0] += g[0];
-        acc[1] += g[1];
-        acc[2] += g[2];
-        acc[3] += r1 * g[2] - r2 * g[1];
-        acc[4] += r2 * g[0] - r0 * g[2];
-        acc[5] += r0 * g[1] - r1 * g[0];
-        // HA = H A (3x3), W = A^T H A (symmetric)
-        double HAm[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) HAm[i][j] = (H[i][0] * A[0][j] + H[i][1] * A[1][j]) + H[i][2] * A[2][j];
-        const double gr = (g[0] * r0 + g[1] * r1) + g[2] * r2;
-        const double r[3] = {r0, r1, r2};
-        // the upper triangle of the 6x6, row by row: rows 0..2 hold [H | H A], rows 3..5 hold [. | W + K]
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = i; j < 3; ++j) acc[twist_slot(i, j)] += H[i][j];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[twist_slot(i, 3 + j)] += HAm[i][j];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = i; j < 3; ++j) {
-                const double w = (A[0][i] * HAm[0][j] + A[1][i] * HAm[1][j]) + A[2][i] * HAm[2][j];
-                const double kk = 0.5 * (g[i] * r[j] + r[i] * g[j]) - (i == j ? gr : 0.0);
-                acc[twist_slot(3 + i, 3 + j)] += w + kk;
-            }
-        }
+        const double h[6] = {atom_hess[6 * a],     atom_hess[6 * a + 1], atom_hess[6 * a + 2],
+                             atom_hess[6 * a + 3], atom_hess[6 * a + 4], atom_hess[6 * a + 5]};
+        if (twist_rows_zero(g, h)) continue;
+        const double r[3] = {rec[a].px - o0, rec[a].py - o1, rec[a].pz - o2};
+        twist_accumulate<false>(g, h, r, acc);
     }
-#pragma unroll
-    for (int i = 0; i < TWIST_VALUES; ++i) {
-        const double v = wave_sum(acc[i]);
-        if (lane == 0) part[wave][i] = v;
-    }
-    __syncthreads();
+    twist_wave_partials(acc, part, lane, wave);
     if (threadIdx.x != 0) return;
     double t[TWIST_VALUES]; // (no atoms: exact zeros)
 #pragma unroll

@@ -6,7 +6,8 @@
 
 namespace mvx {
 
-// every array on the device; the current state is read and written, the trial's S2, G2 and H2 are read with have_trial only
+// every array on the device; the current state is read and written, the trial's S2, G2 and H2 are read with have_trial only.
+// The shapes are the rigid step's, n = 6; FlexLmArgs (mvx_flex.h) extends the record for n = 6 + T.
 struct LmArgs {
     int32_t B, have_trial, max_dropped;
     double lam_down, lam_up;
@@ -14,7 +15,7 @@ struct LmArgs {
     int32_t *taken, *dropped;        // (B,) (B,)
     double *q2, *t2;                 // (B, 4) (B, 3): the trial pose, read on an accepted trial, then written
     const double *S2, *G2, *H2;      // (B,) (B, 6) (B, 36)
-    double *xi;                      // (B, 6) or null
+    double *xi;                      // (B, 6) or null: the step
 };
 
 // One thread per pose, blocks of 64: the decision on the trial, then the damped Newton step and the pose it leads to.

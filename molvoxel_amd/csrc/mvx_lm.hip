@@ -3,18 +3,20 @@
 // refinement - the accept / drop decision on the last trial, the damping update, the 6x6 solve and the twist onto the pose.
 //
 //   lm_step_kernel  one thread per pose, blocks of 64, float64 throughout. Per pose:
-//                   1. with a trial and dropped < max_dropped: S2 > S (false for a NaN) makes the trial the state - q, t, S, G, H
-//                      copied bit for bit, lam *= lam_down, taken += 1, dropped = 0 -, otherwise lam *= lam_up, dropped += 1
+//                   1. with a trial and dropped < max_dropped: the decision (lm_decide, mvx_newton_device.h); an accepted trial
+//                      becomes the state - q, t, S, G, H copied bit for bit, taken += 1
 //                   2. dropped >= max_dropped: the pose is finished; q2 = q, t2 = t, xi = 0 and nothing else is written
 //                   3. otherwise (-H + lam I) xi = G by Gaussian elimination with partial pivoting (the matrix may be indefinite
-//                      while lam is small), and (q2, t2) = apply_twist(q, t, xi): u = (cos(|w|/2), sin(|w|/2) w/|w|), q2 = u (x) q,
-//                      t2 = t + tau; w = 0 gives q2 = q exactly. A zero pivot, a non-finite xi, q, t, lam, q2 or t2: xi = 0 and
-//                      (q2, t2) = (q, t) - the next call sees S2 == S, drops the step and raises lam.
+//                      while lam is small), and (q2, t2) = apply_twist(q, t, xi) (mvx_newton_device.h). A zero pivot, a
+//                      non-finite xi, q, t, lam, q2 or t2: xi = 0 and (q2, t2) = (q, t) - the next call sees S2 == S, drops the
+//                      step and raises lam.
+// The decision rule and the twist are shared with the step in torsion coordinates (mvx_flex.hip); the solve is this kernel's own.
 //
 // The 6x7 system lives in registers: every loop over it is unrolled with compile-time indices, the pivot row is exchanged by
 // selects and never used as an index, so nothing goes to scratch (tests/test_lm_host.py pins scratch 0 and no spills). No
 // atomics, no LDS, no host read; a pose's values do not depend on its batch.
 #include "mvx_lm.h"
+#include "mvx_newton_device.h"
 
 #include <math.h>
 
@@ -32,19 +34,11 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_step_kernel(const LmArgs a) {
     int32_t dropped = a.dropped[i];
     // ---- 1. the decision on the trial ----
     bool accept = false;
-    if (a.have_trial && dropped < a.max_dropped) {
-        const double S2 = a.S2[i];
-        accept = S2 > S; // (a NaN compares false: a non-finite trial is dropped)
-        if (accept) {
-            S = S2;
-            lam *= a.lam_down;
-            dropped = 0;
+    if (lm_has_trial(a, dropped)) {
+        accept = lm_decide(a, a.S2[i], S, lam, dropped, [&] {
             a.S[i] = S;
             a.taken[i] += 1;
-        } else {
-            lam *= a.lam_up;
-            dropped += 1;
-        }
+        });
         a.lam[i] = lam;
         a.dropped[i] = dropped;
     }
@@ -128,23 +122,12 @@ __global__ void __launch_bounds__(LM_BLOCK) lm_step_kernel(const LmArgs a) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) ok = ok && isfinite(x[k]);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) ok = ok && isfinite(q[k]);
+        for (int k = 0; k < 4; ++k) ok = ok && isfinite(q[k]); // (spelled out: see mvx_newton_device.h)
 #pragma unroll
         for (int k = 0; k < 3; ++k) ok = ok && isfinite(t[k]);
         ok = ok && isfinite(lam);
         if (ok) {
-            const double wx = x[3], wy = x[4], wz = x[5];
-            const double half = 0.5 * sqrt(wx * wx + wy * wy + wz * wz);
-            if (half != 0.0) { // (w = 0: u = (1, 0, 0, 0), the quaternion itself)
-                const double u0 = cos(half), f = 0.5 * (sin(half) / half);
-                const double u1 = f * wx, u2 = f * wy, u3 = f * wz;
-                q2[0] = u0 * q[0] - u1 * q[1] - u2 * q[2] - u3 * q[3];
-                q2[1] = u0 * q[1] + u1 * q[0] + u2 * q[3] - u3 * q[2];
-                q2[2] = u0 * q[2] - u1 * q[3] + u2 * q[0] + u3 * q[1];
-                q2[3] = u0 * q[3] + u1 * q[2] - u2 * q[1] + u3 * q[0];
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) t2[k] = t[k] + x[k];
+            apply_twist(q, t, x, q2, t2);
 #pragma unroll
             for (int k = 0; k < 4; ++k) ok = ok && isfinite(q2[k]);
 #pragma unroll

@@ -138,35 +138,53 @@ class _Call:
                 vox._radii_type_code(), self.N, self.C, C.addressof(self.xforms), self.B)
 
 
-class LMState:
+class _StepState:
+    """What LMState and FlexLMState share: the tensors of both, one constructor body, and what the step body
+    (Voxelizer._lm_step) and the refinement loop read off a state class - POINT: the coordinates in the library's order,
+    TRIAL: the trial point they lead to, STEP: the step's name, ENTRY, METHOD: the library entry and the method that serve it."""
+
+    __slots__ = ("q", "t", "S", "G", "H", "lam", "taken", "dropped", "q2", "t2")
+
+    def _fill(self, point, S, G, H, lam, taken, dropped):
+        q, B = point[0], int(point[0].shape[0])
+        for name, x in zip(self.POINT, point):
+            setattr(self, name, x)
+        self.S, self.G, self.H, self.lam = S, G, H, lam
+        self.taken = torch.zeros(B, dtype=torch.int32, device=q.device) if taken is None else taken
+        self.dropped = torch.zeros(B, dtype=torch.int32, device=q.device) if dropped is None else dropped
+        for name in self.TRIAL + (self.STEP,):
+            setattr(self, name, None)
+
+    def point(self):  # the accepted coordinates: what a refinement returns in front of the scores
+        return tuple(getattr(self, name) for name in self.POINT)
+
+    def trial(self):  # the trial point: where the next evaluation is made
+        return tuple(getattr(self, name) for name in self.TRIAL)
+
+
+class LMState(_StepState):
     """The state lm_step works on, B poses as tensors on the voxelizer's device: q (B, 4), t (B, 3): the poses; S (B,), G (B, 6),
     H (B, 6, 6): their scores, twist gradients and twist Hessians (float64, contiguous); lam (B,): the damping; taken, dropped
     (B,) int32: accepted steps, and steps dropped in a row (zeros when not given). q2, t2, xi: the trial poses and their twists,
     made by the first lm_step and reused."""
 
-    __slots__ = ("q", "t", "S", "G", "H", "lam", "taken", "dropped", "q2", "t2", "xi")
+    __slots__ = ("xi",)
+    POINT, TRIAL, STEP, ENTRY, METHOD = ("q", "t"), ("q2", "t2"), "xi", "mvx_lm_step", "lm_step"
 
     def __init__(self, q, t, S, G, H, lam, taken=None, dropped=None):
-        B = int(q.shape[0])
-        self.q, self.t, self.S, self.G, self.H, self.lam = q, t, S, G, H, lam
-        self.taken = torch.zeros(B, dtype=torch.int32, device=q.device) if taken is None else taken
-        self.dropped = torch.zeros(B, dtype=torch.int32, device=q.device) if dropped is None else dropped
-        self.q2 = self.t2 = self.xi = None
+        self._fill((q, t), S, G, H, lam, taken, dropped)
 
 
-class FlexLMState:
+class FlexLMState(_StepState):
     """The state flex_lm_step works on: LMState's tensors for n = 6 + T coordinates - G (B, n), H (B, n, n) - with the torsion
     angles theta (B, T) next to the pose. q2, t2, theta2, x (B, n): the trial and its step, made by the first flex_lm_step and
     reused."""
 
-    __slots__ = ("q", "t", "theta", "S", "G", "H", "lam", "taken", "dropped", "q2", "t2", "theta2", "x")
+    __slots__ = ("theta", "theta2", "x")
+    POINT, TRIAL, STEP, ENTRY, METHOD = ("q", "t", "theta"), ("q2", "t2", "theta2"), "x", "mvx_flex_lm_step", "flex_lm_step"
 
     def __init__(self, q, t, theta, S, G, H, lam, taken=None, dropped=None):
-        B = int(q.shape[0])
-        self.q, self.t, self.theta, self.S, self.G, self.H, self.lam = q, t, theta, S, G, H, lam
-        self.taken = torch.zeros(B, dtype=torch.int32, device=q.device) if taken is None else taken
-        self.dropped = torch.zeros(B, dtype=torch.int32, device=q.device) if dropped is None else dropped
-        self.q2 = self.t2 = self.theta2 = self.x = None
+        self._fill((q, t, theta), S, G, H, lam, taken, dropped)
 
 
 def _host_array(x, dtype):
@@ -1622,22 +1640,29 @@ class Voxelizer(BaseVoxelizer):
                                     check=self._hessian_rules(field, pivots))
             return self._score_hessian(call, field, pivots, posed, per_atom)
 
-    def _score_hessian(self, call, field, pivots, posed, per_atom):
+    def _score_hessian(self, call, field, pivots, posed, per_atom, torsions=None):
         """The body of the Hessian entries, under no_grad: one mvx_score_hessian_batch or mvx_score_hessian_views call. Returns
         (scores, twist_grad, twist_hess), with per_atom also (atom_grad, atom_hess): one row per atom of a batch, per
-        (view, atom) of the selection of a views call."""
+        (view, atom) of the selection of a views call. torsions: (T, axes, moves) as _torsion_arrays gives them - then one
+        mvx_score_hessian_flex_batch call, G (B, n) and H (B, n, n) for n = 6 + T, and atom_pos behind the per-atom rows."""
         F, stride = self._grid_operand(field, call.C, self._gdt)
         piv = self._hessian_pivots(pivots, posed)
         self._select_rows(call, per_atom)
-        B, n = call.B, call.rows
+        B, rows, n = call.B, call.rows, 6 if torsions is None else 6 + torsions[0]
         f64 = dict(dtype=torch.float64, device=self.device)
-        scores, tg, th = torch.empty(B, **f64), torch.empty((B, 6), **f64), torch.empty((B, 6, 6), **f64)
-        ag = torch.empty((n, 3), **f64) if per_atom else None
-        ah = torch.empty((n, 6), **f64) if per_atom else None
-        entry = call.pick(self._lib.mvx_score_hessian_batch, self._lib.mvx_score_hessian_views)
-        _lib.check(entry(*call.entry_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores), self._ptr(ag),
-                         self._ptr(ah), self._ptr(tg), self._ptr(th), self._stream()))
-        return (scores, tg, th, ag, ah) if per_atom else (scores, tg, th)
+        scores, G, H = torch.empty(B, **f64), torch.empty((B, n), **f64), torch.empty((B, n, n), **f64)
+        widths = () if not per_atom else (3, 6) if torsions is None else (3, 6, 3)  # atom_grad, atom_hess, atom_pos
+        per = tuple(torch.empty((rows, w), **f64) for w in widths)
+        ag, ah, ap = (per + (None, None, None))[:3]
+        head = (*call.entry_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores), self._ptr(ag), self._ptr(ah))
+        if torsions is None:
+            entry = call.pick(self._lib.mvx_score_hessian_batch, self._lib.mvx_score_hessian_views)
+            _lib.check(entry(*head, self._ptr(G), self._ptr(H), self._stream()))
+        else:  # (the twist outputs of its own are not asked for: they are G[:, :6] and H[:, :6, :6])
+            T, ax, mv = torsions
+            _lib.check(self._lib.mvx_score_hessian_flex_batch(*head, None, None, T, self._ptr(ax), self._ptr(mv), self._ptr(G),
+                                                              self._ptr(H), self._ptr(ap), self._stream()))
+        return (scores, G, H) + per
 
     def score_hessian_views(self, coords, centers, channels, radii, field, num_channels=None, pivots=None, per_atom=False):
         """score_hessian_batch for B views of ONE shared cloud, without B copies of it: each view's atoms are selected on the
@@ -1693,28 +1718,35 @@ class Voxelizer(BaseVoxelizer):
         (lam *= lam_up, dropped += 1); a pose with dropped >= max_dropped is finished and stays; every other pose gets
         xi = solve(-H + lam I, G) and the next trial (q2, t2) = apply_twist(q, t, xi) (a singular or non-finite system: xi = 0).
         state.q2, state.t2 and state.xi are allocated on the first call and reused. Returns state."""
-        B = int(state.q.shape[0])
-        for name, shape, dt in (("q", (B, 4), torch.float64), ("t", (B, 3), torch.float64), ("S", (B,), torch.float64),
-                                ("G", (B, 6), torch.float64), ("H", (B, 6, 6), torch.float64), ("lam", (B,), torch.float64),
-                                ("taken", (B,), torch.int32), ("dropped", (B,), torch.int32)):
+        return self._lm_step(state, trial, lam_down, lam_up, max_dropped)
+
+    def _lm_step(self, state, trial, lam_down, lam_up, max_dropped, T=None):
+        """The body of lm_step and flex_lm_step (T: the torsions of a FlexLMState): the state's tensors checked against their
+        shapes for n = 6 + T coordinates, the trial checked, the trial buffers made on the first call, one library call."""
+        B, n, f64, ptr = int(state.q.shape[0]), 6 if T is None else 6 + T, torch.float64, self._ptr
+        for name, shape, dt in ((("q", (B, 4), f64), ("t", (B, 3), f64)) + (() if T is None else (("theta", (B, T), f64),)) +
+                                (("S", (B,), f64), ("G", (B, n), f64), ("H", (B, n, n), f64), ("lam", (B,), f64),
+                                 ("taken", (B,), torch.int32), ("dropped", (B,), torch.int32))):
             x = getattr(state, name)
             assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == dt and x.is_contiguous() and self._on_device(x), (
                 f"state.{name} should be a contiguous {dt} tensor of shape {shape} on this voxelizer's device")
         if trial is not None:
-            assert state.q2 is not None, "a trial needs the trial pose of an earlier lm_step"
+            assert state.q2 is not None, f"a trial needs the trial pose of an earlier {state.METHOD}"
             S2, G2, H2 = trial
-            for name, x, shape in (("S2", S2, (B,)), ("G2", G2, (B, 6)), ("H2", H2, (B, 6, 6))):
-                assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == torch.float64 and x.is_contiguous() and self._on_device(x), (
+            for name, x, shape in (("S2", S2, (B,)), ("G2", G2, (B, n)), ("H2", H2, (B, n, n))):
+                assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == f64 and x.is_contiguous() and self._on_device(x), (
                     f"trial {name} should be a contiguous float64 tensor of shape {shape} on this voxelizer's device")
         else:
             S2 = G2 = H2 = None
         if state.q2 is None:
-            state.q2, state.t2, state.xi = torch.empty_like(state.q), torch.empty_like(state.t), torch.empty_like(state.G)
-        _lib.check(self._lib.mvx_lm_step(
-            self._handle, B, 0 if trial is None else 1, float(lam_down), float(lam_up), int(max_dropped), self._ptr(state.q),
-            self._ptr(state.t), self._ptr(state.S), self._ptr(state.G), self._ptr(state.H), self._ptr(state.lam), self._ptr(state.taken),
-            self._ptr(state.dropped), self._ptr(state.q2), self._ptr(state.t2), self._ptr(S2), self._ptr(G2), self._ptr(H2),
-            self._ptr(state.xi), self._stream()))
+            for name, like in zip(state.TRIAL + (state.STEP,), state.point() + (state.G,)):
+                setattr(state, name, torch.empty_like(like))
+        angles, angles2 = ((), ()) if T is None else ((ptr(state.theta),), (ptr(state.theta2),))
+        _lib.check(getattr(self._lib, state.ENTRY)(
+            self._handle, B, *(() if T is None else (T,)), 0 if trial is None else 1, float(lam_down), float(lam_up),
+            int(max_dropped), ptr(state.q), ptr(state.t), *angles, ptr(state.S), ptr(state.G), ptr(state.H), ptr(state.lam),
+            ptr(state.taken), ptr(state.dropped), ptr(state.q2), ptr(state.t2), *angles2, ptr(S2), ptr(G2), ptr(H2),
+            ptr(getattr(state, state.STEP)), self._stream()))
         return state
 
     def refine_posed_batch(self, coords, offsets, centers, quaternions, translations, channels, radii, field, num_channels=None,
@@ -1732,7 +1764,7 @@ class Voxelizer(BaseVoxelizer):
         self._hessian_guard(channels)
         self._check_pose(self._pose_count(offsets), centers, quaternions, translations)
         return self._refine(lambda q, t: self.score_hessian_posed_batch(coords, offsets, centers, q, t, channels, radii, field, num_channels),
-                            quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
+                            LMState, self.lm_step, (quaternions, translations), steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
 
     def refine_posed_views(self, coords, centers, quaternions, translations, channels, radii, field, num_channels=None, steps=40,
                            lam0=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3, stop_when_done=False):
@@ -1741,13 +1773,12 @@ class Voxelizer(BaseVoxelizer):
         self._hessian_guard(channels)
         self._check_pose(self._pose_count(None, centers), centers, quaternions, translations)
         return self._refine(lambda q, t: self.score_hessian_posed_views(coords, centers, q, t, channels, radii, field, num_channels),
-                            quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
+                            LMState, self.lm_step, (quaternions, translations), steps, lam0, lam_down, lam_up, max_dropped, stop_when_done)
 
-    def _refine(self, evaluate, quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done, angles=None):
-        """The loop of refine_posed_batch / refine_posed_views, evaluate(q, t) -> (S, G, H), and - with angles (B, T) - of
-        refine_flex_posed_batch, evaluate(q, t, theta) -> (S, G (B, n), H (B, n, n)): flex_lm_step in place of lm_step, and the
-        angles returned behind the poses."""
-        flex = angles is not None
+    def _refine(self, evaluate, State, step, start, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done):
+        """The loop of refine_posed_batch / refine_posed_views - State = LMState, step = lm_step, start = (q, t) - and of
+        refine_flex_posed_batch - FlexLMState, flex_lm_step, (q, t, theta): evaluate(*point) -> (S, G (B, n), H (B, n, n)) at
+        the start and at every trial point of the state. Returns the state's point, the scores and info."""
         assert int(steps) >= 0, "steps must be >= 0"
         with torch.no_grad():
             def own(x):  # a float64 copy on this device: the caller's poses are not modified
@@ -1755,28 +1786,23 @@ class Voxelizer(BaseVoxelizer):
                 return x.detach().to(device=self.device, dtype=torch.float64).clone().contiguous()
 
             # (the rules of the arguments fire here, before anything is copied)
-            S, G, H = evaluate(quaternions, translations, angles) if flex else evaluate(quaternions, translations)
-            q, t = own(quaternions), own(translations)
-            B = int(q.shape[0])
+            S, G, H = evaluate(*start)
+            point = [own(x) for x in start]
+            B = int(point[0].shape[0])
             if lam0 is None:
                 lam = (1e-3 * H.abs().reshape(B, int(G.shape[1]) ** 2).amax(dim=1) if B else
                        torch.zeros(0, dtype=torch.float64, device=self.device))
             else:
                 lam = (lam0.detach().to(device=self.device, dtype=torch.float64) if _is_torch(lam0) else
                        torch.as_tensor(np.asarray(lam0, dtype=np.float64), device=self.device)).expand(B).clone()
-            if flex:
-                state = FlexLMState(q, t, own(angles), S.clone(), G.clone(), H.clone(), lam.contiguous())
-                step, at_trial = self.flex_lm_step, lambda: evaluate(state.q2, state.t2, state.theta2)
-            else:
-                state = LMState(q, t, S.clone(), G.clone(), H.clone(), lam.contiguous())
-                step, at_trial = self.lm_step, lambda: evaluate(state.q2, state.t2)
+            state = State(*point, S.clone(), G.clone(), H.clone(), lam.contiguous())
             history = torch.empty((int(steps) + 1, B), dtype=torch.float64, device=self.device)
             history[0] = state.S
             kw = dict(lam_down=lam_down, lam_up=lam_up, max_dropped=max_dropped)
             step(state, **kw)
             evaluations, rounds = 1, 0
             for r in range(int(steps)):
-                trial = at_trial()
+                trial = evaluate(*state.trial())
                 evaluations += 1
                 step(state, trial, **kw)
                 history[r + 1] = state.S
@@ -1785,7 +1811,7 @@ class Voxelizer(BaseVoxelizer):
                     break
             info = dict(lam=state.lam, taken=state.taken, dropped=state.dropped, evaluations=evaluations,
                         score_history=history[:rounds + 1])
-        return (state.q, state.t, state.theta, state.S, info) if flex else (state.q, state.t, state.S, info)
+        return state.point() + (state.S, info)
 
     # ------------------------------------------------------------------------------------------
     # TORSION COORDINATES (rotatable bonds next to the rigid twist: mvx_apply_torsions, mvx_score_hessian_flex_batch,
@@ -1875,17 +1901,7 @@ class Voxelizer(BaseVoxelizer):
             call = self._batch_call(coords, offsets, centers, channels, radii, num_channels, posed=posed, device=True,
                                     check=self._hessian_rules(field, pivots))
             _, T, ax, mv, _ = self._torsion_arrays(call.offsets, axes, moves)
-            F, stride = self._grid_operand(field, call.C, self._gdt)
-            piv = self._hessian_pivots(pivots, posed)
-            B, N, n = call.B, call.N, 6 + T
-            f64 = dict(dtype=torch.float64, device=self.device)
-            scores, G, H = torch.empty(B, **f64), torch.empty((B, n), **f64), torch.empty((B, n, n), **f64)
-            ag, ah, ap = ((torch.empty((N, 3), **f64), torch.empty((N, 6), **f64), torch.empty((N, 3), **f64)) if per_atom
-                          else (None, None, None))
-            _lib.check(self._lib.mvx_score_hessian_flex_batch(
-                *call.entry_args(self), self._ptr(F), stride, self._ptr(piv), self._ptr(scores), self._ptr(ag), self._ptr(ah), None,
-                None, T, self._ptr(ax), self._ptr(mv), self._ptr(G), self._ptr(H), self._ptr(ap), self._stream()))
-        return (scores, G, H, ag, ah, ap) if per_atom else (scores, G, H)
+            return self._score_hessian(call, field, pivots, posed, per_atom, torsions=(T, ax, mv))
 
     def flex_lm_step(self, state, trial=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3):
         """lm_step for the B poses of a FlexLMState, in n = 6 + T coordinates (mvx_flex_lm_step): the same decisions, damping and
@@ -1897,30 +1913,7 @@ class Voxelizer(BaseVoxelizer):
         assert _is_torch(state.theta) and state.theta.ndim == 2 and state.theta.shape[0] == B and state.theta.shape[1] <= 32, (
             f"state.theta should be a (B, T) tensor with T <= 32")
         T = int(state.theta.shape[1])
-        n = 6 + T
-        for name, shape, dt in (("q", (B, 4), torch.float64), ("t", (B, 3), torch.float64), ("theta", (B, T), torch.float64),
-                                ("S", (B,), torch.float64), ("G", (B, n), torch.float64), ("H", (B, n, n), torch.float64),
-                                ("lam", (B,), torch.float64), ("taken", (B,), torch.int32), ("dropped", (B,), torch.int32)):
-            x = getattr(state, name)
-            assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == dt and x.is_contiguous() and self._on_device(x), (
-                f"state.{name} should be a contiguous {dt} tensor of shape {shape} on this voxelizer's device")
-        if trial is not None:
-            assert state.q2 is not None, "a trial needs the trial pose of an earlier flex_lm_step"
-            S2, G2, H2 = trial
-            for name, x, shape in (("S2", S2, (B,)), ("G2", G2, (B, n)), ("H2", H2, (B, n, n))):
-                assert _is_torch(x) and tuple(x.shape) == shape and x.dtype == torch.float64 and x.is_contiguous() and self._on_device(x), (
-                    f"trial {name} should be a contiguous float64 tensor of shape {shape} on this voxelizer's device")
-        else:
-            S2 = G2 = H2 = None
-        if state.q2 is None:
-            state.q2, state.t2, state.theta2 = torch.empty_like(state.q), torch.empty_like(state.t), torch.empty_like(state.theta)
-            state.x = torch.empty_like(state.G)
-        _lib.check(self._lib.mvx_flex_lm_step(
-            self._handle, B, T, 0 if trial is None else 1, float(lam_down), float(lam_up), int(max_dropped), self._ptr(state.q),
-            self._ptr(state.t), self._ptr(state.theta), self._ptr(state.S), self._ptr(state.G), self._ptr(state.H),
-            self._ptr(state.lam), self._ptr(state.taken), self._ptr(state.dropped), self._ptr(state.q2), self._ptr(state.t2),
-            self._ptr(state.theta2), self._ptr(S2), self._ptr(G2), self._ptr(H2), self._ptr(state.x), self._stream()))
-        return state
+        return self._lm_step(state, trial, lam_down, lam_up, max_dropped, T)
 
     def refine_flex_posed_batch(self, coords, offsets, centers, quaternions, translations, angles, channels, radii, field, axes, moves,
                                 num_channels=None, steps=40, lam0=None, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3,
@@ -1943,8 +1936,8 @@ class Voxelizer(BaseVoxelizer):
             return self._score_hessian_flex(conformer, off, centers, channels, radii, field, ax, mv, num_channels, None, False,
                                             posed=(q, t), checked=True)
 
-        return self._refine(evaluate, quaternions, translations, steps, lam0, lam_down, lam_up, max_dropped, stop_when_done,
-                            angles=angles)
+        return self._refine(evaluate, FlexLMState, self.flex_lm_step, (quaternions, translations, angles), steps, lam0, lam_down,
+                            lam_up, max_dropped, stop_when_done)
 
     # ------------------------------------------------------------------------------------------
     # SCORES OF VIEWS (many poses or boxes of one shared cloud against a field: mvx_score_views / mvx_views_reduce)
