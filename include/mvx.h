@@ -740,6 +740,30 @@ int mvx_apply_torsions(mvx_handle *h, const double *coords, const int64_t *offse
                        const int32_t *moves, const double *angles, double *out, void *stream);
 
 /*
+ * mvx_apply_torsions_backward: the adjoint of mvx_apply_torsions: from the conformer C(theta) that call returned and grad_out =
+ * dL/dC to grad_coords = dL/dcoords and grad_angles = dL/dangles. The turns are swept in reverse, k = T-1 .. 0, on working
+ * positions in handle-owned workspace (sumN * 3 doubles; `conformer` is not written) and on the rows in grad_coords, which start
+ * as grad_out. With c = cos angles[b, k], s = sin angles[b, k], R = c I + s [u]x + (1 - c) u u^T about the current axis, for
+ * every atom n of M_k, w = y_n - p_b: the turn is undone, v = R^T w; grad_angles[b, k] += ybar_n . (u x w); the row becomes
+ * R^T ybar_n; b_bar += ybar_n - R^T ybar_n; u_bar += s (v x ybar_n) + (1 - c) ((u . v) ybar_n + (u . ybar_n) v); then d_bar =
+ * (u_bar - u (u . u_bar)) / |p_b - p_a| and the rows of b_k and a_k receive b_bar + d_bar and -d_bar. One workgroup per molecule;
+ * the seven sums are float64 lane partials in a fixed order (thread i takes the atoms i, i + 256, ...), a butterfly per wave, the
+ * four waves in a fixed order: no atomics, two runs give the same bits, a molecule's values do not depend on its batch.
+ *   conformer, grad_out, grad_coords: (sumN, 3) double, device; grad_coords may be grad_out. grad_angles: (B, T) double, device.
+ *   offsets, axes, moves, angles: as for mvx_apply_torsions, the arguments of the call that made `conformer`.
+ * An angle of exactly 0 moves neither positions nor rows, and its grad_angles entry is the derivative all the same. An inert
+ * torsion gets +0.0 and touches nothing else. An atom whose current row is all zero is left out of the sums and keeps its row:
+ * its coordinates may be NaN or infinite. The tree rules are assumed, as undoing the turns needs them (a_k not in M_k): outside
+ * them the call stays inside its arrays and its values are unspecified. T == 0 copies grad_out to grad_coords. Asynchronous on
+ * `stream`. MVX_ERR_INVALID before any device is touched for, in order: B < 0; T outside 0 .. 32; NULL offsets with B > 0,
+ * offsets[0] != 0 or decreasing offsets; offsets[B] >= 2^31; NULL conformer, grad_out or grad_coords with atoms; NULL axes, moves,
+ * angles or grad_angles with atoms and T > 0; a NULL handle. No molecules or no atoms: MVX_OK.
+ */
+int mvx_apply_torsions_backward(mvx_handle *h, const double *conformer, const int64_t *offsets, int32_t B, int32_t T,
+                                const int32_t *axes, const int32_t *moves, const double *angles, const double *grad_out,
+                                double *grad_coords, double *grad_angles, void *stream);
+
+/*
  * mvx_score_hessian_batch with torsions: the gradient and Hessian of the scores in the coordinates x = (tau, omega, theta_0 ..
  * theta_{T-1}), n = 6 + T, at x = 0, where p_n(x) = exp([omega]x) (C(theta)_n - o_b) + o_b + tau in the grid frame and the
  * caller's coords are the conformer the angles are counted from. The same walk and reductions as mvx_score_hessian_batch - its

@@ -13,6 +13,7 @@
 #include "mvx_plan.h"
 #include "mvx_pose.h"
 #include "mvx_sum.h"
+#include "mvx_torsion_grad.h"
 #include "mvx_views.h"
 
 #include <algorithm>
@@ -132,8 +133,9 @@ struct mvx_handle : NoCopy {
     DevBuf score_atoms; // mvx_score_batch without atom_scores: the per-atom scores its reduction reads, 8 bytes per atom
     DevBuf hess_rows;   // mvx_score_hessian_batch: [s_n | g_n | H_n], 8 + 24 + 48 bytes per atom; rows handed out are not used
     // mvx_score_hessian_flex_batch: [subset sums, B * T * 36 doubles | twist_grad, B * 6 | twist_hess, B * 36] (the twist values
-    // only where the caller passed null for them); mvx_apply_torsions: the call's offsets
+    // only where the caller passed null for them); mvx_apply_torsions and mvx_apply_torsions_backward: the call's offsets
     DevBuf flex_ws, flex_off;
+    DevBuf torsion_pos; // mvx_apply_torsions_backward: the positions the sweep turns back, 24 bytes per atom
     // "grad_order" option: 0 atoms in the caller's order (the default), 1 in spatial order, XCD by XCD. The spatial order cuts
     // the gradient kernel's memory traffic five-fold at cfg-2 x 256 but not its time (-2 %), and its sort costs small batches
     // more than it saves (profiles/r05_grad.txt)
@@ -2117,6 +2119,38 @@ int mvx_apply_torsions(mvx_handle *h, const double *coords, const int64_t *offse
     DeviceInputs in; // the offsets through a pinned slot, as the backward entries stage theirs
     if (int rc = stage_meta(h, h->flex_off, c, false, 0, in)) return rc;
     HIP_TRY(launch_torsion_apply(coords, in.offsets, B, T, axes, moves, angles, out, c.stream));
+    return release_slot(in.slot, c.stream);
+}
+
+int mvx_apply_torsions_backward(mvx_handle *h, const double *conformer, const int64_t *offsets, int32_t B, int32_t T,
+                                const int32_t *axes, const int32_t *moves, const double *angles, const double *grad_out,
+                                double *grad_coords, double *grad_angles, void *stream) {
+    // ---- what is checked before any device is touched (mvx_apply_torsions' rules in its order) ----
+    if (B < 0) return fail(MVX_ERR_INVALID, "B must be >= 0");
+    if (T < 0 || T > FLEX_MAX_T) return fail(MVX_ERR_INVALID, "T must be 0 ... 32");
+    Extent e;
+    if (const char *bad = check_offsets(offsets, B, e)) return fail(MVX_ERR_INVALID, bad);
+    if (const char *bad = too_many_atoms(e.total)) return fail(MVX_ERR_INVALID, bad);
+    if (e.total > 0 && (!conformer || !grad_out || !grad_coords))
+        return fail(MVX_ERR_INVALID, "conformer / grad_out / grad_coords must not be null");
+    if (e.total > 0 && T > 0 && (!axes || !moves || !angles || !grad_angles))
+        return fail(MVX_ERR_INVALID, "axes, moves, angles and grad_angles must not be null with T > 0");
+    if (!h) return fail(MVX_ERR_INVALID, "null handle");
+    if (e.total == 0) return MVX_OK;
+
+    const Call c = batch_call(0, nullptr, nullptr, nullptr, 0.0, 0, offsets, nullptr, B, 0, stream); // (what stage_meta reads)
+    CallScope scope(h, c.stream);
+    if (scope.rc) return scope.rc;
+    const size_t bytes = (size_t)e.total * 3 * sizeof(double);
+    if (T == 0) { // no turn to pull the rows back through
+        if (grad_coords != grad_out) HIP_TRY(hipMemcpyAsync(grad_coords, grad_out, bytes, hipMemcpyDeviceToDevice, c.stream));
+        return MVX_OK;
+    }
+    if (int rc = ensure(h->torsion_pos, bytes)) return rc;
+    DeviceInputs in; // the offsets through a pinned slot, as the backward entries stage theirs
+    if (int rc = stage_meta(h, h->flex_off, c, false, 0, in)) return rc;
+    HIP_TRY(launch_torsion_backward(conformer, in.offsets, B, T, axes, moves, angles, grad_out,
+                                    reinterpret_cast<double *>(h->torsion_pos.p), grad_coords, grad_angles, c.stream));
     return release_slot(in.slot, c.stream);
 }
 

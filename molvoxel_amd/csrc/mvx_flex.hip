@@ -9,7 +9,8 @@
 //   c_k = tau_k x F_k + (K_k - tr(K_k) I) u_k
 //   G[6 + k] = s_k . (F_k, N_k)      H[:6, 6 + k] = X_k s_k + (0, c_k)      H[6 + k, 6 + l] = s_k^T X_l s_l + u_k . c_l  (k <= l related)
 // and 0 for unrelated pairs. G[:6] and H[:6, :6] are the rigid twist sums (launch_twist_reduce), copied. One atom's terms of
-// F, N, X and K, the rule for an atom without rows, the decision on a trial and the twist onto the pose are mvx_newton_device.h's.
+// F, N, X and K, the rule for an atom without rows, the decision on a trial and the twist onto the pose are mvx_newton_device.h's;
+// the unit axis of a torsion is mvx_flex_device.h's, shared with the adjoint of torsion_apply_kernel (mvx_torsion_grad.hip).
 //
 //   torsion_apply_kernel  one workgroup per molecule; the positions are worked on in the output array. Per torsion in order: every
 //                         thread reads the current axis atoms, a barrier, the atoms of the set are turned (Rodrigues), a barrier.
@@ -27,6 +28,7 @@
 // entry, zero Hessian row and column; no axis index is used before it is checked. No atomics, no scratch
 // (tests/test_flex_host.py pins it), no host read; a molecule's values do not depend on its batch.
 #include "mvx_flex.h"
+#include "mvx_flex_device.h"
 #include "mvx_newton_device.h"
 
 #include <math.h>
@@ -36,18 +38,6 @@ namespace mvx {
 namespace {
 
 static_assert(FLEX_SUBSET == TWIST_K_SLOT + 9, "F, N, the upper triangle of X, K");
-
-// The unit axis u from pa to pb, or false: no length, or none that is finite (then pa and pb are not both finite).
-__device__ __forceinline__ bool unit_axis(const double (&pa)[3], const double (&pb)[3], double (&u)[3]) {
-    const double d0 = pb[0] - pa[0], d1 = pb[1] - pa[1], d2 = pb[2] - pa[2];
-    const double len2 = (d0 * d0 + d1 * d1) + d2 * d2;
-    if (!(len2 > 0.0) || !isfinite(len2)) return false;
-    const double len = sqrt(len2);
-    u[0] = d0 / len;
-    u[1] = d1 / len;
-    u[2] = d2 / len;
-    return true;
-}
 
 // Torsion `ax` = (a, b) of a molecule with atoms [a0, a0 + N) in the records: false when it is inert, else p_b and the axis.
 __device__ __forceinline__ bool record_axis(const AtomRec *rec, int64_t a0, int64_t N, const int32_t *ax, double (&pb)[3], double (&u)[3]) {

@@ -110,6 +110,7 @@ SIGNATURES = {
     "mvx_lm_step": (C.c_int, [Handle, _i32, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp]),
     "mvx_apply_torsions": (C.c_int, [Handle, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "mvx_apply_torsions_backward": (C.c_int, [Handle, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvx_score_hessian_flex_batch": (C.c_int, [Handle, _i32, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _vp,
                                                _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvx_flex_lm_step": (C.c_int, [Handle, _i32, _i32, _i32, _dbl, _dbl, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

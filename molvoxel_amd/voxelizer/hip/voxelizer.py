@@ -22,6 +22,9 @@ Constructor options:
   moments_grad=True (with differentiable)  `moments_batch` / `moments_posed_batch` record an autograd graph: coords, features,
                                centres and poses that require grad get their gradients through the moments
                                (mvx_moments_backward_batch), without B grids and without any grid of dL/dgrid
+  torsion_grad=True (with differentiable)  `apply_torsions` records an autograd graph: coords and angles that require grad get
+                               their gradients through the conformer (mvx_apply_torsions_backward), so that rotatable bonds
+                               can be refined with a torch optimiser through any entry that takes device coords
   overlap_prepass=True         see `set_overlap_prepass`
 
 Entries, next to the reference's `forward_features / forward_types / forward_single`:
@@ -243,6 +246,7 @@ class Voxelizer(BaseVoxelizer):
     blockdim = 8
     field_grad = False
     _mgrad = False  # (the constructor's moments_grad)
+    _tgrad = False  # (the constructor's torsion_grad)
     _sum_parts = 1
     _views_total = 0
 
@@ -264,6 +268,7 @@ class Voxelizer(BaseVoxelizer):
         grid_layout=None,
         field_grad: bool = False,
         moments_grad: bool = False,
+        torsion_grad: bool = False,
         **kwargs,
     ):
         # sigma as a tensor (sigma_grad): kept as `sigma_tensor`; `_sigma` stays the python float the base class stores
@@ -289,9 +294,12 @@ class Voxelizer(BaseVoxelizer):
             raise ValueError("field_grad=True needs differentiable=True: the field gradient is part of the autograd graph")
         if moments_grad and not differentiable:
             raise ValueError("moments_grad=True needs differentiable=True: the gradients of the moments are part of the autograd graph")
+        if torsion_grad and not differentiable:
+            raise ValueError("torsion_grad=True needs differentiable=True: the gradients of the conformer are part of the autograd graph")
         self.differentiable = bool(differentiable)
         self.field_grad = bool(field_grad)
         self._mgrad = bool(moments_grad)
+        self._tgrad = bool(torsion_grad)
         self.radii_grad = bool(radii_grad)
         self.sigma_grad = bool(sigma_grad)
         self._sigma_src = sigma_src
@@ -532,7 +540,7 @@ class Voxelizer(BaseVoxelizer):
                                self.blockdim, idx, self.output, self.overlap_prepass,
                                grid_dtype="bfloat16" if self._bf16 else None, differentiable=self.differentiable,
                                radii_grad=self.radii_grad, sigma_grad=self.sigma_grad, grid_layout=self.grid_layout,
-                               field_grad=self.field_grad, moments_grad=self._mgrad, **kw)
+                               field_grad=self.field_grad, moments_grad=self._mgrad, torsion_grad=self._tgrad, **kw)
             if self.sum_parts != 1:
                 moved.set_sum_parts(self.sum_parts)
             return moved
@@ -1851,19 +1859,71 @@ class Voxelizer(BaseVoxelizer):
         atom axes[b, k, 1] (local indices), through the latter. coords (N, 3); offsets (B + 1,); axes (B, T, 2) int32, padded
         with -1; moves (N,) int32; angles (B, T) radians. Applying angles and then more angles to the result is the same as
         applying their sum. An angle of exactly 0 and an inert torsion (padding, an index outside the molecule, coincident
-        axis atoms) turn nothing. Returns the new coordinates (N, 3), float64 on this device; outside autograd. The tree rules
-        are not checked here: check_torsions."""
+        axis atoms) turn nothing. Returns the new coordinates (N, 3), float64 on this device. The tree rules are not checked
+        here: check_torsions.
+
+        Outside autograd unless the voxelizer was made with torsion_grad=True (and differentiable=True). Then, with grad mode
+        on and `coords` or `angles` a tensor on this device that requires grad, the call is part of the autograd graph: the
+        same launch and the same bits, and backward() is mvx_apply_torsions_backward from the returned conformer and the angles
+        - dL/dcoords and dL/dangles in the inputs' dtype and shape. The adjoint undoes the turns, which needs the tree rules (an
+        axis atom a_k outside its set): outside them the gradients are unspecified. No double backward."""
         self._flex_guard(None, "apply_torsions")
         assert len(getattr(coords, "shape", ())) == 2 and coords.shape[1] == 3, "coords should be (N, 3)"
         off = np.ascontiguousarray(offsets, dtype=np.int64)
         assert off[0] == 0 and off[-1] == coords.shape[0], "offsets must span coords"
+        self._torsion_arrays(off, axes, moves, angles, convert=False)
+        wanted = self._torsion_grad_wanted(coords, angles)  # (its refusal needs no device)
         B, T, ax, mv, th = self._torsion_arrays(off, axes, moves, angles)
+        if wanted:
+            tracked = lambda x: x if _is_torch(x) and x.requires_grad else None  # noqa: E731
+            return _TorsionFunction.apply(self, (off, B, T, ax, mv), self._device_coords(coords), th, tracked(coords), tracked(angles))
+        return self._apply_torsions(self._device_coords(coords), off, B, T, ax, mv, th)
+
+    def _torsion_grad_wanted(self, coords, angles) -> bool:
+        """Does apply_torsions record an autograd graph: a torsion_grad voxelizer, grad mode on and coords or angles a tensor
+        that requires grad - on this device, or _grad_wanted raises."""
+        if not self._tgrad or torch is None or not torch.is_grad_enabled():
+            return False
+        tracked = [x for x in (coords, angles) if _is_torch(x) and x.requires_grad]
+        return bool(tracked) and self._grad_wanted(tracked[0], tracked[-1], None, None, None)
+
+    def _apply_torsions(self, coords, off, B, T, ax, mv, th):
+        """The call of apply_torsions, as plain values: coords on this device, the others as _torsion_arrays gives them."""
         with torch.no_grad():
-            c = self._device_coords(coords).to(torch.float64).contiguous()
+            c = coords.detach().to(torch.float64).contiguous()
             out = torch.empty_like(c)
             _lib.check(self._lib.mvx_apply_torsions(self._handle, self._ptr(c), off.ctypes.data, B, T, self._ptr(ax), self._ptr(mv),
                                                     self._ptr(th), self._ptr(out), self._stream()))
         return out
+
+    def apply_torsions_backward(self, conformer, offsets, axes, moves, angles, grad):
+        """The adjoint of apply_torsions (mvx_apply_torsions_backward): from the conformer (N, 3) that apply_torsions returned
+        for (offsets, axes, moves, angles) and grad = dL/dconformer (N, 3) to (dL/dcoords (N, 3), dL/dangles (B, T)), float64
+        on this device; plain values on any output='torch' voxelizer - what backward() of a recorded apply_torsions calls. The
+        turns are undone last first on a copy of the conformer while the rows are pulled back through them; nothing the caller
+        passed is modified. An angle of exactly 0 has its true derivative; an inert torsion has +0.0; an atom whose row is all
+        zero may have NaN coordinates. Deterministic, no atomics: two runs give the same bits and a molecule's values do not
+        depend on its batch. The tree rules are assumed, not checked (check_torsions): outside them the values are
+        unspecified."""
+        self._flex_guard(None, "apply_torsions_backward")
+        assert len(getattr(conformer, "shape", ())) == 2 and conformer.shape[1] == 3, "conformer should be (N, 3)"
+        assert tuple(getattr(grad, "shape", ())) == tuple(conformer.shape), (
+            f"grad does not match dimension: {tuple(getattr(grad, 'shape', ()))} vs {tuple(conformer.shape)}")
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        assert off[0] == 0 and off[-1] == conformer.shape[0], "offsets must span conformer"
+        B, T, ax, mv, th = self._torsion_arrays(off, axes, moves, angles)
+        return self._apply_torsions_backward(self._device_coords(conformer), off, B, T, ax, mv, th, self._device_coords(grad))
+
+    def _apply_torsions_backward(self, conformer, off, B, T, ax, mv, th, grad):
+        with torch.no_grad():
+            c = conformer.detach().to(torch.float64).contiguous()
+            g = grad.detach().to(torch.float64).contiguous()
+            gc = torch.empty_like(c)
+            ga = (torch.empty if c.shape[0] else torch.zeros)((B, T), dtype=torch.float64, device=c.device)  # (no atoms: no launch)
+            _lib.check(self._lib.mvx_apply_torsions_backward(self._handle, self._ptr(c), off.ctypes.data, B, T, self._ptr(ax),
+                                                             self._ptr(mv), self._ptr(th), self._ptr(g), self._ptr(gc), self._ptr(ga),
+                                                             self._stream()))
+        return gc, ga
 
     def score_hessian_flex_batch(self, coords, offsets, centers, channels, radii, field, axes, moves, num_channels=None, pivots=None,
                                  per_atom=False):
@@ -2262,6 +2322,28 @@ if torch is not None:
             need_c, need_f, need_cen, need_pose = ctx.needs_input_grad[3:7]
             gc, gf = ctx.vox._moments_backward(ctx.spec, c, f, T, gm, need_f)
             return (None, None, None) + _input_grads(ctx.vox, ctx.spec, c, index, gc, gf, cen, need_c, need_cen, need_pose)
+
+
+    class _TorsionFunction(torch.autograd.Function):
+        """conformer = apply_torsions(coords, angles) on a torsion_grad voxelizer: the forward call as it runs without autograd
+        (same launch, same bits); backward = mvx_apply_torsions_backward from the saved conformer and angles. `c`, `th`: the
+        values as the library reads them; `coords`, `angles`: the caller's tensors that require grad, or None."""
+
+        @staticmethod
+        def forward(ctx, vox, spec, c, th, coords, angles):
+            out = vox._apply_torsions(c, *spec, th)
+            ctx.vox, ctx.spec = vox, spec
+            ctx.like = tuple(None if x is None else (x.dtype, x.shape) for x in (coords, angles))
+            ctx.save_for_backward(out, th)
+            return out
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(ctx, grad):
+            out, th = ctx.saved_tensors
+            gc, ga = ctx.vox._apply_torsions_backward(out, *ctx.spec, th, grad)
+            like = lambda g, t: None if t is None else g.to(dtype=t[0]).reshape(t[1])  # noqa: E731
+            return None, None, None, None, like(gc, ctx.like[0]), like(ga, ctx.like[1])
 
 
 def transform_on_device(coords, center, translation, quaternion):
