@@ -46,7 +46,7 @@ def _read(addr, dtype, count):
     return name
 
 
-def _records(addr, count):
+def _read_records(addr, count):
     """The fields of `count` mvx_xform records that their flags tell the library to read."""
     out = []
     for b in range(count):
@@ -100,7 +100,7 @@ class StubLib:
             if a["radii"]:
                 call["radii@"] = _read(a["radii"], np.float32, n_atoms if a["radii_type"] == _lib.MVX_RADII_ATOM else nc)
             if a["xforms"]:
-                call["xforms@"] = _records(a["xforms"], nb)
+                call["xforms@"] = _read_records(a["xforms"], nb)
             self.calls.append(call)
             return 0
 

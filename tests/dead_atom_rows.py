@@ -28,7 +28,7 @@ import functools
 
 import numpy as np
 
-from tests.entry_fuzz_rows import CEN, NORMS, WALK_ELEMENTS
+from tests.entry_fuzz_rows import CEN, NORMS, WALK_ELEMENTS, _freeze
 
 NAN, INF = float("nan"), float("inf")
 DEAD_COORDS = {"x nan": [NAN, 0.0, 0.0], "y nan": [0.0, NAN, 0.0], "x inf": [INF, 1.0, -1.0], "x -inf y nan": [-INF, NAN, 2.0],
@@ -75,13 +75,6 @@ def kinds_of(mode, radii_type, C_):
     if mode == "types" and radii_type in ("scalar", "atom-wise"):
         out += list(dead_types(C_))
     return out
-
-
-def _freeze(d):
-    for v in d.values():
-        if isinstance(v, np.ndarray):
-            v.setflags(write=False)
-    return d
 
 
 def _live_channels(rng, mode, n, C_, fp):

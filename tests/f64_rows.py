@@ -157,9 +157,8 @@ BATCH_IDS = [r.id for r in BATCH_ROWS]
 
 
 # ---- the molecules -------------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def positions(geom: str) -> np.ndarray:
-    g = GEOMS[geom]
+def geom_positions(g) -> np.ndarray:
+    """The seeded cloud of a geometry (this table's or tests/narrow_rows.py's), read-only."""
     rng = np.random.default_rng(1)
     if g.positions == "uniform":
         W = RES * (g.D - 1)
@@ -168,6 +167,11 @@ def positions(geom: str) -> np.ndarray:
         xyz = rng.normal(0.0, float(g.positions.split(":")[1]), (g.atoms, 3))
     xyz.setflags(write=False)
     return xyz
+
+
+@functools.lru_cache(maxsize=None)
+def positions(geom: str) -> np.ndarray:
+    return geom_positions(GEOMS[geom])
 
 
 def make_molecule(row: Row) -> dict:

@@ -121,15 +121,7 @@ def narrow_plan(plan: dict) -> dict:
 
 @functools.lru_cache(maxsize=None)
 def positions(geom: str) -> np.ndarray:
-    g = GEOMS[geom]
-    rng = np.random.default_rng(1)
-    if g.positions == "uniform":
-        W = RES * (g.D - 1)
-        xyz = rng.uniform(-W / 2, W / 2, (g.atoms, 3))
-    else:
-        xyz = rng.normal(0.0, float(g.positions.split(":")[1]), (g.atoms, 3))
-    xyz.setflags(write=False)
-    return xyz
+    return F.geom_positions(GEOMS[geom])
 
 
 @functools.lru_cache(maxsize=None)

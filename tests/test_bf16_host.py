@@ -9,9 +9,9 @@ import subprocess
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, VERSION, call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
 
 
 def test_header_compiles_as_c99_with_grid_type_in_the_old_reserved_slot(tmp_path):
@@ -35,7 +35,7 @@ def test_header_compiles_as_c99_with_grid_type_in_the_old_reserved_slot(tmp_path
     libdir = os.path.dirname(_lib.LIB_PATH)
     subprocess.check_call([gcc, str(obj), "-L", libdir, "-lmvx_hip", f"-Wl,-rpath,{libdir}", "-o", str(exe)])
     out = subprocess.check_output([str(exe)]).decode().split()
-    assert [int(v) for v in out] == [40, 36, 4, 0, 1, 140]
+    assert [int(v) for v in out] == [40, 36, 4, 0, 1, VERSION]
     assert _lib.MvxConfig.grid_type.offset == 36 and C.sizeof(_lib.MvxConfig) == 40
 
 
@@ -43,10 +43,10 @@ def _create(precision, grid_type, dimension=32):
     cfg = _lib.MvxConfig(0.5, 0.5, dimension, 8, _lib.MVX_GAUSSIAN, 0, precision, grid_type)
     h = _lib.Handle()
     lib = _lib.load()
-    rc = lib.mvx_create(C.byref(cfg), C.byref(h))
+    rc, msg = call(lib.mvx_create, C.byref(cfg), C.byref(h))
     if rc == 0:
         lib.mvx_destroy(h)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return rc, msg
 
 
 @pytest.mark.parametrize("precision, grid_type", [(64, 1), (32, 2), (32, -1), (0, 7)])

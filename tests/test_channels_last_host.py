@@ -7,10 +7,10 @@ import re
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, call
 from tests.test_hip_fuzz import DIMS as FUZZ_DIMS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
 NDHWC, NCDHW = 1, 0
 
 
@@ -59,15 +59,9 @@ def test_setter_is_declared_in_the_header_and_bound_by_ctypes():
 def test_setter_rejects_before_a_device_is_looked_for(layout, word):
     """No handle can exist on a machine without a GPU: the setter's checks that need none - the layout value first, then the
     handle - answer MVX_ERR_INVALID, never MVX_ERR_NO_DEVICE."""
-    lib = _lib.load()
-    assert lib.mvx_set_grid_layout(None, layout) == MVX_ERR_INVALID
-    assert word in (lib.mvx_last_error() or b"").decode()
-
-
-def test_config_size_and_version_are_unchanged():
-    lib = _lib.load()
-    assert C.sizeof(_lib.MvxConfig) == 40
-    assert lib.mvx_version() == 140
+    rc, msg = call(_lib.load().mvx_set_grid_layout, None, layout)
+    assert rc == MVX_ERR_INVALID
+    assert word in msg
 
 
 # ---- plan ----------------------------------------------------------------------------------------------------------------------

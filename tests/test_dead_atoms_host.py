@@ -19,6 +19,7 @@ from tests import entry_fuzz_rows as E
 from tests import grad_reference as gr
 from tests import pose_reference as pr
 from tests import views_reference as vr
+from tests import hip_support as hip
 from tests.tolerance import GAUSS_TOL, P64_TOL, gaussian_excess
 
 
@@ -47,10 +48,6 @@ def test_an_infinite_radius_at_precision_64_is_dead_in_the_library_only():
         g = numpy_port.voxelize(spec, np.zeros((1, 3)), np.ones((1, 1)), np.array([np.inf]), radii_type="atom-wise", density="gaussian",
                                 sigma=0.5, precision=64)
     assert (g == 1.0).all()
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 def test_the_rows_cover_every_kind_position_placement_and_shape():
@@ -102,7 +99,7 @@ def test_the_oracle_gives_the_clean_grid_for_the_dirty_batch_and_the_mutants_do_
     d, c = R.dirty(r), R.clean(r)
     dirty, clean = _grids(d, r["dead_kind"]), _grids(c)
     for b in range(r["B"]):
-        assert _same_bits(dirty[b], clean[b]), (row_id, b)
+        assert hip.same_bits(dirty[b], clean[b]), (row_id, b)
         for ch in range(r["C"]):  # every channel that has a live atom (all of them: dead_atom_rows._live_channels)
             assert R.LIVE[b] == 0 or clean[b][ch].any(), (row_id, b, ch)
         if R.LIVE[b] == 0:
@@ -134,7 +131,7 @@ def test_the_oracle_gives_the_clean_grid_for_the_dirty_batch_and_the_mutants_do_
             if r["radii_type"] == "scalar":
                 ra = None
         mutant = R.oracle_grid(d, p, b, xyz=xyz, w=w, r_atom=ra)
-        assert not _same_bits(mutant, clean[b]) and np.abs(mutant.astype(np.float64) - clean[b]).max() > 0.1, (row_id, b)
+        assert not hip.same_bits(mutant, clean[b]) and np.abs(mutant.astype(np.float64) - clean[b]).max() > 0.1, (row_id, b)
         changed += 1
     assert changed >= 1
 

@@ -1,6 +1,6 @@
 """Torsion coordinates without a GPU: the numpy reference (tests/flex_reference.py) against central finite differences of a smooth
 analytic score and its two conformer identities, the three C ABI entries (mvx_apply_torsions, mvx_score_hessian_flex_batch,
-mvx_flex_lm_step) against the header and the ctypes table, every rejection and its order, what the Python layer and check_torsions
+mvx_flex_lm_step; prototypes: tests/test_abi_header_host.py), every rejection and its order, what the Python layer and check_torsions
 refuse before they need the library, torsion_tree on the 10GS ligand, the four kernels' resources read from mvx_flex.o, and the
 conditions of the GPU refinement test on the numpy loop (tests/flex_rows.py).
 
@@ -12,7 +12,6 @@ rigid refinement of the same starts ends at 633 ... 641."""
 import ctypes as C
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -20,11 +19,10 @@ import pytest
 from molvoxel_amd.voxelizer.hip import _lib
 from tests import flex_reference as fr
 from tests import flex_rows as X
+from tests.abi import MVX_ERR_INVALID, P, call, records
 from tests.fake_voxelizer import fake as _fake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
 
 
 # ---- the reference against finite differences -------------------------------------------------------------------------------
@@ -104,45 +102,15 @@ def test_inert_torsions_in_the_reference_give_exact_zeros():
 
 
 # ---- the entries against the header -------------------------------------------------------------------------------------------
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-HESS_HEAD = ["h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "offsets", "xforms", "B", "C", "field",
-             "field_mol_stride", "pivots", "scores", "atom_grad", "atom_hess", "twist_grad", "twist_hess"]
-
-
-@pytest.mark.parametrize("name, names", [
-    ("mvx_apply_torsions", ["h", "coords", "offsets", "B", "T", "axes", "moves", "angles", "out", "stream"]),
-    ("mvx_score_hessian_flex_batch", HESS_HEAD + ["T", "axes", "moves", "flex_grad", "flex_hess", "atom_pos", "stream"]),
-    ("mvx_flex_lm_step", ["h", "B", "T", "have_trial", "lam_down", "lam_up", "max_dropped", "q", "t", "theta", "S", "G", "H", "lam",
-                          "taken", "dropped", "q2", "t2", "theta2", "S2", "G2", "H2", "x", "stream"]),
-])
-def test_ctypes_prototypes_match_the_header(name, names):
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(rf"\bint {name}\(([^;]*?)\);", text, re.S)
-    assert m
-    args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES[name]
-    assert res is C.c_int and got == want
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == names
-
-
-def test_the_flex_entry_begins_like_the_hessian_entry_and_the_library_keeps_its_version():
+def test_the_flex_entry_begins_like_the_hessian_entry():
     assert _lib.SIGNATURES["mvx_score_hessian_flex_batch"][1][:19] == _lib.SIGNATURES["mvx_score_hessian_batch"][1][:19]
-    lib = _lib.load()
-    for name in ("mvx_apply_torsions", "mvx_score_hessian_flex_batch", "mvx_flex_lm_step"):
-        assert hasattr(lib, name)
-    assert lib.mvx_version() == 140
 
 
 # ---- rejections --------------------------------------------------------------------------------------------------------------
-def _msg(rc):
-    return rc, (_lib.load().mvx_last_error() or b"").decode()
-
-
 def _apply(handle=None, coords=P, offsets=(0, 3), B=1, T=2, axes=P, moves=P, angles=P, out=P):
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    return _msg(_lib.load().mvx_apply_torsions(handle, coords, None if off is None else off.ctypes.data, B, T, axes, moves, angles, out,
-                                               None))
+    return call(_lib.load().mvx_apply_torsions, handle, coords, None if off is None else off.ctypes.data, B, T, axes, moves, angles, out,
+                None)
 
 
 @pytest.mark.parametrize("kw, words", [
@@ -170,15 +138,7 @@ def test_apply_torsions_rules_fire_in_their_order():
     assert _apply(handle=P, B=0, offsets=None)[0] == 0
 
 
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-ONE = _records([0])
+ONE = records([0])
 
 
 def _flex(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, offsets=(0, 3), xforms=ONE, B=1, C_=4, field=P, stride=0,
@@ -188,8 +148,8 @@ def _flex(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, o
     head = (handle, mode, coords, channels, radii, 1.0, radii_type, None if off is None else off.ctypes.data,
             None if xforms is None else C.addressof(xforms), B, C_, field, stride, None, scores, None, None, twist_grad, twist_hess)
     if not flex:
-        return _msg(lib.mvx_score_hessian_batch(*head, None))
-    return _msg(lib.mvx_score_hessian_flex_batch(*head, T, axes, moves, flex_grad, flex_hess, atom_pos, None))
+        return call(lib.mvx_score_hessian_batch, *head, None)
+    return call(lib.mvx_score_hessian_flex_batch, *head, T, axes, moves, flex_grad, flex_hess, atom_pos, None)
 
 
 HESSIAN_RULES = [dict(mode=3), dict(C_=0), dict(mode=2, C_=3), dict(stride=-1), dict(scores=None), dict(B=-1), dict(radii_type=7),
@@ -237,8 +197,8 @@ STATE = ("q", "t", "theta", "S", "G", "H", "lam", "taken", "dropped", "q2", "t2"
 def _lm(handle=None, B=2, T=3, have_trial=1, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3, x=P, **ptrs):
     a = {k: P for k in STATE + ("S2", "G2", "H2")}
     a.update(ptrs)
-    return _msg(_lib.load().mvx_flex_lm_step(handle, B, T, have_trial, lam_down, lam_up, max_dropped, *(a[k] for k in STATE), a["S2"],
-                                             a["G2"], a["H2"], x, None))
+    return call(_lib.load().mvx_flex_lm_step, handle, B, T, have_trial, lam_down, lam_up, max_dropped, *(a[k] for k in STATE), a["S2"],
+                a["G2"], a["H2"], x, None)
 
 
 @pytest.mark.parametrize("kw, words", [(dict(B=-1), "B must be >= 0"), (dict(T=-1), "T must be 0 ... 32"), (dict(T=33), "T must be 0 ... 32")]

@@ -1,6 +1,5 @@
 """The backward pass without a GPU: the C ABI entry (mvx_backward_batch), the checks it makes before it touches a device, the
 `differentiable` option's validation and the gradient kernels' register use read from mvx_grad.o."""
-import ctypes as C
 import os
 import shutil
 import subprocess
@@ -9,9 +8,9 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, VERSION, call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
 
 
 def test_header_compiles_as_c99_with_the_backward_prototype(tmp_path):
@@ -35,22 +34,13 @@ def test_header_compiles_as_c99_with_the_backward_prototype(tmp_path):
     exe = tmp_path / "bwd"
     libdir = os.path.dirname(_lib.LIB_PATH)
     subprocess.check_call([gcc, str(obj), "-L", libdir, "-lmvx_hip", f"-Wl,-rpath,{libdir}", "-o", str(exe)])
-    assert subprocess.check_output([str(exe)]).decode().split() == [str(MVX_ERR_INVALID), "140"]
-
-
-def test_library_exports_the_backward_entry():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_backward_batch") and "mvx_backward_batch" in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    assert C.sizeof(_lib.MvxConfig) == 40 and C.sizeof(_lib.MvxXform) == 80
+    assert subprocess.check_output([str(exe)]).decode().split() == [str(MVX_ERR_INVALID), str(VERSION)]
 
 
 def _call(mode=0, B=1, C_=4, offsets=(0, 3), grad_coords=1, grad_features=None, radii_type=0, handle=None):
-    lib = _lib.load()
     off = np.asarray(offsets, np.int64)
-    rc = lib.mvx_backward_batch(handle, mode, 16, 16, None, 1.0, radii_type, off.ctypes.data, None, B, C_, 16,
-                                grad_coords, grad_features, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_backward_batch, handle, mode, 16, 16, None, 1.0, radii_type, off.ctypes.data, None, B, C_, 16,
+                grad_coords, grad_features, None)
 
 
 @pytest.mark.parametrize("kw, words", [

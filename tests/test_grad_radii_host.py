@@ -9,18 +9,10 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "molvoxel_amd", "csrc")
-MVX_ERR_INVALID = -1
-
-
-def test_library_exports_the_radii_entry():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_backward_radii_batch") and "mvx_backward_radii_batch" in _lib.SIGNATURES
-    with open(os.path.join(ROOT, "include", "mvx.h")) as fh:
-        assert "int mvx_backward_radii_batch(" in fh.read()
-    assert lib.mvx_version() == 140
 
 
 def test_header_compiles_as_c99_with_the_radii_prototype(tmp_path):
@@ -49,11 +41,9 @@ def test_header_compiles_as_c99_with_the_radii_prototype(tmp_path):
 
 
 def _call(mode=0, B=1, C_=4, offsets=(0, 3), grad_coords=None, grad_features=None, grad_radii=16, radii_type=1, handle=None):
-    lib = _lib.load()
     off = np.asarray(offsets, np.int64)
-    rc = lib.mvx_backward_radii_batch(handle, mode, 16, 16, 16, 1.0, radii_type, off.ctypes.data, None, B, C_, 16,
-                                      grad_coords, grad_features, grad_radii, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_backward_radii_batch, handle, mode, 16, 16, 16, 1.0, radii_type, off.ctypes.data, None, B, C_, 16,
+                grad_coords, grad_features, grad_radii, None)
 
 
 @pytest.mark.parametrize("kw, words", [

@@ -30,12 +30,12 @@ import numpy as np
 import pytest
 
 from tests import batch_cut_rows as R
+from tests.abi import MVX_ERR_ALLOC
 from tests.tolerance import GAUSS_TOL, P64_TOL, assert_gaussian
 
 pytestmark = pytest.mark.gpu
 
 TRANSLATION = 0.7
-MVX_ERR_ALLOC = -4  # include/mvx.h
 
 
 def _voxelizer(case, options=True):

@@ -41,8 +41,10 @@ import pytest
 
 from tests import dead_atom_rows as R
 from tests import density_reference as dref
+from tests import entry_drivers as X
 from tests import entry_fuzz_rows as E
 from tests import grad_reference as gr
+from tests import hip_support as hip
 from tests import moments_grad_reference as MG
 from tests import moments_reference as MR
 from tests import pose_reference as pr
@@ -52,7 +54,7 @@ from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL, P64_TOL,
 pytestmark = pytest.mark.gpu
 
 BF16_HALF_ULP = 2.0 ** -8  # (tests/test_hip_sum.py: the final rounding of a bfloat16 field gradient)
-_WORST, _CASES = {}, {}
+_W = X.Worst()  # entry -> worst error / bar, and the cases
 POSE_KEYS = (("center", "cen"), ("quaternion", "q"), ("translation", "t"))
 
 ALL = R.ROW_IDS
@@ -64,120 +66,15 @@ SUMMED = [i for i in ALL if R.ROWS[i][3] != "f64" and R.ROWS[i][7] == "d16" and 
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    print("\n" + "\n".join(f"{k:>28s}: worst error / bar {v:.3g} over {_CASES[k]} cases" for k, v in sorted(_WORST.items())))
+    print("\n" + "\n".join(f"{k:>28s}: worst error / bar {v:.3g} over {_W.cases[k]} cases" for k, v in sorted(_W.worst.items())))
 
 
-def _note(entry, ratio):
-    _WORST[entry] = max(_WORST.get(entry, 0.0), float(ratio))
-    _CASES[entry] = _CASES.get(entry, 0) + 1
+_note = _W.note
 
 
 def _close(entry, d, got, ref, bound, what, exact_terms=False):
-    """The gradient rule with the bars of the row's precision (tests/test_hip_entry_fuzz.py's _close)."""
-    rel, abs_ = (GRAD64_REL, GRAD64_ABS) if (d["precision"] == 64 or exact_terms) else (GRAD_REL, GRAD_ABS)
-    _note(entry, gr.close(np.asarray(got, np.float64), ref, bound, f"{d['seed']}: {what}", rel, abs_))
-
-
-def _vox(d, kind=None, **kw):
-    import molvoxel_amd as mv
-
-    kind = kind or d["kind"]
-    extra = {} if d["blockdim"] is None else {"blockdim": d["blockdim"]}
-    if kind == "bf16":
-        extra["grid_dtype"] = "bfloat16"
-    kw.setdefault("sigma", d["sigma"])
-    return mv.create_voxelizer(d["res"], d["D"], d["radii_type"], d["density"], library="hip", precision=64 if kind == "f64" else 32,
-                               **extra, **kw)
-
-
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
-
-
-def _nan(shape, dt=None):
-    import torch
-
-    return torch.full(shape, float("nan"), dtype=dt or torch.float64, device="cuda")
-
-
-def _ptr(x):
-    return None if x is None else x.data_ptr()
-
-
-def _nc(d):
-    return d["C"] if d["mode"] == "types" else None
-
-
-def _grid_dtype(d):
-    import torch
-
-    return {"f32": torch.float32, "bf16": torch.bfloat16, "f64": torch.float64}[d["kind"]]
-
-
-def _inputs(d, grad=False, radii_grad=False, host=False):
-    """The inputs of a batch on the device (host: as numpy arrays). grad: coordinates, features, centres and poses are leaves;
-    radii_grad: the radii too (a scalar radius as a one-element host tensor)."""
-    import torch
-
-    conv = (lambda x, g=False: x) if host else _dev
-    radii = d["radii"]
-    if radii_grad and np.isscalar(radii):
-        radii = torch.tensor([radii], dtype=torch.float64, requires_grad=True)
-    else:
-        radii = conv(radii, radii_grad)
-    return dict(xyz=conv(d["xyz"], grad), cen=conv(d["cen"], grad), chan=conv(d["chan"], grad and d["mode"] == "features"), radii=radii,
-                q=conv(d["q"], grad and d["posed"]), t=conv(d["t"], grad and d["posed"]))
-
-
-def _rot(d):
-    """The seeded random rotation of a row that has one: the same quaternions for the dirty and the clean batch."""
-    if "transform" in d and not d["posed"]:
-        np.random.seed(d["transform"])
-        return dict(random_rotation=True)
-    return {}
-
-
-def _forward(vox, d, a, **kw):
-    if d["posed"]:
-        return vox.forward_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=_nc(d), **kw)
-    return vox.forward_batch(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], num_channels=_nc(d), **_rot(d), **kw)
-
-
-def _score(vox, d, a, F, per_atom=False):
-    if d["posed"]:
-        return vox.score_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], F, num_channels=_nc(d),
-                                     per_atom=per_atom)
-    return vox.score_batch(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], F, num_channels=_nc(d), per_atom=per_atom, **_rot(d))
-
-
-def _sum(vox, d, a, weights=None):
-    if d["posed"]:
-        return vox.forward_posed_sum(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], weights=weights,
-                                     num_channels=_nc(d))
-    return vox.forward_sum(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], weights=weights, num_channels=_nc(d), **_rot(d))
-
-
-def _moments(vox, d, a, target=None):
-    if d["posed"]:
-        return vox.moments_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], target=target,
-                                       num_channels=_nc(d))
-    return vox.moments_batch(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], target=target, num_channels=_nc(d), **_rot(d))
-
-
-def _spec(vox, d, a):
-    """The call record as the Python layer builds it for the library."""
-    import torch
-
-    with torch.no_grad():
-        if d["posed"]:
-            return vox._batch_call(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], _nc(d), posed=(a["q"], a["t"]), device=True)
-        if _rot(d):
-            return vox._batch_call(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], _nc(d), 0.0, True, device=True)
-        return vox._batch_call(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], _nc(d), device=True)
+    """The gradient rule with the bars of the row's precision; the worst error / bar goes into the report under `entry`."""
+    _W.close(entry, d, got, ref, bound, f"{d['seed']}: {what}", exact_terms)
 
 
 def _pair(row_id):
@@ -192,7 +89,7 @@ def _field(d):
     import torch
 
     Fref = E.field_of(d)
-    return torch.tensor(Fref, device="cuda").to(_grid_dtype(d)), Fref
+    return torch.tensor(Fref, device="cuda").to(hip.grid_dtype(d)), Fref
 
 
 def _upstream(d, F):
@@ -258,17 +155,17 @@ def test_grids_of_the_dirty_batch_are_the_clean_batchs(row_id, direct):
     import torch
 
     r, d, c, live = _pair(row_id)
-    vox = _vox(d)
+    vox = X.vox(d)
     vox.debug_option("direct", direct)
-    got, want = _forward(vox, d, _inputs(d)), _forward(vox, c, _inputs(c))
-    assert got.dtype == _grid_dtype(d) and tuple(got.shape) == (d["B"], d["C"]) + (d["D"],) * 3
+    got, want = X.forward(vox, d, X.inputs(d)), X.forward(vox, c, X.inputs(c))
+    assert got.dtype == hip.grid_dtype(d) and tuple(got.shape) == (d["B"], d["C"]) + (d["D"],) * 3
     assert torch.equal(got, want), f"{int((got != want).sum())} voxels differ"
     for b, n in enumerate(R.LIVE):
         assert bool(got[b].any()) == (n > 0), b  # the all-dead molecule and the empty one: zeros
     if direct:
         return
     if d["kind"] == "bf16":  # a bfloat16 grid is the float32 grid rounded once (tests/test_hip_bf16.py); that one meets the oracle
-        base = _forward(_vox(d, "f32"), c, _inputs(c))
+        base = X.forward(X.vox(d, "f32"), c, X.inputs(c))
         assert torch.equal(want, base.to(torch.bfloat16))
         want = base
     want = want.cpu().numpy()
@@ -288,27 +185,27 @@ def test_grids_in_other_layouts_from_host_arrays_and_in_molecule_chunks(row_id, 
     import torch
 
     r, d, c, live = _pair(row_id)
-    base = _forward(_vox(d), c, _inputs(c))
+    base = X.forward(X.vox(d), c, X.inputs(c))
     if variant == "channels_last":
-        vox = _vox(d, grid_layout="channels_last")
-        got, want = _forward(vox, d, _inputs(d)), _forward(vox, c, _inputs(c))
+        vox = X.vox(d, grid_layout="channels_last")
+        got, want = X.forward(vox, d, X.inputs(d)), X.forward(vox, c, X.inputs(c))
         assert got.is_contiguous(memory_format=torch.channels_last_3d)
     elif variant == "numpy":
-        vox = _vox(d, "f32", output="numpy")
-        got, want = _forward(vox, d, _inputs(d, host=True)), _forward(vox, c, _inputs(c, host=True))
+        vox = X.vox(d, "f32", output="numpy")
+        got, want = X.forward(vox, d, X.inputs(d, host=True)), X.forward(vox, c, X.inputs(c, host=True))
         assert isinstance(got, np.ndarray)
         got, want = torch.tensor(got, device="cuda"), torch.tensor(want, device="cuda")
-        base = _forward(_vox(d, "f32"), c, _inputs(c))
+        base = X.forward(X.vox(d, "f32"), c, X.inputs(c))
     else:
-        vox = _vox(d)
+        vox = X.vox(d)
         vox.debug_option("direct", 0)
         # a cache budget of 16 KB cuts these five molecules into several launches (mvx_plan.hip: ceil(workspace / budget) chunks,
         # at most one per molecule). tests/test_hip_batch_cuts.py uses this option and "chunks", which cuts only batches of
         # 4 x chunks molecules or more - eight for two chunks, and the rows have five.
         vox.debug_option("mall_budget_kb", 16)
-        got = _forward(vox, d, _inputs(d))
+        got = X.forward(vox, d, X.inputs(d))
         assert 2 <= vox.last_plan()["nchunk"] <= d["B"]  # cut into several launches, the all-dead molecule in one of them
-        want = _forward(vox, c, _inputs(c))
+        want = X.forward(vox, c, X.inputs(c))
     assert torch.equal(got, want) and torch.equal(got, base)
     _note("grids", 0.0)
 
@@ -321,14 +218,14 @@ def test_summed_grids_of_the_dirty_batch_are_the_clean_batchs(row_id):
     from oracle import c_oracle
 
     r, d, c, live = _pair(row_id)
-    vox = _vox(d)
+    vox = X.vox(d)
     rng = np.random.default_rng(r["fseed"] + 5)
     wb = rng.uniform(0.5, 1.5, d["B"]).astype(np.float32)
     wa = rng.uniform(0.5, 1.5, d["N"]).astype(np.float32)
     wa[~R.live(r)] = np.nan  # the dead atoms' weights are NaN
     plain = None
     for name, wd, wc in (("none", None, None), ("molecule", wb, wb), ("atom", wa, wa[R.live(r)])):
-        got, want = _sum(vox, d, _inputs(d), _dev(wd)), _sum(vox, c, _inputs(c), _dev(wc))
+        got, want = X.sum(vox, d, X.inputs(d), hip.dev(wd)), X.sum(vox, c, X.inputs(c), hip.dev(wc))
         assert got.dtype == torch.float32 and not bool(torch.isnan(got).any()), name
         assert torch.equal(got, want), (name, int((got != want).sum()))
         assert bool(got.any())
@@ -354,8 +251,8 @@ def _entry(vox, call, gm, target):
 
     g = torch.tensor(np.ascontiguousarray(gm, np.float64), device="cuda")
     assert tuple(g.shape) == (call.B, call.C, 2 if target is None else 3)
-    gc, gf = _nan((call.N, 3)), (_nan((call.N, call.C), torch.float32) if call.mode == "features" else None)
-    _lib.check(vox._lib.mvx_moments_backward_batch(*call.batch_args(vox), _ptr(target), g.data_ptr(), gc.data_ptr(), _ptr(gf),
+    gc, gf = hip.nan((call.N, 3)), (hip.nan((call.N, call.C), torch.float32) if call.mode == "features" else None)
+    _lib.check(vox._lib.mvx_moments_backward_batch(*call.batch_args(vox), hip.ptr(target), g.data_ptr(), gc.data_ptr(), hip.ptr(gf),
                                                    vox._stream()))
     return gc, gf
 
@@ -369,13 +266,13 @@ def test_moments_and_their_gradient_rows(row_id):
     import torch
 
     r, d, c, live = _pair(row_id)
-    vox = _vox(d)
-    T = _dev(_target(c))
-    ad, ac = _inputs(d), _inputs(c)
-    g32 = _forward(_vox(c, "f32"), c, ac).cpu().numpy()
+    vox = X.vox(d)
+    T = hip.dev(_target(c))
+    ad, ac = X.inputs(d), X.inputs(c)
+    g32 = X.forward(X.vox(c, "f32"), c, ac).cpu().numpy()
     ref, bnd = MR.moments_and_bound(g32, _target(c))
     for t, K in ((None, 2), (T, 3)):
-        got, want = _moments(vox, d, ad, t), _moments(vox, c, ac, t)
+        got, want = X.moments(vox, d, ad, t), X.moments(vox, c, ac, t)
         assert got.dtype == torch.float64 and torch.equal(got, want), K
         g = got.cpu().numpy()
         err, b = np.abs(g - ref[..., :K]), bnd[..., :K]
@@ -385,7 +282,7 @@ def test_moments_and_their_gradient_rows(row_id):
     # mvx_moments_backward_batch: per-atom rows in buffers that start as NaN
     p, quats = _reference(row_id)["p"], _reference(row_id)["quats"]
     w, types = E.reference_channels(c)
-    sd, sc = _spec(vox, d, ad), _spec(vox, c, ac)
+    sd, sc = X.spec(vox, d, ad), X.spec(vox, c, ac)
     for K in (3, 2):
         gm = np.random.default_rng(r["fseed"] + K).standard_normal((d["B"], d["C"], K))
         (gcd, gfd), (gcc, gfc) = _entry(vox, sd, gm, T if K == 3 else None), _entry(vox, sc, gm, T if K == 3 else None)
@@ -417,17 +314,17 @@ def _abi_rows(vox, d, Fd, G=None):
 
     from molvoxel_amd.voxelizer.hip import _lib
 
-    call = _spec(vox, d, _inputs(d))
+    call = X.spec(vox, d, X.inputs(d))
     B, N, C_ = call.B, call.N, call.C
     fdt = torch.float64 if d["kind"] == "f64" else torch.float32
     feat = d["mode"] == "features"
-    out = dict(scores=_nan((B,)), atoms=_nan((N,)), gc=_nan((N, 3)), gf=_nan((N, C_), fdt) if feat else None)
+    out = dict(scores=hip.nan((B,)), atoms=hip.nan((N,)), gc=hip.nan((N, 3)), gf=hip.nan((N, C_), fdt) if feat else None)
     stride = 0 if Fd.dim() == 4 else C_ * d["D"] ** 3
-    _lib.check(vox._lib.mvx_score_batch(*call.batch_args(vox), Fd.data_ptr(), stride, _ptr(out["scores"]), _ptr(out["atoms"]),
-                                        _ptr(out["gc"]), _ptr(out["gf"]), vox._stream()))
+    _lib.check(vox._lib.mvx_score_batch(*call.batch_args(vox), Fd.data_ptr(), stride, hip.ptr(out["scores"]), hip.ptr(out["atoms"]),
+                                        hip.ptr(out["gc"]), hip.ptr(out["gf"]), vox._stream()))
     G = _upstream(d, Fd) if G is None else G
-    ref = dict(gc=_nan((N, 3)), gf=_nan((N, C_), fdt) if feat else None)
-    _lib.check(vox._lib.mvx_backward_batch(*call.batch_args(vox), G.data_ptr(), _ptr(ref["gc"]), _ptr(ref["gf"]), vox._stream()))
+    ref = dict(gc=hip.nan((N, 3)), gf=hip.nan((N, C_), fdt) if feat else None)
+    _lib.check(vox._lib.mvx_backward_batch(*call.batch_args(vox), G.data_ptr(), hip.ptr(ref["gc"]), hip.ptr(ref["gf"]), vox._stream()))
     torch.cuda.synchronize()
     return out, ref
 
@@ -442,11 +339,11 @@ def test_scores_their_rows_and_the_backward_entry(row_id):
     import torch
 
     r, d, c, live = _pair(row_id)
-    vox = _vox(d)
+    vox = X.vox(d)
     Fd, _ = _field(c)
     ref = _reference(row_id)
-    Sd, sd = _score(vox, d, _inputs(d), Fd, per_atom=True)
-    Sc, sc = _score(vox, c, _inputs(c), Fd, per_atom=True)
+    Sd, sd = X.score(vox, d, X.inputs(d), Fd, per_atom=True)
+    Sc, sc = X.score(vox, c, X.inputs(c), Fd, per_atom=True)
     _same_rows(sd, sc, live, "atom scores")
     assert bool(torch.isfinite(Sd).all())
     exact = c["density"] == "binary" and c["mode"] != "features"
@@ -480,17 +377,17 @@ def test_the_field_gradient_of_the_dirty_batch_is_the_clean_batchs(row_id):
     import torch
 
     r, d, c, live = _pair(row_id)
-    vox = _vox(d, differentiable=True, field_grad=True)
+    vox = X.vox(d, differentiable=True, field_grad=True)
     Fd, _ = _field(c)
     g = np.random.default_rng(r["fseed"] + 1).standard_normal(d["B"])
     grads = []
     for x in (d, c):
         field = Fd.clone().requires_grad_()
-        (_score(vox, x, _inputs(x), field) * _dev(g)).sum().backward()
+        (X.score(vox, x, X.inputs(x), field) * hip.dev(g)).sum().backward()
         grads.append(field.grad)
     assert grads[0].dtype == Fd.dtype and not bool(torch.isnan(grads[0]).any())
     assert torch.equal(grads[0], grads[1]), int((grads[0] != grads[1]).sum())
-    grids = _forward(_vox(c, "f32"), c, _inputs(c)).to(torch.float64)
+    grids = X.forward(X.vox(c, "f32"), c, X.inputs(c)).to(torch.float64)
     gw = torch.tensor(g, device="cuda").reshape(-1, 1, 1, 1, 1)
     want, bound = (gw * grids).sum(0).cpu().numpy(), (gw.abs() * grids.abs()).sum(0).cpu().numpy()
     err = np.abs(grads[0].to(torch.float64).cpu().numpy() - want)
@@ -508,14 +405,14 @@ def _backward(row_id, d, entry, upstream=None):
     sigma = torch.tensor(d["sigma"], dtype=torch.float64, requires_grad=True)
     grid_entry = entry == "grid"
     kw = dict(radii_grad=True, sigma_grad=True, sigma=sigma) if grid_entry else {}
-    vox = _vox(d, differentiable=True, **kw)
-    a = _inputs(d, grad=True, radii_grad=grid_entry)
+    vox = X.vox(d, differentiable=True, **kw)
+    a = X.inputs(d, grad=True, radii_grad=grid_entry)
     Fd, _ = _field(d)
     if grid_entry:
-        grid = _forward(vox, d, a)
+        grid = X.forward(vox, d, a)
         grid.backward(gradient=_upstream(d, Fd) if upstream is None else upstream)
     else:
-        _score(vox, d, a, Fd).sum().backward()
+        X.score(vox, d, a, Fd).sum().backward()
     a["sigma"] = sigma
     return a
 
@@ -587,13 +484,13 @@ def test_backward_through_the_posed_moments(row_id):
     import torch
 
     r, d, c, live = _pair(row_id)
-    vox = _vox(d, differentiable=True, moments_grad=True)
-    T = _dev(_target(c))
+    vox = X.vox(d, differentiable=True, moments_grad=True)
+    T = hip.dev(_target(c))
     gm = torch.tensor(np.random.default_rng(r["fseed"] + 3).standard_normal((d["B"], d["C"], 3)), device="cuda")
     out = []
     for x in (d, c):
-        a = _inputs(x, grad=True)
-        m = _moments(vox, x, a, T)
+        a = X.inputs(x, grad=True)
+        m = X.moments(vox, x, a, T)
         assert m.requires_grad
         (m * gm).sum().backward()
         out.append(a)
@@ -601,7 +498,7 @@ def test_backward_through_the_posed_moments(row_id):
     _same_rows(got["xyz"].grad, want["xyz"].grad, live, "moments: coords.grad")
     if c["mode"] == "features":
         _same_rows(got["chan"].grad, want["chan"].grad, live, "moments: features.grad")
-    g32 = _forward(_vox(c, "f32"), c, _inputs(c)).cpu().numpy()
+    g32 = X.forward(X.vox(c, "f32"), c, X.inputs(c)).cpu().numpy()
     p, quats = _reference(row_id)["p"], _reference(row_id)["quats"]
     w, types = E.reference_channels(c)
     for b in range(c["B"]):
@@ -631,7 +528,7 @@ def _cloud_pair(cloud_id):
 
 
 def _view_args(x, grad=False):
-    return (_dev(x["xyz"], grad), _dev(x["cen"], grad), _dev(x["q"], grad), _dev(x["t"], grad), _dev(x["chan"]), _dev(x["radii"]))
+    return (hip.dev(x["xyz"], grad), hip.dev(x["cen"], grad), hip.dev(x["q"], grad), hip.dev(x["t"], grad), hip.dev(x["chan"]), hip.dev(x["radii"]))
 
 
 def _radius_dead(c):
@@ -646,20 +543,20 @@ def test_views_of_a_cloud_with_dead_atoms(cloud_id):
     from tests import views_reference as vr
 
     c, d, k, live = _cloud_pair(cloud_id)
-    vox = _vox(d)
-    nc = _nc(d)
+    vox = X.vox(d)
+    nc = hip.nc(d)
     got, want = vox.forward_posed_views(*_view_args(d), num_channels=nc), vox.forward_posed_views(*_view_args(k), num_channels=nc)
     assert torch.equal(got, want) and all(bool(want[b].any()) for b in range(c["B"]))
     rep = R.repeated(d)
-    assert torch.equal(got, _forward(vox, rep, _inputs(rep)))  # ... and forward_posed_batch on the repeated dirty cloud
+    assert torch.equal(got, X.forward(vox, rep, X.inputs(rep)))  # ... and forward_posed_batch on the repeated dirty cloud
     if d["precision"] == 32 and not (d["mode"] == "features" and d["radii_type"] == "channel-wise"):
-        w = _dev(np.random.default_rng(c["fseed"]).uniform(0.5, 1.5, c["B"]).astype(np.float32))
+        w = hip.dev(np.random.default_rng(c["fseed"]).uniform(0.5, 1.5, c["B"]).astype(np.float32))
         for weights in (None, w):
             sd = vox.forward_posed_views_sum(*_view_args(d), weights=weights, num_channels=nc)
             sk = vox.forward_posed_views_sum(*_view_args(k), weights=weights, num_channels=nc)
             assert torch.equal(sd, sk) and bool(sd.any()) and not bool(torch.isnan(sd).any())
     # the same under identity views (forward_views / forward_views_sum: the cloud seen from each centre)
-    plain = lambda x: (_dev(x["xyz"]), _dev(x["cen"]), _dev(x["chan"]), _dev(x["radii"]))  # noqa: E731
+    plain = lambda x: (hip.dev(x["xyz"]), hip.dev(x["cen"]), hip.dev(x["chan"]), hip.dev(x["radii"]))  # noqa: E731
     gv, wv = vox.forward_views(*plain(d), num_channels=nc), vox.forward_views(*plain(k), num_channels=nc)
     assert torch.equal(gv, wv) and bool(wv.any())
     if d["precision"] == 32 and not (d["mode"] == "features" and d["radii_type"] == "channel-wise"):
@@ -699,7 +596,7 @@ def test_views_of_a_cloud_with_dead_atoms(cloud_id):
 
     # score_posed_views: scores, atom scores in selection order, and - through autograd - the rows reduced onto the shared cloud
     Fd, Fref = _field(d)
-    dvox = _vox(d, differentiable=True)
+    dvox = X.vox(d, differentiable=True)
     res = []
     for x in (d, k):
         a = _view_args(x, grad=True)
@@ -744,15 +641,15 @@ def test_posed_views_and_the_posed_batch_on_the_repeated_dirty_cloud_agree(cloud
     import torch
 
     c, d, k, live = _cloud_pair(cloud_id)
-    vox = _vox(d, differentiable=True)
+    vox = X.vox(d, differentiable=True)
     Fd, _ = _field(d)
-    nc = _nc(d)
+    nc = hip.nc(d)
     a = _view_args(d, grad=True)
     S = vox.score_posed_views(*a, Fd, num_channels=nc)
     S.sum().backward()
     rep = R.repeated(d)
-    b_ = _inputs(rep, grad=True)
-    S2, s2 = _score(vox, rep, b_, Fd, per_atom=True)
+    b_ = X.inputs(rep, grad=True)
+    S2, s2 = X.score(vox, rep, b_, Fd, per_atom=True)
     S2.sum().backward()
     # (tests/test_hip_score_views.py's rule: dropping the zero rows of the atoms a view does not keep regroups a float64 sum)
     bound = s2.detach().abs().reshape(c["B"], d["N"]).sum(1)
@@ -791,15 +688,15 @@ def test_a_molecule_with_a_non_finite_pose_contributes_nothing(row_id, where):
     others = [m for m in range(c["B"]) if m != b]
     mine = torch.zeros(c["N"], dtype=torch.bool, device="cuda")
     mine[lo:hi] = True
-    vox = _vox(c)
+    vox = X.vox(c)
     Fd, _ = _field(c)
-    got, want = _forward(vox, bad, _inputs(bad)), _forward(vox, c, _inputs(c))
+    got, want = X.forward(vox, bad, X.inputs(bad)), X.forward(vox, c, X.inputs(c))
     assert not bool(got[b].any()) and torch.equal(got[others], want[others]) and bool(want[b].any())
-    (Sg, sg), (Sw, sw) = _score(vox, bad, _inputs(bad), Fd, per_atom=True), _score(vox, c, _inputs(c), Fd, per_atom=True)
+    (Sg, sg), (Sw, sw) = X.score(vox, bad, X.inputs(bad), Fd, per_atom=True), X.score(vox, c, X.inputs(c), Fd, per_atom=True)
     assert float(Sg[b]) == 0.0 and torch.equal(Sg[others], Sw[others]) and float(Sw[b]) != 0.0
     assert not bool(sg[mine].any()) and torch.equal(sg[~mine], sw[~mine])
     if c["precision"] == 32:
-        mg, mw = _moments(vox, bad, _inputs(bad), _dev(_target(c))), _moments(vox, c, _inputs(c), _dev(_target(c)))
+        mg, mw = X.moments(vox, bad, X.inputs(bad), hip.dev(_target(c))), X.moments(vox, c, X.inputs(c), hip.dev(_target(c)))
         assert not bool(mg[b].any()) and torch.equal(mg[others], mw[others]) and bool(mw[b].any())
     (gb, bb), (gw, bw) = _abi_rows(vox, bad, Fd), _abi_rows(vox, c, Fd)
     for k in ("gc", "gf"):
@@ -808,9 +705,9 @@ def test_a_molecule_with_a_non_finite_pose_contributes_nothing(row_id, where):
                 assert not bool(x[mine].any()) and torch.equal(x[~mine], y[~mine]) and bool(y[mine].any()), k
     if c["precision"] == 32:  # mvx_moments_backward_batch: the same walk, the same guard
         gm = np.random.default_rng(r["fseed"] + 3).standard_normal((c["B"], c["C"], 3))
-        T = _dev(_target(c))
-        rows_bad = _entry(vox, _spec(vox, bad, _inputs(bad)), gm, T)
-        rows_ok = _entry(vox, _spec(vox, c, _inputs(c)), gm, T)
+        T = hip.dev(_target(c))
+        rows_bad = _entry(vox, X.spec(vox, bad, X.inputs(bad)), gm, T)
+        rows_ok = _entry(vox, X.spec(vox, c, X.inputs(c)), gm, T)
         for x, y in zip(rows_bad, rows_ok):
             if x is not None:
                 assert not bool(x[mine].any()) and torch.equal(x[~mine], y[~mine]) and bool(y[mine].any())
@@ -870,8 +767,8 @@ def test_a_non_finite_upstream_where_no_atom_reaches_changes_nothing(row_id):
     # the score entries with such a field: per molecule where the row's field is, else the voxels no molecule reaches
     Fp = torch.where(hole if Fd.dim() == 5 else hole.all(dim=0), poison, Fd)
     assert int(torch.isnan(Fp).sum()) > 100
-    vox = _vox(c)
-    (S1, s1), (S2, s2) = _score(vox, c, _inputs(c), Fp, per_atom=True), _score(vox, c, _inputs(c), Fd, per_atom=True)
+    vox = X.vox(c)
+    (S1, s1), (S2, s2) = X.score(vox, c, X.inputs(c), Fp, per_atom=True), X.score(vox, c, X.inputs(c), Fd, per_atom=True)
     assert torch.equal(S1, S2) and torch.equal(s1, s2)
     (g1, _), (g2, _) = _abi_rows(vox, c, Fp), _abi_rows(vox, c, Fd)
     for k in ("scores", "atoms", "gc", "gf"):

@@ -29,40 +29,41 @@ import os
 import numpy as np
 import pytest
 
+from tests import entry_drivers as X
 from tests import entry_fuzz_rows as E
 from tests import grad_reference as gr
+from tests import hip_support as hip
 from tests import moments_grad_reference as MG
 from tests import moments_reference as MR
 from tests import pose_reference as pr
 from tests import score_reference as sr
 from tests import sum_sweep_rows as S
-from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL, P64_TOL, assert_exact, assert_gaussian
+from tests.tolerance import GRAD_ABS, GRAD_REL, P64_TOL, assert_exact, assert_gaussian
 
 pytestmark = pytest.mark.gpu
 
 BF16_HALF_ULP = 2.0 ** -8  # (tests/test_hip_sum.py: the final rounding of a bfloat16 field gradient)
-_WORST = {}  # (output kind, grid kind) -> worst error / bar over the sweep
+_W = X.Worst()  # (output kind, grid kind) -> worst error / bar over the sweep
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _report():
     yield
-    lines = [f"{k[0]:>16s} {k[1]:>4s}: worst error / bar {v:.3g}" for k, v in sorted(_WORST.items())]
+    lines = [f"{k[0]:>16s} {k[1]:>4s}: worst error / bar {v:.3g}" for k, v in sorted(_W.worst.items())]
     print("\n" + "\n".join(lines))
     path = os.environ.get("MVX_ENTRY_FUZZ_REPORT")
     if path:
         with open(path, "w") as fh:
-            json.dump({f"{k[0]} {k[1]}": v for k, v in sorted(_WORST.items())}, fh, indent=1)
+            json.dump({f"{k[0]} {k[1]}": v for k, v in sorted(_W.worst.items())}, fh, indent=1)
 
 
 def _note(kind, grid, ratio):
-    _WORST[(kind, grid)] = max(_WORST.get((kind, grid), 0.0), float(ratio))
+    _W.note((kind, grid), ratio)
 
 
 def _close(kind, d, got, ref, bound, what, exact_terms=False):
     """The gradient rule with the bars of the draw's precision; the worst error / bar goes into the report."""
-    rel, abs_ = (GRAD64_REL, GRAD64_ABS) if (d["precision"] == 64 or exact_terms) else (GRAD_REL, GRAD_ABS)
-    _note(kind, d["kind"], gr.close(got, ref, bound, f"{_tag(d)}: {what}", rel, abs_))
+    _W.close((kind, d["kind"]), d, got, ref, bound, f"{_tag(d)}: {what}", exact_terms)
 
 
 def _tag(d):
@@ -71,94 +72,14 @@ def _tag(d):
     return {k: d[k] for k in keys if k in d}
 
 
-def _vox(d, kind=None, **kw):
-    import molvoxel_amd as mv
-
-    kind = kind or d["kind"]
-    extra = {} if d["blockdim"] is None else {"blockdim": d["blockdim"]}
-    if kind == "bf16":
-        extra["grid_dtype"] = "bfloat16"
-    return mv.create_voxelizer(d["res"], d["D"], d["radii_type"], d["density"], library="hip", sigma=d["sigma"],
-                               precision=64 if kind == "f64" else 32, **extra, **kw)
-
-
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
-
-
-def _nan(shape, dt=None):
-    import torch
-
-    return torch.full(shape, float("nan"), dtype=dt or torch.float64, device="cuda")
-
-
-def _ptr(x):
-    return None if x is None else x.data_ptr()
-
-
-def _nc(d):
-    return d["C"] if d["mode"] == "types" else None
-
-
-def _grid_dtype(d):
-    import torch
-
-    return {"f32": torch.float32, "bf16": torch.bfloat16, "f64": torch.float64}[d["kind"]]
-
-
 def _field(d):
     """(the field on the device in the grid's type, the float64 array the kernel reads): the same values."""
     import torch
 
     Fref = E.field_of(d)
-    Fd = torch.tensor(Fref, device="cuda").to(_grid_dtype(d))
+    Fd = torch.tensor(Fref, device="cuda").to(hip.grid_dtype(d))
     assert torch.equal(Fd.to(torch.float64).cpu(), torch.tensor(Fref))  # (the host's rounding is the device type's)
     return Fd, Fref
-
-
-def _inputs(d, grad=False):
-    """The device inputs of a draw; grad: coordinates, features, centres and - posed - quaternions and translations are leaves."""
-    a = dict(xyz=_dev(d["xyz"], grad), cen=_dev(d["cen"], grad), chan=_dev(d["chan"], grad and d["mode"] == "features"),
-             radii=_dev(d["radii"]))
-    if d["posed"]:
-        a.update(q=_dev(d["q"], grad), t=_dev(d["t"], grad))
-    return a
-
-
-def _score(vox, d, a, F, per_atom=False):
-    if d["posed"]:
-        return vox.score_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], F, num_channels=_nc(d),
-                                     per_atom=per_atom)
-    np.random.seed(d["transform"])
-    return vox.score_batch(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], F, num_channels=_nc(d), random_rotation=True,
-                           per_atom=per_atom)
-
-
-def _forward(vox, d, a):
-    """The grids of a draw: forward_posed_batch, forward_batch with the draw's seeded rotation (walk draws), or forward_batch."""
-    if d["posed"]:
-        return vox.forward_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=_nc(d))
-    if "transform" in d:
-        np.random.seed(d["transform"])
-        return vox.forward_batch(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], num_channels=_nc(d), random_rotation=True)
-    return vox.forward_batch(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], num_channels=_nc(d))
-
-
-def _spec(vox, d, a):
-    """The call record as the Python layer builds it for the library (offsets, records, converted arrays)."""
-    import torch
-
-    with torch.no_grad():
-        if d["posed"]:
-            return vox._batch_call(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], _nc(d), posed=(a["q"], a["t"]), device=True)
-        if "transform" in d:
-            np.random.seed(d["transform"])
-            return vox._batch_call(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], _nc(d), 0.0, True, device=True)
-        return vox._batch_call(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], _nc(d), device=True)
 
 
 def _reference_kw(d):
@@ -173,11 +94,11 @@ def _sample(d):
 def _check_scores(d, vox, Fd, Fref, p):
     import torch
 
-    a = _inputs(d)
-    scores, atoms = _score(vox, d, a, Fd, per_atom=True)
+    a = X.inputs(d)
+    scores, atoms = X.score(vox, d, a, Fd, per_atom=True)
     assert scores.dtype == torch.float64 and atoms.dtype == torch.float64 and scores.is_cuda and atoms.is_cuda
     assert tuple(scores.shape) == (d["B"],) and tuple(atoms.shape) == (d["N"],)
-    assert torch.equal(_score(vox, d, a, Fd), scores)  # per_atom=False: the same bits
+    assert torch.equal(X.score(vox, d, a, Fd), scores)  # per_atom=False: the same bits
     S_, s = scores.cpu().numpy(), atoms.cpu().numpy()
     w, types = E.reference_channels(d)
     s_ref, b_ref, S_ref, Sb_ref = sr.batch_reference(p, d["off"], Fref, d["radii"], d["radii_type"], w=w, mode=d["mode"], types=types,
@@ -205,17 +126,17 @@ def _abi_rows(vox, d, Fd):
 
     from molvoxel_amd.voxelizer.hip import _lib
 
-    call = _spec(vox, d, _inputs(d))
+    call = X.spec(vox, d, X.inputs(d))
     B, N, C_ = call.B, call.N, call.C
     fdt = torch.float64 if d["kind"] == "f64" else torch.float32
     feat = d["mode"] == "features"
-    out = dict(scores=_nan((B,)), atoms=_nan((N,)), gc=_nan((N, 3)), gf=_nan((N, C_), fdt) if feat else None)
+    out = dict(scores=hip.nan((B,)), atoms=hip.nan((N,)), gc=hip.nan((N, 3)), gf=hip.nan((N, C_), fdt) if feat else None)
     stride = 0 if Fd.dim() == 4 else C_ * d["D"] ** 3
-    _lib.check(vox._lib.mvx_score_batch(*call.batch_args(vox), Fd.data_ptr(), stride, _ptr(out["scores"]), _ptr(out["atoms"]),
-                                        _ptr(out["gc"]), _ptr(out["gf"]), vox._stream()))
+    _lib.check(vox._lib.mvx_score_batch(*call.batch_args(vox), Fd.data_ptr(), stride, hip.ptr(out["scores"]), hip.ptr(out["atoms"]),
+                                        hip.ptr(out["gc"]), hip.ptr(out["gf"]), vox._stream()))
     G = Fd.expand((B,) + tuple(Fd.shape)).contiguous() if Fd.dim() == 4 else Fd
-    ref = dict(gc=_nan((N, 3)), gf=_nan((N, C_), fdt) if feat else None)
-    _lib.check(vox._lib.mvx_backward_batch(*call.batch_args(vox), G.data_ptr(), _ptr(ref["gc"]), _ptr(ref["gf"]), vox._stream()))
+    ref = dict(gc=hip.nan((N, 3)), gf=hip.nan((N, C_), fdt) if feat else None)
+    _lib.check(vox._lib.mvx_backward_batch(*call.batch_args(vox), G.data_ptr(), hip.ptr(ref["gc"]), hip.ptr(ref["gf"]), vox._stream()))
     torch.cuda.synchronize()
     return out, ref
 
@@ -226,14 +147,14 @@ def _check_field_gradient(d, p):
     bfloat16 field)."""
     import torch
 
-    vox = _vox(d, differentiable=True, field_grad=True)
+    vox = X.vox(d, differentiable=True, field_grad=True)
     Fd, _ = _field(d)
     field = Fd.clone().requires_grad_()
     g = np.random.default_rng(d["fseed"] + 1).standard_normal(d["B"])
-    scores = _score(vox, d, _inputs(d), field)
-    (scores * _dev(g)).sum().backward()
+    scores = X.score(vox, d, X.inputs(d), field)
+    (scores * hip.dev(g)).sum().backward()
     assert field.grad is not None and field.grad.dtype == Fd.dtype and field.grad.shape == Fd.shape
-    grids = _forward(_vox(d, "f32"), d, _inputs(d)).to(torch.float64)
+    grids = X.forward(X.vox(d, "f32"), d, X.inputs(d)).to(torch.float64)
     gw = torch.tensor(g, device="cuda").reshape(-1, 1, 1, 1, 1)
     ref = (gw * grids).sum(0).cpu().numpy()
     bound = (gw.abs() * grids.abs()).sum(0).cpu().numpy()
@@ -252,13 +173,13 @@ def test_walk_draw_scores_and_gradients(seed):
     d = E.walk_draw(seed)
     Fd, Fref = _field(d)
     p = E.positions_of(d)
-    plain = _vox(d)
+    plain = X.vox(d)
     scores = _check_scores(d, plain, Fd, Fref, p)
 
     # b. gradient rows through autograd on a differentiable voxelizer: L = sum_b S_b, so dL/dgrid_b = F
-    vox = _vox(d, differentiable=True)
-    a = _inputs(d, grad=True)
-    recorded = _score(vox, d, a, Fd)
+    vox = X.vox(d, differentiable=True)
+    a = X.inputs(d, grad=True)
+    recorded = X.score(vox, d, a, Fd)
     assert torch.equal(recorded.detach(), scores)  # recording the graph does not change the scores
     gauss = d["density"] == "gaussian"
     feat = d["mode"] == "features"
@@ -331,10 +252,10 @@ def test_walk_draw_posed_grids_match_the_oracle_on_the_reference_positions(seed)
 
     d = E.walk_draw(seed)
     p = E.positions_of(d)
-    got = _forward(_vox(d), d, _inputs(d))
-    assert tuple(got.shape) == (d["B"], d["C"]) + (d["D"],) * 3 and got.dtype == _grid_dtype(d)
+    got = X.forward(X.vox(d), d, X.inputs(d))
+    assert tuple(got.shape) == (d["B"], d["C"]) + (d["D"],) * 3 and got.dtype == hip.grid_dtype(d)
     if d["kind"] == "bf16":  # a bfloat16 grid is the float32 grid rounded once (tests/test_hip_bf16.py); that one meets the oracle
-        base = _forward(_vox(d, "f32"), d, _inputs(d))
+        base = X.forward(X.vox(d, "f32"), d, X.inputs(d))
         assert torch.equal(got, base.to(torch.bfloat16)), _tag(d)
         got = base
     got = got.cpu().numpy()
@@ -349,9 +270,9 @@ def test_walk_draw_posed_grids_match_the_oracle_on_the_reference_positions(seed)
 # ---- e. summed draws ------------------------------------------------------------------------------------------------------------------
 def _summed(seed):
     d = E.summed_draw(seed)
-    vox = _vox(d)
-    a = _inputs(d)
-    grids = _forward(vox, d, a)
+    vox = X.vox(d)
+    a = X.inputs(d)
+    grids = X.forward(vox, d, a)
     assert tuple(grids.shape) == (d["B"], d["C"]) + (d["D"],) * 3
     return d, vox, a, grids, E.positions_of(d)
 
@@ -371,9 +292,9 @@ def test_summed_draw_grids_and_their_sum_match_the_oracle(seed):
         else:
             assert_gaussian(got[b], ref)
     if d["posed"]:
-        total = vox.forward_posed_sum(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=_nc(d))
+        total = vox.forward_posed_sum(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=hip.nc(d))
     else:
-        total = vox.forward_sum(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], num_channels=_nc(d))
+        total = vox.forward_sum(a["xyz"], d["off"], a["cen"], a["chan"], a["radii"], num_channels=hip.nc(d))
     merged = c_oracle.voxelize(p, E.features_of(d), d["r_atom"].astype(np.float32), resolution=d["res"], dimension=d["D"],
                                density=d["density"], blockdim=d["blockdim"], sigma=d["sigma"], radii_type="atom-wise")
     _check_merged(total.cpu().numpy(), merged, d["density"], str(_tag(d)))
@@ -401,10 +322,10 @@ def test_summed_draw_moments_and_their_gradient(seed):
 
     d, vox, a, grids, p = _summed(seed)
     target = E.target_of(d)
-    T = _dev(target)
+    T = hip.dev(target)
     g32 = grids.cpu().numpy()
     ref, bnd = MR.moments_and_bound(g32, target)
-    kw = dict(num_channels=_nc(d))
+    kw = dict(num_channels=hip.nc(d))
     if d["posed"]:
         call = lambda t: vox.moments_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], target=t, **kw)  # noqa: E731
     else:
@@ -419,7 +340,7 @@ def test_summed_draw_moments_and_their_gradient(seed):
 
     # the moments gradient with the drawn dL/dm against the float64 reference with G = a0 + a1 g + a2 t
     # (tests/test_hip_moments_grad.py: test_general_coefficients_match_the_float64_reference)
-    spec = _spec(vox, d, a)
+    spec = X.spec(vox, d, a)
     quats = E.quaternions_of(d)
     w, types = E.reference_channels(d)
     for K in (3, 2):

@@ -37,6 +37,7 @@ from tests import hessian_reference as hr
 from tests import lm_reference as lm
 from tests import lm_rows as R
 from tests import pose_reference as pr
+from tests import hip_support as hip
 from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -47,21 +48,10 @@ KW = dict(lam_down=R.LAM_DOWN, lam_up=R.LAM_UP, max_dropped=R.MAX_DROPPED)
 CASES = ("base", "long", "deep", "binary")
 
 
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _vox(d):
     import molvoxel_amd as mv
 
     return mv.create_voxelizer(0.5, X.D, d["radii_type"], d["density"], library="hip", precision=64 if d["kind"] == "f64" else 32)
-
-
-def _dev(x):
-    import torch
-
-    return x if x is None or np.isscalar(x) else torch.tensor(np.ascontiguousarray(x), device="cuda")
 
 
 def _field(d):
@@ -74,15 +64,15 @@ def _field(d):
 
 def _flex(vox, d, Fd, axes=None, moves=None, per_atom=True):
     """(scores, G, H, atom_grad, atom_hess, atom_pos) of the case's batch as host arrays."""
-    out = vox.score_hessian_flex_posed_batch(_dev(d["xyz"]), d["off"], _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), _dev(d["chan"]),
-                                             _dev(d["radii"]), Fd, d["axes"] if axes is None else axes,
+    out = vox.score_hessian_flex_posed_batch(hip.dev(d["xyz"]), d["off"], hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), hip.dev(d["chan"]),
+                                             hip.dev(d["radii"]), Fd, d["axes"] if axes is None else axes,
                                              d["moves"] if moves is None else moves, per_atom=per_atom)
     return tuple(x.cpu().numpy() for x in out)
 
 
 def _rigid(vox, d, Fd):
-    out = vox.score_hessian_posed_batch(_dev(d["xyz"]), d["off"], _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), _dev(d["chan"]),
-                                        _dev(d["radii"]), Fd, per_atom=True)
+    out = vox.score_hessian_posed_batch(hip.dev(d["xyz"]), d["off"], hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), hip.dev(d["chan"]),
+                                        hip.dev(d["radii"]), Fd, per_atom=True)
     return tuple(x.cpu().numpy() for x in out)
 
 
@@ -115,9 +105,9 @@ def test_the_twist_block_the_scores_and_the_rows_are_the_rigid_entrys_bits(name)
     (S, G, H, ag, ah, ap), (S6, tg, th, ag6, ah6) = _got(name)
     n = 6 + d["T"]
     assert G.shape == (d["B"], n) and H.shape == (d["B"], n, n) and ap.shape == (d["N"], 3)
-    assert _same_bits(S, S6) and _same_bits(G[:, :6], tg) and _same_bits(H[:, :6, :6], th)
-    assert _same_bits(ag, ag6) and _same_bits(ah, ah6)
-    assert _same_bits(H, H.transpose(0, 2, 1))
+    assert hip.same_bits(S, S6) and hip.same_bits(G[:, :6], tg) and hip.same_bits(H[:, :6, :6], th)
+    assert hip.same_bits(ag, ag6) and hip.same_bits(ah, ah6)
+    assert hip.same_bits(H, H.transpose(0, 2, 1))
     assert np.isfinite(G).all() and np.isfinite(H).all()
     # the positions the records hold: the reference's, to rounding of the pose arithmetic
     p = pr.batch_positions(d["xyz"], d["off"], d["cen"], d["q"], d["t"])
@@ -136,7 +126,7 @@ def test_no_torsions_give_the_rigid_entry_entirely(name):
     Fd, _ = _field(d)
     S, G, H = _flex(vox, d, Fd, axes=np.zeros((d["B"], 0, 2), np.int32), per_atom=False)
     _, (S6, tg, th, _, _) = _got(name)
-    assert _same_bits(S, S6) and _same_bits(G, tg) and _same_bits(H, th)
+    assert hip.same_bits(S, S6) and hip.same_bits(G, tg) and hip.same_bits(H, th)
 
 
 @pytest.mark.parametrize("name", ("base", "long", "deep"))
@@ -147,12 +137,12 @@ def test_two_runs_agree_and_a_molecule_alone_is_the_molecule_in_its_batch(name):
     first, _ = _got(name)
     again = _flex(vox, d, Fd)
     for a, b in zip(first, again):
-        assert _same_bits(a, b)
+        assert hip.same_bits(a, b)
     for b in range(d["B"]):
         alone = _flex(vox, _sub(d, b), Fd)
         lo, hi = int(d["off"][b]), int(d["off"][b + 1])
-        assert _same_bits(alone[0][0], first[0][b]) and _same_bits(alone[1][0], first[1][b]) and _same_bits(alone[2][0], first[2][b])
-        assert _same_bits(alone[5], first[5][lo:hi])
+        assert hip.same_bits(alone[0][0], first[0][b]) and hip.same_bits(alone[1][0], first[1][b]) and hip.same_bits(alone[2][0], first[2][b])
+        assert hip.same_bits(alone[5], first[5][lo:hi])
 
 
 # ---- against the reference ----------------------------------------------------------------------------------------------------
@@ -211,14 +201,14 @@ def test_an_inert_torsion_gives_exact_zeros_and_leaves_the_other_bits(bad):
     moves[9:12] |= 1 << 4  # the fifth set is a live set: only its axis is not
     S, G, H = _flex(vox, d, Fd, axes=axes, moves=moves, per_atom=False)
     (S4, G4, H4, _, _, _), _ = _got("base")
-    assert _same_bits(S, S4) and _same_bits(G[:, :10], G4) and _same_bits(H[:, :10, :10], H4)
+    assert hip.same_bits(S, S4) and hip.same_bits(G[:, :10], G4) and hip.same_bits(H[:, :10, :10], H4)
     assert not G[:, 10].any() and not H[:, 10, :].any() and not H[:, :, 10].any()
     assert not np.signbit(G[:, 10]).any() and not np.signbit(H[:, 10, :]).any()
     # ... and apply_torsions turns nothing about it
     ang = np.random.default_rng(1).uniform(-1, 1, (3, 5))
-    with_it = vox.apply_torsions(_dev(d["xyz"]), d["off"], axes, moves, ang).cpu().numpy()
-    without = vox.apply_torsions(_dev(d["xyz"]), d["off"], d["axes"], d["moves"], ang[:, :4]).cpu().numpy()
-    assert _same_bits(with_it, without)
+    with_it = vox.apply_torsions(hip.dev(d["xyz"]), d["off"], axes, moves, ang).cpu().numpy()
+    without = vox.apply_torsions(hip.dev(d["xyz"]), d["off"], d["axes"], d["moves"], ang[:, :4]).cpu().numpy()
+    assert hip.same_bits(with_it, without)
 
 
 def test_a_dead_atom_in_a_moving_set_gives_the_bits_of_the_call_without_it():
@@ -235,7 +225,7 @@ def test_a_dead_atom_in_a_moving_set_gives_the_bits_of_the_call_without_it():
     off[-1] -= 1
     cut = dict(d, xyz=d["xyz"][:last], chan=d["chan"][:last], radii=d["radii"][:last], off=off, moves=d["moves"][:last], N=last)
     S2, G2, H2 = _flex(vox, cut, Fd, per_atom=False)
-    assert _same_bits(S, S2) and _same_bits(G, G2) and _same_bits(H, H2)
+    assert hip.same_bits(S, S2) and hip.same_bits(G, G2) and hip.same_bits(H, H2)
 
 
 # ---- apply_torsions -----------------------------------------------------------------------------------------------------------
@@ -250,12 +240,12 @@ def test_apply_torsions_against_the_reference(name):
     ang = rng.uniform(-np.pi, np.pi, (B, T))
     if name == "base":
         ang[0, 1] = 0.0  # an angle of exactly zero turns nothing
-    xyz = _dev(d["xyz"])
+    xyz = hip.dev(d["xyz"])
     same = vox.apply_torsions(xyz, d["off"], d["axes"], d["moves"], np.zeros((B, T))).cpu().numpy()
-    assert _same_bits(same, d["xyz"])
+    assert hip.same_bits(same, d["xyz"])
     got = vox.apply_torsions(xyz, d["off"], d["axes"], d["moves"], ang).cpu().numpy()
     again = vox.apply_torsions(xyz, d["off"], d["axes"], d["moves"], ang).cpu().numpy()
-    assert _same_bits(got, again) and _same_bits(xyz.cpu().numpy(), d["xyz"])
+    assert hip.same_bits(got, again) and hip.same_bits(xyz.cpu().numpy(), d["xyz"])
     worst = worst_d = 0.0
     for b in range(B):
         lo, hi = int(d["off"][b]), int(d["off"][b + 1])
@@ -267,7 +257,7 @@ def test_apply_torsions_against_the_reference(name):
         for k in range(T):
             if fr.axis(p0, ax[k]) is not None and ang[b, k] != 0.0:
                 turned |= fr.bits(mv, k)
-        assert _same_bits(got[lo:hi][~turned], p0[~turned])
+        assert hip.same_bits(got[lo:hi][~turned], p0[~turned])
         bar = 64 * T * U * fr.reach(p0, ax, mv)
         worst = max(worst, float(np.abs(got[lo:hi] - ref).max() / bar))
         # the distances inside every rigid part of a moving set - the atoms with one and the same mask, which turn together (a set
@@ -324,7 +314,7 @@ def test_flex_lm_step_without_torsions_is_lm_step_to_the_bit(vox, B, have_trial)
     vox.flex_lm_step(b, dev_trial if have_trial else None, **KW)
     for k, k2 in (("q", "q"), ("t", "t"), ("S", "S"), ("G", "G"), ("H", "H"), ("lam", "lam"), ("taken", "taken"), ("dropped", "dropped"),
                   ("q2", "q2"), ("t2", "t2"), ("xi", "x")):
-        assert _same_bits(getattr(a, k).cpu().numpy(), getattr(b, k2).cpu().numpy()), k
+        assert hip.same_bits(getattr(a, k).cpu().numpy(), getattr(b, k2).cpu().numpy()), k
 
 
 @pytest.mark.parametrize("have_trial", [True, False])
@@ -338,26 +328,26 @@ def test_flex_lm_step_against_the_reference(vox, T, have_trial):
     again, _ = _flex_state(s0, trial, B, T)
     vox.flex_lm_step(again, dev_trial if have_trial else None, **KW)
     for k in got:
-        assert _same_bits(got[k], getattr(again, k).cpu().numpy()), k
+        assert hip.same_bits(got[k], getattr(again, k).cpu().numpy()), k
     ref, rtrial = X.lm_reference_state(T)
     decisions = fr.step(ref, rtrial if have_trial else None, x_from=got["x"], **KW)
     for k in NAMES:  # decisions, damping, counters and the copied state: to the bit
-        assert _same_bits(got[k], getattr(ref, k)), (k, np.argwhere(got[k] != getattr(ref, k))[:3].tolist())
+        assert hip.same_bits(got[k], getattr(ref, k)), (k, np.argwhere(got[k] != getattr(ref, k))[:3].tolist())
     for b in range(B):
         kind = R.kind_of(B, b)
         if decisions[b] == "accept":
-            assert _same_bits(got["theta"][b], s0["theta2"][b]) and _same_bits(got["H"][b], rtrial[2][b]) and got["taken"][b] == s0["taken"][b] + 1
+            assert hip.same_bits(got["theta"][b], s0["theta2"][b]) and hip.same_bits(got["H"][b], rtrial[2][b]) and got["taken"][b] == s0["taken"][b] + 1
         else:
-            assert _same_bits(got["theta"][b], s0["theta"][b]) and _same_bits(got["H"][b], s0["H"][b]) and got["taken"][b] == s0["taken"][b]
+            assert hip.same_bits(got["theta"][b], s0["theta"][b]) and hip.same_bits(got["H"][b], s0["H"][b]) and got["taken"][b] == s0["taken"][b]
         stays = kind in R.FAILS or kind == "finished" or (have_trial and kind == "dropped_last")
         if stays:  # no step: x = 0 and the state itself, to the bit
             assert not got["x"][b].any() and not np.signbit(got["x"][b]).any(), (b, kind)
-            assert _same_bits(got["q2"][b], got["q"][b]) and _same_bits(got["t2"][b], got["t"][b]) and _same_bits(got["theta2"][b], got["theta"][b])
+            assert hip.same_bits(got["q2"][b], got["q"][b]) and hip.same_bits(got["t2"][b], got["t"][b]) and hip.same_bits(got["theta2"][b], got["theta"][b])
         else:
             assert got["x"][b].any() and np.isfinite(got["x"][b]).all(), (b, kind)
-            assert _same_bits(got["theta2"][b], got["theta"][b] + got["x"][b, 6:])
+            assert hip.same_bits(got["theta2"][b], got["theta"][b] + got["x"][b, 6:])
         if kind == "omega_zero":
-            assert not got["x"][b, 3:6].any() and _same_bits(got["q2"][b], got["q"][b])
+            assert not got["x"][b, 3:6].any() and hip.same_bits(got["q2"][b], got["q"][b])
     numpy_worst, cond = X.lm_numpy_residual()
     gamma = 4.0 * numpy_worst
     assert cond < 1e8
@@ -371,7 +361,7 @@ def test_flex_lm_step_against_the_reference(vox, T, have_trial):
           f"q2 error / bar {qerr.max():.3g}, t2 error / bar {terr.max():.3g}")
     assert worst <= gamma, (worst, gamma)
     assert (qerr <= 1.0).all() and (terr <= 1.0).all()
-    assert _same_bits(got["theta2"], ref.theta2)
+    assert hip.same_bits(got["theta2"], ref.theta2)
 
 
 # ---- the refinement -----------------------------------------------------------------------------------------------------------
@@ -383,23 +373,23 @@ def test_refinement_with_torsions_ends_above_the_rigid_refinement_of_every_start
     B = X.REFINE_POSES
     vox = mv.create_voxelizer(0.5, X.D, "atom-wise", "gaussian", library="hip")
     off1 = np.array([0, 14], np.int64)
-    ident = (_dev(np.array([[1.0, 0.0, 0.0, 0.0]])), _dev(np.zeros((1, 3))))
-    field = vox.forward_posed_batch(_dev(xyz), off1, _dev(cen), ident[0], ident[1], _dev(W), _dev(rad))[0].clone()
+    ident = (hip.dev(np.array([[1.0, 0.0, 0.0, 0.0]])), hip.dev(np.zeros((1, 3))))
+    field = vox.forward_posed_batch(hip.dev(xyz), off1, hip.dev(cen), ident[0], ident[1], hip.dev(W), hip.dev(rad))[0].clone()
     assert np.abs(field.cpu().numpy().astype(np.float64) - X.cpu_field()).max() <= 1e-4
     # B copies of the molecule, one per start
     off = 14 * np.arange(B + 1, dtype=np.int64)
-    rep = lambda x: _dev(np.concatenate([x] * B))
+    rep = lambda x: hip.dev(np.concatenate([x] * B))
     coords, chan, radii, cens = rep(xyz), rep(W), rep(rad), rep(cen)
     ax, mvs = np.concatenate([axes] * B), np.concatenate([moves] * B)
     kw = dict(steps=X.REFINE_ROUNDS, **KW)
-    q, t, theta, S, info = vox.refine_flex_posed_batch(coords, off, cens, _dev(q0), _dev(t0), _dev(th0), chan, radii, field, ax, mvs, **kw)
+    q, t, theta, S, info = vox.refine_flex_posed_batch(coords, off, cens, hip.dev(q0), hip.dev(t0), hip.dev(th0), chan, radii, field, ax, mvs, **kw)
     hist = info["score_history"].cpu().numpy()
     assert hist.shape == (X.REFINE_ROUNDS + 1, B) and tuple(theta.shape) == (B, 4) and info["evaluations"] == X.REFINE_ROUNDS + 1
-    assert _same_bits(hist[-1], S.cpu().numpy())
+    assert hip.same_bits(hist[-1], S.cpu().numpy())
     # the rigid refinement of the same starts: the start conformers, then refine_posed_batch
-    start = vox.apply_torsions(coords, off, ax, mvs, _dev(th0))
-    _, _, S6, info6 = vox.refine_posed_batch(start, off, cens, _dev(q0), _dev(t0), chan, radii, field, **kw)
-    assert _same_bits(hist[0], info6["score_history"][0].cpu().numpy())  # (both start from the same evaluation)
+    start = vox.apply_torsions(coords, off, ax, mvs, hip.dev(th0))
+    _, _, S6, info6 = vox.refine_posed_batch(start, off, cens, hip.dev(q0), hip.dev(t0), chan, radii, field, **kw)
+    assert hip.same_bits(hist[0], info6["score_history"][0].cpu().numpy())  # (both start from the same evaluation)
     print(f"FLEX_REFINE taken {info['taken'].tolist()} (rigid {info6['taken'].tolist()}); score {hist[0].min():.1f} ... {hist[0].max():.1f} "
           f"-> {hist[-1].min():.1f} ... {hist[-1].max():.1f}, rigid -> {float(S6.min()):.1f} ... {float(S6.max()):.1f}")
     X.refine_conditions(hist, S.cpu().numpy(), S6.cpu().numpy())

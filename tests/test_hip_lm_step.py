@@ -14,6 +14,7 @@ import pytest
 
 from tests import lm_reference as lm
 from tests import lm_rows as R
+from tests import hip_support as hip
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +46,6 @@ def _host(st):
     return {k: getattr(st, k).cpu().numpy() for k in NAMES + ("q2", "t2", "xi")}
 
 
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _run(vox, B, have_trial):
     st, trial = _device_state(B)
     vox.lm_step(st, trial if have_trial else None, **KW)
@@ -66,21 +62,21 @@ def test_step_against_the_reference(vox, B, have_trial):
     decisions = lm.step(ref, rtrial if have_trial else None, xi_from=got["xi"], **KW)
     # decisions, damping, counters and the copied state: to the bit
     for k in NAMES:
-        assert _same_bits(got[k], getattr(ref, k)), (k, np.argwhere(got[k] != getattr(ref, k))[:3].tolist())
+        assert hip.same_bits(got[k], getattr(ref, k)), (k, np.argwhere(got[k] != getattr(ref, k))[:3].tolist())
     for b in range(B):
         kind = R.kind_of(B, b)
         if decisions[b] == "accept":
-            assert _same_bits(got["q"][b], s0["q2"][b]) and _same_bits(got["H"][b], rtrial[2][b]) and got["taken"][b] == s0["taken"][b] + 1
+            assert hip.same_bits(got["q"][b], s0["q2"][b]) and hip.same_bits(got["H"][b], rtrial[2][b]) and got["taken"][b] == s0["taken"][b] + 1
         else:
-            assert _same_bits(got["q"][b], s0["q"][b]) and _same_bits(got["H"][b], s0["H"][b]) and got["taken"][b] == s0["taken"][b]
+            assert hip.same_bits(got["q"][b], s0["q"][b]) and hip.same_bits(got["H"][b], s0["H"][b]) and got["taken"][b] == s0["taken"][b]
         stays = kind in R.FAILS or kind == "finished" or (have_trial and kind == "dropped_last")
         if stays:  # no step: xi = 0 and the pose itself, to the bit
             assert not got["xi"][b].any() and not np.signbit(got["xi"][b]).any(), (b, kind)
-            assert _same_bits(got["q2"][b], got["q"][b]) and _same_bits(got["t2"][b], got["t"][b]), (b, kind)
+            assert hip.same_bits(got["q2"][b], got["q"][b]) and hip.same_bits(got["t2"][b], got["t"][b]), (b, kind)
         else:
             assert got["xi"][b].any() and np.isfinite(got["xi"][b]).all(), (b, kind)
         if kind == "omega_zero":
-            assert not got["xi"][b, 3:].any() and _same_bits(got["q2"][b], got["q"][b])
+            assert not got["xi"][b, 3:].any() and hip.same_bits(got["q2"][b], got["q"][b])
     # the solve: the residual of the kernel's xi against four times np.linalg.solve's own
     numpy_worst, cond = R.numpy_residual()
     gamma = 4.0 * numpy_worst
@@ -106,7 +102,7 @@ def test_finished_rows_stay_untouched_and_two_runs_agree(vox, B):
     st, trial = _run(vox, B, True)
     again, _ = _run(vox, B, True)
     for k in NAMES + ("q2", "t2", "xi"):
-        assert torch.equal(getattr(st, k), getattr(again, k)) or _same_bits(getattr(st, k).cpu().numpy(), getattr(again, k).cpu().numpy()), k
+        assert torch.equal(getattr(st, k), getattr(again, k)) or hip.same_bits(getattr(st, k).cpu().numpy(), getattr(again, k).cpu().numpy()), k
     first = _host(st)
     done = first["dropped"] >= R.MAX_DROPPED
     kinds = {R.kind_of(B, b) for b in np.flatnonzero(done)}
@@ -118,8 +114,8 @@ def test_finished_rows_stay_untouched_and_two_runs_agree(vox, B):
         S2 = S2 + 100.0
     later = _host(st)
     for k in NAMES + ("q2", "t2", "xi"):
-        assert _same_bits(later[k][done], first[k][done]), k
-    assert not later["xi"][done].any() and _same_bits(later["q2"][done], later["q"][done]) and _same_bits(later["t2"][done], later["t"][done])
+        assert hip.same_bits(later[k][done], first[k][done]), k
+    assert not later["xi"][done].any() and hip.same_bits(later["q2"][done], later["q"][done]) and hip.same_bits(later["t2"][done], later["t"][done])
     live = ~done & np.isfinite(first["S"])
     assert (later["taken"][live] == first["taken"][live] + 2).all() and not later["dropped"][live].any()
 
@@ -137,7 +133,7 @@ def test_the_trial_pose_tensors_are_made_once_and_xi_may_be_left_out(vox):
     q2, t2, xi = st.q2, st.t2, st.xi
     assert tuple(q2.shape) == (B, 4) and tuple(t2.shape) == (B, 3) and tuple(xi.shape) == (B, 6)
     full, _ = _run(vox, B, False)
-    assert torch.equal(q2, full.q2) or _same_bits(q2.cpu().numpy(), full.q2.cpu().numpy())
+    assert torch.equal(q2, full.q2) or hip.same_bits(q2.cpu().numpy(), full.q2.cpu().numpy())
     vox.lm_step(st, **KW)
     assert st.q2 is q2 and st.t2 is t2 and st.xi is xi
     # the C entry without xi: the same trial poses
@@ -146,4 +142,4 @@ def test_the_trial_pose_tensors_are_made_once_and_xi_may_be_left_out(vox):
                               st.G.data_ptr(), st.H.data_ptr(), st.lam.data_ptr(), st.taken.data_ptr(), st.dropped.data_ptr(),
                               out_q.data_ptr(), out_t.data_ptr(), None, None, None, None, torch.cuda.current_stream().cuda_stream)
     assert rc == 0, vox._lib.mvx_last_error()
-    assert _same_bits(out_q.cpu().numpy(), q2.cpu().numpy()) and _same_bits(out_t.cpu().numpy(), t2.cpu().numpy())
+    assert hip.same_bits(out_q.cpu().numpy(), q2.cpu().numpy()) and hip.same_bits(out_t.cpu().numpy(), t2.cpu().numpy())

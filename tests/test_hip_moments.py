@@ -15,12 +15,13 @@ import pytest
 from tests import moments_reference as MR
 from tests import sum_rows as R
 from tests import sum_sweep_rows as S
+from tests import hip_support as hip
+from tests.abi import MVX_ERR_INVALID, last_error
 
 pytestmark = pytest.mark.gpu
 
 SWEEP_IDS = ["edge20", "edge20d", "edge12", "cut96", "bd16", "tall"]
 ROW_IDS = R.ROW_IDS + SWEEP_IDS
-MVX_ERR_INVALID = -1
 
 
 def _make(row_id):
@@ -40,14 +41,6 @@ def _new_vox(row_id, **kw):
     return mv.create_voxelizer(0.5, row.D, row.radii_type, row.density, library="hip", blockdim=getattr(row, "blockdim", None), **kw)
 
 
-def _dev(x):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda")
-
-
 def _args(d, lo=0, hi=None):
     """forward_batch's arguments for the molecules [lo, hi) of a row's batch."""
     row = d["row"]
@@ -55,13 +48,13 @@ def _args(d, lo=0, hi=None):
     a0, a1 = int(d["off"][lo]), int(d["off"][hi])
     chan = None if d["chan"] is None else d["chan"][a0:a1]
     radii = d["radii"][a0:a1] if row.radii_type == "atom-wise" else d["radii"]
-    return dict(coords=_dev(d["xyz"][a0:a1]), offsets=d["off"][lo:hi + 1] - a0, centers=_dev(d["cen"][lo:hi]), channels=_dev(chan),
-                radii=_dev(radii), num_channels=row.C if row.mode == "types" else None)
+    return dict(coords=hip.dev(d["xyz"][a0:a1]), offsets=d["off"][lo:hi + 1] - a0, centers=hip.dev(d["cen"][lo:hi]), channels=hip.dev(chan),
+                radii=hip.dev(radii), num_channels=row.C if row.mode == "types" else None)
 
 
 def _posed_args(d):
     a = _args(d)
-    return dict(a, quaternions=_dev(d["q"]), translations=_dev(d["t"]))
+    return dict(a, quaternions=hip.dev(d["q"]), translations=hip.dev(d["t"]))
 
 
 @functools.lru_cache(maxsize=None)
@@ -135,7 +128,7 @@ def test_moments_are_those_of_forward_batchs_grids(row_id):
     vox = _vox(row_id)
     plain = _call(vox, d, "centred")
     _check(plain, ref[..., :2], bnd[..., :2], row, f"{row_id} without a target")
-    with_t = _call(vox, d, "centred", _dev(_target(row_id)))
+    with_t = _call(vox, d, "centred", hip.dev(_target(row_id)))
     _check(with_t, ref, bnd, row, f"{row_id} with a target")
     # molecules without atoms, or with none inside the box: exact zeros
     sizes = np.diff(d["off"])
@@ -155,7 +148,7 @@ def test_the_rows_have_molecules_that_reach_no_voxel_next_to_ones_that_do():
 def test_posed_moments_are_those_of_forward_posed_batchs_grids(row_id):
     d = _make(row_id)
     ref, bnd = _reference(row_id, "posed")
-    _check(_call(_vox(row_id), d, "posed", _dev(_target(row_id))), ref, bnd, d["row"], f"{row_id} posed")
+    _check(_call(_vox(row_id), d, "posed", hip.dev(_target(row_id))), ref, bnd, d["row"], f"{row_id} posed")
     _check(_call(_vox(row_id), d, "posed"), ref[..., :2], bnd[..., :2], d["row"], f"{row_id} posed, no target")
     assert not np.array_equal(ref, _reference(row_id, "centred")[0])  # (the poses reach the call)
 
@@ -164,7 +157,7 @@ def test_posed_moments_are_those_of_forward_posed_batchs_grids(row_id):
 def test_rotated_moments_are_those_of_forward_batch_with_the_same_rng_state(row_id):
     d = _make(row_id)
     ref, bnd = _reference(row_id, "rotated")
-    _check(_call(_vox(row_id), d, "rotated", _dev(_target(row_id))), ref, bnd, d["row"], f"{row_id} rotated")
+    _check(_call(_vox(row_id), d, "rotated", hip.dev(_target(row_id))), ref, bnd, d["row"], f"{row_id} rotated")
     drawn = np.random.rand()
     np.random.seed(SEED)
     _vox(row_id).forward_batch(random_rotation=True, random_translation=0.5, **_args(d))
@@ -175,7 +168,7 @@ def test_rotated_moments_are_those_of_forward_batch_with_the_same_rng_state(row_
 # ---- 2. bit identities -------------------------------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _uncut(row_id, with_target):
-    return _call(_vox(row_id), _make(row_id), "centred", _dev(_target(row_id)) if with_target else None)
+    return _call(_vox(row_id), _make(row_id), "centred", hip.dev(_target(row_id)) if with_target else None)
 
 
 @pytest.mark.parametrize("row_id", ROW_IDS)
@@ -184,7 +177,7 @@ def test_a_molecule_alone_two_runs_and_the_target_do_not_change_the_bits(row_id)
 
     d = _make(row_id)
     vox = _vox(row_id)
-    t = _dev(_target(row_id))
+    t = hip.dev(_target(row_id))
     both, plain = _uncut(row_id, True), _uncut(row_id, False)
     assert torch.equal(both[..., :2], plain)  # the first two moments do not depend on the target
     assert torch.equal(_call(vox, d, "centred", t), both) and torch.equal(_call(vox, d, "centred"), plain)  # two runs
@@ -207,7 +200,7 @@ def test_molecule_chunks_give_the_uncut_bits(row_id, option, value, nchunk):
     vox = _new_vox(row_id)  # (a voxelizer of its own: the option stays with the handle)
     vox.debug_option(option, value)
     for with_target in (True, False):
-        got = _call(vox, d, "centred", _dev(_target(row_id)) if with_target else None)
+        got = _call(vox, d, "centred", hip.dev(_target(row_id)) if with_target else None)
         plan = vox.last_plan()
         assert plan["nchunk"] == nchunk, plan  # the cut really happened
         assert plan["ct"] == 32 and plan["ncc"] == -(-d["row"].C // 32) and plan["route"] == 0 and plan["grouped"] == 0, plan
@@ -222,7 +215,7 @@ def test_bfloat16_and_channels_last_voxelizers_give_the_float32_bits(row_id, kw)
     d = _make(row_id)
     vox = _vox(row_id, **kw)
     assert vox.forward_batch(**_args(d, 0, 1)).dtype == (torch.bfloat16 if "grid_dtype" in kw else torch.float32)
-    assert torch.equal(_call(vox, d, "centred", _dev(_target(row_id))), _uncut(row_id, True))
+    assert torch.equal(_call(vox, d, "centred", hip.dev(_target(row_id))), _uncut(row_id, True))
     assert torch.equal(_call(vox, d, "centred"), _uncut(row_id, False))
 
 
@@ -239,8 +232,8 @@ def test_sixty_six_thousand_molecules_cross_the_grid_limit_and_the_chunk_workspa
     xyz = rng.uniform(-half - 0.5, half + 0.5, (int(off[-1]), 3))
     target = rng.standard_normal((1, D, D, D)).astype(np.float32)
     vox = mv.create_voxelizer(0.5, D, "scalar", "gaussian", library="hip")
-    a = dict(coords=_dev(xyz), offsets=off, centers=None, channels=None, radii=1.0)
-    got = vox.moments_batch(target=_dev(target), **a)
+    a = dict(coords=hip.dev(xyz), offsets=off, centers=None, channels=None, radii=1.0)
+    got = vox.moments_batch(target=hip.dev(target), **a)
     plan = vox.last_plan()
     assert plan["nchunk"] >= 2 and B > 65535, plan  # more molecules than one launch's grid holds
     assert got.dtype == torch.float64 and tuple(got.shape) == (B, 1, 3)
@@ -253,8 +246,8 @@ def test_sixty_six_thousand_molecules_cross_the_grid_limit_and_the_chunk_workspa
     assert torch.equal(vox.moments_batch(**a), got[..., :2])
     # the last molecules alone: what sits behind the cut is not a function of the cut
     lo = B - 500
-    tail = dict(a, coords=_dev(xyz[off[lo]:]), offsets=off[lo:] - off[lo])
-    assert torch.equal(vox.moments_batch(target=_dev(target), **tail), got[lo:])
+    tail = dict(a, coords=hip.dev(xyz[off[lo]:]), offsets=off[lo:] - off[lo])
+    assert torch.equal(vox.moments_batch(target=hip.dev(target), **tail), got[lo:])
 
 
 # ---- 4. what the calls refuse, and the calls without molecules or atoms ----------------------------------------------------------
@@ -264,7 +257,7 @@ def test_no_molecules_and_no_atoms():
     vox = _vox("light")
     none = dict(coords=torch.empty((0, 3), dtype=torch.float64, device="cuda"), centers=None, channels=torch.empty((0, 5), device="cuda"),
                 radii=1.0)
-    t = _dev(_target("light"))
+    t = hip.dev(_target("light"))
     for offsets, B in ((np.array([0]), 0), (np.array([0, 0, 0]), 2)):
         for target in (None, t):
             got = vox.moments_batch(offsets=offsets, target=target, **none)
@@ -300,7 +293,7 @@ def test_the_library_names_what_it_does_not_serve():
         rc = vox._lib.mvx_moments_batch(vox._handle, 0, xyz.data_ptr(), feat.data_ptr(), None if radii is None else radii.data_ptr(),
                                         1.0, rt, off.ctypes.data, None, 1, C_, None if target is None else target.data_ptr(),
                                         out.data_ptr(), None)
-        return rc, (vox._lib.mvx_last_error() or b"").decode(), out
+        return rc, last_error(), out
 
     mk = lambda D, rt="scalar", **kw: mv.create_voxelizer(0.5, D, rt, "gaussian", library="hip", **kw)  # noqa: E731
     for vox, kw, words in [

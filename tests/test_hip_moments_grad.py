@@ -22,13 +22,14 @@ from tests import moments_grad_reference as MG
 from tests import pose_reference as PR
 from tests import sum_rows as R
 from tests import sum_sweep_rows as S
+from tests import hip_support as hip
+from tests.abi import MVX_ERR_INVALID, last_error
 from tests.tolerance import GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
 
 ROW_IDS = ["light", "carry", "chunks", "wide", "types", "single"]
 LEGS = ["centred", "posed", "rotated"]
-MVX_ERR_INVALID = -1
 SEED = 77      # the rotated leg seeds numpy's global generator, as tests/test_hip_moments.py does
 SAMPLE = 96    # atoms per case that go through the float64 reference
 
@@ -50,14 +51,6 @@ def _new_vox(row_id, **kw):
     return mv.create_voxelizer(0.5, row.D, row.radii_type, row.density, library="hip", blockdim=getattr(row, "blockdim", None), **kw)
 
 
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
-
-
 def _args(d, lo=0, hi=None):
     """forward_batch's arguments for the molecules [lo, hi) of a row's batch."""
     row = d["row"]
@@ -65,8 +58,8 @@ def _args(d, lo=0, hi=None):
     a0, a1 = int(d["off"][lo]), int(d["off"][hi])
     chan = None if d["chan"] is None else d["chan"][a0:a1]
     radii = d["radii"][a0:a1] if row.radii_type == "atom-wise" else d["radii"]
-    return dict(coords=_dev(d["xyz"][a0:a1]), offsets=d["off"][lo:hi + 1] - a0, centers=_dev(d["cen"][lo:hi]), channels=_dev(chan),
-                radii=_dev(radii), num_channels=row.C if row.mode == "types" else None)
+    return dict(coords=hip.dev(d["xyz"][a0:a1]), offsets=d["off"][lo:hi + 1] - a0, centers=hip.dev(d["cen"][lo:hi]), channels=hip.dev(chan),
+                radii=hip.dev(radii), num_channels=row.C if row.mode == "types" else None)
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,7 +84,7 @@ def _forward(vox, d, leg, lo=0, hi=None):
     """The grids of a leg: forward_batch / forward_posed_batch of the molecules [lo, hi)."""
     a = _args(d, lo, hi)
     if leg == "posed":
-        return vox.forward_posed_batch(quaternions=_dev(d["q"][lo:hi]), translations=_dev(d["t"][lo:hi]), **a)
+        return vox.forward_posed_batch(quaternions=hip.dev(d["q"][lo:hi]), translations=hip.dev(d["t"][lo:hi]), **a)
     if leg == "rotated":
         np.random.seed(SEED)
         return vox.forward_batch(random_rotation=True, random_translation=0.5, **a)
@@ -106,7 +99,7 @@ def _spec(vox, d, leg, lo=0, hi=None):
     with torch.no_grad():
         if leg == "posed":
             return vox._batch_call(a["coords"], a["offsets"], a["centers"], a["channels"], a["radii"], a["num_channels"],
-                                   posed=(_dev(d["q"][lo:hi]), _dev(d["t"][lo:hi])), device=True)
+                                   posed=(hip.dev(d["q"][lo:hi]), hip.dev(d["t"][lo:hi])), device=True)
         if leg == "rotated":
             np.random.seed(SEED)
             return vox._batch_call(a["coords"], a["offsets"], a["centers"], a["channels"], a["radii"], a["num_channels"], 0.5, True,
@@ -114,21 +107,11 @@ def _spec(vox, d, leg, lo=0, hi=None):
         return vox._batch_call(a["coords"], a["offsets"], a["centers"], a["channels"], a["radii"], a["num_channels"], device=True)
 
 
-def _nan(shape, dt=None):
-    import torch
-
-    return torch.full(shape, float("nan"), dtype=dt or torch.float64, device="cuda")
-
-
-def _ptr(x):
-    return None if x is None else x.data_ptr()
-
-
 def _outputs(call):
     """(grad_coords, grad_features or None), full of NaN: whatever is not overwritten fails every comparison."""
     import torch
 
-    return _nan((call.N, 3)), (_nan((call.N, call.C), torch.float32) if call.mode == "features" else None)
+    return hip.nan((call.N, 3)), (hip.nan((call.N, call.C), torch.float32) if call.mode == "features" else None)
 
 
 def _entry(vox, call, gm, target):
@@ -140,7 +123,7 @@ def _entry(vox, call, gm, target):
     g = torch.tensor(np.ascontiguousarray(gm, np.float64), device="cuda")
     assert tuple(g.shape) == (call.B, call.C, 2 if target is None else 3)
     gc, gf = _outputs(call)
-    _lib.check(vox._lib.mvx_moments_backward_batch(*call.batch_args(vox), _ptr(target), g.data_ptr(), gc.data_ptr(), _ptr(gf),
+    _lib.check(vox._lib.mvx_moments_backward_batch(*call.batch_args(vox), hip.ptr(target), g.data_ptr(), gc.data_ptr(), hip.ptr(gf),
                                                    vox._stream()))
     return gc, gf
 
@@ -149,7 +132,7 @@ def _backward_entry(vox, call, grad_out):
     from molvoxel_amd.voxelizer.hip import _lib
 
     gc, gf = _outputs(call)
-    _lib.check(vox._lib.mvx_backward_batch(*call.batch_args(vox), grad_out.data_ptr(), gc.data_ptr(), _ptr(gf), vox._stream()))
+    _lib.check(vox._lib.mvx_backward_batch(*call.batch_args(vox), grad_out.data_ptr(), gc.data_ptr(), hip.ptr(gf), vox._stream()))
     return gc, gf
 
 
@@ -176,11 +159,11 @@ def test_the_third_moment_alone_is_score_batch_over_the_target(row_id, leg):
     d = _make(row_id)
     vox = _vox(row_id)
     call = _spec(vox, d, leg)
-    t = _dev(_target(row_id))
+    t = hip.dev(_target(row_id))
     got = _entry(vox, call, _const(d, 3, 0.0, 0.0, 1.0), t)  # a0 = a1 = 0, a2 = 1: u = t exactly
     gc, gf = _outputs(call)
     scores = torch.empty(call.B, dtype=torch.float64, device="cuda")
-    _lib.check(vox._lib.mvx_score_batch(*call.batch_args(vox), t.data_ptr(), 0, scores.data_ptr(), None, gc.data_ptr(), _ptr(gf),
+    _lib.check(vox._lib.mvx_score_batch(*call.batch_args(vox), t.data_ptr(), 0, scores.data_ptr(), None, gc.data_ptr(), hip.ptr(gf),
                                         vox._stream()))
     assert _same(got, (gc, gf)), (row_id, leg)
     assert (gf if gf is not None else gc).abs().sum() > 0 or d["row"].density == "binary"
@@ -194,7 +177,7 @@ def test_the_second_moment_alone_is_backward_batch_with_the_grids_as_upstream(ro
     grids = _forward(vox, d, "posed")
     want = _backward_entry(vox, call, grids)  # a0 = 0, a1 = (float)(2 * 0.5) = 1, a2 = 0: u = g exactly
     assert _same(_entry(vox, call, _const(d, 2, 0.0, 0.5), None), want), row_id
-    assert _same(_entry(vox, call, _const(d, 3, 0.0, 0.5, 0.0), _dev(_target(row_id))), want), row_id  # (0 * t + 0: finite targets)
+    assert _same(_entry(vox, call, _const(d, 3, 0.0, 0.5, 0.0), hip.dev(_target(row_id))), want), row_id  # (0 * t + 0: finite targets)
 
 
 @pytest.mark.parametrize("row_id", ROW_IDS)
@@ -277,7 +260,7 @@ def test_general_coefficients_match_the_float64_reference(row_id, leg):
     for with_target in (True, False):
         K = 3 if with_target else 2
         gm = _dm(row_id, K)
-        gc, gf = _entry(vox, call, gm, _dev(_target(row_id)) if with_target else None)
+        gc, gf = _entry(vox, call, gm, hip.dev(_target(row_id)) if with_target else None)
         gc = gc.cpu().numpy()
         gf = None if gf is None else gf.cpu().numpy()
         assert not np.isnan(gc).any() and (gf is None or not np.isnan(gf).any())  # fully overwritten
@@ -304,14 +287,14 @@ def test_general_coefficients_match_the_float64_reference(row_id, leg):
 def _uncut(row_id, with_target):
     d = _make(row_id)
     vox = _vox(row_id)
-    return _entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3 if with_target else 2), _dev(_target(row_id)) if with_target else None)
+    return _entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3 if with_target else 2), hip.dev(_target(row_id)) if with_target else None)
 
 
 @pytest.mark.parametrize("row_id", ROW_IDS)
 def test_a_molecule_alone_and_two_runs_give_the_batchs_bits(row_id):
     d = _make(row_id)
     vox = _vox(row_id)
-    t = _dev(_target(row_id))
+    t = hip.dev(_target(row_id))
     whole = _uncut(row_id, True)
     assert _same(_entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3), t), whole)  # two runs
     for b in range(d["B"]):
@@ -334,7 +317,7 @@ def test_molecule_chunks_give_the_uncut_bits(row_id, option, value, nchunk):
     vox = _new_vox(row_id)  # (a voxelizer of its own: the option stays with the handle)
     vox.debug_option(option, value)
     for with_target in (True, False):
-        got = _entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3 if with_target else 2), _dev(_target(row_id)) if with_target else None)
+        got = _entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3 if with_target else 2), hip.dev(_target(row_id)) if with_target else None)
         plan = vox.last_plan()
         assert plan["nchunk"] == nchunk, plan  # the cut really happened, and the entry reports it
         assert _same(got, _uncut(row_id, with_target)), (row_id, with_target)
@@ -345,7 +328,7 @@ def test_the_spatial_order_applies_per_chunk_and_keeps_the_bits():
     vox.debug_option("grad_order", 1)
     vox.debug_option("chunks", 2)
     d = _make("carry")
-    assert _same(_entry(vox, _spec(vox, d, "centred"), _dm("carry", 3), _dev(_target("carry"))), _uncut("carry", True))
+    assert _same(_entry(vox, _spec(vox, d, "centred"), _dm("carry", 3), hip.dev(_target("carry"))), _uncut("carry", True))
     assert vox.last_plan()["nchunk"] == 2
 
 
@@ -358,7 +341,7 @@ def test_bfloat16_and_channels_last_voxelizers_give_the_float32_bits(row_id, kw)
     vox = _vox(row_id, **kw)
     assert vox.forward_batch(**_args(d, 0, 1)).dtype == (torch.bfloat16 if "grid_dtype" in kw else torch.float32)
     for with_target in (True, False):
-        got = _entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3 if with_target else 2), _dev(_target(row_id)) if with_target else None)
+        got = _entry(vox, _spec(vox, d, "centred"), _dm(row_id, 3 if with_target else 2), hip.dev(_target(row_id)) if with_target else None)
         assert _same(got, _uncut(row_id, with_target)), (row_id, with_target)
     # the handle still writes its own grid type afterwards
     assert vox.forward_batch(**_args(d, 0, 1)).dtype == (torch.bfloat16 if "grid_dtype" in kw else torch.float32)
@@ -397,7 +380,7 @@ def test_autograd_gives_coordinate_and_feature_gradients_of_the_ncc_loss():
     d = _make(row_id)
     vox = _new_vox(row_id, differentiable=True, moments_grad=True)
     plain = _new_vox(row_id, differentiable=True)
-    T = _dev(_target(row_id))
+    T = hip.dev(_target(row_id))
     tt = (T.double() ** 2).sum((1, 2, 3))
     a = _args(d)
 
@@ -447,12 +430,12 @@ def test_autograd_gives_pose_gradients_of_the_ncc_loss():
     B = d["B"]
     vox = _new_vox(row_id, differentiable=True, moments_grad=True)
     plain = _new_vox(row_id, differentiable=True)
-    T = _dev(_target(row_id))
+    T = hip.dev(_target(row_id))
     tt = (T.double() ** 2).sum((1, 2, 3))
     a = _args(d)
 
     def leaves():
-        return dict(a, centers=_dev(d["cen"], True), quaternions=_dev(d["q"], True), translations=_dev(d["t"], True))
+        return dict(a, centers=hip.dev(d["cen"], True), quaternions=hip.dev(d["q"], True), translations=hip.dev(d["t"], True))
 
     x = leaves()
     m = vox.moments_posed_batch(target=T, **x)
@@ -502,12 +485,12 @@ def test_the_library_names_what_it_does_not_serve_and_what_it_misses():
         xyz = torch.zeros((3, 3), dtype=torch.float64, device="cuda")
         feat = torch.ones((3, C_), device="cuda") if mode == 0 else torch.zeros(3, dtype=torch.int32, device="cuda")
         g = torch.ones((1, C_, 2 if target is None else 3), dtype=torch.float64, device="cuda")
-        out_c, out_f = _nan((3, 3)), _nan((3, C_), torch.float32)
+        out_c, out_f = hip.nan((3, 3)), hip.nan((3, C_), torch.float32)
         off = np.array([0, 3] if B else [0], np.int64)
-        rc = vox._lib.mvx_moments_backward_batch(vox._handle, mode, xyz.data_ptr(), feat.data_ptr(), _ptr(radii), 1.0, rt, off.ctypes.data,
-                                                 None, B, C_, _ptr(target), g.data_ptr() if gm else None, out_c.data_ptr() if gc else None,
+        rc = vox._lib.mvx_moments_backward_batch(vox._handle, mode, xyz.data_ptr(), feat.data_ptr(), hip.ptr(radii), 1.0, rt, off.ctypes.data,
+                                                 None, B, C_, hip.ptr(target), g.data_ptr() if gm else None, out_c.data_ptr() if gc else None,
                                                  out_f.data_ptr() if gf else None, None)
-        return rc, (vox._lib.mvx_last_error() or b"").decode(), out_c, out_f
+        return rc, last_error(), out_c, out_f
 
     mk = lambda D, rt="scalar", **kw: mv.create_voxelizer(0.5, D, rt, "gaussian", library="hip", **kw)  # noqa: E731
     for vox, kw, words in [

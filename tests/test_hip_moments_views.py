@@ -30,6 +30,8 @@ from tests import moments_grad_reference as MG
 from tests import moments_reference as MR
 from tests import pose_reference as PR
 from tests import views_reference as VW
+from tests import hip_support as hip
+from tests.abi import MVX_ERR_INVALID
 from tests.tolerance import GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +39,6 @@ pytestmark = pytest.mark.gpu
 CEN = np.array([30.0, -20.0, 12.0])
 NORMS = np.array([1.0, 0.9, 1.1])
 RES = 0.5
-MVX_ERR_INVALID = -1
 SEED = 41  # the rotated leg seeds numpy's global generator
 
 # id: mode, C, radii type, density, D, views
@@ -104,33 +105,21 @@ def _vox(row_id, **kw):
     return _new_vox(row_id, **kw)
 
 
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
-
-
-def _nc(d):
-    return d["C"] if d["mode"] == "types" else None
-
-
 def _take(x, index):
     return x if (x is None or np.isscalar(x)) else x[index]
 
 
 def _tensors(d, **over):
-    return {k: over.get(k, _dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
+    return {k: over.get(k, hip.dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
 
 
 def _views(vox, d, target=None, transform="posed", **over):
     """moments_posed_views, or moments_views under the random rotations of np.random.seed(transform)."""
     a = _tensors(d, **over)
     if transform == "posed":
-        return vox.moments_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], target=target, num_channels=_nc(d))
+        return vox.moments_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], target=target, num_channels=hip.nc(d))
     np.random.seed(transform)
-    return vox.moments_views(a["xyz"], a["cen"], a["chan"], a["radii"], target=target, num_channels=_nc(d), random_rotation=True)
+    return vox.moments_views(a["xyz"], a["cen"], a["chan"], a["radii"], target=target, num_channels=hip.nc(d), random_rotation=True)
 
 
 def _batch(vox, d, index, offsets, target=None, transform="posed", **over):
@@ -140,9 +129,9 @@ def _batch(vox, d, index, offsets, target=None, transform="posed", **over):
     xyz = over["rows"] if "rows" in over else a["xyz"][index]
     chan = over["chan_rows"] if "chan_rows" in over else _take(a["chan"], index)
     if transform == "posed":
-        return vox.moments_posed_batch(xyz, offsets, a["cen"], a["q"], a["t"], chan, r, target=target, num_channels=_nc(d))
+        return vox.moments_posed_batch(xyz, offsets, a["cen"], a["q"], a["t"], chan, r, target=target, num_channels=hip.nc(d))
     np.random.seed(transform)
-    return vox.moments_batch(xyz, offsets, a["cen"], chan, r, target=target, num_channels=_nc(d), random_rotation=True)
+    return vox.moments_batch(xyz, offsets, a["cen"], chan, r, target=target, num_channels=hip.nc(d), random_rotation=True)
 
 
 @functools.lru_cache(maxsize=None)
@@ -152,10 +141,10 @@ def _selection(row_id, transform="posed"):
     a = _tensors(d)
     vox = _vox(row_id)
     if transform == "posed":
-        index, offsets = vox._select_views(a["xyz"], a["cen"], a["chan"], a["radii"], num_channels=_nc(d), posed=(a["q"], a["t"]))
+        index, offsets = vox._select_views(a["xyz"], a["cen"], a["chan"], a["radii"], num_channels=hip.nc(d), posed=(a["q"], a["t"]))
     else:
         np.random.seed(transform)
-        index, offsets = vox._select_views(a["xyz"], a["cen"], a["chan"], a["radii"], random_rotation=True, num_channels=_nc(d))
+        index, offsets = vox._select_views(a["xyz"], a["cen"], a["chan"], a["radii"], random_rotation=True, num_channels=hip.nc(d))
     offsets.setflags(write=False)
     return index, offsets
 
@@ -173,7 +162,7 @@ def _views_spec(vox, d):
 
     a = _tensors(d)
     with torch.no_grad():
-        return vox._views_call(a["xyz"], a["cen"], a["chan"], a["radii"], _nc(d), posed=(a["q"], a["t"]), device=True)
+        return vox._views_call(a["xyz"], a["cen"], a["chan"], a["radii"], hip.nc(d), posed=(a["q"], a["t"]), device=True)
 
 
 def _batch_spec(vox, d, index, offsets):
@@ -183,18 +172,8 @@ def _batch_spec(vox, d, index, offsets):
     a = _tensors(d)
     r = _take(a["radii"], index) if d["radii_type"] == "atom-wise" else a["radii"]
     with torch.no_grad():
-        return vox._batch_call(a["xyz"][index], offsets, a["cen"], _take(a["chan"], index), r, _nc(d), posed=(a["q"], a["t"]),
+        return vox._batch_call(a["xyz"][index], offsets, a["cen"], _take(a["chan"], index), r, hip.nc(d), posed=(a["q"], a["t"]),
                                device=True)
-
-
-def _nan(shape, dt=None):
-    import torch
-
-    return torch.full(shape, float("nan"), dtype=dt or torch.float64, device="cuda")
-
-
-def _ptr(x):
-    return None if x is None else x.data_ptr()
 
 
 def _stride(d, T):
@@ -206,8 +185,8 @@ def _abi_forward(vox, d, index, offsets, T, stride=None):
     import torch
 
     call = _views_spec(vox, d)
-    out = _nan((d["B"], d["C"], 2 if T is None else 3))
-    rc = vox._lib.mvx_moments_views(*call.views_args(vox), _ptr(index), None if index is None else offsets.ctypes.data, _ptr(T),
+    out = hip.nan((d["B"], d["C"], 2 if T is None else 3))
+    rc = vox._lib.mvx_moments_views(*call.views_args(vox), hip.ptr(index), None if index is None else offsets.ctypes.data, hip.ptr(T),
                                     _stride(d, T) if stride is None else stride, out.data_ptr(), vox._stream())
     torch.cuda.synchronize()
     return rc, out
@@ -222,9 +201,9 @@ def _rows_views(vox, d, index, offsets, gm, T, stride=None, check=True):
     call = _views_spec(vox, d)
     total = int(offsets[-1])
     g = torch.tensor(np.ascontiguousarray(gm, np.float64), device="cuda")
-    gc, gf = _nan((total, 3)), (_nan((total, d["C"]), torch.float32) if d["mode"] == "features" else None)
-    rc = vox._lib.mvx_moments_backward_views(*call.views_args(vox), index.data_ptr(), offsets.ctypes.data, _ptr(T),
-                                             _stride(d, T) if stride is None else stride, g.data_ptr(), gc.data_ptr(), _ptr(gf),
+    gc, gf = hip.nan((total, 3)), (hip.nan((total, d["C"]), torch.float32) if d["mode"] == "features" else None)
+    rc = vox._lib.mvx_moments_backward_views(*call.views_args(vox), index.data_ptr(), offsets.ctypes.data, hip.ptr(T),
+                                             _stride(d, T) if stride is None else stride, g.data_ptr(), gc.data_ptr(), hip.ptr(gf),
                                              vox._stream())
     torch.cuda.synchronize()
     if not check:
@@ -242,8 +221,8 @@ def _rows_batch(vox, d, index, offsets, gm, T):
     call = _batch_spec(vox, d, index, offsets)
     total = int(offsets[-1])
     g = torch.tensor(np.ascontiguousarray(gm, np.float64), device="cuda")
-    gc, gf = _nan((total, 3)), (_nan((total, d["C"]), torch.float32) if d["mode"] == "features" else None)
-    _lib.check(vox._lib.mvx_moments_backward_batch(*call.batch_args(vox), _ptr(T), g.data_ptr(), gc.data_ptr(), _ptr(gf), vox._stream()))
+    gc, gf = hip.nan((total, 3)), (hip.nan((total, d["C"]), torch.float32) if d["mode"] == "features" else None)
+    _lib.check(vox._lib.mvx_moments_backward_batch(*call.batch_args(vox), hip.ptr(T), g.data_ptr(), gc.data_ptr(), hip.ptr(gf), vox._stream()))
     torch.cuda.synchronize()
     return gc, gf
 
@@ -282,7 +261,7 @@ def test_moments_are_the_batch_entrys_bits_on_the_gathered_rows(row_id):
         cull = (p, RES, d["D"], _cull_source(d), d["radii"], 32, None, None)
         assert float(VW.margin(*cull).min()) > 1e-9
         assert VW.selection_mismatch(index.cpu().numpy(), offsets, *VW.select_exact(*cull)) is None
-    T = _dev(_target(row_id, False))
+    T = hip.dev(_target(row_id, False))
     with_t, plain = _views(vox, d, T), _views(vox, d)
     assert with_t.dtype == torch.float64 and with_t.is_cuda and tuple(with_t.shape) == (B, C_, 3) and tuple(plain.shape) == (B, C_, 2)
     assert not with_t.requires_grad
@@ -305,7 +284,7 @@ def test_rotated_views_draw_as_the_batch_entry_draws(row_id):
     d = _data(row_id)
     vox = _vox(row_id)
     index, offsets = _selection(row_id, SEED)
-    T = _dev(_target(row_id, False))
+    T = hip.dev(_target(row_id, False))
     got = _views(vox, d, T, SEED)
     drawn = np.random.rand()
     assert torch.equal(got, _batch(vox, d, index, offsets, T, SEED))
@@ -319,12 +298,12 @@ def test_bfloat16_and_channels_last_voxelizers_give_the_float32_bits(row_id, kw)
     import torch
 
     d = _data(row_id)
-    T = _dev(_target(row_id, True))
+    T = hip.dev(_target(row_id, True))
     other = _vox(row_id, **kw)
     assert torch.equal(_views(other, d, T), _views(_vox(row_id), d, T))
     assert torch.equal(_views(other, d), _views(_vox(row_id), d))
     a = _tensors(d)  # the handle still writes its own grid type afterwards
-    grid = other.forward_posed_views(a["xyz"], a["cen"][:1], a["q"][:1], a["t"][:1], a["chan"], a["radii"], num_channels=_nc(d))
+    grid = other.forward_posed_views(a["xyz"], a["cen"][:1], a["q"][:1], a["t"][:1], a["chan"], a["radii"], num_channels=hip.nc(d))
     assert grid.dtype == (torch.bfloat16 if "grid_dtype" in kw else torch.float32)
 
 
@@ -333,18 +312,18 @@ def test_views_that_keep_nothing_and_a_cloud_without_atoms():
 
     d = _data("base")
     vox = _new_vox("base", differentiable=True, moments_grad=True)
-    T = _dev(_target("base", True))
-    a = _tensors(d, xyz=_dev(d["xyz"], True), chan=_dev(d["chan"], True))
-    far = _dev(d["cen"] + 500.0)
+    T = hip.dev(_target("base", True))
+    a = _tensors(d, xyz=hip.dev(d["xyz"], True), chan=hip.dev(d["chan"], True))
+    far = hip.dev(d["cen"] + 500.0)
     m = vox.moments_posed_views(a["xyz"], far, a["q"], a["t"], a["chan"], 1.25, target=T)
     assert m.requires_grad and tuple(m.shape) == (5, 5, 3) and not m.any() and not torch.signbit(m).any()
-    (m * _dev(_dm("base", 3))).sum().backward()
+    (m * hip.dev(_dm("base", 3))).sum().backward()
     assert tuple(a["xyz"].grad.shape) == (150, 3) and not a["xyz"].grad.any()
     assert tuple(a["chan"].grad.shape) == (150, 5) and not a["chan"].grad.any()
     plain = _vox("base")
-    none = plain.moments_posed_views(_dev(d["xyz"])[:0], _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), _dev(d["chan"])[:0], 1.25, target=T)
+    none = plain.moments_posed_views(hip.dev(d["xyz"])[:0], hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), hip.dev(d["chan"])[:0], 1.25, target=T)
     assert tuple(none.shape) == (5, 5, 3) and not none.any() and not torch.signbit(none).any()
-    assert tuple(plain.moments_posed_views(_dev(d["xyz"])[:0], _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), _dev(d["chan"])[:0], 1.25).shape) == (5, 5, 2)
+    assert tuple(plain.moments_posed_views(hip.dev(d["xyz"])[:0], hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), hip.dev(d["chan"])[:0], 1.25).shape) == (5, 5, 2)
 
 
 # ---- 2. one target per view ----------------------------------------------------------------------------------------------------------
@@ -354,7 +333,7 @@ def _shared_rows(row_id):
     import torch
 
     d = _data(row_id)
-    T = _dev(_target(row_id, True))
+    T = hip.dev(_target(row_id, True))
     return torch.stack([_views(_vox(row_id), d, T[b])[b] for b in range(d["B"])])
 
 
@@ -363,10 +342,10 @@ def test_a_view_reads_its_own_target(row_id):
     import torch
 
     d = _data(row_id)
-    got = _views(_vox(row_id), d, _dev(_target(row_id, True)))
+    got = _views(_vox(row_id), d, hip.dev(_target(row_id, True)))
     assert tuple(got.shape) == (d["B"], d["C"], 3)
     assert torch.equal(got, _shared_rows(row_id))
-    other = _views(_vox(row_id), d, _dev(_target(row_id, True)[0]))  # (the targets differ, and the views see it)
+    other = _views(_vox(row_id), d, hip.dev(_target(row_id, True)[0]))  # (the targets differ, and the views see it)
     assert torch.equal(other[..., :2], got[..., :2]) and not torch.equal(other[2:, :, 2], got[2:, :, 2])
 
 
@@ -381,11 +360,11 @@ def test_a_view_reads_its_own_target_in_every_chunk(row_id, option, value, nchun
     d = _data(row_id)
     vox = _new_vox(row_id)  # (a voxelizer of its own: the option stays with the handle)
     vox.debug_option(option, value)
-    got = _views(vox, d, _dev(_target(row_id, True)))
+    got = _views(vox, d, hip.dev(_target(row_id, True)))
     plan = vox.last_plan()
     assert plan["nchunk"] == nchunk, plan  # the cut really happened
     assert torch.equal(got, _shared_rows(row_id))
-    assert torch.equal(_views(vox, d, _dev(_target(row_id, False))), _views(_vox(row_id), d, _dev(_target(row_id, False))))
+    assert torch.equal(_views(vox, d, hip.dev(_target(row_id, False))), _views(_vox(row_id), d, hip.dev(_target(row_id, False))))
 
 
 def test_the_rules_that_read_the_handle():
@@ -397,7 +376,7 @@ def test_the_rules_that_read_the_handle():
     d = _data("base")
     vox = _vox("base")
     index, offsets = _selection("base")
-    T = _dev(_target("base", True))
+    T = hip.dev(_target("base", True))
     for stride in (7, 5 * 16 ** 3 - 4, 33 * 16 ** 3):
         rc, out = _abi_forward(vox, d, None, None, T, stride=stride)
         assert rc == MVX_ERR_INVALID and "target_view_stride" in vox._lib.mvx_last_error().decode() and torch.isnan(out).all()
@@ -412,8 +391,8 @@ def test_the_rules_that_read_the_handle():
         (vox, 0, None, torch.zeros(5 * 16 ** 3 + 1, device="cuda")[1:], "16-byte aligned"),
     ]:
         call = _views_spec(vox, d)
-        head = (other._handle,) + call.views_args(vox)[1:4] + (_ptr(radii), 1.25, rt) + call.views_args(vox)[7:]
-        gm, gc = _nan((5, 5, 3)), _nan((int(offsets[-1]), 3))
+        head = (other._handle,) + call.views_args(vox)[1:4] + (hip.ptr(radii), 1.25, rt) + call.views_args(vox)[7:]
+        gm, gc = hip.nan((5, 5, 3)), hip.nan((int(offsets[-1]), 3))
         for rc in (vox._lib.mvx_moments_views(*head, None, None, target.data_ptr(), 0, gm.data_ptr(), None),
                    vox._lib.mvx_moments_backward_views(*head, index.data_ptr(), offsets.ctypes.data, target.data_ptr(), 0, gm.data_ptr(),
                                                        gc.data_ptr(), None, None)):
@@ -423,7 +402,7 @@ def test_the_rules_that_read_the_handle():
     call = _views_spec(vox, d)
     head = call.views_args(vox)[:9] + (None, 0)
     assert vox._lib.mvx_moments_views(*head, None, None, None, 0, None, None) == 0
-    assert vox._lib.mvx_moments_backward_views(*head, index.data_ptr(), None, None, 0, None, _nan((1, 3)).data_ptr(), None, None) == 0
+    assert vox._lib.mvx_moments_backward_views(*head, index.data_ptr(), None, None, 0, None, hip.nan((1, 3)).data_ptr(), None, None) == 0
     # a good call overwrites every row
     gc, gf = _rows_views(vox, d, index, offsets, _dm("base", 3), T)
     assert not torch.isnan(gc).any() and not torch.isnan(gf).any()
@@ -437,13 +416,13 @@ def test_moments_are_those_of_forward_views_grids(row_id):
     d = _data(row_id)
     vox = _vox(row_id)
     a = _tensors(d)
-    grids = vox.forward_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=_nc(d))
+    grids = vox.forward_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=hip.nc(d))
     assert grids.dtype == torch.float32 and tuple(grids.shape) == (d["B"], d["C"]) + (d["D"],) * 3
     g = grids.cpu().numpy()
     T = _target(row_id, True)
     pairs = [MR.moments_and_bound(g[b], T[b]) for b in range(d["B"])]  # (every view against its own target)
     ref, bnd = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
-    got = _views(vox, d, _dev(T)).cpu().numpy()
+    got = _views(vox, d, hip.dev(T)).cpu().numpy()
     err = np.abs(got - ref)
     live = bnd > 0
     assert live.any() and (np.abs(ref[..., 2]) > 0).any()
@@ -467,7 +446,7 @@ def test_rows_are_the_batch_entrys_bits_on_the_compact_batch(row_id):
     d = _data(row_id)
     vox = _vox(row_id)
     index, offsets = _selection(row_id)
-    T = _dev(_target(row_id, False))
+    T = hip.dev(_target(row_id, False))
     for Tk, K in ((T, 3), (None, 2)):
         got = _rows_views(vox, d, index, offsets, _dm(row_id, K), Tk)
         assert _same(got, _rows_batch(vox, d, index, offsets, _dm(row_id, K), Tk)), (row_id, K)
@@ -489,7 +468,7 @@ def _uncut_rows(row_id, with_target):
     d = _data(row_id)
     index, offsets = _selection(row_id)
     return _rows_views(_vox(row_id), d, index, offsets, _dm(row_id, 3 if with_target else 2),
-                       _dev(_target(row_id, True)) if with_target else None)
+                       hip.dev(_target(row_id, True)) if with_target else None)
 
 
 @pytest.mark.parametrize("row_id", ["base", "chunks", "types"])
@@ -505,7 +484,7 @@ def test_rows_of_a_view_come_from_its_own_target(row_id):
         lo, hi = int(offsets[b]), int(offsets[b + 1])
         if hi == lo:
             continue
-        sc, sf = _rows_views(_vox(row_id), d, index, offsets, _dm(row_id, 3), _dev(T[b]))
+        sc, sf = _rows_views(_vox(row_id), d, index, offsets, _dm(row_id, 3), hip.dev(T[b]))
         assert torch.equal(gc[lo:hi], sc[lo:hi]) and (gf is None or torch.equal(gf[lo:hi], sf[lo:hi])), (row_id, b)
         if b >= 2 and d["density"] != "binary":  # (... and not from another view's)
             assert not torch.equal(gc[:lo], sc[:lo])
@@ -523,7 +502,7 @@ def test_cuts_of_the_backward_give_the_uncut_bits_with_a_target_per_view(row_id,
     vox.debug_option(option, value)
     index, offsets = _selection(row_id)
     for with_target in (True, False):
-        got = _rows_views(vox, d, index, offsets, _dm(row_id, 3 if with_target else 2), _dev(_target(row_id, True)) if with_target else None)
+        got = _rows_views(vox, d, index, offsets, _dm(row_id, 3 if with_target else 2), hip.dev(_target(row_id, True)) if with_target else None)
         plan = vox.last_plan()
         assert plan["nchunk"] == nchunk, plan  # the cut really happened, and the entry reports it
         assert _same(got, _uncut_rows(row_id, with_target)), (row_id, with_target)
@@ -533,7 +512,7 @@ def test_cuts_of_the_backward_give_the_uncut_bits_with_a_target_per_view(row_id,
 def _grids(row_id):
     d = _data(row_id)
     a = _tensors(d)
-    g = _vox(row_id).forward_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=_nc(d)).cpu().numpy()
+    g = _vox(row_id).forward_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], num_channels=hip.nc(d)).cpu().numpy()
     assert g.dtype == np.float32
     g.setflags(write=False)
     return g
@@ -587,7 +566,7 @@ def test_seeded_upstreams_match_the_float64_reference(row_id):
     for per_view, K in ((True, 3), (False, 3), (None, 2)):
         target = None if per_view is None else _target(row_id, per_view)
         gm = _dm(row_id, K)
-        gc, gf = _rows_views(vox, d, index, offsets, gm, _dev(target))
+        gc, gf = _rows_views(vox, d, index, offsets, gm, hip.dev(target))
         ref, take = _rows_reference(d, idx, offsets, _grids(row_id), gm, target, rows)
         worst = max(worst, GR.close(gc.cpu().numpy()[take], ref["coords"][take], ref["coords_bound"][take],
                                     f"{row_id} K={K} per_view={per_view} coords", GRAD_REL, GRAD_ABS))
@@ -601,9 +580,9 @@ def test_seeded_upstreams_match_the_float64_reference(row_id):
 def _leaves(d, features):
     import torch
 
-    out = dict(xyz=_dev(d["xyz"], True), cen=_dev(d["cen"], True), q=_dev(d["q"], True), t=_dev(d["t"], True))
+    out = dict(xyz=hip.dev(d["xyz"], True), cen=hip.dev(d["cen"], True), q=hip.dev(d["q"], True), t=hip.dev(d["t"], True))
     if features:
-        out["chan"] = _dev(d["chan"], True)
+        out["chan"] = hip.dev(d["chan"], True)
     torch.cuda.synchronize()
     return out
 
@@ -618,8 +597,8 @@ def test_shared_gradients_are_views_reduce_of_the_rows(row_id, per_view):
     d = _data(row_id)
     N, features = d["N"], d["mode"] == "features"
     vox = _vox(row_id, differentiable=True, moments_grad=True)
-    T = _dev(_target(row_id, per_view))
-    W = _dev(_dm(row_id, 3))
+    T = hip.dev(_target(row_id, per_view))
+    W = hip.dev(_dm(row_id, 3))
 
     def run():
         a = _leaves(d, features)
@@ -643,13 +622,13 @@ def test_shared_gradients_are_views_reduce_of_the_rows(row_id, per_view):
     # centres and poses per view: the reduction of the rows the entry wrote
     spec = _views_spec(vox, d)
     spec.offsets = np.asarray(offsets)
-    gp = vox._pose_backward(spec, _dev(d["xyz"])[index], gc)
+    gp = vox._pose_backward(spec, hip.dev(d["xyz"])[index], gc)
     assert torch.equal(a["cen"].grad, gp[:, :3]) and torch.equal(a["q"].grad, gp[:, 3:7]) and torch.equal(a["t"].grad, gp[:, 7:])
     assert bool(a["q"].grad.any()) and not a["q"].grad[1].any()
     if not per_view:  # the compact batch with leaves of its own
         b = _leaves(d, features)
         rows = b.pop("xyz").detach()[index].requires_grad_()
-        chan_rows = b.pop("chan").detach()[index].requires_grad_() if features else _take(_dev(d["chan"]), index)
+        chan_rows = b.pop("chan").detach()[index].requires_grad_() if features else _take(hip.dev(d["chan"]), index)
         (_batch(vox, d, index, offsets, T, rows=rows, chan_rows=chan_rows, **b) * W).sum().backward()
         assert torch.equal(rows.grad, gc) and (not features or torch.equal(chan_rows.grad, gf))
         for k in b:
@@ -687,7 +666,7 @@ def test_autograd_gives_the_gradients_of_the_ncc_loss_of_the_grid_path():
     B, N = d["B"], d["N"]
     vox = _vox(row_id, differentiable=True, moments_grad=True)
     plain = _vox(row_id, differentiable=True)
-    T = _dev(_target(row_id, True))
+    T = hip.dev(_target(row_id, True))
     tt = (T.double() ** 2).sum((2, 3, 4))
     x = _leaves(d, True)
     m = _views(vox, d, T, **x)
@@ -724,7 +703,7 @@ def test_autograd_gives_the_gradients_of_the_ncc_loss_of_the_grid_path():
 def test_a_change_of_density_between_forward_and_backward_is_refused():
     d = _data("base")
     vox = _new_vox("base", differentiable=True, moments_grad=True)
-    m = _views(vox, d, None, xyz=_dev(d["xyz"], True))
+    m = _views(vox, d, None, xyz=hip.dev(d["xyz"], True))
     vox.density_type = "binary"
     with pytest.raises(RuntimeError, match="changed between the forward call and backward"):
         m.sum().backward()

@@ -11,6 +11,7 @@ import pytest
 from tests import grad_reference as gr
 from tests import pose_reference as pr
 from tests import views_reference as vr
+from tests import hip_support as hip
 from tests.tolerance import (GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL, P64_TOL, assert_exact, assert_gaussian)
 
 pytestmark = pytest.mark.gpu
@@ -44,19 +45,11 @@ def _data(seed, sizes, D, C_, mode, radii_type, precision=32):
     return dict(off=off, cen=cen, xyz=xyz, q=q, t=t, chan=chan, radii=radii, B=B, N=N)
 
 
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
-
-
 def _posed(vox, d, mode, C_, device=True, **over):
     """forward_posed_batch on the batch `d`, inputs as device tensors or as numpy arrays."""
     a = {k: over.get(k, d[k]) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
     if device:
-        a = {k: (v if not isinstance(v, np.ndarray) else _dev(v)) for k, v in a.items()}
+        a = {k: (v if not isinstance(v, np.ndarray) else hip.dev(v)) for k, v in a.items()}
     return vox.forward_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"],
                                    num_channels=C_ if mode == "types" else None)
 
@@ -93,9 +86,9 @@ def test_drawn_quaternions_give_the_random_paths_bits(mode, C_, seed):
     vox = _vox(D)
     np.random.seed(seed)
     quats = np.array([draw_forward_transform(0.0, True)[1] for _ in range(d["B"])])
-    xyz, cen, chan = _dev(d["xyz"]), _dev(d["cen"]), _dev(d["chan"])
+    xyz, cen, chan = hip.dev(d["xyz"]), hip.dev(d["cen"]), hip.dev(d["chan"])
     nc = C_ if mode == "types" else None
-    got = vox.forward_posed_batch(xyz, d["off"], cen, _dev(quats), torch.zeros((d["B"], 3), device="cuda"), chan, 1.25, num_channels=nc)
+    got = vox.forward_posed_batch(xyz, d["off"], cen, hip.dev(quats), torch.zeros((d["B"], 3), device="cuda"), chan, 1.25, num_channels=nc)
     np.random.seed(seed)
     ref = vox.forward_batch(xyz, d["off"], cen, chan, 1.25, num_channels=nc, random_rotation=True)
     assert float(ref.abs().sum()) > 0 and torch.equal(got, ref)
@@ -146,7 +139,7 @@ def test_poses_without_centres_and_in_other_dtypes():
     vox = _vox(D)
     q32 = d["q"].astype(np.float32)
     shifted = d["xyz"] - np.repeat(d["cen"], np.diff(d["off"]), axis=0)
-    got = vox.forward_posed_batch(_dev(shifted), d["off"], None, _dev(q32), _dev(d["t"]), _dev(d["chan"]), 1.25)
+    got = vox.forward_posed_batch(hip.dev(shifted), d["off"], None, hip.dev(q32), hip.dev(d["t"]), hip.dev(d["chan"]), 1.25)
     ref = _posed(vox, d, "features", C_, True, xyz=shifted, cen=np.zeros((3, 3)), q=q32.astype(np.float64),
                  t=d["t"].astype(np.float32))
     assert torch.equal(got, ref)
@@ -199,7 +192,7 @@ def test_posed_views_equal_the_posed_batch_on_the_repeated_cloud(mode, C_, radii
     D = 16
     c = _cloud(D, C_, mode, radii_type)
     vox = _vox(D, radii_type)
-    conv = _dev if device else (lambda x: x)
+    conv = hip.dev if device else (lambda x: x)
     nc = C_ if mode == "types" else None
     got = vox.forward_posed_views(conv(c["xyz"]), conv(c["cen"]), conv(c["q"]), conv(c["t"]), conv(c["chan"]), conv(c["radii"]),
                                   num_channels=nc)
@@ -215,7 +208,7 @@ def test_posed_selection_is_the_reference_selection(mode, C_, radii_type, source
     D = 16
     c = _cloud(D, C_, mode, radii_type)
     vox = _vox(D, radii_type)
-    index, offsets = vox.select_posed_views(_dev(c["xyz"]), _dev(c["cen"]), _dev(c["q"]), _dev(c["t"]), _dev(c["chan"]), _dev(c["radii"]))
+    index, offsets = vox.select_posed_views(hip.dev(c["xyz"]), hip.dev(c["cen"]), hip.dev(c["q"]), hip.dev(c["t"]), hip.dev(c["chan"]), hip.dev(c["radii"]))
     p = pr.view_positions(c["xyz"], c["cen"], c["q"], c["t"])
     ref_index, ref_offsets = vr.select_exact(p, 0.5, D, source, c["radii"], types=c["chan"] if mode == "types" else None,
                                              num_channels=C_ if mode == "types" else None)
@@ -250,11 +243,11 @@ def _pose_backward(vox, d, mode, C_, G, radii=None, pose_dtype=None):
     import torch
 
     pd = pose_dtype or torch.float64
-    xyz = _dev(d["xyz"], True)
+    xyz = hip.dev(d["xyz"], True)
     cen, q, t = (torch.tensor(d[k], device="cuda", dtype=pd, requires_grad=True) for k in ("cen", "q", "t"))
-    chan = _dev(d["chan"], mode == "features")
+    chan = hip.dev(d["chan"], mode == "features")
     r = d["radii"] if radii is None else radii
-    r = r if not isinstance(r, np.ndarray) else _dev(r, vox.radii_grad)
+    r = r if not isinstance(r, np.ndarray) else hip.dev(r, vox.radii_grad)
     grid = vox.forward_posed_batch(xyz, d["off"], cen, q, t, chan, r, num_channels=C_ if mode == "types" else None)
     assert grid.grad_fn is not None
     (grid.double() * torch.as_tensor(G, device="cuda")).sum().backward()
@@ -358,7 +351,7 @@ def test_the_pose_path_leaves_coordinate_and_feature_gradients_as_they_are():
     vox = _vox(D, differentiable=True)
     out = _pose_backward(vox, d, "features", C_, G)
     p = torch.tensor(pr.batch_positions(d["xyz"], d["off"], d["cen"], d["q"], d["t"]), device="cuda", requires_grad=True)
-    f = _dev(d["chan"], True)
+    f = hip.dev(d["chan"], True)
     grid = vox.forward_batch(p, d["off"], None, f, 1.25)
     assert torch.equal(grid, out["grid"])
     (grid.double() * torch.as_tensor(G, device="cuda")).sum().backward()
@@ -412,14 +405,14 @@ def test_posed_views_gradients_match_the_repeated_cloud(mode, C_, radii_type):
     def leaves():
         return [torch.tensor(c[k], device="cuda", requires_grad=True) for k in ("cen", "q", "t")]
 
-    xyz = _dev(c["xyz"], True)
+    xyz = hip.dev(c["xyz"], True)
     cen, q, t = leaves()
-    grid = vox.forward_posed_views(xyz, cen, q, t, _dev(c["chan"]), _dev(c["radii"]), num_channels=nc)
+    grid = vox.forward_posed_views(xyz, cen, q, t, hip.dev(c["chan"]), hip.dev(c["radii"]), num_channels=nc)
     (grid.double() * G).sum().backward()
     rx, rchan, rradii = _repeat(c)
-    xyz2 = _dev(rx, True)
+    xyz2 = hip.dev(rx, True)
     cen2, q2, t2 = leaves()
-    grid2 = vox.forward_posed_batch(xyz2, c["off"], cen2, q2, t2, _dev(rchan), _dev(rradii), num_channels=nc)
+    grid2 = vox.forward_posed_batch(xyz2, c["off"], cen2, q2, t2, hip.dev(rchan), hip.dev(rradii), num_channels=nc)
     assert torch.equal(grid, grid2)
     (grid2.double() * G).sum().backward()
     gc2 = xyz2.grad.cpu().numpy().reshape(c["B"], c["N"], 3)
@@ -442,7 +435,7 @@ def test_device_poses_never_visit_the_host():
     d = _data(7, FULL, D, C_, "features", "scalar")
     G = torch.as_tensor(_upstream(7, d["B"], C_, D, 32), device="cuda", dtype=torch.float32)
     vox = _vox(D, differentiable=True)
-    xyz, chan = _dev(d["xyz"]), _dev(d["chan"])
+    xyz, chan = hip.dev(d["xyz"]), hip.dev(d["chan"])
 
     def step():
         cen, q, t = (torch.tensor(d[k], device="cuda", requires_grad=True) for k in ("cen", "q", "t"))

@@ -13,6 +13,8 @@ import pytest
 from tests import grad_reference as gr
 from tests import pose_reference as pr
 from tests import score_reference as sr
+from tests import hip_support as hip
+from tests.abi import MVX_ERR_INVALID, last_error
 from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +22,6 @@ pytestmark = pytest.mark.gpu
 CEN = np.array([30.0, -20.0, 12.0])
 NORMS = np.array([1.0, 0.8, 1.25])
 FULL, SPARSE = (37, 150, 300), (0, 1, 300)
-MVX_ERR_INVALID = -1
 
 
 def _vox(D, radii_type="scalar", density="gaussian", kind="f32", **kw):
@@ -54,14 +55,6 @@ def _data(seed, sizes, D, C_, mode, radii_type, kind="f32", beyond=False):
                 radii_type=radii_type, kind=kind)
 
 
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
-
-
 def _field(d, per_mol, seed=9):
     """(device field in the grid type of `kind`, the float64 array the kernel reads)."""
     import torch
@@ -83,7 +76,7 @@ def _quats(d, seed):
 
 
 def _call(vox, d, F, transform, per_atom=True, **over):
-    a = {k: over.get(k, _dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
+    a = {k: over.get(k, hip.dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
     nc = d["C"] if d["mode"] == "types" else None
     if transform == "posed":
         return vox.score_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], F, num_channels=nc,
@@ -195,7 +188,7 @@ def test_a_bad_stride_and_a_channel_of_four_gib_are_rejected_before_the_device()
     def entry(vox, C_, stride):
         rc = vox._lib.mvx_score_batch(vox._handle, 0, P, P, None, 1.0, 0, off.ctypes.data, None, 1, C_, P, stride, P, None, None,
                                       None, None)
-        return rc, (vox._lib.mvx_last_error() or b"").decode()
+        return rc, last_error()
 
     vox = _vox(16)
     for stride in (1, 4 * 16 ** 3 - 1, 4 * 16 ** 3 + 1, 16 ** 3, 5 * 16 ** 3):
@@ -217,11 +210,11 @@ def _abi(vox, d, F, entry="score", want=("scores", "atoms", "gc", "gf")):
 
     mode, C_, B, N = d["mode"], d["C"], d["B"], d["N"]
     fdt = torch.float64 if d["kind"] == "f64" else torch.float32
-    c = _dev(d["xyz"])
-    ch = None if mode == "single" else (_dev(d["chan"]).to(fdt) if mode == "features" else _dev(d["chan"]).to(torch.int32))
-    r = None if np.isscalar(d["radii"]) else _dev(d["radii"]).to(fdt)
+    c = hip.dev(d["xyz"])
+    ch = None if mode == "single" else (hip.dev(d["chan"]).to(fdt) if mode == "features" else hip.dev(d["chan"]).to(torch.int32))
+    r = None if np.isscalar(d["radii"]) else hip.dev(d["radii"]).to(fdt)
     rs = float(d["radii"]) if np.isscalar(d["radii"]) else 0.0
-    pose = vox._pack_pose(B, _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), True)
+    pose = vox._pack_pose(B, hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), True)
     xfs = vox._pose_xforms(pose, B)
     nan = lambda shape, dt=torch.float64: torch.full(shape, float("nan"), dtype=dt, device="cuda")  # noqa: E731
     out = dict(scores=nan((B,)), atoms=nan((N,)) if "atoms" in want else None, gc=nan((N, 3)) if "gc" in want else None,
@@ -282,15 +275,15 @@ def test_gradient_rows_are_the_backward_entrys_bits(mode, C_, radii_type, densit
 # ---- 3. autograd --------------------------------------------------------------------------------------------------------------
 def _leaves(d, posed):
     names = ("xyz", "cen", "q", "t") if posed else ("xyz", "cen")
-    a = {k: _dev(d[k], grad=True) for k in names}
+    a = {k: hip.dev(d[k], grad=True) for k in names}
     if d["mode"] == "features":
-        a["chan"] = _dev(d["chan"], grad=True)
+        a["chan"] = hip.dev(d["chan"], grad=True)
     return a
 
 
 def _unfused(vox, d, F, transform, a):
     nc = d["C"] if d["mode"] == "types" else None
-    chan, radii = a.get("chan", _dev(d["chan"])), _dev(d["radii"])
+    chan, radii = a.get("chan", hip.dev(d["chan"])), hip.dev(d["radii"])
     if transform == "posed":
         grid = vox.forward_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], chan, radii, num_channels=nc)
     else:
@@ -302,7 +295,7 @@ def _unfused(vox, d, F, transform, a):
 
 def _fused(vox, d, F, transform, a, per_atom=False):
     nc = d["C"] if d["mode"] == "types" else None
-    chan, radii = a.get("chan", _dev(d["chan"])), _dev(d["radii"])
+    chan, radii = a.get("chan", hip.dev(d["chan"])), hip.dev(d["radii"])
     if transform == "posed":
         return vox.score_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], chan, radii, F, num_channels=nc, per_atom=per_atom)
     np.random.seed(transform)
@@ -350,11 +343,11 @@ def test_only_what_requires_grad_is_recorded():
     Fd, _ = _field(d, False)
     vox = _vox(16, differentiable=True)
     assert not _call(vox, d, Fd, "posed", per_atom=False).requires_grad
-    f = _dev(d["chan"], grad=True)
+    f = hip.dev(d["chan"], grad=True)
     s = _call(vox, d, Fd, "posed", per_atom=False, chan=f)
     s.sum().backward()
-    g = _dev(d["chan"], grad=True)
-    _unfused(vox, d, Fd, "posed", dict(xyz=_dev(d["xyz"]), cen=_dev(d["cen"]), q=_dev(d["q"]), t=_dev(d["t"]), chan=g)).sum().backward()
+    g = hip.dev(d["chan"], grad=True)
+    _unfused(vox, d, Fd, "posed", dict(xyz=hip.dev(d["xyz"]), cen=hip.dev(d["cen"]), q=hip.dev(d["q"]), t=hip.dev(d["t"]), chan=g)).sum().backward()
     assert torch.equal(f.grad, g.grad)
     with torch.no_grad():
         assert not _call(vox, d, Fd, "posed", per_atom=False, chan=f).requires_grad
@@ -371,8 +364,8 @@ def test_a_non_uniform_upstream_matches_the_unfused_path_within_the_gradient_bar
     vox = _vox(D, "atom-wise", differentiable=True)
     wts = np.array([0.37, -2.9, 1.7])
     a, b = _leaves(d, True), _leaves(d, True)
-    (_fused(vox, d, Fd, "posed", a) * _dev(wts)).sum().backward()
-    (_unfused(vox, d, Fd, "posed", b) * _dev(wts)).sum().backward()
+    (_fused(vox, d, Fd, "posed", a) * hip.dev(wts)).sum().backward()
+    (_unfused(vox, d, Fd, "posed", b) * hip.dev(wts)).sum().backward()
     p = _positions(d, "posed")
     for m in range(d["B"]):
         lo, hi = int(d["off"][m]), int(d["off"][m + 1])
@@ -401,13 +394,13 @@ def test_a_per_atom_upstream_is_the_sum_of_the_atoms_own_gradients():
     a = _leaves(d, False)
     scores, atoms = _fused(vox, d, Fd, 41, a, per_atom=True)
     assert torch.equal(scores, _fused(vox, d, Fd, 41, {k: v.detach() for k, v in a.items()}))
-    (atoms * _dev(u)).sum().backward()
+    (atoms * hip.dev(u)).sum().backward()
     gx, gf, gc = torch.zeros_like(a["xyz"]), torch.zeros_like(a["chan"]), torch.zeros_like(a["cen"])
     mol = np.repeat(np.arange(d["B"]), np.diff(d["off"]))
     for v in np.unique(u):
         keep = np.flatnonzero(u == v)
         off = np.concatenate([[0], np.cumsum(np.bincount(mol[keep], minlength=d["B"]))]).astype(np.int64)
-        x, f, c = _dev(d["xyz"][keep], grad=True), _dev(d["chan"][keep], grad=True), _dev(d["cen"], grad=True)
+        x, f, c = hip.dev(d["xyz"][keep], grad=True), hip.dev(d["chan"][keep], grad=True), hip.dev(d["cen"], grad=True)
         np.random.seed(41)
         grid = vox.forward_batch(x, off, c, f, 1.25, random_rotation=True, random_translation=0.5)
         (float(v) * (grid * Fd).sum()).backward()

@@ -28,6 +28,8 @@ import pytest
 
 from tests import hessian_reference as hr
 from tests import pose_reference as pr
+from tests import hip_support as hip
+from tests.abi import last_error
 from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -114,14 +116,6 @@ def _vox(d, **kw):
     return mv.create_voxelizer(0.5, D, d["radii_type"], d["density"], library="hip", precision=64 if d["kind"] == "f64" else 32, **kw)
 
 
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
-
-
 def _field(d):
     """(device field in the grid type of the case, the float64 array the kernel reads)."""
     import torch
@@ -163,9 +157,9 @@ def _call(vox, d, Fd, pivots=None, per_atom=True, **over):
     """(scores, twist_grad, twist_hess, atom_grad, atom_hess) of the case's batch."""
     if d["name"] == "types":
         return _raw(vox, d, Fd, pivots)
-    a = {k: over.get(k, _dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
+    a = {k: over.get(k, hip.dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
     nc = d["C"] if d["mode"] == "types" else None
-    piv = None if pivots is None else _dev(np.asarray(pivots, np.float64))
+    piv = None if pivots is None else hip.dev(np.asarray(pivots, np.float64))
     if d["posed"]:
         return vox.score_hessian_posed_batch(a["xyz"], d["off"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], Fd, num_channels=nc,
                                              pivots=piv, per_atom=per_atom)
@@ -177,12 +171,12 @@ def _first_order(d, Fd):
     if d["name"] == "types":
         return _raw(_vox(d), d, Fd, first_order=True)
     vox = _vox(d, differentiable=True)
-    xyz = _dev(d["xyz"], grad=True)
+    xyz = hip.dev(d["xyz"], grad=True)
     nc = d["C"] if d["mode"] == "types" else None
     if d["posed"]:
-        scores = vox.score_posed_batch(xyz, d["off"], _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), _dev(d["chan"]), _dev(d["radii"]), Fd, num_channels=nc)
+        scores = vox.score_posed_batch(xyz, d["off"], hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), hip.dev(d["chan"]), hip.dev(d["radii"]), Fd, num_channels=nc)
     else:
-        scores = vox.score_batch(xyz, d["off"], _dev(d["cen"]), _dev(d["chan"]), _dev(d["radii"]), Fd, num_channels=nc)
+        scores = vox.score_batch(xyz, d["off"], hip.dev(d["cen"]), hip.dev(d["chan"]), hip.dev(d["radii"]), Fd, num_channels=nc)
     scores.sum().backward()
     return scores.detach(), xyz.grad
 
@@ -420,7 +414,7 @@ def test_one_undamped_newton_step_raises_the_score_and_lowers_the_gradient():
 
     d = _sub(_data("single"), 0)
     vox = _vox(d)
-    xyz, cen = _dev(d["xyz"]), _dev(d["cen"])
+    xyz, cen = hip.dev(d["xyz"]), hip.dev(d["cen"])
     q0 = torch.tensor([[1.0, 0.0, 0.0, 0.0]], dtype=torch.float64, device="cuda")
     t0 = torch.zeros((1, 3), dtype=torch.float64, device="cuda")
     field = vox.forward_posed_batch(xyz, d["off"], cen, q0, t0, None, d["radii"])[0]  # the molecule's own grid at the identity pose
@@ -454,7 +448,7 @@ def test_a_bad_stride_is_rejected_before_the_entrys_own_rules():
     def entry(stride, radii_type=1, twist_grad=P):
         rc = vox._lib.mvx_score_hessian_batch(vox._handle, 0, P, P, P, 1.0, radii_type, off.ctypes.data, None, 1, 5, P, stride, None, P, None,
                                               None, twist_grad, P, None)
-        return rc, (vox._lib.mvx_last_error() or b"").decode()
+        return rc, last_error()
 
     rc, msg = entry(7, radii_type=2, twist_grad=None)
     assert rc == -1 and "field_mol_stride" in msg, (rc, msg)

@@ -30,6 +30,8 @@ import pytest
 from tests import hessian_reference as hr
 from tests import lm_rows as R
 from tests import pose_reference as pr
+from tests import hip_support as hip
+from tests.abi import last_error
 from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -83,12 +85,6 @@ def _vox(d, **kw):
     return mv.create_voxelizer(0.5, D, d["radii_type"], d["density"], library="hip", precision=64 if d["kind"] == "f64" else 32, **kw)
 
 
-def _dev(x):
-    import torch
-
-    return x if (x is None or np.isscalar(x)) else torch.tensor(x, device="cuda")
-
-
 def _field(d):
     """(device field in the grid type of the case, the float64 array the kernel reads)."""
     import torch
@@ -98,16 +94,12 @@ def _field(d):
     return Fd, Fd.to(torch.float64).cpu().numpy()
 
 
-def _nc(d):
-    return d["C"] if d["mode"] == "types" else None
-
-
 def _views(vox, d, Fd, posed=True, per_atom=True, pivots=None):
-    a = {k: _dev(d[k]) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
+    a = {k: hip.dev(d[k]) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
     if posed:
-        return vox.score_hessian_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], Fd, num_channels=_nc(d),
-                                             pivots=_dev(pivots), per_atom=per_atom)
-    return vox.score_hessian_views(a["xyz"], a["cen"], a["chan"], a["radii"], Fd, num_channels=_nc(d), pivots=_dev(pivots), per_atom=per_atom)
+        return vox.score_hessian_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], Fd, num_channels=hip.nc(d),
+                                             pivots=hip.dev(pivots), per_atom=per_atom)
+    return vox.score_hessian_views(a["xyz"], a["cen"], a["chan"], a["radii"], Fd, num_channels=hip.nc(d), pivots=hip.dev(pivots), per_atom=per_atom)
 
 
 def _take(x, index):
@@ -116,13 +108,13 @@ def _take(x, index):
 
 def _batch(vox, d, Fd, index, offsets, posed=True, pivots=None):
     """The same records on the gathered rows: (scores, twist_grad, twist_hess, atom_grad, atom_hess)."""
-    a = {k: _dev(d[k]) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
+    a = {k: hip.dev(d[k]) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
     r = _take(a["radii"], index) if d["radii_type"] == "atom-wise" else a["radii"]
     xyz, chan = a["xyz"][index], _take(a["chan"], index)
     if posed:
-        return vox.score_hessian_posed_batch(xyz, offsets, a["cen"], a["q"], a["t"], chan, r, Fd, num_channels=_nc(d), pivots=_dev(pivots),
+        return vox.score_hessian_posed_batch(xyz, offsets, a["cen"], a["q"], a["t"], chan, r, Fd, num_channels=hip.nc(d), pivots=hip.dev(pivots),
                                              per_atom=True)
-    return vox.score_hessian_batch(xyz, offsets, a["cen"], chan, r, Fd, num_channels=_nc(d), pivots=_dev(pivots), per_atom=True)
+    return vox.score_hessian_batch(xyz, offsets, a["cen"], chan, r, Fd, num_channels=hip.nc(d), pivots=hip.dev(pivots), per_atom=True)
 
 
 def _repeated(vox, d, Fd, posed=True):
@@ -306,7 +298,7 @@ def test_a_bad_stride_is_rejected_before_the_entrys_own_rules():
     def entry(stride, radii_type=1, twist_grad=P):
         rc = vox._lib.mvx_score_hessian_views(vox._handle, 0, P, P, P, 1.0, radii_type, 3, 5, C.addressof(xfs), 1, None, None, P, stride, None, P,
                                               None, None, twist_grad, P, None)
-        return rc, (vox._lib.mvx_last_error() or b"").decode()
+        return rc, last_error()
 
     rc, msg = entry(7, radii_type=2, twist_grad=None)
     assert rc == -1 and "field_view_stride" in msg, (rc, msg)

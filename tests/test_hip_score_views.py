@@ -16,6 +16,8 @@ from tests import pose_reference as pr
 from tests import score_reference as sr
 from tests import views_reduce_reference as vr
 from tests import views_reference as vw
+from tests import hip_support as hip
+from tests.abi import MVX_ERR_INVALID
 from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +25,6 @@ pytestmark = pytest.mark.gpu
 CEN = np.array([30.0, -20.0, 12.0])
 NORMS = np.array([1.0, 0.8, 1.25])
 D, RES = 16, 0.5
-MVX_ERR_INVALID = -1
 
 
 def _vox(radii_type="scalar", density="gaussian", kind="f32", **kw):
@@ -32,14 +33,6 @@ def _vox(radii_type="scalar", density="gaussian", kind="f32", **kw):
     if kind == "bf16":
         kw["grid_dtype"] = "bfloat16"
     return mv.create_voxelizer(RES, D, radii_type, density, library="hip", precision=64 if kind == "f64" else 32, **kw)
-
-
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
 
 
 # ---- 1. the reduction: slot lookup and coverage, exactly --------------------------------------------------------------------
@@ -182,17 +175,13 @@ def _field(d, per_view, seed=9):
     return Fd, Fd.to(torch.float64).cpu().numpy()
 
 
-def _nc(d):
-    return d["C"] if d["mode"] == "types" else None
-
-
 def _views(vox, d, F, transform, per_atom=True, **over):
     """score_posed_views, or score_views under the random rotations of np.random.seed(transform)."""
-    a = {k: over.get(k, _dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
+    a = {k: over.get(k, hip.dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
     if transform == "posed":
-        return vox.score_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], F, num_channels=_nc(d), per_atom=per_atom)
+        return vox.score_posed_views(a["xyz"], a["cen"], a["q"], a["t"], a["chan"], a["radii"], F, num_channels=hip.nc(d), per_atom=per_atom)
     np.random.seed(transform)
-    return vox.score_views(a["xyz"], a["cen"], a["chan"], a["radii"], F, num_channels=_nc(d), random_rotation=True, per_atom=per_atom)
+    return vox.score_views(a["xyz"], a["cen"], a["chan"], a["radii"], F, num_channels=hip.nc(d), random_rotation=True, per_atom=per_atom)
 
 
 def _take(x, index):
@@ -201,14 +190,14 @@ def _take(x, index):
 
 def _batch(vox, d, F, transform, index, offsets, per_atom=True, **over):
     """The same records on the gathered rows: score_posed_batch / score_batch on coords[index], channels[index] and offsets."""
-    a = {k: over.get(k, _dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
+    a = {k: over.get(k, hip.dev(d[k])) for k in ("xyz", "cen", "q", "t", "chan", "radii")}
     r = _take(a["radii"], index) if d["radii_type"] == "atom-wise" else a["radii"]
     xyz = over["rows"] if "rows" in over else a["xyz"][index]
     chan = over["chan_rows"] if "chan_rows" in over else _take(a["chan"], index)
     if transform == "posed":
-        return vox.score_posed_batch(xyz, offsets, a["cen"], a["q"], a["t"], chan, r, F, num_channels=_nc(d), per_atom=per_atom)
+        return vox.score_posed_batch(xyz, offsets, a["cen"], a["q"], a["t"], chan, r, F, num_channels=hip.nc(d), per_atom=per_atom)
     np.random.seed(transform)
-    return vox.score_batch(xyz, offsets, a["cen"], chan, r, F, num_channels=_nc(d), random_rotation=True, per_atom=per_atom)
+    return vox.score_batch(xyz, offsets, a["cen"], chan, r, F, num_channels=hip.nc(d), random_rotation=True, per_atom=per_atom)
 
 
 def _quats(B, seed):
@@ -239,7 +228,7 @@ def _abi_records(vox, d, transform):
 
     B = d["B"]
     if transform == "posed":
-        pose = vox._pack_pose(B, _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), True)
+        pose = vox._pack_pose(B, hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), True)
         return vox._pose_xforms(pose, B), pose
     xfs = (_lib.MvxXform * B)()
     for b, qb in enumerate(_quats(B, transform)):
@@ -257,7 +246,7 @@ def _abi(vox, d, F, per_view, xfs, index=None, offsets=None, gathered=False, row
     from molvoxel_amd.voxelizer.hip import _lib
 
     kind = None if d["mode"] == "single" else d["mode"]
-    xyz, chan, radii = _dev(d["xyz"]), _dev(d["chan"]), _dev(d["radii"])
+    xyz, chan, radii = hip.dev(d["xyz"]), hip.dev(d["chan"]), hip.dev(d["radii"])
     if gathered:
         xyz, chan = xyz[index], _take(chan, index)
         radii = _take(radii, index) if d["radii_type"] == "atom-wise" else radii
@@ -402,16 +391,16 @@ def test_views_that_keep_nothing_and_a_cloud_without_atoms():
     d = _data(33, 150, 4, 5, "features", "scalar")
     Fd, _ = _field(d, False)
     vox = _vox(differentiable=True)
-    far = _dev(d["cen"] + 500.0)
-    xyz, chan = _dev(d["xyz"], True), _dev(d["chan"], True)
-    scores, atoms, index, offsets = vox.score_posed_views(xyz, far, _dev(d["q"]), _dev(d["t"]), chan, 1.25, Fd, per_atom=True)
+    far = hip.dev(d["cen"] + 500.0)
+    xyz, chan = hip.dev(d["xyz"], True), hip.dev(d["chan"], True)
+    scores, atoms, index, offsets = vox.score_posed_views(xyz, far, hip.dev(d["q"]), hip.dev(d["t"]), chan, 1.25, Fd, per_atom=True)
     assert not offsets.any() and index.numel() == 0 and atoms.numel() == 0
     assert not scores.any() and not torch.signbit(scores).any()
     (scores * torch.arange(1.0, 5.0, device="cuda")).sum().backward()
     assert tuple(xyz.grad.shape) == (150, 3) and not xyz.grad.any() and tuple(chan.grad.shape) == (150, 5) and not chan.grad.any()
-    only = vox.score_posed_views(xyz.detach(), far, _dev(d["q"]), _dev(d["t"]), chan.detach(), 1.25, Fd)
+    only = vox.score_posed_views(xyz.detach(), far, hip.dev(d["q"]), hip.dev(d["t"]), chan.detach(), 1.25, Fd)
     assert tuple(only.shape) == (4,) and not only.any()
-    none = vox.score_posed_views(xyz.detach()[:0], far, _dev(d["q"]), _dev(d["t"]), chan.detach()[:0], 1.25, Fd)
+    none = vox.score_posed_views(xyz.detach()[:0], far, hip.dev(d["q"]), hip.dev(d["t"]), chan.detach()[:0], 1.25, Fd)
     assert tuple(none.shape) == (4,) and not none.any() and not torch.signbit(none).any()
 
 
@@ -428,11 +417,11 @@ def test_a_bad_stride_is_rejected_with_a_real_handle():
 def _leaves(d, posed, features):
     import torch
 
-    out = dict(xyz=_dev(d["xyz"], True), cen=_dev(d["cen"], True))
+    out = dict(xyz=hip.dev(d["xyz"], True), cen=hip.dev(d["cen"], True))
     if features:
-        out["chan"] = _dev(d["chan"], True)
+        out["chan"] = hip.dev(d["chan"], True)
     if posed:
-        out.update(q=_dev(d["q"], True), t=_dev(d["t"], True))
+        out.update(q=hip.dev(d["q"], True), t=hip.dev(d["t"], True))
     torch.cuda.synchronize()
     return out
 
@@ -459,13 +448,13 @@ def test_shared_gradients_are_the_reduction_of_the_compact_batchs(mode, C_, radi
     Fd, _ = _field(d, per_view)
     vox = _vox(radii_type, density, kind, differentiable=True)
     rng = np.random.default_rng(5)
-    w = _dev(rng.uniform(0.5, 2.0, B) * rng.choice([-1.0, 1.0], B))
+    w = hip.dev(rng.uniform(0.5, 2.0, B) * rng.choice([-1.0, 1.0], B))
     posed, features = transform == "posed", mode == "features"
 
     def run():
         a = _leaves(d, posed, features)
         scores, atoms, index, offsets = _views(vox, d, Fd, transform, **a)
-        wa = _dev(np.random.default_rng(6).standard_normal(int(offsets[-1])))
+        wa = hip.dev(np.random.default_rng(6).standard_normal(int(offsets[-1])))
         L = (scores * w).sum() + ((atoms * wa).sum() if per_atom else 0.0)
         L.backward()
         return a, index, offsets, wa
@@ -477,7 +466,7 @@ def test_shared_gradients_are_the_reduction_of_the_compact_batchs(mode, C_, radi
     # the compact batch with leaves of its own
     b = _leaves(d, posed, features)
     rows = b.pop("xyz").detach()[index].requires_grad_()
-    chan_rows = b.pop("chan").detach()[index].requires_grad_() if features else _take(_dev(d["chan"]), index)
+    chan_rows = b.pop("chan").detach()[index].requires_grad_() if features else _take(hip.dev(d["chan"]), index)
     s_b, a_b = _batch(vox, d, Fd, transform, index, offsets, rows=rows, chan_rows=chan_rows, **b)
     ((s_b * w).sum() + ((a_b * wa).sum() if per_atom else 0.0)).backward()
     idx = index.cpu().numpy()
@@ -517,19 +506,19 @@ def test_finite_differences_at_precision_64():
     Fd, _ = _field(d, True)
     vox = _vox("scalar", "gaussian", "f64", differentiable=True)
     mask = _vox("scalar", "binary", "f64")
-    w = _dev(np.array([1.5, -0.7, 1.1]))
-    chan = _dev(d["chan"])
+    w = hip.dev(np.array([1.5, -0.7, 1.1]))
+    chan = hip.dev(d["chan"])
     ids = torch.arange(N, device="cuda")
 
     def loss(xyz, q, t):
         with torch.no_grad():
-            return float((vox.score_posed_views(_dev(xyz), _dev(d["cen"]), _dev(q), _dev(t), chan, 1.25, Fd) * w).sum())
+            return float((vox.score_posed_views(hip.dev(xyz), hip.dev(d["cen"]), hip.dev(q), hip.dev(t), chan, 1.25, Fd) * w).sum())
 
     def support(xyz, q, t):
-        return mask.forward_posed_views(_dev(xyz), _dev(d["cen"]), _dev(q), _dev(t), ids, 1.25, num_channels=N) != 0
+        return mask.forward_posed_views(hip.dev(xyz), hip.dev(d["cen"]), hip.dev(q), hip.dev(t), ids, 1.25, num_channels=N) != 0
 
-    a = dict(xyz=_dev(d["xyz"], True), q=_dev(d["q"], True), t=_dev(d["t"], True))
-    (vox.score_posed_views(a["xyz"], _dev(d["cen"]), a["q"], a["t"], chan, 1.25, Fd) * w).sum().backward()
+    a = dict(xyz=hip.dev(d["xyz"], True), q=hip.dev(d["q"], True), t=hip.dev(d["t"], True))
+    (vox.score_posed_views(a["xyz"], hip.dev(d["cen"]), a["q"], a["t"], chan, 1.25, Fd) * w).sum().backward()
     base = support(d["xyz"], d["q"], d["t"])
     assert bool(base.any(dim=(2, 3, 4)).all())  # every view keeps every atom
     h, checked = 2.0 ** -20, 0
@@ -559,7 +548,7 @@ def test_a_step_with_device_poses_does_not_synchronise_outside_the_selection():
     d = _data(36, 150, 5, 32, "features", "scalar")
     Fd, _ = _field(d, False)
     vox = _vox(differentiable=True)
-    w = _dev(np.array([1.0, -2.0, 0.5, 1.5, -1.0]))
+    w = hip.dev(np.array([1.0, -2.0, 0.5, 1.5, -1.0]))
 
     def step():
         a = _leaves(d, True, True)

@@ -8,12 +8,13 @@ import numpy as np
 import pytest
 
 from tests import sum_rows as R
+from tests import hip_support as hip
+from tests.abi import MVX_ERR_INVALID, last_error
 from tests.tolerance import GRAD_ABS, GRAD_REL, assert_exact, assert_gaussian, gaussian_excess
 
 pytestmark = pytest.mark.gpu
 
 FEATURE_ROWS = [r.id for r in R.ROWS if r.mode == "features"]
-MVX_ERR_INVALID = -1
 
 
 @functools.lru_cache(maxsize=None)
@@ -22,14 +23,6 @@ def _vox(row_id, radii_type=None, **kw):
 
     row = R.BY_ID[row_id]
     return mv.create_voxelizer(0.5, row.D, radii_type or row.radii_type, row.density, library="hip", **dict(kw))
-
-
-def _dev(x, grad=False):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    return torch.tensor(x, device="cuda", requires_grad=grad)
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,8 +47,8 @@ def _sum(vox, d, weights=None, lo=0, hi=None, out_grid=None, accumulate=False, *
     radii = d["radii"][a0:a1] if d["row"].radii_type == "atom-wise" else d["radii"]
     if weights is not None:
         weights = weights[a0:a1] if len(weights) == d["N"] else weights[lo:hi]
-    return vox.forward_sum(_dev(d["xyz"][a0:a1]), d["off"][lo:hi + 1] - a0, _dev(d["cen"][lo:hi]), _dev(chan), _dev(radii),
-                           weights=None if weights is None else _dev(weights), num_channels=_nc(d), out_grid=out_grid,
+    return vox.forward_sum(hip.dev(d["xyz"][a0:a1]), d["off"][lo:hi + 1] - a0, hip.dev(d["cen"][lo:hi]), hip.dev(chan), hip.dev(radii),
+                           weights=None if weights is None else hip.dev(weights), num_channels=_nc(d), out_grid=out_grid,
                            accumulate=accumulate, **kw)
 
 
@@ -101,19 +94,19 @@ def test_unweighted_and_centred_only_is_the_forward_on_the_merged_molecule(row_i
     d = R.make(row_id)
     row = d["row"]
     got = _uncut(row_id)
-    m = _dev(R.merged(d))
+    m = hip.dev(R.merged(d))
     vox = _vox(row_id)
     if row.mode == "features":
-        ref = vox.forward_features(m, None, _dev(d["chan"]), _dev(d["radii"]))
+        ref = vox.forward_features(m, None, hip.dev(d["chan"]), hip.dev(d["radii"]))
     elif row.mode == "single":
         ref = vox.forward_single(m, None, d["radii"])
     else:
         # (forward_types refuses a negative type: the merged molecule without that atom - it reaches no voxel - and, with it, the
         # batched entry on the one merged molecule)
         keep = np.arange(d["N"]) != R.BAD_TYPE_ATOM
-        ref = vox.forward_types(_dev(R.merged(d)[keep]), None, _dev(d["chan"][keep]), _dev(d["radii"]),
+        ref = vox.forward_types(hip.dev(R.merged(d)[keep]), None, hip.dev(d["chan"][keep]), hip.dev(d["radii"]),
                                 out_grid=torch.empty((row.C,) + (row.D,) * 3, device="cuda"))
-        one = vox.forward_batch(m, np.array([0, d["N"]]), None, _dev(d["chan"]), _dev(d["radii"]), num_channels=row.C)[0]
+        one = vox.forward_batch(m, np.array([0, d["N"]]), None, hip.dev(d["chan"]), hip.dev(d["radii"]), num_channels=row.C)[0]
         assert_exact(got, one.cpu().numpy())
     assert_exact(got, ref.cpu().numpy())
 
@@ -247,7 +240,7 @@ def test_the_library_names_what_it_does_not_serve():
         off = np.array([0, 3], np.int64)
         rc = vox._lib.mvx_forward_sum_batch(vox._handle, 0, xyz.data_ptr(), feat.data_ptr(), None if radii is None else radii.data_ptr(),
                                             1.0, rt, off.ctypes.data, None, 1, C_, None, out.data_ptr(), 0, None)
-        return rc, (vox._lib.mvx_last_error() or b"").decode()
+        return rc, last_error()
 
     mk = lambda D, rt="scalar", **kw: mv.create_voxelizer(0.5, D, rt, "gaussian", library="hip", **kw)  # noqa: E731
     for vox, kw, words in [
@@ -283,10 +276,10 @@ def test_rotated_sums_are_the_weighted_sum_of_forward_batchs_grids(row_id):
     d = R.make(row_id)
     vox = _vox(row_id)
     w = _weights(row_id, "mol")
-    a = dict(coords=_dev(d["xyz"]), offsets=d["off"], centers=_dev(d["cen"]), channels=_dev(d["chan"]), radii=_dev(d["radii"]),
+    a = dict(coords=hip.dev(d["xyz"]), offsets=d["off"], centers=hip.dev(d["cen"]), channels=hip.dev(d["chan"]), radii=hip.dev(d["radii"]),
              num_channels=_nc(d))
     np.random.seed(77)
-    got = vox.forward_sum(weights=_dev(w), random_rotation=True, random_translation=0.3, **a)
+    got = vox.forward_sum(weights=hip.dev(w), random_rotation=True, random_translation=0.3, **a)
     np.random.seed(77)
     grids = vox.forward_batch(random_rotation=True, random_translation=0.3, **a)
     _check_weighted_sum(got.cpu().numpy(), grids, w, f"{row_id} rotated")
@@ -297,9 +290,9 @@ def test_posed_sums_are_the_weighted_sum_of_forward_posed_batchs_grids(row_id):
     d = R.make(row_id)
     vox = _vox(row_id)
     w = _weights(row_id, "mol")
-    a = dict(coords=_dev(d["xyz"]), offsets=d["off"], centers=_dev(d["cen"]), quaternions=_dev(d["q"]), translations=_dev(d["t"]),
-             channels=_dev(d["chan"]), radii=_dev(d["radii"]), num_channels=_nc(d))
-    got = vox.forward_posed_sum(weights=_dev(w), **a)
+    a = dict(coords=hip.dev(d["xyz"]), offsets=d["off"], centers=hip.dev(d["cen"]), quaternions=hip.dev(d["q"]), translations=hip.dev(d["t"]),
+             channels=hip.dev(d["chan"]), radii=hip.dev(d["radii"]), num_channels=_nc(d))
+    got = vox.forward_posed_sum(weights=hip.dev(w), **a)
     grids = vox.forward_posed_batch(**a)
     _check_weighted_sum(got.cpu().numpy(), grids, w, f"{row_id} posed")
     # poses given on the host take the same route
@@ -313,10 +306,10 @@ BF16_HALF_ULP = 2.0 ** -8  # rounding a value v to bfloat16 moves it by at most 
 
 def _score_args(d, posed, grad=False):
     feat = d["row"].mode == "features"
-    a = dict(coords=_dev(d["xyz"], grad), offsets=d["off"], centers=_dev(d["cen"], grad), channels=_dev(d["chan"], grad and feat),
-             radii=_dev(d["radii"]), num_channels=_nc(d))
+    a = dict(coords=hip.dev(d["xyz"], grad), offsets=d["off"], centers=hip.dev(d["cen"], grad), channels=hip.dev(d["chan"], grad and feat),
+             radii=hip.dev(d["radii"]), num_channels=_nc(d))
     if posed:
-        a.update(quaternions=_dev(d["q"], grad), translations=_dev(d["t"], grad))
+        a.update(quaternions=hip.dev(d["q"], grad), translations=hip.dev(d["t"], grad))
     return a
 
 
@@ -380,8 +373,8 @@ def test_a_per_atom_upstream_weights_every_atom_by_its_own_sum():
     ((scores * g).sum() + (atoms * ga).sum()).backward()
     lengths = np.diff(d["off"])
     rep = lambda x: np.repeat(x, lengths, axis=0)  # noqa: E731
-    grids = _vox("light").forward_posed_batch(_dev(d["xyz"]), np.arange(d["N"] + 1), _dev(rep(d["cen"])), _dev(rep(d["q"])),
-                                              _dev(rep(d["t"])), _dev(d["chan"]), d["radii"])
+    grids = _vox("light").forward_posed_batch(hip.dev(d["xyz"]), np.arange(d["N"] + 1), hip.dev(rep(d["cen"])), hip.dev(rep(d["q"])),
+                                              hip.dev(rep(d["t"])), hip.dev(d["chan"]), d["radii"])
     w = (rep(g.cpu().numpy()) + ga.cpu().numpy()).astype(np.float32)  # (rounded to float32, as the call rounds it)
     _check_weighted_sum(field.grad.cpu().numpy(), grids, w, "light per-atom upstream")
 
@@ -423,8 +416,8 @@ def test_a_field_gradient_step_allocates_far_less_than_the_grids():
     xyz = np.repeat(cen, sizes, axis=0) + rng.uniform(-2.0, 2.0, (N, 3))
     q = rng.standard_normal((B, 4))
     q /= np.linalg.norm(q, axis=1)[:, None]
-    a = dict(coords=_dev(xyz, True), offsets=off, centers=_dev(cen), quaternions=_dev(q, True), translations=_dev(rng.uniform(-0.5, 0.5, (B, 3)), True),
-             channels=_dev(rng.random((N, C_)).astype(np.float32)), radii=1.0)
+    a = dict(coords=hip.dev(xyz, True), offsets=off, centers=hip.dev(cen), quaternions=hip.dev(q, True), translations=hip.dev(rng.uniform(-0.5, 0.5, (B, 3)), True),
+             channels=hip.dev(rng.random((N, C_)).astype(np.float32)), radii=1.0)
     import molvoxel_amd as mv
 
     vox = mv.create_voxelizer(0.5, D, "scalar", "gaussian", library="hip", differentiable=True, field_grad=True)

@@ -12,6 +12,7 @@ import pytest
 import tests.test_hip_sum as HS  # (_sum, _weights, _vox, _fresh, _dev: forward_sum on the molecules [lo, hi) of a row)
 import tests.test_hip_views_sum as VS  # (the views cases)
 from tests import sum_rows as R
+from tests import hip_support as hip
 from tests.tolerance import GRAD_ABS, GRAD_REL, assert_exact, assert_gaussian, gaussian_excess
 
 pytestmark = pytest.mark.gpu
@@ -186,11 +187,11 @@ def test_views_sum_in_three_parts_is_the_chain_of_the_parts_views(case_id):
     w = c["w"]
     vox3 = mv.create_voxelizer(1.0, VS.D, c["rt"], c["density"], library="hip")
     vox3.set_sum_parts(3)
-    got = VS._views_sum(c, vox=vox3, weights=VS._dev(w))
+    got = VS._views_sum(c, vox=vox3, weights=hip.dev(w))
     r = torch.zeros_like(got)
     for lo, hi in _ranges(VS.B, 3):
-        r = r + c["vox"].forward_views_sum(VS._dev(c["xyz"]), VS._dev(c["cen"][lo:hi]), VS._dev(c["chan"]), VS._dev(c["radii"]),
-                                           weights=VS._dev(w[lo:hi]), num_channels=c["nc"])
+        r = r + c["vox"].forward_views_sum(hip.dev(c["xyz"]), hip.dev(c["cen"][lo:hi]), hip.dev(c["chan"]), hip.dev(c["radii"]),
+                                           weights=hip.dev(w[lo:hi]), num_channels=c["nc"])
     assert float(r.abs().max()) > 0
     assert_exact(got.cpu().numpy(), r.cpu().numpy())
 

@@ -14,6 +14,7 @@ import pytest
 import tests.test_hip_sum as HS  # (_sum: forward_sum on the molecules [lo, hi) of a batch; _dev)
 import tests.test_hip_sum_parts as PS  # (_ranges: the parts of the contract)
 from tests import sum_sweep_rows as S
+from tests import hip_support as hip
 from tests.tolerance import GRAD_ABS, GRAD_REL, assert_exact, assert_gaussian, gaussian_excess
 
 pytestmark = pytest.mark.gpu
@@ -150,12 +151,12 @@ def test_unweighted_is_the_forward_on_the_merged_molecule_with_the_same_blockdim
     assert vox.blockdim == (row.blockdim or 8)
     m = S.merged(d)
     if row.mode == "features":
-        ref = vox.forward_features(HS._dev(m), None, HS._dev(d["chan"]), HS._dev(d["radii"]))
+        ref = vox.forward_features(hip.dev(m), None, hip.dev(d["chan"]), hip.dev(d["radii"]))
     elif row.mode == "single":
-        ref = vox.forward_single(HS._dev(m), None, HS._dev(d["radii"]))
+        ref = vox.forward_single(hip.dev(m), None, hip.dev(d["radii"]))
     else:  # (forward_types refuses the one type outside [0, C): the merged molecule without that atom, which reaches no voxel)
         keep = np.arange(d["N"]) != S.R.BAD_TYPE_ATOM
-        ref = vox.forward_types(HS._dev(m[keep]), None, HS._dev(d["chan"][keep]), HS._dev(d["radii"]),
+        ref = vox.forward_types(hip.dev(m[keep]), None, hip.dev(d["chan"][keep]), hip.dev(d["radii"]),
                                 out_grid=torch.empty((row.C,) + (row.D,) * 3, device="cuda"))
     assert float(ref.abs().max()) > 0
     _equal(_uncut(row_id), ref)
@@ -280,12 +281,12 @@ def _views(row_id, nviews):
 
 
 def _views_sum(vox, c, weights=None):
-    return vox.forward_views_sum(HS._dev(c["xyz"]), HS._dev(c["cen"]), HS._dev(c["chan"]), c["radii"], weights=HS._dev(weights))
+    return vox.forward_views_sum(hip.dev(c["xyz"]), hip.dev(c["cen"]), hip.dev(c["chan"]), c["radii"], weights=hip.dev(weights))
 
 
 def _repeated_sum(vox, c, weights=None):
     r = c["rep"]
-    return vox.forward_sum(HS._dev(r["coords"]), r["offsets"], HS._dev(c["cen"]), HS._dev(r["channels"]), c["radii"], weights=HS._dev(weights))
+    return vox.forward_sum(hip.dev(r["coords"]), r["offsets"], hip.dev(c["cen"]), hip.dev(r["channels"]), c["radii"], weights=hip.dev(weights))
 
 
 @pytest.mark.parametrize("row_id, nviews", [("edge20", 12), ("cut96", 6)])

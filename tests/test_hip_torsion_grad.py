@@ -38,6 +38,7 @@ from tests import flex_rows as X
 from tests import hessian_reference as hr
 from tests import pose_reference as pr
 from tests import torsion_grad_reference as tg
+from tests import hip_support as hip
 from tests.tolerance import GRAD64_ABS, GRAD64_REL, GRAD_ABS, GRAD_REL
 
 pytestmark = pytest.mark.gpu
@@ -45,21 +46,10 @@ pytestmark = pytest.mark.gpu
 CASES = ("base", "long", "deep")
 
 
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
 def _vox(d, **kw):
     import molvoxel_amd as mv
 
     return mv.create_voxelizer(0.5, X.D, d["radii_type"], d["density"], library="hip", precision=64 if d["kind"] == "f64" else 32, **kw)
-
-
-def _dev(x):
-    import torch
-
-    return x if x is None or np.isscalar(x) else torch.tensor(np.ascontiguousarray(x), device="cuda")
 
 
 @functools.lru_cache(maxsize=None)
@@ -75,7 +65,7 @@ def _rows(name, seed=23):
 
 def _back(vox, conformer, d, ang, up, axes=None, moves=None, off=None):
     gc, ga = vox.apply_torsions_backward(conformer, d["off"] if off is None else off, d["axes"] if axes is None else axes,
-                                         d["moves"] if moves is None else moves, ang, _dev(up))
+                                         d["moves"] if moves is None else moves, ang, hip.dev(up))
     return gc.cpu().numpy(), ga.cpu().numpy()
 
 
@@ -85,10 +75,10 @@ def _got(name):
     d = X.data(name)
     vox = _vox(d)
     ang, up = _rows(name)
-    conformer = vox.apply_torsions(_dev(d["xyz"]), d["off"], d["axes"], d["moves"], ang)
+    conformer = vox.apply_torsions(hip.dev(d["xyz"]), d["off"], d["axes"], d["moves"], ang)
     kept = conformer.clone()
     gc, ga = _back(vox, conformer, d, ang, up)
-    assert _same_bits(conformer.cpu().numpy(), kept.cpu().numpy())  # the caller's conformer is not modified
+    assert hip.same_bits(conformer.cpu().numpy(), kept.cpu().numpy())  # the caller's conformer is not modified
     return conformer.cpu().numpy(), gc, ga
 
 
@@ -101,13 +91,13 @@ def test_two_runs_agree_and_a_molecule_alone_is_the_molecule_in_its_batch(name):
     conformer, gc, ga = _got(name)
     assert gc.shape == (d["N"], 3) and ga.shape == (d["B"], d["T"]) and gc.dtype == np.float64 and ga.dtype == np.float64
     assert np.isfinite(gc).all() and np.isfinite(ga).all()
-    again = _back(vox, _dev(conformer), d, ang, up)
-    assert _same_bits(again[0], gc) and _same_bits(again[1], ga)
+    again = _back(vox, hip.dev(conformer), d, ang, up)
+    assert hip.same_bits(again[0], gc) and hip.same_bits(again[1], ga)
     for b in range(d["B"]):
         lo, hi = int(d["off"][b]), int(d["off"][b + 1])
-        alone = _back(vox, _dev(conformer[lo:hi]), d, ang[b:b + 1], up[lo:hi], axes=d["axes"][b:b + 1], moves=d["moves"][lo:hi],
+        alone = _back(vox, hip.dev(conformer[lo:hi]), d, ang[b:b + 1], up[lo:hi], axes=d["axes"][b:b + 1], moves=d["moves"][lo:hi],
                       off=np.array([0, hi - lo], np.int64))
-        assert _same_bits(alone[0], gc[lo:hi]) and _same_bits(alone[1][0], ga[b])
+        assert hip.same_bits(alone[0], gc[lo:hi]) and hip.same_bits(alone[1][0], ga[b])
     live = (d["axes"][:, :, 0] >= 0) & (np.diff(d["off"]) > 0)[:, None]
     assert ga[live].all() and not ga[~live].any() and not np.signbit(ga[~live]).any()  # (padding and the empty molecule: +0.0)
 
@@ -117,8 +107,8 @@ def test_no_torsions_return_the_upstream(name):
     d = X.data(name)
     vox = _vox(d)
     _, up = _rows(name)
-    gc, ga = _back(vox, _dev(d["xyz"]), d, np.zeros((d["B"], 0)), up, axes=np.zeros((d["B"], 0, 2), np.int32))
-    assert _same_bits(gc, up) and ga.shape == (d["B"], 0)
+    gc, ga = _back(vox, hip.dev(d["xyz"]), d, np.zeros((d["B"], 0)), up, axes=np.zeros((d["B"], 0, 2), np.int32))
+    assert hip.same_bits(gc, up) and ga.shape == (d["B"], 0)
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -127,8 +117,8 @@ def test_angles_of_exactly_zero_return_the_upstream_rows_and_their_true_derivati
     vox = _vox(d)
     _, up = _rows(name)
     zero = np.zeros((d["B"], d["T"]))
-    gc, ga = _back(vox, _dev(d["xyz"]), d, zero, up)
-    assert _same_bits(gc, up)
+    gc, ga = _back(vox, hip.dev(d["xyz"]), d, zero, up)
+    assert hip.same_bits(gc, up)
     live = (d["axes"][:, :, 0] >= 0) & (np.diff(d["off"]) > 0)[:, None]
     assert ga[live].all() and not ga[~live].any()
     worst = 0.0
@@ -154,8 +144,8 @@ def test_an_inert_torsion_gives_plus_zero_and_leaves_the_other_bits(bad):
     moves = d["moves"].copy()
     moves[9:12] |= 1 << 4  # the fifth set is a live set: only its axis is not
     ang5 = np.concatenate([ang, np.full((3, 1), 0.7)], axis=1)
-    gc, ga = _back(vox, _dev(conformer), d, ang5, up, axes=axes, moves=moves)
-    assert _same_bits(gc, gc4) and _same_bits(ga[:, :4], ga4)
+    gc, ga = _back(vox, hip.dev(conformer), d, ang5, up, axes=axes, moves=moves)
+    assert hip.same_bits(gc, gc4) and hip.same_bits(ga[:, :4], ga4)
     assert not ga[:, 4].any() and not np.signbit(ga[:, 4]).any()
 
 
@@ -171,9 +161,9 @@ def test_an_atom_without_a_row_may_have_nan_coordinates():
     far, dead = conformer.copy(), conformer.copy()
     far[last] = [1e3, -2e3, 5e2]
     dead[last, 1] = np.nan
-    want, got = _back(vox, _dev(far), d, ang, up0), _back(vox, _dev(dead), d, ang, up0)
+    want, got = _back(vox, hip.dev(far), d, ang, up0), _back(vox, hip.dev(dead), d, ang, up0)
     assert np.isfinite(got[0]).all() and np.isfinite(got[1]).all()
-    assert _same_bits(got[0], want[0]) and _same_bits(got[1], want[1])
+    assert hip.same_bits(got[0], want[0]) and hip.same_bits(got[1], want[1])
     assert not got[0][last].any() and not np.signbit(got[0][last]).any() and got[1][2, :2].all()
 
 
@@ -185,12 +175,12 @@ def test_the_in_place_call_is_the_out_of_place_call(name):
     vox = _vox(d)
     ang, up = _rows(name)
     conformer, gc, ga = _got(name)
-    c, g = _dev(conformer), _dev(up)
+    c, g = hip.dev(conformer), hip.dev(up)
     B, T, ax, mv, th = vox._torsion_arrays(d["off"], d["axes"], d["moves"], ang)
     ga2 = torch.empty((B, T), dtype=torch.float64, device="cuda")
     _lib.check(vox._lib.mvx_apply_torsions_backward(vox._handle, c.data_ptr(), d["off"].ctypes.data, B, T, ax.data_ptr(), mv.data_ptr(),
                                                     th.data_ptr(), g.data_ptr(), g.data_ptr(), ga2.data_ptr(), vox._stream()))
-    assert _same_bits(g.cpu().numpy(), gc) and _same_bits(ga2.cpu().numpy(), ga) and _same_bits(c.cpu().numpy(), conformer)
+    assert hip.same_bits(g.cpu().numpy(), gc) and hip.same_bits(ga2.cpu().numpy(), ga) and hip.same_bits(c.cpu().numpy(), conformer)
 
 
 # ---- against the reference -------------------------------------------------------------------------------------------------------
@@ -228,15 +218,15 @@ def _losses(vox, d, entry):
     import torch
 
     rng = np.random.default_rng(31)
-    pose = (d["off"], _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), _dev(d["chan"]), _dev(d["radii"]))
+    pose = (d["off"], hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), hip.dev(d["chan"]), hip.dev(d["radii"]))
     F = _field(d)
     if entry == "score":
-        w = _dev(rng.standard_normal(d["B"]))
+        w = hip.dev(rng.standard_normal(d["B"]))
         return lambda c: (vox.score_posed_batch(c, *pose, F) * w).sum()
     if entry == "moments":
-        w = _dev(rng.standard_normal((d["B"], d["C"], 3)))
+        w = hip.dev(rng.standard_normal((d["B"], d["C"], 3)))
         return lambda c: (vox.moments_posed_batch(c, *pose, target=F) * w).sum()
-    w = _dev(rng.standard_normal((d["B"], d["C"]) + (X.D,) * 3)).to(F.dtype)
+    w = hip.dev(rng.standard_normal((d["B"], d["C"]) + (X.D,) * 3)).to(F.dtype)
     return lambda c: (vox.forward_posed_batch(c, *pose) * w).sum()
 
 
@@ -247,16 +237,16 @@ def test_autograd_through_apply_torsions_is_the_backward_entry_on_the_conformers
     vox = _vox(d, differentiable=True, torsion_grad=True, moments_grad=(entry == "moments"))
     ang, _ = _rows(name)
     loss = _losses(vox, d, entry)
-    x, theta = _dev(d["xyz"]).requires_grad_(), _dev(ang).requires_grad_()
+    x, theta = hip.dev(d["xyz"]).requires_grad_(), hip.dev(ang).requires_grad_()
     conformer = vox.apply_torsions(x, d["off"], d["axes"], d["moves"], theta)
-    assert conformer.requires_grad and conformer.dtype == x.dtype and _same_bits(conformer.detach().cpu().numpy(), _got(name)[0])
+    assert conformer.requires_grad and conformer.dtype == x.dtype and hip.same_bits(conformer.detach().cpu().numpy(), _got(name)[0])
     loss(conformer).backward()
     leaf = conformer.detach().clone().requires_grad_()
     loss(leaf).backward()
     assert leaf.grad.abs().max() > 0
     gc, ga = vox.apply_torsions_backward(leaf.detach(), d["off"], d["axes"], d["moves"], ang, leaf.grad)
     assert x.grad.shape == x.shape and theta.grad.shape == theta.shape
-    assert _same_bits(x.grad.cpu().numpy(), gc.cpu().numpy()) and _same_bits(theta.grad.cpu().numpy(), ga.cpu().numpy())
+    assert hip.same_bits(x.grad.cpu().numpy(), gc.cpu().numpy()) and hip.same_bits(theta.grad.cpu().numpy(), ga.cpu().numpy())
     assert not gc.requires_grad and not ga.requires_grad
 
 
@@ -268,19 +258,19 @@ def test_only_a_torsion_grad_voxelizer_records_and_the_forward_bits_are_the_same
     want = _got("base")[0]
     for kw in (dict(), dict(differentiable=True)):
         vox = _vox(d, **kw)
-        out = vox.apply_torsions(_dev(d["xyz"]).requires_grad_(), d["off"], d["axes"], d["moves"], _dev(ang).requires_grad_())
-        assert not out.requires_grad and _same_bits(out.cpu().numpy(), want)
+        out = vox.apply_torsions(hip.dev(d["xyz"]).requires_grad_(), d["off"], d["axes"], d["moves"], hip.dev(ang).requires_grad_())
+        assert not out.requires_grad and hip.same_bits(out.cpu().numpy(), want)
     vox = _vox(d, differentiable=True, torsion_grad=True)
-    x32 = _dev(d["xyz"].astype(np.float32)).requires_grad_()  # (gradients come back in the inputs' dtype)
+    x32 = hip.dev(d["xyz"].astype(np.float32)).requires_grad_()  # (gradients come back in the inputs' dtype)
     out = vox.apply_torsions(x32, d["off"], d["axes"], d["moves"], ang)
     assert out.requires_grad and out.dtype == torch.float64
     out.sum().backward()
     assert x32.grad.dtype == torch.float32 and x32.grad.shape == x32.shape
-    only_theta = vox.apply_torsions(d["xyz"].copy(), d["off"], d["axes"], d["moves"], _dev(ang).requires_grad_())
-    assert only_theta.requires_grad and _same_bits(only_theta.detach().cpu().numpy(), want)
+    only_theta = vox.apply_torsions(d["xyz"].copy(), d["off"], d["axes"], d["moves"], hip.dev(ang).requires_grad_())
+    assert only_theta.requires_grad and hip.same_bits(only_theta.detach().cpu().numpy(), want)
     with torch.no_grad():
-        assert not vox.apply_torsions(_dev(d["xyz"]).requires_grad_(), d["off"], d["axes"], d["moves"], ang).requires_grad
-    assert not vox.apply_torsions(_dev(d["xyz"]), d["off"], d["axes"], d["moves"], ang).requires_grad
+        assert not vox.apply_torsions(hip.dev(d["xyz"]).requires_grad_(), d["off"], d["axes"], d["moves"], ang).requires_grad
+    assert not vox.apply_torsions(hip.dev(d["xyz"]), d["off"], d["axes"], d["moves"], ang).requires_grad
 
 
 # ---- against the second-order path -------------------------------------------------------------------------------------------------
@@ -291,9 +281,9 @@ def test_the_angle_gradients_of_the_scores_against_the_flex_hessian_entry(name):
     vox = _vox(d, differentiable=True, torsion_grad=True)
     ang = np.random.default_rng(37).uniform(-1.0, 1.0, (d["B"], d["T"]))
     F = _field(d)
-    pose = (d["off"], _dev(d["cen"]), _dev(d["q"]), _dev(d["t"]), _dev(d["chan"]), _dev(d["radii"]))
-    theta = _dev(ang).requires_grad_()
-    conformer = vox.apply_torsions(_dev(d["xyz"]), d["off"], d["axes"], d["moves"], theta)
+    pose = (d["off"], hip.dev(d["cen"]), hip.dev(d["q"]), hip.dev(d["t"]), hip.dev(d["chan"]), hip.dev(d["radii"]))
+    theta = hip.dev(ang).requires_grad_()
+    conformer = vox.apply_torsions(hip.dev(d["xyz"]), d["off"], d["axes"], d["moves"], theta)
     vox.score_posed_batch(conformer, *pose, F).sum().backward()
     got = theta.grad.cpu().numpy()
     _, G, _ = vox.score_hessian_flex_posed_batch(conformer.detach(), *pose, F, d["axes"], d["moves"])
@@ -334,13 +324,13 @@ def test_adam_on_the_score_over_poses_and_torsions_improves_every_start():
     vox = mv.create_voxelizer(0.5, X.D, "atom-wise", "gaussian", library="hip", differentiable=True, torsion_grad=True)
     off1 = np.array([0, 14], np.int64)
     with torch.no_grad():
-        field = vox.forward_posed_batch(_dev(xyz), off1, _dev(cen), _dev(np.array([[1.0, 0.0, 0.0, 0.0]])), _dev(np.zeros((1, 3))),
-                                        _dev(W), _dev(rad))[0].clone()
+        field = vox.forward_posed_batch(hip.dev(xyz), off1, hip.dev(cen), hip.dev(np.array([[1.0, 0.0, 0.0, 0.0]])), hip.dev(np.zeros((1, 3))),
+                                        hip.dev(W), hip.dev(rad))[0].clone()
     off = 14 * np.arange(B + 1, dtype=np.int64)
-    rep = lambda x: _dev(np.concatenate([x] * B))  # noqa: E731  (B copies of the molecule, one per start)
+    rep = lambda x: hip.dev(np.concatenate([x] * B))  # noqa: E731  (B copies of the molecule, one per start)
     coords, chan, radii, cens = rep(xyz), rep(W), rep(rad), rep(cen)
     ax, mvs = np.concatenate([axes] * B), np.concatenate([moves] * B)
-    q, t, theta = (_dev(x).requires_grad_() for x in (q0, t0, th0))
+    q, t, theta = (hip.dev(x).requires_grad_() for x in (q0, t0, th0))
 
     def scores():
         conformer = vox.apply_torsions(coords, off, ax, mvs, theta)
@@ -357,6 +347,6 @@ def test_adam_on_the_score_over_poses_and_torsions_improves_every_start():
     with torch.no_grad():
         end = scores()
     print(f"TORSION_GRAD_ADAM score {float(start.min()):.1f} ... {float(start.max()):.1f} -> {float(end.min()):.1f} ... {float(end.max()):.1f}; "
-          f"largest |theta - theta0| {float((theta.detach() - _dev(th0)).abs().max()):.3f}")
+          f"largest |theta - theta0| {float((theta.detach() - hip.dev(th0)).abs().max()):.3f}")
     assert bool((end > start).all()), (start.tolist(), end.tolist())
-    assert float((theta.detach() - _dev(th0)).abs().min()) > 0.0  # every torsion of every start moved
+    assert float((theta.detach() - hip.dev(th0)).abs().min()) > 0.0  # every torsion of every start moved

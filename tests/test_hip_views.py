@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+from tests import hip_support as hip
 from tests import views_reference as vr
 from tests.tolerance import assert_exact, assert_gaussian
 from tests.views_rows import CUBE  # noqa: F401  (clouds are uniform in a cube of this edge, centred at the origin)
@@ -31,14 +32,6 @@ def _vox(D, res, radii_type="scalar", density="gaussian", variant="float32", **k
     elif variant == "precision64":
         kw["precision"] = 64
     return mv.create_voxelizer(res, D, radii_type, density, "hip", output="torch", **kw)
-
-def _dev(vox, x, dtype=None):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    t = torch.as_tensor(x, device=vox.device)
-    return t if dtype is None else t.to(dtype)
 
 
 def _repeat(x, B):
@@ -97,10 +90,10 @@ def test_views_equal_the_repeated_cloud_bit_for_bit(row, xf):
     cen = _centers(N, B, xyz)
     if B == 1 and N:
         cen[0] = xyz[N // 2]
-    x = _dev(vox, xyz)
-    ch = _dev(vox, chan, vox._tfp if mode == "features" else None)
-    r = _dev(vox, radii)
-    got, ref = _both(vox, x, _dev(vox, cen), ch, r, C, xf, radii_type == "atom-wise")
+    x = hip.dev(xyz)
+    ch = hip.dev(chan, dtype=vox._tfp if mode == "features" else None)
+    r = hip.dev(radii)
+    got, ref = _both(vox, x, hip.dev(cen), ch, r, C, xf, radii_type == "atom-wise")
     assert got.shape == ref.shape == (B, C, D, D, D) and got.dtype == ref.dtype
     assert torch.equal(got, ref)
     if B >= 2:
@@ -122,7 +115,7 @@ def test_all_inclusive_view_far_view_and_host_inputs():
     assert torch.equal(index[offsets[1]:offsets[2]].cpu(), torch.arange(700))
     got, ref = _both(vox, xyz, cen, feat, 1.5, 8, False, False)
     assert torch.equal(got, ref)
-    dev, _ = _both(vox, _dev(vox, xyz), _dev(vox, cen), _dev(vox, feat), 1.5, 8, False, False)
+    dev, _ = _both(vox, hip.dev(xyz), hip.dev(cen), hip.dev(feat), 1.5, 8, False, False)
     assert torch.equal(got, dev)
     out = vox.get_empty_grid(8, batch_size=5)
     assert vox.forward_views(xyz, cen, feat, 1.5, out_grid=out) is out and torch.equal(out, ref)
@@ -138,7 +131,7 @@ def test_views_against_the_c_oracle(mode, density):
     xyz, chan, _ = _cloud(11, 1500, mode, C, "scalar")
     cen = _centers(11, 6, xyz)
     nc = dict(num_channels=C) if mode == "types" else {}
-    got = vox.forward_views(_dev(vox, xyz), _dev(vox, cen), _dev(vox, chan), 1.5, **nc).cpu().numpy()
+    got = vox.forward_views(hip.dev(xyz), hip.dev(cen), hip.dev(chan), 1.5, **nc).cpu().numpy()
     for b in range(cen.shape[0]):
         ref = c_oracle.voxelize(xyz - cen[b], chan, 1.5, resolution=res, dimension=D, density=density, **nc)
         (assert_exact if density == "binary" else assert_gaussian)(got[b], ref)
@@ -160,7 +153,7 @@ def test_selection_covers_every_contributing_atom_and_culls():
     vox = _vox(D, res, "scalar", "binary")
     xyz, _, _ = _cloud(5, N, "single", 1, "scalar")
     cen = _centers(5, B, xyz)
-    index, offsets = vox.select_views(_dev(vox, xyz), _dev(vox, cen), radii=r)
+    index, offsets = vox.select_views(hip.dev(xyz), hip.dev(cen), radii=r)
     index = index.cpu().numpy()
     assert offsets[0] == 0 and offsets[-1] == index.size and index.dtype == np.int64
     expect = vr.select(xyz, cen, r, res, D)
@@ -192,7 +185,7 @@ def test_rotated_selection_covers_every_contributing_atom():
     cen = _centers(6, B, xyz)
     kw = dict(random_rotation=True, random_translation=1.0)
     np.random.seed(3)
-    index, offsets = vox.select_views(_dev(vox, xyz), _dev(vox, cen), radii=r, **kw)
+    index, offsets = vox.select_views(hip.dev(xyz), hip.dev(cen), radii=r, **kw)
     index = index.cpu().numpy()
     sub = np.arange(0, N, 25)
     types = np.full(N, len(sub), np.int64)
@@ -215,11 +208,11 @@ def test_two_calls_give_the_same_bytes():
     vox = _vox(16, 1.0, "atom-wise")
     xyz, feat, radii = _cloud(9, 3000, "features", 32, "atom-wise")
     cen = _centers(9, 67, xyz)
-    args = (_dev(vox, xyz), _dev(vox, cen), _dev(vox, feat))
-    i0, o0 = vox.select_views(*args, radii=_dev(vox, radii))
-    g0 = vox.forward_views(*args, _dev(vox, radii))
-    i1, o1 = vox.select_views(*args, radii=_dev(vox, radii))
-    g1 = vox.forward_views(*args, _dev(vox, radii))
+    args = (hip.dev(xyz), hip.dev(cen), hip.dev(feat))
+    i0, o0 = vox.select_views(*args, radii=hip.dev(radii))
+    g0 = vox.forward_views(*args, hip.dev(radii))
+    i1, o1 = vox.select_views(*args, radii=hip.dev(radii))
+    g1 = vox.forward_views(*args, hip.dev(radii))
     assert torch.equal(i0, i1) and np.array_equal(o0, o1) and torch.equal(g0, g1) and i0.numel() > 0
 
 
@@ -230,8 +223,8 @@ def test_gradients_equal_the_repeated_cloud():
     D, res, B, N, C = 16, 1.0, 5, 600, 4
     vox = _vox(D, res, "atom-wise", differentiable=True, radii_grad=True)
     xyz, feat, radii = _cloud(13, N, "features", C, "atom-wise", edge=24.0)
-    cen = _dev(vox, _centers(13, B, xyz))
-    x, f, r = _dev(vox, xyz), _dev(vox, feat), _dev(vox, radii)
+    cen = hip.dev(_centers(13, B, xyz))
+    x, f, r = hip.dev(xyz), hip.dev(feat), hip.dev(radii)
     index, offsets = vox.select_views(x, cen, f, r)
     w = torch.rand((B, C, D, D, D), device=vox.device, generator=torch.Generator(vox.device).manual_seed(1))
 
@@ -270,9 +263,9 @@ def test_differentiable_views_with_overlap_prepass():
     out = []
     for overlap in (False, True):
         vox = _vox(D, res, differentiable=True, overlap_prepass=overlap)
-        cen = _dev(vox, _centers(21, B, xyz))
-        x = _dev(vox, xyz).requires_grad_(True)
-        f = _dev(vox, feat).requires_grad_(True)
+        cen = hip.dev(_centers(21, B, xyz))
+        x = hip.dev(xyz).requires_grad_(True)
+        f = hip.dev(feat).requires_grad_(True)
         for _ in range(2):  # (the second call runs its pre-pass under the first call's voxelize launches)
             x.grad = f.grad = None
             g = vox.forward_views(x, cen, f, 1.5)
@@ -297,7 +290,7 @@ def test_10gs_pocket_views():
     N = xyz.shape[0]
     cen = xyz[np.arange(8) * (N // 8)]  # eight views centred on atoms spread over the file
     vox = _vox(24, 1.0)
-    got, ref = _both(vox, _dev(vox, xyz), _dev(vox, cen), _dev(vox, types), 1.5, 5, False, False)
+    got, ref = _both(vox, hip.dev(xyz), hip.dev(cen), hip.dev(types), 1.5, 5, False, False)
     assert torch.equal(got, ref) and bool(got.any())
     assert_gaussian(got[0].cpu().numpy(), c_oracle.voxelize(xyz - cen[0], types, 1.5, resolution=1.0, dimension=24, num_channels=5))
 
@@ -309,7 +302,7 @@ def test_chunked_views_call():
     vox = _vox(16, 1.0)
     xyz, feat, _ = _cloud(17, 3000, "features", 8, "scalar")
     cen = _centers(17, 67, xyz)
-    args = (_dev(vox, xyz), _dev(vox, cen), _dev(vox, feat), 1.5)
+    args = (hip.dev(xyz), hip.dev(cen), hip.dev(feat), 1.5)
     whole = vox.forward_views(*args)
     vox.debug_option("chunks", 2)
     vox.debug_option("mall_budget_kb", 64)

@@ -12,28 +12,21 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests import hip_support as hip
 from tests import views_reference as vr
 from tests import views_rows as rows
+from tests.abi import MVX_ERR_INVALID
 from tests.tolerance import assert_exact, assert_gaussian
 
 pytestmark = pytest.mark.gpu
 
-MVX_OK, MVX_ERR_INVALID = 0, -1
+MVX_OK = 0
 
 
 def _vox(D, res, radii_type="scalar", density="gaussian", precision=32):
     import molvoxel_amd as mv
 
     return mv.create_voxelizer(res, D, radii_type, density, "hip", output="torch", precision=precision)
-
-
-def _dev(vox, x, dtype=None):
-    import torch
-
-    if x is None or np.isscalar(x):
-        return x
-    t = torch.as_tensor(x if x.flags.writeable else x.copy(), device=vox.device)  # (shared row inputs are read-only)
-    return t if dtype is None else t.to(dtype)
 
 
 def _check(index, offsets, ref_index, ref_offsets):
@@ -62,7 +55,7 @@ def test_scan_rows_equal_the_reference(case):
     ref_index, ref_offsets, _ = rows.row_reference(row, rotated)
     vox = _vox(row.D, row.res, row.radii)
     np.random.seed(rows.row_seed(row))
-    index, offsets = vox.select_views(_dev(vox, xyz), _dev(vox, cen), radii=_dev(vox, radii), **(rows.TRANSFORM if rotated else {}))
+    index, offsets = vox.select_views(hip.dev(xyz), hip.dev(cen), radii=hip.dev(radii), **(rows.TRANSFORM if rotated else {}))
     _check(index, offsets, ref_index, ref_offsets)
 
 
@@ -75,7 +68,7 @@ def test_forward_views_at_scale_equals_the_repeated_cloud(xf):
     vox = _vox(D, 1.0)
     xyz, feat, _ = rows.cloud(41, N, "features", C_, "scalar")
     cen = rows.centers(41, B, xyz)
-    got, ref = _grids(vox, _dev(vox, xyz), _dev(vox, cen), _dev(vox, feat), 1.5, xf, False)
+    got, ref = _grids(vox, hip.dev(xyz), hip.dev(cen), hip.dev(feat), 1.5, xf, False)
     assert got.shape == (B, C_, D, D, D) and torch.equal(got, ref)
     assert not bool(got[0].any()) and int(got.flatten(1).any(dim=1).sum()) > B // 2
 
@@ -95,14 +88,14 @@ def test_select_views_grows_a_too_small_index_buffer():
     B, N = cen.shape[0], xyz.shape[0]
     assert B * N > 1 << 20
     vox = _vox(16, 1.0)
-    x = _dev(vox, xyz)
+    x = hip.dev(xyz)
     expect = torch.arange(N, device=vox.device).repeat(B)
     for call in range(2):  # the first call finds 2^20 entries too few; the second sizes the buffer from the first one's total
-        index, offsets = vox.select_views(x, _dev(vox, cen), radii=1.5)
+        index, offsets = vox.select_views(x, hip.dev(cen), radii=1.5)
         assert np.array_equal(offsets, np.arange(B + 1, dtype=np.int64) * N), call
         assert index.dtype == torch.int64 and torch.equal(index, expect), call
         assert vox._views_total == B * N
-    index, offsets = vox.select_views(x, _dev(vox, cen + [1000.0, 0.0, 0.0]), radii=1.5)
+    index, offsets = vox.select_views(x, hip.dev(cen + [1000.0, 0.0, 0.0]), radii=1.5)
     assert index.numel() == 0 and not offsets.any() and offsets.shape == (B + 1,)
 
 
@@ -117,7 +110,7 @@ def test_c_abi_reports_a_too_small_buffer_and_leaves_it_untouched():
     total = int(ref_offsets[-1])
     assert total == (B - 1) * N
     vox = _vox(16, 1.0)
-    x = _dev(vox, xyz)
+    x = hip.dev(xyz)
     keep = []
     xfs, _ = vox._make_xforms(B, cen, _lib.MVX_DEVICE, 0.0, False, keep)
     sentinel = -7
@@ -195,7 +188,7 @@ def test_gather_widths_and_bases(row, xf):
         chan = chan.astype(tdtype)
     if radii_type == "atom-wise":
         radii = radii.astype(vox.fp)
-    place = lambda name, a: _offset_view(vox, a, skip) if off_what == name else _dev(vox, a)  # noqa: E731
+    place = lambda name, a: _offset_view(vox, a, skip) if off_what == name else hip.dev(a)  # noqa: E731
     x, ch, r = place("coords", xyz), place("chan", chan), (place("radii", radii) if radii_type == "atom-wise" else radii)
     # what the library is handed: the wrapper passes tensors of the right type through, whatever their base
     c_in, ch_in, r_in, _, _ = vox._views_inputs(x, ch, mode, r, C_)
@@ -210,7 +203,7 @@ def test_gather_widths_and_bases(row, xf):
         assert r_in.data_ptr() == r.data_ptr() and r_in.data_ptr() % 16 == (skip * esz if off_what == "radii" else 0)
         assert _gather_width(esz, r_in) == widths["radii"]
     nc = dict(num_channels=C_) if mode == "types" else {}
-    got, ref = _grids(vox, x, _dev(vox, cen), ch, r, xf, radii_type == "atom-wise", **nc)
+    got, ref = _grids(vox, x, hip.dev(cen), ch, r, xf, radii_type == "atom-wise", **nc)
     assert torch.equal(got, ref) and bool(got[1:].any()) and not bool(got[0].any())
 
 
@@ -224,7 +217,7 @@ def test_selection_of_every_radii_source_equals_the_reference(case):
     if row.mode == "features":
         chan = chan.astype(vox.fp)
     np.random.seed(rows.source_seed(row))
-    index, offsets = vox.select_views(_dev(vox, xyz), _dev(vox, cen), _dev(vox, chan), _dev(vox, radii),
+    index, offsets = vox.select_views(hip.dev(xyz), hip.dev(cen), hip.dev(chan), hip.dev(radii),
                                       **(rows.TRANSFORM if rotated else {}))
     _check(index, offsets, ref_index, ref_offsets)
 
@@ -247,7 +240,7 @@ def test_selection_one_ulp_either_side_of_each_bound(source, precision):
         assert list(keep) == ([True] * 4 + [False] * 4) * 2
         chan = np.zeros((16, 3), fp) if source == "channel-features" else None
         radii = np.full(16, radius, fp) if source == "atom-wise" else radius
-        index, offsets = vox.select_views(_dev(vox, xyz), _dev(vox, np.zeros((1, 3))), _dev(vox, chan), _dev(vox, radii))
+        index, offsets = vox.select_views(hip.dev(xyz), hip.dev(np.zeros((1, 3))), hip.dev(chan), hip.dev(radii))
         _check(index, offsets, np.flatnonzero(keep).astype(np.int64), np.array([0, 8], np.int64))
 
 
@@ -266,8 +259,8 @@ def test_types_outside_the_range_never_pass(radii_type, density):
     types = pool[np.random.default_rng(72).integers(0, pool.size, N)]
     inside = (types >= 0) & (types < C_)
     assert 0.3 < inside.mean() < 0.7
-    x, t, c = _dev(vox, xyz), _dev(vox, types), _dev(vox, cen)
-    r = _dev(vox, radii)
+    x, t, c = hip.dev(xyz), hip.dev(types), hip.dev(cen)
+    r = hip.dev(radii)
     got, ref = _grids(vox, x, c, t, r, False, radii_type == "atom-wise", num_channels=C_)
     assert got.shape == (B, C_, D, D, D) and torch.equal(got, ref)
     got_xf, ref_xf = _grids(vox, x, c, t, r, True, radii_type == "atom-wise", num_channels=C_)

@@ -9,12 +9,13 @@ import pytest
 
 import tests.test_hip_sum as HS  # (_check_weighted_sum: the bar of the rotated and posed sums, GRAD_REL * bound + GRAD_ABS)
 from tests import views_rows as V
+from tests import hip_support as hip
+from tests.abi import MVX_ERR_INVALID, last_error
 from tests.tolerance import assert_exact
 
 pytestmark = pytest.mark.gpu
 
 B, N, D = 7, 600, 16
-MVX_ERR_INVALID = -1
 # id: (seed, mode, C, radii_type, density)
 CASES = {
     "features-C5-scalar": (11, "features", 5, "scalar", "gaussian"),  # one padded chunk
@@ -30,10 +31,6 @@ def _vox(radii_type, density, D_=D, **kw):
     import molvoxel_amd as mv
 
     return mv.create_voxelizer(1.0, D_, radii_type, density, library="hip", **dict(kw))
-
-
-def _dev(x):
-    return HS._dev(x)
 
 
 @functools.lru_cache(maxsize=None)
@@ -54,12 +51,12 @@ def _case(case_id, nviews=B):
 
 
 def _views_sum(c, vox=None, **kw):
-    return (vox or c["vox"]).forward_views_sum(_dev(c["xyz"]), _dev(c["cen"]), _dev(c["chan"]), _dev(c["radii"]), num_channels=c["nc"], **kw)
+    return (vox or c["vox"]).forward_views_sum(hip.dev(c["xyz"]), hip.dev(c["cen"]), hip.dev(c["chan"]), hip.dev(c["radii"]), num_channels=c["nc"], **kw)
 
 
 def _repeated_sum(c, vox=None, **kw):
     r = c["rep"]
-    return (vox or c["vox"]).forward_sum(_dev(r["coords"]), r["offsets"], _dev(c["cen"]), _dev(r["channels"]), _dev(r["radii"]),
+    return (vox or c["vox"]).forward_sum(hip.dev(r["coords"]), r["offsets"], hip.dev(c["cen"]), hip.dev(r["channels"]), hip.dev(r["radii"]),
                                          num_channels=c["nc"], **kw)
 
 
@@ -93,11 +90,11 @@ def test_random_transforms_are_drawn_per_view_as_forward_sum_draws_them(case_id)
 def test_views_sum_is_forward_sum_on_the_gathered_selection(case_id):
     c = _case(case_id)
     vox = c["vox"]
-    index, offsets = vox.select_views(_dev(c["xyz"]), _dev(c["cen"]), _dev(c["chan"]) if c["mode"] == "types" else None, _dev(c["radii"]))
+    index, offsets = vox.select_views(hip.dev(c["xyz"]), hip.dev(c["cen"]), hip.dev(c["chan"]) if c["mode"] == "types" else None, hip.dev(c["radii"]))
     assert offsets[1] == 0 and 0 < offsets[-1] < B * N  # view 0 selects nothing; atoms are culled
     i = index.cpu().numpy()
-    ref = vox.forward_sum(_dev(c["xyz"][i]), offsets, _dev(c["cen"]), None if c["chan"] is None else _dev(c["chan"][i]),
-                          _dev(c["radii"][i]) if c["rt"] == "atom-wise" else _dev(c["radii"]), num_channels=c["nc"])
+    ref = vox.forward_sum(hip.dev(c["xyz"][i]), offsets, hip.dev(c["cen"]), None if c["chan"] is None else hip.dev(c["chan"][i]),
+                          hip.dev(c["radii"][i]) if c["rt"] == "atom-wise" else hip.dev(c["radii"]), num_channels=c["nc"])
     assert_exact(_plain(case_id), ref.cpu().numpy())
 
 
@@ -106,10 +103,10 @@ def test_posed_views_sum_is_forward_posed_sum_on_the_repeated_cloud(case_id):
     c = _case(case_id)
     r = c["rep"]
     w = c["w"]
-    got = c["vox"].forward_posed_views_sum(_dev(c["xyz"]), _dev(c["cen"]), _dev(c["q"]), _dev(c["t"]), _dev(c["chan"]), _dev(c["radii"]),
-                                           weights=_dev(w))
-    ref = c["vox"].forward_posed_sum(_dev(r["coords"]), r["offsets"], _dev(c["cen"]), _dev(c["q"]), _dev(c["t"]), _dev(r["channels"]),
-                                     _dev(r["radii"]), weights=_dev(w))
+    got = c["vox"].forward_posed_views_sum(hip.dev(c["xyz"]), hip.dev(c["cen"]), hip.dev(c["q"]), hip.dev(c["t"]), hip.dev(c["chan"]), hip.dev(c["radii"]),
+                                           weights=hip.dev(w))
+    ref = c["vox"].forward_posed_sum(hip.dev(r["coords"]), r["offsets"], hip.dev(c["cen"]), hip.dev(c["q"]), hip.dev(c["t"]), hip.dev(r["channels"]),
+                                     hip.dev(r["radii"]), weights=hip.dev(w))
     assert float(ref.abs().max()) > 0
     assert_exact(got.cpu().numpy(), ref.cpu().numpy())
 
@@ -118,8 +115,8 @@ def test_posed_views_sum_is_forward_posed_sum_on_the_repeated_cloud(case_id):
 def test_view_weights_are_the_molecule_weights_of_forward_sum(case_id):
     c = _case(case_id)
     assert (c["w"][1:] > 0).any() and (c["w"][1:] < 0).any()  # mixed signs among the views that select atoms
-    got = _views_sum(c, weights=_dev(c["w"])).cpu().numpy()
-    assert_exact(got, _repeated_sum(c, weights=_dev(c["w"])).cpu().numpy())
+    got = _views_sum(c, weights=hip.dev(c["w"])).cpu().numpy()
+    assert_exact(got, _repeated_sum(c, weights=hip.dev(c["w"])).cpu().numpy())
     assert not np.array_equal(got, _plain(case_id))
 
 
@@ -129,9 +126,9 @@ def test_accumulate_continues_from_the_grid_as_forward_sum_does():
     c = _case("features-C33-atom")
     start = np.random.default_rng(3).standard_normal((33, D, D, D)).astype(np.float32)
     out, ref = torch.tensor(start, device="cuda"), torch.tensor(start, device="cuda")
-    ret = _views_sum(c, weights=_dev(c["w"]), out_grid=out, accumulate=True)
+    ret = _views_sum(c, weights=hip.dev(c["w"]), out_grid=out, accumulate=True)
     assert ret is out
-    _repeated_sum(c, weights=_dev(c["w"]), out_grid=ref, accumulate=True)
+    _repeated_sum(c, weights=hip.dev(c["w"]), out_grid=ref, accumulate=True)
     assert_exact(out.cpu().numpy(), ref.cpu().numpy())
     assert not np.array_equal(out.cpu().numpy(), start)
 
@@ -143,12 +140,12 @@ def test_no_atoms_or_no_selected_atoms_write_zeros_or_leave_an_accumulated_grid_
     vox = _vox("scalar", "gaussian")
     start = np.random.default_rng(4).standard_normal((5, D, D, D)).astype(np.float32)
     c = _case("features-C5-scalar")
-    nobody = dict(coords=torch.empty((0, 3), dtype=torch.float64, device="cuda"), centers=_dev(c["cen"]),
+    nobody = dict(coords=torch.empty((0, 3), dtype=torch.float64, device="cuda"), centers=hip.dev(c["cen"]),
                   channels=torch.empty((0, 5), device="cuda"), radii=1.5)
-    far = dict(coords=_dev(c["xyz"]), centers=_dev(c["cen"] + 1000.0), channels=_dev(c["chan"]), radii=1.5)
+    far = dict(coords=hip.dev(c["xyz"]), centers=hip.dev(c["cen"] + 1000.0), channels=hip.dev(c["chan"]), radii=1.5)
     for a in (nobody, far):
         out = torch.tensor(start, device="cuda")
-        vox.forward_views_sum(out_grid=out, accumulate=True, weights=_dev(c["w"]), **a)
+        vox.forward_views_sum(out_grid=out, accumulate=True, weights=hip.dev(c["w"]), **a)
         assert_exact(out.cpu().numpy(), start)
         vox.forward_views_sum(out_grid=out, **a)
         assert float(out.abs().max()) == 0.0
@@ -159,9 +156,9 @@ def test_no_atoms_or_no_selected_atoms_write_zeros_or_leave_an_accumulated_grid_
 @pytest.mark.parametrize("case_id", ["features-C33-atom", "types-C8-by-type", "single-atom"])
 def test_views_sum_is_the_weighted_sum_of_forward_views_grids(case_id):
     c = _case(case_id)
-    a = (_dev(c["xyz"]), _dev(c["cen"]), _dev(c["chan"]), _dev(c["radii"]))
+    a = (hip.dev(c["xyz"]), hip.dev(c["cen"]), hip.dev(c["chan"]), hip.dev(c["radii"]))
     np.random.seed(9)
-    got = c["vox"].forward_views_sum(*a, weights=_dev(c["w"]), num_channels=c["nc"], **V.TRANSFORM)
+    got = c["vox"].forward_views_sum(*a, weights=hip.dev(c["w"]), num_channels=c["nc"], **V.TRANSFORM)
     np.random.seed(9)
     grids = c["vox"].forward_views(*a, num_channels=c["nc"], **V.TRANSFORM)
     HS._check_weighted_sum(got.cpu().numpy(), grids, c["w"], f"{case_id} views")
@@ -174,14 +171,14 @@ def test_molecule_chunks_give_the_uncut_bits():
     import molvoxel_amd as mv
 
     c = _case("features-C33-atom", 12)
-    uncut = _views_sum(c, weights=_dev(c["w"])).cpu().numpy()
+    uncut = _views_sum(c, weights=hip.dev(c["w"])).cpu().numpy()
     vox = mv.create_voxelizer(1.0, D, c["rt"], c["density"], library="hip")  # (a voxelizer of its own: the option stays with the handle)
     vox.debug_option("chunks", 3)
-    got = _views_sum(c, vox=vox, weights=_dev(c["w"])).cpu().numpy()
+    got = _views_sum(c, vox=vox, weights=hip.dev(c["w"])).cpu().numpy()
     plan = vox.last_plan()
     assert plan["nchunk"] == 3 and plan["ncc"] == 2 and plan["ct"] == 32, plan
     assert_exact(got, uncut)
-    assert_exact(uncut, _repeated_sum(c, weights=_dev(c["w"])).cpu().numpy())
+    assert_exact(uncut, _repeated_sum(c, weights=hip.dev(c["w"])).cpu().numpy())
 
 
 # ---- 10. host arrays, grid types ---------------------------------------------------------------------------------------------
@@ -191,9 +188,9 @@ def test_host_arrays_are_accepted_and_the_grid_is_contiguous_float32_whatever_th
     c = _case("features-C5-scalar")
     got = c["vox"].forward_views_sum(c["xyz"], c["cen"], c["chan"], c["radii"], weights=c["w"])
     assert got.is_cuda and got.dtype == torch.float32
-    assert_exact(got.cpu().numpy(), _views_sum(c, weights=_dev(c["w"])).cpu().numpy())
+    assert_exact(got.cpu().numpy(), _views_sum(c, weights=hip.dev(c["w"])).cpu().numpy())
     host = c["vox"].forward_posed_views_sum(c["xyz"], c["cen"], c["q"], c["t"], c["chan"], c["radii"])
-    dev = c["vox"].forward_posed_views_sum(_dev(c["xyz"]), _dev(c["cen"]), _dev(c["q"]), _dev(c["t"]), _dev(c["chan"]), _dev(c["radii"]))
+    dev = c["vox"].forward_posed_views_sum(hip.dev(c["xyz"]), hip.dev(c["cen"]), hip.dev(c["q"]), hip.dev(c["t"]), hip.dev(c["chan"]), hip.dev(c["radii"]))
     assert_exact(host.cpu().numpy(), dev.cpu().numpy())
     other = _vox("scalar", "gaussian", grid_dtype="bfloat16", grid_layout="channels_last")
     got = _views_sum(c, vox=other)
@@ -223,7 +220,7 @@ def test_the_library_names_what_it_does_not_serve_in_forward_sums_order():
         xf = (_lib.MvxXform * 1)()
         rc = vox._lib.mvx_forward_views_sum(vox._handle, 0, xyz.data_ptr(), feat.data_ptr(), None if radii is None else radii.data_ptr(),
                                             1.0, rt, 3, C_, C.addressof(xf), 1, None, out.data_ptr(), 0, None)
-        return rc, (vox._lib.mvx_last_error() or b"").decode()
+        return rc, last_error()
 
     mk = lambda D_, rt="scalar", **kw: mv.create_voxelizer(0.5, D_, rt, "gaussian", library="hip", **kw)  # noqa: E731
     ones = torch.ones(4, device="cuda")
@@ -251,7 +248,7 @@ def test_sixty_four_views_allocate_less_than_their_grids():
     xyz, chan, _ = V.cloud(21, N, "features", C_, "scalar")
     cen = V.centers(21, nv, xyz)
     vox = _vox("scalar", "gaussian", D_)
-    a = (_dev(xyz), _dev(cen), _dev(chan), 1.5)
+    a = (hip.dev(xyz), hip.dev(cen), hip.dev(chan), 1.5)
     vox.forward_views_sum(*a)  # (warm: the library's workspace and torch's pools)
     torch.cuda.synchronize()
     torch.cuda.reset_peak_memory_stats()

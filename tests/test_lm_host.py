@@ -1,5 +1,5 @@
 """Hessians of views and the on-device Levenberg-Marquardt step without a GPU: the two C ABI entries (mvx_score_hessian_views,
-mvx_lm_step) against the header and the ctypes table, what they reject before they touch a device - mvx_score_views' rules in its
+mvx_lm_step; prototypes: tests/test_abi_header_host.py), what they reject before they touch a device - mvx_score_views' rules in its
 order, then the two rules of mvx_score_hessian_batch -, what the Python layer refuses before it needs the library, lm_step_kernel's
 resources read from mvx_lm.o, the numpy restatement of the step (tests/lm_reference.py) on a quadratic and on hand-made rows, the
 residual np.linalg.solve itself attains on the systems of tests/test_hip_lm_step.py, and the conditions of the GPU refinement test
@@ -10,7 +10,6 @@ the largest condition number 7.1e3). The GPU test takes four times the figure it
 import ctypes as C
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,44 +17,11 @@ import pytest
 from molvoxel_amd.voxelizer.hip import _lib
 from tests import lm_reference as lm
 from tests import lm_rows as R
+from tests.abi import MVX_ERR_INVALID, P, call, records
 from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-ONE = _records([0])
-
-
-# ---- the entries against the header -------------------------------------------------------------------------------------------
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-@pytest.mark.parametrize("name, names", [
-    ("mvx_score_hessian_views", ["h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "N", "C", "xforms", "B",
-                                 "index", "offsets_host", "field", "field_view_stride", "pivots", "scores", "atom_grad", "atom_hess",
-                                 "twist_grad", "twist_hess", "stream"]),
-    ("mvx_lm_step", ["h", "B", "have_trial", "lam_down", "lam_up", "max_dropped", "q", "t", "S", "G", "H", "lam", "taken", "dropped",
-                     "q2", "t2", "S2", "G2", "H2", "xi", "stream"]),
-])
-def test_ctypes_prototypes_match_the_header(name, names):
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(rf"\bint {name}\(([^;]*?)\);", text, re.S)
-    assert m
-    args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES[name]
-    assert res is C.c_int and got == want
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == names
+ONE = records([0])
 
 
 def test_the_views_entry_begins_like_score_views():
@@ -63,25 +29,15 @@ def test_the_views_entry_begins_like_score_views():
     assert _lib.SIGNATURES["mvx_score_hessian_views"][1][15:] == _lib.SIGNATURES["mvx_score_hessian_batch"][1][13:]
 
 
-def test_library_exports_the_entries_and_keeps_its_version():
-    lib = _lib.load()
-    for name in ("mvx_score_hessian_views", "mvx_lm_step"):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
-
-
 # ---- mvx_lm_step's rejections -------------------------------------------------------------------------------------------------
 STATE = ("q", "t", "S", "G", "H", "lam", "taken", "dropped", "q2", "t2")
 
 
 def _lm(handle=None, B=2, have_trial=1, lam_down=1.0 / 3.0, lam_up=10.0, max_dropped=3, xi=P, **ptrs):
-    lib = _lib.load()
     a = {k: P for k in STATE + ("S2", "G2", "H2")}
     a.update(ptrs)
-    rc = lib.mvx_lm_step(handle, B, have_trial, lam_down, lam_up, max_dropped, *(a[k] for k in STATE), a["S2"], a["G2"], a["H2"], xi, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_lm_step, handle, B, have_trial, lam_down, lam_up, max_dropped, *(a[k] for k in STATE), a["S2"], a["G2"],
+                a["H2"], xi, None)
 
 
 @pytest.mark.parametrize("kw, words", [(dict(B=-1), "B must be >= 0")]
@@ -115,12 +71,10 @@ def test_lm_step_rules_fire_in_their_order_and_need_no_arrays_where_there_is_not
 # ---- mvx_score_hessian_views' rejections --------------------------------------------------------------------------------------
 def _hess(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, N=3, C_=4, xforms=ONE, B=1, index=None, offsets=None,
           field=P, stride=0, pivots=None, scores=P, atom_grad=None, atom_hess=None, twist_grad=P, twist_hess=P):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_score_hessian_views(handle, mode, coords, channels, radii, 1.0, radii_type, N, C_,
-                                     None if xforms is None else C.addressof(xforms), B, index, None if off is None else off.ctypes.data,
-                                     field, stride, pivots, scores, atom_grad, atom_hess, twist_grad, twist_hess, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_score_hessian_views, handle, mode, coords, channels, radii, 1.0, radii_type, N, C_,
+                None if xforms is None else C.addressof(xforms), B, index, None if off is None else off.ctypes.data,
+                field, stride, pivots, scores, atom_grad, atom_hess, twist_grad, twist_hess, None)
 
 
 SCORE_VIEWS_RULES = [
@@ -150,14 +104,14 @@ SCORE_VIEWS_RULES = [
     # an index without offsets, and bad offsets
     (dict(index=P), "offsets_host must not be null"),
     (dict(index=P, offsets=(1, 3)), "offsets[0]"),
-    (dict(index=P, B=2, xforms=_records([0, 0]), offsets=(0, 3, 2)), "non-decreasing"),
+    (dict(index=P, B=2, xforms=records([0, 0]), offsets=(0, 3, 2)), "non-decreasing"),
     (dict(index=P, offsets=(0, 1 << 31)), "2^31"),
     (dict(channels=None), "channels must not be null"),
     (dict(field=None), "field must not be null"),
     (dict(field=None, index=P, offsets=(0, 2)), "field must not be null"),
     (dict(), "null handle"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
 ]
 # a call that breaks both of the entry's own rules: every rule of mvx_score_views must still win
 BOTH = dict(mode=0, radii_type=2, radii=P, twist_grad=None)
@@ -183,9 +137,8 @@ def test_score_views_rules_fire_in_its_order():
     for kw in (dict(stride=-1, scores=None), dict(scores=None, channels=None), dict(channels=None, field=None)):
         a = dict(stride=0, scores=P, channels=P, field=P)
         a.update(kw)
-        rc = lib.mvx_score_views(None, 0, P, a["channels"], None, 1.0, 0, 3, 4, C.addressof(ONE), 1, None, None, a["field"], a["stride"],
-                                 a["scores"], None, None, None, None)
-        first = (lib.mvx_last_error() or b"").decode()
+        rc, first = call(lib.mvx_score_views, None, 0, P, a["channels"], None, 1.0, 0, 3, 4, C.addressof(ONE), 1, None, None, a["field"],
+                         a["stride"], a["scores"], None, None, None, None)
         assert rc == MVX_ERR_INVALID and _hess(**kw)[1] == first
 
 

@@ -1,6 +1,6 @@
 """Host half of tests/test_hip_moments_grad.py: no GPU, nothing is launched.
 
-* the C ABI entry mvx_moments_backward_batch: declared, exported, bound with the header's prototype, its rejections and their order
+* the C ABI entry mvx_moments_backward_batch: its rejections and their order
   up to the rules that read the handle (those need a real one: tests/test_hip_moments_grad.py);
 * the constructor option moments_grad and what a moments call on such a voxelizer refuses before the library is needed;
 * the registers of the eight moments_grad_kernel instantiations read from mvx_moments_grad.o, against grad_kernel's for the same key;
@@ -19,64 +19,32 @@ from molvoxel_amd.voxelizer.hip import _lib
 from tests import grad_reference as GR
 from tests import moments_grad_reference as MG
 from tests import moments_reference as MR
+from tests.abi import MVX_ERR_INVALID, P, call, declarations, records
 from tests.fake_voxelizer import fake as _fake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
 BIG = 1 << 31
 POSE = _lib.MVX_XF_POSE_PTR
 ENTRY = "mvx_moments_backward_batch"
 
 
 # ---- the C ABI entry ---------------------------------------------------------------------------------------------------------
-def test_library_exports_the_entry_and_keeps_its_version():
-    lib = _lib.load()
-    assert hasattr(lib, ENTRY) and ENTRY in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def test_ctypes_prototype_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint mvx_moments_backward_batch\(([^;]*?)\);", text, re.S)
-    assert m
-    decl = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    args = [a.strip() for a in decl.replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES[ENTRY]
-    assert res is C.c_int and got == want and len(want) == 16
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == [
-        "h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "offsets", "xforms", "B", "C", "target", "grad_moments",
-        "grad_coords", "grad_features", "stream"]
+def test_the_entry_begins_like_moments_batch_and_keeps_its_pointee_types():
     # the first eleven are mvx_moments_batch's, so that one _Call.batch_args serves both
-    assert got[:12] == _lib.SIGNATURES["mvx_moments_batch"][1][:12]
-    assert re.search(r"const float \*target", decl) and re.search(r"const double \*grad_moments", decl)
-    assert re.search(r"double \*grad_coords", decl) and re.search(r"mvx_real \*grad_features", decl)
+    assert _lib.SIGNATURES[ENTRY][1][:12] == _lib.SIGNATURES["mvx_moments_batch"][1][:12]
+    types = {name: text for text, name in declarations()[ENTRY][1]}
+    assert types["target"] == "const float *" and types["grad_moments"] == "const double *"
+    assert types["grad_coords"] == "double *" and types["grad_features"] == "mvx_real *"
 
 
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-BAD_POSE = _records([POSE | _lib.MVX_XF_ROTATE])
+BAD_POSE = records([POSE | _lib.MVX_XF_ROTATE])
 
 
 def _backward(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, offsets=(0, 3), xforms=None, B=1, C_=4, target=None, gm=P, gc=P,
               gf=P):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_moments_backward_batch(h, mode, coords, channels, radii, 1.0, rt, None if off is None else off.ctypes.data,
-                                        None if xforms is None else C.addressof(xforms), B, C_, target, gm, gc, gf, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_moments_backward_batch, h, mode, coords, channels, radii, 1.0, rt, None if off is None else off.ctypes.data,
+                None if xforms is None else C.addressof(xforms), B, C_, target, gm, gc, gf, None)
 
 
 M_MODE = "bad mode (0 features, 1 types, 2 single)"

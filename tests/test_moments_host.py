@@ -1,7 +1,7 @@
 """Host half of tests/test_hip_moments.py: no GPU, nothing is launched.
 
 * the method surface of moments_batch / moments_posed_batch and the guards they raise before the library is needed;
-* the C ABI entry mvx_moments_batch: declared, exported, bound with the header's prototype, its rejections and their order (the four
+* the C ABI entry mvx_moments_batch: its rejections and their order (the four
   unsupported configurations read the handle and need a real one: tests/test_hip_moments.py);
 * the registers of moments_kernel and moments_finish_kernel read from mvx_moments.o;
 * tests/moments_reference.py itself: exact sums against math.fsum, and a float64 numpy sum inside bound().
@@ -18,11 +18,10 @@ import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
 from tests import moments_reference as MR
+from tests.abi import MVX_ERR_INVALID, P, call, declarations, records
 from tests.fake_voxelizer import fake as _fake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
 BIG = 1 << 31
 POSE = _lib.MVX_XF_POSE_PTR
 
@@ -92,50 +91,19 @@ def test_a_voxelizer_made_with_new_still_has_every_default():
 
 
 # ---- the C ABI entry ---------------------------------------------------------------------------------------------------------
-def test_library_exports_the_entry_and_keeps_its_version():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_moments_batch") and "mvx_moments_batch" in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
+def test_the_header_has_a_float_target_and_double_moments():
+    # the types, not only pointer or not
+    types = {name: text for text, name in declarations()["mvx_moments_batch"][1]}
+    assert types["target"] == "const float *" and types["moments"] == "double *"
 
 
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def test_ctypes_prototype_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint mvx_moments_batch\(([^;]*?)\);", text, re.S)
-    assert m
-    decl = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    args = [a.strip() for a in decl.replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES["mvx_moments_batch"]
-    assert res is C.c_int and got == want and len(want) == 14
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == [
-        "h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "offsets", "xforms", "B", "C", "target", "moments",
-        "stream"]
-    # the types, not only pointer or not: a float target, double moments
-    assert re.search(r"const float \*target", decl) and re.search(r"double \*moments", decl)
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-BAD_POSE = _records([POSE | _lib.MVX_XF_ROTATE])
+BAD_POSE = records([POSE | _lib.MVX_XF_ROTATE])
 
 
 def _moments(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, offsets=(0, 3), xforms=None, B=1, C_=4, target=None, moments=P):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_moments_batch(h, mode, coords, channels, radii, 1.0, rt, None if off is None else off.ctypes.data,
-                               None if xforms is None else C.addressof(xforms), B, C_, target, moments, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_moments_batch, h, mode, coords, channels, radii, 1.0, rt, None if off is None else off.ctypes.data,
+                None if xforms is None else C.addressof(xforms), B, C_, target, moments, None)
 
 
 M_MODE = "bad mode (0 features, 1 types, 2 single)"

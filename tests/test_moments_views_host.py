@@ -1,37 +1,23 @@
 """Moments of many views of one shared cloud without a GPU: the two C ABI entries (mvx_moments_views, mvx_moments_backward_views)
-and every check they make before they touch a device, in order; the ctypes table against the header; the errors the Python layer
+and every check they make before they touch a device, in order; the errors the Python layer
 raises before it needs the library. The handle is looked at last by the rules that need no device: where a rule sits behind the
 handle rule (the records of explicit poses) the handle is P in a call that still fails, so P is never dereferenced. The rules
 behind those read the handle (the stride against C * D^3, the configurations named "moments:", the target's alignment):
 tests/test_hip_moments_views.py checks them with a real one."""
-import ctypes as C
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, P, call, declarations, records
 from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
+from tests.test_reject_order_host import _addr, _check, _off  # (the same scaffolding for tables of two mistakes)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
 BIG = 1 << 31
 POSE = _lib.MVX_XF_POSE_PTR
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-ONE, TWO = _records([0]), _records([0, 0])
-BAD_POSE = _records([POSE | _lib.MVX_XF_ROTATE])
+ONE, TWO = records([0]), records([0, 0])
+BAD_POSE = records([POSE | _lib.MVX_XF_ROTATE])
 
 M_HANDLE = "null handle"
 M_MODE_V = "bad mode"
@@ -60,27 +46,6 @@ M_NEED_INDEX = ("atom_scores, grad_coords and grad_features need an index: their
                 "(mvx_select_views)")
 
 
-def _addr(x):
-    return None if x is None else C.addressof(x)
-
-
-def _off(offsets):
-    if offsets is None:
-        return None, None
-    a = np.asarray(offsets, np.int64)
-    return a, a.ctypes.data
-
-
-def _done(rc):
-    return rc, (_lib.load().mvx_last_error() or b"").decode()
-
-
-def _check(fn, rows):
-    for kw, want in rows:
-        rc, msg = fn(**kw)
-        assert rc == MVX_ERR_INVALID and msg == want, (kw, rc, msg, want)
-
-
 def _views_chain(own_first_kw):
     """The rules every views entry shares, in order (device arrays only: no memory kind to get wrong). own_first_kw: what breaks
     the entry's first own rule."""
@@ -102,15 +67,15 @@ def _views_chain(own_first_kw):
 def _mviews(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, N=3, C_=4, xforms=ONE, B=1, index=None, offsets=None, target=P,
             stride=0, moments=P):
     keep, off = _off(offsets)
-    return _done(_lib.load().mvx_moments_views(h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, index, off, target,
-                                               stride, moments, None))
+    return call(_lib.load().mvx_moments_views, h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, index, off, target,
+                stride, moments, None)
 
 
 def _bviews(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, N=3, C_=4, xforms=ONE, B=1, index=P, offsets=(0, 2), target=P,
             stride=0, gm=P, gc=P, gf=P):
     keep, off = _off(offsets)
-    return _done(_lib.load().mvx_moments_backward_views(h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, index, off,
-                                                        target, stride, gm, gc, gf, None))
+    return call(_lib.load().mvx_moments_backward_views, h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, index, off,
+                target, stride, gm, gc, gf, None)
 
 
 def test_moments_views_reports_the_earlier_of_two_mistakes():
@@ -171,43 +136,11 @@ def test_moments_backward_views_gets_as_far_as_the_handle_with_good_arguments():
         assert rc == MVX_ERR_INVALID and msg == M_HANDLE, (kw, rc, msg)
 
 
-def test_library_exports_the_entries_and_keeps_its_version():
-    lib = _lib.load()
-    for name in ("mvx_moments_views", "mvx_moments_backward_views", "mvx_moments_batch", "mvx_moments_backward_batch"):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-_HEAD = ["h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "N", "C", "xforms", "B", "index", "offsets_host",
-         "target", "target_view_stride"]
-
-
-@pytest.mark.parametrize("name, names", [
-    ("mvx_moments_views", _HEAD + ["moments", "stream"]),
-    ("mvx_moments_backward_views", _HEAD + ["grad_moments", "grad_coords_rows", "grad_features_rows", "stream"]),
-])
-def test_ctypes_prototypes_match_the_header(name, names):
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, text, re.S)
-    assert m
-    body = re.sub(r"/\*.*?\*/", " ", m.group(1), flags=re.S)  # (a parameter may carry a comment on its shape)
-    args = [a.strip() for a in body.replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES[name]
-    assert res is C.c_int and got == want
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == names
-
-
 def test_the_batch_entries_keep_their_prototypes():
     """The stride is an argument of the views entries alone: mvx_moments_batch and mvx_moments_backward_batch are as they were."""
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
     for name, count in (("mvx_moments_batch", 14), ("mvx_moments_backward_batch", 16)):
-        m = re.search(r"\bint %s\(([^;]*?)\);" % name, text, re.S)
-        body = re.sub(r"/\*.*?\*/", " ", m.group(1), flags=re.S)
-        assert len(body.split(",")) == count == len(_lib.SIGNATURES[name][1]) and "stride" not in body, name
+        params = declarations()[name][1]
+        assert len(params) == count == len(_lib.SIGNATURES[name][1]) and "stride" not in " ".join(t + n for t, n in params), name
 
 
 # ---- the Python layer ------------------------------------------------------------------------------------------------------

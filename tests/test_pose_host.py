@@ -13,28 +13,17 @@ import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
 from tests import pose_reference as pr
+from tests.abi import MVX_ERR_INVALID, P, call, header_text, last_error, records
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
 
 
 def _pose_grad(handle=None, coords=P, grad_coords=P, offsets=(0, 3), xforms="pose", B=1, grad_pose=P):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
     if isinstance(xforms, str):
-        xforms = _records([_lib.MVX_XF_POSE_PTR] * max(B, 1))
-    rc = lib.mvx_pose_grad_batch(handle, coords, grad_coords, None if off is None else off.ctypes.data,
-                                 None if xforms is None else C.addressof(xforms), B, grad_pose, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+        xforms = records([_lib.MVX_XF_POSE_PTR] * max(B, 1))
+    return call(_lib.load().mvx_pose_grad_batch, handle, coords, grad_coords, None if off is None else off.ctypes.data,
+                None if xforms is None else C.addressof(xforms), B, grad_pose, None)
 
 
 @pytest.mark.parametrize("kw, words", [
@@ -47,11 +36,11 @@ def _pose_grad(handle=None, coords=P, grad_coords=P, offsets=(0, 3), xforms="pos
     (dict(offsets=None), "offsets"),
     (dict(offsets=(1, 3)), "offsets[0]"),
     (dict(offsets=(0, 5, 3), B=2), "non-decreasing"),
-    (dict(xforms=_records([0])), "MVX_XF_POSE_PTR"),
-    (dict(xforms=_records([_lib.MVX_XF_CENTER | _lib.MVX_XF_ROTATE])), "MVX_XF_POSE_PTR"),
-    (dict(xforms=_records([_lib.MVX_XF_POSE_PTR, _lib.MVX_XF_CENTER_PTR]), offsets=(0, 2, 3), B=2), "MVX_XF_POSE_PTR"),
-    (dict(xforms=_records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_CENTER])), "other flag bit"),
-    (dict(xforms=_records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
+    (dict(xforms=records([0])), "MVX_XF_POSE_PTR"),
+    (dict(xforms=records([_lib.MVX_XF_CENTER | _lib.MVX_XF_ROTATE])), "MVX_XF_POSE_PTR"),
+    (dict(xforms=records([_lib.MVX_XF_POSE_PTR, _lib.MVX_XF_CENTER_PTR]), offsets=(0, 2, 3), B=2), "MVX_XF_POSE_PTR"),
+    (dict(xforms=records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_CENTER])), "other flag bit"),
+    (dict(xforms=records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
 ])
 def test_pose_grad_rejects_bad_arguments_before_touching_a_device(kw, words):
     rc, msg = _pose_grad(**kw)
@@ -68,7 +57,7 @@ def test_pose_grad_without_atoms_accepts_null_arrays_up_to_the_handle():
 @pytest.mark.parametrize("entry", ["forward", "views", "backward", "transform"])
 def test_entries_reject_a_pose_record_with_other_flag_bits(entry):
     lib = _lib.load()
-    bad = _records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])
+    bad = records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])
     off = np.array([0, 3], np.int64)
     x = C.addressof(bad)  # (the handle is any non-null pointer: the records are checked before it is used)
     if entry == "forward":
@@ -79,32 +68,12 @@ def test_entries_reject_a_pose_record_with_other_flag_bits(entry):
         rc = lib.mvx_backward_batch(P, 2, P, None, None, 1.0, 0, off.ctypes.data, x, 1, 1, P, P, None, None)
     else:
         rc = lib.mvx_transform_coords(P, P, 3, x, P, 1, 1, None)
-    assert rc == MVX_ERR_INVALID and "other flag bit" in lib.mvx_last_error().decode()
-
-
-def test_library_exports_the_entry_and_keeps_its_version():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_pose_grad_batch") and "mvx_pose_grad_batch" in _lib.SIGNATURES
-    assert lib.mvx_version() == 140 and C.sizeof(_lib.MvxXform) == 80  # (additive: flags and one entry)
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def test_ctypes_prototype_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint mvx_pose_grad_batch\(([^;]*?)\);", text, re.S)
-    assert m
-    want = [C.c_void_p if "*" in a else _CTYPE[a.strip().rsplit(" ", 1)[0].strip()] for a in m.group(1).replace("\n", " ").split(",")]
-    res, args = _lib.SIGNATURES["mvx_pose_grad_batch"]
-    assert res is C.c_int and args == want
+    assert rc == MVX_ERR_INVALID and "other flag bit" in last_error()
 
 
 def test_flag_values_match_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
     for name, value in (("MVX_XF_POSE_PTR", 32), ("MVX_XF_TRANSLATE_ONCE", 64)):
-        assert int(re.search(name + r" = (\d+)", text).group(1)) == value == getattr(_lib, name)
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
+        assert int(re.search(name + r" = (\d+)", header_text()).group(1)) == value == getattr(_lib, name)
 
 
 def test_header_compiles_as_c99_with_the_pose_prototype(tmp_path):

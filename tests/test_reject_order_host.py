@@ -14,25 +14,14 @@ import ctypes as C
 import numpy as np
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, P, call, records
 
-MVX_ERR_INVALID = -1
-P = 16
 BIG = 1 << 31
 POSE = _lib.MVX_XF_POSE_PTR
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-ONE, TWO = _records([0]), _records([0, 0])
-BAD_POSE = _records([POSE | _lib.MVX_XF_ROTATE])  # breaks the pose-record rule
-BAD_POSE2 = _records([POSE, POSE | _lib.MVX_XF_ROTATE])
-GOOD_POSE = _records([POSE])
+ONE, TWO = records([0]), records([0, 0])
+BAD_POSE = records([POSE | _lib.MVX_XF_ROTATE])  # breaks the pose-record rule
+BAD_POSE2 = records([POSE, POSE | _lib.MVX_XF_ROTATE])
+GOOD_POSE = records([POSE])
 
 M_HANDLE = "null handle"
 M_RTYPE = "bad radii_type"
@@ -61,10 +50,6 @@ def _off(offsets):
     return a, a.ctypes.data
 
 
-def _done(rc):
-    return rc, (_lib.load().mvx_last_error() or b"").decode()
-
-
 def _check(fn, rows):
     for kw, want in rows:
         rc, msg = fn(**kw)
@@ -77,8 +62,8 @@ def _fwd(entry="features", h=P, coords=P, channels=P, radii=None, rt=0, offsets=
     lib = _lib.load()
     keep, off = _off(offsets)
     if entry == "single":
-        return _done(lib.mvx_forward_single_batch(h, coords, radii, 1.0, rt, off, _addr(xforms), B, out, ik, ok, None))
-    return _done(lib.mvx_forward_features_batch(h, coords, channels, radii, 1.0, rt, off, _addr(xforms), B, C_, out, ik, ok, None))
+        return call(lib.mvx_forward_single_batch, h, coords, radii, 1.0, rt, off, _addr(xforms), B, out, ik, ok, None)
+    return call(lib.mvx_forward_features_batch, h, coords, channels, radii, 1.0, rt, off, _addr(xforms), B, C_, out, ik, ok, None)
 
 
 M_FWD_BC = "B must be >= 0 and C > 0"
@@ -157,8 +142,8 @@ def _views_chain(own_first_kw, with_in_kind=True):
 
 def _select(h=None, coords=P, channels=P, radii=None, rt=0, mode=0, N=3, C_=4, xforms=ONE, B=1, index=P, cap=8, offsets_out=P,
             ik=1):
-    return _done(_lib.load().mvx_select_views(h, coords, channels, radii, 1.0, rt, mode, N, C_, _addr(xforms), B, index, cap,
-                                              offsets_out, ik, None))
+    return call(_lib.load().mvx_select_views, h, coords, channels, radii, 1.0, rt, mode, N, C_, _addr(xforms), B, index, cap,
+                offsets_out, ik, None)
 
 
 def test_select_views_reports_the_earlier_of_two_mistakes():
@@ -174,7 +159,7 @@ def test_select_views_reports_the_earlier_of_two_mistakes():
 
 
 def _fviews(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, N=3, C_=4, xforms=ONE, B=1, out=P, ik=1, ok=1):
-    return _done(_lib.load().mvx_forward_views(h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, out, ik, ok, None))
+    return call(_lib.load().mvx_forward_views, h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, out, ik, ok, None)
 
 
 def test_forward_views_reports_the_earlier_of_two_mistakes():
@@ -199,8 +184,8 @@ M_STRIDE_V = "field_view_stride must be 0 (one shared field) or C * D^3 (one fie
 def _sviews(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, N=3, C_=4, xforms=ONE, B=1, index=None, offsets=None, field=P,
             stride=0, scores=P, atom_scores=None, gc=None, gf=None):
     keep, off = _off(offsets)
-    return _done(_lib.load().mvx_score_views(h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, index, off, field,
-                                             stride, scores, atom_scores, gc, gf, None))
+    return call(_lib.load().mvx_score_views, h, mode, coords, channels, radii, 1.0, rt, N, C_, _addr(xforms), B, index, off, field,
+                stride, scores, atom_scores, gc, gf, None)
 
 
 def test_score_views_reports_the_earlier_of_two_mistakes():
@@ -242,12 +227,12 @@ def _bwd(entry="plain", h=None, mode=0, coords=P, channels=P, radii=None, rt=0, 
     keep, off = _off(offsets)
     head = (h, mode, coords, channels, radii, 1.0, rt, off, _addr(xforms), B, C_, g)
     if entry == "plain":
-        return _done(lib.mvx_backward_batch(*head, gc, gf, None))
+        return call(lib.mvx_backward_batch, *head, gc, gf, None)
     if entry == "radii":
-        return _done(lib.mvx_backward_radii_batch(*head, gc, gf, gr, None))
+        return call(lib.mvx_backward_radii_batch, *head, gc, gf, gr, None)
     if entry == "density":
-        return _done(lib.mvx_backward_density_batch(*head, gc, gf, gr, gsig, grs, None))
-    return _done(lib.mvx_score_batch(*head, stride, scores, atoms, gc, gf, None))
+        return call(lib.mvx_backward_density_batch, *head, gc, gf, gr, gsig, grs, None)
+    return call(lib.mvx_score_batch, *head, stride, scores, atoms, gc, gf, None)
 
 
 def _backward_chain(entry, ok, middle, first_mid_kw, last_mid_kw, last_mid_msg, chanwise_shadowed, m_grid):
@@ -335,7 +320,7 @@ def test_score_batch_reports_the_earlier_of_two_mistakes():
 # ---- mvx_pose_grad_batch --------------------------------------------------------------------------------------------------
 def _pose(h=None, coords=P, gcoords=P, offsets=(0, 3), xforms=GOOD_POSE, B=1, gp=P):
     keep, off = _off(offsets)
-    return _done(_lib.load().mvx_pose_grad_batch(h, coords, gcoords, off, _addr(xforms), B, gp, None))
+    return call(_lib.load().mvx_pose_grad_batch, h, coords, gcoords, off, _addr(xforms), B, gp, None)
 
 
 def test_pose_grad_batch_reports_the_earlier_of_two_mistakes():
@@ -352,7 +337,7 @@ def test_pose_grad_batch_reports_the_earlier_of_two_mistakes():
         (dict(B=2, xforms=BAD_POSE2, offsets=(0, 3, 2), coords=None), M_OFFDEC),
         (dict(coords=None, xforms=ONE), m_coords),
         (dict(gcoords=None, xforms=ONE), m_coords),
-        (dict(B=2, offsets=(0, 2, 3), xforms=_records([0, POSE | _lib.MVX_XF_ROTATE])), m_every),
+        (dict(B=2, offsets=(0, 2, 3), xforms=records([0, POSE | _lib.MVX_XF_ROTATE])), m_every),
         (dict(xforms=BAD_POSE), M_POSE),  # (and a null handle)
         (dict(), M_HANDLE),
     ])
@@ -361,7 +346,7 @@ def test_pose_grad_batch_reports_the_earlier_of_two_mistakes():
 # ---- mvx_views_reduce -------------------------------------------------------------------------------------------------------
 def _reduce(h=None, index=P, offsets=(0, 2, 3), B=2, N=4, rows=P, width=3, row_type=1, out=P):
     keep, off = _off(offsets)
-    return _done(_lib.load().mvx_views_reduce(h, index, off, B, N, rows, width, row_type, out, None))
+    return call(_lib.load().mvx_views_reduce, h, index, off, B, N, rows, width, row_type, out, None)
 
 
 def test_views_reduce_reports_the_earlier_of_two_mistakes():
@@ -387,7 +372,7 @@ def test_views_reduce_reports_the_earlier_of_two_mistakes():
 
 # ---- mvx_transform_coords: one rule for every null argument, then the record -----------------------------------------------
 def _xform(h=P, coords=P, N=3, xform=ONE, out=P):
-    return _done(_lib.load().mvx_transform_coords(h, coords, N, _addr(xform), out, 1, 1, None))
+    return call(_lib.load().mvx_transform_coords, h, coords, N, _addr(xform), out, 1, 1, None)
 
 
 def test_transform_coords_reports_the_earlier_of_two_mistakes():

@@ -1,5 +1,5 @@
 """Second-order scores without a GPU: the C ABI entry (mvx_score_hessian_batch) and the checks it makes before it touches a
-device, in mvx_score_batch's order; the ctypes table against the header; what the Python layer refuses before it needs the
+device, in mvx_score_batch's order; what the Python layer refuses before it needs the
 library; the registers of both kernels read from mvx_hess.o; the float64 reference (tests/hessian_reference.py) against central
 differences of tests/grad_reference.py's coordinate gradient; its twist helper against differences of a smooth function under
 exp twists; and apply_twist on CPU tensors. (Rules judged against the handle's dimension - a stride that is neither 0 nor
@@ -15,29 +15,18 @@ import pytest
 from molvoxel_amd.voxelizer.hip import _lib
 from tests import grad_reference as gr
 from tests import hessian_reference as hr
+from tests.abi import MVX_ERR_INVALID, P, call, records
 from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
 
 
 def _hess(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, offsets=(0, 3), xforms=None, B=1, C_=4, field=P,
           stride=0, pivots=None, scores=P, atom_grad=None, atom_hess=None, twist_grad=P, twist_hess=P):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_score_hessian_batch(handle, mode, coords, channels, radii, 1.0, radii_type, None if off is None else off.ctypes.data,
-                                     None if xforms is None else C.addressof(xforms), B, C_, field, stride, pivots, scores, atom_grad,
-                                     atom_hess, twist_grad, twist_hess, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_score_hessian_batch, handle, mode, coords, channels, radii, 1.0, radii_type,
+                None if off is None else off.ctypes.data, None if xforms is None else C.addressof(xforms), B, C_, field, stride, pivots,
+                scores, atom_grad, atom_hess, twist_grad, twist_hess, None)
 
 
 # a call that breaks both of the entry's own rules: every rule of mvx_score_batch must still win
@@ -58,8 +47,8 @@ SCORE_RULES = [
     (dict(offsets=(1, 3)), "offsets[0]"),
     (dict(B=2, offsets=(0, 3, 2)), "non-decreasing"),
     (dict(), "null handle"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
     (dict(handle=P, offsets=(0, 1 << 31)), "too many atoms"),
     (dict(handle=P, coords=None), "coords / field"),
     (dict(handle=P, field=None), "coords / field"),
@@ -102,30 +91,9 @@ def test_its_own_rules_fire_before_a_device_is_touched():
     assert rc == MVX_ERR_INVALID and "null handle" in msg, (rc, msg)
 
 
-def test_library_exports_the_entry_and_keeps_its_version():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_score_hessian_batch") and "mvx_score_hessian_batch" in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def test_ctypes_prototype_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint mvx_score_hessian_batch\(([^;]*?)\);", text, re.S)
-    assert m
-    args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES["mvx_score_hessian_batch"]
-    assert res is C.c_int and got == want and len(want) == 20
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == [
-        "h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "offsets", "xforms", "B", "C", "field",
-        "field_mol_stride", "pivots", "scores", "atom_grad", "atom_hess", "twist_grad", "twist_hess", "stream"]
+def test_the_entry_begins_like_score_batch():
     # the arguments up to the field's stride are mvx_score_batch's
-    assert got[:13] == _lib.SIGNATURES["mvx_score_batch"][1][:13]
+    assert _lib.SIGNATURES["mvx_score_hessian_batch"][1][:13] == _lib.SIGNATURES["mvx_score_batch"][1][:13]
 
 
 # ---- the Python layer ------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """Scores against a field grid without a GPU: the C ABI entry (mvx_score_batch) and the checks it makes before it touches a
-device, the ctypes table against the header, the errors the Python layer raises before it needs the library, and the score
+device, the errors the Python layer raises before it needs the library, and the score
 kernels' registers read from mvx_score.o. (A stride that is neither 0 nor C * D^3 and a channel of 4 GiB are judged against the
 handle's dimension: tests/test_hip_score.py checks them with a real handle.)"""
 import ctypes as C
@@ -11,29 +11,18 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, P, call, records
 from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
 
 
 def _score(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, offsets=(0, 3), xforms=None, B=1, C_=4, field=P,
            stride=0, scores=P, atom_scores=None, grad_coords=None, grad_features=None):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_score_batch(handle, mode, coords, channels, radii, 1.0, radii_type, None if off is None else off.ctypes.data,
-                             None if xforms is None else C.addressof(xforms), B, C_, field, stride, scores, atom_scores,
-                             grad_coords, grad_features, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_score_batch, handle, mode, coords, channels, radii, 1.0, radii_type,
+                None if off is None else off.ctypes.data, None if xforms is None else C.addressof(xforms), B, C_, field, stride, scores,
+                atom_scores, grad_coords, grad_features, None)
 
 
 @pytest.mark.parametrize("kw, words", [
@@ -51,8 +40,8 @@ def _score(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, 
     (dict(offsets=(1, 3)), "offsets[0]"),
     (dict(B=2, offsets=(0, 3, 2)), "non-decreasing"),
     (dict(), "null handle"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
     (dict(handle=P, offsets=(0, 1 << 31)), "too many atoms"),
     (dict(handle=P, coords=None), "coords / field"),
     (dict(handle=P, channels=None), "channels"),
@@ -80,30 +69,6 @@ def test_all_optional_outputs_may_be_null():
 def test_no_molecules_need_no_scores():
     rc, msg = _score(B=0, offsets=(0,), scores=None, field=None, coords=None)
     assert rc == MVX_ERR_INVALID and "null handle" in msg, (rc, msg)
-
-
-def test_library_exports_the_entry_and_keeps_its_version():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_score_batch") and "mvx_score_batch" in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def test_ctypes_prototype_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint mvx_score_batch\(([^;]*?)\);", text, re.S)
-    assert m
-    args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES["mvx_score_batch"]
-    assert res is C.c_int and got == want and len(want) == 18
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == [
-        "h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "offsets", "xforms", "B", "C", "field",
-        "field_mol_stride", "scores", "atom_scores", "grad_coords", "grad_features", "stream"]
 
 
 # ---- the Python layer ------------------------------------------------------------------------------------------------------

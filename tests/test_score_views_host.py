@@ -1,5 +1,5 @@
 """Scores of many views of one shared cloud without a GPU: the two C ABI entries (mvx_score_views, mvx_views_reduce) and the
-checks they make before they touch a device, the ctypes table against the header, the errors the Python layer raises before it
+checks they make before they touch a device, the errors the Python layer raises before it
 needs the library, the numpy restatement of the reduction checked against a dense scatter, and view_reduce_kernel's registers
 read from mvx_views_reduce.o. (A stride that is neither 0 nor C * D^3 is judged against the handle's dimension:
 tests/test_hip_score_views.py checks it with a real handle.)"""
@@ -12,33 +12,20 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, P, call, header_text, records
 from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 from tests import views_reduce_reference as vr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-ONE = _records([0])
+ONE = records([0])
 
 
 def _score(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, N=3, C_=4, xforms=ONE, B=1, index=None,
            offsets=None, field=P, stride=0, scores=P, atom_scores=None, grad_coords=None, grad_features=None):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_score_views(handle, mode, coords, channels, radii, 1.0, radii_type, N, C_,
-                             None if xforms is None else C.addressof(xforms), B, index, None if off is None else off.ctypes.data,
-                             field, stride, scores, atom_scores, grad_coords, grad_features, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_score_views, handle, mode, coords, channels, radii, 1.0, radii_type, N, C_,
+                None if xforms is None else C.addressof(xforms), B, index, None if off is None else off.ctypes.data,
+                field, stride, scores, atom_scores, grad_coords, grad_features, None)
 
 
 @pytest.mark.parametrize("kw, words", [
@@ -58,8 +45,8 @@ def _score(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, 
     (dict(mode=1, channels=None), "types must not be null"),
     (dict(N=1 << 31), "too many atoms"),
     (dict(), "null handle"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
-    (dict(handle=P, xforms=_records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR | _lib.MVX_XF_ROTATE])), "other flag bit"),
+    (dict(handle=P, xforms=records([_lib.MVX_XF_POSE_PTR], ptr=None)), "center_ptr"),
     # what mvx_score_batch rejects for field, stride and scores (and its rule for grad_features)
     (dict(scores=None), "scores must not be null"),
     (dict(field=None), "field must not be null"),
@@ -76,7 +63,7 @@ def _score(handle=None, mode=0, coords=P, channels=P, radii=None, radii_type=0, 
     # an index without offsets, and bad offsets
     (dict(index=P), "offsets_host must not be null"),
     (dict(index=P, offsets=(1, 3)), "offsets[0]"),
-    (dict(index=P, B=2, xforms=_records([0, 0]), offsets=(0, 3, 2)), "non-decreasing"),
+    (dict(index=P, B=2, xforms=records([0, 0]), offsets=(0, 3, 2)), "non-decreasing"),
     (dict(index=P, offsets=(0, 1 << 31)), "2^31"),
 ])
 def test_score_views_rejects_bad_arguments_before_touching_a_device(kw, words):
@@ -94,10 +81,8 @@ def test_score_views_gets_as_far_as_the_handle_with_good_arguments():
 
 
 def _reduce(handle=None, index=P, offsets=(0, 2, 3), B=2, N=4, rows=P, width=3, row_type=1, out=P):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_views_reduce(handle, index, None if off is None else off.ctypes.data, B, N, rows, width, row_type, out, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_views_reduce, handle, index, None if off is None else off.ctypes.data, B, N, rows, width, row_type, out, None)
 
 
 @pytest.mark.parametrize("kw, words", [
@@ -129,35 +114,9 @@ def test_views_reduce_needs_no_arrays_where_sizes_are_zero():
         assert rc == MVX_ERR_INVALID and "null handle" in msg, (kw, rc, msg)
 
 
-def test_library_exports_the_entries_and_keeps_its_version():
-    lib = _lib.load()
-    for name in ("mvx_score_views", "mvx_views_reduce"):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
+def test_the_row_types_are_the_headers():
     assert (_lib.MVX_ROW_FLOAT, _lib.MVX_ROW_DOUBLE) == (0, 1)
-    assert re.search(r"enum mvx_row_type \{ MVX_ROW_FLOAT = 0, MVX_ROW_DOUBLE = 1 \}", text)
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-@pytest.mark.parametrize("name, names", [
-    ("mvx_score_views", ["h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "N", "C", "xforms", "B", "index",
-                         "offsets_host", "field", "field_view_stride", "scores", "atom_scores", "grad_coords", "grad_features",
-                         "stream"]),
-    ("mvx_views_reduce", ["h", "index", "offsets_host", "B", "N", "rows", "width", "row_type", "out", "stream"]),
-])
-def test_ctypes_prototypes_match_the_header(name, names):
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint %s\(([^;]*?)\);" % name, text, re.S)
-    assert m
-    args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES[name]
-    assert res is C.c_int and got == want
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == names
+    assert re.search(r"enum mvx_row_type \{ MVX_ROW_FLOAT = 0, MVX_ROW_DOUBLE = 1 \}", header_text())
 
 
 # ---- the Python layer ------------------------------------------------------------------------------------------------------

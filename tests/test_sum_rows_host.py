@@ -2,7 +2,7 @@
 
 * every row of tests/sum_rows.py reaches what its `reaches` column says, by numpy and the pre-pass's own culls alone;
 * the method surface of forward_sum / forward_posed_sum and the field_grad constructor option;
-* the C ABI entry mvx_forward_sum_batch: declared, exported, bound, its rejections and their order (the rules that read the handle -
+* the C ABI entry mvx_forward_sum_batch: its rejections and their order (the rules that read the handle -
   the four unsupported configurations and the alignment of `out` - need a real handle: tests/test_hip_sum.py);
 * the NotImplementedErrors the Python layer raises before it needs the library;
 * the registers of voxelize_sum_kernel read from mvx_sum.o.
@@ -16,12 +16,11 @@ import numpy as np
 import pytest
 
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, P, call, records
 from tests.fake_voxelizer import fake as _fake  # (a voxelizer without a handle)
 from tests import sum_rows as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
 BIG = 1 << 31
 POSE = _lib.MVX_XF_POSE_PTR
 
@@ -200,49 +199,14 @@ def test_a_field_that_requires_grad_needs_the_option_and_a_shared_field():
 
 
 # ---- the C ABI entry ---------------------------------------------------------------------------------------------------------
-def test_library_exports_the_entry_and_keeps_its_version():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_forward_sum_batch") and "mvx_forward_sum_batch" in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def test_ctypes_prototype_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint mvx_forward_sum_batch\(([^;]*?)\);", text, re.S)
-    assert m
-    decl = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    args = [a.strip() for a in decl.replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES["mvx_forward_sum_batch"]
-    assert res is C.c_int and got == want and len(want) == 15
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == [
-        "h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "offsets", "xforms", "B", "C", "atom_weights",
-        "out", "accumulate", "stream"]
-
-
-def _records(flags, ptr=P):
-    xfs = (_lib.MvxXform * len(flags))()
-    for b, f in enumerate(flags):
-        xfs[b].flags = f
-        xfs[b].center_ptr = ptr
-    return xfs
-
-
-BAD_POSE = _records([POSE | _lib.MVX_XF_ROTATE])
+BAD_POSE = records([POSE | _lib.MVX_XF_ROTATE])
 
 
 def _sum(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, offsets=(0, 3), xforms=None, B=1, C_=4, weights=None, out=P,
          accumulate=0):
-    lib = _lib.load()
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    rc = lib.mvx_forward_sum_batch(h, mode, coords, channels, radii, 1.0, rt, None if off is None else off.ctypes.data,
-                                   None if xforms is None else C.addressof(xforms), B, C_, weights, out, accumulate, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_forward_sum_batch, h, mode, coords, channels, radii, 1.0, rt, None if off is None else off.ctypes.data,
+                None if xforms is None else C.addressof(xforms), B, C_, weights, out, accumulate, None)
 
 
 M_MODE = "bad mode (0 features, 1 types, 2 single)"

@@ -10,10 +10,8 @@ Finite differences on the 12-atom tree (4 torsions, one branch, nesting depth 3)
 conformer against one another, worst difference over the bar (N_b + 128)(T_b + 1) 2^-53 bound: 0.0080 (base), 0.00065 (long),
 0.00037 (deep); the shortcut 0.0010, 0.00019, 0.000095 of the same bar (deep: 8.7e-13 absolute at max |g| = 146). The numpy Adam
 loop (learning rate 0.01, 20 steps): 8 starts, score 591.1 ... 616.5 -> 634.8 ... 641.3."""
-import ctypes as C
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -22,11 +20,10 @@ from molvoxel_amd.voxelizer.hip import _lib
 from tests import flex_reference as fr
 from tests import flex_rows as X
 from tests import torsion_grad_reference as tg
+from tests.abi import MVX_ERR_INVALID, P, call
 from tests.fake_voxelizer import fake as _fake
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing behind it is read before the checks are through
 
 
 # ---- the reference against finite differences -------------------------------------------------------------------------------
@@ -139,39 +136,17 @@ def test_an_atom_without_a_row_may_have_nan_coordinates():
 
 
 # ---- the entry against the header -----------------------------------------------------------------------------------------------
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-NAMES = ["h", "conformer", "offsets", "B", "T", "axes", "moves", "angles", "grad_out", "grad_coords", "grad_angles", "stream"]
-
-
-def test_the_ctypes_prototype_matches_the_header():
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint mvx_apply_torsions_backward\(([^;]*?)\);", text, re.S)
-    assert m
-    args = [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    res, got = _lib.SIGNATURES["mvx_apply_torsions_backward"]
-    assert res is C.c_int and got == want
-    assert [a.rsplit(" ", 1)[1].lstrip("*") for a in args] == NAMES
+def test_the_entry_begins_like_apply_torsions():
     # the forward's arguments, with the conformer in place of coords, in front of the three gradients
-    fwd = _lib.SIGNATURES["mvx_apply_torsions"][1]
+    got, fwd = _lib.SIGNATURES["mvx_apply_torsions_backward"][1], _lib.SIGNATURES["mvx_apply_torsions"][1]
     assert got[:8] == fwd[:8] and got[-1] == fwd[-1]
 
 
-def test_the_library_exports_the_entry_and_keeps_its_version():
-    lib = _lib.load()
-    assert hasattr(lib, "mvx_apply_torsions_backward")
-    assert lib.mvx_version() == 140
-
-
 # ---- rejections ------------------------------------------------------------------------------------------------------------------
-def _msg(rc):
-    return rc, (_lib.load().mvx_last_error() or b"").decode()
-
-
 def _back(handle=None, conformer=P, offsets=(0, 3), B=1, T=2, axes=P, moves=P, angles=P, grad_out=P, grad_coords=P, grad_angles=P):
     off = None if offsets is None else np.asarray(offsets, np.int64)
-    return _msg(_lib.load().mvx_apply_torsions_backward(handle, conformer, None if off is None else off.ctypes.data, B, T, axes, moves,
-                                                        angles, grad_out, grad_coords, grad_angles, None))
+    return call(_lib.load().mvx_apply_torsions_backward, handle, conformer, None if off is None else off.ctypes.data, B, T, axes, moves,
+                angles, grad_out, grad_coords, grad_angles, None)
 
 
 @pytest.mark.parametrize("kw, words", [
@@ -195,7 +170,7 @@ def test_the_rules_fire_in_the_order_of_apply_torsions_with_its_words():
 
     def forward(offsets=(0, 3), B=1, T=2, coords=P, axes=P):
         off = None if offsets is None else np.asarray(offsets, np.int64)
-        return _msg(fwd(None, coords, None if off is None else off.ctypes.data, B, T, axes, P, P, P, None))
+        return call(fwd, None, coords, None if off is None else off.ctypes.data, B, T, axes, P, P, P, None)
 
     # the rules the two entries share: the same words
     for kw in (dict(B=-1), dict(T=40), dict(offsets=None), dict(offsets=(1, 3)), dict(B=2, offsets=(0, 3, 2)), dict(offsets=(0, 1 << 31)),

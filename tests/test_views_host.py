@@ -1,9 +1,7 @@
 """Views of a shared cloud without a GPU: the C ABI entries (mvx_select_views, mvx_forward_views), the checks they make before
-they touch a device, the ctypes prototypes against the header, the numpy restatement of the selection on the cull face, the
+they touch a device, the numpy restatement of the selection on the cull face, the
 public signatures, and the new kernels' register use read from mvx_views.o."""
-import ctypes as C
 import os
-import re
 import shutil
 import subprocess
 
@@ -13,24 +11,21 @@ import pytest
 from molvoxel_amd.voxelizer.hip import _lib
 from tests import views_reference as vr
 from tests import views_rows as rows
+from tests.abi import MVX_ERR_INVALID, P, call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = 16  # any non-null pointer: nothing is dereferenced before the checks are through
 
 
 def _select(handle=None, coords=P, types=None, radii=None, rs=1.0, radii_type=0, mode=0, N=3, C_=4, xforms=P, B=1, index=None,
             cap=0, offsets=P, in_kind=1):
-    lib = _lib.load()
-    rc = lib.mvx_select_views(handle, coords, types, radii, rs, radii_type, mode, N, C_, xforms, B, index, cap, offsets, in_kind, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_select_views, handle, coords, types, radii, rs, radii_type, mode, N, C_, xforms, B, index, cap, offsets,
+                in_kind, None)
 
 
 def _forward(handle=None, mode=0, coords=P, channels=P, radii=None, rs=1.0, radii_type=0, N=3, C_=4, xforms=P, B=1, out=P,
              in_kind=1, out_kind=1):
-    lib = _lib.load()
-    rc = lib.mvx_forward_views(handle, mode, coords, channels, radii, rs, radii_type, N, C_, xforms, B, out, in_kind, out_kind, None)
-    return rc, (lib.mvx_last_error() or b"").decode()
+    return call(_lib.load().mvx_forward_views, handle, mode, coords, channels, radii, rs, radii_type, N, C_, xforms, B, out, in_kind,
+                out_kind, None)
 
 
 SHARED = [
@@ -75,37 +70,6 @@ def test_forward_views_rejects_bad_arguments_before_touching_a_device(kw, words)
     rc, msg = _forward(**kw)
     assert rc == MVX_ERR_INVALID, (rc, msg)
     assert words in msg, msg
-
-
-def test_library_exports_the_views_entries():
-    lib = _lib.load()
-    for name in ("mvx_select_views", "mvx_forward_views"):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.mvx_version() == 140  # (additive entries)
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def _header_args(name):
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint " + name + r"\(([^;]*?)\);", text, re.S)
-    assert m, name
-    out = []
-    for arg in m.group(1).replace("\n", " ").split(","):
-        arg = arg.strip()
-        if "*" in arg:
-            out.append(C.c_void_p)
-        else:
-            out.append(_CTYPE[arg.rsplit(" ", 1)[0].strip()])
-    return out
-
-
-@pytest.mark.parametrize("name", ["mvx_select_views", "mvx_forward_views"])
-def test_ctypes_prototypes_match_the_header(name):
-    res, args = _lib.SIGNATURES[name]
-    assert res is C.c_int
-    assert args == _header_args(name)
 
 
 def test_header_compiles_as_c99_with_the_views_prototypes(tmp_path):

@@ -1,14 +1,12 @@
 """Host half of tests/test_hip_views_sum.py and tests/test_hip_sum_parts.py: no GPU, nothing is launched.
 
 * the method surface of forward_views_sum / forward_posed_views_sum and of set_sum_parts / sum_parts;
-* the C ABI entries mvx_forward_views_sum and mvx_set_sum_parts: declared, exported, bound, prototypes as the header has them;
 * the ORDER of mvx_forward_views_sum's rejections, in the manner of tests/test_reject_order_host.py: every call breaks two rules
   that follow each other and must report the earlier one, texts compared in full (the rules that read the handle - the four
   unsupported configurations and the alignment of `out` - need a real handle: tests/test_hip_views_sum.py);
 * the guards the Python layer raises, with forward_sum's messages, before it needs the library;
 * the registers of voxelize_sum_parts_kernel read from mvx_sum.o.
 """
-import ctypes as C
 import inspect
 import os
 import re
@@ -19,10 +17,9 @@ import pytest
 import tests.test_reject_order_host as RO  # (the rules every views entry shares, and their texts)
 import tests.test_sum_rows_host as SH  # (_fake: a voxelizer without a handle)
 from molvoxel_amd.voxelizer.hip import _lib
+from tests.abi import MVX_ERR_INVALID, P, call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MVX_ERR_INVALID = -1
-P = RO.P
 
 
 # ---- the method surface ------------------------------------------------------------------------------------------------------
@@ -52,41 +49,9 @@ def test_voxelizer_has_the_sum_parts_setting():
 
 
 # ---- the C ABI entries -------------------------------------------------------------------------------------------------------
-def test_library_exports_the_entries_and_keeps_its_version():
-    lib = _lib.load()
-    for name in ("mvx_forward_views_sum", "mvx_set_sum_parts"):
-        assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert lib.mvx_version() == 140
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    assert int(re.search(r"#define MVX_VERSION (\d+)", text).group(1)) == 140
-
-
-_CTYPE = {"mvx_handle *": C.c_void_p, "int32_t": C.c_int32, "int64_t": C.c_int64, "double": C.c_double}
-
-
-def _header_args(name):
-    text = open(os.path.join(ROOT, "include", "mvx.h")).read()
-    m = re.search(r"\bint " + name + r"\(([^;]*?)\);", text, re.S)
-    assert m, name
-    decl = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    args = [a.strip() for a in decl.replace("\n", " ").split(",")]
-    want = [C.c_void_p if "*" in a else _CTYPE[a.rsplit(" ", 1)[0].strip()] for a in args]
-    return want, [a.rsplit(" ", 1)[1].lstrip("*") for a in args]
-
-
-def test_ctypes_prototypes_match_the_header():
-    want, names = _header_args("mvx_forward_views_sum")
-    res, got = _lib.SIGNATURES["mvx_forward_views_sum"]
-    assert res is C.c_int and got == want and len(want) == 15
-    assert names == ["h", "mode", "coords", "channels", "radii", "radius_scalar", "radii_type", "N", "C", "xforms", "B",
-                     "view_weights", "out", "accumulate", "stream"]
-    want, names = _header_args("mvx_set_sum_parts")
-    assert _lib.SIGNATURES["mvx_set_sum_parts"] == (C.c_int, want) and names == ["h", "parts"]
-
-
 def _vsum(h=None, mode=0, coords=P, channels=P, radii=None, rt=0, N=3, C_=4, xforms=RO.ONE, B=1, weights=None, out=P, accumulate=0):
-    return RO._done(_lib.load().mvx_forward_views_sum(h, mode, coords, channels, radii, 1.0, rt, N, C_, RO._addr(xforms), B, weights,
-                                                      out, accumulate, None))
+    return call(_lib.load().mvx_forward_views_sum, h, mode, coords, channels, radii, 1.0, rt, N, C_, RO._addr(xforms), B, weights,
+                out, accumulate, None)
 
 
 M_ACC = "accumulate must be 0 or 1"
@@ -121,8 +86,7 @@ def test_set_sum_parts_refuses_what_is_out_of_range_and_a_null_handle():
     lib = _lib.load()
     for h, parts, want in ((P, 0, "sum parts must be 1 ... 64"), (P, 65, "sum parts must be 1 ... 64"), (P, -3, "sum parts must be 1 ... 64"),
                            (None, 4, "null handle"), (None, 0, "null handle")):
-        rc = lib.mvx_set_sum_parts(h, parts)
-        assert rc == MVX_ERR_INVALID and (lib.mvx_last_error() or b"").decode() == want, (h, parts)
+        assert call(lib.mvx_set_sum_parts, h, parts) == (MVX_ERR_INVALID, want), (h, parts)
 
 
 # ---- the Python guards -------------------------------------------------------------------------------------------------------
